@@ -11,8 +11,9 @@ A "step" is one mini-batch through the whole hot path: exact best-matching-unit 
 batch + the in-order neighbourhood update.  Batch sizes are the engine's own schedule (somhip.h SOMHIP_BATCH_AUTO,
 somhip_som_auto_batch: a rule in (units, radius(t), alpha(t)) -- at this workload 32768 vectors up to iteration
 8 486 912, 8192 after; `--batch B` fixes one size).  The timed region is EXACTLY --steps such batches of the real
-10 M-iteration schedule, evenly spread over it (step k = the batch that holds iteration k * length / steps), so the
-radius sweeps its whole range inside the timed region; `value_timed_steps` = vectors of those batches / time.  `value`
+10 M-iteration schedule, evenly spread over it (step k = the batch that holds iteration k * length / steps, or the next
+free batch where an earlier step holds that one; with more steps than the schedule's 444 batches, each batch in turn, some
+more than once), so the radius sweeps its whole range inside the timed region; `value_timed_steps` = vectors of those batches / time.  `value`
 is the rate of the COMPLETE 10 M-vector run made after the timed region (`full_run`): the timed steps start from the
 initial map, the complete run is what they are samples of.
 
@@ -38,6 +39,7 @@ keys gives the global winners, each rank updates its own rows.  Total work is fi
 Prints ONE JSON line on rank 0.
 """
 import argparse
+import bisect
 import ctypes as C
 import json
 import os
@@ -60,7 +62,8 @@ GOLDEN = os.path.join(ROOT, "profiles", "r03_c4_online_golden.json")
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=128)
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed steps, exactly (default: 128; --config c2: as many of its 1024-iteration steps as its schedule holds, <= 128)")
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--config", default="c4", choices=["c4", "c2", "c3", "c5"],
                     help="c4 = BASELINE configs[3] (SOM 256x256x512, the headline); c2 = configs[1] (SOM 32x32x128, 100k vectors: the "
@@ -97,7 +100,56 @@ def parse():
                     help="N = 1: iterations of the real schedule the reference-exact online engine runs live (its rate); 0 = skip")
     ap.add_argument("--online-full", action="store_true",
                     help="N = 1: run the online engine over the WHOLE schedule live (minutes) instead of using the recorded qerror")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: after the timed steps, write what the last of them computed as DIR/<name>.npy (float32 / float64, "
+                         "<= 64 MB in all; a fixed, seeded sample of the codebook's rows where it is larger)")
+    a = ap.parse_args()
+    if a.steps is not None and a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and a.gpus != 1:
+        ap.error("--dump-outputs is a one-GPU option (the codebook of an N > 1 run is spread over the ranks)")
+    return a
+
+
+DUMP_BYTES = 64 << 20          # --dump-outputs: everything written, at most
+DUMP_ROWS_BYTES = 32 << 20     # ... of which the codebook rows
+
+
+def sample_rows(n, dim):
+    """Indices (ascending) of the codebook rows --dump-outputs writes: all of them if they fit DUMP_ROWS_BYTES, else a fixed
+    seeded sample -- the same rows on every run and every build."""
+    k = max(1, DUMP_ROWS_BYTES // (4 * dim))
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.RandomState(0).choice(n, k, replace=False))
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: each array as DIR/<name>.npy, float32 kept as float32, anything else (indices) as float64."""
+    conv = {}
+    for name, v in arrays.items():
+        v = np.asarray(v)
+        conv[name] = np.ascontiguousarray(v, dtype=np.float32 if v.dtype == np.float32 else np.float64)
+    total = sum(v.nbytes for v in conv.values())
+    if total > DUMP_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_BYTES))
+    os.makedirs(dirname, exist_ok=True)
+    for name, v in conv.items():
+        np.save(os.path.join(dirname, name + ".npy"), v)
+
+
+def timed_batches(wanted, nb):
+    """Indices into the schedule's nb batches of exactly len(wanted) timed steps.  Step k takes batch wanted[k] (ascending)
+    unless an earlier step has taken it -- then the next free one, leaving room for the steps after it -- so the steps are
+    distinct batches, in schedule order, as close to the wanted spread as fits.  More steps than batches: every batch in
+    order, each once or more, consecutively."""
+    K = len(wanted)
+    if K > nb:
+        return [(k * nb) // K for k in range(K)]
+    out = []
+    for k, w in enumerate(wanted):
+        out.append(min(max(w, out[-1] + 1 if out else 0), nb - (K - k)))
+    return out
 
 
 def setup_dist(a):
@@ -197,7 +249,7 @@ def bench_som(a):
     from som_lvq_pak_amd._lib import SomParams
 
     rank, world, local, dev = setup_dist(a)
-    B, K, W, L = a.batch, a.steps, a.warmup, a.length
+    B, K, W, L = a.batch, a.steps if a.steps is not None else 128, a.warmup, a.length
     xdim, ydim, d = a.xdim, a.ydim, a.dim
     N = xdim * ydim
     radius = a.radius if a.radius is not None else max(xdim, ydim) / 2.0
@@ -207,9 +259,7 @@ def bench_som(a):
         nbatches = L // B
         if nbatches < 1:
             raise SystemExit("--length must be at least one batch")
-        stride = max(1, nbatches // max(K, 1)) * B        # timed step k starts at iteration k * stride
-        if (K - 1) * stride + B > L:
-            raise SystemExit("--steps %d x --batch %d does not fit a schedule of %d iterations" % (K, B, L))
+        stride = max(1, nbatches // max(K, 1)) * B        # timed step k starts at iteration k * stride (while they fit)
 
     # ---- the stream, resident in HBM before any timing; identical on every rank (counter-based generator) ----
     eng = E.Engine(local)
@@ -241,15 +291,16 @@ def bench_som(a):
         raise SystemExit("the engine's schedule for this map / run length is batch 1 (the rule does not vouch for mini-batches "
                          "here: somhip_som_auto_batch); use --batch B, or --config c2 for the online engine's bench line")
     if auto_b:
-        steps_at = []
-        for k in range(K):
-            st, ln = auto_at((k * L) // max(K, 1))
-            if not steps_at or st != steps_at[-1][0]:
-                steps_at.append((st, ln))
-        if len(steps_at) != K:
-            raise SystemExit("--steps %d: more steps than batches in a schedule of %d iterations" % (K, L))
+        batches, it = [], 0                                  # every batch of the schedule, in order
+        while it < L:
+            batches.append(auto_at(it))
+            it = batches[-1][0] + batches[-1][1]
+        starts = [st for st, _ in batches]
+        wanted = [bisect.bisect_right(starts, (k * L) // K) - 1 for k in range(K)]     # the batch holding iteration k * L / K
     else:
-        steps_at = [(k * stride, B) for k in range(K)]
+        batches = [(j * B, B) for j in range(nbatches)]
+        wanted = [k * stride // B for k in range(K)]
+    steps_at = [batches[j] for j in timed_batches(wanted, len(batches))]
     vectors_timed = sum(ln for _, ln in steps_at)
 
     def barrier():
@@ -302,11 +353,16 @@ def bench_som(a):
     barrier()
     t0 = time.perf_counter()
     for st, ln in steps_at:
-        ssom.step(st, st, ln)
+        keys = ssom.step(st, st, ln)
     barrier()
     t1 = time.perf_counter()
     eng.timing(False)
     elapsed = max_over_ranks(t1 - t0)
+    if a.dump_outputs:                                   # the last timed step's winners and the codebook it left, before anything reuses them
+        wdist, widx = sharded.unpack_keys(keys.cpu().numpy())
+        rows = sample_rows(N, d)
+        dump_outputs(a.dump_outputs, {"winner_index": widx, "winner_dist": wdist, "codebook_rows": rows,
+                                      "codebook": cb.download()[rows]})
     table = eng.timing_table()
     stats_after = eng.scan_stats()
     table_all = table
@@ -605,8 +661,10 @@ def bench_c2(a):
         raise SystemExit("bench.py needs an MI355X: no GPU visible and there is no CPU path")
     xdim, ydim, d, L, seed, kcent, init_seed, alpha, radius = 32, 32, 128, 100000, 1234, 16, 7, 0.05, 10.0
     K, W, STEP = a.steps, a.warmup, 1024
-    if K * STEP > L:                                      # (the default --steps is sized for configs[3]: as many steps as the schedule holds)
-        K = L // STEP
+    if K is None:                                         # (the default --steps is sized for configs[3]: as many steps as the schedule holds)
+        K = min(128, L // STEP)
+    elif K * STEP > L:
+        raise SystemExit("--steps %d: more steps of %d iterations than the %d-iteration schedule holds" % (K, STEP, L))
     eng = E.Engine(0)
     lib = eng.lib
     ds = E.Dataset(eng, generate=(seed, kcent, d, 0, L))
@@ -629,6 +687,8 @@ def bench_c2(a):
         run(k * STEP, STEP)
     eng.sync(); torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if a.dump_outputs:                                    # the map the timed steps trained
+        dump_outputs(a.dump_outputs, {"codebook": cb.download()})
     # per-launch duration of the step kernel: the same steps again with HIP events (no graph while events are on)
     cb.upload(init)
     eng.timing(True); eng.timing_reset()
@@ -739,9 +799,11 @@ def bench_lvq(a):
 
     cfg = LVQ_CONFIGS[a.config]
     rank, world, local, dev = setup_dist(a)
-    K, W, STEP = a.steps, a.warmup, 1024
+    K, W, STEP = a.steps if a.steps is not None else 128, a.warmup, 1024
     kind, N, d, L, nwin = cfg["kind"], cfg["codes"], cfg["dim"], cfg["length"], cfg["window"]
     knn = 2 if kind in (3, 4) else 1
+    if K * STEP > L:
+        raise SystemExit("--steps %d: more steps of %d iterations than the %d-iteration schedule holds" % (K, STEP, L))
     eng = E.Engine(local)
     ds = E.Dataset(eng, generate=(cfg["seed"], cfg["classes"], d, 0, nwin))
     lab = ds.centres.astype(np.int32) + 1                         # class = mixture id (1-based: 0 is LABEL_EMPTY, labels.h)
@@ -806,6 +868,12 @@ def bench_lvq(a):
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev if a.backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if a.dump_outputs:                   # the codebook the timed steps trained (+ OLVQ1's per-code rates)
+        rows = sample_rows(len(codes), d)
+        outs = {"codebook_rows": rows, "codebook": cb.download()[rows]}
+        if kind == 2:
+            outs["olvq1_rates"] = state["talpha"]
+        dump_outputs(a.dump_outputs, outs)
     table = eng.timing_table()
     st1 = eng.lvq_stats()
     table_all = table

@@ -299,13 +299,17 @@ class RefHarness(_Base):
         secs = C.c_double(0)
         tal = None
         with tempfile.TemporaryDirectory(prefix="orclra") as tmp:
-            assert "." not in tmp
-            lin = os.path.join(tmp, "in.cod").encode()
-            lout = os.path.join(tmp, "out.cod").encode()
-            rc = self._lvq(kind, _ptr(codes, c_float_p), _ptr(clabels, c_int_p), n, d,
-                           _ptr(data, c_float_p), _ptr(dlabels, c_int_p), data.shape[0], length,
-                           alpha, alpha_type, winlen, epsilon, lin, lout,
-                           _ptr(ti, c_long_p), _ptr(td, c_float_p), C.byref(secs))
+            # the reference names the rates file after what precedes the FIRST "." of the path (datafile.c:1037),
+            # so a "." anywhere in the temporary directory's path would send it elsewhere: names relative to it
+            cwd = os.getcwd()
+            os.chdir(tmp)
+            try:
+                rc = self._lvq(kind, _ptr(codes, c_float_p), _ptr(clabels, c_int_p), n, d,
+                               _ptr(data, c_float_p), _ptr(dlabels, c_int_p), data.shape[0], length,
+                               alpha, alpha_type, winlen, epsilon, b"in.cod", b"out.cod",
+                               _ptr(ti, c_long_p), _ptr(td, c_float_p), C.byref(secs))
+            finally:
+                os.chdir(cwd)
             assert rc == 0
             lra = os.path.join(tmp, "out.lra")
             if kind == 2 and os.path.exists(lra):

@@ -127,11 +127,14 @@ def test_vfind_matches_reference_cli(tools, tmp_path):
     """vfind.c:244-306: three trials (seeds 3, 2, 1) of randinit -> two som_training runs -> qerror
     (or -qetype 1); per-trial errors, the winning seed and the saved map must equal the reference's"""
     answers = ["3", "{data}", "{data}", "{out}", "hexa", "bubble", "6", "5", "800", "0.05", "5", "2000", "0.02", "2"]
+    # vfind reads each answer as one line of at most 99 characters (fgets into 100 bytes, as the reference's
+    # vfind.c:69-120): file names relative to the test's own directory, however long its absolute path
+    shutil.copy(os.path.join(DATA, "ex.dat"), tmp_path / "ex.dat")
     for tag, ex in EXPECTED["som"]["vfind"].items():
         out = tmp_path / (tag + ".cod")
-        ans = "\n".join(a.format(data=os.path.join(DATA, "ex.dat"), out=out) for a in answers) + "\n"
+        ans = "\n".join(a.format(data="ex.dat", out=out.name) for a in answers) + "\n"
         p = subprocess.run([os.path.join(BIN, "vfind")] + ex["args"], input=ans, stdout=subprocess.PIPE,
-                           stderr=subprocess.PIPE, text=True)
+                           stderr=subprocess.PIPE, text=True, cwd=tmp_path)
         assert p.returncode == 0, p.stderr
         trials = [ln for ln in p.stderr.splitlines() if ": " in ln and ln.strip()[:1].isdigit()]
         assert trials == ex["trials_stderr"], tag
@@ -147,9 +150,10 @@ def test_vfind_gpus_replicas_equal_the_sequential_run(tools, tmp_path):
     answers = ["3", "{data}", "{data}", "{out}", "hexa", "bubble", "6", "5", "800", "0.05", "5", "2000", "0.02", "2"]
     ex = EXPECTED["som"]["vfind"]["q0"]
     out = tmp_path / "g2.cod"
-    ans = "\n".join(a.format(data=os.path.join(DATA, "ex.dat"), out=out) for a in answers) + "\n"
+    shutil.copy(os.path.join(DATA, "ex.dat"), tmp_path / "ex.dat")       # short answers (test_vfind_matches_reference_cli)
+    ans = "\n".join(a.format(data="ex.dat", out=out.name) for a in answers) + "\n"
     p = subprocess.run([os.path.join(BIN, "vfind"), "-gpus", "2"] + ex["args"], input=ans, stdout=subprocess.PIPE,
-                       stderr=subprocess.PIPE, text=True)
+                       stderr=subprocess.PIPE, text=True, cwd=tmp_path)
     assert p.returncode == 0, p.stderr
     trials = [ln for ln in p.stderr.splitlines() if ": " in ln and ln.strip()[:1].isdigit()]
     assert trials == ex["trials_stderr"]
