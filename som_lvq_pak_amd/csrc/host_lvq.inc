@@ -125,7 +125,7 @@ static int lvq_walk_batch(somhip_codebook *cb, somhip_dataset *ds, const LvqBatc
     // codebooks, scan_keys_topk) needs no pass over the whole codebook -- only if they were current for the codebook
     // this batch started from (a scan that took the direct path never made them so: re-splitting a few rows of stale
     // tiles must not validate them)
-    if (cb->prep_valid && cb->d_chi && cb->d_cn && e->scan_mode == SOMHIP_SCAN_MFMA_BF16 && !getenv("SOMHIP_ALWAYS_PREP")) {
+    if (cb->prep_valid && cb->d_chi && cb->d_cn && e->scan_mode == SOMHIP_SCAN_MFMA_BF16) {
       hipLaunchKernelGGL(k_prep_rows_bf16, dim3((unsigned)((bound + 3) / 4)), dim3(256), 0, e->stream, cb->v,
                          (cb->v.d4 + 1) / 2, (const int32_t *)b.mod_rows, (int)bound, (const int32_t *)b.mod_count, cb->d_cn,
                          cb->d_chi, cb->d_clo);
@@ -188,7 +188,7 @@ static int lvq_walk_batch_nowait(somhip_codebook *cb, somhip_dataset *ds, const 
   }
   HIPCHK(hipGetLastError());
   // the bf16 copies / norms of the rows this batch corrected (see lvq_walk_batch); at most two rows per sample
-  if (cb->prep_valid && cb->d_chi && cb->d_cn && e->scan_mode == SOMHIP_SCAN_MFMA_BF16 && !getenv("SOMHIP_ALWAYS_PREP")) {
+  if (cb->prep_valid && cb->d_chi && cb->d_cn && e->scan_mode == SOMHIP_SCAN_MFMA_BF16) {
     hipLaunchKernelGGL(k_prep_rows_bf16, dim3((unsigned)((2 * c + 3) / 4)), dim3(256), 0, e->stream, cb->v,
                        (cb->v.d4 + 1) / 2, (const int32_t *)b.mod_rows, 2 * c, (const int32_t *)b.mod_count, cb->d_cn,
                        cb->d_chi, cb->d_clo, (const int32_t *)&d_ctl->poison);

@@ -42,11 +42,11 @@ static void prefilter_err3(const somhip_engine *e, int d, double *prod, double *
   const double gam = k / (1.0 - k);
   if (e->scan_mode == SOMHIP_SCAN_MFMA_BF16) {
     const double k3 = 3.0 * (d + 2) * u;
-    *prod = (4.04 * (k3 / (1.0 - k3)) + 3.1 / 65536.0 + 2.0 * u) * e->tau_scale;
-    *sq = (2.0 * gam + 2.0 * u) * e->tau_scale;
+    *prod = 4.04 * (k3 / (1.0 - k3)) + 3.1 / 65536.0 + 2.0 * u;
+    *sq = 2.0 * gam + 2.0 * u;
   } else {
     *prod = 0.0;
-    *sq = 2.0 * gam * e->tau_scale;
+    *sq = 2.0 * gam;
   }
 }
 
@@ -57,12 +57,12 @@ static void prefilter_err3(const somhip_engine *e, int d, double *prod, double *
 //   fp32 accumulation of d exact products, any order:   <= 2 gamma 1.01 ab
 //   the norm term cn, the reference's direct-form sum, the final subtraction:  <= (2 gamma + u) (a + b)^2
 // so |s~1 - s| <= prod * ab + sq * (a + b)^2 with the two coefficients below (s~ carries -2 <c,x>: the factor 2).
-static void prefilter_err_l1(const somhip_engine *e, int d, double *prod, double *sq) {
+static void prefilter_err_l1(int d, double *prod, double *sq) {
   const double u = 5.9604644775390625e-08;
   const double k = (d + 2) * u;
   const double gam = k / (1.0 - k);
-  *prod = 2.0 * ((1.0 / 256.0) * (1.0 + 1.0 / 256.0) + 2.02 * gam) * e->tau_scale;
-  *sq = (2.0 * gam + u) * e->tau_scale;
+  *prod = 2.0 * ((1.0 / 256.0) * (1.0 + 1.0 / 256.0) + 2.02 * gam);
+  *sq = 2.0 * gam + u;
 }
 
 // MFMA pre-filter + exact re-rank (kernels.hpp K2/K2b/K2s/K2p/K2r)
@@ -95,11 +95,17 @@ static int scan_keys_mfma(somhip_codebook *cb, somhip_dataset *ds, int64_t first
   const size_t xt_bytes = bf16 ? 2 * sizeof(uint4) * (size_t)nsb * d8 * 32 : sizeof(float4) * (size_t)nsb * cb->v.d4 * SCAN_S;
   CHK(engine_scratch(e, 1, xt_bytes, &xt));
   uint4 *xhi = (uint4 *)xt, *xlo = xhi + (size_t)nsb * d8 * 32;
-  // the two-level form's level 2 gathers single samples: it gets a sample-major copy of the same pieces
-  const bool two_level_early = bf16 && (!prefilter_only || kth > 1) && (d8 % 4) == 0 && nsb >= 8 && bpad <= 65535 && !getenv("SOMHIP_ONE_LEVEL") &&
-                               !getenv("SOMHIP_NO_LDS_DMA") && !getenv("SOMHIP_DIST_NARROW");
+  // two-level form (K2c): bf16 mode, whole k-steps pairs, sample indices that fit 16 bits; behind it either the
+  // re-rank of the nearest row (window above the smallest level-1 group minimum) or a top-K search (kth = K: window
+  // above the K-th smallest -- a row of the true top K has level-1 value <= S_K + d1 <= (K-th smallest level-1 row
+  // value) + 2 d1 <= (K-th smallest level-1 group minimum) + 2 d1; the groups left out keep their level-1 minimum,
+  // which lies above S_K + d1 >= S_K + 3 d3: beyond the K-th smallest three-product minimum plus tau, so
+  // k_topk_select never takes them and its K-th smallest is formed from exact three-product values).  A bare
+  // pre-filter (somhip_debug_prefilter) wants every group's three-product minimum: one level.
+  const bool two_level = bf16 && (!prefilter_only || kth > 1) && (d8 % 4) == 0 && nsb >= 8 && bpad <= 65535;
+  // level 2 gathers single samples: it gets a sample-major copy of the same pieces
   uint4 *xrow = nullptr;
-  if (two_level_early && !getenv("SOMHIP_L2_TILE_GATHER")) {
+  if (two_level) {
     void *pr;
     CHK(engine_scratch(e, 31, xt_bytes, &pr));
     xrow = (uint4 *)pr;
@@ -116,7 +122,7 @@ static int scan_keys_mfma(somhip_codebook *cb, somhip_dataset *ds, int64_t first
   HIPCHK(hipGetLastError());
   // the bf16 tiles and norms of an unchanged codebook are reused (read-only scans chunk by chunk; the LVQ engine
   // re-splits exactly the rows it corrected); every writer of the rows clears the flag
-  const bool prep_was_current = bf16 && cb->prep_valid && !getenv("SOMHIP_ALWAYS_PREP");
+  const bool prep_was_current = bf16 && cb->prep_valid;
   if (!bf16 && xphase <= 1) HIPCHK(hipMemsetAsync(cb->d_cnmax, 0, sizeof(unsigned int), e->stream));   // (the bf16 pack kernel zeroes it)
   // scratch of the re-rank, preset by k_sample_tau
   const uint32_t ncols = (uint32_t)(bpad / 32);
@@ -128,14 +134,6 @@ static int scan_keys_mfma(somhip_codebook *cb, somhip_dataset *ds, int64_t first
   // signed MIN all-reduce needs) -- saves somhip_batch_winner_keys a pass over the keys
   RerankInit rinit = {prefilter_only ? nullptr : d_keys, dgmin, d_paircount, bpad, (int)ncols,
                       nonneg_keys ? 0x7FFFFFFFFFFFFFFFull : KEY_NONE, nullptr, nullptr, 0};
-  // two-level form (K2c): bf16 mode, whole k-steps pairs, sample indices that fit 16 bits; behind it either the
-  // re-rank of the nearest row (window above the smallest level-1 group minimum) or a top-K search (kth = K: window
-  // above the K-th smallest -- a row of the true top K has level-1 value <= S_K + d1 <= (K-th smallest level-1 row
-  // value) + 2 d1 <= (K-th smallest level-1 group minimum) + 2 d1; the groups left out keep their level-1 minimum,
-  // which lies above S_K + d1 >= S_K + 3 d3: beyond the K-th smallest three-product minimum plus tau, so
-  // k_topk_select never takes them and its K-th smallest is formed from exact three-product values).  A bare
-  // pre-filter (somhip_debug_prefilter) wants every group's three-product minimum: one level.
-  const bool two_level = two_level_early;
   // the per-sample minimum behind level 2 comes out of the level-2 kernel itself (an atomicMin per (group, sample) it
   // covers) instead of a pass over the whole wmin matrix (k_group_min: 21 us per 32768 vectors and a launch)
   const bool fused_gmin = two_level && !prefilter_only && !getenv("SOMHIP_NO_FUSED_GMIN");
@@ -161,7 +159,7 @@ static int scan_keys_mfma(somhip_codebook *cb, somhip_dataset *ds, int64_t first
   }
   double l1_prod = 0.0, l1_sq = 0.0, err_prod = 0.0, err_sq = 0.0;
   prefilter_err3(e, ds->d, &err_prod, &err_sq);
-  if (two_level) prefilter_err_l1(e, ds->d, &l1_prod, &l1_sq);
+  if (two_level) prefilter_err_l1(ds->d, &l1_prod, &l1_sq);
   if (xphase <= 1) {
     LaunchTimer t(e, KID_NORMS);
     if (prep_was_current) {
@@ -171,7 +169,7 @@ static int scan_keys_mfma(somhip_codebook *cb, somhip_dataset *ds, int64_t first
       // with the tiles a row-major copy of the rows for the exact re-rank of single rows (k_rerank_pairs), where that
       // kernel will run behind this pre-filter on a long enough run (a shard of a map included)
       // (the copy costs ~55 us at 65536 x 512 and saves 36 us of re-rank per 4096 vectors: from 8192 vectors per run on)
-      const bool want_rm = !prefilter_only && kth == 1 && (cb->v.d & 3) == 0 && cb->v.ngroups >= 64 && count >= 8192 && !getenv("SOMHIP_NO_ROWMAJOR");
+      const bool want_rm = !prefilter_only && kth == 1 && (cb->v.d & 3) == 0 && cb->v.ngroups >= 64 && count >= 8192;
       if (want_rm && !cb->d_rowmajor) HIPCHK(hipMalloc((void **)&cb->d_rowmajor, sizeof(float) * (size_t)cb->v.ngroups * WAVE * cb->v.d));
       hipLaunchKernelGGL(k_prep_codes_bf16, dim3((unsigned)cb->v.ngroups), dim3(d8 >= 16 ? 1024 : d8 >= 4 ? 256 : 64), 0,
                          e->stream, cb->v, d8, cb->d_cn, cb->d_cnmax, cb->d_chi, cb->d_clo, want_rm ? cb->d_rowmajor : (float *)nullptr);
@@ -194,14 +192,12 @@ static int scan_keys_mfma(somhip_codebook *cb, somhip_dataset *ds, int64_t first
     // (a shard of a map has few row groups but the same long batches: the persistent kernel needs tiles, not rows -- at
     // least one 256 x 256 tile per CU)
     const int64_t l1_tiles = ((nsb + 7) / 8) * ((cb->v.ngroups + 3) / 4);
-    const bool l1_ring = (cb->v.ngroups >= 512 || (l1_tiles >= 256 && !getenv("SOMHIP_L1_RING_BIG_ONLY"))) && (d8 % 8) == 0 &&
-                         !getenv("SOMHIP_L1_NARROW") && !getenv("SOMHIP_L1_32X32") && !getenv("SOMHIP_L1_NORING");
-    const bool l1_ring_gmin = l1_ring && kth != LVQ_K0 && !getenv("SOMHIP_L1_RING_NOGMIN");
+    const bool l1_ring = (cb->v.ngroups >= 512 || l1_tiles >= 256) && (d8 % 8) == 0;
+    const bool l1_ring_gmin = l1_ring && kth != LVQ_K0;
     if (xphase <= 1) {
       LaunchTimer t(e, KID_DIST_MFMA_BF16);
-      if ((cb->v.ngroups >= 512 || l1_ring) && !getenv("SOMHIP_L1_NARROW")) {        // 256 x 256 tile: a third less L2 -> LDS traffic per MFMA
+      if (cb->v.ngroups >= 512 || l1_ring) {        // 256 x 256 tile: a third less L2 -> LDS traffic per MFMA
         dim3 gridw((unsigned)((nsb + 7) / 8), (unsigned)((cb->v.ngroups + 3) / 4));
-        const bool l1_32 = getenv("SOMHIP_L1_32X32") != nullptr;      // the 32x32x16 form of the same kernel
         if (l1_ring) {
           // persistent form over an LDS ring (kernels/prefilter_l1_ring.hpp): one workgroup per CU, a multiple of 8 of them
           if (!e->l1r_attr_set) {
@@ -214,16 +210,12 @@ static int scan_keys_mfma(somhip_codebook *cb, somhip_dataset *ds, int64_t first
             e->n_cus = v > 0 ? v : 256;
           }
           int nwg = e->n_cus >= 8 ? e->n_cus / 8 * 8 : e->n_cus;
-          if (const char *sg = getenv("SOMHIP_L1_RING_WGS")) { const int v = atoi(sg); if (v > 0) nwg = v; }
           const int64_t ntiles = (int64_t)gridw.x * gridw.y;
           if (ntiles < nwg) nwg = (int)ntiles;
           hipLaunchKernelGGL(k_dist_mfma_bf16_l1r, dim3((unsigned)nwg), dim3(512), L1R_LDS_BYTES, e->stream, cb->v, d8, (const uint4 *)cb->d_chi,
                              (const uint4 *)xhi, (const float *)cb->d_cn, bpad, (float *)dwmin, l1_ring_gmin ? dgmin1 : (uint32_t *)nullptr,
                              (int)gridw.x, (int)gridw.y);
-        } else if (l1_32)
-          hipLaunchKernelGGL((k_dist_mfma_bf16_l1w<4>), gridw, dim3(512), 0, e->stream, cb->v, d8, (const uint4 *)cb->d_chi,
-                             (const uint4 *)xhi, (const float *)cb->d_cn, bpad, (float *)dwmin);
-        else
+        } else
           hipLaunchKernelGGL((k_dist_mfma_bf16_l1w16<4>), dim3(gridw.x * gridw.y), dim3(512), 0, e->stream, cb->v, d8, (const uint4 *)cb->d_chi,
                              (const uint4 *)xhi, (const float *)cb->d_cn, bpad, (float *)dwmin, (int)gridw.x, (int)gridw.y);
       } else {
@@ -263,18 +255,14 @@ static int scan_keys_mfma(somhip_codebook *cb, somhip_dataset *ds, int64_t first
           e->l2_lds_attr_set = true;
         }
         hipLaunchKernelGGL(k_dist_l2_lds, dim3((unsigned)cb->v.ngroups, 4), dim3(64 * L2_WAVES), a_bytes, e->stream, cb->v, d8, (const uint4 *)cb->d_chi,
+                           (const uint4 *)cb->d_clo, (const uint4 *)xrow, (const float *)cb->d_cn,
+                           (const float *)dtau, bpad, (const uint32_t *)dl2cnt, (const uint16_t *)dl2list, (float *)dwmin,
+                           (uint64_t *)dwmask, e->d_stats + 8 + 128 + 8, l2_gmin);
+      } else
+        hipLaunchKernelGGL(k_dist_l2, dim3((unsigned)cb->v.ngroups, 8), dim3(256), 0, e->stream, cb->v, d8, (const uint4 *)cb->d_chi,
                            (const uint4 *)cb->d_clo, (const uint4 *)xhi, (const uint4 *)xlo, (const float *)cb->d_cn,
                            (const float *)dtau, bpad, (const uint32_t *)dl2cnt, (const uint16_t *)dl2list, (float *)dwmin,
                            (uint64_t *)dwmask, e->d_stats + 8 + 128 + 8, (const uint4 *)xrow, l2_gmin);
-      } else {
-      const int l2_depth = getenv("SOMHIP_L2_DEPTH") ? atoi(getenv("SOMHIP_L2_DEPTH")) : 2;      // (configs[4] shape: 62 us per launch against 65 at 4)
-#define GOL2(DD) hipLaunchKernelGGL((k_dist_l2<DD>), dim3((unsigned)cb->v.ngroups, 8), dim3(256), 0, e->stream, cb->v, d8, (const uint4 *)cb->d_chi, \
-                         (const uint4 *)cb->d_clo, (const uint4 *)xhi, (const uint4 *)xlo, (const float *)cb->d_cn,                                 \
-                         (const float *)dtau, bpad, (const uint32_t *)dl2cnt, (const uint16_t *)dl2list, (float *)dwmin,                            \
-                         (uint64_t *)dwmask, e->d_stats + 8 + 128 + 8, (const uint4 *)xrow, l2_gmin)
-      if (l2_depth == 8) GOL2(8); else if (l2_depth == 6) GOL2(6); else if (l2_depth == 2) GOL2(2); else GOL2(4);
-#undef GOL2
-      }
     }
     HIPCHK(hipGetLastError());
     if (xphase == 2) {                                   // bound = smallest three-product value among the kept groups + delta3
@@ -287,19 +275,13 @@ static int scan_keys_mfma(somhip_codebook *cb, somhip_dataset *ds, int64_t first
   } else {
     LaunchTimer t(e, bf16 ? KID_DIST_MFMA_BF16 : KID_DIST_MFMA);
     dim3 grid((unsigned)((nsb + 3) / 4), (unsigned)((cb->v.ngroups + 1) / 2));
-#ifndef SOMHIP_DMA_KB
-#define SOMHIP_DMA_KB 4
-#endif
-#ifndef SOMHIP_DMA_MINB
-#define SOMHIP_DMA_MINB 2
-#endif
-    if (bf16 && (d8 % 2) == 0 && nsb >= 8 && !getenv("SOMHIP_NO_LDS_DMA") && !getenv("SOMHIP_DIST_NARROW")) {
+    if (bf16 && (d8 % 2) == 0 && nsb >= 8) {
       dim3 gridw((unsigned)((nsb + 7) / 8), (unsigned)((cb->v.ngroups + 1) / 2));
       hipLaunchKernelGGL((k_dist_mfma_bf16_wide<2>), gridw, dim3(256), 0, e->stream, cb->v, d8,
                          (const uint4 *)cb->d_chi, (const uint4 *)cb->d_clo, (const uint4 *)xhi, (const uint4 *)xlo,
                          (const float *)cb->d_cn, (const float *)dtau, count, bpad, (float *)dwmin, (uint64_t *)dwmask);
-    } else if (bf16 && (d8 % SOMHIP_DMA_KB) == 0 && !getenv("SOMHIP_NO_LDS_DMA"))
-      hipLaunchKernelGGL((k_dist_mfma_bf16_dma<SOMHIP_DMA_KB, SOMHIP_DMA_MINB>), grid, dim3(256), 0, e->stream, cb->v, d8,
+    } else if (bf16 && (d8 % 4) == 0)
+      hipLaunchKernelGGL((k_dist_mfma_bf16_dma<4, 2>), grid, dim3(256), 0, e->stream, cb->v, d8,
                          (const uint4 *)cb->d_chi, (const uint4 *)cb->d_clo, (const uint4 *)xhi, (const uint4 *)xlo,
                          (const float *)cb->d_cn, (const float *)dtau, count, bpad, (float *)dwmin, (uint64_t *)dwmask);
     else if (bf16)
@@ -316,8 +298,7 @@ static int scan_keys_mfma(somhip_codebook *cb, somhip_dataset *ds, int64_t first
   // k_rerank for flagged samples (too many candidates / list full)
   // pair list: one segment per 32-sample column
   if (ncols > (uint32_t)PAIR_MAX_COLS) return fail("winner search: more than %d samples in one run", PAIR_MAX_COLS * 32);
-  const uint32_t cap_col_env = getenv("SOMHIP_PAIR_CAP") ? (uint32_t)atoi(getenv("SOMHIP_PAIR_CAP")) : 0u;
-  const uint32_t cap_col = cap_col_env >= 256 ? cap_col_env : 16384;   // 512 per sample on average; a full segment -> K2r
+  const uint32_t cap_col = 16384;   // 512 per sample on average; a full segment -> K2r
   const uint32_t cap = (uint32_t)std::min<int64_t>((int64_t)ncols * cap_col, 0x7FFFFFF0);
   void *dpairs;
   CHK(engine_scratch(e, 11, sizeof(uint2) * (size_t)ncols * cap_col + 16, &dpairs));
@@ -338,10 +319,10 @@ static int scan_keys_mfma(somhip_codebook *cb, somhip_dataset *ds, int64_t first
   }
   {
     LaunchTimer t(e, KID_RERANK_PAIRS);
-    hipLaunchKernelGGL(k_rerank_pairs, dim3(getenv("SOMHIP_PAIR_GRID") ? atoi(getenv("SOMHIP_PAIR_GRID")) : 4096), dim3(256), 0, e->stream, cb->v, ds->d_rows,
+    hipLaunchKernelGGL(k_rerank_pairs, dim3(4096), dim3(256), 0, e->stream, cb->v, ds->d_rows,
                        ds->n, first, cap, cap_col, (int)ncols, (const uint2 *)dpairs, (const uint32_t *)dcolcount,
                        (const uint32_t *)d_paircount, d_keys, e->d_stats,
-                       bf16 && cb->prep_valid && cb->rowmajor_valid && !getenv("SOMHIP_NO_ROWMAJOR") ? (const float *)cb->d_rowmajor : (const float *)nullptr);
+                       bf16 && cb->prep_valid && cb->rowmajor_valid ? (const float *)cb->d_rowmajor : (const float *)nullptr);
   }
   {
     LaunchTimer t(e, KID_RERANK);
@@ -401,8 +382,8 @@ static int scan_keys_topk(somhip_codebook *cb, somhip_dataset *ds, int64_t first
                           uint64_t *d_keys /*[count][K]*/, int tie_knn = 1) {
   somhip_engine *e = cb->e;
   // big codebooks: bf16 pre-filter + exact re-rank of the surviving row groups (kernels.hpp K2k)
-  const bool force_mfma = getenv("SOMHIP_TOPK_MFMA") != nullptr, no_mfma = getenv("SOMHIP_TOPK_DIRECT") != nullptr;
-  if (!no_mfma && e->scan_mode == SOMHIP_SCAN_MFMA_BF16 && !ds->d_mask && count >= MFMA_MIN_SAMPLES &&
+  const bool force_mfma = getenv("SOMHIP_TOPK_MFMA") != nullptr;
+  if (e->scan_mode == SOMHIP_SCAN_MFMA_BF16 && !ds->d_mask && count >= MFMA_MIN_SAMPLES &&
       cb->v.n >= (force_mfma ? 64 : 4096) && count <= (int64_t)PAIR_MAX_COLS * 32) {
     const int64_t nsb = (count + SCAN_S - 1) / SCAN_S;
     float *dw = nullptr, *dt = nullptr;
@@ -531,8 +512,7 @@ static bool shard_exchange_ok(const somhip_codebook *cb, const somhip_dataset *d
     return false;
   const int64_t nsb = (count + SCAN_S - 1) / SCAN_S, bpad = nsb * SCAN_S;
   const int d8 = (cb->v.d4 + 1) / 2;
-  return (d8 % 4) == 0 && nsb >= 8 && bpad <= 65535 && !getenv("SOMHIP_ONE_LEVEL") && !getenv("SOMHIP_NO_LDS_DMA") &&
-         !getenv("SOMHIP_DIST_NARROW") && !getenv("SOMHIP_NO_SHARD_EXCHANGE");
+  return (d8 % 4) == 0 && nsb >= 8 && bpad <= 65535 && !getenv("SOMHIP_NO_SHARD_EXCHANGE");
 }
 extern "C" int somhip_shard_exchange_available(somhip_codebook *cb, somhip_dataset *ds, int64_t count) try {
   if (check_pair(cb, ds, "somhip_shard_exchange_available")) return 0;

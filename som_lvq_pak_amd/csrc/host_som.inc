@@ -59,7 +59,6 @@ static int som_scalars(const somhip_codebook *cb, const somhip_dataset *ds, cons
 }
 
 constexpr int ONLINE_U = 8;    // chunks (KiB) per register buffer; two buffers per wave
-constexpr int ONLINE_U_DEFAULT = 8;
 template <bool G, bool M>
 static void launch_online(somhip_engine *e, const somhip_codebook *cb, const somhip_dataset *ds,
                           const int64_t *prev_row, const int64_t *cur_row, int has_prev, int has_cur,
@@ -68,12 +67,9 @@ static void launch_online(somhip_engine *e, const somhip_codebook *cb, const som
   LaunchTimer t(e, KID_SOM_ONLINE_STEP);
   // chunks (KiB) per register buffer: a wave is alone on its SIMD here (one wave per 64 rows: 1024 waves on 1024 SIMDs at
   // 65536 rows), so registers are free and what bounds the kernel is how many bytes it keeps in flight
-  const int u = e->online_u;
-#define GO_ONLINE(UU) hipLaunchKernelGGL((k_som_online_step<G, M, UU>), dim3((unsigned)((cb->v.ngroups + 3) / 4)), dim3(256), 0, \
-                     e->stream, cb->v, ds->d_rows, (const uint8_t *)ds->d_mask, prev_row, cur_row,                            \
-                     has_prev, has_cur, prev_slot, cur_slot, prev_sc, cur_sc)
-  if (!M && u == 16) GO_ONLINE(16); else if (!M && u == 24) GO_ONLINE(24); else if (!M && u == 4) GO_ONLINE(4); else if (!M && u == 2) GO_ONLINE(2); else GO_ONLINE(ONLINE_U);
-#undef GO_ONLINE
+  hipLaunchKernelGGL((k_som_online_step<G, M, ONLINE_U>), dim3((unsigned)((cb->v.ngroups + 3) / 4)), dim3(256), 0,
+                     e->stream, cb->v, ds->d_rows, (const uint8_t *)ds->d_mask, prev_row, cur_row,
+                     has_prev, has_cur, prev_slot, cur_slot, prev_sc, cur_sc);
 }
 static void launch_online_any(somhip_engine *e, const somhip_codebook *cb, const somhip_dataset *ds, bool G, bool M,
                               const int64_t *prev_row, const int64_t *cur_row, int has_prev, int has_cur,
@@ -115,15 +111,7 @@ static int som_train_online(somhip_codebook *cb, somhip_dataset *ds, const somhi
   // graph of one full chunk, cached per engine while its arguments stay the same
   OnlineGraphKey key{cb->v.tiles, cb->v.n, cb->v.d, cb->v.patch_w, cb->v.row_offset, cb->v.xdim, cb->v.topol,
                      ds->d_rows, ds->d_mask, slot, sc, rowidx, G, M};
-  {
-    const char *su = getenv("SOMHIP_ONLINE_U");
-    const int u = su ? atoi(su) : ONLINE_U_DEFAULT;
-    if (u != e->online_u) {                              // (the captured graph holds the launches of one form)
-      e->online_u = u;
-      if (e->online_graph_exec) { (void)hipGraphExecDestroy(e->online_graph_exec); e->online_graph_exec = nullptr; }
-    }
-  }
-  const bool want_graph = !e->timing && p->count >= CH && !getenv("SOMHIP_NO_GRAPH");
+  const bool want_graph = !e->timing && p->count >= CH;
   if (want_graph && !(e->online_graph_exec && e->online_graph_key == key)) {
     if (e->online_graph_exec) { (void)hipGraphExecDestroy(e->online_graph_exec); e->online_graph_exec = nullptr; }
     hipGraph_t graph = nullptr;
@@ -202,13 +190,11 @@ static int som_update_run(somhip_codebook *cb, somhip_dataset *ds, int64_t data_
   // (profiles/r01_shard_rehearsal.txt): 4 with the pipelined tile walk beats 8 even on the whole 65536-row map.
   int QW = 4;
   while (QW > 2 && (int64_t)cb->v.ngroups * ((cb->v.d4 + QW - 1) / QW) < 8192) QW >>= 1;
-  if (const char *s = getenv("SOMHIP_UPD_QW")) { const int v = atoi(s); if (v == 2 || v == 4 || v == 8) QW = v; }
-  bool pipe = true;
-  if (const char *s = getenv("SOMHIP_UPD_PIPE")) pipe = atoi(s) != 0;
+  if (const char *s = getenv("SOMHIP_UPD_QW")) { const int v = atoi(s); if (v == 2 || v == 4) QW = v; }
   // bubble, no masks, whole chunks, enough waves at 4 chunks each: the scalar-operand kernel K4s (a shard so small
   // that QW fell to 2 is better off with K4's pipelined tile walk); K4b then writes row offsets into the entries
   // data sets below 4 GiB: byte offsets in the entries and register-offset scalar loads (OFF32)
-  const bool off32_ok = ds->n * (int64_t)cb->v.d * 4 < (1ll << 32) && !getenv("SOMHIP_UPD_NO_OFF32");
+  const bool off32_ok = ds->n * (int64_t)cb->v.d * 4 < (1ll << 32);
   // 2 chunks per wave (a small shard) only with OFF32: with ten scalar instructions of address work per entry the
   // scalar unit, not the 12 packed vector instructions, was the bound (8 shards of the 256x256x512 map: 225 -> 203 us;
   // the LDS-tile kernel: 241)
@@ -218,7 +204,7 @@ static int som_update_run(somhip_codebook *cb, somhip_dataset *ds, int64_t data_
   // (gaussian: lattice_sq in fp32 needs both map sides <= 1024, the winner's coordinates travel as 16-bit fields)
   const bool gemm_form = e->update_mode == SOMHIP_UPDATE_GEMM && !M && cb->v.d % 128 == 0 && count <= GEMM_MAX_RUN &&
                          ds->n * (int64_t)(cb->v.d >> 2) < (1ll << 32) &&      // the entries carry 32-bit row offsets in float4 units
-                         (!G || (cb->v.xdim <= 1024 && cb->ydim <= 1024 && !getenv("SOMHIP_GAUSS_EXACT")));
+                         (!G || (cb->v.xdim <= 1024 && cb->ydim <= 1024));
   const bool off32 = scalar_form && off32_ok && !gemm_form;
   void *dbxy, *dcnt, *dent;
   CHK(engine_scratch(e, 8, sizeof(int2) * (size_t)count, &dbxy));
@@ -228,8 +214,7 @@ static int som_update_run(somhip_codebook *cb, somhip_dataset *ds, int64_t data_
   dent = (MemberEntry *)dent + GEMM_FRONT_PAD;
   // the winners' lattice coordinates: K4b decodes them itself from the keys (a division per (sample, row group), but no
   // launch) in a short run; a long run pays for the launch many times over (1024 groups x 32768 samples: members 201 -> 180 us, the decode launch 6)
-  bool decode = G || count >= 16384;                      // (the gaussian update needs the decoded winners itself)
-  if (const char *s = getenv("SOMHIP_MEMBERS_DECODE")) decode = G || atoi(s) != 0;
+  const bool decode = G || count >= 16384;                // (the gaussian update needs the decoded winners itself)
   if (decode) {
     LaunchTimer t(e, KID_DECODE);
     hipLaunchKernelGGL(k_decode_winners, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, e->stream,
@@ -268,7 +253,6 @@ static int som_update_run(somhip_codebook *cb, somhip_dataset *ds, int64_t data_
       const double full = r > 0.0 ? std::min(1.0, 3.6276 * r * r / std::max<double>(1.0, (double)cb->v.xdim * cb->ydim)) : 0.0;
       wide = tail_need == 0 || (double)tail_need > 3.0 * 1024.0 * full;
     }
-    if (const char *s = getenv("SOMHIP_MEMBERS_WIDE")) wide = atoi(s) != 0;
 #define GO(GG, NT, BXY, KEYS)                                                                              \
     hipLaunchKernelGGL((k_som_members<GG, NT>), dim3((unsigned)cb->v.ngroups), dim3(NT), 0, e->stream, cb->v, count, \
                        (const int2 *)(BXY), (const uint64_t *)(KEYS), d_sc, (uint32_t *)dcnt, (MemberEntry *)dent, e->d_stats, \
@@ -276,7 +260,7 @@ static int som_update_run(somhip_codebook *cb, somhip_dataset *ds, int64_t data_
                        (GG) && gemm_form ? 1 : 0, reach_max)
     // (decoded winners, long run, lists not cut short: 8 samples per thread -- four trips over a 32768-vector run; what a
     // trip costs besides the membership arithmetic of the queued samples is its barriers and dependent loads)
-    const bool deep = wide && !G && decode && reach_max >= 0 && count >= 16384 && !getenv("SOMHIP_MEMBERS_SHALLOW");
+    const bool deep = wide && !G && decode && reach_max >= 0 && count >= 16384;
     if (G) { if (wide) GO(true, 1024, dbxy, nullptr); else GO(true, 256, dbxy, nullptr); }
     else if (deep) hipLaunchKernelGGL((k_som_members<false, 1024, 8>), dim3((unsigned)cb->v.ngroups), dim3(1024), 0, e->stream, cb->v, count,
                        (const int2 *)dbxy, (const uint64_t *)nullptr, d_sc, (uint32_t *)dcnt, (MemberEntry *)dent, e->d_stats,
@@ -287,7 +271,7 @@ static int som_update_run(somhip_codebook *cb, somhip_dataset *ds, int64_t data_
   }
   HIPCHK(hipGetLastError());
   uint32_t *dorder = nullptr;
-  if (cb->v.ngroups <= 8192 && !getenv("SOMHIP_NO_ORDER")) {
+  if (cb->v.ngroups <= 8192) {
     void *p_;
     CHK(engine_scratch(e, 0, sizeof(uint32_t) * (size_t)cb->v.ngroups, &p_));
     dorder = (uint32_t *)p_;
@@ -303,7 +287,7 @@ static int som_update_run(somhip_codebook *cb, somhip_dataset *ds, int64_t data_
     // list: the run's samples x the share of the map a neighbourhood (dilated by a row group's 8x8 patch) covers.
     // (Round 3: 512-dim workgroups -- 64 KiB of LDS, two per CU -- kept the matrix pipe busy 46 % of the time, the rest
     // was spent waiting for the next chunk's rows; at 256 dims four fit and the kernel is 4-20 % faster at every
-    // radius of the configs[3] schedule, profiles/r03_gemm_ntw.txt.  SOMHIP_GEMM_NTW=4 brings the wide form back.)
+    // radius of the configs[3] schedule, profiles/r03_gemm_ntw.txt.)
     int ntw = G && cb->v.d % 512 == 0 ? 4 : cb->v.d % 256 == 0 ? 2 : 1;      // (gaussian: the rates are made once per workgroup slice -- wide)
     {
       const float r = sqrtf(std::max(h_sc[0].thresh, 0.0f)) + 4.5f;
@@ -313,8 +297,6 @@ static int som_update_run(somhip_codebook *cb, somhip_dataset *ds, int64_t data_
       while (by_grid > 1 && (int64_t)cb->v.ngroups * (cb->v.d / (128 * by_grid)) < 1024) by_grid >>= 1;
       ntw = std::min(ntw, std::min(by_len, by_grid));
     }
-    const char *ntw_env = getenv("SOMHIP_GEMM_NTW");       // experiment switch: 1, 2 or 4 (where the dims allow)
-    if (ntw_env && (atoi(ntw_env) == 1 || atoi(ntw_env) == 2 || atoi(ntw_env) == 4) && cb->v.d % (128 * atoi(ntw_env)) == 0) ntw = atoi(ntw_env);
     const dim3 ggrid((unsigned)(cb->v.ngroups * (cb->v.d / (128 * ntw))));
 #define GOG(NN) do { if (G) hipLaunchKernelGGL((k_som_update_gemm<NN, true>), ggrid, dim3(256), 0, e->stream, cb->v, ds->d_rows, ds->n, data_first, count, \
                                    (const uint32_t *)dcnt, (const MemberEntry *)dent, (const uint32_t *)dorder, e->d_stats, \
@@ -338,18 +320,14 @@ static int som_update_run(somhip_codebook *cb, somhip_dataset *ds, int64_t data_
     LaunchTimer tg(e, KID_SOM_UPDATE_RUN);
     // K4h: the run in one piece in the data set and smaller than 4 GiB, 32 dims per wave
     const int64_t f0 = data_first % ds->n;
-    if (cb->v.d4 % 8 == 0 && f0 + count <= ds->n && count * (int64_t)cb->v.d * 4 < (1ll << 32) && !getenv("SOMHIP_GAUSS_K4G")) {
+    if (cb->v.d4 % 8 == 0 && f0 + count <= ds->n && count * (int64_t)cb->v.d * 4 < (1ll << 32)) {
       const int per_row8 = cb->v.d4 / 8;
       int nw8 = 1;
       for (int w = 1; w <= 16; w++) if (per_row8 % w == 0) nw8 = w;
       dim3 hgrid((unsigned)(cb->v.ngroups * (per_row8 / nw8)));
       const float *xrun = ds->d_rows + f0 * cb->v.d;
-      if (getenv("SOMHIP_GAUSS_LIBM"))
-        hipLaunchKernelGGL((k_som_update_gauss_h<false>), hgrid, dim3(64 * nw8), 0, e->stream, cb->v, xrun, count,
-                           (const int2 *)dbxy, d_sc, (const uint32_t *)dcnt, (const MemberEntry *)dent, (const uint32_t *)dorder);
-      else
-        hipLaunchKernelGGL((k_som_update_gauss_h<true>), hgrid, dim3(64 * nw8), 0, e->stream, cb->v, xrun, count,
-                           (const int2 *)dbxy, d_sc, (const uint32_t *)dcnt, (const MemberEntry *)dent, (const uint32_t *)dorder);
+      hipLaunchKernelGGL(k_som_update_gauss_h, hgrid, dim3(64 * nw8), 0, e->stream, cb->v, xrun, count,
+                         (const int2 *)dbxy, d_sc, (const uint32_t *)dcnt, (const MemberEntry *)dent, (const uint32_t *)dorder);
       HIPCHK(hipGetLastError());
       return 0;
     }
@@ -362,11 +340,9 @@ static int som_update_run(somhip_codebook *cb, somhip_dataset *ds, int64_t data_
   // bubble, no masks, whole chunks, enough waves at 4 chunks each: the scalar-operand kernel K4s (a shard so small
   // that QW fell to 2 is better off with K4's pipelined tile walk: 244 vs 282 us on an eighth of the 256x256x512 map)
   if (scalar_form) {
-    const bool pk = !(getenv("SOMHIP_UPD_PK") && atoi(getenv("SOMHIP_UPD_PK")) == 0);   // packed fp32 (default): 1.44 -> 1.16 ms on the 256x256x512 map
+    // (packed fp32: 1.44 -> 1.16 ms on the 256x256x512 map)
 #define GOS(QQ)                                                                                      \
-    if (pk && off32) hipLaunchKernelGGL((k_som_update_bubble_s<QQ, true, true>), grid, dim3(256), 0, e->stream, cb->v, ds->d_rows, ds->n, data_first, \
-                       count, (const uint32_t *)dcnt, (const MemberEntry *)dent, (const uint32_t *)dorder);          \
-    else if (pk) hipLaunchKernelGGL((k_som_update_bubble_s<QQ, true>), grid, dim3(256), 0, e->stream, cb->v, ds->d_rows, ds->n, data_first, \
+    if (off32) hipLaunchKernelGGL((k_som_update_bubble_s<QQ, true>), grid, dim3(256), 0, e->stream, cb->v, ds->d_rows, ds->n, data_first, \
                        count, (const uint32_t *)dcnt, (const MemberEntry *)dent, (const uint32_t *)dorder);          \
     else hipLaunchKernelGGL((k_som_update_bubble_s<QQ>), grid, dim3(256), 0, e->stream, cb->v, ds->d_rows, ds->n, data_first, \
                        count, (const uint32_t *)dcnt, (const MemberEntry *)dent, (const uint32_t *)dorder)
@@ -376,15 +352,12 @@ static int som_update_run(somhip_codebook *cb, somhip_dataset *ds, int64_t data_
     return 0;
   }
 #define GO(QQ, GG, MM)                                                                               \
-  if (pipe) hipLaunchKernelGGL((k_som_update_run<QQ, TB, GG, MM, true>), grid, dim3(256), 0, e->stream, cb->v, ds->d_rows, \
-                     (const uint8_t *)ds->d_mask, ds->n, data_first, count, (const int2 *)dbxy, d_sc,   \
-                     (const uint32_t *)dcnt, (const MemberEntry *)dent, (const uint32_t *)dorder);      \
-  else hipLaunchKernelGGL((k_som_update_run<QQ, TB, GG, MM>), grid, dim3(256), 0, e->stream, cb->v, ds->d_rows, \
+  hipLaunchKernelGGL((k_som_update_run<QQ, TB, GG, MM>), grid, dim3(256), 0, e->stream, cb->v, ds->d_rows, \
                      (const uint8_t *)ds->d_mask, ds->n, data_first, count, (const int2 *)dbxy, d_sc,   \
                      (const uint32_t *)dcnt, (const MemberEntry *)dent, (const uint32_t *)dorder)
 #define GOQ(QQ)                                                                                      \
   do { if (G && M) { GO(QQ, true, true); } else if (G) { GO(QQ, true, false); } else if (M) { GO(QQ, false, true); } else { GO(QQ, false, false); } } while (0)
-  if (QW == 8) GOQ(8); else if (QW == 4) GOQ(4); else GOQ(2);
+  if (QW == 4) GOQ(4); else GOQ(2);
 #undef GOQ
 #undef GO
   HIPCHK(hipGetLastError());

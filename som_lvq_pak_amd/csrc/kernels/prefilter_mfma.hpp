@@ -823,84 +823,11 @@ __global__ __launch_bounds__(256, 2) void k_dist_mfma_bf16_l1(CbView cb, int d8,
 // The same level-1 GEMM on a 256 codes x 256 samples workgroup tile (8 waves, each 64 x 128 as before): with one
 // product per K-step the kernel is bound by the L2 -> LDS operand traffic, and the square tile moves a third less of it
 // per MFMA ((256 + 256) / (256 * 256) against (128 + 256) / (128 * 256)).  Wave w brings k-blocks [2 (w & 1), + 2) of
-// code group w >> 1 and of sample tiles 2 (w >> 1), 2 (w >> 1) + 1.
-template <int BD_KB>
-__global__ __launch_bounds__(512, 2) void k_dist_mfma_bf16_l1w(CbView cb, int d8, const uint4 *__restrict__ chi,
-                                                               const uint4 *__restrict__ xhi, const float *__restrict__ cn,
-                                                               int64_t bpad, float *__restrict__ wmin) {
-  static_assert(BD_KB == 4, "two k-steps per stage, one per staging half");
-  constexpr int CH = 0, XH = 4 * BD_KB * 64, TOT = XH + 8 * BD_KB * 32;
-  __shared__ uint4 lds[2 * TOT];
-  typedef __attribute__((address_space(3))) void lds_void;
-  typedef const __attribute__((address_space(1))) void glb_void;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wr = wave >> 1, wc = wave & 1;                // this wave multiplies code group wr x sample tiles 4 wc .. 4 wc + 3
-  const int half = lane >> 5, l31 = lane & 31;
-  const int64_t g0 = static_cast<int64_t>(blockIdx.y) * 4;
-  const int64_t st0 = static_cast<int64_t>(blockIdx.x) * 8;
-  const int64_t nst = bpad / 32;
-  const int arr = wave & 1, sel = wave >> 1;
-  const int64_t gsrc = g0 + sel < cb.ngroups ? g0 + sel : cb.ngroups - 1;
-  const uint4 *pc = chi + (gsrc * d8 + 2 * arr) * 64 + lane;
-  const uint4 *px[2];
-#pragma unroll
-  for (int t = 0; t < 2; t++) {
-    const int64_t ts = st0 + 2 * sel + t < nst ? st0 + 2 * sel + t : nst - 1;
-    px[t] = xhi + (ts * d8 + 2 * arr) * 32 + lane;
-  }
-  const int dc = CH + (sel * BD_KB + 2 * arr) * 64;
-  const int dx = XH + ((2 * sel) * BD_KB + 2 * arr) * 32;             // + t * BD_KB * 32
-  const int nstage = d8 / BD_KB;
-  auto issue = [&](int s) {
-    uint4 *buf = lds + (s & 1) * TOT;
-    const int kb0 = s * BD_KB;
-#pragma unroll
-    for (int k = 0; k < 2; k++)
-      __builtin_amdgcn_global_load_lds((glb_void *)(pc + (kb0 + k) * 64), (lds_void *)(buf + dc + k * 64), 16, 0, 0);
-#pragma unroll
-    for (int t = 0; t < 2; t++)
-      __builtin_amdgcn_global_load_lds((glb_void *)(px[t] + kb0 * 32), (lds_void *)(buf + dx + t * BD_KB * 32), 16, 0, 0);
-  };
-  f32x16 acc[2][4];
-#pragma unroll
-  for (int i = 0; i < 2; i++)
-#pragma unroll
-    for (int j = 0; j < 4; j++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) acc[i][j][r] = 0.0f;
-  issue(0);
-  for (int s = 0; s < nstage; s++) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (s + 1 < nstage) issue(s + 1);
-    const uint4 *buf = lds + (s & 1) * TOT;
-#pragma unroll
-    for (int m = 0; m < BD_KB / 2; m++) {
-      const int kb = 2 * m + half;
-      bf16x8 ah[2], bh[4];
-#pragma unroll
-      for (int i = 0; i < 2; i++) ah[i] = __builtin_bit_cast(bf16x8, buf[CH + (wr * BD_KB + kb) * 64 + 32 * i + l31]);
-#pragma unroll
-      for (int j = 0; j < 4; j++) bh[j] = __builtin_bit_cast(bf16x8, buf[XH + ((wc * 4 + j) * BD_KB + kb) * 32 + l31]);
-#pragma unroll
-      for (int i = 0; i < 2; i++)
-#pragma unroll
-        for (int j = 0; j < 4; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-    }
-  }
-#pragma unroll
-  for (int h2 = 0; h2 < 2; h2++) {
-    f32x16 sub[2][2] = {{acc[0][2 * h2], acc[0][2 * h2 + 1]}, {acc[1][2 * h2], acc[1][2 * h2 + 1]}};
-    prefilter_epilogue_min(cb, sub, g0 + wr, st0 + wc * 4 + 2 * h2, nst, lane, cn, bpad, wmin);
-  }
-}
-
-// The same workgroup tile, staging and LDS layout with v_mfma_f32_16x16x32_bf16: a stage of 4 k-blocks is ONE K-step of
-// 32 dims; lane (r = lane & 15, kg = lane >> 4) supplies k-block kg of row / sample r, which is one 16-byte piece of the
-// staged tiles as they are.  A wave's 64 x 128 tile is 4 x 8 MFMAs per stage on the same 12 fragment reads; register v
+// code group w >> 1 and of sample tiles 2 (w >> 1), 2 (w >> 1) + 1.  With v_mfma_f32_16x16x32_bf16 a stage of 4
+// k-blocks is ONE K-step of 32 dims; lane (r = lane & 15, kg = lane >> 4) supplies k-block kg of row / sample r, which
+// is one 16-byte piece of the staged tiles as they are.  A wave's 64 x 128 tile is 4 x 8 MFMAs per stage on the same 12 fragment reads; register v
 // of an output tile is row 4 (lane >> 4) + v, column lane & 15.  (The 16x16x32 form sustains a higher rate than
-// 32x32x16 on this part: MI355X_MICROARCH.md, bare-loop measurements.)
+// 32x32x16 on this part: MI355X_MICROARCH.md, bare-loop measurements; the 32x32x16 form of this tile was removed.)
 template <int BD_KB>
 __global__ __launch_bounds__(512, 2) void k_dist_mfma_bf16_l1w16(CbView cb, int d8, const uint4 *__restrict__ chi,
                                                                  const uint4 *__restrict__ xhi, const float *__restrict__ cn,
@@ -1056,15 +983,18 @@ __global__ __launch_bounds__(256) void k_l2_select(int64_t ngroups, int64_t coun
 
 // level 2: the three-product GEMM of one row group against tiles of 32 of ITS surviving samples; one wave per tile,
 // operands straight from global memory (each lane loads the 16-byte pieces the MFMA wants from it: for B the piece
-// of its own gathered sample).  Writes wmin / wmask of the (group, sample) pairs it covers.
-template <int DEPTH>                   // k-steps whose operands are requested together
+// of its own gathered sample, from the sample-major copy xrow of k_pack_samples_bf16 -- consecutive bytes per sample,
+// so whole cache lines are used).  Writes wmin / wmask of the (group, sample) pairs it covers.
+// (The host always passes xrow.  The select on it below stays: without it hipcc schedules the k-step loop with one more
+// full wait for memory, and the kernel measured 0.066-0.069 ms per launch against 0.061-0.062 at the configs[4] shape.)
 __global__ __launch_bounds__(256) void k_dist_l2(CbView cb, int d8, const uint4 *__restrict__ chi, const uint4 *__restrict__ clo,
                                                  const uint4 *__restrict__ xhi, const uint4 *__restrict__ xlo,
                                                  const float *__restrict__ cn, const float *__restrict__ tau, int64_t bpad,
                                                  const uint32_t *__restrict__ cnt, const uint16_t *__restrict__ list,
                                                  float *__restrict__ wmin, uint64_t *__restrict__ wmask,
-                                                 unsigned long long *__restrict__ stats, const uint4 *__restrict__ xrow = nullptr,
+                                                 unsigned long long *__restrict__ stats, const uint4 *__restrict__ xrow,
                                                  uint32_t *__restrict__ gmin = nullptr) {
+  constexpr int DEPTH = 2;             // k-steps whose operands are requested together (configs[4] shape: 62 us per launch against 65 at 4)
   const int64_t g = blockIdx.x;
   const int n = static_cast<int>(cnt[g]);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l31 = lane & 31;
@@ -1076,8 +1006,7 @@ __global__ __launch_bounds__(256) void k_dist_l2(CbView cb, int d8, const uint4 
     const bool valid = slot < n;
     const int64_t b = list[g * bpad + (valid ? slot : 0)];
     const uint4 *pa = chi + (g * d8 + half) * 64 + l31, *pl = clo + (g * d8 + half) * 64 + l31;
-    // operand B: this lane's sample, k-block o + half -- from the sample-major copy when there is one (consecutive bytes
-    // per sample: whole cache lines are used), else from the 32-sample tiles (16 bytes out of every 512)
+    // operand B: this lane's sample, k-block o + half
     const uint4 *pxh = xrow ? xrow + (b * d8 + half) * 2 : xhi + ((b >> 5) * d8 + half) * 32 + (b & 31);
     const uint4 *pxl = xrow ? pxh + 1 : xlo + ((b >> 5) * d8 + half) * 32 + (b & 31);
     const int xs = xrow ? 2 : 32;                          // uint4 between consecutive k-blocks of one sample
@@ -1156,12 +1085,11 @@ __global__ __launch_bounds__(256) void k_dist_l2(CbView cb, int d8, const uint4 
 #endif                   // launch along the configs[3] schedule: depth 8 (round 2) 546 ... 91, 4: 498 ... 80, 2: 444 ... 73, 1: 453 ... 79
 constexpr int L2_WAVES = L2_WAVES_V;   // waves of a k_dist_l2_lds workgroup (one workgroup per CU: its LDS holds a group's tiles)
 __global__ __launch_bounds__(64 * L2_WAVES, 1) void k_dist_l2_lds(CbView cb, int d8, const uint4 *__restrict__ chi, const uint4 *__restrict__ clo,
-                                                        const uint4 *__restrict__ xhi, const uint4 *__restrict__ xlo,
+                                                        const uint4 *__restrict__ xrow,
                                                         const float *__restrict__ cn, const float *__restrict__ tau, int64_t bpad,
                                                         const uint32_t *__restrict__ cnt, const uint16_t *__restrict__ list,
                                                         float *__restrict__ wmin, uint64_t *__restrict__ wmask,
-                                                        unsigned long long *__restrict__ stats, const uint4 *__restrict__ xrow = nullptr,
-                                                        uint32_t *__restrict__ gmin = nullptr) {
+                                                        unsigned long long *__restrict__ stats, uint32_t *__restrict__ gmin = nullptr) {
   extern __shared__ uint4 s_l2a[];                         // [hi | lo][d8][64]
   typedef __attribute__((address_space(3))) void lds_void;
   typedef const __attribute__((address_space(1))) void glb_void;
@@ -1186,9 +1114,8 @@ __global__ __launch_bounds__(64 * L2_WAVES, 1) void k_dist_l2_lds(CbView cb, int
     const int slot = tile * 32 + l31;
     const bool valid = slot < n;
     const int64_t b = list[g * bpad + (valid ? slot : 0)];
-    const uint4 *pxh = xrow ? xrow + (b * d8 + half) * 2 : xhi + ((b >> 5) * d8 + half) * 32 + (b & 31);   // (see k_dist_l2)
-    const uint4 *pxl = xrow ? pxh + 1 : xlo + ((b >> 5) * d8 + half) * 32 + (b & 31);
-    const int xs = xrow ? 2 : 32;
+    const uint4 *pxh = xrow + (b * d8 + half) * 2, *pxl = pxh + 1;   // (see k_dist_l2)
+    constexpr int xs = 2;
     f32x16 acc[2];
 #pragma unroll
     for (int i = 0; i < 2; i++)

@@ -367,13 +367,13 @@ __global__ __launch_bounds__(256) void k_order_groups(const uint32_t *__restrict
 // between barriers.  The list is walked in tiles of TB entries: entry scalars -> LDS, the
 // tile's sample slices staged into LDS (one coalesced pass), then every wave applies the
 // tile's updates in order (member lanes from the entry's mask, x as broadcast reads).
-// =====================================================================================
 //
-// PIPE = true is the form for small shards (few waves per SIMD, nothing to hide LDS latency behind):
-// the lane's membership bits of the whole tile are gathered first, then the entries are walked in
-// unrolled groups of 8 with the next entry's x chunks and alpha already in flight while the current
-// one is applied.  Same operations on the same values in the same order as PIPE = false.
-template <int QW, int TB, bool GAUSS, bool MASKED, bool PIPE = false>
+// The walk is pipelined (it was written for small shards: few waves per SIMD, nothing to hide LDS latency
+// behind): the lane's membership bits of the whole tile are gathered first, then the entries are walked in
+// unrolled groups of 8 with the next entry's x chunks and alpha already in flight while the current one is
+// applied.
+// =====================================================================================
+template <int QW, int TB, bool GAUSS, bool MASKED>
 __global__ __launch_bounds__(256) void k_som_update_run(CbView cb, const float *__restrict__ rows,
                                                         const uint8_t *__restrict__ mask,
                                                         int64_t n_rows, int64_t data_first,
@@ -384,8 +384,8 @@ __global__ __launch_bounds__(256) void k_som_update_run(CbView cb, const float *
                                                         const MemberEntry *__restrict__ ent,
                                                         const uint32_t *__restrict__ order) {
   constexpr int BQ = 4 * QW;                          // chunks per workgroup
-  static_assert(TB % 8 == 0, "PIPE walks the tile in groups of 8 entries");
-  __shared__ float4 xs[TB + (PIPE ? 1 : 0)][BQ];              // PIPE: one row of slack for the last prefetch
+  static_assert(TB % 8 == 0, "the walk goes through the tile in groups of 8 entries");
+  __shared__ float4 xs[TB + 1][BQ];                           // one row of slack for the last prefetch
   __shared__ uint32_t ms[MASKED ? TB : 1][MASKED ? BQ : 1];   // 4 mask bits per chunk
   __shared__ float s_ga[GAUSS ? TB + 1 : 1][GAUSS ? WAVE : 1];    // gaussian: per-lane alpha
   __shared__ unsigned long long s_mask[TB];
@@ -429,8 +429,8 @@ __global__ __launch_bounds__(256) void k_som_update_run(CbView cb, const float *
       s_alpha[tid] = s.alpha;
       s_xoff[tid] = ((data_first + e.sample) % n_rows) * cb.d;
       if (GAUSS) { const int2 w = bxy[e.sample]; s_bx[tid] = w.x; s_by[tid] = w.y; s_thr[tid] = s.thresh; }
-    } else if (PIPE && tid < TB) {
-      s_mask[tid] = 0ull;                             // PIPE gathers the bits of all TB slots
+    } else if (tid < TB) {
+      s_mask[tid] = 0ull;                             // the walk gathers the bits of all TB slots
     }
     __syncthreads();
     // ---- sample slices -> LDS (+ gaussian: per-lane alpha, once per workgroup)
@@ -457,7 +457,7 @@ __global__ __launch_bounds__(256) void k_som_update_run(CbView cb, const float *
     __syncthreads();
     // ---- the tile's updates, in iteration order
     auto apply = [&](int i, const float4 *x, float a) {
-      if (!MASKED && PIPE) {                          // packed fp32: two elements per instruction, each half rounded like the scalar op
+      if (!MASKED) {                                  // packed fp32: two elements per instruction, each half rounded like the scalar op
         const f32x2 a2 = {a, a};
 #pragma unroll
         for (int j = 0; j < QW; j++) {
@@ -483,34 +483,28 @@ __global__ __launch_bounds__(256) void k_som_update_run(CbView cb, const float *
         }
       }
     };
-    if (PIPE) {
-      if (q0 < cb.d4) {
-        const uint32_t *m32 = reinterpret_cast<const uint32_t *>(s_mask) + (lane >> 5);
-        uint32_t bits = 0;
+    if (q0 < cb.d4) {
+      const uint32_t *m32 = reinterpret_cast<const uint32_t *>(s_mask) + (lane >> 5);
+      uint32_t bits = 0;
 #pragma unroll
-        for (int i = 0; i < TB; i++) bits |= ((m32[2 * i] >> (lane & 31)) & 1u) << i;
-        float4 xa[QW], xb[QW];
-        float aa, ab;
-        auto fetch = [&](int i, float4 *x, float &a) {
+      for (int i = 0; i < TB; i++) bits |= ((m32[2 * i] >> (lane & 31)) & 1u) << i;
+      float4 xa[QW], xb[QW];
+      float aa, ab;
+      auto fetch = [&](int i, float4 *x, float &a) {
 #pragma unroll
-          for (int j = 0; j < QW; j++) x[j] = xs[i][wave * QW + j];
-          a = GAUSS ? s_ga[i][lane] : s_alpha[i];
-        };
-        fetch(0, xa, aa);
-        for (int i0 = 0; i0 < tb; i0 += 8) {
+        for (int j = 0; j < QW; j++) x[j] = xs[i][wave * QW + j];
+        a = GAUSS ? s_ga[i][lane] : s_alpha[i];
+      };
+      fetch(0, xa, aa);
+      for (int i0 = 0; i0 < tb; i0 += 8) {
 #pragma unroll
-          for (int u = 0; u < 8; u += 2) {
-            fetch(i0 + u + 1, xb, ab);
-            if (bits & (1u << u)) apply(i0 + u, xa, aa);
-            fetch(i0 + u + 2, xa, aa);
-            if (bits & (2u << u)) apply(i0 + u + 1, xb, ab);
-          }
-          bits >>= 8;
+        for (int u = 0; u < 8; u += 2) {
+          fetch(i0 + u + 1, xb, ab);
+          if (bits & (1u << u)) apply(i0 + u, xa, aa);
+          fetch(i0 + u + 2, xa, aa);
+          if (bits & (2u << u)) apply(i0 + u + 1, xb, ab);
         }
-      }
-    } else if (q0 < cb.d4) {
-      for (int i = 0; i < tb; i++) {
-        if ((s_mask[i] >> lane) & 1ull) apply(i, &xs[i][wave * QW], GAUSS ? s_ga[i][lane] : s_alpha[i]);
+        bits >>= 8;
       }
     }
     __syncthreads();
@@ -593,7 +587,7 @@ __device__ __forceinline__ void k4s_load_entry_off(u32x4_t &e, const MemberEntry
 // scalar load take their address as base + register offset, so an entry costs the scalar unit three instructions
 // of address work instead of ten (8 scalar instructions per entry in all; the measured time did not change --
 // neither on the whole map, where the vector ALU is the bound, nor on an eighth of it).
-template <int QW, bool PK = false, bool OFF32 = false>
+template <int QW, bool OFF32 = false>
 __global__ __launch_bounds__(256) void k_som_update_bubble_s(CbView cb, const float *__restrict__ rows,
                                                              int64_t n_rows, int64_t data_first, int64_t count,
                                                              const uint32_t *__restrict__ cnt,
@@ -633,20 +627,16 @@ __global__ __launch_bounds__(256) void k_som_update_bubble_s(CbView cb, const fl
   auto apply = [&](const u32x4_t &e, const K4sX<4 * QW> &x) {
     if (__builtin_amdgcn_inverse_ballot_w64((static_cast<unsigned long long>(e.w) << 32) | e.z)) {
       const float a = __uint_as_float(e.y);
-      if (PK) {                                        // v_pk_add/mul_f32: two elements per instruction, each half rounded like the scalar op
-        const f32x2 a2 = {a, a};
+      // v_pk_add/mul_f32: two elements per instruction, each half rounded like the scalar op
+      const f32x2 a2 = {a, a};
 #pragma unroll
-        for (int j = 0; j < QW; j++) {
-          const float4 xv = x.chunk(j);
-          f32x2 lo = {c[j].x, c[j].y}, hi = {c[j].z, c[j].w};
-          const f32x2 tl = f32x2{xv.x, xv.y} - lo, th = f32x2{xv.z, xv.w} - hi;
-          const f32x2 sl = a2 * tl, sh = a2 * th;
-          lo = lo + sl; hi = hi + sh;
-          c[j] = make_float4(lo.x, lo.y, hi.x, hi.y);
-        }
-      } else {
-#pragma unroll
-        for (int j = 0; j < QW; j++) c[j] = adapt4(c[j], x.chunk(j), a);
+      for (int j = 0; j < QW; j++) {
+        const float4 xv = x.chunk(j);
+        f32x2 lo = {c[j].x, c[j].y}, hi = {c[j].z, c[j].w};
+        const f32x2 tl = f32x2{xv.x, xv.y} - lo, th = f32x2{xv.z, xv.w} - hi;
+        const f32x2 sl = a2 * tl, sh = a2 * th;
+        lo = lo + sl; hi = hi + sh;
+        c[j] = make_float4(lo.x, lo.y, hi.x, hi.y);
       }
     }
   };
@@ -828,7 +818,7 @@ __global__ __launch_bounds__(1024) void k_som_update_gauss_s(CbView cb, const fl
 
 // =====================================================================================
 // K4h: K4g for runs that lie in one piece in the data set (no wrap inside the batch, the batch smaller than 4 GiB),
-// dims in whole 32s; the rate in gauss_rate.hpp's short form (FAST false: the library chain, SOMHIP_GAUSS_LIBM=1).
+// dims in whole 32s; the rate in gauss_rate.hpp's short form, with the library chain where that form declines.
 // K4g costs the CU's ONE scalar unit ~36 instructions per (wave, entry) -- list entry, clamped index, 64-bit row
 // address, tile tests, four branches -- against 24 packed vector instructions: with 32 waves on a CU the scalar unit
 // is the bound (36 x 32 = 1152 issue cycles per round of entries against 768 of vector work per SIMD).  Here:
@@ -859,7 +849,6 @@ struct K4hX {                                              // 16 dims of a sampl
   __device__ __forceinline__ float4 chunk(int j) const { return make_float4(v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]); }
 };
 
-template <bool FAST = true>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_som_update_gauss_h(CbView cb, const float *__restrict__ xrun, int64_t count,
                                                              const int2 *__restrict__ bxy,
                                                              const StepScalars *__restrict__ sc,
@@ -925,7 +914,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
       const double den = k4g_readlane(den_l, i), rcp = k4g_readlane(rcp_l, i);
       const float lat = lattice_sq(cb.topol, wx, wy, tx, ty);
       float h, a;
-      if (FAST && gauss_rate_fast(lat, den, rcp, &h)) a = alpha * h;
+      if (gauss_rate_fast(lat, den, rcp, &h)) a = alpha * h;
       else a = gaussian_alpha_call(lat, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(radius_l), il)), alpha);
       dst[i * WAVE] = a;
     }

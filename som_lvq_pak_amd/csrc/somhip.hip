@@ -112,7 +112,6 @@ struct somhip_engine {
   uint64_t timing_mask = ~0ull;              // which kernel ids get events when timing is on
   int scan_mode = SOMHIP_SCAN_MFMA_BF16;
   int update_mode = SOMHIP_UPDATE_EXACT;
-  double tau_scale = 1.0;                    // >= 1: widen the pre-filter window (experiments only)
   unsigned long long *d_stats = nullptr;     // [4] re-rank statistics (device)
   uint64_t samples_searched = 0;
   // somhip_shard_winner_begin / _refine / _finish: which search is under way on this engine (0 = none)
@@ -146,7 +145,6 @@ struct somhip_engine {
   bool l2_lds_attr_set = false;                // ... and for k_dist_l2_lds
   bool l1r_attr_set = false;                   // ... and for k_dist_mfma_bf16_l1r
   int n_cus = 0;                               // compute units of the device (grid of the persistent kernels)
-  int online_u = 8;                            // register-buffer depth of the online step kernel in use (SOMHIP_ONLINE_U)
   LvqCtl *lvq_hctl = nullptr;                  // pinned: read-backs of the LVQ batch loop's control block, one per batch in flight
   hipEvent_t lvq_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 };
@@ -242,7 +240,6 @@ extern "C" int somhip_engine_create(int device, somhip_engine **out) try {
   e->device = device;
   auto init = [&]() -> int {
     HIPCHK(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-    if (const char *ts = getenv("SOMHIP_TAU_SCALE")) { double v = atof(ts); if (v >= 1.0) e->tau_scale = v; }
     HIPCHK(hipMalloc((void **)&e->d_stats, (8 + 128 + 8 + 2) * sizeof(unsigned long long)));   // + 64 {rows, pairs} update counters + 8 gemm-walk counters + level-2 pairs + top-k pairs
     HIPCHK(hipMemset(e->d_stats, 0, (8 + 128 + 8 + 2) * sizeof(unsigned long long)));
     if (const char *um = getenv("SOMHIP_UPDATE_MODE")) e->update_mode = strcmp(um, "gemm") == 0 ? SOMHIP_UPDATE_GEMM : SOMHIP_UPDATE_EXACT;
@@ -440,7 +437,7 @@ static int codebook_create(somhip_engine *e, const float *rows, const int32_t *l
     cb->v.patch_stride = patch_stride;
     cb->v.patch_phase = patch_phase;
   } else if (topol >= SOMHIP_TOPOL_HEXA && xdim % 8 == 0 && ydim % 8 == 0 && row_offset % (8 * (int64_t)xdim) == 0 &&
-      n_rows % (8 * (int64_t)xdim) == 0 && !getenv("SOMHIP_LINEAR_ROWS"))
+      n_rows % (8 * (int64_t)xdim) == 0)
     cb->v.patch_w = xdim / 8;                     // 8x8-unit row groups (kernels.hpp CbView)
   cb->ydim = ydim;
   cb->n_global = n_global;
