@@ -150,7 +150,11 @@ void somhip_dataset_destroy(somhip_dataset *ds);
  * Samples are data rows [first, first+count).  Outputs are host arrays
  * [count][knn]: index = global row (or -1: nothing beat FLT_MAX), diff = SQUARED
  * distance exactly as the reference's fp32 left-to-right sum gives it; ret[i] = the
- * function's return value (knn, or 0 = every component masked). ret may be NULL. */
+ * function's return value (knn, or 0 = every component masked). ret may be NULL.
+ * Masked data sets (somhip_dataset_create with a mask) work for every knn: only the sample's
+ * mask counts (lvq_pak.c:179-186), a code row's own masked components take part with their
+ * stored value; a sample with every component masked gets ret 0 and index -2 in all knn slots.
+ * Masked runs always take the exact direct-form scan (no MFMA pre-filter). */
 int  somhip_find_winners(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count,
                          int knn, int tie, int32_t *index, float *diff, int32_t *ret);
 
@@ -202,8 +206,12 @@ int  somhip_som_auto_batch(const somhip_som_params *p, int64_t n_units, int topo
  * reference, bit for bit; internally the loop runs as exact speculative batches (one
  * frozen-codebook scan per batch, samples certified and applied in order; see
  * kernels.hpp K6) unless SOMHIP_LVQ_ONLINE=1 or a row does not fit the on-chip cache
- * (dim > 2048), in which case every iteration is its own launch.  The trace has knn
- * entries per iteration (knn = 2 for LVQ2/LVQ3, else 1). */
+ * (dim > 2048) or the data set is masked, in which case every iteration is its own launch.
+ * Masked data: distances and adapt_vector skip the sample's masked components
+ * (lvq_pak.c:65-69, 179-186, 343-347); a run that would visit a row with every component
+ * masked is refused before anything is trained (the reference dereferences a NULL winner
+ * there, lvq_rout.c:542-545).  The trace has knn entries per iteration (knn = 2 for
+ * LVQ2/LVQ3, else 1). */
 typedef struct somhip_lvq_params {
   int32_t kind;
   int64_t length;
@@ -287,7 +295,10 @@ int  somhip_shard_winner_finish(somhip_codebook *cb, somhip_dataset *ds, int64_t
  * this shard's knn best rows per sample, ascending; tag = global row index (SOMHIP_TIE_FIRST) or its
  * bitwise complement (SOMHIP_TIE_KNN: on equal distances the LATER row sorts first, lvq_pak.c:197).
  * Missing entries (shard smaller than knn) are all-ones.  All-gather the lists and keep the knn
- * smallest keys per sample: that is find_winner_knn (lvq_pak.c:152-221) over the whole codebook. */
+ * smallest keys per sample: that is find_winner_knn (lvq_pak.c:152-221) over the whole codebook.
+ * Masked data sets are accepted (exact direct-form scan, the sample's mask alone counts); a sample
+ * with every component masked has distance 0 to every row here -- the reference finds no neighbour
+ * for it (ret 0 of somhip_find_winners), so a host checks such rows itself. */
 int  somhip_batch_topk_keys(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count,
                             int knn, int tie, uint64_t *dev_keys);
 /* The lists of all shards, all-gathered into dev_gathered[n_shards][count][knn] -> dev_keys[count][knn], the knn
@@ -311,7 +322,8 @@ int  somhip_merge_topk_keys(somhip_engine *e, const uint64_t *dev_gathered, int 
  *        all ranks take the same decisions) and commits the corrected rows it owns.  *consumed <= count iterations
  *        were applied -- the same number on every rank; the next batch starts there.  A winner beyond the `xrows`
  *        exchanged rows ends the batch early (a larger xrows trades exchange volume for longer batches; 8 = never).
- * trace_index / trace_diff: as somhip_lvq_train, for the consumed iterations. */
+ * trace_index / trace_diff: as somhip_lvq_train, for the consumed iterations.
+ * Masked data sets are refused by somhip_lvq_batch_apply (the batched walk takes no masks); somhip_lvq_train runs them. */
 int  somhip_lvq_rates_upload(somhip_codebook *cb, const float *talpha);     /* [n_rows] local rows, lvq_rout.c:614-627 */
 int  somhip_lvq_rates_download(somhip_codebook *cb, float *talpha);
 int  somhip_lvq_batch_candidates(somhip_codebook *cb, int64_t count, int kind, const uint64_t *dev_keys, int xrows,

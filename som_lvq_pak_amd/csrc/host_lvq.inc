@@ -359,6 +359,8 @@ static int lvq_train_batched(somhip_codebook *cb, somhip_dataset *ds, const somh
   return 0;
 }
 
+// lvq*_training (include/somhip.h): the exact batched engine for unmasked data, else one k_lvq_online_step launch per
+// iteration -- masked data sets always take that path (k_lvq_online_step<true>: the sample's mask in distance and update)
 extern "C" int somhip_lvq_train(somhip_codebook *cb, somhip_dataset *ds, const somhip_lvq_params *p,
                                 float *talpha, int32_t *trace_index, float *trace_diff) try {
   CHK(check_pair(cb, ds, "somhip_lvq_train"));
@@ -366,10 +368,19 @@ extern "C" int somhip_lvq_train(somhip_codebook *cb, somhip_dataset *ds, const s
   if (p->kind < SOMHIP_LVQ1 || p->kind > SOMHIP_LVQ3) return fail("Unknown LVQ type %d", p->kind);
   if (!cb->d_labels) return fail("somhip_lvq_train: codebook has no labels");
   if (ds->labels.empty()) return fail("somhip_lvq_train: data has no labels");
-  if (ds->d_mask) return fail("somhip_lvq_train: masked samples are not supported by the LVQ loops");
   if (p->kind == SOMHIP_OLVQ1 && !talpha) return fail("somhip_lvq_train: OLVQ1 needs talpha");
   if (p->length <= 0 || p->count < 0 || p->start_iter + p->count > p->length)
     return fail("somhip_lvq_train: iterations outside schedule");
+  // masked data: a sample with every component masked has no winner, and the reference then adapts through a NULL
+  // winner (lvq_rout.c:542-545) -- refuse such a run before anything is trained
+  const bool masked = ds->d_mask != nullptr;
+  if (masked && !ds->all_masked.empty())
+    for (int64_t j = 0; j < std::min<int64_t>(p->count, ds->n); j++) {
+      const int64_t r = (p->data_first + j) % ds->n;
+      if (ds->all_masked[(size_t)r])
+        return fail("somhip_lvq_train: data row %lld has every component masked: no winner (the reference crashes here)",
+                    (long long)r);
+    }
   if (cb->v.row_offset != 0 || cb->n_global != cb->v.n) return fail("somhip_lvq_train: sharded codebook not supported");
   const int knn = (p->kind >= SOMHIP_LVQ2) ? 2 : 1;
   if (knn == 2 && cb->v.n < 2) return fail("somhip_lvq_train: LVQ2/LVQ3 need at least two code rows");
@@ -380,8 +391,9 @@ extern "C" int somhip_lvq_train(somhip_codebook *cb, somhip_dataset *ds, const s
     if (!cb->d_talpha) HIPCHK(hipMalloc((void **)&cb->d_talpha, sizeof(float) * (size_t)cb->v.n));
     HIPCHK(hipMemcpyAsync(cb->d_talpha, talpha, sizeof(float) * (size_t)cb->v.n, hipMemcpyHostToDevice, e->stream));
   }
-  // exact batched engine unless asked otherwise (SOMHIP_LVQ_ONLINE=1), or the row does not fit the cache
-  if (!getenv("SOMHIP_LVQ_ONLINE") && cb->v.patch_w == 0 && cb->v.d4 <= LVQ_BT && lvq_cache_slots(cb->v.d4) >= 8) {
+  // exact batched engine unless asked otherwise (SOMHIP_LVQ_ONLINE=1), the data are masked (the batched engine's
+  // frozen-codebook scan and walk take no masks), or the row does not fit the cache
+  if (!masked && !getenv("SOMHIP_LVQ_ONLINE") && cb->v.patch_w == 0 && cb->v.d4 <= LVQ_BT && lvq_cache_slots(cb->v.d4) >= 8) {
     int rc = lvq_train_batched(cb, ds, p, knn, talpha, trace_index, trace_diff);
     if (rc) return rc;
     if (p->kind == SOMHIP_OLVQ1)
@@ -390,6 +402,7 @@ extern "C" int somhip_lvq_train(somhip_codebook *cb, somhip_dataset *ds, const s
     return 0;
   }
   cb->prep_valid = false;                                 // the per-iteration kernel rewrites rows in place
+  auto step = masked ? k_lvq_online_step<true> : k_lvq_online_step<false>;
   const int64_t CH = 4096;
   const int nblk = (int)((cb->v.ngroups + 3) / 4);
   void *dpart, *dfinal, *dst;
@@ -428,10 +441,10 @@ extern "C" int somhip_lvq_train(somhip_codebook *cb, somhip_dataset *ds, const s
       int64_t cur_row = (row0 + j) % ds->n;
       {
         LaunchTimer t(e, KID_LVQ_ONLINE_STEP);
-        hipLaunchKernelGGL(k_lvq_online_step, dim3((unsigned)nblk), dim3(256), 0, e->stream, cb->v,
-                           ds->d_rows, (const int32_t *)cb->d_labels, cb->d_talpha, prev_row, cur_row,
-                           have_prev ? 1 : 0, 1, knn, (const uint64_t *)part[flip], nblk, part[flip ^ 1],
-                           fin + 2 * j, (const LvqStep *)(st + j));
+        hipLaunchKernelGGL(step, dim3((unsigned)nblk), dim3(256), 0, e->stream, cb->v,
+                           ds->d_rows, (const uint8_t *)ds->d_mask, (const int32_t *)cb->d_labels, cb->d_talpha,
+                           prev_row, cur_row, have_prev ? 1 : 0, 1, knn, (const uint64_t *)part[flip], nblk,
+                           part[flip ^ 1], fin + 2 * j, (const LvqStep *)(st + j));
       }
       flip ^= 1;
       prev_row = cur_row;
@@ -460,9 +473,9 @@ extern "C" int somhip_lvq_train(somhip_codebook *cb, somhip_dataset *ds, const s
   // flush: apply the last iteration's correction; its winners land in fin[0]
   {
     LaunchTimer t(e, KID_LVQ_ONLINE_STEP);
-    hipLaunchKernelGGL(k_lvq_online_step, dim3((unsigned)nblk), dim3(256), 0, e->stream, cb->v, ds->d_rows,
-                       (const int32_t *)cb->d_labels, cb->d_talpha, prev_row, prev_row, 1, 0, knn,
-                       (const uint64_t *)part[flip], nblk, part[flip ^ 1], fin, (const LvqStep *)st);
+    hipLaunchKernelGGL(step, dim3((unsigned)nblk), dim3(256), 0, e->stream, cb->v, ds->d_rows,
+                       (const uint8_t *)ds->d_mask, (const int32_t *)cb->d_labels, cb->d_talpha, prev_row, prev_row, 1,
+                       0, knn, (const uint64_t *)part[flip], nblk, part[flip ^ 1], fin, (const LvqStep *)st);
   }
   HIPCHK(hipGetLastError());
   if (trace_index || trace_diff) {
@@ -553,6 +566,7 @@ extern "C" int somhip_lvq_batch_apply(somhip_codebook *cb, somhip_dataset *ds, c
   if (!p || !dev_keys || !dev_lab || !dev_rows || !consumed) return fail("somhip_lvq_batch_apply: null argument");
   if (p->kind < SOMHIP_LVQ1 || p->kind > SOMHIP_LVQ3) return fail("Unknown LVQ type %d", p->kind);
   if (ds->labels.empty()) return fail("somhip_lvq_batch_apply: data has no labels");
+  // (masked data: somhip_lvq_train's per-iteration path; the batched walk and the row-sharded LVQ path take no masks)
   if (ds->d_mask) return fail("somhip_lvq_batch_apply: masked samples are not supported by the LVQ loops");
   if (count < 0 || count > LVQ_BMAX) return fail("somhip_lvq_batch_apply: at most %d samples per batch", LVQ_BMAX);
   if (xrows < 1 || xrows > LVQ_K0) return fail("somhip_lvq_batch_apply: xrows must be 1..%d", LVQ_K0);

@@ -446,8 +446,28 @@ static int scan_keys_topk(somhip_codebook *cb, somhip_dataset *ds, int64_t first
     HIPCHK(hipGetLastError());
     return 0;
   }
-  int64_t nsb = (count + SCAN_S - 1) / SCAN_S;
   int nblk = (int)((cb->v.ngroups + 3) / 4);
+  if (ds->d_mask) {
+    // masked samples (kernels.hpp K1mk): one sample per launch column, the same partial lists as the exact scan below
+    void *part;
+    CHK(engine_scratch(e, 2, sizeof(uint64_t) * (size_t)count * nblk * K, &part));
+    for (int64_t off = 0; off < count; off += 32768) {      // grid.y limit
+      int64_t c = std::min<int64_t>(32768, count - off);
+      LaunchTimer t(e, KID_SCAN_MASKED);
+      hipLaunchKernelGGL(k_scan_masked_topk<K>, dim3((unsigned)nblk, (unsigned)c), dim3(256), 0, e->stream, cb->v, ds->d_rows,
+                         (const uint8_t *)ds->d_mask, ds->n, (first + off) % ds->n, tie_knn,
+                         (uint64_t *)part + (size_t)off * nblk * K);
+    }
+    HIPCHK(hipGetLastError());
+    {
+      LaunchTimer t(e, KID_MERGE_TOPK);
+      hipLaunchKernelGGL(k_merge_topk<K>, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, e->stream,
+                         (const uint64_t *)part, nblk, count, d_keys);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
+  int64_t nsb = (count + SCAN_S - 1) / SCAN_S;
   void *xt, *part;
   CHK(engine_scratch(e, 1, sizeof(float4) * (size_t)nsb * cb->v.d4 * SCAN_S, &xt));
   CHK(engine_scratch(e, 2, sizeof(uint64_t) * (size_t)count * nblk * K, &part));
@@ -555,11 +575,11 @@ extern "C" int somhip_shard_winner_finish(somhip_codebook *cb, somhip_dataset *d
 // X2 (SURVEY 8e): this shard's k best rows per sample as packed keys, ascending; a host all-gathers
 // the shards' lists and keeps the k smallest per sample (keys are unique: tag = global row, or its
 // complement for the k-NN tie order, so the merge IS find_winner_knn over the whole codebook).
+// Masked data sets: K1m (knn 1) / K1mk (knn 2, 4, 8); fully masked samples are the caller's to skip.
 extern "C" int somhip_batch_topk_keys(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count,
                                       int knn, int tie, uint64_t *dev_keys) try {
   CHK(check_pair(cb, ds, "somhip_batch_topk_keys"));
   if (knn < 1 || knn > 8) return fail("somhip_batch_topk_keys: knn %d not in 1..8", knn);
-  if (ds->d_mask) return fail("somhip_batch_topk_keys: masked samples are not supported");
   if (count <= 0) return 0;
   HIPCHK(hipSetDevice(cb->e->device));
   const int t = tie == SOMHIP_TIE_KNN ? 1 : 0;
@@ -584,6 +604,8 @@ static void decode_key(uint64_t k, bool inverted, int32_t *index, float *diff) {
   memcpy(diff, &bits, 4);
 }
 
+// find_winner_euc / find_winner_knn over a run of samples (include/somhip.h); masked data sets take K1m / K1mk for
+// every knn, and a fully masked sample reports ret 0, index -2 (lvq_pak.c:65-69 / :188-189 return 0 neighbours)
 extern "C" int somhip_find_winners(somhip_codebook *cb, somhip_dataset *ds, int64_t first,
                                    int64_t count, int knn, int tie, int32_t *index, float *diff,
                                    int32_t *ret) try {
@@ -596,7 +618,6 @@ extern "C" int somhip_find_winners(somhip_codebook *cb, somhip_dataset *ds, int6
   // find_winner_knn(knn == 1) IS find_winner_euc (lvq_pak.c:160-161)
   const bool knn_rule = (tie == SOMHIP_TIE_KNN) && knn >= 2;
   if (!knn_rule && knn != 1) return fail("somhip_find_winners: knn > 1 needs SOMHIP_TIE_KNN");
-  if (ds->d_mask && knn_rule) return fail("somhip_find_winners: k-NN with masked samples is not implemented");
   const int64_t CH = 4096;
   const int KK = knn == 1 ? 1 : knn == 2 ? 2 : knn <= 4 ? 4 : 8;
   void *dk;

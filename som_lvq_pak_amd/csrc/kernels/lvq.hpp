@@ -31,7 +31,15 @@ struct LvqStep {
     (k1) = hi_ < (k1) ? hi_ : (k1);                    \
   } while (0)
 
+//
+// MASKED (data with 'x' components): the distance skips the components the SAMPLE masks
+// (lvq_pak.c:179-186) and adapt_vector leaves them untouched (lvq_pak.c:343-347) -- a
+// select keeps the stored bits, so a -0.0 stays -0.0; the code row's own mask plays no
+// part (its stored value, 0.0, is used like any other).  Every sample of a masked run
+// has at least one live component (somhip_lvq_train refuses the run otherwise).
+template <bool MASKED>
 __global__ __launch_bounds__(256) void k_lvq_online_step(CbView cb, const float *__restrict__ rows,
+                                                         const uint8_t *__restrict__ mask,
                                                          const int32_t *__restrict__ clabels,
                                                          float *__restrict__ talpha,
                                                          int64_t prev_row, int64_t cur_row,
@@ -104,13 +112,15 @@ __global__ __launch_bounds__(256) void k_lvq_online_step(CbView cb, const float 
   const bool any_upd = __any(upd);
   const float *xp = rows + prev_row * cb.d;
   const float *xc = rows + cur_row * cb.d;
+  const uint8_t *mp = MASKED ? mask + prev_row * cb.d : nullptr;
+  const uint8_t *mc = MASKED ? mask + cur_row * cb.d : nullptr;
   const bool vec = (cb.d & 3) == 0;
   float acc = 0.0f;
   if (g < cb.ngroups && (any_upd || has_cur)) {
     // same pipelined, branch-free row stream as the SOM step (two register buffers per wave)
 #define LVQ_GO(UU, SS)                                                                                  \
-    acc = vec ? online_stream<UU, SS, false, true, 8>(cb, g, lane, upd, a, xp, xc, nullptr, nullptr)     \
-              : online_stream<UU, SS, false, false, 8>(cb, g, lane, upd, a, xp, xc, nullptr, nullptr)
+    acc = vec ? online_stream<UU, SS, MASKED, true, 8>(cb, g, lane, upd, a, xp, xc, mp, mc)              \
+              : online_stream<UU, SS, MASKED, false, 8>(cb, g, lane, upd, a, xp, xc, mp, mc)
     if (any_upd && has_cur) { LVQ_GO(true, true); }
     else if (has_cur) { LVQ_GO(false, true); }
     else { LVQ_GO(true, false); }

@@ -300,7 +300,10 @@ def randinit_from_bbox(lo, hi, cnt, xdim, ydim, seed):
 
 
 def find_winners(cb, ds, first=0, count=None, knn=1, tie=TIE_FIRST):
-    """WINNER_FUNCTION over data rows [first, first+count): (index, diff, ret)."""
+    """WINNER_FUNCTION over data rows [first, first+count): (index, diff, ret).
+
+    Masked data sets (Dataset(..., mask=...)) work for every knn (1..8): only the sample's mask counts
+    (lvq_pak.c:179-186); a sample with every component masked gives ret 0 and index -2."""
     count = ds.n if count is None else count
     idx = np.empty((count, knn), dtype=np.int32)
     diff = np.empty((count, knn), dtype=np.float32)
@@ -339,7 +342,10 @@ def som_auto_batch(lib, length, it, alpha=0.05, radius=128.0, n_units=65536, top
 
 def lvq_train(cb, ds, kind, length, alpha, alpha_type=ALPHA_LINEAR, winlen=0.0, epsilon=0.0,
               talpha=None, start_iter=0, count=None, data_first=None, trace=True):
-    """lvq1/olvq1/lvq2/lvq3_training (reference lvq_rout.c:498-916)."""
+    """lvq1/olvq1/lvq2/lvq3_training (reference lvq_rout.c:498-916).
+
+    A masked data set runs one launch per iteration (the sample's mask in distance and update,
+    lvq_pak.c:343-347); a run that visits a row with every component masked raises before training."""
     count = length - start_iter if count is None else count
     data_first = start_iter % ds.n if data_first is None else data_first
     knn = 2 if kind in (LVQ2, LVQ3) else 1

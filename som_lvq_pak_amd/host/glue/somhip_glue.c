@@ -448,9 +448,8 @@ static int lvq_segments(struct teach_params *teach, somhip_codebook *cb, somhip_
   return 0;
 }
 
-/* returns codes, NULL on an error, or (struct entries *)-1 when the data hold masked vectors (the LVQ loops of the engine
- * take none): the caller then runs the reference's loop -- only possible before anything was trained, i.e. without -buffer */
-#define LVQ_MASKED ((struct entries *)-1)
+/* returns codes, or NULL on an error.  Masked data vectors go to the engine with their masks (somhip_lvq_train runs them
+ * one launch per iteration and refuses a run that meets a vector with every component masked) */
 static struct entries *lvq_on_engine(struct teach_params *teach, int kind, float winlen, float epsilon, float *talpha, float clamp,
                                      const char *who)
 {
@@ -461,7 +460,6 @@ static struct entries *lvq_on_engine(struct teach_params *teach, int kind, float
   memset(&c, 0, sizeof c); memset(&x, 0, sizeof x);
   if (!buffered(data)) {
     if (!to_dense(data, &x)) { fprintf(stderr, "%s: can't get data\n", who); return NULL; }
-    if (x.any_mask) { free_dense(&x); return LVQ_MASKED; }
   }
   if (!to_dense(codes, &c)) { free_dense(&x); return NULL; }
   if (!engine_up(who)) goto done;
@@ -470,7 +468,7 @@ static struct entries *lvq_on_engine(struct teach_params *teach, int kind, float
     goto done;
   }
   if (!buffered(data)) {
-    if (somhip_dataset_create(eng, x.rows, x.n, x.dim, NULL, x.label, NULL, NULL, &ds)) { fprintf(stderr, "%s: %s\n", who, somhip_last_error()); goto done; }
+    if (somhip_dataset_create(eng, x.rows, x.n, x.dim, x.any_mask ? x.mask : NULL, x.label, NULL, NULL, &ds)) { fprintf(stderr, "%s: %s\n", who, somhip_last_error()); goto done; }
     if (lvq_segments(teach, cb, ds, &c, kind, winlen, epsilon, talpha, clamp, who, 0, teach->length, 0)) goto done;
   } else {                                             /* -buffer N: as in som_training above (lvq_rout.c:527-541 wraps the same way) */
     eptr p;
@@ -484,9 +482,8 @@ static struct entries *lvq_on_engine(struct teach_params *teach, int kind, float
         if (sample == NULL) { fprintf(stderr, "%s: couldn't rewind data (%ld/%ld iterations done)\n", who, it, teach->length); goto done; }
       }
       if (!chain_dense(data, &x, NULL)) goto done;
-      if (x.any_mask) { fprintf(stderr, "%s: masked data vectors with -buffer are not bound to the engine\n", who); goto done; }
       cnt = x.n < teach->length - it ? x.n : teach->length - it;
-      if (somhip_dataset_create(eng, x.rows, x.n, x.dim, NULL, x.label, NULL, NULL, &ds)) { fprintf(stderr, "%s: %s\n", who, somhip_last_error()); goto done; }
+      if (somhip_dataset_create(eng, x.rows, x.n, x.dim, x.any_mask ? x.mask : NULL, x.label, NULL, NULL, &ds)) { fprintf(stderr, "%s: %s\n", who, somhip_last_error()); goto done; }
       if (lvq_segments(teach, cb, ds, &c, kind, winlen, epsilon, talpha, clamp, who, it, cnt, 0)) goto done;
       somhip_dataset_destroy(ds); ds = NULL;
       free_dense(&x); memset(&x, 0, sizeof x);
@@ -519,21 +516,21 @@ done:
 struct entries *lvq1_training(struct teach_params *teach)
 {
   struct entries *ret;
-  if (hip_selected && (ret = lvq_on_engine(teach, SOMHIP_LVQ1, 0, 0, NULL, teach->alpha, "lvq1_training")) != LVQ_MASKED) return ret;
+  if (hip_selected) return lvq_on_engine(teach, SOMHIP_LVQ1, 0, 0, NULL, teach->alpha, "lvq1_training");
   WITH_CPU_ROW(teach, ref_lvq1_training(teach));
   return ret;
 }
 struct entries *lvq2_training(struct teach_params *teach, float winlen)
 {
   struct entries *ret;
-  if (hip_selected && (ret = lvq_on_engine(teach, SOMHIP_LVQ2, winlen, 0, NULL, teach->alpha, "lvq2_training")) != LVQ_MASKED) return ret;
+  if (hip_selected) return lvq_on_engine(teach, SOMHIP_LVQ2, winlen, 0, NULL, teach->alpha, "lvq2_training");
   WITH_CPU_ROW(teach, ref_lvq2_training(teach, winlen));
   return ret;
 }
 struct entries *lvq3_training(struct teach_params *teach, float epsilon, float winlen)
 {
   struct entries *ret;
-  if (hip_selected && (ret = lvq_on_engine(teach, SOMHIP_LVQ3, winlen, epsilon, NULL, teach->alpha, "lvq3_training")) != LVQ_MASKED) return ret;
+  if (hip_selected) return lvq_on_engine(teach, SOMHIP_LVQ3, winlen, epsilon, NULL, teach->alpha, "lvq3_training");
   WITH_CPU_ROW(teach, ref_lvq3_training(teach, epsilon, winlen));
   return ret;
 }
@@ -556,11 +553,6 @@ struct entries *olvq1_training(struct teach_params *teach, char *infile, char *o
     for (i = 0; i < noc; i++) talpha[i] = alpha;
   }
   ret = lvq_on_engine(teach, SOMHIP_OLVQ1, 0, 0, talpha, alpha, "olvq1_training");
-  if (ret == LVQ_MASKED) {                            /* nothing was trained: the reference's loop from the start */
-    ofree(talpha);
-    WITH_CPU_ROW(teach, ref_olvq1_training(teach, infile, outfile));
-    return ret;
-  }
   if (ret) alpha_write(talpha, noc, outfile);         /* :694 */
   ofree(talpha);
   return ret;

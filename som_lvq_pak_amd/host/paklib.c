@@ -1260,6 +1260,8 @@ int som_training_multi(struct teach_params *teach, int gpus, int (*after)(struct
   return pak_run_ranks(gpus, som_multi_rank, &m);
 }
 
+/* lvq*_training on one GPU.  Masked data go to the engine with their masks (one launch per iteration there); the
+ * codes keep their own masks for save_entries. */
 static struct entries *lvq_training(struct teach_params *teach, int kind, float winlen, float epsilon,
                                     float *talpha, const char *who)
 {
@@ -1592,7 +1594,9 @@ fail:
 }
 
 /* k nearest codes of every data row (find_winner_knn, lvq_pak.c:152-221; knn = 1 is
- * find_winner_euc): index/diff [n][knn], nearest first, ties in the reference's order. */
+ * find_winner_euc): index/diff [n][knn], nearest first, ties in the reference's order.
+ * Masked data rows (`x`) go to the GPU with their masks; the codes' own masks play no part
+ * (lvq_pak.c:179-186), and a row with every component masked gets index -2 (no neighbour). */
 int find_all_knn(struct entries *codes, struct entries *data, int knn, int32_t *index, float *diff)
 {
   if (knn < 1) knn = 1;
