@@ -16,7 +16,7 @@ static int lvq_cache_slots(int d4) {
   return (int)std::min<int64_t>(s, LVQ_BT);
 }
 
-// device buffers of one batch of the exact LVQ engine (engine scratch slots 17..27)
+// device buffers of one batch of the exact LVQ engine
 struct LvqBatchBufs {
   float *rho, *xnorm; uint32_t *adj; int32_t *comp_samples; LvqBatchOut *out;
   float4 *stage_rows; int32_t *stage_rowid; float *stage_ta;
@@ -24,16 +24,16 @@ struct LvqBatchBufs {
 };
 static int lvq_batch_bufs(somhip_engine *e, int d4, LvqBatchBufs *b) {
   void *p;
-  CHK(engine_scratch(e, 17, sizeof(float) * 2 * LVQ_BMAX + 16, &p)); b->rho = (float *)p; b->xnorm = b->rho + LVQ_BMAX; b->amax_dev = b->xnorm + LVQ_BMAX;
-  CHK(engine_scratch(e, 18, sizeof(uint32_t) * LVQ_BMAX * LVQ_AW, &p)); b->adj = (uint32_t *)p;
-  CHK(engine_scratch(e, 19, sizeof(int32_t) * LVQ_BMAX, &p)); b->comp_samples = (int32_t *)p;
-  CHK(engine_scratch(e, 20, sizeof(LvqBatchOut), &p)); b->out = (LvqBatchOut *)p;
-  CHK(engine_scratch(e, 21, sizeof(float4) * 2 * LVQ_BMAX * (size_t)d4, &p)); b->stage_rows = (float4 *)p;
-  CHK(engine_scratch(e, 22, sizeof(int32_t) * 2 * LVQ_BMAX, &p)); b->stage_rowid = (int32_t *)p;
-  CHK(engine_scratch(e, 23, sizeof(float) * 2 * LVQ_BMAX, &p)); b->stage_ta = (float *)p;
-  CHK(engine_scratch(e, 24, sizeof(int32_t) * LVQ_BMAX * LVQ_K0, &p)); b->cand_lab = (int32_t *)p;
-  CHK(engine_scratch(e, 25, sizeof(float) * LVQ_BMAX * LVQ_K0, &p)); b->cand_ta = (float *)p;
-  CHK(engine_scratch(e, 16, sizeof(int32_t) * (2 * LVQ_BMAX + 4), &p)); b->mod_rows = (int32_t *)p; b->mod_count = b->mod_rows + 2 * LVQ_BMAX;
+  CHK(engine_scratch(e, SLOT_LVQ_RHO, sizeof(float) * 2 * LVQ_BMAX + 16, &p)); b->rho = (float *)p; b->xnorm = b->rho + LVQ_BMAX; b->amax_dev = b->xnorm + LVQ_BMAX;
+  CHK(engine_scratch(e, SLOT_LVQ_ADJ, sizeof(uint32_t) * LVQ_BMAX * LVQ_AW, &p)); b->adj = (uint32_t *)p;
+  CHK(engine_scratch(e, SLOT_LVQ_COMP, sizeof(int32_t) * LVQ_BMAX, &p)); b->comp_samples = (int32_t *)p;
+  CHK(engine_scratch(e, SLOT_LVQ_OUT, sizeof(LvqBatchOut), &p)); b->out = (LvqBatchOut *)p;
+  CHK(engine_scratch(e, SLOT_LVQ_STAGE_ROWS, sizeof(float4) * 2 * LVQ_BMAX * (size_t)d4, &p)); b->stage_rows = (float4 *)p;
+  CHK(engine_scratch(e, SLOT_LVQ_STAGE_ROWID, sizeof(int32_t) * 2 * LVQ_BMAX, &p)); b->stage_rowid = (int32_t *)p;
+  CHK(engine_scratch(e, SLOT_LVQ_STAGE_TA, sizeof(float) * 2 * LVQ_BMAX, &p)); b->stage_ta = (float *)p;
+  CHK(engine_scratch(e, SLOT_LVQ_CAND_LAB, sizeof(int32_t) * LVQ_BMAX * LVQ_K0, &p)); b->cand_lab = (int32_t *)p;
+  CHK(engine_scratch(e, SLOT_LVQ_CAND_TA, sizeof(float) * LVQ_BMAX * LVQ_K0, &p)); b->cand_ta = (float *)p;
+  CHK(engine_scratch(e, SLOT_LVQ_MOD, sizeof(int32_t) * (2 * LVQ_BMAX + 4), &p)); b->mod_rows = (int32_t *)p; b->mod_count = b->mod_rows + 2 * LVQ_BMAX;
   return 0;
 }
 
@@ -215,10 +215,10 @@ static int lvq_train_batched(somhip_codebook *cb, somhip_dataset *ds, const somh
   const bool want_trace = trace_index || trace_diff;
   // no waiting only if the winners of the whole call fit a device buffer (they are read back at the end)
   const bool nowait = !getenv("SOMHIP_LVQ_SYNC") && !getenv("SOMHIP_LVQ_SERIAL") && (!want_trace || p->count <= (1ll << 22));
-  CHK(engine_scratch(e, 3, sizeof(uint64_t) * (size_t)BMAX * LVQ_K0, &dcand));
-  CHK(engine_scratch(e, 4, sizeof(LvqStep) * (size_t)BMAX, &dst));
-  CHK(engine_scratch(e, 13, sizeof(uint64_t) * 2 * (size_t)(nowait && want_trace ? std::max<int64_t>(p->count, BMAX) : BMAX), &dfin));   // (5..7, 11, 12 belong to the pre-filter)
-  CHK(engine_scratch(e, 28, sizeof(LvqCtl), &dctl_v));                 // (26, 27: the two-level pre-filter)
+  CHK(engine_scratch(e, SLOT_CALL_A, sizeof(uint64_t) * (size_t)BMAX * LVQ_K0, &dcand));
+  CHK(engine_scratch(e, SLOT_CALL_B, sizeof(LvqStep) * (size_t)BMAX, &dst));
+  CHK(engine_scratch(e, SLOT_LVQ_FINAL, sizeof(uint64_t) * 2 * (size_t)(nowait && want_trace ? std::max<int64_t>(p->count, BMAX) : BMAX), &dfin));
+  CHK(engine_scratch(e, SLOT_LVQ_CTL, sizeof(LvqCtl), &dctl_v));
   LvqCtl *dctl = (LvqCtl *)dctl_v;
   LvqBatchBufs b;
   CHK(lvq_batch_bufs(e, cb->v.d4, &b));
@@ -406,9 +406,9 @@ extern "C" int somhip_lvq_train(somhip_codebook *cb, somhip_dataset *ds, const s
   const int64_t CH = 4096;
   const int nblk = (int)((cb->v.ngroups + 3) / 4);
   void *dpart, *dfinal, *dst;
-  CHK(engine_scratch(e, 2, sizeof(uint64_t) * (size_t)nblk * 2 * 2, &dpart));
-  CHK(engine_scratch(e, 3, sizeof(uint64_t) * (size_t)(CH + 1) * 2, &dfinal));
-  CHK(engine_scratch(e, 4, sizeof(LvqStep) * (size_t)(CH + 1), &dst));
+  CHK(engine_scratch(e, SLOT_PARTIAL, sizeof(uint64_t) * (size_t)nblk * 2 * 2, &dpart));
+  CHK(engine_scratch(e, SLOT_CALL_A, sizeof(uint64_t) * (size_t)(CH + 1) * 2, &dfinal));
+  CHK(engine_scratch(e, SLOT_CALL_B, sizeof(LvqStep) * (size_t)(CH + 1), &dst));
   uint64_t *part[2] = {(uint64_t *)dpart, (uint64_t *)dpart + (size_t)nblk * 2};
   uint64_t *fin = (uint64_t *)dfinal;
   LvqStep *st = (LvqStep *)dst;
@@ -525,14 +525,12 @@ extern "C" int somhip_merge_topk_keys(somhip_engine *e, const uint64_t *dev_gath
   if (n_shards < 1 || count < 0) return fail("somhip_merge_topk_keys: bad shape");
   if (count == 0) return 0;
   HIPCHK(hipSetDevice(e->device));
-  const dim3 grid((unsigned)((count + 255) / 256));
-  if (knn == 1) hipLaunchKernelGGL(k_merge_shard_topk<1>, grid, dim3(256), 0, e->stream, dev_gathered, n_shards, count, dev_keys);
-  else if (knn == 2) hipLaunchKernelGGL(k_merge_shard_topk<2>, grid, dim3(256), 0, e->stream, dev_gathered, n_shards, count, dev_keys);
-  else if (knn == 4) hipLaunchKernelGGL(k_merge_shard_topk<4>, grid, dim3(256), 0, e->stream, dev_gathered, n_shards, count, dev_keys);
-  else if (knn == 8) hipLaunchKernelGGL(k_merge_shard_topk<8>, grid, dim3(256), 0, e->stream, dev_gathered, n_shards, count, dev_keys);
-  else return fail("somhip_merge_topk_keys: knn must be 1, 2, 4 or 8");
-  HIPCHK(hipGetLastError());
-  return 0;
+  return with_topk_width(knn, "somhip_merge_topk_keys", [&](auto k) {
+    hipLaunchKernelGGL(k_merge_shard_topk<decltype(k)::value>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, e->stream,
+                       dev_gathered, n_shards, count, dev_keys);
+    HIPCHK(hipGetLastError());
+    return 0;
+  });
 } ABI_CATCH(somhip_merge_topk_keys)
 
 extern "C" int somhip_lvq_batch_candidates(somhip_codebook *cb, int64_t count, int kind, const uint64_t *dev_keys, int xrows,
@@ -580,8 +578,8 @@ extern "C" int somhip_lvq_batch_apply(somhip_codebook *cb, somhip_dataset *ds, c
   const int knn = p->kind >= SOMHIP_LVQ2 ? 2 : 1;
   const bool olvq = p->kind == SOMHIP_OLVQ1;
   void *dst, *dfin;
-  CHK(engine_scratch(e, 4, sizeof(LvqStep) * (size_t)LVQ_BMAX, &dst));
-  CHK(engine_scratch(e, 13, sizeof(uint64_t) * (size_t)LVQ_BMAX * 2, &dfin));
+  CHK(engine_scratch(e, SLOT_CALL_B, sizeof(LvqStep) * (size_t)LVQ_BMAX, &dst));
+  CHK(engine_scratch(e, SLOT_LVQ_FINAL, sizeof(uint64_t) * (size_t)LVQ_BMAX * 2, &dfin));
   LvqBatchBufs b;
   CHK(lvq_batch_bufs(e, cb->v.d4, &b));
   std::vector<LvqStep> hst((size_t)count);

@@ -65,450 +65,459 @@ static void prefilter_err_l1(int d, double *prod, double *sq) {
   *sq = 2.0 * gam + u;
 }
 
-// MFMA pre-filter + exact re-rank (kernels.hpp K2/K2b/K2s/K2p/K2r)
-static int scan_keys_mfma(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count,
-                          int64_t nsb, uint64_t *d_keys, bool prefilter_only = false,
-                          float **out_wmin = nullptr, float **out_tau = nullptr, bool nonneg_keys = false, int kth = 1,
-                          int xphase = 0, float *xbound = nullptr) {
-  // xphase (shard exchange, kernels.hpp K2x): 0 = the whole search; 1 = up to level 1, xbound <- this shard's bound;
-  // 2 = level 2 under the bound in xbound (the MIN over the shards), xbound <- the tighter bound; 3 = the exact re-rank
-  // under the bound in xbound.  The phases of one search share the engine's scratch: nothing else may run on the
-  // engine between them.
-  somhip_engine *e = cb->e;
-  if (xphase == 0) e->xc_phase = 0;                       // a whole search takes the scratch of one that was under way
-  const int64_t bpad = nsb * SCAN_S;
-  const bool bf16 = e->scan_mode == SOMHIP_SCAN_MFMA_BF16;
-  const int d8 = (cb->v.d4 + 1) / 2;
-  if (!cb->d_cn) {
-    HIPCHK(hipMalloc((void **)&cb->d_cn, sizeof(float) * (size_t)cb->v.ngroups * WAVE));
-    HIPCHK(hipMalloc((void **)&cb->d_cnmax, sizeof(unsigned int)));
+// The route of a search, for every caller.  want: 1 = the nearest row, K (2, 4, 8) = the K nearest, 0 = bare pre-filter
+enum ScanRoute { ROUTE_MASKED, ROUTE_DIRECT, ROUTE_ONE_LEVEL, ROUTE_TWO_LEVEL };
+struct ScanPlan {
+  ScanRoute route;
+  int want, kth;       // kth: level 1's window above the smallest group minimum (1) or the LVQ_K0-th (k_group_kth)
+  bool bf16, l1_ring;  // split-bf16 GEMMs (else fp32 MFMA); level 1 by the persistent ring kernel
+  int64_t nsb, bpad;   // 32-sample tiles of the run, and the run padded to them
+  int d8;              // 8-dim bf16 K-steps of a row
+};
+static ScanPlan scan_plan(const somhip_codebook *cb, const somhip_dataset *ds, int64_t count, int want) {
+  const int64_t nsb = (count + SCAN_S - 1) / SCAN_S;
+  ScanPlan p = {ROUTE_DIRECT, want, 1, cb->e->scan_mode == SOMHIP_SCAN_MFMA_BF16, false, nsb, nsb * SCAN_S, (cb->v.d4 + 1) / 2};
+  const bool run_ok = count >= MFMA_MIN_SAMPLES && count <= (int64_t)PAIR_MAX_COLS * 32;   // longer runs: the direct scan
+  bool prefilter = cb->e->scan_mode != SOMHIP_SCAN_DIRECT;
+  if (want == 1) prefilter = prefilter && run_ok && cb->v.n >= 64;
+  else if (want > 1) {
+    // big codebooks: bf16 pre-filter + exact re-rank of the surviving row groups (kernels.hpp K2k)
+    prefilter = p.bf16 && run_ok && cb->v.n >= (getenv("SOMHIP_TOPK_MFMA") ? 64 : 4096);
+    // two levels pay on big codebooks (100 000 x 1024: 0.52 -> 0.43 ms per 1024 samples); on 10 000 rows the
+    // level-2 block costs more than the two products it saves (0.026 -> 0.049 ms)
+    if (prefilter && want == LVQ_K0 && cb->v.ngroups >= 512 && !getenv("SOMHIP_TOPK_ONE_LEVEL")) p.kth = LVQ_K0;
   }
-  if (bf16 && !cb->d_chi) {
-    HIPCHK(hipMalloc((void **)&cb->d_chi, sizeof(uint4) * (size_t)cb->v.ngroups * d8 * WAVE));
-    HIPCHK(hipMalloc((void **)&cb->d_clo, sizeof(uint4) * (size_t)cb->v.ngroups * d8 * WAVE));
-  }
-  void *dtau, *dwmin, *dwmask, *xt;
-  CHK(engine_scratch(e, 5, sizeof(float) * (size_t)bpad, &dtau));
-  CHK(engine_scratch(e, 6, sizeof(float) * (size_t)cb->v.ngroups * bpad, &dwmin));
-  CHK(engine_scratch(e, 7, sizeof(uint64_t) * (size_t)cb->v.ngroups * bpad, &dwmask));
-  // sample tiles: fp32 xt[sb][q][32][4], or bf16 hi | lo xt[sb][kb][32][8]
-  const size_t xt_bytes = bf16 ? 2 * sizeof(uint4) * (size_t)nsb * d8 * 32 : sizeof(float4) * (size_t)nsb * cb->v.d4 * SCAN_S;
-  CHK(engine_scratch(e, 1, xt_bytes, &xt));
-  uint4 *xhi = (uint4 *)xt, *xlo = xhi + (size_t)nsb * d8 * 32;
   // two-level form (K2c): bf16 mode, whole k-steps pairs, sample indices that fit 16 bits; behind it either the
   // re-rank of the nearest row (window above the smallest level-1 group minimum) or a top-K search (kth = K: window
   // above the K-th smallest -- a row of the true top K has level-1 value <= S_K + d1 <= (K-th smallest level-1 row
   // value) + 2 d1 <= (K-th smallest level-1 group minimum) + 2 d1; the groups left out keep their level-1 minimum,
   // which lies above S_K + d1 >= S_K + 3 d3: beyond the K-th smallest three-product minimum plus tau, so
-  // k_topk_select never takes them and its K-th smallest is formed from exact three-product values).  A bare
-  // pre-filter (somhip_debug_prefilter) wants every group's three-product minimum: one level.
-  const bool two_level = bf16 && (!prefilter_only || kth > 1) && (d8 % 4) == 0 && nsb >= 8 && bpad <= 65535;
-  // level 2 gathers single samples: it gets a sample-major copy of the same pieces
-  uint4 *xrow = nullptr;
-  if (two_level) {
-    void *pr;
-    CHK(engine_scratch(e, 31, xt_bytes, &pr));
-    xrow = (uint4 *)pr;
+  // k_topk_select never takes them and its K-th smallest is formed from exact three-product values).
+  if (ds->d_mask) p.route = ROUTE_MASKED;
+  else if (!prefilter) p.route = ROUTE_DIRECT;
+  else if (p.bf16 && (want == 1 || p.kth > 1) && (p.d8 % 4) == 0 && nsb >= 8 && p.bpad <= 65535) p.route = ROUTE_TWO_LEVEL;
+  else p.route = ROUTE_ONE_LEVEL;
+  // level 1 as the persistent ring kernel: the wide tile's shape (>= 512 row groups), an even number of 32-dim K-steps
+  // (a shard of a map has few row groups but the same long batches: the persistent kernel needs tiles, not rows -- at
+  // least one 256 x 256 tile per CU)
+  const int64_t l1_tiles = ((nsb + 7) / 8) * ((cb->v.ngroups + 3) / 4);
+  p.l1_ring = p.route == ROUTE_TWO_LEVEL && (cb->v.ngroups >= 512 || l1_tiles >= 256) && (p.d8 % 8) == 0;
+  return p;
+}
+// (32-sample columns) x (chunks of about `per` row groups, whole 8s, at most 64): the passes over the group minima
+// (chunks of 32 groups for k_l2_select, of 128 for k_rerank_select: profiles/r03_select_chunks.txt)
+static dim3 group_chunks(int64_t ngroups, int64_t bpad, int64_t per, int64_t *chunk) {
+  const int64_t nchunks = std::max<int64_t>(1, std::min<int64_t>(64, (ngroups + per - 1) / per));
+  *chunk = ((ngroups + nchunks - 1) / nchunks + 7) / 8 * 8;
+  return dim3((unsigned)(bpad / 32), (unsigned)((ngroups + *chunk - 1) / *chunk));
+}
+
+// MFMA pre-filter + exact re-rank (kernels.hpp K2/K2b/K2s/K2p/K2r/K2x) in stages over one binding of its buffers.
+// The calls of a shard exchange find the state of the calls before them there: nothing else may run between them.
+struct PrefilterBufs {
+  float *tau, *wmin; uint64_t *wmask;     // per-sample window; per (group, sample) minimum and candidate mask
+  void *xt; uint4 *xhi, *xlo, *xrow;      // tiles: fp32 xt[sb][q][32][4] or bf16 hi | lo [sb][kb][32][8]; xrow: sample-major
+  uint32_t *gmin, *gcount, *colcount, *paircount;            // re-rank counters (preset by k_sample_tau)
+  float *tau1; uint32_t *gmin1, *l2cnt; uint16_t *l2list;   // two levels: level 1's window and minimum, level 2's lists
+  float *xw;                              // shard exchange: delta1, max(delta1, 3 delta3), delta3 per sample
+};
+static int bind_prefilter(somhip_codebook *cb, const ScanPlan &p, bool exchange, PrefilterBufs *b) {
+  somhip_engine *e = cb->e;
+  const int64_t bpad = p.bpad, ng = cb->v.ngroups;
+  if (!cb->d_cn) {
+    HIPCHK(hipMalloc((void **)&cb->d_cn, sizeof(float) * (size_t)ng * WAVE));
+    HIPCHK(hipMalloc((void **)&cb->d_cnmax, sizeof(unsigned int)));
   }
-  if (xphase <= 1) {
+  if (p.bf16 && !cb->d_chi) {
+    HIPCHK(hipMalloc((void **)&cb->d_chi, sizeof(uint4) * (size_t)ng * p.d8 * WAVE));
+    HIPCHK(hipMalloc((void **)&cb->d_clo, sizeof(uint4) * (size_t)ng * p.d8 * WAVE));
+  }
+  *b = PrefilterBufs{};
+  void *q;
+  CHK(engine_scratch(e, SLOT_TAU, sizeof(float) * (size_t)bpad, &q)); b->tau = (float *)q;
+  CHK(engine_scratch(e, SLOT_WMIN, sizeof(float) * (size_t)ng * bpad, &q)); b->wmin = (float *)q;
+  CHK(engine_scratch(e, SLOT_WMASK, sizeof(uint64_t) * (size_t)ng * bpad, &q)); b->wmask = (uint64_t *)q;
+  const size_t xt_bytes = p.bf16 ? 2 * sizeof(uint4) * (size_t)p.nsb * p.d8 * 32 : sizeof(float4) * (size_t)p.nsb * cb->v.d4 * SCAN_S;
+  CHK(engine_scratch(e, SLOT_SAMPLES, xt_bytes, &b->xt));
+  b->xhi = (uint4 *)b->xt;
+  b->xlo = b->xhi + (size_t)p.nsb * p.d8 * 32;
+  CHK(engine_scratch(e, SLOT_RERANK_COUNT, sizeof(uint32_t) * (2 * (size_t)bpad + 4 * (size_t)(bpad / 32)), &q)); b->gmin = (uint32_t *)q;
+  b->gcount = b->gmin + bpad;
+  b->colcount = b->gcount + bpad;
+  b->paircount = reinterpret_cast<uint32_t *>(e->d_stats + 6);   // stays 0 unless a segment overflows
+  if (exchange) { CHK(engine_scratch(e, SLOT_XBOUND, sizeof(float) * 3 * (size_t)bpad, &q)); b->xw = (float *)q; }
+  if (p.route == ROUTE_TWO_LEVEL) {
+    CHK(engine_scratch(e, SLOT_SAMPLE_ROWS, xt_bytes, &q)); b->xrow = (uint4 *)q;
+    CHK(engine_scratch(e, SLOT_L2_STATE, sizeof(float) * (size_t)bpad + sizeof(uint32_t) * ((size_t)bpad + (size_t)ng), &q)); b->tau1 = (float *)q;
+    CHK(engine_scratch(e, SLOT_L2_LIST, sizeof(uint16_t) * (size_t)ng * bpad, &q)); b->l2list = (uint16_t *)q;
+    b->gmin1 = reinterpret_cast<uint32_t *>(b->tau1 + bpad);
+    b->l2cnt = b->gmin1 + bpad;
+  }
+  return 0;
+}
+// prepare: the sample tiles, the codebook's norms or bf16 split, the windows and the re-rank's presets (k_sample_tau).
+// d_keys: the nearest-row keys it presets (nullptr: top-K or bare pre-filter), as INT64_MAX under nonneg_keys (above
+// every real key, and what a signed MIN all-reduce needs -- saves somhip_batch_winner_keys a pass over the keys)
+static int pf_prepare(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count, const ScanPlan &p,
+                      const PrefilterBufs &b, uint64_t *d_keys, bool nonneg_keys) {
+  somhip_engine *e = cb->e;
+  const bool two = p.route == ROUTE_TWO_LEVEL;
+  const int d8 = p.d8;
+  {
     LaunchTimer t(e, KID_PACK_SAMPLES);
-    if (bf16)
-      hipLaunchKernelGGL(k_pack_samples_bf16, dim3((unsigned)nsb, (unsigned)(d8 >= 32 ? 8 : d8 >= 8 ? 2 : 1)), dim3(256), 0, e->stream, ds->d_rows, ds->n, ds->d,
-                         d8, first, count, xhi, xlo, cb->d_cnmax, xrow);
+    if (p.bf16)
+      hipLaunchKernelGGL(k_pack_samples_bf16, dim3((unsigned)p.nsb, (unsigned)(d8 >= 32 ? 8 : d8 >= 8 ? 2 : 1)), dim3(256), 0, e->stream, ds->d_rows, ds->n, ds->d,
+                         d8, first, count, b.xhi, b.xlo, cb->d_cnmax, b.xrow);
     else
-      hipLaunchKernelGGL(k_pack_samples<SCAN_S>, dim3((unsigned)nsb), dim3(256), 0, e->stream, ds->d_rows, ds->n,
-                         ds->d, cb->v.d4, first, count, (float4 *)xt);
+      hipLaunchKernelGGL(k_pack_samples<SCAN_S>, dim3((unsigned)p.nsb), dim3(256), 0, e->stream, ds->d_rows, ds->n,
+                         ds->d, cb->v.d4, first, count, (float4 *)b.xt);
   }
   HIPCHK(hipGetLastError());
   // the bf16 tiles and norms of an unchanged codebook are reused (read-only scans chunk by chunk; the LVQ engine
   // re-splits exactly the rows it corrected); every writer of the rows clears the flag
-  const bool prep_was_current = bf16 && cb->prep_valid;
-  if (!bf16 && xphase <= 1) HIPCHK(hipMemsetAsync(cb->d_cnmax, 0, sizeof(unsigned int), e->stream));   // (the bf16 pack kernel zeroes it)
-  // scratch of the re-rank, preset by k_sample_tau
-  const uint32_t ncols = (uint32_t)(bpad / 32);
-  void *dg;
-  CHK(engine_scratch(e, 12, sizeof(uint32_t) * (2 * (size_t)bpad + 4 * (size_t)ncols), &dg));
-  uint32_t *dgmin = (uint32_t *)dg, *dgcount = dgmin + bpad, *dcolcount = dgcount + bpad;
-  uint32_t *d_paircount = reinterpret_cast<uint32_t *>(e->d_stats + 6);   // stays 0 unless a segment overflows
-  // nonneg_keys: "no winner" is preset as INT64_MAX instead of all ones (still above every real key, and what a
-  // signed MIN all-reduce needs) -- saves somhip_batch_winner_keys a pass over the keys
-  RerankInit rinit = {prefilter_only ? nullptr : d_keys, dgmin, d_paircount, bpad, (int)ncols,
-                      nonneg_keys ? 0x7FFFFFFFFFFFFFFFull : KEY_NONE, nullptr, nullptr, 0};
-  // the per-sample minimum behind level 2 comes out of the level-2 kernel itself (an atomicMin per (group, sample) it
-  // covers) instead of a pass over the whole wmin matrix (k_group_min: 21 us per 32768 vectors and a launch)
-  const bool fused_gmin = two_level && !prefilter_only && !getenv("SOMHIP_NO_FUSED_GMIN");
-  if (xphase && !two_level) return fail("shard exchange: the two-level pre-filter does not run on this shape (somhip_shard_exchange_available)");
-  float *dtau1 = nullptr, *dxw = nullptr;
-  if (xphase) {
-    void *px;
-    CHK(engine_scratch(e, 14, sizeof(float) * 3 * (size_t)bpad, &px));
-    dxw = (float *)px;
-  }
-  const unsigned xgrid = (unsigned)((count + 255) / 256);
-  uint32_t *dgmin1 = nullptr, *dl2cnt = nullptr;
-  uint16_t *dl2list = nullptr;
-  if (two_level) {
-    void *p1, *p2;
-    CHK(engine_scratch(e, 26, sizeof(float) * (size_t)bpad + sizeof(uint32_t) * ((size_t)bpad + (size_t)cb->v.ngroups), &p1));
-    CHK(engine_scratch(e, 27, sizeof(uint16_t) * (size_t)cb->v.ngroups * bpad, &p2));
-    dtau1 = (float *)p1;
-    dgmin1 = reinterpret_cast<uint32_t *>(dtau1 + bpad);
-    dl2cnt = dgmin1 + bpad;
-    dl2list = (uint16_t *)p2;
-    rinit.l2_gmin1 = dgmin1; rinit.l2_cnt = dl2cnt; rinit.l2_ngroups = cb->v.ngroups;     // preset by k_sample_tau
-  }
+  const bool prep_was_current = p.bf16 && cb->prep_valid;
+  if (!p.bf16) HIPCHK(hipMemsetAsync(cb->d_cnmax, 0, sizeof(unsigned int), e->stream));   // (the bf16 pack kernel zeroes it)
+  const RerankInit rinit = {d_keys, b.gmin, b.paircount, p.bpad, (int)(p.bpad / 32), nonneg_keys ? 0x7FFFFFFFFFFFFFFFull : KEY_NONE,
+                            b.gmin1, b.l2cnt, two ? cb->v.ngroups : 0};
   double l1_prod = 0.0, l1_sq = 0.0, err_prod = 0.0, err_sq = 0.0;
   prefilter_err3(e, ds->d, &err_prod, &err_sq);
-  if (two_level) prefilter_err_l1(ds->d, &l1_prod, &l1_sq);
-  if (xphase <= 1) {
-    LaunchTimer t(e, KID_NORMS);
-    if (prep_was_current) {
-      // tiles and norms are current (unchanged codebook, or the LVQ engine re-split the rows it corrected): only the maximum is due
-      hipLaunchKernelGGL(k_max_norm, dim3(64), dim3(256), 0, e->stream, cb->v, (const float *)cb->d_cn, cb->d_cnmax);
-    } else if (bf16) {
-      // with the tiles a row-major copy of the rows for the exact re-rank of single rows (k_rerank_pairs), where that
-      // kernel will run behind this pre-filter on a long enough run (a shard of a map included)
-      // (the copy costs ~55 us at 65536 x 512 and saves 36 us of re-rank per 4096 vectors: from 8192 vectors per run on)
-      const bool want_rm = !prefilter_only && kth == 1 && (cb->v.d & 3) == 0 && cb->v.ngroups >= 64 && count >= 8192;
-      if (want_rm && !cb->d_rowmajor) HIPCHK(hipMalloc((void **)&cb->d_rowmajor, sizeof(float) * (size_t)cb->v.ngroups * WAVE * cb->v.d));
-      hipLaunchKernelGGL(k_prep_codes_bf16, dim3((unsigned)cb->v.ngroups), dim3(d8 >= 16 ? 1024 : d8 >= 4 ? 256 : 64), 0,
-                         e->stream, cb->v, d8, cb->d_cn, cb->d_cnmax, cb->d_chi, cb->d_clo, want_rm ? cb->d_rowmajor : (float *)nullptr);
-      cb->prep_valid = true;
-      cb->rowmajor_valid = want_rm;
-    } else
-      hipLaunchKernelGGL(k_row_norms, dim3((unsigned)((cb->v.ngroups + 3) / 4)), dim3(256), 0, e->stream,
-                         cb->v, cb->d_cn, cb->d_cnmax);
-    hipLaunchKernelGGL(k_sample_tau, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, e->stream,
-                       ds->d_rows, ds->n, ds->d, first, count, (const unsigned int *)cb->d_cnmax,
-                       err_prod, err_sq, (float *)dtau, rinit, l1_prod, l1_sq, dtau1, dxw);
-  }
+  if (two) prefilter_err_l1(ds->d, &l1_prod, &l1_sq);
+  LaunchTimer t(e, KID_NORMS);
+  if (prep_was_current) {
+    // tiles and norms are current (unchanged codebook, or the LVQ engine re-split the rows it corrected): only the maximum is due
+    hipLaunchKernelGGL(k_max_norm, dim3(64), dim3(256), 0, e->stream, cb->v, (const float *)cb->d_cn, cb->d_cnmax);
+  } else if (p.bf16) {
+    // with the tiles a row-major copy of the rows for the exact re-rank of single rows (k_rerank_pairs), where that
+    // kernel will run behind this pre-filter on a long enough run (a shard of a map included)
+    // (the copy costs ~55 us at 65536 x 512 and saves 36 us of re-rank per 4096 vectors: from 8192 vectors per run on)
+    const bool want_rm = p.want == 1 && (cb->v.d & 3) == 0 && cb->v.ngroups >= 64 && count >= 8192;
+    if (want_rm && !cb->d_rowmajor) HIPCHK(hipMalloc((void **)&cb->d_rowmajor, sizeof(float) * (size_t)cb->v.ngroups * WAVE * cb->v.d));
+    hipLaunchKernelGGL(k_prep_codes_bf16, dim3((unsigned)cb->v.ngroups), dim3(d8 >= 16 ? 1024 : d8 >= 4 ? 256 : 64), 0,
+                       e->stream, cb->v, d8, cb->d_cn, cb->d_cnmax, cb->d_chi, cb->d_clo, want_rm ? cb->d_rowmajor : (float *)nullptr);
+    cb->prep_valid = true;
+    cb->rowmajor_valid = want_rm;
+  } else
+    hipLaunchKernelGGL(k_row_norms, dim3((unsigned)((cb->v.ngroups + 3) / 4)), dim3(256), 0, e->stream,
+                       cb->v, cb->d_cn, cb->d_cnmax);
+  hipLaunchKernelGGL(k_sample_tau, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, e->stream,
+                     ds->d_rows, ds->n, ds->d, first, count, (const unsigned int *)cb->d_cnmax,
+                     err_prod, err_sq, b.tau, rinit, l1_prod, l1_sq, b.tau1, b.xw);
   HIPCHK(hipGetLastError());
-  if (two_level) {
-    // (chunks of 32 groups for k_l2_select, of 128 for k_rerank_select: profiles/r03_select_chunks.txt)
-    const int64_t nchunks = std::max<int64_t>(1, std::min<int64_t>(64, (cb->v.ngroups + 31) / 32));
-    const int64_t chunk = ((cb->v.ngroups + nchunks - 1) / nchunks + 7) / 8 * 8;
-    const dim3 sgrid((unsigned)(bpad / 32), (unsigned)((cb->v.ngroups + chunk - 1) / chunk));
-    // level 1 as the persistent ring kernel: the wide tile's shape (>= 512 row groups), an even number of 32-dim K-steps; its epilogue also gives the per-sample minimum unless a top-K window is wanted
-    // (a shard of a map has few row groups but the same long batches: the persistent kernel needs tiles, not rows -- at
-    // least one 256 x 256 tile per CU)
-    const int64_t l1_tiles = ((nsb + 7) / 8) * ((cb->v.ngroups + 3) / 4);
-    const bool l1_ring = (cb->v.ngroups >= 512 || l1_tiles >= 256) && (d8 % 8) == 0;
-    const bool l1_ring_gmin = l1_ring && kth != LVQ_K0;
-    if (xphase <= 1) {
-      LaunchTimer t(e, KID_DIST_MFMA_BF16);
-      if (cb->v.ngroups >= 512 || l1_ring) {        // 256 x 256 tile: a third less L2 -> LDS traffic per MFMA
-        dim3 gridw((unsigned)((nsb + 7) / 8), (unsigned)((cb->v.ngroups + 3) / 4));
-        if (l1_ring) {
-          // persistent form over an LDS ring (kernels/prefilter_l1_ring.hpp): one workgroup per CU, a multiple of 8 of them
-          if (!e->l1r_attr_set) {
-            HIPCHK(hipFuncSetAttribute((const void *)k_dist_mfma_bf16_l1r, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L1R_LDS_BYTES));
-            e->l1r_attr_set = true;
-          }
-          if (!e->n_cus) {
-            int v = 0;
-            HIPCHK(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, e->device));
-            e->n_cus = v > 0 ? v : 256;
-          }
-          int nwg = e->n_cus >= 8 ? e->n_cus / 8 * 8 : e->n_cus;
-          const int64_t ntiles = (int64_t)gridw.x * gridw.y;
-          if (ntiles < nwg) nwg = (int)ntiles;
-          hipLaunchKernelGGL(k_dist_mfma_bf16_l1r, dim3((unsigned)nwg), dim3(512), L1R_LDS_BYTES, e->stream, cb->v, d8, (const uint4 *)cb->d_chi,
-                             (const uint4 *)xhi, (const float *)cb->d_cn, bpad, (float *)dwmin, l1_ring_gmin ? dgmin1 : (uint32_t *)nullptr,
-                             (int)gridw.x, (int)gridw.y);
-        } else
-          hipLaunchKernelGGL((k_dist_mfma_bf16_l1w16<4>), dim3(gridw.x * gridw.y), dim3(512), 0, e->stream, cb->v, d8, (const uint4 *)cb->d_chi,
-                             (const uint4 *)xhi, (const float *)cb->d_cn, bpad, (float *)dwmin, (int)gridw.x, (int)gridw.y);
-      } else {
-        dim3 gridw((unsigned)((nsb + 7) / 8), (unsigned)((cb->v.ngroups + 1) / 2));
-        hipLaunchKernelGGL((k_dist_mfma_bf16_l1<4>), gridw, dim3(256), 0, e->stream, cb->v, d8, (const uint4 *)cb->d_chi,
-                           (const uint4 *)xhi, (const float *)cb->d_cn, bpad, (float *)dwmin);
-      }
-    }
-    if (xphase <= 1) {
-      LaunchTimer t(e, KID_DIST_L2);
-      if (kth == LVQ_K0)
-        hipLaunchKernelGGL(k_group_kth<LVQ_K0>, dim3((unsigned)(bpad / 32)), dim3(1024), 0, e->stream, cb->v.ngroups, bpad,
-                           (const float *)dwmin, dgmin1);
-      else if (!l1_ring_gmin)                            // (the ring kernel's epilogue has folded the minima into dgmin1 itself)
-        hipLaunchKernelGGL(k_group_min, sgrid, dim3(256), 0, e->stream, cb->v.ngroups, bpad, chunk, (const float *)dwmin, dgmin1);
-      if (xphase == 1) {                                 // bound = smallest level-1 value + delta1
-        hipLaunchKernelGGL(k_shard_bound, dim3(xgrid), dim3(256), 0, e->stream, count, (const uint32_t *)dgmin1, (const float *)dxw, xbound);
-        HIPCHK(hipGetLastError());
-        return 0;
-      }
-    }
-    if (xphase == 0 || xphase == 2) {
-      {
-      LaunchTimer t(e, KID_L2_SELECT);
-      // xphase 2: the exchanged bound for the shard's own minimum, max(delta1, 3 delta3) for the window
-      hipLaunchKernelGGL(k_l2_select, dim3((unsigned)((bpad + 255) / 256), sgrid.y), dim3(256), 0, e->stream, cb->v.ngroups, count, bpad, chunk,
-                         (const float *)dwmin, (const uint32_t *)dgmin1, xphase == 2 ? (const float *)(dxw + bpad) : (const float *)dtau1,
-                         dl2cnt, dl2list, xphase == 2 ? (float *)dwmin : (float *)nullptr, xphase == 2 ? (const float *)xbound : (const float *)nullptr);
-      }
-      LaunchTimer t(e, KID_DIST_L2);
-      const bool l2_global = getenv("SOMHIP_L2_GLOBAL") != nullptr;    // operand A from global memory for every tile (k_dist_l2)
-      uint32_t *l2_gmin = fused_gmin ? dgmin : nullptr;
-      if (d8 <= 64 && !l2_global) {
-        const size_t a_bytes = sizeof(uint4) * 2 * (size_t)d8 * 64;
-        if (!e->l2_lds_attr_set) {
-          HIPCHK(hipFuncSetAttribute((const void *)k_dist_l2_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-          e->l2_lds_attr_set = true;
+  return 0;
+}
+// level 1 (K2c): one bf16 product per (group, sample); per sample the smallest group minimum (k_group_min or the ring
+// kernel's epilogue) or the K-th smallest (k_group_kth).  xbound (shard exchange) <- smallest level-1 value + delta1.
+static int pf_level1(somhip_codebook *cb, int64_t count, const ScanPlan &p, const PrefilterBufs &b, float *xbound) {
+  somhip_engine *e = cb->e;
+  const int64_t ng = cb->v.ngroups, nsb = p.nsb;
+  const bool l1_ring_gmin = p.l1_ring && p.kth != LVQ_K0;
+  {
+    LaunchTimer t(e, KID_DIST_MFMA_BF16);
+    if (ng >= 512 || p.l1_ring) {        // 256 x 256 tile: a third less L2 -> LDS traffic per MFMA
+      dim3 gridw((unsigned)((nsb + 7) / 8), (unsigned)((ng + 3) / 4));
+      if (p.l1_ring) {
+        // persistent form over an LDS ring (kernels/prefilter_l1_ring.hpp): one workgroup per CU, a multiple of 8 of them
+        if (!e->l1r_attr_set) {
+          HIPCHK(hipFuncSetAttribute((const void *)k_dist_mfma_bf16_l1r, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L1R_LDS_BYTES));
+          e->l1r_attr_set = true;
         }
-        hipLaunchKernelGGL(k_dist_l2_lds, dim3((unsigned)cb->v.ngroups, 4), dim3(64 * L2_WAVES), a_bytes, e->stream, cb->v, d8, (const uint4 *)cb->d_chi,
-                           (const uint4 *)cb->d_clo, (const uint4 *)xrow, (const float *)cb->d_cn,
-                           (const float *)dtau, bpad, (const uint32_t *)dl2cnt, (const uint16_t *)dl2list, (float *)dwmin,
-                           (uint64_t *)dwmask, e->d_stats + 8 + 128 + 8, l2_gmin);
+        if (!e->n_cus) {
+          int v = 0;
+          HIPCHK(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, e->device));
+          e->n_cus = v > 0 ? v : 256;
+        }
+        int nwg = e->n_cus >= 8 ? e->n_cus / 8 * 8 : e->n_cus;
+        const int64_t ntiles = (int64_t)gridw.x * gridw.y;
+        if (ntiles < nwg) nwg = (int)ntiles;
+        hipLaunchKernelGGL(k_dist_mfma_bf16_l1r, dim3((unsigned)nwg), dim3(512), L1R_LDS_BYTES, e->stream, cb->v, p.d8, (const uint4 *)cb->d_chi,
+                           (const uint4 *)b.xhi, (const float *)cb->d_cn, p.bpad, b.wmin, l1_ring_gmin ? b.gmin1 : (uint32_t *)nullptr,
+                           (int)gridw.x, (int)gridw.y);
       } else
-        hipLaunchKernelGGL(k_dist_l2, dim3((unsigned)cb->v.ngroups, 8), dim3(256), 0, e->stream, cb->v, d8, (const uint4 *)cb->d_chi,
-                           (const uint4 *)cb->d_clo, (const uint4 *)xhi, (const uint4 *)xlo, (const float *)cb->d_cn,
-                           (const float *)dtau, bpad, (const uint32_t *)dl2cnt, (const uint16_t *)dl2list, (float *)dwmin,
-                           (uint64_t *)dwmask, e->d_stats + 8 + 128 + 8, (const uint4 *)xrow, l2_gmin);
+        hipLaunchKernelGGL((k_dist_mfma_bf16_l1w16<4>), dim3(gridw.x * gridw.y), dim3(512), 0, e->stream, cb->v, p.d8, (const uint4 *)cb->d_chi,
+                           (const uint4 *)b.xhi, (const float *)cb->d_cn, p.bpad, b.wmin, (int)gridw.x, (int)gridw.y);
+    } else {
+      dim3 gridw((unsigned)((nsb + 7) / 8), (unsigned)((ng + 1) / 2));
+      hipLaunchKernelGGL((k_dist_mfma_bf16_l1<4>), gridw, dim3(256), 0, e->stream, cb->v, p.d8, (const uint4 *)cb->d_chi,
+                         (const uint4 *)b.xhi, (const float *)cb->d_cn, p.bpad, b.wmin);
     }
-    HIPCHK(hipGetLastError());
-    if (xphase == 2) {                                   // bound = smallest three-product value among the kept groups + delta3
-      LaunchTimer t(e, KID_RERANK_SELECT);
-      if (!fused_gmin) hipLaunchKernelGGL(k_group_min, sgrid, dim3(256), 0, e->stream, cb->v.ngroups, bpad, chunk, (const float *)dwmin, dgmin);
-      hipLaunchKernelGGL(k_shard_bound, dim3(xgrid), dim3(256), 0, e->stream, count, (const uint32_t *)dgmin, (const float *)(dxw + 2 * bpad), xbound);
-      HIPCHK(hipGetLastError());
-      return 0;
-    }
-  } else {
-    LaunchTimer t(e, bf16 ? KID_DIST_MFMA_BF16 : KID_DIST_MFMA);
-    dim3 grid((unsigned)((nsb + 3) / 4), (unsigned)((cb->v.ngroups + 1) / 2));
-    if (bf16 && (d8 % 2) == 0 && nsb >= 8) {
-      dim3 gridw((unsigned)((nsb + 7) / 8), (unsigned)((cb->v.ngroups + 1) / 2));
-      hipLaunchKernelGGL((k_dist_mfma_bf16_wide<2>), gridw, dim3(256), 0, e->stream, cb->v, d8,
-                         (const uint4 *)cb->d_chi, (const uint4 *)cb->d_clo, (const uint4 *)xhi, (const uint4 *)xlo,
-                         (const float *)cb->d_cn, (const float *)dtau, count, bpad, (float *)dwmin, (uint64_t *)dwmask);
-    } else if (bf16 && (d8 % 4) == 0)
-      hipLaunchKernelGGL((k_dist_mfma_bf16_dma<4, 2>), grid, dim3(256), 0, e->stream, cb->v, d8,
-                         (const uint4 *)cb->d_chi, (const uint4 *)cb->d_clo, (const uint4 *)xhi, (const uint4 *)xlo,
-                         (const float *)cb->d_cn, (const float *)dtau, count, bpad, (float *)dwmin, (uint64_t *)dwmask);
-    else if (bf16)
-      hipLaunchKernelGGL(k_dist_mfma_bf16, grid, dim3(256), 0, e->stream, cb->v, d8, (const uint4 *)cb->d_chi,
-                         (const uint4 *)cb->d_clo, (const uint4 *)xhi, (const uint4 *)xlo, (const float *)cb->d_cn,
-                         (const float *)dtau, count, bpad, (float *)dwmin, (uint64_t *)dwmask);
-    else
-      hipLaunchKernelGGL(k_dist_mfma, grid, dim3(256), 0, e->stream, cb->v, (const float4 *)xt, (const float *)cb->d_cn,
-                         (const float *)dtau, count, bpad, (float *)dwmin, (uint64_t *)dwmask);
+  }
+  LaunchTimer t(e, KID_DIST_L2);
+  int64_t chunk;
+  const dim3 sgrid = group_chunks(ng, p.bpad, 32, &chunk);
+  if (p.kth == LVQ_K0)
+    hipLaunchKernelGGL(k_group_kth<LVQ_K0>, dim3((unsigned)(p.bpad / 32)), dim3(1024), 0, e->stream, ng, p.bpad,
+                       (const float *)b.wmin, b.gmin1);
+  else if (!l1_ring_gmin)                            // (the ring kernel's epilogue has folded the minima into gmin1 itself)
+    hipLaunchKernelGGL(k_group_min, sgrid, dim3(256), 0, e->stream, ng, p.bpad, chunk, (const float *)b.wmin, b.gmin1);
+  if (xbound)
+    hipLaunchKernelGGL(k_shard_bound, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, e->stream, count, (const uint32_t *)b.gmin1, (const float *)b.xw, xbound);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+// level 2 (K2c): the three-product split for the groups level 1 keeps.  fused_gmin: the per-sample minimum behind it
+// comes out of the level-2 kernel itself (an atomicMin per (group, sample) it covers) instead of a pass over the whole
+// wmin matrix (k_group_min: 21 us per 32768 vectors and a launch).  xbound (shard exchange): in, the MIN of the
+// shards' level-1 bounds (window max(delta1, 3 delta3)); out, the smallest kept three-product value + delta3.
+static int pf_level2(somhip_codebook *cb, int64_t count, const ScanPlan &p, const PrefilterBufs &b, bool fused_gmin, float *xbound) {
+  somhip_engine *e = cb->e;
+  const int64_t ng = cb->v.ngroups, bpad = p.bpad;
+  const int d8 = p.d8;
+  int64_t chunk;
+  const dim3 sgrid = group_chunks(ng, bpad, 32, &chunk);
+  {
+    LaunchTimer t(e, KID_L2_SELECT);
+    hipLaunchKernelGGL(k_l2_select, dim3((unsigned)((bpad + 255) / 256), sgrid.y), dim3(256), 0, e->stream, ng, count, bpad, chunk,
+                       (const float *)b.wmin, (const uint32_t *)b.gmin1, xbound ? (const float *)(b.xw + bpad) : (const float *)b.tau1,
+                       b.l2cnt, b.l2list, xbound ? b.wmin : (float *)nullptr, (const float *)xbound);
+  }
+  {
+    LaunchTimer t(e, KID_DIST_L2);
+    const bool l2_global = getenv("SOMHIP_L2_GLOBAL") != nullptr;    // operand A from global memory for every tile (k_dist_l2)
+    uint32_t *l2_gmin = fused_gmin ? b.gmin : nullptr;
+    if (d8 <= 64 && !l2_global) {
+      const size_t a_bytes = sizeof(uint4) * 2 * (size_t)d8 * 64;
+      if (!e->l2_lds_attr_set) {
+        HIPCHK(hipFuncSetAttribute((const void *)k_dist_l2_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+        e->l2_lds_attr_set = true;
+      }
+      hipLaunchKernelGGL(k_dist_l2_lds, dim3((unsigned)ng, 4), dim3(64 * L2_WAVES), a_bytes, e->stream, cb->v, d8, (const uint4 *)cb->d_chi,
+                         (const uint4 *)cb->d_clo, (const uint4 *)b.xrow, (const float *)cb->d_cn,
+                         (const float *)b.tau, bpad, (const uint32_t *)b.l2cnt, (const uint16_t *)b.l2list, b.wmin,
+                         b.wmask, e->d_stats + 8 + 128 + 8, l2_gmin);
+    } else
+      hipLaunchKernelGGL(k_dist_l2, dim3((unsigned)ng, 8), dim3(256), 0, e->stream, cb->v, d8, (const uint4 *)cb->d_chi,
+                         (const uint4 *)cb->d_clo, (const uint4 *)b.xhi, (const uint4 *)b.xlo, (const float *)cb->d_cn,
+                         (const float *)b.tau, bpad, (const uint32_t *)b.l2cnt, (const uint16_t *)b.l2list, b.wmin,
+                         b.wmask, e->d_stats + 8 + 128 + 8, (const uint4 *)b.xrow, l2_gmin);
   }
   HIPCHK(hipGetLastError());
-  if (prefilter_only) { *out_wmin = (float *)dwmin; *out_tau = (float *)dtau; return 0; }
-  // exact re-rank: row-granular pair path for the usual few candidates, group-granular
-  // k_rerank for flagged samples (too many candidates / list full)
-  // pair list: one segment per 32-sample column
-  if (ncols > (uint32_t)PAIR_MAX_COLS) return fail("winner search: more than %d samples in one run", PAIR_MAX_COLS * 32);
+  if (xbound) {
+    LaunchTimer t(e, KID_RERANK_SELECT);
+    if (!fused_gmin) hipLaunchKernelGGL(k_group_min, sgrid, dim3(256), 0, e->stream, ng, bpad, chunk, (const float *)b.wmin, b.gmin);
+    hipLaunchKernelGGL(k_shard_bound, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, e->stream, count, (const uint32_t *)b.gmin, (const float *)(b.xw + 2 * bpad), xbound);
+    HIPCHK(hipGetLastError());
+  }
+  return 0;
+}
+// one level: the distance GEMM of every (group, sample), fp32 or three-product bf16
+static int pf_one_level(somhip_codebook *cb, int64_t count, const ScanPlan &p, const PrefilterBufs &b) {
+  somhip_engine *e = cb->e;
+  const int64_t nsb = p.nsb, ng = cb->v.ngroups;
+  LaunchTimer t(e, p.bf16 ? KID_DIST_MFMA_BF16 : KID_DIST_MFMA);
+  dim3 grid((unsigned)((nsb + 3) / 4), (unsigned)((ng + 1) / 2));
+  if (p.bf16) {
+    const bool wide = (p.d8 % 2) == 0 && nsb >= 8;
+    if (wide) grid = dim3((unsigned)((nsb + 7) / 8), (unsigned)((ng + 1) / 2));
+    auto kern = wide ? k_dist_mfma_bf16_wide<2> : (p.d8 % 4) == 0 ? k_dist_mfma_bf16_dma<4, 2> : k_dist_mfma_bf16;
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, e->stream, cb->v, p.d8, (const uint4 *)cb->d_chi, (const uint4 *)cb->d_clo,
+                       (const uint4 *)b.xhi, (const uint4 *)b.xlo, (const float *)cb->d_cn, (const float *)b.tau, count, p.bpad, b.wmin, b.wmask);
+  } else
+    hipLaunchKernelGGL(k_dist_mfma, grid, dim3(256), 0, e->stream, cb->v, (const float4 *)b.xt, (const float *)cb->d_cn,
+                       (const float *)b.tau, count, p.bpad, b.wmin, b.wmask);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+// the pre-filter of a whole search: prepare -> level 1 -> level 2, or prepare -> one level
+static int pf_filter(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count, const ScanPlan &p,
+                     PrefilterBufs *b, uint64_t *d_keys, bool nonneg_keys, bool fused_gmin) {
+  cb->e->xc_phase = XC_NONE;                       // a whole search takes the scratch of an exchanged one under way
+  CHK(bind_prefilter(cb, p, false, b));
+  CHK(pf_prepare(cb, ds, first, count, p, *b, d_keys, nonneg_keys));
+  if (p.route == ROUTE_ONE_LEVEL) return pf_one_level(cb, count, p, *b);
+  CHK(pf_level1(cb, count, p, *b, nullptr));
+  return pf_level2(cb, count, p, *b, fused_gmin, nullptr);
+}
+// the nearest-row re-rank: row-granular pairs for the usual few candidates (a segment per 32-sample column), k_rerank
+// for flagged samples.  gmin_ready: the per-sample minimum is formed (else k_group_min).  xbound (shard exchange): the
+// rows of the groups whose three-product minimum is <= (MIN over the shards of their bounds) + delta3.
+static int pf_rerank(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count, const ScanPlan &p,
+                     const PrefilterBufs &b, uint64_t *d_keys, bool gmin_ready, const float *xbound) {
+  somhip_engine *e = cb->e;
+  const int64_t ng = cb->v.ngroups, bpad = p.bpad;
+  const uint32_t ncols = (uint32_t)(bpad / 32);
   const uint32_t cap_col = 16384;   // 512 per sample on average; a full segment -> K2r
   const uint32_t cap = (uint32_t)std::min<int64_t>((int64_t)ncols * cap_col, 0x7FFFFFF0);
   void *dpairs;
-  CHK(engine_scratch(e, 11, sizeof(uint2) * (size_t)ncols * cap_col + 16, &dpairs));
+  CHK(engine_scratch(e, SLOT_PAIRS, sizeof(uint2) * (size_t)ncols * cap_col + 16, &dpairs));
   {
-    // global minimum of the group minima per sample, then the candidate pairs; both over a grid of
-    // (32-sample columns) x (chunks of row groups)
-    const int64_t nchunks = std::max<int64_t>(1, std::min<int64_t>(64, (cb->v.ngroups + 127) / 128));
-    const int64_t chunk = ((cb->v.ngroups + nchunks - 1) / nchunks + 7) / 8 * 8;
-    const dim3 sgrid((unsigned)(bpad / 32), (unsigned)((cb->v.ngroups + chunk - 1) / chunk));
+    int64_t chunk;
+    const dim3 sgrid = group_chunks(ng, bpad, 128, &chunk);
     LaunchTimer t(e, KID_RERANK_SELECT);
-    // shard exchange: rows of the groups whose three-product minimum is <= (MIN over the shards of their bounds) + delta3
-    if (xphase != 3 && !fused_gmin)
-      hipLaunchKernelGGL(k_group_min, sgrid, dim3(256), 0, e->stream, cb->v.ngroups, bpad, chunk, (const float *)dwmin, dgmin);
+    if (!gmin_ready)
+      hipLaunchKernelGGL(k_group_min, sgrid, dim3(256), 0, e->stream, ng, bpad, chunk, (const float *)b.wmin, b.gmin);
     hipLaunchKernelGGL(k_rerank_select, sgrid, dim3(256), 0, e->stream, cb->v, count, bpad, chunk,
-                       (const float *)dwmin, (const uint64_t *)dwmask, xphase == 3 ? (const float *)(dxw + 2 * bpad) : (const float *)dtau, (const uint32_t *)dgmin,
-                       dgcount, cap, cap_col, (uint2 *)dpairs, dcolcount, d_paircount, e->d_stats,
-                       xphase == 3 ? (const float *)xbound : (const float *)nullptr);
+                       (const float *)b.wmin, (const uint64_t *)b.wmask, xbound ? (const float *)(b.xw + 2 * bpad) : (const float *)b.tau,
+                       (const uint32_t *)b.gmin, b.gcount, cap, cap_col, (uint2 *)dpairs, b.colcount, b.paircount, e->d_stats, xbound);
   }
   {
     LaunchTimer t(e, KID_RERANK_PAIRS);
     hipLaunchKernelGGL(k_rerank_pairs, dim3(4096), dim3(256), 0, e->stream, cb->v, ds->d_rows,
-                       ds->n, first, cap, cap_col, (int)ncols, (const uint2 *)dpairs, (const uint32_t *)dcolcount,
-                       (const uint32_t *)d_paircount, d_keys, e->d_stats,
-                       bf16 && cb->prep_valid && cb->rowmajor_valid ? (const float *)cb->d_rowmajor : (const float *)nullptr);
+                       ds->n, first, cap, cap_col, (int)ncols, (const uint2 *)dpairs, (const uint32_t *)b.colcount,
+                       (const uint32_t *)b.paircount, d_keys, e->d_stats,
+                       p.bf16 && cb->prep_valid && cb->rowmajor_valid ? (const float *)cb->d_rowmajor : (const float *)nullptr);
   }
+  LaunchTimer t(e, KID_RERANK);
+  hipLaunchKernelGGL(k_rerank, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, e->stream, cb->v,
+                     ds->d_rows, ds->n, first, count, bpad, (const float *)b.wmin,
+                     (const uint64_t *)b.wmask, (const float *)b.tau, (const uint32_t *)b.paircount, cap, d_keys,
+                     e->d_stats);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+// the direct scan (K1): packed sample tiles against every row group; keys (top-1) or per-block top-K lists in part
+template <int K>
+static int scan_exact(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count, const ScanPlan &p,
+                      int tie_knn, uint64_t *keys, uint64_t *part) {
+  somhip_engine *e = cb->e;
+  void *xt;
+  CHK(engine_scratch(e, SLOT_SAMPLES, sizeof(float4) * (size_t)p.nsb * cb->v.d4 * SCAN_S, &xt));
   {
-    LaunchTimer t(e, KID_RERANK);
-    hipLaunchKernelGGL(k_rerank, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, e->stream, cb->v,
-                       ds->d_rows, ds->n, first, count, bpad, (const float *)dwmin,
-                       (const uint64_t *)dwmask, (const float *)dtau, (const uint32_t *)d_paircount, cap, d_keys,
-                       e->d_stats);
+    LaunchTimer t(e, KID_PACK_SAMPLES);
+    hipLaunchKernelGGL(k_pack_samples<SCAN_S>, dim3((unsigned)p.nsb), dim3(256), 0, e->stream,
+                       ds->d_rows, ds->n, ds->d, cb->v.d4, first, count, (float4 *)xt);
+  }
+  HIPCHK(hipGetLastError());
+  LaunchTimer t(e, KID_SCAN_EXACT);
+  dim3 grid((unsigned)p.nsb, (unsigned)((cb->v.ngroups + 3) / 4));
+  hipLaunchKernelGGL((k_scan_exact<SCAN_S, 1, K>), grid, dim3(256), 0, e->stream, cb->v,
+                     (const float4 *)xt, count, tie_knn, keys, part);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+// masked samples (K1m / K1mk), one launch column each: launch(offset, first sample, columns) per 32768 (grid.y limit)
+template <class Launch>
+static int masked_columns(somhip_engine *e, const somhip_dataset *ds, int64_t first, int64_t count, Launch launch) {
+  for (int64_t off = 0; off < count; off += 32768) {
+    const int64_t c = std::min<int64_t>(32768, count - off);
+    LaunchTimer t(e, KID_SCAN_MASKED);
+    launch(off, (first + off) % ds->n, c);
   }
   HIPCHK(hipGetLastError());
   return 0;
 }
-
 // keys[count] <- exact nearest row per sample, FIRST tie rule, local shard
 static int scan_keys_top1(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count,
                           uint64_t *d_keys, bool *nonneg_keys = nullptr) {
   somhip_engine *e = cb->e;
-  const bool use_mfma = !ds->d_mask && e->scan_mode != SOMHIP_SCAN_DIRECT && count >= MFMA_MIN_SAMPLES && cb->v.n >= 64 &&
-                        count <= (int64_t)PAIR_MAX_COLS * 32;      // longer runs: the direct scan below
-  if (!use_mfma) HIPCHK(hipMemsetAsync(d_keys, 0xFF, sizeof(uint64_t) * (size_t)count, e->stream));   // (else k_sample_tau presets them)
-  if (ds->d_mask) {
-    for (int64_t off = 0; off < count; off += 32768) {      // grid.y limit
-      int64_t c = std::min<int64_t>(32768, count - off);
-      LaunchTimer t(e, KID_SCAN_MASKED);
-      dim3 grid((unsigned)((cb->v.ngroups + 3) / 4), (unsigned)c);
-      hipLaunchKernelGGL(k_scan_masked, grid, dim3(256), 0, e->stream, cb->v, ds->d_rows, ds->d_mask,
-                         ds->n, (first + off) % ds->n, c, 0, d_keys + off);
-    }
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
-  int64_t nsb = (count + SCAN_S - 1) / SCAN_S;
+  const ScanPlan p = scan_plan(cb, ds, count, 1);
+  if (p.route == ROUTE_MASKED || p.route == ROUTE_DIRECT)
+    HIPCHK(hipMemsetAsync(d_keys, 0xFF, sizeof(uint64_t) * (size_t)count, e->stream));   // (else k_sample_tau presets them)
+  if (p.route == ROUTE_MASKED)
+    return masked_columns(e, ds, first, count, [&](int64_t off, int64_t f, int64_t c) {
+      hipLaunchKernelGGL(k_scan_masked, dim3((unsigned)((cb->v.ngroups + 3) / 4), (unsigned)c), dim3(256), 0, e->stream, cb->v,
+                         ds->d_rows, ds->d_mask, ds->n, f, c, 0, d_keys + off);
+    });
   e->samples_searched += (uint64_t)count;
-  if (use_mfma) {
-    if (nonneg_keys) *nonneg_keys = true;
-    return scan_keys_mfma(cb, ds, first, count, nsb, d_keys, false, nullptr, nullptr, nonneg_keys != nullptr);
-  }
-  void *xt;
-  CHK(engine_scratch(e, 1, sizeof(float4) * (size_t)nsb * cb->v.d4 * SCAN_S, &xt));
-  {
-    LaunchTimer t(e, KID_PACK_SAMPLES);
-    hipLaunchKernelGGL(k_pack_samples<SCAN_S>, dim3((unsigned)nsb), dim3(256), 0, e->stream,
-                       ds->d_rows, ds->n, ds->d, cb->v.d4, first, count, (float4 *)xt);
-  }
-  HIPCHK(hipGetLastError());
-  {
-    LaunchTimer t(e, KID_SCAN_EXACT);
-    dim3 grid((unsigned)nsb, (unsigned)((cb->v.ngroups + 3) / 4));
-    hipLaunchKernelGGL((k_scan_exact<SCAN_S, 1, 1>), grid, dim3(256), 0, e->stream, cb->v,
-                       (const float4 *)xt, count, 0, d_keys, (uint64_t *)nullptr);
-  }
-  HIPCHK(hipGetLastError());
-  return 0;
+  if (p.route == ROUTE_DIRECT) return scan_exact<1>(cb, ds, first, count, p, 0, d_keys, (uint64_t *)nullptr);
+  if (nonneg_keys) *nonneg_keys = true;
+  const bool fused_gmin = p.route == ROUTE_TWO_LEVEL && !getenv("SOMHIP_NO_FUSED_GMIN");
+  PrefilterBufs b;
+  CHK(pf_filter(cb, ds, first, count, p, &b, d_keys, nonneg_keys != nullptr, fused_gmin));
+  return pf_rerank(cb, ds, first, count, p, b, d_keys, fused_gmin, nullptr);
 }
-
 template <int K>
 static int scan_keys_topk(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count,
                           uint64_t *d_keys /*[count][K]*/, int tie_knn = 1) {
   somhip_engine *e = cb->e;
-  // big codebooks: bf16 pre-filter + exact re-rank of the surviving row groups (kernels.hpp K2k)
-  const bool force_mfma = getenv("SOMHIP_TOPK_MFMA") != nullptr;
-  if (e->scan_mode == SOMHIP_SCAN_MFMA_BF16 && !ds->d_mask && count >= MFMA_MIN_SAMPLES &&
-      cb->v.n >= (force_mfma ? 64 : 4096) && count <= (int64_t)PAIR_MAX_COLS * 32) {
-    const int64_t nsb = (count + SCAN_S - 1) / SCAN_S;
-    float *dw = nullptr, *dt = nullptr;
-    CHK(scan_keys_mfma(cb, ds, first, count, nsb, nullptr, true, &dw, &dt, false,
-                       // two levels pay on big codebooks (100 000 x 1024: 0.52 -> 0.43 ms per 1024 samples); on 10 000 rows the
-                       // level-2 block costs more than the two products it saves (0.026 -> 0.049 ms)
-                       K == LVQ_K0 && cb->v.ngroups >= 512 && !getenv("SOMHIP_TOPK_ONE_LEVEL") ? K : 1));
-    const int64_t bpad = nsb * SCAN_S;
-    // pair-parallel re-rank (three launches); the one-wave-per-sample kernel only if the list overflows
-    const uint32_t cap = (uint32_t)std::min<int64_t>(count * 128 + 4096, 0x3FFFFFF0);
-    void *dpairs, *dspan, *dpart, *dcnt;
-    CHK(engine_scratch(e, 11, sizeof(uint2) * (size_t)cap, &dpairs));
-    CHK(engine_scratch(e, 2, sizeof(uint64_t) * (size_t)cap * K, &dpart));
-    CHK(engine_scratch(e, 15, sizeof(TopkSpan) * (size_t)count + 16, &dspan));
-    uint32_t *dcounter = reinterpret_cast<uint32_t *>(e->d_stats + 7);
-    (void)dcnt;
-    HIPCHK(hipMemsetAsync(dcounter, 0, 2 * sizeof(uint32_t), e->stream));
-    LaunchTimer t(e, KID_RERANK);
-    // pairs filed by row group (the group's tile is then streamed once per four samples) when rows are whole float4s
-    // (64 KiB of LDS for the samples' rows; a workgroup per group needs many groups to fill the chip)
-    // (ngroups >= 512: on configs[2]'s 157 groups the by-group pass is faster than the pairs -- 100 against 117 us -- but the
-    // step is not: 0.51 against 0.40 ms per 1024 iterations with the three extra launches and the lists' upkeep)
-    const bool by_group = (cb->v.d & 3) == 0 && cb->v.d4 <= 256 && cb->v.ngroups >= 512 && !getenv("SOMHIP_TOPK_BYPAIR");
-    // room per group: every sample of the run (a sample is filed at most once per group) unless that is too much memory
-    // (then a crowded group sends the run to the overflow path)
-    const uint32_t cap_g = (uint64_t)cb->v.ngroups * (uint64_t)count <= (8ull << 20)
-                               ? (uint32_t)count : (uint32_t)std::max<uint64_t>(64, (8ull << 20) / (uint64_t)cb->v.ngroups);
-    uint32_t *dgcnt = nullptr, *dwcount = nullptr;
-    uint2 *dglist = nullptr, *dwork = nullptr;
-    if (by_group) {
-      void *pg;
-      // [lists of the groups][their counts][the pass counter, padded][the passes: at most one per filed sample]
-      CHK(engine_scratch(e, 29, sizeof(uint2) * (size_t)cb->v.ngroups * cap_g + sizeof(uint32_t) * ((size_t)cb->v.ngroups + 4 + (cb->v.ngroups & 1)) +
-                                sizeof(uint2) * (size_t)cap, &pg));
-      dglist = (uint2 *)pg;
-      dgcnt = reinterpret_cast<uint32_t *>(dglist + (size_t)cb->v.ngroups * cap_g);
-      dwcount = dgcnt + cb->v.ngroups;
-      dwork = reinterpret_cast<uint2 *>(dgcnt + cb->v.ngroups + 4 + (cb->v.ngroups & 1));
-      HIPCHK(hipMemsetAsync(dgcnt, 0, sizeof(uint32_t) * ((size_t)cb->v.ngroups + 4), e->stream));
-    }
-    hipLaunchKernelGGL(k_topk_select<K>, dim3((unsigned)((count + TOPK_NB - 1) / TOPK_NB)), dim3(1024), 0, e->stream, cb->v, count, bpad,
-                       (const float *)dw, (const float *)dt, cap, (uint2 *)dpairs, (TopkSpan *)dspan, dcounter, dgcnt, dglist, cap_g);
-    if (by_group) {
-      hipLaunchKernelGGL(k_topk_worklist<4>, dim3((unsigned)std::min<int64_t>((cb->v.ngroups + 255) / 256, 256)), dim3(256), 0, e->stream,
-                         cb->v.ngroups, (const uint32_t *)dgcnt, cap_g, (const uint32_t *)dcounter, dwcount, dwork, cap);
-      hipLaunchKernelGGL(k_topk_pairs_bygroup<K>, dim3(8192), dim3(64), 0, e->stream, cb->v, ds->d_rows, ds->n,
-                         first, tie_knn, (const uint32_t *)dgcnt, (const uint2 *)dglist, cap_g, (const uint32_t *)dcounter,
-                         (const uint32_t *)dwcount, (const uint2 *)dwork, cap, (uint64_t *)dpart);
-    }
-    else
-      hipLaunchKernelGGL(k_topk_pairs<K>, dim3(1024), dim3(256), 0, e->stream, cb->v, ds->d_rows, ds->n, first, tie_knn,
-                         (const uint2 *)dpairs, (const uint32_t *)dcounter, (uint64_t *)dpart);
-    hipLaunchKernelGGL(k_topk_merge<K>, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, e->stream, count,
-                       (const TopkSpan *)dspan, (const uint64_t *)dpart, (const uint32_t *)dcounter, d_keys,
-                       e->d_stats + 8 + 128 + 8 + 1);
-    // list full (dcounter[1] != 0, seen on the device: no host round trip): every sample through the one-wave kernel
-    hipLaunchKernelGGL(k_rerank_topk<K>, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, e->stream, cb->v, ds->d_rows,
-                       ds->n, first, count, bpad, (const float *)dw, (const float *)dt, tie_knn, d_keys,
-                       (const uint32_t *)(dcounter + 1));
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
-  int nblk = (int)((cb->v.ngroups + 3) / 4);
-  if (ds->d_mask) {
-    // masked samples (kernels.hpp K1mk): one sample per launch column, the same partial lists as the exact scan below
+  const ScanPlan p = scan_plan(cb, ds, count, K);
+  if (p.route == ROUTE_MASKED || p.route == ROUTE_DIRECT) {
+    const int nblk = (int)((cb->v.ngroups + 3) / 4);
     void *part;
-    CHK(engine_scratch(e, 2, sizeof(uint64_t) * (size_t)count * nblk * K, &part));
-    for (int64_t off = 0; off < count; off += 32768) {      // grid.y limit
-      int64_t c = std::min<int64_t>(32768, count - off);
-      LaunchTimer t(e, KID_SCAN_MASKED);
-      hipLaunchKernelGGL(k_scan_masked_topk<K>, dim3((unsigned)nblk, (unsigned)c), dim3(256), 0, e->stream, cb->v, ds->d_rows,
-                         (const uint8_t *)ds->d_mask, ds->n, (first + off) % ds->n, tie_knn,
-                         (uint64_t *)part + (size_t)off * nblk * K);
-    }
-    HIPCHK(hipGetLastError());
-    {
-      LaunchTimer t(e, KID_MERGE_TOPK);
-      hipLaunchKernelGGL(k_merge_topk<K>, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, e->stream,
-                         (const uint64_t *)part, nblk, count, d_keys);
-    }
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
-  int64_t nsb = (count + SCAN_S - 1) / SCAN_S;
-  void *xt, *part;
-  CHK(engine_scratch(e, 1, sizeof(float4) * (size_t)nsb * cb->v.d4 * SCAN_S, &xt));
-  CHK(engine_scratch(e, 2, sizeof(uint64_t) * (size_t)count * nblk * K, &part));
-  {
-    LaunchTimer t(e, KID_PACK_SAMPLES);
-    hipLaunchKernelGGL(k_pack_samples<SCAN_S>, dim3((unsigned)nsb), dim3(256), 0, e->stream,
-                       ds->d_rows, ds->n, ds->d, cb->v.d4, first, count, (float4 *)xt);
-  }
-  HIPCHK(hipGetLastError());
-  {
-    LaunchTimer t(e, KID_SCAN_EXACT);
-    dim3 grid((unsigned)nsb, (unsigned)nblk);
-    hipLaunchKernelGGL((k_scan_exact<SCAN_S, 1, K>), grid, dim3(256), 0, e->stream, cb->v,
-                       (const float4 *)xt, count, tie_knn, (uint64_t *)nullptr, (uint64_t *)part);
-  }
-  HIPCHK(hipGetLastError());
-  {
+    CHK(engine_scratch(e, SLOT_PARTIAL, sizeof(uint64_t) * (size_t)count * nblk * K, &part));
+    if (p.route == ROUTE_MASKED)
+      CHK(masked_columns(e, ds, first, count, [&](int64_t off, int64_t f, int64_t c) {
+        hipLaunchKernelGGL(k_scan_masked_topk<K>, dim3((unsigned)nblk, (unsigned)c), dim3(256), 0, e->stream, cb->v, ds->d_rows,
+                           (const uint8_t *)ds->d_mask, ds->n, f, tie_knn, (uint64_t *)part + (size_t)off * nblk * K);
+      }));
+    else
+      CHK(scan_exact<K>(cb, ds, first, count, p, tie_knn, (uint64_t *)nullptr, (uint64_t *)part));
     LaunchTimer t(e, KID_MERGE_TOPK);
     hipLaunchKernelGGL(k_merge_topk<K>, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, e->stream,
                        (const uint64_t *)part, nblk, count, d_keys);
+    HIPCHK(hipGetLastError());
+    return 0;
   }
+  PrefilterBufs b;
+  CHK(pf_filter(cb, ds, first, count, p, &b, nullptr, false, false));
+  // pair-parallel re-rank (three launches); the one-wave-per-sample kernel only if the list overflows
+  const uint32_t cap = (uint32_t)std::min<int64_t>(count * 128 + 4096, 0x3FFFFFF0);
+  void *dpairs, *dspan, *dpart;
+  CHK(engine_scratch(e, SLOT_PAIRS, sizeof(uint2) * (size_t)cap, &dpairs));
+  CHK(engine_scratch(e, SLOT_PARTIAL, sizeof(uint64_t) * (size_t)cap * K, &dpart));
+  CHK(engine_scratch(e, SLOT_TOPK_SPAN, sizeof(TopkSpan) * (size_t)count + 16, &dspan));
+  uint32_t *dcounter = reinterpret_cast<uint32_t *>(e->d_stats + 7);
+  HIPCHK(hipMemsetAsync(dcounter, 0, 2 * sizeof(uint32_t), e->stream));
+  LaunchTimer t(e, KID_RERANK);
+  // pairs filed by row group (the group's tile is then streamed once per four samples) when rows are whole float4s
+  // (64 KiB of LDS for the samples' rows; a workgroup per group needs many groups to fill the chip)
+  // (ngroups >= 512: on configs[2]'s 157 groups the by-group pass is faster than the pairs -- 100 against 117 us -- but the
+  // step is not: 0.51 against 0.40 ms per 1024 iterations with the three extra launches and the lists' upkeep)
+  const bool by_group = (cb->v.d & 3) == 0 && cb->v.d4 <= 256 && cb->v.ngroups >= 512 && !getenv("SOMHIP_TOPK_BYPAIR");
+  // room per group: every sample of the run (a sample is filed at most once per group) unless that is too much memory
+  // (then a crowded group sends the run to the overflow path)
+  const uint32_t cap_g = (uint64_t)cb->v.ngroups * (uint64_t)count <= (8ull << 20)
+                             ? (uint32_t)count : (uint32_t)std::max<uint64_t>(64, (8ull << 20) / (uint64_t)cb->v.ngroups);
+  uint32_t *dgcnt = nullptr, *dwcount = nullptr;
+  uint2 *dglist = nullptr, *dwork = nullptr;
+  if (by_group) {
+    void *pg;
+    // [lists of the groups][their counts][the pass counter, padded][the passes: at most one per filed sample]
+    CHK(engine_scratch(e, SLOT_TOPK_GROUPS, sizeof(uint2) * (size_t)cb->v.ngroups * cap_g + sizeof(uint32_t) * ((size_t)cb->v.ngroups + 4 + (cb->v.ngroups & 1)) +
+                                            sizeof(uint2) * (size_t)cap, &pg));
+    dglist = (uint2 *)pg;
+    dgcnt = reinterpret_cast<uint32_t *>(dglist + (size_t)cb->v.ngroups * cap_g);
+    dwcount = dgcnt + cb->v.ngroups;
+    dwork = reinterpret_cast<uint2 *>(dgcnt + cb->v.ngroups + 4 + (cb->v.ngroups & 1));
+    HIPCHK(hipMemsetAsync(dgcnt, 0, sizeof(uint32_t) * ((size_t)cb->v.ngroups + 4), e->stream));
+  }
+  hipLaunchKernelGGL(k_topk_select<K>, dim3((unsigned)((count + TOPK_NB - 1) / TOPK_NB)), dim3(1024), 0, e->stream, cb->v, count, p.bpad,
+                     (const float *)b.wmin, (const float *)b.tau, cap, (uint2 *)dpairs, (TopkSpan *)dspan, dcounter, dgcnt, dglist, cap_g);
+  if (by_group) {
+    hipLaunchKernelGGL(k_topk_worklist<4>, dim3((unsigned)std::min<int64_t>((cb->v.ngroups + 255) / 256, 256)), dim3(256), 0, e->stream,
+                       cb->v.ngroups, (const uint32_t *)dgcnt, cap_g, (const uint32_t *)dcounter, dwcount, dwork, cap);
+    hipLaunchKernelGGL(k_topk_pairs_bygroup<K>, dim3(8192), dim3(64), 0, e->stream, cb->v, ds->d_rows, ds->n,
+                       first, tie_knn, (const uint32_t *)dgcnt, (const uint2 *)dglist, cap_g, (const uint32_t *)dcounter,
+                       (const uint32_t *)dwcount, (const uint2 *)dwork, cap, (uint64_t *)dpart);
+  }
+  else
+    hipLaunchKernelGGL(k_topk_pairs<K>, dim3(1024), dim3(256), 0, e->stream, cb->v, ds->d_rows, ds->n, first, tie_knn,
+                       (const uint2 *)dpairs, (const uint32_t *)dcounter, (uint64_t *)dpart);
+  hipLaunchKernelGGL(k_topk_merge<K>, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, e->stream, count,
+                     (const TopkSpan *)dspan, (const uint64_t *)dpart, (const uint32_t *)dcounter, d_keys,
+                     e->d_stats + 8 + 128 + 8 + 1);
+  // list full (dcounter[1] != 0, seen on the device: no host round trip): every sample through the one-wave kernel
+  hipLaunchKernelGGL(k_rerank_topk<K>, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, e->stream, cb->v, ds->d_rows,
+                     ds->n, first, count, p.bpad, (const float *)b.wmin, (const float *)b.tau, tie_knn, d_keys,
+                     (const uint32_t *)(dcounter + 1));
   HIPCHK(hipGetLastError());
   return 0;
+}
+
+// f(integral_constant<int, K>) for the top-K width K (1, 2, 4, 8) holding knn (1..8) neighbours; who: knn must be K
+template <class F>
+static int with_topk_width(int knn, const char *who, F f) {
+  const int k = knn == 1 ? 1 : knn == 2 ? 2 : knn <= 4 ? 4 : 8;
+  if (who && k != knn) return fail("%s: knn must be 1, 2, 4 or 8", who);
+  if (k == 1) return f(std::integral_constant<int, 1>());
+  if (k == 2) return f(std::integral_constant<int, 2>());
+  return k == 4 ? f(std::integral_constant<int, 4>()) : f(std::integral_constant<int, 8>());
 }
 
 extern "C" int somhip_debug_prefilter(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count,
                                       float *wmin, float *tau, int64_t *bpad) try {
   CHK(check_pair(cb, ds, "somhip_debug_prefilter"));
   somhip_engine *e = cb->e;
-  if (e->scan_mode == SOMHIP_SCAN_DIRECT || ds->d_mask) return fail("somhip_debug_prefilter: no pre-filter in this mode");
+  const ScanPlan p = scan_plan(cb, ds, count, 0);
+  if (p.route != ROUTE_ONE_LEVEL) return fail("somhip_debug_prefilter: no pre-filter in this mode");
   HIPCHK(hipSetDevice(e->device));
-  int64_t nsb = (count + SCAN_S - 1) / SCAN_S;
-  float *dw = nullptr, *dt = nullptr;
-  CHK(scan_keys_mfma(cb, ds, first, count, nsb, nullptr, true, &dw, &dt));
-  HIPCHK(hipMemcpyAsync(wmin, dw, sizeof(float) * (size_t)cb->v.ngroups * nsb * SCAN_S, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipMemcpyAsync(tau, dt, sizeof(float) * (size_t)count, hipMemcpyDeviceToHost, e->stream));
+  PrefilterBufs b;
+  CHK(pf_filter(cb, ds, first, count, p, &b, nullptr, false, false));
+  HIPCHK(hipMemcpyAsync(wmin, b.wmin, sizeof(float) * (size_t)cb->v.ngroups * p.bpad, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipMemcpyAsync(tau, b.tau, sizeof(float) * (size_t)count, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
-  if (bpad) *bpad = nsb * SCAN_S;
+  if (bpad) *bpad = p.bpad;
   return 0;
 } ABI_CATCH(somhip_debug_prefilter)
-
 extern "C" int somhip_batch_winner_keys(somhip_codebook *cb, somhip_dataset *ds, int64_t first,
                                         int64_t count, uint64_t *dev_keys) try {
   CHK(check_pair(cb, ds, "somhip_batch_winner_keys"));
@@ -525,51 +534,51 @@ extern "C" int somhip_batch_winner_keys(somhip_codebook *cb, somhip_dataset *ds,
 // X1 with the pre-filter's bounds exchanged between the shards (kernels.hpp K2x): begin -> MIN all-reduce of the
 // bounds -> refine -> MIN all-reduce -> finish -> MIN all-reduce of the keys.  Same keys as somhip_batch_winner_keys
 // after the last all-reduce; every shard re-ranks only what the WHOLE codebook's search would.
-static bool shard_exchange_ok(const somhip_codebook *cb, const somhip_dataset *ds, int64_t count) {
-  const somhip_engine *e = cb->e;
-  if (ds->d_mask || e->scan_mode != SOMHIP_SCAN_MFMA_BF16 || count < MFMA_MIN_SAMPLES || cb->v.n < 64 ||
-      count > (int64_t)PAIR_MAX_COLS * 32)
-    return false;
-  const int64_t nsb = (count + SCAN_S - 1) / SCAN_S, bpad = nsb * SCAN_S;
-  const int d8 = (cb->v.d4 + 1) / 2;
-  return (d8 % 4) == 0 && nsb >= 8 && bpad <= 65535 && !getenv("SOMHIP_NO_SHARD_EXCHANGE");
-}
 extern "C" int somhip_shard_exchange_available(somhip_codebook *cb, somhip_dataset *ds, int64_t count) try {
   if (check_pair(cb, ds, "somhip_shard_exchange_available")) return 0;
-  return shard_exchange_ok(cb, ds, count) ? 1 : 0;
+  return scan_plan(cb, ds, count, 1).route == ROUTE_TWO_LEVEL && !getenv("SOMHIP_NO_SHARD_EXCHANGE") ? 1 : 0;
 } catch (...) { return 0; }
-static int shard_winner_phase(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count, int phase,
-                              float *dev_bound, uint64_t *dev_keys, const char *who) {
+// One call of an exchanged search: the checks, then run(plan, buffers).  The calls of ONE search run in order on the
+// same codebook / data / range, handing their state over in scratch; `after`: the e->xc_phase this call continues.
+template <class Run>
+static int shard_call(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count, XcState after, bool bufs_ok,
+                      const char *who, Run run) {
   CHK(check_pair(cb, ds, who));
   if (count <= 0) return 0;
-  if (!dev_bound || (phase != 2 && !dev_keys)) return fail("%s: null buffer", who);
-  if (!shard_exchange_ok(cb, ds, count)) return fail("%s: not available for this shape (ask somhip_shard_exchange_available; use somhip_batch_winner_keys)", who);
+  if (!bufs_ok) return fail("%s: null buffer", who);
+  if (!somhip_shard_exchange_available(cb, ds, count)) return fail("%s: not available for this shape (ask somhip_shard_exchange_available; use somhip_batch_winner_keys)", who);
   HIPCHK(hipSetDevice(cb->e->device));
   somhip_engine *e = cb->e;
-  // the phases of ONE search, in order, on the same codebook / data / range: they hand their state over in the engine's scratch
-  if (phase > 1 && (e->xc_phase != phase - 1 || e->xc_cb != cb || e->xc_ds != ds || e->xc_first != first || e->xc_count != count)) {
-    const int was = e->xc_phase;
-    e->xc_phase = 0;
-    return fail("%s: not the continuation of the search somhip_shard_winner_begin started on this engine (phase %d after %d)", who, phase, was);
-  }
-  if (phase == 1) e->samples_searched += (uint64_t)count;
-  const int64_t nsb = (count + SCAN_S - 1) / SCAN_S;
-  e->xc_phase = 0;
-  CHK(scan_keys_mfma(cb, ds, first, count, nsb, dev_keys, false, nullptr, nullptr, true, 1, phase, dev_bound));
-  e->xc_phase = phase == 3 ? 0 : phase; e->xc_cb = cb; e->xc_ds = ds; e->xc_first = first; e->xc_count = count;
+  const bool continues = after == XC_NONE || (e->xc_phase == after && e->xc_cb == cb && e->xc_ds == ds && e->xc_first == first && e->xc_count == count);
+  const int was = e->xc_phase;
+  e->xc_phase = XC_NONE;                           // (until this call has run)
+  if (!continues) return fail("%s: not the continuation of the search somhip_shard_winner_begin started on this engine (phase %d after %d)", who, after + 1, was);
+  if (after == XC_NONE) e->samples_searched += (uint64_t)count;
+  const ScanPlan p = scan_plan(cb, ds, count, 1);
+  PrefilterBufs b;
+  CHK(bind_prefilter(cb, p, true, &b));
+  CHK(run(p, b));
+  e->xc_phase = after == XC_REFINED ? XC_NONE : after + 1; e->xc_cb = cb; e->xc_ds = ds; e->xc_first = first; e->xc_count = count;
   return 0;
 }
 extern "C" int somhip_shard_winner_begin(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count,
                                          uint64_t *dev_keys, float *dev_bound) try {
-  return shard_winner_phase(cb, ds, first, count, 1, dev_bound, dev_keys, "somhip_shard_winner_begin");
+  return shard_call(cb, ds, first, count, XC_NONE, dev_bound && dev_keys, "somhip_shard_winner_begin", [&](const ScanPlan &p, const PrefilterBufs &b) {
+    CHK(pf_prepare(cb, ds, first, count, p, b, dev_keys, true));
+    return pf_level1(cb, count, p, b, dev_bound);
+  });
 } ABI_CATCH(somhip_shard_winner_begin)
 extern "C" int somhip_shard_winner_refine(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count,
                                           float *dev_bound) try {
-  return shard_winner_phase(cb, ds, first, count, 2, dev_bound, nullptr, "somhip_shard_winner_refine");
+  return shard_call(cb, ds, first, count, XC_BEGUN, dev_bound, "somhip_shard_winner_refine", [&](const ScanPlan &p, const PrefilterBufs &b) {
+    return pf_level2(cb, count, p, b, !getenv("SOMHIP_NO_FUSED_GMIN"), dev_bound);
+  });
 } ABI_CATCH(somhip_shard_winner_refine)
 extern "C" int somhip_shard_winner_finish(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count,
                                           const float *dev_bound, uint64_t *dev_keys) try {
-  return shard_winner_phase(cb, ds, first, count, 3, const_cast<float *>(dev_bound), dev_keys, "somhip_shard_winner_finish");
+  return shard_call(cb, ds, first, count, XC_REFINED, dev_bound && dev_keys, "somhip_shard_winner_finish", [&](const ScanPlan &p, const PrefilterBufs &b) {
+    return pf_rerank(cb, ds, first, count, p, b, dev_keys, true, dev_bound);      // (refine formed the group minima)
+  });
 } ABI_CATCH(somhip_shard_winner_finish)
 
 // X2 (SURVEY 8e): this shard's k best rows per sample as packed keys, ascending; a host all-gathers
@@ -583,17 +592,11 @@ extern "C" int somhip_batch_topk_keys(somhip_codebook *cb, somhip_dataset *ds, i
   if (count <= 0) return 0;
   HIPCHK(hipSetDevice(cb->e->device));
   const int t = tie == SOMHIP_TIE_KNN ? 1 : 0;
-  if (knn == 1) {
-    if (t) return fail("somhip_batch_topk_keys: knn 1 is find_winner_euc (SOMHIP_TIE_FIRST)");
-    return somhip_batch_winner_keys(cb, ds, first, count, dev_keys);
-  }
-  if (knn == 2) return scan_keys_topk<2>(cb, ds, first, count, dev_keys, t);
-  if (knn <= 4) {
-    if (knn != 4) return fail("somhip_batch_topk_keys: knn must be 1, 2, 4 or 8");
-    return scan_keys_topk<4>(cb, ds, first, count, dev_keys, t);
-  }
-  if (knn != 8) return fail("somhip_batch_topk_keys: knn must be 1, 2, 4 or 8");
-  return scan_keys_topk<8>(cb, ds, first, count, dev_keys, t);
+  if (knn == 1 && t) return fail("somhip_batch_topk_keys: knn 1 is find_winner_euc (SOMHIP_TIE_FIRST)");
+  return with_topk_width(knn, "somhip_batch_topk_keys", [&](auto k) {
+    if constexpr (decltype(k)::value == 1) return somhip_batch_winner_keys(cb, ds, first, count, dev_keys);
+    else return scan_keys_topk<decltype(k)::value>(cb, ds, first, count, dev_keys, t);
+  });
 } ABI_CATCH(somhip_batch_topk_keys)
 
 static void decode_key(uint64_t k, bool inverted, int32_t *index, float *diff) {
@@ -619,32 +622,32 @@ extern "C" int somhip_find_winners(somhip_codebook *cb, somhip_dataset *ds, int6
   const bool knn_rule = (tie == SOMHIP_TIE_KNN) && knn >= 2;
   if (!knn_rule && knn != 1) return fail("somhip_find_winners: knn > 1 needs SOMHIP_TIE_KNN");
   const int64_t CH = 4096;
-  const int KK = knn == 1 ? 1 : knn == 2 ? 2 : knn <= 4 ? 4 : 8;
-  void *dk;
-  CHK(engine_scratch(e, 3, sizeof(uint64_t) * (size_t)std::min(CH, count) * KK, &dk));
-  std::vector<uint64_t> hk((size_t)std::min(CH, count) * KK);
-  for (int64_t off = 0; off < count; off += CH) {
-    int64_t c = std::min(CH, count - off);
-    int64_t f = (first + off) % ds->n;
-    if (!knn_rule) CHK(scan_keys_top1(cb, ds, f, c, (uint64_t *)dk));
-    else if (KK == 2) CHK(scan_keys_topk<2>(cb, ds, f, c, (uint64_t *)dk));
-    else if (KK == 4) CHK(scan_keys_topk<4>(cb, ds, f, c, (uint64_t *)dk));
-    else CHK(scan_keys_topk<8>(cb, ds, f, c, (uint64_t *)dk));
-    HIPCHK(hipMemcpyAsync(hk.data(), dk, sizeof(uint64_t) * (size_t)c * KK, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    for (int64_t i = 0; i < c; i++) {
-      int64_t r = (f + i) % ds->n;
-      bool empty = !ds->all_masked.empty() && ds->all_masked[(size_t)r];
-      for (int k = 0; k < knn; k++) {
-        int32_t *pi = index + (off + i) * knn + k;
-        float *pd = diff + (off + i) * knn + k;
-        if (empty) { *pi = -2; *pd = -1.0f; }
-        else decode_key(hk[(size_t)i * KK + k], knn_rule, pi, pd);
+  return with_topk_width(knn, nullptr, [&](auto width) {
+    constexpr int KK = decltype(width)::value;
+    void *dk;
+    CHK(engine_scratch(e, SLOT_CALL_A, sizeof(uint64_t) * (size_t)std::min(CH, count) * KK, &dk));
+    std::vector<uint64_t> hk((size_t)std::min(CH, count) * KK);
+    for (int64_t off = 0; off < count; off += CH) {
+      int64_t c = std::min(CH, count - off);
+      int64_t f = (first + off) % ds->n;
+      if constexpr (KK == 1) CHK(scan_keys_top1(cb, ds, f, c, (uint64_t *)dk));
+      else CHK(scan_keys_topk<KK>(cb, ds, f, c, (uint64_t *)dk));
+      HIPCHK(hipMemcpyAsync(hk.data(), dk, sizeof(uint64_t) * (size_t)c * KK, hipMemcpyDeviceToHost, e->stream));
+      HIPCHK(hipStreamSynchronize(e->stream));
+      for (int64_t i = 0; i < c; i++) {
+        int64_t r = (f + i) % ds->n;
+        bool empty = !ds->all_masked.empty() && ds->all_masked[(size_t)r];
+        for (int k = 0; k < knn; k++) {
+          int32_t *pi = index + (off + i) * knn + k;
+          float *pd = diff + (off + i) * knn + k;
+          if (empty) { *pi = -2; *pd = -1.0f; }
+          else decode_key(hk[(size_t)i * KK + k], knn_rule, pi, pd);
+        }
+        if (ret) ret[off + i] = empty ? 0 : knn;
       }
-      if (ret) ret[off + i] = empty ? 0 : knn;
     }
-  }
-  return 0;
+    return 0;
+  });
 } ABI_CATCH(somhip_find_winners)
 
 // lininit's data passes (find_eigenvectors, som_rout.c:211-289): per-component sums / counts over the
@@ -656,8 +659,8 @@ extern "C" int somhip_column_sums(somhip_dataset *ds, float *sum, int64_t *count
   somhip_engine *e = ds->e;
   HIPCHK(hipSetDevice(e->device));
   void *dsum, *dcnt;
-  CHK(engine_scratch(e, 3, sizeof(float) * (size_t)ds->d, &dsum));
-  CHK(engine_scratch(e, 4, sizeof(unsigned long long) * (size_t)ds->d, &dcnt));
+  CHK(engine_scratch(e, SLOT_CALL_A, sizeof(float) * (size_t)ds->d, &dsum));
+  CHK(engine_scratch(e, SLOT_CALL_B, sizeof(unsigned long long) * (size_t)ds->d, &dcnt));
   hipLaunchKernelGGL(k_column_sums, dim3((unsigned)((ds->d + 255) / 256)), dim3(256), 0, e->stream, ds->d_rows,
                      (const uint8_t *)ds->d_mask, ds->n, ds->d, (float *)dsum, (unsigned long long *)dcnt);
   HIPCHK(hipGetLastError());
@@ -676,8 +679,8 @@ extern "C" int somhip_centered_products(somhip_dataset *ds, const float *mean, f
   HIPCHK(hipSetDevice(e->device));
   const size_t dd = (size_t)ds->d * ds->d;
   void *dmean, *dr;
-  CHK(engine_scratch(e, 3, sizeof(float) * (size_t)ds->d, &dmean));
-  CHK(engine_scratch(e, 4, sizeof(float) * dd, &dr));
+  CHK(engine_scratch(e, SLOT_CALL_A, sizeof(float) * (size_t)ds->d, &dmean));
+  CHK(engine_scratch(e, SLOT_CALL_B, sizeof(float) * dd, &dr));
   HIPCHK(hipMemcpyAsync(dmean, mean, sizeof(float) * (size_t)ds->d, hipMemcpyHostToDevice, e->stream));
   HIPCHK(hipMemsetAsync(dr, 0, sizeof(float) * dd, e->stream));
   const unsigned nb = (unsigned)((ds->d + 15) / 16);
@@ -698,8 +701,8 @@ extern "C" int somhip_column_minmax(somhip_dataset *ds, float *lo, float *hi, in
   somhip_engine *e = ds->e;
   HIPCHK(hipSetDevice(e->device));
   void *dmm, *dcnt;
-  CHK(engine_scratch(e, 3, sizeof(uint32_t) * 2 * (size_t)ds->d, &dmm));
-  CHK(engine_scratch(e, 4, sizeof(unsigned long long) * (size_t)ds->d, &dcnt));
+  CHK(engine_scratch(e, SLOT_CALL_A, sizeof(uint32_t) * 2 * (size_t)ds->d, &dmm));
+  CHK(engine_scratch(e, SLOT_CALL_B, sizeof(unsigned long long) * (size_t)ds->d, &dcnt));
   uint32_t *dmin = (uint32_t *)dmm, *dmax = dmin + ds->d;
   HIPCHK(hipMemsetAsync(dmin, 0xFF, sizeof(uint32_t) * (size_t)ds->d, e->stream));
   HIPCHK(hipMemsetAsync(dmax, 0, sizeof(uint32_t) * (size_t)ds->d, e->stream));
@@ -741,19 +744,15 @@ extern "C" int somhip_qerror2(somhip_codebook *cb, somhip_dataset *ds, float rad
   const int ireach = reach > 1e6 ? 1000000 : (int)reach;
   const int64_t CH = 4096;
   void *dk, *dq;
-  CHK(engine_scratch(e, 3, sizeof(uint64_t) * (size_t)std::min(CH, count), &dk));
-  CHK(engine_scratch(e, 4, sizeof(float) * (size_t)std::min(CH, count), &dq));
+  CHK(engine_scratch(e, SLOT_CALL_A, sizeof(uint64_t) * (size_t)std::min(CH, count), &dk));
+  CHK(engine_scratch(e, SLOT_CALL_B, sizeof(float) * (size_t)std::min(CH, count), &dq));
   const size_t dyn = (size_t)cb->v.d * 5 + 16;
   for (int64_t off = 0; off < count; off += CH) {
     const int64_t c = std::min(CH, count - off);
     const int64_t f = (first + off) % ds->n;
     CHK(scan_keys_top1(cb, ds, f, c, (uint64_t *)dk));
-    if (gauss)
-      hipLaunchKernelGGL(k_qerror2<true>, dim3((unsigned)c), dim3(256), dyn, e->stream, cb->v, cb->ydim, ds->d_rows,
-                         ds->d_mask, ds->n, f, (const uint64_t *)dk, radius, thresh, ireach, (float *)dq);
-    else
-      hipLaunchKernelGGL(k_qerror2<false>, dim3((unsigned)c), dim3(256), dyn, e->stream, cb->v, cb->ydim, ds->d_rows,
-                         ds->d_mask, ds->n, f, (const uint64_t *)dk, radius, thresh, ireach, (float *)dq);
+    hipLaunchKernelGGL(gauss ? k_qerror2<true> : k_qerror2<false>, dim3((unsigned)c), dim3(256), dyn, e->stream, cb->v, cb->ydim,
+                       ds->d_rows, ds->d_mask, ds->n, f, (const uint64_t *)dk, radius, thresh, ireach, (float *)dq);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out + off, dq, sizeof(float) * (size_t)c, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));

@@ -91,9 +91,9 @@ static int som_train_online(somhip_codebook *cb, somhip_dataset *ds, const somhi
   const bool G = cb->v.neigh == SOMHIP_NEIGH_GAUSSIAN, M = ds->d_mask != nullptr;
   void *dslot, *dsc, *drow;
   // entry 0 of the arrays carries the last iteration of the previous chunk
-  CHK(engine_scratch(e, 3, sizeof(uint64_t) * (size_t)(CH + 1), &dslot));
-  CHK(engine_scratch(e, 4, sizeof(StepScalars) * (size_t)(CH + 1), &dsc));
-  CHK(engine_scratch(e, 2, sizeof(int64_t) * (size_t)(CH + 1), &drow));
+  CHK(engine_scratch(e, SLOT_CALL_A, sizeof(uint64_t) * (size_t)(CH + 1), &dslot));
+  CHK(engine_scratch(e, SLOT_CALL_B, sizeof(StepScalars) * (size_t)(CH + 1), &dsc));
+  CHK(engine_scratch(e, SLOT_PARTIAL, sizeof(int64_t) * (size_t)(CH + 1), &drow));
   uint64_t *slot = (uint64_t *)dslot;
   StepScalars *sc = (StepScalars *)dsc;
   int64_t *rowidx = (int64_t *)drow;
@@ -207,10 +207,10 @@ static int som_update_run(somhip_codebook *cb, somhip_dataset *ds, int64_t data_
                          (!G || (cb->v.xdim <= 1024 && cb->ydim <= 1024));
   const bool off32 = scalar_form && off32_ok && !gemm_form;
   void *dbxy, *dcnt, *dent;
-  CHK(engine_scratch(e, 8, sizeof(int2) * (size_t)count, &dbxy));
-  CHK(engine_scratch(e, 9, sizeof(uint32_t) * (size_t)cb->v.ngroups, &dcnt));
+  CHK(engine_scratch(e, SLOT_MEMBER_XY, sizeof(int2) * (size_t)count, &dbxy));
+  CHK(engine_scratch(e, SLOT_MEMBER_COUNT, sizeof(uint32_t) * (size_t)cb->v.ngroups, &dcnt));
   // (GEMM_FRONT_PAD entries in front of the first list: K4m's scalar quarter loads may start before a list)
-  CHK(engine_scratch(e, 10, sizeof(MemberEntry) * ((size_t)cb->v.ngroups * (size_t)list_stride(count) + GEMM_FRONT_PAD), &dent));
+  CHK(engine_scratch(e, SLOT_MEMBER_LIST, sizeof(MemberEntry) * ((size_t)cb->v.ngroups * (size_t)list_stride(count) + GEMM_FRONT_PAD), &dent));
   dent = (MemberEntry *)dent + GEMM_FRONT_PAD;
   // the winners' lattice coordinates: K4b decodes them itself from the keys (a division per (sample, row group), but no
   // launch) in a short run; a long run pays for the launch many times over (1024 groups x 32768 samples: members 201 -> 180 us, the decode launch 6)
@@ -234,7 +234,7 @@ static int som_update_run(somhip_codebook *cb, somhip_dataset *ds, int64_t data_
       if (need < (double)count / 2) tail_need = (uint32_t)need;
     }
     void *pl;
-    CHK(engine_scratch(e, 30, sizeof(uint32_t) * (size_t)cb->v.ngroups, &pl));
+    CHK(engine_scratch(e, SLOT_TAIL_START, sizeof(uint32_t) * (size_t)cb->v.ngroups, &pl));
     dlstart = (uint32_t *)pl;
   }
   int reach_max = -1;                                      // (see k_som_members: early rejection on the winners' coordinates)
@@ -273,7 +273,7 @@ static int som_update_run(somhip_codebook *cb, somhip_dataset *ds, int64_t data_
   uint32_t *dorder = nullptr;
   if (cb->v.ngroups <= 8192) {
     void *p_;
-    CHK(engine_scratch(e, 0, sizeof(uint32_t) * (size_t)cb->v.ngroups, &p_));
+    CHK(engine_scratch(e, SLOT_STAGE, sizeof(uint32_t) * (size_t)cb->v.ngroups, &p_));
     dorder = (uint32_t *)p_;
     LaunchTimer t(e, KID_DECODE);
     hipLaunchKernelGGL(k_order_groups, dim3((unsigned)((cb->v.ngroups * 8 + 255) / 256)), dim3(256), 0, e->stream,
@@ -374,7 +374,7 @@ extern "C" int somhip_som_batch_update(somhip_codebook *cb, somhip_dataset *ds,
   HIPCHK(hipSetDevice(e->device));
   void *dsc, *hsc;
   int slot;
-  CHK(engine_scratch(e, 4, sizeof(StepScalars) * (size_t)count, &dsc));
+  CHK(engine_scratch(e, SLOT_CALL_B, sizeof(StepScalars) * (size_t)count, &dsc));
   CHK(pin_acquire(e, sizeof(StepScalars) * (size_t)count, &hsc, &slot));
   CHK(som_scalars(cb, ds, p, batch_start_iter, count, data_first % ds->n, (StepScalars *)hsc));
   CHK(pin_upload(e, slot, dsc, sizeof(StepScalars) * (size_t)count));
@@ -467,8 +467,8 @@ static int som_train_batched(somhip_codebook *cb, somhip_dataset *ds, const somh
   const AutoPlan plan = auto_b ? som_auto_plan(p, cb->n_global, cb->v.topol, cb->v.neigh) : AutoPlan();
   const int64_t B = auto_b ? AUTO_B_LONG : p->batch;        // the longest batch of the run
   void *dkeys, *dsc;
-  CHK(engine_scratch(e, 3, sizeof(uint64_t) * (size_t)B, &dkeys));
-  CHK(engine_scratch(e, 4, sizeof(StepScalars) * (size_t)B, &dsc));
+  CHK(engine_scratch(e, SLOT_CALL_A, sizeof(uint64_t) * (size_t)B, &dkeys));
+  CHK(engine_scratch(e, SLOT_CALL_B, sizeof(StepScalars) * (size_t)B, &dsc));
   std::vector<uint64_t> hk((size_t)B);
   const bool trace = trace_index || trace_diff;
   // batches are aligned to the schedule (iteration 0, B, 2B, ...), as in the oracle; the host runs

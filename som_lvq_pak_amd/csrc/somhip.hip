@@ -12,6 +12,7 @@
 #include <cstring>
 #include <exception>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "kernels.hpp"
@@ -105,6 +106,46 @@ struct OnlineGraphKey {
   }
 };
 
+// Device scratch of an engine (engine_scratch): one buffer per slot, grown on demand and kept.  The owners of a slot
+// never hold it at the same time; the stages named below hold their slots together.
+enum ScratchSlot {
+  SLOT_STAGE = 0,          // staging of codebook upload / download; the SOM update's group order (k_order_groups)
+  SLOT_SAMPLES,            // the packed sample tiles of a scan: direct scan, or the pre-filter from prepare to level 2
+  SLOT_PARTIAL,            // partial top-K lists (top-K scans and re-rank), the LVQ online loop's, the online SOM's rows
+  SLOT_CALL_A,             // a host call's own array around the scans it runs: keys, LVQ candidates, column sums
+  SLOT_CALL_B,             // ... and its second one: step scalars, LvqStep, column counts, products
+  SLOT_TAU,                // pre-filter: per-sample window, from prepare to the re-rank
+  SLOT_WMIN,               // pre-filter: per (group, sample) minimum, from level 1 / one level to the re-rank
+  SLOT_WMASK,              // pre-filter: per (group, sample) candidate mask, from level 2 / one level to the re-rank
+  SLOT_MEMBER_XY,          // SOM update: the winners' lattice positions
+  SLOT_MEMBER_COUNT,       // SOM update: members per row group
+  SLOT_MEMBER_LIST,        // SOM update: the member lists
+  SLOT_PAIRS,              // top-1 re-rank: candidate pairs; top-K re-rank: its pair list
+  SLOT_RERANK_COUNT,       // pre-filter: re-rank counters preset by k_sample_tau, from prepare to the re-rank
+  SLOT_LVQ_FINAL,          // exact LVQ batches: the final keys
+  SLOT_XBOUND,             // shard exchange: the deltas behind the exchanged bounds, from begin to finish
+  SLOT_TOPK_SPAN,          // top-K re-rank: each sample's span of the pair list
+  SLOT_LVQ_MOD,            // exact LVQ batch (lvq_batch_bufs, with the ten slots below): rows it modified
+  SLOT_LVQ_RHO,            // ... sample norms, rates, the OLVQ1 rate bound
+  SLOT_LVQ_ADJ,            // ... the pair relation
+  SLOT_LVQ_COMP,           // ... samples per component
+  SLOT_LVQ_OUT,            // ... the batch's verdict
+  SLOT_LVQ_STAGE_ROWS,     // ... staged rows
+  SLOT_LVQ_STAGE_ROWID,    // ... their row ids
+  SLOT_LVQ_STAGE_TA,       // ... their rates
+  SLOT_LVQ_CAND_LAB,       // ... the candidates' labels
+  SLOT_LVQ_CAND_TA,        // ... the candidates' rates
+  SLOT_L2_STATE,           // two-level pre-filter: level 1's window and minimum, level 2's counts, from prepare to level 2
+  SLOT_L2_LIST,            // two-level pre-filter: level 2's group lists, from level 1 to level 2
+  SLOT_LVQ_CTL,            // exact LVQ loop: its control block
+  SLOT_TOPK_GROUPS,        // top-K re-rank by row group: the groups' lists and the passes
+  SLOT_TAIL_START,         // GEMM update: where each group's list tail starts
+  SLOT_SAMPLE_ROWS,        // two-level pre-filter: the sample-major copy of the tiles, from prepare to level 2
+  SLOT_COUNT
+};
+
+enum XcState { XC_NONE, XC_BEGUN, XC_REFINED };   // a shard-exchanged search: the last of its calls that ran
+
 struct somhip_engine {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -114,8 +155,8 @@ struct somhip_engine {
   int update_mode = SOMHIP_UPDATE_EXACT;
   unsigned long long *d_stats = nullptr;     // [4] re-rank statistics (device)
   uint64_t samples_searched = 0;
-  // somhip_shard_winner_begin / _refine / _finish: which search is under way on this engine (0 = none)
-  int xc_phase = 0;
+  // somhip_shard_winner_begin / _refine / _finish: which search is under way on this engine, and how far it got
+  int xc_phase = 0;                          // XC_NONE, XC_BEGUN, XC_REFINED
   const void *xc_cb = nullptr, *xc_ds = nullptr;
   int64_t xc_first = 0, xc_count = 0;
   uint64_t lvq_batches = 0, lvq_samples = 0;   // exact batched LVQ: rescans and samples
@@ -135,8 +176,8 @@ struct somhip_engine {
   int64_t launches[KID_COUNT] = {0};
   double total_ms[KID_COUNT] = {0};
   // reusable device scratch
-  void *scratch[32] = {nullptr};
-  size_t scratch_bytes[32] = {0};
+  void *scratch[SLOT_COUNT] = {nullptr};
+  size_t scratch_bytes[SLOT_COUNT] = {0};
   // the mirrors created on this engine: destroying the engine first releases their device memory and orphans
   // them (their own destroy then only frees the host struct; any other call on them fails with a message)
   std::vector<somhip_codebook *> codebooks;
@@ -149,7 +190,7 @@ struct somhip_engine {
   hipEvent_t lvq_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 };
 
-static int engine_scratch(somhip_engine *e, int slot, size_t bytes, void **out) {
+static int engine_scratch(somhip_engine *e, ScratchSlot slot, size_t bytes, void **out) {
   if (e->scratch_bytes[slot] < bytes) {
     if (e->scratch[slot]) HIPCHK(hipFree(e->scratch[slot]));
     e->scratch[slot] = nullptr;
@@ -395,7 +436,7 @@ static int upload_rows(somhip_codebook *cb, const float *rows) {
   cb->prep_valid = false;
   void *stage;
   size_t bytes = sizeof(float) * (size_t)cb->v.n * cb->v.d;
-  CHK(engine_scratch(e, 0, bytes, &stage));
+  CHK(engine_scratch(e, SLOT_STAGE, bytes, &stage));
   HIPCHK(hipMemcpyAsync(stage, rows, bytes, hipMemcpyHostToDevice, e->stream));
   {
     LaunchTimer t(e, KID_LAYOUT);
@@ -509,7 +550,7 @@ extern "C" int somhip_codebook_download(somhip_codebook *cb, float *rows) try {
   HIPCHK(hipSetDevice(e->device));
   void *stage;
   size_t bytes = sizeof(float) * (size_t)cb->v.n * cb->v.d;
-  CHK(engine_scratch(e, 0, bytes, &stage));
+  CHK(engine_scratch(e, SLOT_STAGE, bytes, &stage));
   {
     LaunchTimer t(e, KID_LAYOUT);
     hipLaunchKernelGGL(k_tiles_to_rows, dim3((unsigned)cb->v.ngroups), dim3(256), 0, e->stream,
