@@ -201,10 +201,22 @@ static int som_update_run(somhip_codebook *cb, somhip_dataset *ds, int64_t data_
   const bool scalar_form = !G && !M && (QW == 4 || (QW == 2 && off32_ok)) && (cb->v.d & 3) == 0 && cb->v.d4 % (4 * QW) == 0 &&
                            count <= ds->n && ds->n * (int64_t)(cb->v.d >> 2) < (1ll << 32) && !getenv("SOMHIP_UPD_LDS");
   // the matrix-pipe form of the same update (kernels/som_update_gemm.hpp): opt-in, bubble, no masks, dims in whole 128s
-  // (gaussian: lattice_sq in fp32 needs both map sides <= 1024, the winner's coordinates travel as 16-bit fields)
-  const bool gemm_form = e->update_mode == SOMHIP_UPDATE_GEMM && !M && cb->v.d % 128 == 0 && count <= GEMM_MAX_RUN &&
-                         ds->n * (int64_t)(cb->v.d >> 2) < (1ll << 32) &&      // the entries carry 32-bit row offsets in float4 units
-                         (!G || (cb->v.xdim <= 1024 && cb->ydim <= 1024));
+  // (gaussian: lattice_sq in fp32 needs both map sides <= 1024, the winner's coordinates travel as 10-bit fields)
+  bool gemm_form = e->update_mode == SOMHIP_UPDATE_GEMM && !M && cb->v.d % 128 == 0 && count <= GEMM_MAX_RUN &&
+                   ds->n * (int64_t)(cb->v.d >> 2) < (1ll << 32) &&      // the entries carry 32-bit row offsets in float4 units
+                   (!G || (cb->v.xdim <= 1024 && cb->ydim <= 1024));
+  // one pass over the run's scalars: the smallest rate (for the list tail below), and what the GEMM form cannot take --
+  // a rate outside [0, 1] (the backward walk's decay P (1 - a) would change sign and stop it early; NaN fails the test
+  // too), or, gaussian, a fixed point with a coordinate above 1023 (it would not fit the entry's 10-bit fields)
+  float amin = 1.0f;
+  if (gemm_form) {
+    for (int64_t j = 0; j < count && gemm_form; j++) {
+      const StepScalars &s = h_sc[j];
+      if (!(s.alpha >= 0.0f && s.alpha <= 1.0f)) gemm_form = false;
+      if (G && s.fixed >= 0 && (fixed_x(s.fixed) > 1023 || fixed_y(s.fixed) > 1023)) gemm_form = false;
+      amin = std::min(amin, s.alpha);
+    }
+  }
   const bool off32 = scalar_form && off32_ok && !gemm_form;
   void *dbxy, *dcnt, *dent;
   CHK(engine_scratch(e, SLOT_MEMBER_XY, sizeof(int2) * (size_t)count, &dbxy));
@@ -227,8 +239,6 @@ static int som_update_run(somhip_codebook *cb, somhip_dataset *ds, int64_t data_
   uint32_t tail_need = 0;
   uint32_t *dlstart = nullptr;
   if (gemm_form && !G && !getenv("SOMHIP_GEMM_FULL_LISTS")) {
-    float amin = 1.0f;
-    for (int64_t j = 0; j < count; j++) amin = std::min(amin, h_sc[j].alpha);
     if (amin > 1e-6f && amin < 1.0f) {
       const double need = std::ceil(std::log((double)GEMM_CUT) / std::log1p(-(double)amin)) + GEMM_KT + 1;
       if (need < (double)count / 2) tail_need = (uint32_t)need;

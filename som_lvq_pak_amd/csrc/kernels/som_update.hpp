@@ -209,11 +209,12 @@ __global__ __launch_bounds__(NT) void k_som_members(CbView cb, int64_t count,
                 (static_cast<unsigned long long>(static_cast<uint32_t>(w.y) & 0x3FFu) << 10) | (static_cast<uint32_t>(w.x) & 0x3FFu);
           }
         } else if (GAUSS) m = live_mask;
-        else if (cb.patch_w && small_map) {
+        else if (cb.patch_w && small_map && s.thresh <= 5.0e8f && w.y <= 25000) {
           // 8x8 patch, exact integer form: with every lattice quantity a multiple of 1/4,
           //   lattice_sq <= thresh  <=>  (2dx)^2 + 3 dy^2 <= floor(4 thresh)   (hexa)
           //                              dx^2 + dy^2     <= floor(thresh)     (rect)
-          // and in one lattice row the members are a contiguous run of tx.
+          // and in one lattice row the members are a contiguous run of tx.  In 32-bit ints while K <= 2e9 (radius up to
+          // ~22 000) and 3 dy^2 < 2^31 (a fixed point's y up to 25 000); beyond that the per-unit test below.
           const bool rect = cb.topol == 4;
           const int K = static_cast<int>(floor(static_cast<double>(s.thresh) * (rect ? 1.0 : 4.0)));
           if (K >= 0) {
@@ -256,7 +257,8 @@ __global__ __launch_bounds__(NT) void k_som_members(CbView cb, int64_t count,
         } else {
           int tx = g_tx0, ty = g_ty0;
           for (int u = 0; u < nlive; u++) {
-            const float lsq = small_map ? lattice_sq_small(cb.topol, w.x, w.y, tx, ty)
+            // (the fp32 form is the reference's value while dy^2 stays exact: a fixed point's y below 2048)
+            const float lsq = small_map && w.y < 2048 ? lattice_sq_small(cb.topol, w.x, w.y, tx, ty)
                                         : lattice_sq(cb.topol, w.x, w.y, tx, ty);
             if (lsq <= s.thresh) m |= 1ull << u;
             if (++tx == static_cast<int>(xdim)) { tx = 0; ty++; }

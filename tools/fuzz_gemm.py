@@ -12,6 +12,7 @@ import numpy as np
 sys.path.insert(0, ".")
 sys.path.insert(0, "tests")
 from som_lvq_pak_amd import engine as E  # noqa: E402
+from helpers.som_replay import replay  # noqa: E402
 
 
 def main():
@@ -31,7 +32,7 @@ def main():
         ds = E.Dataset(eng, generate=(int(rs.randint(1, 1 << 30)), int(rs.randint(1, 12)), d, 0, nvec))
         lo, hi, cnt = E.column_minmax(ds)
         init = E.randinit_from_bbox(lo, hi, cnt, xd, yd, int(rs.randint(1, 1000)))
-        ds_rows = ds.rows(0, nvec).astype(np.float64)
+        ds_rows = ds.rows(0, nvec)
         it0 = int(rs.randint(0, max(1, length - B + 1)))
         got = {}
         for mode in ("exact", "gemm"):
@@ -48,41 +49,16 @@ def main():
         assert np.isfinite(b).all(), case
         scale = float(np.abs(a).max())
         err = float(np.abs(a - b).max()) / scale
-        # the yardstick: a float64 replay of the batch on a few units (the exact kernels' fp32 chain of thousands of
-        # hits has an error of its own, as large as the GEMM's: the two may differ by their sum)
+        # the yardstick: a float64 replay of the batch on a few units (tests/helpers/som_replay.py: the reference's own
+        # float arithmetic for radii, rates and lattice distances, so no unit on a neighbourhood's rim is decided the
+        # other way; the exact kernels' fp32 chain of thousands of hits has an error of its own, as large as the GEMM's)
         units = rs.choice(xd * yd, min(48, xd * yd), replace=False)
         win = got["exact"][1]
         cnt_it = len(win)
-        c = init[units].astype(np.float64)
-        ux, uy = (units % xd).astype(np.int64), (units // xd).astype(np.int64)
-        rows = ds_rows
-        for j in range(cnt_it):
-            it = it0 + j
-            al = np.float32(np.float32(alpha) * np.float32(length - it) / np.float32(length))
-            rad = np.float32(1.0) + np.float32(radius - 1.0) * np.float32(length - it) / np.float32(length)
-            if win[j] < 0:
-                continue
-            bx, by = int(win[j]) % xd, int(win[j]) // xd
-            dx = (bx - ux).astype(np.float64)
-            dy = (by - uy).astype(np.float64)
-            if topol == 3:
-                odd = ((by - uy) % 2) != 0
-                dx = np.where(odd, dx + (0.5 if by % 2 else -0.5), dx)
-                lat = dx * dx + 0.75 * dy * dy
-            else:
-                lat = dx * dx + dy * dy
-            if neigh == 1:
-                r = np.where(np.sqrt(lat).astype(np.float32) <= rad, np.float64(al), 0.0)
-            else:
-                dd = np.sqrt(lat).astype(np.float32)
-                neg = -(dd * dd)
-                r = np.float64(al) * np.exp(neg.astype(np.float64) / (2.0 * float(rad) * float(rad))).astype(np.float32).astype(np.float64)
-            c += r[:, None] * (rows[(it % nvec)][None, :] - c)
+        c = replay(init, xd, yd, topol, neigh, ds_rows, length, alpha, radius, win, start_iter=it0, count=cnt_it,
+                   dtype=np.float64, units=units).codes
         e_exact = float(np.abs(a[units] - c).max()) / scale
         e_gemm = float(np.abs(b[units] - c).max()) / scale
-        # (a unit that sits on the rim of a neighbourhood to within an ulp can fall on the other side in the float64
-        # replay's own radius arithmetic: then BOTH kernels differ from the replay by a whole hit -- the replay's doing;
-        # the largest difference between the two kernels is reported beside it)
         worst = max(worst, e_gemm)
         worst_pair = max(worst_pair, err)
         # a sum of k products accumulated in fp32 carries ~ sqrt(k) 2^-24 of the magnitude of the sum (the exact kernels'
