@@ -92,6 +92,16 @@ int  somhip_scan_stats(somhip_engine *e, uint64_t out[8]);
 int  somhip_debug_prefilter(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count,
                             float *wmin, float *tau, int64_t *bpad);
 
+/* diagnostics (tests): the route somhip_batch_winner_keys / somhip_batch_topk_keys / somhip_find_winners would take
+ * for `count` samples and `want` (1, or the top-k width 2/4/8); host arithmetic only, no GPU work.  (somhip_find_winners
+ * searches its run in pieces of at most 4096 samples: ask with the length of a piece.)
+ * out[0] = route (0 masked scan, 1 direct scan, 2 one-level pre-filter, 3 two-level pre-filter), out[1] = kth (level 1's
+ * window above the smallest group minimum: 1, or above the 8th smallest), out[2] = split-bf16 GEMMs (else fp32 MFMA),
+ * out[3] = level 1 by the persistent ring kernel, out[4] = top-k re-rank filed by row group (else by pair), out[5] =
+ * level 2 reads its samples from global memory (else LDS), out[6] = the two-level nearest-row search takes its
+ * per-sample minimum from level 2, out[7] = 0 */
+int  somhip_debug_scan_plan(somhip_codebook *cb, somhip_dataset *ds, int64_t count, int want, int32_t out[8]);
+
 /* ---- codebook mirror -------------------------------------------------------
  * rows: host, row-major [n_rows][dim] fp32, row k = list position k of the
  * reference's codebook (datafile.c:781,836) = map unit (k % xdim, k / xdim)
@@ -229,7 +239,8 @@ int  somhip_lvq_train(somhip_codebook *cb, somhip_dataset *ds, const somhip_lvq_
  * its phases (inputs, cached-row distances, decision, correction; summed over the components of a batch),
  * out[8] = independent components walked, out[9] = sum over the batches of the largest component's size
  * (the length of the longest serial walk), out[10] = (sample, 64-row group) pairs the exact top-k re-rank behind the
- * MFMA pre-filter evaluated, out[11] reserved */
+ * MFMA pre-filter evaluated, out[11] = 1 if the pair list of the last top-k search behind the pre-filter overflowed (its
+ * samples then went through the one-wave exact re-rank), else 0 */
 int  somhip_lvq_stats(somhip_engine *e, uint64_t out[12]);
 
 /* ---- lininit's data passes (find_eigenvectors, som_rout.c:211-289) ----------------

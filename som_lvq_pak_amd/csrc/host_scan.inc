@@ -73,6 +73,9 @@ struct ScanPlan {
   bool bf16, l1_ring;  // split-bf16 GEMMs (else fp32 MFMA); level 1 by the persistent ring kernel
   int64_t nsb, bpad;   // 32-sample tiles of the run, and the run padded to them
   int d8;              // 8-dim bf16 K-steps of a row
+  bool by_group;       // top-K behind a pre-filter: exact re-rank filed by row group (k_topk_pairs_bygroup), else by pair
+  bool l2_global;      // two levels: level 2's sample operand from global memory (k_dist_l2), else from LDS (k_dist_l2_lds)
+  bool fused_gmin;     // two levels, nearest row: the per-sample minimum comes out of level 2 (else k_group_min)
 };
 static ScanPlan scan_plan(const somhip_codebook *cb, const somhip_dataset *ds, int64_t count, int want) {
   const int64_t nsb = (count + SCAN_S - 1) / SCAN_S;
@@ -102,6 +105,14 @@ static ScanPlan scan_plan(const somhip_codebook *cb, const somhip_dataset *ds, i
   // least one 256 x 256 tile per CU)
   const int64_t l1_tiles = ((nsb + 7) / 8) * ((cb->v.ngroups + 3) / 4);
   p.l1_ring = p.route == ROUTE_TWO_LEVEL && (cb->v.ngroups >= 512 || l1_tiles >= 256) && (p.d8 % 8) == 0;
+  // the re-rank behind a top-K pre-filter filed by row group when rows are whole float4s (64 KiB of LDS for the samples'
+  // rows; a workgroup per group needs many groups to fill the chip)
+  // (ngroups >= 512: on configs[2]'s 157 groups the by-group pass is faster than the pairs -- 100 against 117 us -- but the
+  // step is not: 0.51 against 0.40 ms per 1024 iterations with the three extra launches and the lists' upkeep)
+  const bool filtered = p.route == ROUTE_ONE_LEVEL || p.route == ROUTE_TWO_LEVEL;
+  p.by_group = filtered && want > 1 && (cb->v.d & 3) == 0 && cb->v.d4 <= 256 && cb->v.ngroups >= 512 && !getenv("SOMHIP_TOPK_BYPAIR");
+  p.l2_global = p.route == ROUTE_TWO_LEVEL && (p.d8 > 64 || getenv("SOMHIP_L2_GLOBAL") != nullptr);
+  p.fused_gmin = p.route == ROUTE_TWO_LEVEL && want == 1 && !getenv("SOMHIP_NO_FUSED_GMIN");
   return p;
 }
 // (32-sample columns) x (chunks of about `per` row groups, whole 8s, at most 64): the passes over the group minima
@@ -272,9 +283,8 @@ static int pf_level2(somhip_codebook *cb, int64_t count, const ScanPlan &p, cons
   }
   {
     LaunchTimer t(e, KID_DIST_L2);
-    const bool l2_global = getenv("SOMHIP_L2_GLOBAL") != nullptr;    // operand A from global memory for every tile (k_dist_l2)
     uint32_t *l2_gmin = fused_gmin ? b.gmin : nullptr;
-    if (d8 <= 64 && !l2_global) {
+    if (!p.l2_global) {
       const size_t a_bytes = sizeof(uint4) * 2 * (size_t)d8 * 64;
       if (!e->l2_lds_attr_set) {
         HIPCHK(hipFuncSetAttribute((const void *)k_dist_l2_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
@@ -410,10 +420,9 @@ static int scan_keys_top1(somhip_codebook *cb, somhip_dataset *ds, int64_t first
   e->samples_searched += (uint64_t)count;
   if (p.route == ROUTE_DIRECT) return scan_exact<1>(cb, ds, first, count, p, 0, d_keys, (uint64_t *)nullptr);
   if (nonneg_keys) *nonneg_keys = true;
-  const bool fused_gmin = p.route == ROUTE_TWO_LEVEL && !getenv("SOMHIP_NO_FUSED_GMIN");
   PrefilterBufs b;
-  CHK(pf_filter(cb, ds, first, count, p, &b, d_keys, nonneg_keys != nullptr, fused_gmin));
-  return pf_rerank(cb, ds, first, count, p, b, d_keys, fused_gmin, nullptr);
+  CHK(pf_filter(cb, ds, first, count, p, &b, d_keys, nonneg_keys != nullptr, p.fused_gmin));
+  return pf_rerank(cb, ds, first, count, p, b, d_keys, p.fused_gmin, nullptr);
 }
 template <int K>
 static int scan_keys_topk(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count,
@@ -448,11 +457,8 @@ static int scan_keys_topk(somhip_codebook *cb, somhip_dataset *ds, int64_t first
   uint32_t *dcounter = reinterpret_cast<uint32_t *>(e->d_stats + 7);
   HIPCHK(hipMemsetAsync(dcounter, 0, 2 * sizeof(uint32_t), e->stream));
   LaunchTimer t(e, KID_RERANK);
-  // pairs filed by row group (the group's tile is then streamed once per four samples) when rows are whole float4s
-  // (64 KiB of LDS for the samples' rows; a workgroup per group needs many groups to fill the chip)
-  // (ngroups >= 512: on configs[2]'s 157 groups the by-group pass is faster than the pairs -- 100 against 117 us -- but the
-  // step is not: 0.51 against 0.40 ms per 1024 iterations with the three extra launches and the lists' upkeep)
-  const bool by_group = (cb->v.d & 3) == 0 && cb->v.d4 <= 256 && cb->v.ngroups >= 512 && !getenv("SOMHIP_TOPK_BYPAIR");
+  // pairs filed by row group (scan_plan: by_group): the group's tile is then streamed once per four samples
+  const bool by_group = p.by_group;
   // room per group: every sample of the run (a sample is filed at most once per group) unless that is too much memory
   // (then a crowded group sends the run to the overflow path)
   const uint32_t cap_g = (uint64_t)cb->v.ngroups * (uint64_t)count <= (8ull << 20)
@@ -518,6 +524,16 @@ extern "C" int somhip_debug_prefilter(somhip_codebook *cb, somhip_dataset *ds, i
   if (bpad) *bpad = p.bpad;
   return 0;
 } ABI_CATCH(somhip_debug_prefilter)
+extern "C" int somhip_debug_scan_plan(somhip_codebook *cb, somhip_dataset *ds, int64_t count, int want, int32_t *out) try {
+  CHK(check_pair(cb, ds, "somhip_debug_scan_plan"));
+  if (!out) return fail("somhip_debug_scan_plan: null output");
+  if (want != 1 && want != 2 && want != 4 && want != 8) return fail("somhip_debug_scan_plan: want %d is not 1, 2, 4 or 8", want);
+  if (count <= 0) return fail("somhip_debug_scan_plan: count %lld < 1", (long long)count);
+  const ScanPlan p = scan_plan(cb, ds, count, want);
+  out[0] = (int32_t)p.route; out[1] = p.kth; out[2] = p.bf16; out[3] = p.l1_ring;
+  out[4] = p.by_group; out[5] = p.l2_global; out[6] = p.fused_gmin; out[7] = 0;
+  return 0;
+} ABI_CATCH(somhip_debug_scan_plan)
 extern "C" int somhip_batch_winner_keys(somhip_codebook *cb, somhip_dataset *ds, int64_t first,
                                         int64_t count, uint64_t *dev_keys) try {
   CHK(check_pair(cb, ds, "somhip_batch_winner_keys"));

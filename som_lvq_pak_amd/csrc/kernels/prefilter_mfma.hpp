@@ -95,7 +95,12 @@ __global__ void k_sample_tau(const float *__restrict__ rows, int64_t n_rows, int
     const double u = 5.9604644775390625e-08;                         // 2^-24
     const double cmax = sqrt(static_cast<double>(__uint_as_float(*cn_max_bits)) * (1.0 + 4.0 * d * u));
     const double a = sqrt(acc), s = a + cmax;
-    const double t = 2.0 * (err_prod * a * cmax + err_sq * s * s) * 1.001;
+    // every value of the GEMM forms (cn, the dot products, s~ and their partial sums) is at most ~(||x|| + ||c||)^2; past
+    // 2^126 one may overflow fp32 (inf - inf = NaN in s~) while the direct-form distance does not, and a NaN component
+    // makes the bound itself NaN: such a sample gets tau = +inf -- the re-rank (k_rerank / k_rerank_topk) then takes
+    // every row of the codebook for it with the reference's arithmetic, whatever the pre-filter kept
+    const bool all_rows = !(s * s <= 0x1p126);
+    const double t = all_rows ? static_cast<double>(INFINITY) : 2.0 * (err_prod * a * cmax + err_sq * s * s) * 1.001;
     float tf = static_cast<float>(t);
     if (static_cast<double>(tf) < t) tf = __uint_as_float(__float_as_uint(tf) + 1);   // round up
     tau[b] = tf;
@@ -105,7 +110,8 @@ __global__ void k_sample_tau(const float *__restrict__ rows, int64_t n_rows, int
       // every group outside it with a level-1 minimum beyond what the re-rank looks at, min3 + tau <= s_min + 3 delta3,
       // i.e. W >= delta1 + 3 delta3 (a group outside has wmin1 > min1 + W >= s_min - delta1 + W).  delta1 >= 3 delta3 in
       // every ordinary case (the dropped lo parts dwarf the accumulation error), but not for a codebook of tiny norm.
-      const double d1 = (l1_prod * a * cmax + l1_sq * s * s) * 1.001, d3 = 0.5 * static_cast<double>(tf);
+      const double d1 = all_rows ? static_cast<double>(INFINITY) : (l1_prod * a * cmax + l1_sq * s * s) * 1.001,
+                   d3 = 0.5 * static_cast<double>(tf);
       const double t1 = d1 + (d1 > 3.0 * d3 ? d1 : 3.0 * d3);
       float t1f = static_cast<float>(t1);
       if (static_cast<double>(t1f) < t1) t1f = __uint_as_float(__float_as_uint(t1f) + 1);

@@ -22,7 +22,9 @@ __global__ __launch_bounds__(256) void k_rerank(CbView cb, const float *__restri
   const int64_t b = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (b >= count) return;
-  if (pair_count && *pair_count <= cap) return;          // the pair path handled the run
+  // tau +inf (k_sample_tau): the GEMM form may overflow or meet a NaN for this sample -- every row, exactly
+  const bool all_rows = !(tau[b] <= 3.0e38f);
+  if (!all_rows && pair_count && *pair_count <= cap) return;   // the pair path handled the run
   float m = 3.4e38f;
   for (int64_t g = lane; g < cb.ngroups; g += WAVE) m = fminf(m, wmin[g * bpad + b]);
 #pragma unroll
@@ -35,13 +37,13 @@ __global__ __launch_bounds__(256) void k_rerank(CbView cb, const float *__restri
   for (int64_t gb = 0; gb < cb.ngroups; gb += WAVE) {
     const int64_t gl = gb + lane;
     const float wv = gl < cb.ngroups ? wmin[gl * bpad + b] : 3.4e38f;
-    const bool q = wv <= thr && wv < 3.0e38f;              // (3.4e38: left out by k_l2_select under a shard-exchange bound)
+    const bool q = all_rows ? gl < cb.ngroups : wv <= thr && wv < 3.0e38f;   // (3.4e38: left out by k_l2_select under a shard-exchange bound)
     uint64_t ball = __ballot(q);
     while (ball) {
       const int t = __builtin_ctzll(ball);
       ball &= ball - 1;
       const int64_t g = gb + t;
-      const uint64_t mask = wmask[g * bpad + b];
+      const uint64_t mask = all_rows ? ~0ull : wmask[g * bpad + b];
       // lane -> code row of the group: the mask bit of row rr is
       //   half = (rr>>2)&1, i = rr>>5, r = (rr&3) + 4*((rr&31)>>3)  -> bit 32*half + 16*i + r
       const int rr = lane;
@@ -85,10 +87,12 @@ __global__ __launch_bounds__(256) void k_rerank_topk(CbView cb, const float *__r
                                                      const float *__restrict__ tau, int tie_knn,
                                                      uint64_t *__restrict__ keys_out,
                                                      const uint32_t *__restrict__ only_if = nullptr) {
-  if (only_if && *only_if == 0u) return;                 // launched behind the pair-list kernels: runs only if their list overflowed
   const int64_t b = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (b >= count) return;
+  // tau +inf (k_sample_tau): the GEMM form may overflow or meet a NaN for this sample -- every row, exactly
+  const bool all_rows = !(tau[b] <= 3.0e38f);
+  if (!all_rows && only_if && *only_if == 0u) return;    // launched behind the pair-list kernels: runs only if their list overflowed
   // ---- m_K: K-th smallest group minimum
   float mine[K];
 #pragma unroll
@@ -124,7 +128,7 @@ __global__ __launch_bounds__(256) void k_rerank_topk(CbView cb, const float *__r
   for (int t = 0; t < K; t++) top[t] = KEY_NONE;
   for (int64_t gb = 0; gb < cb.ngroups; gb += WAVE) {
     const int64_t gl = gb + lane;
-    const bool q = gl < cb.ngroups && wmin[gl * bpad + b] <= thr;
+    const bool q = gl < cb.ngroups && (all_rows || wmin[gl * bpad + b] <= thr);
     uint64_t ball = __ballot(q);
     while (ball) {
       const int t = __builtin_ctzll(ball);

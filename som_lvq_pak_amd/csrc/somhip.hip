@@ -354,10 +354,12 @@ extern "C" int somhip_lvq_stats(somhip_engine *e, uint64_t out[12]) try {
   out[0] = e->lvq_batches; out[1] = e->lvq_samples; out[2] = e->lvq_stop_list; out[3] = e->lvq_stop_cache;
   for (int k = 0; k < 4; k++) out[4 + k] = e->lvq_cycles[k];
   unsigned long long pairs = 0;                            // counted on the device (the top-k search does not wait for the host)
+  uint32_t topk_counter[2] = {0, 0};                       // the last pre-filtered top-k search's pair list: [0] fill, [1] overflow
   HIPCHK(hipSetDevice(e->device));
   HIPCHK(hipMemcpyAsync(&pairs, e->d_stats + 8 + 128 + 8 + 1, sizeof pairs, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipMemcpyAsync(topk_counter, e->d_stats + 7, sizeof topk_counter, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
-  out[8] = e->lvq_components; out[9] = e->lvq_largest; out[10] = pairs; out[11] = 0;
+  out[8] = e->lvq_components; out[9] = e->lvq_largest; out[10] = pairs; out[11] = topk_counter[1] != 0 ? 1 : 0;
   return 0;
 } ABI_CATCH(somhip_lvq_stats)
 extern "C" int somhip_timing_enable(somhip_engine *e, int on) try {

@@ -74,7 +74,7 @@ class Engine:
         check(self.lib.somhip_lvq_stats(self.h, out))
         return {"batches": out[0], "samples": out[1], "stop_list": out[2], "stop_cache": out[3],
                 "phase_us": [out[4 + k] / 100.0 for k in range(4)], "components": out[8], "largest": out[9],
-                "topk_pairs": out[10]}
+                "topk_pairs": out[10], "topk_overflow": out[11]}
 
     # --- timing table (HIP events on the engine's stream) ---
     def timing(self, on=True):
@@ -311,6 +311,18 @@ def find_winners(cb, ds, first=0, count=None, knn=1, tie=TIE_FIRST):
     check(cb.e.lib.somhip_find_winners(cb.h, ds.h, first, count, knn, tie, _p(idx, _lib.c_i32_p),
                                        _p(diff, _lib.c_float_p), _p(ret, _lib.c_i32_p)))
     return idx, diff, ret
+
+
+ROUTES = ("masked", "direct", "one_level", "two_level")
+
+
+def scan_plan(cb, ds, count, want=1):
+    """The plan of a winner search of `count` samples for the nearest row (want 1) or the top-k width `want` (2, 4, 8)
+    (somhip_debug_scan_plan; host arithmetic, no GPU work): a dict of the route and the stage choices behind it."""
+    out = (C.c_int32 * 8)()
+    check(cb.e.lib.somhip_debug_scan_plan(cb.h, ds.h, count, want, out))
+    return {"route": ROUTES[out[0]], "kth": out[1], "bf16": bool(out[2]), "l1_ring": bool(out[3]),
+            "by_group": bool(out[4]), "l2_global": bool(out[5]), "fused_gmin": bool(out[6])}
 
 
 def som_train(cb, ds, length, alpha, radius, alpha_type=ALPHA_LINEAR, use_fixed=0, use_weights=0,
