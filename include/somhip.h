@@ -101,6 +101,20 @@ int  somhip_debug_prefilter(somhip_codebook *cb, somhip_dataset *ds, int64_t fir
  * level 2 reads its samples from global memory (else LDS), out[6] = the two-level nearest-row search takes its
  * per-sample minimum from level 2, out[7] = 0 */
 int  somhip_debug_scan_plan(somhip_codebook *cb, somhip_dataset *ds, int64_t count, int want, int32_t out[8]);
+/* diagnostics (tests): the plan somhip_som_batch_update (and somhip_som_train, per batch) would follow for the mini-batch
+ * update of iterations [batch_start_iter, +count) on data rows from data_first: the same arguments but the keys, the
+ * same checks; the step scalars are made on the host, nothing is launched.
+ * out[0] = apply kernel (0 k_som_update_gemm, 1 k_som_update_gauss_h, 2 k_som_update_gauss_s, 3 k_som_update_bubble_s,
+ * 4 k_som_update_run), out[1] = chunks per wave of bubble_s / run (else 0), out[2] = bubble_s with byte offsets,
+ * out[3] = gemm's 32-dim tiles per wave (else 0), out[4] = k_decode_winners runs, out[5] / out[6] = k_som_members'
+ * threads per workgroup and samples per thread and trip, out[7] = what a member entry carries (0 the sample's index in
+ * the run, 1 its row offset in float4 units, 2 in bytes), out[8] = entries carry packed winner coordinates (gaussian
+ * gemm), out[9] = only the tail of each list is made, out[10] = its length (0: whole lists), out[11] = the run's largest
+ * reach (-1: not used), out[12] = k_order_groups runs, out[13] / out[14] = the apply kernel's grid and workgroup size,
+ * out[15] = 0 */
+struct somhip_som_params;                          /* (below, with somhip_som_train) */
+int  somhip_debug_update_plan(somhip_codebook *cb, somhip_dataset *ds, const struct somhip_som_params *p,
+                              int64_t batch_start_iter, int64_t count, int64_t data_first, int32_t out[16]);
 
 /* ---- codebook mirror -------------------------------------------------------
  * rows: host, row-major [n_rows][dim] fp32, row k = list position k of the

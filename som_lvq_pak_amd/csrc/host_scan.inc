@@ -508,6 +508,14 @@ static int with_topk_width(int knn, const char *who, F f) {
   if (k == 2) return f(std::integral_constant<int, 2>());
   return k == 4 ? f(std::integral_constant<int, 4>()) : f(std::integral_constant<int, 8>());
 }
+// f(integral_constant<int, v>) for the runtime value v, which must be one of Vs (else an error, not a launch): the SOM
+// update's launches (host_som.inc) turn their plan's choices into template arguments with it; f returns 0 or an error
+template <int V, int... Vs, class F>
+static int with_value(int v, F &&f) {
+  if (v == V) return f(std::integral_constant<int, V>());
+  if constexpr (sizeof...(Vs) > 0) return with_value<Vs...>(v, f);
+  else return fail("with_value: no launch built for the value %d", v);
+}
 
 extern "C" int somhip_debug_prefilter(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count,
                                       float *wmin, float *tau, int64_t *bpad) try {

@@ -59,25 +59,28 @@ static int som_scalars(const somhip_codebook *cb, const somhip_dataset *ds, cons
 }
 
 constexpr int ONLINE_U = 8;    // chunks (KiB) per register buffer; two buffers per wave
-template <bool G, bool M>
-static void launch_online(somhip_engine *e, const somhip_codebook *cb, const somhip_dataset *ds,
-                          const int64_t *prev_row, const int64_t *cur_row, int has_prev, int has_cur,
-                          const uint64_t *prev_slot, uint64_t *cur_slot, const StepScalars *prev_sc,
-                          const StepScalars *cur_sc) {
+static void launch_online_any(somhip_engine *e, const somhip_codebook *cb, const somhip_dataset *ds, bool G, bool M,
+                              const int64_t *prev_row, const int64_t *cur_row, int has_prev, int has_cur, const uint64_t *prev_slot,
+                              uint64_t *cur_slot, const StepScalars *prev_sc, const StepScalars *cur_sc) {
   LaunchTimer t(e, KID_SOM_ONLINE_STEP);
   // chunks (KiB) per register buffer: a wave is alone on its SIMD here (one wave per 64 rows: 1024 waves on 1024 SIMDs at
   // 65536 rows), so registers are free and what bounds the kernel is how many bytes it keeps in flight
-  hipLaunchKernelGGL((k_som_online_step<G, M, ONLINE_U>), dim3((unsigned)((cb->v.ngroups + 3) / 4)), dim3(256), 0,
-                     e->stream, cb->v, ds->d_rows, (const uint8_t *)ds->d_mask, prev_row, cur_row,
-                     has_prev, has_cur, prev_slot, cur_slot, prev_sc, cur_sc);
+  (void)with_value<1, 0>(G, [&](auto g) { return with_value<1, 0>(M, [&](auto m) {    // (two bools: always found)
+    hipLaunchKernelGGL((k_som_online_step<decltype(g)::value != 0, decltype(m)::value != 0, ONLINE_U>),
+                       dim3((unsigned)((cb->v.ngroups + 3) / 4)), dim3(256), 0, e->stream, cb->v, ds->d_rows,
+                       (const uint8_t *)ds->d_mask, prev_row, cur_row, has_prev, has_cur, prev_slot, cur_slot, prev_sc, cur_sc); return 0;
+  }); });
 }
-static void launch_online_any(somhip_engine *e, const somhip_codebook *cb, const somhip_dataset *ds, bool G, bool M,
-                              const int64_t *prev_row, const int64_t *cur_row, int has_prev, int has_cur,
-                              const uint64_t *prev_slot, uint64_t *cur_slot, const StepScalars *prev_sc,
-                              const StepScalars *cur_sc) {
-#define GO(GG, MM) launch_online<GG, MM>(e, cb, ds, prev_row, cur_row, has_prev, has_cur, prev_slot, cur_slot, prev_sc, cur_sc)
-  if (G && M) GO(true, true); else if (G) GO(true, false); else if (M) GO(false, true); else GO(false, false);
-#undef GO
+// the winner trace of iterations [off, off + c): a fixed point (-3, -1), a skipped sample (-2, -1), else the key's row and distance
+static void som_trace(const StepScalars *sc, const uint64_t *keys, int64_t c, int64_t off, int32_t *trace_index, float *trace_diff) {
+  for (int64_t j = 0; j < c; j++) {
+    int32_t idx; float df;
+    if (sc[j].fixed >= 0) { idx = -3; df = -1.0f; }
+    else if (sc[j].reach < 0) { idx = -2; df = -1.0f; }
+    else decode_key(keys[j], false, &idx, &df);
+    if (trace_index) trace_index[off + j] = idx;
+    if (trace_diff) trace_diff[off + j] = df;
+  }
 }
 
 // The online algorithm is one small launch per iteration; a full chunk of them is captured
@@ -132,7 +135,6 @@ static int som_train_online(somhip_codebook *cb, somhip_dataset *ds, const somhi
   }
 
   bool have_prev = false;
-  int64_t last_row = 0;
   for (int64_t off = 0; off < p->count; off += CH) {
     int64_t c = std::min(CH, p->count - off);
     int64_t it0 = p->start_iter + off, row0 = (p->data_first + off) % ds->n;
@@ -149,19 +151,10 @@ static int som_train_online(somhip_codebook *cb, somhip_dataset *ds, const somhi
     }
     HIPCHK(hipGetLastError());
     have_prev = true;
-    last_row = hrow[(size_t)c];
     if (trace_index || trace_diff) {
       HIPCHK(hipMemcpyAsync(hslot.data(), slot + 1, sizeof(uint64_t) * (size_t)c, hipMemcpyDeviceToHost, e->stream));
       HIPCHK(hipStreamSynchronize(e->stream));
-      for (int64_t j = 0; j < c; j++) {
-        int32_t idx; float df;
-        const StepScalars &s = hsc[(size_t)j + 1];
-        if (s.fixed >= 0) { idx = -3; df = -1.0f; }
-        else if (s.reach < 0) { idx = -2; df = -1.0f; }
-        else decode_key(hslot[(size_t)j], false, &idx, &df);
-        if (trace_index) trace_index[off + j] = idx;
-        if (trace_diff) trace_diff[off + j] = df;
-      }
+      som_trace(hsc.data() + 1, hslot.data(), c, off, trace_index, trace_diff);
     }
     // carry the last iteration's slot + scalars + row into entry 0 for the next chunk / the flush
     HIPCHK(hipMemcpyAsync(slot, slot + c, sizeof(uint64_t), hipMemcpyDeviceToDevice, e->stream));
@@ -170,7 +163,6 @@ static int som_train_online(somhip_codebook *cb, somhip_dataset *ds, const somhi
     // the host staging vectors are reused by the next chunk
     HIPCHK(hipStreamSynchronize(e->stream));
   }
-  (void)last_row;
   if (have_prev) {   // flush: apply the last iteration's update
     launch_online_any(e, cb, ds, G, M, rowidx, rowidx, 1, 0, slot, slot, sc, sc);
     HIPCHK(hipGetLastError());
@@ -179,12 +171,29 @@ static int som_train_online(somhip_codebook *cb, somhip_dataset *ds, const somhi
   return 0;
 }
 
-static int som_update_run(somhip_codebook *cb, somhip_dataset *ds, int64_t data_first, int64_t count,
-                          const uint64_t *d_keys, const StepScalars *d_sc, const StepScalars *h_sc) {
-  somhip_engine *e = cb->e;
-  cb->prep_valid = false;
+// The mini-batch update of one run: som_update_plan makes every choice, the stages only read it -- decode (K4a) ->
+// members (K4b) -> order (K4c) -> apply.  K4b writes its entries for the apply kernel the plan picks: what an entry
+// carries (`entry`), its mask field holding packed winner coordinates (`gauss_gemm`) and only a list's tail (`tail`).
+enum UpdateApply { APPLY_GEMM, APPLY_GAUSS_H, APPLY_GAUSS_S, APPLY_BUBBLE_S, APPLY_RUN };
+enum UpdateEntry { ENTRY_SAMPLE, ENTRY_FLOAT4, ENTRY_BYTE };   // sample index in the run, row offset in float4s, in bytes
+struct UpdatePlan {
+  UpdateApply apply; UpdateEntry entry;
+  int qw = 0, ntw = 0;      // bubble_s / run: chunks (float4) per wave (2, 4); gemm: 32-dim tiles per wave (1, 2, 4)
+  bool off32 = false;       // bubble_s: byte offsets in the entries and register-offset scalar loads (OFF32)
+  bool decode;              // k_decode_winners runs and K4b reads its coordinates (else K4b decodes the keys itself)
+  int members_nt, members_rr;   // K4b's threads per workgroup (256, 1024) and samples per thread and trip (4, 8)
+  bool gauss_gemm;          // the entries carry the winner's packed coordinates for the gaussian gemm form
+  bool tail;                // gemm, bubble: K4b says where each list starts (lstart) and makes only its tail ...
+  uint32_t tail_need = 0;   // ... until it holds this many entries with every live unit (0: the whole list)
+  int reach_max = -1;       // decoded winners, bubble: the run's largest reach (K4b's early rejection), else -1
+  bool order;               // k_order_groups runs (the apply kernels take the groups in its order)
+  dim3 grid, block;         // the apply kernel's launch
+};
+
+static UpdatePlan som_update_plan(const somhip_codebook *cb, const somhip_dataset *ds, int64_t data_first, int64_t count,
+                                  const StepScalars *h_sc) {
   const bool G = cb->v.neigh == SOMHIP_NEIGH_GAUSSIAN, M = ds->d_mask != nullptr;
-  constexpr int TB = 32;
+  UpdatePlan p;
   // chunks (float4) per wave (4 waves of a workgroup share a member list): more chunks amortise the per-entry
   // work, fewer give more waves -- a small shard (N > 1 ranks) needs them to keep the vector ALUs busy.  Measured
   // (profiles/r01_shard_rehearsal.txt): 4 with the pipelined tile walk beats 8 even on the whole 65536-row map.
@@ -202,177 +211,177 @@ static int som_update_run(somhip_codebook *cb, somhip_dataset *ds, int64_t data_
                            count <= ds->n && ds->n * (int64_t)(cb->v.d >> 2) < (1ll << 32) && !getenv("SOMHIP_UPD_LDS");
   // the matrix-pipe form of the same update (kernels/som_update_gemm.hpp): opt-in, bubble, no masks, dims in whole 128s
   // (gaussian: lattice_sq in fp32 needs both map sides <= 1024, the winner's coordinates travel as 10-bit fields)
-  bool gemm_form = e->update_mode == SOMHIP_UPDATE_GEMM && !M && cb->v.d % 128 == 0 && count <= GEMM_MAX_RUN &&
+  bool gemm_form = cb->e->update_mode == SOMHIP_UPDATE_GEMM && !M && cb->v.d % 128 == 0 && count <= GEMM_MAX_RUN &&
                    ds->n * (int64_t)(cb->v.d >> 2) < (1ll << 32) &&      // the entries carry 32-bit row offsets in float4 units
                    (!G || (cb->v.xdim <= 1024 && cb->ydim <= 1024));
   // one pass over the run's scalars: the smallest rate (for the list tail below), and what the GEMM form cannot take --
   // a rate outside [0, 1] (the backward walk's decay P (1 - a) would change sign and stop it early; NaN fails the test
   // too), or, gaussian, a fixed point with a coordinate above 1023 (it would not fit the entry's 10-bit fields)
   float amin = 1.0f;
-  if (gemm_form) {
-    for (int64_t j = 0; j < count && gemm_form; j++) {
-      const StepScalars &s = h_sc[j];
-      if (!(s.alpha >= 0.0f && s.alpha <= 1.0f)) gemm_form = false;
-      if (G && s.fixed >= 0 && (fixed_x(s.fixed) > 1023 || fixed_y(s.fixed) > 1023)) gemm_form = false;
-      amin = std::min(amin, s.alpha);
-    }
+  for (int64_t j = 0; j < count && gemm_form; j++) {
+    const StepScalars &s = h_sc[j];
+    if (!(s.alpha >= 0.0f && s.alpha <= 1.0f) || (G && s.fixed >= 0 && (fixed_x(s.fixed) > 1023 || fixed_y(s.fixed) > 1023))) gemm_form = false;
+    amin = std::min(amin, s.alpha);
   }
-  const bool off32 = scalar_form && off32_ok && !gemm_form;
-  void *dbxy, *dcnt, *dent;
-  CHK(engine_scratch(e, SLOT_MEMBER_XY, sizeof(int2) * (size_t)count, &dbxy));
-  CHK(engine_scratch(e, SLOT_MEMBER_COUNT, sizeof(uint32_t) * (size_t)cb->v.ngroups, &dcnt));
-  // (GEMM_FRONT_PAD entries in front of the first list: K4m's scalar quarter loads may start before a list)
-  CHK(engine_scratch(e, SLOT_MEMBER_LIST, sizeof(MemberEntry) * ((size_t)cb->v.ngroups * (size_t)list_stride(count) + GEMM_FRONT_PAD), &dent));
-  dent = (MemberEntry *)dent + GEMM_FRONT_PAD;
+  p.off32 = scalar_form && off32_ok && !gemm_form;
+  p.entry = p.off32 ? ENTRY_BYTE : scalar_form || gemm_form ? ENTRY_FLOAT4 : ENTRY_SAMPLE;
+  p.gauss_gemm = G && gemm_form;
   // the winners' lattice coordinates: K4b decodes them itself from the keys (a division per (sample, row group), but no
   // launch) in a short run; a long run pays for the launch many times over (1024 groups x 32768 samples: members 201 -> 180 us, the decode launch 6)
-  const bool decode = G || count >= 16384;                // (the gaussian update needs the decoded winners itself)
-  if (decode) {
-    LaunchTimer t(e, KID_DECODE);
-    hipLaunchKernelGGL(k_decode_winners, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, e->stream,
-                       d_keys, d_sc, count, cb->v.xdim, (int2 *)dbxy);
-    HIPCHK(hipGetLastError());
-  }
+  p.decode = G || count >= 16384;                         // (the gaussian update needs the decoded winners itself)
   // the GEMM update walks a list from its end and stops once every unit's decay is below GEMM_CUT: K4b then makes only
   // the tail that walk can reach -- until it holds `tail_need` entries with every live unit in them: (1 - a_min)^need <
   // GEMM_CUT for the smallest rate a_min of the run, + one chunk so that the walk's last, whole chunk is there too
-  uint32_t tail_need = 0;
-  uint32_t *dlstart = nullptr;
-  if (gemm_form && !G && !getenv("SOMHIP_GEMM_FULL_LISTS")) {
-    if (amin > 1e-6f && amin < 1.0f) {
-      const double need = std::ceil(std::log((double)GEMM_CUT) / std::log1p(-(double)amin)) + GEMM_KT + 1;
-      if (need < (double)count / 2) tail_need = (uint32_t)need;
-    }
-    void *pl;
-    CHK(engine_scratch(e, SLOT_TAIL_START, sizeof(uint32_t) * (size_t)cb->v.ngroups, &pl));
-    dlstart = (uint32_t *)pl;
+  p.tail = gemm_form && !G && !getenv("SOMHIP_GEMM_FULL_LISTS");
+  if (p.tail && amin > 1e-6f && amin < 1.0f) {
+    const double need = std::ceil(std::log((double)GEMM_CUT) / std::log1p(-(double)amin)) + GEMM_KT + 1;
+    if (need < (double)count / 2) p.tail_need = (uint32_t)need;
   }
-  int reach_max = -1;                                      // (see k_som_members: early rejection on the winners' coordinates)
-  if (decode && !G) { for (int64_t j = 0; j < count; j++) reach_max = std::max(reach_max, (int)h_sc[j].reach); }
-  {
-    LaunchTimer t(e, KID_MEMBERS);
-    // a small shard has few row groups: 1024 threads each (one trip over a 4096 batch) instead of 256
-    bool wide = cb->v.ngroups < 512 && count > 1024;
-    // ... and so does a long run whose lists will not be cut short: a trip costs two barriers and a scan whatever it
-    // finds, and with a small neighbourhood it finds a handful of members per 1024 samples (step_probe.py: 0.47 ms per
-    // 32768 vectors at radius 20-33 in trips of 1024, against 0.06 ms at radius 128 where the tail is full after one trip).
-    // Trips of 1024 only while the tail the GEMM update needs is expected within three of them: the share of the samples
-    // whose neighbourhood covers a whole 8 x 8 patch is about area(radius - 6) / units.
-    if (!wide && !G && count >= 8192) {
-      const double r = std::sqrt((double)std::max(h_sc[count - 1].thresh, 0.0f)) - 6.0;
-      const double full = r > 0.0 ? std::min(1.0, 3.6276 * r * r / std::max<double>(1.0, (double)cb->v.xdim * cb->ydim)) : 0.0;
-      wide = tail_need == 0 || (double)tail_need > 3.0 * 1024.0 * full;
-    }
-#define GO(GG, NT, BXY, KEYS)                                                                              \
-    hipLaunchKernelGGL((k_som_members<GG, NT>), dim3((unsigned)cb->v.ngroups), dim3(NT), 0, e->stream, cb->v, count, \
-                       (const int2 *)(BXY), (const uint64_t *)(KEYS), d_sc, (uint32_t *)dcnt, (MemberEntry *)dent, e->d_stats, \
-                       scalar_form || gemm_form ? data_first : (int64_t)-1, ds->n, off32 ? 4 * cb->v.d : cb->v.d >> 2, tail_need, dlstart, \
-                       (GG) && gemm_form ? 1 : 0, reach_max)
-    // (decoded winners, long run, lists not cut short: 8 samples per thread -- four trips over a 32768-vector run; what a
-    // trip costs besides the membership arithmetic of the queued samples is its barriers and dependent loads)
-    const bool deep = wide && !G && decode && reach_max >= 0 && count >= 16384;
-    if (G) { if (wide) GO(true, 1024, dbxy, nullptr); else GO(true, 256, dbxy, nullptr); }
-    else if (deep) hipLaunchKernelGGL((k_som_members<false, 1024, 8>), dim3((unsigned)cb->v.ngroups), dim3(1024), 0, e->stream, cb->v, count,
-                       (const int2 *)dbxy, (const uint64_t *)nullptr, d_sc, (uint32_t *)dcnt, (MemberEntry *)dent, e->d_stats,
-                       scalar_form || gemm_form ? data_first : (int64_t)-1, ds->n, off32 ? 4 * cb->v.d : cb->v.d >> 2, tail_need, dlstart, 0, reach_max);
-    else if (decode) { if (wide) GO(false, 1024, dbxy, nullptr); else GO(false, 256, dbxy, nullptr); }
-    else { if (wide) GO(false, 1024, nullptr, d_keys); else GO(false, 256, nullptr, d_keys); }
-#undef GO
+  // (see k_som_members: early rejection on the winners' coordinates)
+  if (p.decode && !G) { for (int64_t j = 0; j < count; j++) p.reach_max = std::max(p.reach_max, (int)h_sc[j].reach); }
+  // a small shard has few row groups: 1024 threads each (one trip over a 4096 batch) instead of 256
+  bool wide = cb->v.ngroups < 512 && count > 1024;
+  // ... and so does a long run whose lists will not be cut short: a trip costs two barriers and a scan whatever it
+  // finds, and with a small neighbourhood it finds a handful of members per 1024 samples (step_probe.py: 0.47 ms per
+  // 32768 vectors at radius 20-33 in trips of 1024, against 0.06 ms at radius 128 where the tail is full after one trip).
+  // Trips of 1024 only while the tail the GEMM update needs is expected within three of them: the share of the samples
+  // whose neighbourhood covers a whole 8 x 8 patch is about area(radius - 6) / units.
+  if (!wide && !G && count >= 8192) {
+    const double r = std::sqrt((double)std::max(h_sc[count - 1].thresh, 0.0f)) - 6.0;
+    const double full = r > 0.0 ? std::min(1.0, 3.6276 * r * r / std::max<double>(1.0, (double)cb->v.xdim * cb->ydim)) : 0.0;
+    wide = p.tail_need == 0 || (double)p.tail_need > 3.0 * 1024.0 * full;
   }
-  HIPCHK(hipGetLastError());
-  uint32_t *dorder = nullptr;
-  if (cb->v.ngroups <= 8192) {
-    void *p_;
-    CHK(engine_scratch(e, SLOT_STAGE, sizeof(uint32_t) * (size_t)cb->v.ngroups, &p_));
-    dorder = (uint32_t *)p_;
-    LaunchTimer t(e, KID_DECODE);
-    hipLaunchKernelGGL(k_order_groups, dim3((unsigned)((cb->v.ngroups * 8 + 255) / 256)), dim3(256), 0, e->stream,
-                       (const uint32_t *)dcnt, (int)cb->v.ngroups, dorder);
-    HIPCHK(hipGetLastError());
-  }
+  p.members_nt = wide ? 1024 : 256;
+  // (decoded winners, long run, lists not cut short: 8 samples per thread -- four trips over a 32768-vector run; what a
+  // trip costs besides the membership arithmetic of the queued samples is its barriers and dependent loads)
+  p.members_rr = wide && !G && p.decode && p.reach_max >= 0 && count >= 16384 ? 8 : 4;
+  p.order = cb->v.ngroups <= 8192;                        // (k_order_groups holds the counts in LDS)
   if (gemm_form) {
-    LaunchTimer tg(e, KID_SOM_UPDATE_GEMM);
+    p.apply = APPLY_GEMM;
     // dims per workgroup: 256 when the lists are long, 128 when they are short -- a workgroup is then mostly its fixed
     // costs, and more of them run side by side -- or when a small shard would not fill the chip.  Expected entries per
     // list: the run's samples x the share of the map a neighbourhood (dilated by a row group's 8x8 patch) covers.
     // (Round 3: 512-dim workgroups -- 64 KiB of LDS, two per CU -- kept the matrix pipe busy 46 % of the time, the rest
     // was spent waiting for the next chunk's rows; at 256 dims four fit and the kernel is 4-20 % faster at every
     // radius of the configs[3] schedule, profiles/r03_gemm_ntw.txt.)
-    int ntw = G && cb->v.d % 512 == 0 ? 4 : cb->v.d % 256 == 0 ? 2 : 1;      // (gaussian: the rates are made once per workgroup slice -- wide)
-    {
-      const float r = sqrtf(std::max(h_sc[0].thresh, 0.0f)) + 4.5f;
-      const double expect = (double)count * 3.14159265 * r * r / std::max<double>(1.0, (double)cb->v.xdim * cb->ydim);
-      const int by_len = G ? 4 : expect < 64.0 ? 1 : 2;    // (gaussian: every sample is in every list)
-      int by_grid = 4;
-      while (by_grid > 1 && (int64_t)cb->v.ngroups * (cb->v.d / (128 * by_grid)) < 1024) by_grid >>= 1;
-      ntw = std::min(ntw, std::min(by_len, by_grid));
-    }
-    const dim3 ggrid((unsigned)(cb->v.ngroups * (cb->v.d / (128 * ntw))));
-#define GOG(NN) do { if (G) hipLaunchKernelGGL((k_som_update_gemm<NN, true>), ggrid, dim3(256), 0, e->stream, cb->v, ds->d_rows, ds->n, data_first, count, \
-                                   (const uint32_t *)dcnt, (const MemberEntry *)dent, (const uint32_t *)dorder, e->d_stats, \
-                                   (const uint32_t *)dlstart); \
-                else hipLaunchKernelGGL((k_som_update_gemm<NN, false>), ggrid, dim3(256), 0, e->stream, cb->v, ds->d_rows, ds->n, data_first, count, \
-                                   (const uint32_t *)dcnt, (const MemberEntry *)dent, (const uint32_t *)dorder, e->d_stats, \
-                                   (const uint32_t *)dlstart); } while (0)
-    if (ntw == 4) GOG(4); else if (ntw == 2) GOG(2); else GOG(1);
-#undef GOG
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
-  dim3 grid((unsigned)(cb->v.ngroups * ((cb->v.d4 + 4 * QW - 1) / (4 * QW))));   // (row group, slice) items, see the kernel
-  // gaussian, no masks: K4g, one workgroup (up to 16 waves) per row group so that the rates are computed once
-  if (G && !M && (cb->v.d & 3) == 0 && cb->v.d4 % 4 == 0 && count <= ds->n && ds->n < (1ll << 31) && !getenv("SOMHIP_UPD_LDS")) {
-    const int gq = 4;                                      // chunks per wave (8 would need 64 SGPRs for the two x buffers alone)
-    const int per_row = cb->v.d4 / gq;                     // waves needed for one row group
-    int nw = 1;
-    for (int w = 1; w <= 16; w++) if (per_row % w == 0) nw = w;
-    dim3 ggrid((unsigned)(cb->v.ngroups * (per_row / nw)));
-    LaunchTimer tg(e, KID_SOM_UPDATE_RUN);
-    // K4h: the run in one piece in the data set and smaller than 4 GiB, 32 dims per wave
+    p.ntw = G && cb->v.d % 512 == 0 ? 4 : cb->v.d % 256 == 0 ? 2 : 1;    // (gaussian: the rates are made once per workgroup slice -- wide)
+    const float r = sqrtf(std::max(h_sc[0].thresh, 0.0f)) + 4.5f;
+    const double expect = (double)count * 3.14159265 * r * r / std::max<double>(1.0, (double)cb->v.xdim * cb->ydim);
+    const int by_len = G ? 4 : expect < 64.0 ? 1 : 2;     // (gaussian: every sample is in every list)
+    int by_grid = 4;
+    while (by_grid > 1 && (int64_t)cb->v.ngroups * (cb->v.d / (128 * by_grid)) < 1024) by_grid >>= 1;
+    p.ntw = std::min(p.ntw, std::min(by_len, by_grid));
+    p.grid = dim3((unsigned)(cb->v.ngroups * (cb->v.d / (128 * p.ntw)))); p.block = dim3(256);
+  } else if (G && !M && (cb->v.d & 3) == 0 && cb->v.d4 % 4 == 0 && count <= ds->n && ds->n < (1ll << 31) && !getenv("SOMHIP_UPD_LDS")) {
+    // gaussian, no masks: K4g, one workgroup (up to 16 waves) per row group so that the rates are computed once; K4h:
+    // the run in one piece in the data set and smaller than 4 GiB, 32 dims per wave
     const int64_t f0 = data_first % ds->n;
-    if (cb->v.d4 % 8 == 0 && f0 + count <= ds->n && count * (int64_t)cb->v.d * 4 < (1ll << 32)) {
-      const int per_row8 = cb->v.d4 / 8;
-      int nw8 = 1;
-      for (int w = 1; w <= 16; w++) if (per_row8 % w == 0) nw8 = w;
-      dim3 hgrid((unsigned)(cb->v.ngroups * (per_row8 / nw8)));
-      const float *xrun = ds->d_rows + f0 * cb->v.d;
-      hipLaunchKernelGGL(k_som_update_gauss_h, hgrid, dim3(64 * nw8), 0, e->stream, cb->v, xrun, count,
-                         (const int2 *)dbxy, d_sc, (const uint32_t *)dcnt, (const MemberEntry *)dent, (const uint32_t *)dorder);
-      HIPCHK(hipGetLastError());
-      return 0;
-    }
-    hipLaunchKernelGGL((k_som_update_gauss_s<4>), ggrid, dim3(64 * nw), 0, e->stream, cb->v, ds->d_rows, ds->n, data_first, count,
-                       (const int2 *)dbxy, d_sc, (const uint32_t *)dcnt, (const MemberEntry *)dent, (const uint32_t *)dorder);
-    HIPCHK(hipGetLastError());
-    return 0;
+    p.apply = cb->v.d4 % 8 == 0 && f0 + count <= ds->n && count * (int64_t)cb->v.d * 4 < (1ll << 32) ? APPLY_GAUSS_H : APPLY_GAUSS_S;
+    const int gq = p.apply == APPLY_GAUSS_H ? 8 : 4;     // chunks per wave (K4g: 8 would need 64 SGPRs for the two x buffers alone)
+    const int per_row = cb->v.d4 / gq;                    // waves needed for one row group
+    int nw = 1;                                           // (the most waves, up to 16, that split the row group evenly)
+    for (int w = 1; w <= 16; w++) if (per_row % w == 0) nw = w;
+    p.grid = dim3((unsigned)(cb->v.ngroups * (per_row / nw))); p.block = dim3(64 * nw);
+  } else {
+    // bubble: the scalar-operand kernel K4s when it can take the run (packed fp32: 1.44 -> 1.16 ms on the 256x256x512
+    // map), else K4's LDS tiles (a shard so small that QW fell to 2: 244 vs 282 us on an eighth of the 256x256x512 map)
+    p.apply = scalar_form ? APPLY_BUBBLE_S : APPLY_RUN; p.qw = QW;
+    p.grid = dim3((unsigned)(cb->v.ngroups * ((cb->v.d4 + 4 * QW - 1) / (4 * QW)))); p.block = dim3(256);   // (row group, slice) items, see the kernel
   }
-  LaunchTimer t(e, scalar_form ? KID_SOM_UPDATE_BUBBLE_S : KID_SOM_UPDATE_RUN);
-  // bubble, no masks, whole chunks, enough waves at 4 chunks each: the scalar-operand kernel K4s (a shard so small
-  // that QW fell to 2 is better off with K4's pipelined tile walk: 244 vs 282 us on an eighth of the 256x256x512 map)
-  if (scalar_form) {
-    // (packed fp32: 1.44 -> 1.16 ms on the 256x256x512 map)
-#define GOS(QQ)                                                                                      \
-    if (off32) hipLaunchKernelGGL((k_som_update_bubble_s<QQ, true>), grid, dim3(256), 0, e->stream, cb->v, ds->d_rows, ds->n, data_first, \
-                       count, (const uint32_t *)dcnt, (const MemberEntry *)dent, (const uint32_t *)dorder);          \
-    else hipLaunchKernelGGL((k_som_update_bubble_s<QQ>), grid, dim3(256), 0, e->stream, cb->v, ds->d_rows, ds->n, data_first, \
-                       count, (const uint32_t *)dcnt, (const MemberEntry *)dent, (const uint32_t *)dorder)
-    if (QW == 4) { GOS(4); } else { GOS(2); }
-#undef GOS
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
-#define GO(QQ, GG, MM)                                                                               \
-  hipLaunchKernelGGL((k_som_update_run<QQ, TB, GG, MM>), grid, dim3(256), 0, e->stream, cb->v, ds->d_rows, \
-                     (const uint8_t *)ds->d_mask, ds->n, data_first, count, (const int2 *)dbxy, d_sc,   \
-                     (const uint32_t *)dcnt, (const MemberEntry *)dent, (const uint32_t *)dorder)
-#define GOQ(QQ)                                                                                      \
-  do { if (G && M) { GO(QQ, true, true); } else if (G) { GO(QQ, true, false); } else if (M) { GO(QQ, false, true); } else { GO(QQ, false, false); } } while (0)
-  if (QW == 4) GOQ(4); else GOQ(2);
-#undef GOQ
-#undef GO
-  HIPCHK(hipGetLastError());
+  return p;
+}
+// each stage takes its scratch slots where it starts: the lists' here, the tail starts (members) and the group order (order)
+struct UpdateBufs { int2 *bxy; uint32_t *cnt; MemberEntry *lists; uint32_t *lstart, *order; };
+static int bind_update(somhip_engine *e, const somhip_codebook *cb, int64_t count, UpdateBufs *b) {
+  void *xy, *cnt, *region;
+  CHK(engine_scratch(e, SLOT_MEMBER_XY, sizeof(int2) * (size_t)count, &xy));
+  CHK(engine_scratch(e, SLOT_MEMBER_COUNT, sizeof(uint32_t) * (size_t)cb->v.ngroups, &cnt));
+  // the lists start GEMM_FRONT_PAD entries into their region: K4m's scalar quarter loads may start before a list
+  CHK(engine_scratch(e, SLOT_MEMBER_LIST, sizeof(MemberEntry) * ((size_t)cb->v.ngroups * (size_t)list_stride(count) + GEMM_FRONT_PAD), &region));
+  *b = {(int2 *)xy, (uint32_t *)cnt, (MemberEntry *)region + GEMM_FRONT_PAD, nullptr, nullptr};
   return 0;
 }
+static int update_members(somhip_engine *e, const somhip_codebook *cb, const somhip_dataset *ds, const UpdatePlan &p,
+                          int64_t data_first, int64_t count, const uint64_t *d_keys, const StepScalars *d_sc, UpdateBufs &b) {
+  if (p.tail) { void *ls; CHK(engine_scratch(e, SLOT_TAIL_START, sizeof(uint32_t) * (size_t)cb->v.ngroups, &ls)); b.lstart = (uint32_t *)ls; }
+  LaunchTimer t(e, KID_MEMBERS);
+  const int rc = with_value<1, 0>(cb->v.neigh == SOMHIP_NEIGH_GAUSSIAN, [&](auto g) { return with_value<1024, 256>(p.members_nt, [&](auto nt) {
+    return with_value<8, 4>(p.members_rr, [&](auto rr) {
+      constexpr bool GG = decltype(g)::value != 0; constexpr int NT = decltype(nt)::value, RR = decltype(rr)::value;
+      if constexpr (RR == 4 || (!GG && NT == 1024)) {    // (8 samples per thread: bubble, 1024 threads only)
+        hipLaunchKernelGGL((k_som_members<GG, NT, RR>), dim3((unsigned)cb->v.ngroups), dim3(NT), 0, e->stream, cb->v, count,
+                           p.decode ? b.bxy : nullptr, p.decode ? nullptr : d_keys, d_sc, b.cnt, b.lists, e->d_stats,
+                           p.entry == ENTRY_SAMPLE ? (int64_t)-1 : data_first, ds->n, p.entry == ENTRY_BYTE ? 4 * cb->v.d : cb->v.d >> 2,
+                           p.tail_need, b.lstart, p.gauss_gemm ? 1 : 0, p.reach_max); return 0;
+      } else return fail("update_members: no k_som_members<%d, %d, %d> is built", (int)GG, NT, RR);
+  }); }); });
+  CHK(rc); HIPCHK(hipGetLastError());
+  return 0;
+}
+static int update_apply(somhip_engine *e, const somhip_codebook *cb, const somhip_dataset *ds, const UpdatePlan &p,
+                        int64_t data_first, int64_t count, const StepScalars *d_sc, const UpdateBufs &b) {
+  const bool G = cb->v.neigh == SOMHIP_NEIGH_GAUSSIAN, M = ds->d_mask != nullptr;
+  LaunchTimer t(e, p.apply == APPLY_GEMM ? KID_SOM_UPDATE_GEMM : p.apply == APPLY_BUBBLE_S ? KID_SOM_UPDATE_BUBBLE_S : KID_SOM_UPDATE_RUN);
+  int rc = 0;                                             // (with_value: a plan value no launch was built for)
+  if (p.apply == APPLY_GEMM)
+    rc = with_value<4, 2, 1>(p.ntw, [&](auto n) { return with_value<1, 0>(G, [&](auto g) {
+      hipLaunchKernelGGL((k_som_update_gemm<decltype(n)::value, decltype(g)::value != 0>), p.grid, p.block, 0, e->stream, cb->v,
+                         ds->d_rows, ds->n, data_first, count, b.cnt, b.lists, b.order, e->d_stats, b.lstart); return 0;
+    }); });
+  else if (p.apply == APPLY_GAUSS_H)
+    hipLaunchKernelGGL(k_som_update_gauss_h, p.grid, p.block, 0, e->stream, cb->v, ds->d_rows + data_first % ds->n * cb->v.d,
+                       count, b.bxy, d_sc, b.cnt, b.lists, b.order);
+  else if (p.apply == APPLY_GAUSS_S)
+    hipLaunchKernelGGL((k_som_update_gauss_s<4>), p.grid, p.block, 0, e->stream, cb->v, ds->d_rows, ds->n, data_first, count,
+                       b.bxy, d_sc, b.cnt, b.lists, b.order);
+  else if (p.apply == APPLY_BUBBLE_S)
+    rc = with_value<4, 2>(p.qw, [&](auto q) { return with_value<1, 0>(p.off32, [&](auto o) {
+      hipLaunchKernelGGL((k_som_update_bubble_s<decltype(q)::value, decltype(o)::value != 0>), p.grid, p.block, 0, e->stream,
+                         cb->v, ds->d_rows, ds->n, data_first, count, b.cnt, b.lists, b.order); return 0;
+    }); });
+  else
+    rc = with_value<4, 2>(p.qw, [&](auto q) { return with_value<1, 0>(G, [&](auto g) { return with_value<1, 0>(M, [&](auto m) {
+      hipLaunchKernelGGL((k_som_update_run<decltype(q)::value, 32, decltype(g)::value != 0, decltype(m)::value != 0>), p.grid,
+                         p.block, 0, e->stream, cb->v, ds->d_rows, (const uint8_t *)ds->d_mask, ds->n, data_first, count, b.bxy,
+                         d_sc, b.cnt, b.lists, b.order); return 0;
+    }); }); });
+  CHK(rc); HIPCHK(hipGetLastError());
+  return 0;
+}
+static int som_update_run(somhip_codebook *cb, somhip_dataset *ds, int64_t data_first, int64_t count,
+                          const uint64_t *d_keys, const StepScalars *d_sc, const StepScalars *h_sc) {
+  somhip_engine *e = cb->e;
+  cb->prep_valid = false;
+  const UpdatePlan p = som_update_plan(cb, ds, data_first, count, h_sc);
+  UpdateBufs b; CHK(bind_update(e, cb, count, &b));
+  if (p.decode) {
+    LaunchTimer t(e, KID_DECODE);
+    hipLaunchKernelGGL(k_decode_winners, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, e->stream, d_keys, d_sc, count, cb->v.xdim, b.bxy);
+    HIPCHK(hipGetLastError());
+  }
+  CHK(update_members(e, cb, ds, p, data_first, count, d_keys, d_sc, b));
+  if (p.order) {
+    void *ord; CHK(engine_scratch(e, SLOT_STAGE, sizeof(uint32_t) * (size_t)cb->v.ngroups, &ord)); b.order = (uint32_t *)ord;
+    LaunchTimer t(e, KID_DECODE);                          // (timed with k_decode_winners)
+    hipLaunchKernelGGL(k_order_groups, dim3((unsigned)((cb->v.ngroups * 8 + 255) / 256)), dim3(256), 0, e->stream, b.cnt, (int)cb->v.ngroups, b.order);
+    HIPCHK(hipGetLastError());
+  }
+  return update_apply(e, cb, ds, p, data_first, count, d_sc, b);
+}
+// the plan som_update_run makes for a run (somhip.h): the same checks as somhip_som_batch_update, host arithmetic only
+extern "C" int somhip_debug_update_plan(somhip_codebook *cb, somhip_dataset *ds, const somhip_som_params *p, int64_t batch_start_iter,
+                                        int64_t count, int64_t data_first, int32_t *out) try {
+  CHK(check_pair(cb, ds, "somhip_debug_update_plan"));
+  if (cb->v.topol < SOMHIP_TOPOL_HEXA) return fail("somhip_debug_update_plan: codebook is not a map");
+  if (!p || !out || count <= 0) return fail("somhip_debug_update_plan: null argument, or count %lld < 1", (long long)count);
+  std::vector<StepScalars> sc((size_t)count);
+  CHK(som_scalars(cb, ds, p, batch_start_iter, count, data_first % ds->n, sc.data()));
+  const UpdatePlan u = som_update_plan(cb, ds, data_first % ds->n, count, sc.data());
+  const int32_t v[16] = {u.apply, u.qw, u.off32, u.ntw, u.decode, u.members_nt, u.members_rr, u.entry, u.gauss_gemm, u.tail,
+                         (int32_t)u.tail_need, u.reach_max, u.order, (int32_t)u.grid.x, (int32_t)u.block.x, 0};
+  memcpy(out, v, sizeof v);
+  return 0;
+} ABI_CATCH(somhip_debug_update_plan)
 
 extern "C" int somhip_som_batch_update(somhip_codebook *cb, somhip_dataset *ds,
                                        const somhip_som_params *p, int64_t batch_start_iter,
@@ -500,14 +509,7 @@ static int som_train_batched(somhip_codebook *cb, somhip_dataset *ds, const somh
     if (trace) {
       HIPCHK(hipMemcpyAsync(hk.data(), dkeys, sizeof(uint64_t) * (size_t)c, hipMemcpyDeviceToHost, e->stream));
       HIPCHK(hipStreamSynchronize(e->stream));
-      for (int64_t j = 0; j < c; j++) {
-        int32_t idx; float df;
-        if (hsc[j].fixed >= 0) { idx = -3; df = -1.0f; }
-        else if (hsc[j].reach < 0) { idx = -2; df = -1.0f; }
-        else decode_key(hk[(size_t)j], false, &idx, &df);
-        if (trace_index) trace_index[off + j] = idx;
-        if (trace_diff) trace_diff[off + j] = df;
-      }
+      som_trace(hsc, hk.data(), c, off, trace_index, trace_diff);
     }
     off += c;
   }
@@ -528,9 +530,7 @@ extern "C" int somhip_som_train(somhip_codebook *cb, somhip_dataset *ds, const s
     return fail("somhip_som_train: sharded codebook -- use somhip_batch_winner_keys + somhip_som_batch_update");
   if (p->count == 0) return 0;
   HIPCHK(hipSetDevice(cb->e->device));
-  // SOMHIP_BATCH_AUTO where the rule does not vouch for mini-batches: the reference's own schedule
-  if (p->batch == SOMHIP_BATCH_AUTO && som_auto_plan(p, cb->n_global, cb->v.topol, cb->v.neigh).online)
-    return som_train_online(cb, ds, p, trace_index, trace_diff);
-  if (p->batch <= 1 && p->batch != SOMHIP_BATCH_AUTO) return som_train_online(cb, ds, p, trace_index, trace_diff);
-  return som_train_batched(cb, ds, p, trace_index, trace_diff);
+  // batch 1, or SOMHIP_BATCH_AUTO where the rule does not vouch for mini-batches: the reference's own schedule
+  const bool online = p->batch == SOMHIP_BATCH_AUTO ? som_auto_plan(p, cb->n_global, cb->v.topol, cb->v.neigh).online : p->batch <= 1;
+  return online ? som_train_online(cb, ds, p, trace_index, trace_diff) : som_train_batched(cb, ds, p, trace_index, trace_diff);
 } ABI_CATCH(somhip_som_train)

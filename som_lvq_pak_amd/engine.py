@@ -325,6 +325,25 @@ def scan_plan(cb, ds, count, want=1):
             "by_group": bool(out[4]), "l2_global": bool(out[5]), "fused_gmin": bool(out[6])}
 
 
+UPDATE_APPLY = ("gemm", "gauss_h", "gauss_s", "bubble_s", "run")
+UPDATE_ENTRY = ("sample", "float4", "byte")
+
+
+def update_plan(cb, ds, length, alpha, radius, count, alpha_type=ALPHA_LINEAR, use_fixed=0, use_weights=0, start_iter=0,
+                data_first=None):
+    """The plan of the mini-batch update of iterations [start_iter, start_iter + count) of a schedule of `length` on data
+    rows from data_first (somhip_debug_update_plan; host arithmetic, no GPU work): a dict of the apply kernel and the
+    stage choices before it, with the engine's current update mode."""
+    data_first = start_iter % ds.n if data_first is None else data_first
+    p = SomParams(length, alpha, radius, alpha_type, use_fixed, use_weights, count, start_iter, count, data_first)
+    out = (C.c_int32 * 16)()
+    check(cb.e.lib.somhip_debug_update_plan(cb.h, ds.h, C.byref(p), start_iter, count, data_first, out))
+    return {"apply": UPDATE_APPLY[out[0]], "qw": out[1], "off32": bool(out[2]), "ntw": out[3], "decode": bool(out[4]),
+            "members_nt": out[5], "members_rr": out[6], "entry": UPDATE_ENTRY[out[7]], "gauss_gemm": bool(out[8]),
+            "tail": bool(out[9]), "tail_need": out[10], "reach_max": out[11], "order": bool(out[12]),
+            "grid": out[13], "block": out[14]}
+
+
 def som_train(cb, ds, length, alpha, radius, alpha_type=ALPHA_LINEAR, use_fixed=0, use_weights=0,
               batch=1, start_iter=0, count=None, data_first=None, trace=True):
     """som_training (reference som_rout.c:556); returns (trace_index, trace_diff)."""

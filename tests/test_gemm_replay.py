@@ -228,6 +228,9 @@ def _run(eng, E, ini, cs, ds, mode, monkeypatch, full=False):
         monkeypatch.setenv("SOMHIP_GEMM_FULL_LISTS", "1")
     try:
         cb = E.Codebook(eng, ini, cs["topol"], cs["neigh"], cs["xd"], cs["yd"])
+        plan = E.update_plan(cb, ds, cs["length"], cs["alpha"], cs["radius"], cs["B"], alpha_type=cs["alpha_type"],
+                             use_fixed=cs["use_fixed"], use_weights=cs["use_weights"], start_iter=cs["it0"],
+                             data_first=cs["first"])
         s0 = eng.scan_stats()["gemm_entries"]
         ti, _ = E.som_train(cb, ds, cs["length"], cs["alpha"], cs["radius"], alpha_type=cs["alpha_type"],
                             use_fixed=cs["use_fixed"], use_weights=cs["use_weights"], batch=cs.get("batch", cs["B"]), start_iter=cs["it0"],
@@ -238,7 +241,7 @@ def _run(eng, E, ini, cs, ds, mode, monkeypatch, full=False):
     finally:
         eng.set_update_mode("exact")
         monkeypatch.delenv("SOMHIP_GEMM_FULL_LISTS", raising=False)
-    return out, ti, ran
+    return out, ti, ran, plan
 
 
 @pytest.mark.gpu
@@ -254,8 +257,8 @@ def test_gemm_update_against_float64_replay(eng, E, oracle, monkeypatch, name):
     x, wt, fx, ini = make_inputs(1000 + sorted(CASES).index(name), cs["n"], cs["d"], xd, yd, cs["weights"], cs["fixed"],
                                  cs["every"], cs["same"])
     ds = E.Dataset(eng, x, weight=wt, fixed_xy=fx)
-    exact, ti_e, ran_e = _run(eng, E, ini, cs, ds, "exact", monkeypatch)
-    gemm, ti_g, ran_g = _run(eng, E, ini, cs, ds, "gemm", monkeypatch)
+    exact, ti_e, ran_e, _ = _run(eng, E, ini, cs, ds, "exact", monkeypatch)
+    gemm, ti_g, ran_g, plan_g = _run(eng, E, ini, cs, ds, "gemm", monkeypatch)
     assert ran_e == 0
     assert np.array_equal(ti_e, ti_g), name
     kw = dict(xdim=xd, ydim=yd, topol=cs["topol"], neigh=cs["neigh"], data=x, length=cs["length"], alpha=cs["alpha"],
@@ -271,14 +274,14 @@ def test_gemm_update_against_float64_replay(eng, E, oracle, monkeypatch, name):
         assert np.array_equal(ti_e, wi), name
         assert np.array_equal(bits(exact), bits(want)), name
     if not cs["gemm"]:
-        assert ran_g == 0, name                           # the matrix-pipe kernel did not run ...
+        assert ran_g == 0 and plan_g["apply"] != "gemm", name   # the matrix-pipe kernel did not run ...
         assert np.array_equal(bits(gemm), bits(exact)), name   # ... and the fallback is the exact kernels
         if not oracle_ok:
             assert np.array_equal(bits(exact), bits(replay(ini, **kw).codes)), name
         ds.close()
         return
     assert ran_g > 0, name                                # the matrix-pipe kernel really ran
-    full, ti_f, ran_f = _run(eng, E, ini, cs, ds, "gemm", monkeypatch, full=True)
+    full, ti_f, ran_f, _ = _run(eng, E, ini, cs, ds, "gemm", monkeypatch, full=True)
     ds.close()
     assert np.array_equal(ti_f, ti_g) and np.array_equal(bits(full), bits(gemm)), name   # tail lists == whole lists
     units = None
@@ -308,8 +311,8 @@ def test_gemm_result_is_outside_the_allowance_of_a_faulted_replay(eng, E, monkey
     ds = E.Dataset(eng, x, fixed_xy=fx)
     cs = dict(xd=kw["xdim"], yd=kw["ydim"], topol=HEXA, neigh=neigh, length=kw["length"], alpha=kw["alpha"],
               radius=kw["radius"], alpha_type=1, use_fixed=1, use_weights=0, B=kw["count"], it0=0, first=0)
-    exact, ti, _ = _run(eng, E, ini, cs, ds, "exact", monkeypatch)
-    gemm, ti_g, ran = _run(eng, E, ini, cs, ds, "gemm", monkeypatch)
+    exact, ti, _, _ = _run(eng, E, ini, cs, ds, "exact", monkeypatch)
+    gemm, ti_g, ran, _ = _run(eng, E, ini, cs, ds, "gemm", monkeypatch)
     ds.close()
     assert np.array_equal(ti, ti_g)
     kw = dict(kw, winners=ti)

@@ -907,6 +907,8 @@ def test_long_batches_take_the_decoded_winner_path_and_equal_the_oracle(eng, E, 
     oc, oi, od = oracle.som_train(ini, 64, 48, topol, 1, x, L, 0.06, radius, fixed_xy=fixed, fixed_on=1, batch=B)
     cb = E.Codebook(eng, ini, topol, 1, 64, 48)
     ds = E.Dataset(eng, x, fixed_xy=fixed)
+    plan = E.update_plan(cb, ds, L, 0.06, radius, B, use_fixed=1)
+    assert plan["decode"] and plan["members_nt"] == 1024 and plan["members_rr"] == 8 and plan["reach_max"] >= 0
     ti, td = E.som_train(cb, ds, L, 0.06, radius, use_fixed=1, batch=B)
     assert np.array_equal(ti, oi) and np.array_equal(bits(td), bits(od))
     assert np.array_equal(bits(cb.download()), bits(oc))
@@ -932,6 +934,9 @@ def test_long_batches_gemm_form_tail_lists_equal_full_lists(eng, E, monkeypatch)
                 monkeypatch.delenv("SOMHIP_GEMM_FULL_LISTS", raising=False)
             eng.set_update_mode(mode)
             cb = E.Codebook(eng, ini, 3, 1, 64, 48)
+            plan = E.update_plan(cb, ds, 100000, 0.05, radius, 20000, start_iter=it0, data_first=0)
+            assert plan["decode"] and (plan["apply"] == "gemm") == (mode == "gemm"), (tag, plan)
+            assert plan["tail"] == (tag == "tail"), (tag, plan)
             ti, _ = E.som_train(cb, ds, 100000, 0.05, radius, batch=20000, start_iter=it0, count=20000, data_first=0)
             out[tag] = (ti, cb.download())
             cb.close()
@@ -1053,6 +1058,7 @@ def test_scalar_operand_update_kernels_vs_oracle(eng, E, oracle, shape, monkeypa
         if form == "lds":
             monkeypatch.setenv("SOMHIP_UPD_LDS", "1")
         cb = E.Codebook(eng, ini, topol, neigh, xdim, ydim)
+        plan = E.update_plan(cb, ds, length, 0.06, 6.0, batch)          # (the first batch's)
         eng.timing(True)
         eng.timing_reset()
         ti, td = E.som_train(cb, ds, length, 0.06, 6.0, batch=batch)
@@ -1064,8 +1070,10 @@ def test_scalar_operand_update_kernels_vs_oracle(eng, E, oracle, shape, monkeypa
         assert np.array_equal(bits(got[form]), bits(oc)), form
         if form == "scalar" and neigh == 1:
             assert table["k_som_update_bubble_s"][0] > 0               # the kernel under test did run (dim % 64 == 0)
+            assert plan["apply"] == "bubble_s" and plan["qw"] == 4
         if form == "lds":
             assert table["k_som_update_bubble_s"][0] == 0 and table["k_som_update_run"][0] > 0
+            assert plan["apply"] == "run" and plan["qw"] == 4
 
 
 @pytest.mark.parametrize("batch", [64, 61, 4])
@@ -1080,12 +1088,14 @@ def test_scalar_update_kernel_full_lists(eng, E, oracle, batch, monkeypatch):
     length = 61 * 12
     oc, oi, od = oracle.som_train(ini, xdim, ydim, 3, 1, x, length, 0.04, 60.0, batch=batch)
     cb, ds = E.Codebook(eng, ini, 3, 1, xdim, ydim), E.Dataset(eng, x)
+    plan = E.update_plan(cb, ds, length, 0.04, 60.0, batch)
     eng.timing(True)
     eng.timing_reset()
     ti, td = E.som_train(cb, ds, length, 0.04, 60.0, batch=batch)
     ran = eng.timing_table()["k_som_update_bubble_s"][0]
     eng.timing(False)
     assert ran > 0
+    assert plan["apply"] == "bubble_s" and plan["qw"] == 4
     assert np.array_equal(ti, oi) and np.array_equal(bits(td), bits(od))
     assert np.array_equal(bits(cb.download()), bits(oc))
 
