@@ -230,9 +230,9 @@ int  somhip_som_auto_batch(const somhip_som_params *p, int64_t n_units, int topo
  * reference, bit for bit; internally the loop runs as exact speculative batches (one
  * frozen-codebook scan per batch, samples certified and applied in order; see
  * kernels.hpp K6) unless SOMHIP_LVQ_ONLINE=1 or a row does not fit the on-chip cache
- * (dim > 2048) or the data set is masked, in which case every iteration is its own launch.
+ * (dim > 2048), in which case every iteration is its own launch.
  * Masked data: distances and adapt_vector skip the sample's masked components
- * (lvq_pak.c:65-69, 179-186, 343-347); a run that would visit a row with every component
+ * (lvq_pak.c:65-69, 179-186, 343-347), in the batched engine as in the per-iteration loop; a run that would visit a row with every component
  * masked is refused before anything is trained (the reference dereferences a NULL winner
  * there, lvq_rout.c:542-545).  The trace has knn entries per iteration (knn = 2 for
  * LVQ2/LVQ3, else 1). */
@@ -348,7 +348,9 @@ int  somhip_merge_topk_keys(somhip_engine *e, const uint64_t *dev_gathered, int 
  *        were applied -- the same number on every rank; the next batch starts there.  A winner beyond the `xrows`
  *        exchanged rows ends the batch early (a larger xrows trades exchange volume for longer batches; 8 = never).
  * trace_index / trace_diff: as somhip_lvq_train, for the consumed iterations.
- * Masked data sets are refused by somhip_lvq_batch_apply (the batched walk takes no masks); somhip_lvq_train runs them. */
+ * Masked data sets are accepted (every rank's data set carries the masks: the scan of step 1 and the walk of step 3
+ * use the sample's mask); a batch that contains a row with every component masked is refused by
+ * somhip_lvq_batch_apply with a message naming the row, as somhip_lvq_train refuses such a run. */
 int  somhip_lvq_rates_upload(somhip_codebook *cb, const float *talpha);     /* [n_rows] local rows, lvq_rout.c:614-627 */
 int  somhip_lvq_rates_download(somhip_codebook *cb, float *talpha);
 int  somhip_lvq_batch_candidates(somhip_codebook *cb, int64_t count, int kind, const uint64_t *dev_keys, int xrows,

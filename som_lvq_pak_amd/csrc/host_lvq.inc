@@ -38,15 +38,62 @@ static int lvq_batch_bufs(somhip_engine *e, int d4, LvqBatchBufs *b) {
 }
 
 // relation (*) over all pairs of the batch: Gram form on the matrix pipe where the shape allows (SOMHIP_LVQ_PAIRS_VALU=1:
-// always the direct-form kernel)
+// always the direct-form kernel); masked data: the direct-form kernel over the components both samples have
 static int lvq_launch_pair_adj(somhip_engine *e, somhip_dataset *ds, const LvqBatchBufs &b, int64_t row0, int c) {
   const unsigned nt = (unsigned)((c + 63) / 64);
-  if (ds->d % 8 == 0 && !getenv("SOMHIP_LVQ_PAIRS_VALU"))
+  if (ds->d_mask)
+    hipLaunchKernelGGL(k_lvq_pair_adj<true>, dim3(nt, nt), dim3(256), 0, e->stream, ds->d_rows, ds->n, ds->d, row0, c,
+                       (const float *)b.rho, b.adj, (const uint8_t *)ds->d_mask);
+  else if (ds->d % 8 == 0 && !getenv("SOMHIP_LVQ_PAIRS_VALU"))
     hipLaunchKernelGGL(k_lvq_pair_adj_mfma, dim3(nt, nt), dim3(256), 0, e->stream, ds->d_rows, ds->n, ds->d, row0, c,
                        (const float *)b.rho, (const float *)b.xnorm, b.adj);
   else
-    hipLaunchKernelGGL(k_lvq_pair_adj, dim3(nt, nt), dim3(256), 0, e->stream, ds->d_rows, ds->n, ds->d, row0, c,
+    hipLaunchKernelGGL(k_lvq_pair_adj<false>, dim3(nt, nt), dim3(256), 0, e->stream, ds->d_rows, ds->n, ds->d, row0, c,
                        (const float *)b.rho, b.adj);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// the walk's row cache and the component kernel's adjacency rows need more dynamic LDS than the default limit
+static int lvq_set_attrs(somhip_engine *e) {
+  if (e->lvq_apply_attr_set) return 0;                    // per engine (= per device), not per process
+  HIPCHK(hipFuncSetAttribute((const void *)k_lvq_batch_apply<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LVQ_DYN_LDS));
+  HIPCHK(hipFuncSetAttribute((const void *)k_lvq_batch_apply<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LVQ_DYN_LDS));
+  HIPCHK(hipFuncSetAttribute((const void *)k_lvq_components, hipFuncAttributeMaxDynamicSharedMemorySize, LVQ_BMAX * LVQ_AW * 4));
+  e->lvq_apply_attr_set = true;
+  return 0;
+}
+
+// rho_j of relation (*) for every sample of the batch (masked data: the sample's norm over its own components)
+static int lvq_launch_sample_rho(somhip_engine *e, somhip_dataset *ds, const LvqBatchBufs &b, int64_t row0, int c,
+                                 const uint64_t *d_cand, float amax, bool amax_on_device) {
+  const float *amax_dev = amax_on_device ? (const float *)b.amax_dev : (const float *)nullptr;
+  if (ds->d_mask)
+    hipLaunchKernelGGL(k_lvq_sample_rho<true>, dim3((unsigned)((c + 3) / 4)), dim3(256), 0, e->stream, ds->d_rows, ds->n, ds->d,
+                       row0, c, d_cand, amax, amax_dev, b.rho, b.xnorm, (const uint8_t *)ds->d_mask);
+  else
+    hipLaunchKernelGGL(k_lvq_sample_rho<false>, dim3((unsigned)((c + 3) / 4)), dim3(256), 0, e->stream, ds->d_rows, ds->n, ds->d,
+                       row0, c, d_cand, amax, amax_dev, b.rho, b.xnorm);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// the walk itself: one workgroup per component (k_lvq_batch_apply<true> stages the sample's mask row beside the sample)
+static int lvq_launch_walk(somhip_codebook *cb, somhip_dataset *ds, const LvqBatchBufs &b, const LvqStep *d_st, int64_t row0,
+                           int c, int limit, int knn, const uint64_t *d_cand, const int32_t *d_lab, const float *d_ta,
+                           const float4 *d_xrows, int xc, uint64_t *d_fin) {
+  somhip_engine *e = cb->e;
+  const int slots = lvq_cache_slots(cb->v.d4);
+  const size_t dyn = ((size_t)cb->v.d4 * slots + 3 * (size_t)cb->v.d4) * sizeof(float4);
+  LaunchTimer t(e, KID_LVQ_BATCH_APPLY);
+  if (ds->d_mask)
+    hipLaunchKernelGGL(k_lvq_batch_apply<true>, dim3((unsigned)c), dim3(LVQ_BT), dyn, e->stream, cb->v, ds->d_rows, ds->n, row0,
+                       limit, d_lab, d_ta, d_xrows, xc, d_cand, d_st, knn, slots, (const int32_t *)b.comp_samples, d_fin,
+                       b.stage_rows, b.stage_rowid, b.stage_ta, b.out, (const uint8_t *)ds->d_mask);
+  else
+    hipLaunchKernelGGL(k_lvq_batch_apply<false>, dim3((unsigned)c), dim3(LVQ_BT), dyn, e->stream, cb->v, ds->d_rows, ds->n, row0,
+                       limit, d_lab, d_ta, d_xrows, xc, d_cand, d_st, knn, slots, (const int32_t *)b.comp_samples, d_fin,
+                       b.stage_rows, b.stage_rowid, b.stage_ta, b.out);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -62,19 +109,12 @@ static int lvq_walk_batch(somhip_codebook *cb, somhip_dataset *ds, const LvqBatc
                           const float4 *d_xrows, int xc, float amax, bool amax_on_device, uint64_t *d_fin,
                           int *consumed, int *reason, int64_t *nmod_bound) {
   somhip_engine *e = cb->e;
-  const int slots = lvq_cache_slots(cb->v.d4);
-  const size_t dyn = ((size_t)cb->v.d4 * slots + 3 * (size_t)cb->v.d4) * sizeof(float4);
-  if (!e->lvq_apply_attr_set) {                           // per engine (= per device), not per process
-    HIPCHK(hipFuncSetAttribute((const void *)k_lvq_batch_apply, hipFuncAttributeMaxDynamicSharedMemorySize, LVQ_DYN_LDS));
-    HIPCHK(hipFuncSetAttribute((const void *)k_lvq_components, hipFuncAttributeMaxDynamicSharedMemorySize, LVQ_BMAX * LVQ_AW * 4));
-    e->lvq_apply_attr_set = true;
-  }
+  CHK(lvq_set_attrs(e));
   const bool single = getenv("SOMHIP_LVQ_SERIAL") != nullptr;
   {
     LaunchTimer t(e, KID_LVQ_COMPONENTS);
     if (!single) {
-      hipLaunchKernelGGL(k_lvq_sample_rho, dim3((unsigned)((c + 3) / 4)), dim3(256), 0, e->stream, ds->d_rows, ds->n, ds->d, row0, c,
-                         d_cand, amax, amax_on_device ? (const float *)b.amax_dev : (const float *)nullptr, b.rho, b.xnorm);
+      CHK(lvq_launch_sample_rho(e, ds, b, row0, c, d_cand, amax, amax_on_device));
       CHK(lvq_launch_pair_adj(e, ds, b, row0, c));
     }
     hipLaunchKernelGGL(k_lvq_components, dim3(1), dim3(LVQ_BMAX), (size_t)c * LVQ_AW * 4, e->stream, (const uint32_t *)b.adj, c,
@@ -86,13 +126,7 @@ static int lvq_walk_batch(somhip_codebook *cb, somhip_dataset *ds, const LvqBatc
   LvqBatchOut *ho = reinterpret_cast<LvqBatchOut *>(hbuf.data());
   int limit = c;
   for (int pass = 0; pass < 2; pass++) {
-    {
-      LaunchTimer t(e, KID_LVQ_BATCH_APPLY);
-      hipLaunchKernelGGL(k_lvq_batch_apply, dim3((unsigned)c), dim3(LVQ_BT), dyn, e->stream, cb->v, ds->d_rows, ds->n, row0,
-                         limit, d_lab, d_ta, d_xrows, xc, d_cand, d_st, knn, slots, (const int32_t *)b.comp_samples, d_fin,
-                         b.stage_rows, b.stage_rowid, b.stage_ta, b.out);
-    }
-    HIPCHK(hipGetLastError());
+    CHK(lvq_launch_walk(cb, ds, b, d_st, row0, c, limit, knn, d_cand, d_lab, d_ta, d_xrows, xc, d_fin));
     HIPCHK(hipMemcpyAsync(ho, b.out, sizeof(LvqBatchOut), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     if (ho->ncomp < 1 || ho->ncomp > c) return fail("somhip_lvq_train: bad component count %d", ho->ncomp);
@@ -157,28 +191,15 @@ static int lvq_walk_batch_nowait(somhip_codebook *cb, somhip_dataset *ds, const 
                                  int c, int knn, const uint64_t *d_cand, const int32_t *d_lab, const float *d_ta, float amax,
                                  bool amax_on_device, uint64_t *d_fin, LvqCtl *d_ctl, int batch_id) {
   somhip_engine *e = cb->e;
-  const int slots = lvq_cache_slots(cb->v.d4);
-  const size_t dyn = ((size_t)cb->v.d4 * slots + 3 * (size_t)cb->v.d4) * sizeof(float4);
-  if (!e->lvq_apply_attr_set) {                           // per engine (= per device), not per process
-    HIPCHK(hipFuncSetAttribute((const void *)k_lvq_batch_apply, hipFuncAttributeMaxDynamicSharedMemorySize, LVQ_DYN_LDS));
-    HIPCHK(hipFuncSetAttribute((const void *)k_lvq_components, hipFuncAttributeMaxDynamicSharedMemorySize, LVQ_BMAX * LVQ_AW * 4));
-    e->lvq_apply_attr_set = true;
-  }
+  CHK(lvq_set_attrs(e));
   {
     LaunchTimer t(e, KID_LVQ_COMPONENTS);
-    hipLaunchKernelGGL(k_lvq_sample_rho, dim3((unsigned)((c + 3) / 4)), dim3(256), 0, e->stream, ds->d_rows, ds->n, ds->d, row0, c,
-                       d_cand, amax, amax_on_device ? (const float *)b.amax_dev : (const float *)nullptr, b.rho, b.xnorm);
+    CHK(lvq_launch_sample_rho(e, ds, b, row0, c, d_cand, amax, amax_on_device));
     CHK(lvq_launch_pair_adj(e, ds, b, row0, c));
     hipLaunchKernelGGL(k_lvq_components, dim3(1), dim3(LVQ_BMAX), (size_t)c * LVQ_AW * 4, e->stream, (const uint32_t *)b.adj, c,
                        0, b.comp_samples, b.out);
   }
-  {
-    LaunchTimer t(e, KID_LVQ_BATCH_APPLY);
-    hipLaunchKernelGGL(k_lvq_batch_apply, dim3((unsigned)c), dim3(LVQ_BT), dyn, e->stream, cb->v, ds->d_rows, ds->n, row0,
-                       c, d_lab, d_ta, (const float4 *)nullptr, 0, d_cand, d_st, knn, slots, (const int32_t *)b.comp_samples, d_fin,
-                       b.stage_rows, b.stage_rowid, b.stage_ta, b.out);
-  }
-  HIPCHK(hipGetLastError());
+  CHK(lvq_launch_walk(cb, ds, b, d_st, row0, c, c, knn, d_cand, d_lab, d_ta, (const float4 *)nullptr, 0, d_fin));
   HIPCHK(hipMemsetAsync(b.mod_count, 0, sizeof(int32_t), e->stream));
   {
     LaunchTimer t(e, KID_LVQ_BATCH_APPLY);
@@ -359,8 +380,9 @@ static int lvq_train_batched(somhip_codebook *cb, somhip_dataset *ds, const somh
   return 0;
 }
 
-// lvq*_training (include/somhip.h): the exact batched engine for unmasked data, else one k_lvq_online_step launch per
-// iteration -- masked data sets always take that path (k_lvq_online_step<true>: the sample's mask in distance and update)
+// lvq*_training (include/somhip.h): the exact batched engine, masked data included (the sample's mask in the frozen
+// scan, in relation (*) and in the walk); else -- SOMHIP_LVQ_ONLINE=1, a patch-ordered codebook, a row too long for
+// the cache -- one k_lvq_online_step launch per iteration
 extern "C" int somhip_lvq_train(somhip_codebook *cb, somhip_dataset *ds, const somhip_lvq_params *p,
                                 float *talpha, int32_t *trace_index, float *trace_diff) try {
   CHK(check_pair(cb, ds, "somhip_lvq_train"));
@@ -391,9 +413,8 @@ extern "C" int somhip_lvq_train(somhip_codebook *cb, somhip_dataset *ds, const s
     if (!cb->d_talpha) HIPCHK(hipMalloc((void **)&cb->d_talpha, sizeof(float) * (size_t)cb->v.n));
     HIPCHK(hipMemcpyAsync(cb->d_talpha, talpha, sizeof(float) * (size_t)cb->v.n, hipMemcpyHostToDevice, e->stream));
   }
-  // exact batched engine unless asked otherwise (SOMHIP_LVQ_ONLINE=1), the data are masked (the batched engine's
-  // frozen-codebook scan and walk take no masks), or the row does not fit the cache
-  if (!masked && !getenv("SOMHIP_LVQ_ONLINE") && cb->v.patch_w == 0 && cb->v.d4 <= LVQ_BT && lvq_cache_slots(cb->v.d4) >= 8) {
+  // exact batched engine unless asked otherwise (SOMHIP_LVQ_ONLINE=1) or the row does not fit the cache
+  if (!getenv("SOMHIP_LVQ_ONLINE") && cb->v.patch_w == 0 && cb->v.d4 <= LVQ_BT && lvq_cache_slots(cb->v.d4) >= 8) {
     int rc = lvq_train_batched(cb, ds, p, knn, talpha, trace_index, trace_diff);
     if (rc) return rc;
     if (p->kind == SOMHIP_OLVQ1)
@@ -564,9 +585,15 @@ extern "C" int somhip_lvq_batch_apply(somhip_codebook *cb, somhip_dataset *ds, c
   if (!p || !dev_keys || !dev_lab || !dev_rows || !consumed) return fail("somhip_lvq_batch_apply: null argument");
   if (p->kind < SOMHIP_LVQ1 || p->kind > SOMHIP_LVQ3) return fail("Unknown LVQ type %d", p->kind);
   if (ds->labels.empty()) return fail("somhip_lvq_batch_apply: data has no labels");
-  // (masked data: somhip_lvq_train's per-iteration path; the batched walk and the row-sharded LVQ path take no masks)
-  if (ds->d_mask) return fail("somhip_lvq_batch_apply: masked samples are not supported by the LVQ loops");
   if (count < 0 || count > LVQ_BMAX) return fail("somhip_lvq_batch_apply: at most %d samples per batch", LVQ_BMAX);
+  // masked data: a sample with every component masked has no winner (see somhip_lvq_train) -- refuse the batch
+  if (ds->d_mask && !ds->all_masked.empty())
+    for (int64_t j = 0; j < std::min<int64_t>(count, ds->n); j++) {
+      const int64_t r = (data_first + j) % ds->n;
+      if (ds->all_masked[(size_t)r])
+        return fail("somhip_lvq_batch_apply: data row %lld has every component masked: no winner (the reference crashes here)",
+                    (long long)r);
+    }
   if (xrows < 1 || xrows > LVQ_K0) return fail("somhip_lvq_batch_apply: xrows must be 1..%d", LVQ_K0);
   if (p->kind == SOMHIP_OLVQ1 && (!cb->d_talpha || !dev_ta)) return fail("somhip_lvq_batch_apply: OLVQ1 needs rates (somhip_lvq_rates_upload)");
   if (cb->v.patch_w != 0 || cb->v.d4 > LVQ_BT || lvq_cache_slots(cb->v.d4) < 8)

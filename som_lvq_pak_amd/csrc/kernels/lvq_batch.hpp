@@ -40,6 +40,18 @@ namespace somhip {
 // list exhausted / cache full) the walk is repeated with the batch cut at the smallest such J
 // and only then committed (k_lvq_commit).  Data in one tight blob is one component: the walk is
 // then the serial one of round 1.
+//
+// MASKED data (samples with 'x' components; M_j = the components sample j has).  Sample j measures every row over
+// M_j only and corrects a row on M_j only (lvq_pak.c:179-186, 343-347), so R_j and rho_j are norms over M_j: a winner
+// of j lies within R_j of x_j over M_j, and after its correction -- which scales exactly those components of
+// x_j - c by (1 - a) -- within rho_j over M_j.  A norm over the subset M_i & M_j is not larger than the norm over
+// M_i or over M_j, and the triangle inequality holds on that subspace, so a row can pass from i to j only if
+//        sum over k in (M_i & M_j) of (x_ik - x_jk)^2  <=  (rho_i + rho_j)^2                      (*m)
+// with rho_j made from the 8th frozen MASKED key of j and ||x_j|| over M_j.  What the row holds outside M_i & M_j
+// (other samples may have moved it there) enters neither side.  An empty intersection gives 0 <= ..., an edge:
+// conservative, it costs parallelism, never exactness.  The rest of the argument is word for word the unmasked one.
+// Instantiations <true> of k_lvq_sample_rho, k_lvq_pair_adj and k_lvq_batch_apply; k_lvq_components, k_lvq_commit,
+// k_lvq_cand_meta, k_lvq_cand_rows and k_merge_shard_topk see whole rows and keys only and take no mask.
 // =====================================================================================
 constexpr int LVQ_K0 = 8;
 constexpr int LVQ_BT = 512;          // threads = maximum number of cache slots
@@ -71,16 +83,25 @@ __device__ __forceinline__ float lvq_sq(float c, float x) { const float t = c - 
 // ---- rho_j of relation (*): one wave per sample -------------------------------------------------
 // rho = ((1 + amax) sqrt(d8) ) (1 + 2^-10) + 2^-18 (||x|| + sqrt(d8)), evaluated in double and rounded up;
 // +inf when the sample's list is not full (tiny codebooks: everything interacts).
+// MASKED: ||x|| over the sample's unmasked components M_j only (mask [n_rows][d], != 0 = masked); whatever the data
+// row stores at a masked position is never added (a select, not a product with 0: it may be a NaN).
+template <bool MASKED>
 __global__ __launch_bounds__(256) void k_lvq_sample_rho(const float *__restrict__ rows, int64_t n_rows, int d,
                                                         int64_t first, int count, const uint64_t *__restrict__ cand,
                                                         float amax_host, const float *__restrict__ amax_dev,
-                                                        float *__restrict__ rho, float *__restrict__ xnorm = nullptr) {
+                                                        float *__restrict__ rho, float *__restrict__ xnorm = nullptr,
+                                                        const uint8_t *__restrict__ mask = nullptr) {
   const float amax = amax_dev ? *amax_dev : amax_host;
   const int j = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (j >= count) return;
   const float *x = rows + ((first + j) % n_rows) * static_cast<int64_t>(d);
   float s = 0.0f;
-  for (int i = lane; i < d; i += WAVE) s += x[i] * x[i];
+  if (MASKED) {
+    const uint8_t *mk = mask + ((first + j) % n_rows) * static_cast<int64_t>(d);
+    for (int i = lane; i < d; i += WAVE) s = mk[i] ? s : s + x[i] * x[i];
+  } else {
+    for (int i = lane; i < d; i += WAVE) s += x[i] * x[i];
+  }
   for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, WAVE);
   if (lane == 0) {
     const uint64_t k8 = cand[static_cast<int64_t>(j) * LVQ_K0 + LVQ_K0 - 1];
@@ -129,9 +150,24 @@ __global__ __launch_bounds__(256) void k_lvq_amax(const uint64_t *__restrict__ c
 // Tiles of 64 x 64 pairs (lower triangle + diagonal; the mirror image is written too); each thread
 // forms 4 x 4 squared distances over the dims in chunks of 32 staged in LDS.  Any summation order
 // will do here (the bound only needs |s - S| <= gamma S).
+// MASKED: the masked relation sums over M_j & M_i only.  A masked component is staged as a NaN (whatever the data
+// row stores there), so the difference of a pair is a NaN exactly where either side masks, and fmaxf(t * t, 0)
+// makes such a term 0 (maxNum returns the operand that is a number).  An empty intersection gives 0: an edge.
+// A NaN among a sample's UNMASKED values is dropped the same way, which can only shorten the sum, i.e. add edges.
+__device__ __forceinline__ float4 lvq_nan_masked(float4 v, uint32_t m) {      // m: 4 mask bytes, component x lowest
+  const float nan = __builtin_nanf("");
+  return make_float4((m & 0xFFu) ? nan : v.x, (m & 0xFF00u) ? nan : v.y, (m & 0xFF0000u) ? nan : v.z, (m & 0xFF000000u) ? nan : v.w);
+}
+__device__ __forceinline__ uint32_t lvq_load_m4(const uint8_t *__restrict__ mr, int q, int d, bool vec) {   // mask bytes of chunk q
+  if (vec) return reinterpret_cast<const uint32_t *>(mr)[q];                 // d % 4 == 0: every row starts 4-byte aligned
+  uint32_t m = 0;
+  for (int u = 0; u < 4 && q * 4 + u < d; u++) m |= (mr[q * 4 + u] ? 1u : 0u) << (8 * u);
+  return m;
+}
+template <bool MASKED>
 __global__ __launch_bounds__(256) void k_lvq_pair_adj(const float *__restrict__ rows, int64_t n_rows, int d,
                                                       int64_t first, int count, const float *__restrict__ rho,
-                                                      uint32_t *__restrict__ adj) {
+                                                      uint32_t *__restrict__ adj, const uint8_t *__restrict__ mask = nullptr) {
   const int tj = blockIdx.y, ti = blockIdx.x;
   if (ti > tj) return;
   // chunk-major LDS tiles [k / 4][row] of float4: a thread's 4 + 4 rows are 8 ds_read_b128 per 4 dims (192 flop)
@@ -160,6 +196,10 @@ __global__ __launch_bounds__(256) void k_lvq_pair_adj(const float *__restrict__ 
           for (int u = 0; u < 4 && k + u < d; u++) { if (ja < count) ta[u] = pa[u]; if (ib < count) tb[u] = pb[u]; }
           va = make_float4(ta[0], ta[1], ta[2], ta[3]); vb = make_float4(tb[0], tb[1], tb[2], tb[3]);
         }
+        if (MASKED) {
+          if (ja < count) va = lvq_nan_masked(va, lvq_load_m4(mask + ((first + ja) % n_rows) * static_cast<int64_t>(d), k >> 2, d, vec));
+          if (ib < count) vb = lvq_nan_masked(vb, lvq_load_m4(mask + ((first + ib) % n_rows) * static_cast<int64_t>(d), k >> 2, d, vec));
+        }
       }
       sa[q][r] = va; sb[q][r] = vb;
     }
@@ -174,7 +214,12 @@ __global__ __launch_bounds__(256) void k_lvq_pair_adj(const float *__restrict__ 
 #pragma unroll
         for (int b = 0; b < 4; b++) {
           const float t0 = va[a].x - vb[b].x, t1 = va[a].y - vb[b].y, t2 = va[a].z - vb[b].z, t3 = va[a].w - vb[b].w;
-          acc[a][b] += t0 * t0; acc[a][b] += t1 * t1; acc[a][b] += t2 * t2; acc[a][b] += t3 * t3;
+          if (MASKED) {
+            acc[a][b] += fmaxf(t0 * t0, 0.0f); acc[a][b] += fmaxf(t1 * t1, 0.0f);
+            acc[a][b] += fmaxf(t2 * t2, 0.0f); acc[a][b] += fmaxf(t3 * t3, 0.0f);
+          } else {
+            acc[a][b] += t0 * t0; acc[a][b] += t1 * t1; acc[a][b] += t2 * t2; acc[a][b] += t3 * t3;
+          }
         }
     }
     __syncthreads();
@@ -211,7 +256,7 @@ __global__ __launch_bounds__(256) void k_lvq_pair_adj(const float *__restrict__ 
 // (fp32 products, fp32 accumulation in any order, the two wave-summed norms), so "computed <= (rho_j + rho_i)^2
 // (1 + 2^-10) + 8 (d + 8) u (n_j + n_i)" holds for every pair that satisfies (*).  The inner products are
 // bit-symmetric in (j, i) (same products, same order), hence so is the matrix; every tile of it is computed
-// (no mirror writes).  Needs d % 8 == 0; other shapes use k_lvq_pair_adj.
+// (no mirror writes).  Needs d % 8 == 0; other shapes, and every masked batch, use k_lvq_pair_adj.
 __global__ __launch_bounds__(256) void k_lvq_pair_adj_mfma(const float *__restrict__ rows, int64_t n_rows, int d,
                                                            int64_t first, int count, const float *__restrict__ rho,
                                                            const float *__restrict__ xnorm, uint32_t *__restrict__ adj) {
@@ -399,6 +444,23 @@ __global__ __launch_bounds__(LVQ_BMAX) void k_lvq_components(const uint32_t *__r
 // frozen candidates of every sample, exchanged between the ranks; cand_lab / cand_ta [count][8]: label and
 // OLVQ1 rate of every listed candidate.  Row ids inside keys are GLOBAL rows; local tiles are used when
 // cand_rows is null.  limit: samples >= limit are not walked (the repeat after a stop).
+//
+// MASKED (mask [n_rows][d], != 0 = masked): the sample's mask row travels with x.  Each thread keeps the 4 mask bytes
+// of its chunk in a register (the correction of phase D: a masked component keeps its stored bits, by select, as
+// k_lvq_online_step<true> does), and the walk's waves publish them as ballots s_mb[wave][e] -- bit l = component e of
+// chunk 64 wave + l -- 256 bytes of static LDS whatever d is, so the row cache keeps every slot it has for unmasked
+// data.  The distance of a cached row (phase B) leaves the sum as it is at a masked component (select; the
+// sub / mul / add of the other components in dim order as before), which is the reference's masked distance
+// (lvq_pak.c:179-186).  The frozen candidates' keys were made with the same mask by the scan, so the accept rule
+// (last accepted key <= the sample's 8th frozen key) stands as it is.
+//
+// The reference's fp32 quotients (window test, OLVQ1 rate) are formed out of line in the masked instantiation: the
+// correctly rounded fp32 division expands into a v_fma_f32 sequence, and with that sequence in lvq_div_call the build
+// test can hold the whole body of the masked walk to "no v_fma / v_mac / v_mad _f32" instead of exempting it as a
+// kernel that divides.  One call per sample, on wave 0 only.
+__device__ __attribute__((noinline)) float lvq_div_call(float a, float b) { return a / b; }
+#define LVQ_DIV(a, b) (MASKED ? lvq_div_call((a), (b)) : (a) / (b))
+template <bool MASKED>
 __global__ __launch_bounds__(LVQ_BT) void k_lvq_batch_apply(CbView cb, const float *__restrict__ rows,
                                                             int64_t n_rows, int64_t first, int limit,
                                                             const int32_t *__restrict__ cand_lab,
@@ -409,7 +471,8 @@ __global__ __launch_bounds__(LVQ_BT) void k_lvq_batch_apply(CbView cb, const flo
                                                             int slots, const int32_t *__restrict__ comp_samples,
                                                             uint64_t *__restrict__ fin,
                                                             float4 *__restrict__ stage_rows, int32_t *__restrict__ stage_rowid,
-                                                            float *__restrict__ stage_ta, LvqBatchOut *__restrict__ out) {
+                                                            float *__restrict__ stage_ta, LvqBatchOut *__restrict__ out,
+                                                            const uint8_t *__restrict__ mask = nullptr) {
   const int comp = blockIdx.x;
   if (comp >= out->ncomp) return;
   extern __shared__ float4 lvq_dyn[];
@@ -431,6 +494,7 @@ __global__ __launch_bounds__(LVQ_BT) void k_lvq_batch_apply(CbView cb, const flo
   __shared__ float s_ua[2];
   __shared__ int32_t s_urow[2];
   __shared__ uint16_t s_list[LVQ_BMAX];           // this component's samples, iteration order
+  __shared__ uint64_t s_mb[MASKED ? NW : 1][4];   // the sample's mask: bit l of [w][e] = component e of chunk 64 w + l
 
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const bool vec = (cb.d & 3) == 0;
@@ -452,6 +516,7 @@ __global__ __launch_bounds__(LVQ_BT) void k_lvq_batch_apply(CbView cb, const flo
   int32_t nlab = 0;
   float nta = 0.0f;
   LvqStep nst = {}, cst = {};
+  uint32_t nmk = 0, cmk = 0;                       // MASKED: the 4 mask bytes of chunk tid (next / current sample)
   auto row_chunk = [&](int js, int c, uint32_t r, int q) -> float4 {   // chunk q of frozen candidate c (row r) of sample js
     if (cand_rows) return cand_rows[(static_cast<int64_t>(js) * xc + c) * d4 + q];
     return *tile_ptr(cb, r >> 6, q, r & 63);
@@ -471,6 +536,7 @@ __global__ __launch_bounds__(LVQ_BT) void k_lvq_batch_apply(CbView cb, const flo
     nck = kck;
     if (tid < d4) {
       nx = vec ? reinterpret_cast<const float4 *>(xr)[tid] : load_x4<false>(xr, tid, cb.d);
+      if (MASKED) nmk = lvq_load_m4(mask + ((first + js) % n_rows) * static_cast<int64_t>(cb.d), tid, cb.d, vec);
       if (c0 != KEY_NONE) {
         const uint32_t r = knn2 ? ~static_cast<uint32_t>(c0) : static_cast<uint32_t>(c0);
         np0 = row_chunk(js, 0, r, tid);
@@ -505,6 +571,14 @@ __global__ __launch_bounds__(LVQ_BT) void k_lvq_batch_apply(CbView cb, const flo
     if (tid < LVQ_K0) { s_ck[tid] = nck; s_clab[tid] = nlab; s_cta[tid] = nta; }
     if (tid == 0) s_flags = 0;
     cst = nst;
+    if (MASKED) {
+      cmk = nmk;                                   // (threads >= d4 hold 0)
+#pragma unroll
+      for (int e = 0; e < 4; e++) {
+        const unsigned long long bal = __ballot((cmk >> (8 * e)) & 0xFFu);
+        if (lane == 0) s_mb[wave][e] = bal;
+      }
+    }
     __syncthreads();
     lap(0);
     if (j + 1 < count) fetch(j + 1);
@@ -531,7 +605,18 @@ __global__ __launch_bounds__(LVQ_BT) void k_lvq_batch_apply(CbView cb, const flo
         const f32x2 p0_ = t0_ * t0_, p1_ = t1_ * t1_;   /* v_pk_*: each half rounded like the scalar op */ \
         P[4 * u + 0] = p0_.x; P[4 * u + 1] = p0_.y; P[4 * u + 2] = p1_.x; P[4 * u + 3] = p1_.y; \
       }
-#define LVQ_SUM(P) _Pragma("unroll") for (int i = 0; i < 16; i++) acc = acc + P[i];
+      // MASKED: element i of block BLK is component i % 4 of chunk 4 BLK + i / 4 (4 | 64: one ballot word per block);
+      // the words are wave-uniform, so the selects test scalar bits
+#define LVQ_SUM(P, BLK)                                                                   \
+      {                                                                                   \
+        uint32_t mk_[4] = {0u, 0u, 0u, 0u};                                               \
+        if (MASKED) {                                                                     \
+          _Pragma("unroll") for (int e = 0; e < 4; e++)                                   \
+            mk_[e] = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(s_mb[((BLK) * 4) >> 6][e] >> (((BLK) * 4) & 63))); \
+        }                                                                                 \
+        _Pragma("unroll") for (int i = 0; i < 16; i++)                                    \
+          acc = (MASKED && ((mk_[i & 3] >> (i >> 2)) & 1u)) ? acc : acc + P[i];           \
+      }
       if (nblk > 0) {
         LVQ_LOAD(rAc, rAx, 0)
         LVQ_LOAD(rBc, rBx, 1)
@@ -540,12 +625,12 @@ __global__ __launch_bounds__(LVQ_BT) void k_lvq_batch_apply(CbView cb, const flo
         for (; b + 2 <= nblk; b += 2) {
           LVQ_LOAD(rAc, rAx, b + 2)
           LVQ_PROD(pB, rBc, rBx)
-          LVQ_SUM(pA)
+          LVQ_SUM(pA, b)
           LVQ_LOAD(rBc, rBx, b + 3)
           LVQ_PROD(pA, rAc, rAx)
-          LVQ_SUM(pB)
+          LVQ_SUM(pB, b + 1)
         }
-        if (nblk & 1) { LVQ_SUM(pA) }
+        if (nblk & 1) { LVQ_SUM(pA, b) }
       }
 #undef LVQ_LOAD
 #undef LVQ_PROD
@@ -553,10 +638,18 @@ __global__ __launch_bounds__(LVQ_BT) void k_lvq_batch_apply(CbView cb, const flo
       for (int q = nblk * 4; q < d4; q++) {
         const float4 c = cp[q * slots];
         const float4 x = s_x[q];
-        acc = sq_acc(acc, c.x, x.x);
-        acc = sq_acc(acc, c.y, x.y);
-        acc = sq_acc(acc, c.z, x.z);
-        acc = sq_acc(acc, c.w, x.w);
+        if (MASKED) {
+          const int w_ = q >> 6, l_ = q & 63;
+          acc = ((s_mb[w_][0] >> l_) & 1ull) ? acc : sq_acc(acc, c.x, x.x);
+          acc = ((s_mb[w_][1] >> l_) & 1ull) ? acc : sq_acc(acc, c.y, x.y);
+          acc = ((s_mb[w_][2] >> l_) & 1ull) ? acc : sq_acc(acc, c.z, x.z);
+          acc = ((s_mb[w_][3] >> l_) & 1ull) ? acc : sq_acc(acc, c.w, x.w);
+        } else {
+          acc = sq_acc(acc, c.x, x.x);
+          acc = sq_acc(acc, c.y, x.y);
+          acc = sq_acc(acc, c.z, x.z);
+          acc = sq_acc(acc, c.w, x.w);
+        }
       }
       const uint32_t r = static_cast<uint32_t>(s_slot_row[tid]);
       const uint32_t tag = knn2 ? ~r : r;
@@ -635,7 +728,7 @@ __global__ __launch_bounds__(LVQ_BT) void k_lvq_batch_apply(CbView cb, const flo
           const float d1 = __uint_as_float(static_cast<uint32_t>(k1 >> 32));
           if (wlab[0] != wlab[1]) {
             if (wlab[0] == sp.label || wlab[1] == sp.label) {
-              if ((d0 / d1) > sp.win_ratio) {                       // lvq_rout.c:770 / :876
+              if (LVQ_DIV(d0, d1) > sp.win_ratio) {         // lvq_rout.c:770 / :876
                 const int best = (wlab[1] == sp.label) ? 1 : 0;
                 nupd = 2; uidx[0] = best; ua[0] = sp.alpha; uidx[1] = best ^ 1; ua[1] = -sp.alpha;
               }
@@ -675,9 +768,9 @@ __global__ __launch_bounds__(LVQ_BT) void k_lvq_batch_apply(CbView cb, const flo
           if (sp.kind == 2 && nupd == 1) {         // the corrected row advances its rate (lvq_rout.c:663, :670-672)
             float ta = wta[0];
             if (olvq_correct) {
-              ta = ta / (1 + ta);
+              ta = LVQ_DIV(ta, 1 + ta);
             } else {
-              ta = ta / (1 - ta);
+              ta = LVQ_DIV(ta, 1 - ta);
               if (ta > sp.alpha_clamp) ta = sp.alpha_clamp;
             }
             s_slot_ta[wslot[0]] = ta;
@@ -703,7 +796,14 @@ __global__ __launch_bounds__(LVQ_BT) void k_lvq_batch_apply(CbView cb, const flo
         if (src < 0) c = cache[tid * slots + sl];
         else if (src < 2) c = s_pre[src * d4 + tid];
         else c = row_chunk(js, src, static_cast<uint32_t>(s_urow[u]), tid);
-        cache[tid * slots + sl] = adapt4(c, x, s_ua[u]);
+        float4 n = adapt4(c, x, s_ua[u]);
+        if (MASKED) {                              // lvq_pak.c:343-347: a masked component keeps its stored bits
+          n.x = (cmk & 0xFFu) ? c.x : n.x;
+          n.y = (cmk & 0xFF00u) ? c.y : n.y;
+          n.z = (cmk & 0xFF0000u) ? c.z : n.z;
+          n.w = (cmk & 0xFF000000u) ? c.w : n.w;
+        }
+        cache[tid * slots + sl] = n;
       }
     }
     __syncthreads();
@@ -723,6 +823,8 @@ __global__ __launch_bounds__(LVQ_BT) void k_lvq_batch_apply(CbView cb, const flo
     for (int k = 0; k < 4; k++) atomicAdd(reinterpret_cast<unsigned long long *>(&out->cycles[k]), static_cast<unsigned long long>(cyc[k]));
   }
 }
+
+#undef LVQ_DIV
 
 // ---- commit: staged rows -> codebook tiles (rows of this shard only), OLVQ1 rates, list of written rows ----
 __global__ __launch_bounds__(256) void k_lvq_commit(CbView cb, const LvqBatchOut *__restrict__ out,

@@ -375,8 +375,9 @@ def lvq_train(cb, ds, kind, length, alpha, alpha_type=ALPHA_LINEAR, winlen=0.0, 
               talpha=None, start_iter=0, count=None, data_first=None, trace=True):
     """lvq1/olvq1/lvq2/lvq3_training (reference lvq_rout.c:498-916).
 
-    A masked data set runs one launch per iteration (the sample's mask in distance and update,
-    lvq_pak.c:343-347); a run that visits a row with every component masked raises before training."""
+    A masked data set (Dataset(..., mask=...)) runs in the exact batched engine like an unmasked one (the sample's
+    mask in distance and update, lvq_pak.c:179-186, 343-347; whatever the rows store at masked positions is never
+    read into a result); a run that visits a row with every component masked raises before training."""
     count = length - start_iter if count is None else count
     data_first = start_iter % ds.n if data_first is None else data_first
     knn = 2 if kind in (LVQ2, LVQ3) else 1

@@ -1260,7 +1260,7 @@ int som_training_multi(struct teach_params *teach, int gpus, int (*after)(struct
   return pak_run_ranks(gpus, som_multi_rank, &m);
 }
 
-/* lvq*_training on one GPU.  Masked data go to the engine with their masks (one launch per iteration there); the
+/* lvq*_training on one GPU.  Masked data go to the engine with their masks (the exact batched engine takes them); the
  * codes keep their own masks for save_entries. */
 static struct entries *lvq_training(struct teach_params *teach, int kind, float winlen, float epsilon,
                                     float *talpha, const char *who)
@@ -1324,6 +1324,7 @@ struct entries *olvq1_training(struct teach_params *teach, const char *infile, c
  * iterations (include/somhip.h, "lvq*_training over a ROW-SHARDED codebook"): each rank's 8 nearest rows per sample ->
  * all-gather + merge -> labels / rates / rows of the listed candidates the rank owns -> all-reduce(SUM) as integers ->
  * every rank walks the batch (same decisions everywhere) and commits the rows it owns.  Exactly the online result.
+ * Masked data: every rank's data set carries the masks (mirror_data), so the scan, the walk and its components use them.
  * Collectives: RCCL when every rank has its own GPU, the parent's socketpairs otherwise (somhip_comm). */
 struct lvq_multi {
   struct teach_params *teach; int kind; float winlen, epsilon, clamp; float *talpha;
@@ -1431,7 +1432,6 @@ int lvq_training_multi(struct teach_params *teach, int kind, float winlen, float
     fprintf(stderr, "lvq training: -buffer with -rand is not available with -gpus\n");
     return 1;
   }
-  if (teach->data->masks) { fprintf(stderr, "lvq training: masked samples are not supported by the LVQ loops of the engine\n"); return 1; }
   if (teach->snapshot) fprintf(stderr, "lvq training: snapshots are not written with -gpus\n");
   struct lvq_multi m = { teach, kind, winlen, epsilon, clamp, talpha, after, arg };
   return pak_run_ranks(gpus, lvq_training_rank, &m);

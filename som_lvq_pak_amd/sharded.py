@@ -335,7 +335,8 @@ class ShardedLvq:
       2. every rank: labels / rates / rows of the listed candidates it owns   -> all-reduce(SUM) as integers
       3. every rank walks the batch (deterministic: all take the same decisions) and commits the rows it owns
     `shard` provides topk_keys / merge / candidates / apply (GpuLvqShard on an MI355X; a checker-backed one in
-    the CPU tests).  xrows: how many of the 8 candidates' rows are exchanged (a winner beyond them ends the batch)."""
+    the CPU tests).  The data set of a GpuLvqShard may carry masks (Dataset(..., mask=...)): steps 1 and 3 use the
+    sample's mask; a batch that holds a row with every component masked raises.  xrows: how many of the 8 candidates' rows are exchanged (a winner beyond them ends the batch)."""
 
     def __init__(self, shard, kind, n_data, xrows=4, max_batch=1024, group=None):
         self.shard, self.kind, self.n_data, self.xrows, self.group = shard, kind, n_data, xrows, group
