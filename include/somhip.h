@@ -247,6 +247,14 @@ typedef struct somhip_lvq_params {
 } somhip_lvq_params;
 int  somhip_lvq_train(somhip_codebook *cb, somhip_dataset *ds, const somhip_lvq_params *p,
                       float *talpha, int32_t *trace_index, float *trace_diff);
+/* diagnostics (tests): the plan somhip_lvq_train would follow with these arguments (want_trace: a trace is asked for);
+ * out[2], out[3], out[6], out[7] are also what somhip_lvq_batch_apply follows.  Host arithmetic only, no GPU work.
+ * out[0] = engine (1 exact batched, 0 one launch per iteration), out[1] = the batched loop does not wait for the host
+ * (0: every batch the careful way), out[2] = every batch is one component, out[3] = relation (*) over pairs by (0 the
+ * masked direct-form kernel, 1 the MFMA Gram form, 2 the direct form), out[4] = masked data, out[5] = winners per
+ * sample, out[6] = rows the walk's cache holds, out[7] = its dynamic LDS bytes */
+int  somhip_debug_lvq_plan(somhip_codebook *cb, somhip_dataset *ds, const somhip_lvq_params *p, int want_trace,
+                           int32_t out[8]);
 /* out[0] = codebook rescans (batches) done by somhip_lvq_train so far, out[1] = samples,
  * out[2] / out[3] = batches cut short because a sample's candidate list was exhausted /
  * the on-chip row cache was full, out[4..7] = 100 MHz ticks the in-order kernel spent in

@@ -16,12 +16,73 @@ static int lvq_cache_slots(int d4) {
   return (int)std::min<int64_t>(s, LVQ_BT);
 }
 
+// Every choice of one somhip_lvq_train call or one somhip_lvq_batch_apply, made here and nowhere else (reported by
+// somhip_debug_lvq_plan).  Made per call, never kept on the engine: the switches may change between two calls.
+//   SOMHIP_LVQ_ONLINE=1      the one-launch-per-iteration engine even where the batched one fits
+//   SOMHIP_LVQ_SYNC=1        every batch the careful way (its verdict read back before the next is launched)
+//   SOMHIP_LVQ_SERIAL=1      every batch one component (the serial walk), the careful way
+//   SOMHIP_LVQ_PAIRS_VALU=1  relation (*) always by the direct-form kernel
+enum { LVQ_PAIRS_MASKED = 0, LVQ_PAIRS_MFMA = 1, LVQ_PAIRS_DIRECT = 2 };
+struct LvqPlan {
+  bool fits;       // row-ordered codebook whose rows fit the walk's on-chip cache: the batched engine can run it
+  bool batched;    // somhip_lvq_train: the exact batched engine (else one k_lvq_online_step launch per iteration)
+  bool nowait;     // its loop launches batch after batch without waiting for the host (else every batch the careful way)
+  bool single;     // the whole batch is one component
+  int pairs;       // relation (*) over all pairs: LVQ_PAIRS_MASKED direct form over the components both samples have,
+                   // LVQ_PAIRS_MFMA Gram form on the matrix pipe (dim % 8 == 0), LVQ_PAIRS_DIRECT direct form
+  bool masked, olvq;
+  int knn;         // winners per sample: 2 for LVQ2.1 / LVQ3, else 1
+  int slots;       // rows the walk's cache holds
+  size_t dyn;      // ... and its dynamic LDS bytes
+};
+static LvqPlan lvq_plan(const somhip_codebook *cb, const somhip_dataset *ds, const somhip_lvq_params *p, bool want_trace) {
+  LvqPlan pl;
+  pl.slots = lvq_cache_slots(cb->v.d4);
+  pl.dyn = ((size_t)cb->v.d4 * pl.slots + 3 * (size_t)cb->v.d4) * sizeof(float4);
+  pl.fits = cb->v.patch_w == 0 && cb->v.d4 <= LVQ_BT && pl.slots >= 8;
+  pl.batched = pl.fits && !getenv("SOMHIP_LVQ_ONLINE");
+  pl.single = getenv("SOMHIP_LVQ_SERIAL") != nullptr;
+  // no waiting only if the winners of the whole call fit a device buffer (they are read back at the end)
+  pl.nowait = !getenv("SOMHIP_LVQ_SYNC") && !pl.single && (!want_trace || p->count <= (1ll << 22));
+  pl.masked = ds->d_mask != nullptr;
+  pl.pairs = pl.masked ? LVQ_PAIRS_MASKED : ds->d % 8 == 0 && !getenv("SOMHIP_LVQ_PAIRS_VALU") ? LVQ_PAIRS_MFMA : LVQ_PAIRS_DIRECT;
+  pl.olvq = p->kind == SOMHIP_OLVQ1;
+  pl.knn = p->kind >= SOMHIP_LVQ2 ? 2 : 1;
+  return pl;
+}
+// the plan of a somhip_lvq_train call with these arguments (somhip.h): host arithmetic only
+extern "C" int somhip_debug_lvq_plan(somhip_codebook *cb, somhip_dataset *ds, const somhip_lvq_params *p, int want_trace,
+                                     int32_t *out) try {
+  CHK(check_pair(cb, ds, "somhip_debug_lvq_plan"));
+  if (!p || !out) return fail("somhip_debug_lvq_plan: null argument");
+  if (p->kind < SOMHIP_LVQ1 || p->kind > SOMHIP_LVQ3) return fail("Unknown LVQ type %d", p->kind);
+  const LvqPlan pl = lvq_plan(cb, ds, p, want_trace != 0);
+  out[0] = pl.batched; out[1] = pl.nowait; out[2] = pl.single; out[3] = pl.pairs;
+  out[4] = pl.masked; out[5] = pl.knn; out[6] = pl.slots; out[7] = (int32_t)pl.dyn;
+  return 0;
+} ABI_CATCH(somhip_debug_lvq_plan)
+
 // device buffers of one batch of the exact LVQ engine
 struct LvqBatchBufs {
   float *rho, *xnorm; uint32_t *adj; int32_t *comp_samples; LvqBatchOut *out;
   float4 *stage_rows; int32_t *stage_rowid; float *stage_ta;
   int32_t *cand_lab; float *cand_ta; int32_t *mod_rows, *mod_count; float *amax_dev;
 };
+// one batch after its candidate lists are known: data rows [row0, row0 + c) (mod n)
+struct LvqBatch {
+  int64_t row0; int c;
+  const LvqStep *st;               // device: the step scalars [c]
+  const uint64_t *cand;            // device: global top-8 keys [c][8]
+  const int32_t *lab;              // ... the candidates' labels
+  const float *ta;                 // ... and OLVQ1 rates (else nullptr)
+  const float4 *xrows; int xc;     // sharded codebooks only: tile copies [c][xc][d4] of the xc nearest candidates
+  float amax;                      // bound on |rate| of every correction of the batch (< 0 -- a NaN in the schedule --:
+                                   // unknown, and k_lvq_sample_rho makes the whole batch one component) ...
+  const float *amax_dev;           // ... or, if not null, where the device holds it (OLVQ1: lvq_rate_bound)
+  uint64_t *fin;                   // device: where the batch's winners go (trace)
+};
+
+// the engine's scratch slots behind LvqBatchBufs; the first use on an engine also raises two kernels' dynamic LDS limit
 static int lvq_batch_bufs(somhip_engine *e, int d4, LvqBatchBufs *b) {
   void *p;
   CHK(engine_scratch(e, SLOT_LVQ_RHO, sizeof(float) * 2 * LVQ_BMAX + 16, &p)); b->rho = (float *)p; b->xnorm = b->rho + LVQ_BMAX; b->amax_dev = b->xnorm + LVQ_BMAX;
@@ -34,28 +95,7 @@ static int lvq_batch_bufs(somhip_engine *e, int d4, LvqBatchBufs *b) {
   CHK(engine_scratch(e, SLOT_LVQ_CAND_LAB, sizeof(int32_t) * LVQ_BMAX * LVQ_K0, &p)); b->cand_lab = (int32_t *)p;
   CHK(engine_scratch(e, SLOT_LVQ_CAND_TA, sizeof(float) * LVQ_BMAX * LVQ_K0, &p)); b->cand_ta = (float *)p;
   CHK(engine_scratch(e, SLOT_LVQ_MOD, sizeof(int32_t) * (2 * LVQ_BMAX + 4), &p)); b->mod_rows = (int32_t *)p; b->mod_count = b->mod_rows + 2 * LVQ_BMAX;
-  return 0;
-}
-
-// relation (*) over all pairs of the batch: Gram form on the matrix pipe where the shape allows (SOMHIP_LVQ_PAIRS_VALU=1:
-// always the direct-form kernel); masked data: the direct-form kernel over the components both samples have
-static int lvq_launch_pair_adj(somhip_engine *e, somhip_dataset *ds, const LvqBatchBufs &b, int64_t row0, int c) {
-  const unsigned nt = (unsigned)((c + 63) / 64);
-  if (ds->d_mask)
-    hipLaunchKernelGGL(k_lvq_pair_adj<true>, dim3(nt, nt), dim3(256), 0, e->stream, ds->d_rows, ds->n, ds->d, row0, c,
-                       (const float *)b.rho, b.adj, (const uint8_t *)ds->d_mask);
-  else if (ds->d % 8 == 0 && !getenv("SOMHIP_LVQ_PAIRS_VALU"))
-    hipLaunchKernelGGL(k_lvq_pair_adj_mfma, dim3(nt, nt), dim3(256), 0, e->stream, ds->d_rows, ds->n, ds->d, row0, c,
-                       (const float *)b.rho, (const float *)b.xnorm, b.adj);
-  else
-    hipLaunchKernelGGL(k_lvq_pair_adj<false>, dim3(nt, nt), dim3(256), 0, e->stream, ds->d_rows, ds->n, ds->d, row0, c,
-                       (const float *)b.rho, b.adj);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-// the walk's row cache and the component kernel's adjacency rows need more dynamic LDS than the default limit
-static int lvq_set_attrs(somhip_engine *e) {
+  // the walk's row cache and the component kernel's adjacency rows need more dynamic LDS than the default limit
   if (e->lvq_apply_attr_set) return 0;                    // per engine (= per device), not per process
   HIPCHK(hipFuncSetAttribute((const void *)k_lvq_batch_apply<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LVQ_DYN_LDS));
   HIPCHK(hipFuncSetAttribute((const void *)k_lvq_batch_apply<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LVQ_DYN_LDS));
@@ -64,72 +104,177 @@ static int lvq_set_attrs(somhip_engine *e) {
   return 0;
 }
 
-// rho_j of relation (*) for every sample of the batch (masked data: the sample's norm over its own components)
-static int lvq_launch_sample_rho(somhip_engine *e, somhip_dataset *ds, const LvqBatchBufs &b, int64_t row0, int c,
-                                 const uint64_t *d_cand, float amax, bool amax_on_device) {
-  const float *amax_dev = amax_on_device ? (const float *)b.amax_dev : (const float *)nullptr;
-  if (ds->d_mask)
-    hipLaunchKernelGGL(k_lvq_sample_rho<true>, dim3((unsigned)((c + 3) / 4)), dim3(256), 0, e->stream, ds->d_rows, ds->n, ds->d,
-                       row0, c, d_cand, amax, amax_dev, b.rho, b.xnorm, (const uint8_t *)ds->d_mask);
-  else
-    hipLaunchKernelGGL(k_lvq_sample_rho<false>, dim3((unsigned)((c + 3) / 4)), dim3(256), 0, e->stream, ds->d_rows, ds->n, ds->d,
-                       row0, c, d_cand, amax, amax_dev, b.rho, b.xnorm);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-// the walk itself: one workgroup per component (k_lvq_batch_apply<true> stages the sample's mask row beside the sample)
-static int lvq_launch_walk(somhip_codebook *cb, somhip_dataset *ds, const LvqBatchBufs &b, const LvqStep *d_st, int64_t row0,
-                           int c, int limit, int knn, const uint64_t *d_cand, const int32_t *d_lab, const float *d_ta,
-                           const float4 *d_xrows, int xc, uint64_t *d_fin) {
-  somhip_engine *e = cb->e;
-  const int slots = lvq_cache_slots(cb->v.d4);
-  const size_t dyn = ((size_t)cb->v.d4 * slots + 3 * (size_t)cb->v.d4) * sizeof(float4);
-  LaunchTimer t(e, KID_LVQ_BATCH_APPLY);
-  if (ds->d_mask)
-    hipLaunchKernelGGL(k_lvq_batch_apply<true>, dim3((unsigned)c), dim3(LVQ_BT), dyn, e->stream, cb->v, ds->d_rows, ds->n, row0,
-                       limit, d_lab, d_ta, d_xrows, xc, d_cand, d_st, knn, slots, (const int32_t *)b.comp_samples, d_fin,
-                       b.stage_rows, b.stage_rowid, b.stage_ta, b.out, (const uint8_t *)ds->d_mask);
-  else
-    hipLaunchKernelGGL(k_lvq_batch_apply<false>, dim3((unsigned)c), dim3(LVQ_BT), dyn, e->stream, cb->v, ds->d_rows, ds->n, row0,
-                       limit, d_lab, d_ta, d_xrows, xc, d_cand, d_st, knn, slots, (const int32_t *)b.comp_samples, d_fin,
-                       b.stage_rows, b.stage_rowid, b.stage_ta, b.out);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-// One batch of the exact engine after its candidate lists are known (kernels/lvq_batch.hpp): relation (*) ->
-// components -> one workgroup per component walks its samples in order -> (repeat with the batch cut at the first
-// stop, if any) -> commit the rows this shard owns.  d_cand: global top-8 keys [c][8]; d_lab / d_ta: the candidates'
-// labels and OLVQ1 rates; d_xrows (sharded codebooks only): tile copies [c][xc][d4] of the xc nearest candidates.
-// amax: bound on |rate| of every correction of the batch (< 0: unknown -> one component, the serial walk), or
-// read from b.amax_dev when amax_on_device.  *consumed <= c samples were applied.
-static int lvq_walk_batch(somhip_codebook *cb, somhip_dataset *ds, const LvqBatchBufs &b, const LvqStep *d_st, int64_t row0,
-                          int c, int knn, const uint64_t *d_cand, const int32_t *d_lab, const float *d_ta,
-                          const float4 *d_xrows, int xc, float amax, bool amax_on_device, uint64_t *d_fin,
-                          int *consumed, int *reason, int64_t *nmod_bound) {
-  somhip_engine *e = cb->e;
-  CHK(lvq_set_attrs(e));
-  const bool single = getenv("SOMHIP_LVQ_SERIAL") != nullptr;
-  {
-    LaunchTimer t(e, KID_LVQ_COMPONENTS);
-    if (!single) {
-      CHK(lvq_launch_sample_rho(e, ds, b, row0, c, d_cand, amax, amax_on_device));
-      CHK(lvq_launch_pair_adj(e, ds, b, row0, c));
-    }
-    hipLaunchKernelGGL(k_lvq_components, dim3(1), dim3(LVQ_BMAX), (size_t)c * LVQ_AW * 4, e->stream, (const uint32_t *)b.adj, c,
-                       single ? 1 : 0, b.comp_samples, b.out);
+// ---- small jobs every LVQ entry point shares --------------------------------------------------------------------
+// the step scalars of iterations [it0, it0 + c) on data rows row0, row0 + 1, ... (mod n)
+static void lvq_fill_steps(const somhip_dataset *ds, const somhip_lvq_params *p, int64_t it0, int64_t row0, int64_t c, LvqStep *st) {
+  const float ratio = (1 - p->winlen) / (1 + p->winlen);                  // lvq_rout.c:770, fp32
+  for (int64_t j = 0; j < c; j++) {
+    LvqStep s;
+    s.kind = p->kind;
+    s.alpha = alpha_at(p->alpha_type, it0 + j, p->length, p->alpha);
+    s.alpha_clamp = p->alpha;
+    s.win_ratio = ratio;
+    s.epsilon = p->epsilon;
+    s.label = ds->labels[(size_t)((row0 + j) % ds->n)];
+    st[(size_t)j] = s;
   }
+}
+// bound on |rate| of the batch's corrections from its step scalars (LVQ1 / LVQ2.1 / LVQ3: the schedule value, and
+// alpha * epsilon); OLVQ1 rates live per row: see lvq_rate_bound
+static float lvq_amax_of(const LvqStep *st, int c) {
+  float m = 0.0f;
+  for (int j = 0; j < c; j++) {
+    const float a = std::fabs(st[j].alpha), ae = std::fabs(st[j].alpha * st[j].epsilon);
+    if (!(a == a) || !(ae == ae)) return -1.0f;
+    m = std::max(m, std::max(a, ae));
+  }
+  return m;
+}
+// the winner trace of iterations [it0, it0 + c) from their keys [c][2] (host)
+static void lvq_trace(const uint64_t *keys, int64_t c, int knn, int64_t it0, int32_t *trace_index, float *trace_diff) {
+  for (int64_t j = 0; j < c; j++)
+    for (int k = 0; k < knn; k++) {
+      int32_t idx; float df;
+      decode_key(keys[(size_t)(2 * j + k)], knn == 2, &idx, &df);
+      if (trace_index) trace_index[(it0 + j) * knn + k] = idx;
+      if (trace_diff) trace_diff[(it0 + j) * knn + k] = df;
+    }
+}
+// ... from keys on the device, of walks the host has already waited for
+static int lvq_trace_read(const uint64_t *d_keys, int64_t c, int knn, int64_t it0, int32_t *trace_index, float *trace_diff) {
+  std::vector<uint64_t> hfin((size_t)c * 2);
+  HIPCHK(hipMemcpy(hfin.data(), d_keys, sizeof(uint64_t) * 2 * (size_t)c, hipMemcpyDeviceToHost));
+  lvq_trace(hfin.data(), c, knn, it0, trace_index, trace_diff);
+  return 0;
+}
+// masked data: a sample with every component masked has no winner, and the reference then adapts through a NULL
+// winner (lvq_rout.c:542-545) -- refuse a run over such a row before anything is trained
+static int lvq_refuse_all_masked(const somhip_dataset *ds, int64_t data_first, int64_t count, const char *who) {
+  if (!ds->d_mask || ds->all_masked.empty()) return 0;
+  for (int64_t j = 0; j < std::min<int64_t>(count, ds->n); j++) {
+    const int64_t r = (data_first + j) % ds->n;
+    if (ds->all_masked[(size_t)r])
+      return fail("%s: data row %lld has every component masked: no winner (the reference crashes here)", who, (long long)r);
+  }
+  return 0;
+}
+// OLVQ1's per-row rates to the device and back, on the engine's stream (the caller waits)
+static int lvq_rates_to_device(somhip_codebook *cb, const float *talpha) {
+  if (!cb->d_talpha) HIPCHK(hipMalloc((void **)&cb->d_talpha, sizeof(float) * (size_t)cb->v.n));
+  HIPCHK(hipMemcpyAsync(cb->d_talpha, talpha, sizeof(float) * (size_t)cb->v.n, hipMemcpyHostToDevice, cb->e->stream));
+  return 0;
+}
+static int lvq_rates_to_host(somhip_codebook *cb, float *talpha) {
+  HIPCHK(hipMemcpyAsync(talpha, cb->d_talpha, sizeof(float) * (size_t)cb->v.n, hipMemcpyDeviceToHost, cb->e->stream));
+  return 0;
+}
+
+// ---- the stages of one batch (kernels/lvq_batch.hpp), each launched from here only ----------------------------------
+// front: labels and (OLVQ1; ta may be null otherwise) rates of the listed rows ...
+static int lvq_cand_meta(somhip_codebook *cb, const uint64_t *d_keys, int64_t count, int knn, bool olvq, int32_t *d_lab, float *d_ta) {
+  hipLaunchKernelGGL(k_lvq_cand_meta, dim3((unsigned)((count * LVQ_K0 + 255) / 256)), dim3(256), 0, cb->e->stream, cb->v, d_keys,
+                     count * LVQ_K0, knn, (const int32_t *)cb->d_labels, olvq ? (const float *)cb->d_talpha : (const float *)nullptr,
+                     d_lab, d_ta);
   HIPCHK(hipGetLastError());
+  return 0;
+}
+// ... and OLVQ1's bound on |rate| of the batch's corrections, from the listed rows' rates
+static int lvq_rate_bound(somhip_engine *e, const uint64_t *d_keys, int64_t count, const float *d_ta, float clamp, float *amax_dev) {
+  hipLaunchKernelGGL(k_lvq_amax, dim3(1), dim3(256), 0, e->stream, d_keys, count * LVQ_K0, d_ta, clamp, amax_dev);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// relation: rho_j of relation (*) for every sample (masked data: the sample's norm over its own components), the
+// relation over all pairs of the batch (the plan's kernel), its connected components
+static int lvq_relation(somhip_engine *e, somhip_dataset *ds, const LvqPlan &pl, const LvqBatchBufs &b, const LvqBatch &bt) {
+  LaunchTimer t(e, KID_LVQ_COMPONENTS);
+  if (!pl.single) {
+    const uint8_t *mask = (const uint8_t *)ds->d_mask;
+    const unsigned nt = (unsigned)((bt.c + 63) / 64);
+    (void)with_value<1, 0>(pl.masked, [&](auto m) {       // (a bool: always found)
+      hipLaunchKernelGGL(k_lvq_sample_rho<decltype(m)::value != 0>, dim3((unsigned)((bt.c + 3) / 4)), dim3(256), 0, e->stream,
+                         ds->d_rows, ds->n, ds->d, bt.row0, bt.c, bt.cand, bt.amax, bt.amax_dev, b.rho, b.xnorm, mask);
+      return 0;
+    });
+    HIPCHK(hipGetLastError());
+    if (pl.pairs == LVQ_PAIRS_MFMA)
+      hipLaunchKernelGGL(k_lvq_pair_adj_mfma, dim3(nt, nt), dim3(256), 0, e->stream, ds->d_rows, ds->n, ds->d, bt.row0, bt.c,
+                         (const float *)b.rho, (const float *)b.xnorm, b.adj);
+    else
+      (void)with_value<1, 0>(pl.masked, [&](auto m) {
+        hipLaunchKernelGGL(k_lvq_pair_adj<decltype(m)::value != 0>, dim3(nt, nt), dim3(256), 0, e->stream, ds->d_rows, ds->n,
+                           ds->d, bt.row0, bt.c, (const float *)b.rho, b.adj, mask);
+        return 0;
+      });
+    HIPCHK(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_lvq_components, dim3(1), dim3(LVQ_BMAX), (size_t)bt.c * LVQ_AW * 4, e->stream, (const uint32_t *)b.adj, bt.c,
+                     pl.single ? 1 : 0, b.comp_samples, b.out);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// walk: one workgroup per component walks its samples < limit in order (k_lvq_batch_apply<true> stages the sample's
+// mask row beside the sample)
+static int lvq_walk(somhip_codebook *cb, somhip_dataset *ds, const LvqPlan &pl, const LvqBatchBufs &b, const LvqBatch &bt, int limit) {
+  somhip_engine *e = cb->e;
+  LaunchTimer t(e, KID_LVQ_BATCH_APPLY);
+  return with_value<1, 0>(pl.masked, [&](auto m) {
+    hipLaunchKernelGGL(k_lvq_batch_apply<decltype(m)::value != 0>, dim3((unsigned)bt.c), dim3(LVQ_BT), pl.dyn, e->stream, cb->v,
+                       ds->d_rows, ds->n, bt.row0, limit, bt.lab, bt.ta, bt.xrows, bt.xc, bt.cand, bt.st, pl.knn, pl.slots,
+                       (const int32_t *)b.comp_samples, bt.fin, b.stage_rows, b.stage_rowid, b.stage_ta, b.out,
+                       (const uint8_t *)ds->d_mask);
+    HIPCHK(hipGetLastError());
+    return 0;
+  });
+}
+
+// commit: the staged rows (OLVQ1: rates) of ncomp components into the rows this shard owns, with the list of rows it
+// wrote; with a control block, only if every component ran through and no earlier batch was left stopped
+static int lvq_commit(somhip_codebook *cb, const LvqPlan &pl, const LvqBatchBufs &b, const LvqBatch &bt, int ncomp, LvqCtl *d_ctl,
+                      int batch_id) {
+  somhip_engine *e = cb->e;
+  HIPCHK(hipMemsetAsync(b.mod_count, 0, sizeof(int32_t), e->stream));
+  LaunchTimer t(e, KID_LVQ_BATCH_APPLY);
+  hipLaunchKernelGGL(k_lvq_commit, dim3((unsigned)ncomp), dim3(256), 0, e->stream, cb->v, (const LvqBatchOut *)b.out,
+                     (const float4 *)b.stage_rows, (const int32_t *)b.stage_rowid, (const float *)b.stage_ta,
+                     pl.knn == 1 && bt.ta ? cb->d_talpha : (float *)nullptr, b.mod_rows, b.mod_count, d_ctl, batch_id,
+                     d_ctl ? bt.c : 0);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// refresh of prepared rows: the bf16 copies / norms of exactly the rows this batch corrected (at most `bound` of them;
+// none if *skip), so that the next batch's pre-filter (big codebooks, scan_keys_topk) needs no pass over the whole
+// codebook -- only if they were current for the codebook this batch started from (a scan that took the direct path
+// never made them so: re-splitting a few rows of stale tiles must not validate them)
+static int lvq_refresh_prepared(somhip_codebook *cb, const LvqBatchBufs &b, int bound, const int32_t *skip) {
+  somhip_engine *e = cb->e;
+  if (!cb->prep_valid || !cb->d_chi || !cb->d_cn || e->scan_mode != SOMHIP_SCAN_MFMA_BF16) { cb->prep_valid = false; return 0; }
+  hipLaunchKernelGGL(k_prep_rows_bf16, dim3((unsigned)((bound + 3) / 4)), dim3(256), 0, e->stream, cb->v, (cb->v.d4 + 1) / 2,
+                     (const int32_t *)b.mod_rows, bound, (const int32_t *)b.mod_count, cb->d_cn, cb->d_chi, cb->d_clo, skip);
+  HIPCHK(hipGetLastError());
+  cb->rowmajor_valid = false;                             // (the row-major copy is not re-split row by row)
+  return 0;
+}
+
+// One batch the careful way: relation (*) -> components -> one workgroup per component walks its samples in order ->
+// (repeat with the batch cut at the first stop, if any) -> commit -> refresh.  *consumed <= bt.c samples were applied;
+// *reason: why the batch was cut (0: it was not).
+static int lvq_batch_careful(somhip_codebook *cb, somhip_dataset *ds, const LvqPlan &pl, const LvqBatchBufs &b, const LvqBatch &bt,
+                             int *consumed, int *reason) {
+  somhip_engine *e = cb->e;
+  CHK(lvq_relation(e, ds, pl, b, bt));
   static_assert(sizeof(LvqBatchOut) < 32768, "summary block");
   std::vector<char> hbuf(sizeof(LvqBatchOut));
   LvqBatchOut *ho = reinterpret_cast<LvqBatchOut *>(hbuf.data());
-  int limit = c;
+  int limit = bt.c;
   for (int pass = 0; pass < 2; pass++) {
-    CHK(lvq_launch_walk(cb, ds, b, d_st, row0, c, limit, knn, d_cand, d_lab, d_ta, d_xrows, xc, d_fin));
+    CHK(lvq_walk(cb, ds, pl, b, bt, limit));
     HIPCHK(hipMemcpyAsync(ho, b.out, sizeof(LvqBatchOut), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
-    if (ho->ncomp < 1 || ho->ncomp > c) return fail("somhip_lvq_train: bad component count %d", ho->ncomp);
+    if (ho->ncomp < 1 || ho->ncomp > bt.c) return fail("somhip_lvq_train: bad component count %d", ho->ncomp);
     int first_stop = 0x7FFFFFFF, why = 0;
     for (int k = 0; k < ho->ncomp; k++)
       if (ho->stop[k] < first_stop) { first_stop = ho->stop[k]; why = ho->reason[k]; }
@@ -140,102 +285,46 @@ static int lvq_walk_batch(somhip_codebook *cb, somhip_dataset *ds, const LvqBatc
     if (limit == 0) break;                                // nothing can be applied (cannot happen: an empty cache never blocks)
   }
   *consumed = limit;
-  int64_t bound = 0;
-  for (int k = 0; k < ho->ncomp; k++) bound += ho->nslots[k];
-  *nmod_bound = bound;
+  int bound = 0, big = 0;
+  for (int k = 0; k < ho->ncomp; k++) {
+    bound += ho->nslots[k];
+    big = std::max(big, ho->start[k + 1] - ho->start[k]);
+  }
   e->lvq_components += (uint64_t)ho->ncomp;
-  int big = 0;
-  for (int k = 0; k < ho->ncomp; k++) big = std::max(big, ho->start[k + 1] - ho->start[k]);
   e->lvq_largest += (uint64_t)big;
   for (int k = 0; k < 4; k++) e->lvq_cycles[k] += (uint64_t)ho->cycles[k];
   if (limit > 0 && bound > 0) {
-    HIPCHK(hipMemsetAsync(b.mod_count, 0, sizeof(int32_t), e->stream));
-    LaunchTimer t(e, KID_LVQ_BATCH_APPLY);
-    hipLaunchKernelGGL(k_lvq_commit, dim3((unsigned)ho->ncomp), dim3(256), 0, e->stream, cb->v, (const LvqBatchOut *)b.out,
-                       (const float4 *)b.stage_rows, (const int32_t *)b.stage_rowid, (const float *)b.stage_ta,
-                       knn == 1 && d_ta ? cb->d_talpha : (float *)nullptr, b.mod_rows, b.mod_count);
-    HIPCHK(hipGetLastError());
-    // the bf16 copies / norms of exactly the rows this batch corrected, so that the next batch's pre-filter (big
-    // codebooks, scan_keys_topk) needs no pass over the whole codebook -- only if they were current for the codebook
-    // this batch started from (a scan that took the direct path never made them so: re-splitting a few rows of stale
-    // tiles must not validate them)
-    if (cb->prep_valid && cb->d_chi && cb->d_cn && e->scan_mode == SOMHIP_SCAN_MFMA_BF16) {
-      hipLaunchKernelGGL(k_prep_rows_bf16, dim3((unsigned)((bound + 3) / 4)), dim3(256), 0, e->stream, cb->v,
-                         (cb->v.d4 + 1) / 2, (const int32_t *)b.mod_rows, (int)bound, (const int32_t *)b.mod_count, cb->d_cn,
-                         cb->d_chi, cb->d_clo);
-      HIPCHK(hipGetLastError());
-      cb->rowmajor_valid = false;                           // (the row-major copy is not re-split row by row)
-    } else {
-      cb->prep_valid = false;
-    }
+    CHK(lvq_commit(cb, pl, b, bt, ho->ncomp, nullptr, 0));
+    CHK(lvq_refresh_prepared(cb, b, bound, nullptr));
   }
   return 0;
 }
 
-// bound on |rate| of the batch's corrections from its step scalars (LVQ1 / LVQ2.1 / LVQ3: the schedule value, and
-// alpha * epsilon); OLVQ1 rates live per row: see k_lvq_amax
-static float lvq_amax_of(const LvqStep *st, int c) {
-  float m = 0.0f;
-  for (int j = 0; j < c; j++) {
-    const float a = std::fabs(st[j].alpha), ae = std::fabs(st[j].alpha * st[j].epsilon);
-    if (!(a == a) || !(ae == ae)) return -1.0f;
-    m = std::max(m, std::max(a, ae));
-  }
-  return m;
-}
-
-// The walk of a batch as the loop below launches it when it does not wait for the host: relation (*), components,
-// one walk over the whole batch, then a commit that happens only if every component ran through (k_lvq_commit with
-// the control block) -- no read-back in between.  fin: where this batch's winners go (trace).
-static int lvq_walk_batch_nowait(somhip_codebook *cb, somhip_dataset *ds, const LvqBatchBufs &b, const LvqStep *d_st, int64_t row0,
-                                 int c, int knn, const uint64_t *d_cand, const int32_t *d_lab, const float *d_ta, float amax,
-                                 bool amax_on_device, uint64_t *d_fin, LvqCtl *d_ctl, int batch_id) {
-  somhip_engine *e = cb->e;
-  CHK(lvq_set_attrs(e));
-  {
-    LaunchTimer t(e, KID_LVQ_COMPONENTS);
-    CHK(lvq_launch_sample_rho(e, ds, b, row0, c, d_cand, amax, amax_on_device));
-    CHK(lvq_launch_pair_adj(e, ds, b, row0, c));
-    hipLaunchKernelGGL(k_lvq_components, dim3(1), dim3(LVQ_BMAX), (size_t)c * LVQ_AW * 4, e->stream, (const uint32_t *)b.adj, c,
-                       0, b.comp_samples, b.out);
-  }
-  CHK(lvq_launch_walk(cb, ds, b, d_st, row0, c, c, knn, d_cand, d_lab, d_ta, (const float4 *)nullptr, 0, d_fin));
-  HIPCHK(hipMemsetAsync(b.mod_count, 0, sizeof(int32_t), e->stream));
-  {
-    LaunchTimer t(e, KID_LVQ_BATCH_APPLY);
-    hipLaunchKernelGGL(k_lvq_commit, dim3((unsigned)c), dim3(256), 0, e->stream, cb->v, (const LvqBatchOut *)b.out,
-                       (const float4 *)b.stage_rows, (const int32_t *)b.stage_rowid, (const float *)b.stage_ta,
-                       knn == 1 && d_ta ? cb->d_talpha : (float *)nullptr, b.mod_rows, b.mod_count, d_ctl, batch_id, c);
-  }
-  HIPCHK(hipGetLastError());
-  // the bf16 copies / norms of the rows this batch corrected (see lvq_walk_batch); at most two rows per sample
-  if (cb->prep_valid && cb->d_chi && cb->d_cn && e->scan_mode == SOMHIP_SCAN_MFMA_BF16) {
-    hipLaunchKernelGGL(k_prep_rows_bf16, dim3((unsigned)((2 * c + 3) / 4)), dim3(256), 0, e->stream, cb->v,
-                       (cb->v.d4 + 1) / 2, (const int32_t *)b.mod_rows, 2 * c, (const int32_t *)b.mod_count, cb->d_cn,
-                       cb->d_chi, cb->d_clo, (const int32_t *)&d_ctl->poison);
-    HIPCHK(hipGetLastError());
-    cb->rowmajor_valid = false;                             // (the row-major copy is not re-split row by row)
-  } else {
-    cb->prep_valid = false;
-  }
-  return 0;
+// One batch as the loop below launches it when it does not wait for the host: relation (*), components, one walk
+// over the whole batch, then a commit that happens only if every component ran through (the control block) and a
+// refresh that is skipped if it did not -- no read-back in between.  At most two rows per sample are corrected.
+static int lvq_batch_nowait(somhip_codebook *cb, somhip_dataset *ds, const LvqPlan &pl, const LvqBatchBufs &b, const LvqBatch &bt,
+                            LvqCtl *d_ctl, int batch_id) {
+  CHK(lvq_relation(cb->e, ds, pl, b, bt));
+  CHK(lvq_walk(cb, ds, pl, b, bt, bt.c));
+  CHK(lvq_commit(cb, pl, b, bt, bt.c, d_ctl, batch_id));
+  return lvq_refresh_prepared(cb, b, 2 * bt.c, (const int32_t *)&d_ctl->poison);
 }
 
 // The exact batched engine's loop.  Batch after batch is launched without waiting for the one before (its scalars
 // go through the ring of pinned buffers, its verdict stays on the device: LvqCtl); the control block of every batch
 // is read back asynchronously and looked at a few batches later.  A batch that stopped early -- rare: the candidate
 // lists and the row cache are sized so that it is -- has poisoned everything launched after it; the host then redoes
-// that one batch with lvq_walk_batch (which cuts it at the stop and reads the verdict back) and goes on from there.
-// SOMHIP_LVQ_SYNC=1: every batch the careful way.
-static int lvq_train_batched(somhip_codebook *cb, somhip_dataset *ds, const somhip_lvq_params *p, int knn,
-                             float *talpha, int32_t *trace_index, float *trace_diff) {
+// that one batch with lvq_batch_careful (which cuts it at the stop and reads the verdict back) and goes on from there.
+// A plan without nowait: every batch the careful way.
+static int lvq_train_batched(somhip_codebook *cb, somhip_dataset *ds, const somhip_lvq_params *p, const LvqPlan &pl,
+                             int32_t *trace_index, float *trace_diff) {
   somhip_engine *e = cb->e;
   const int64_t BMAX = LVQ_BMAX;
   constexpr int RING = 8;
   void *dcand, *dfin, *dst, *dctl_v;
   const bool want_trace = trace_index || trace_diff;
-  // no waiting only if the winners of the whole call fit a device buffer (they are read back at the end)
-  const bool nowait = !getenv("SOMHIP_LVQ_SYNC") && !getenv("SOMHIP_LVQ_SERIAL") && (!want_trace || p->count <= (1ll << 22));
+  const bool nowait = pl.nowait;
   CHK(engine_scratch(e, SLOT_CALL_A, sizeof(uint64_t) * (size_t)BMAX * LVQ_K0, &dcand));
   CHK(engine_scratch(e, SLOT_CALL_B, sizeof(LvqStep) * (size_t)BMAX, &dst));
   CHK(engine_scratch(e, SLOT_LVQ_FINAL, sizeof(uint64_t) * 2 * (size_t)(nowait && want_trace ? std::max<int64_t>(p->count, BMAX) : BMAX), &dfin));
@@ -248,57 +337,38 @@ static int lvq_train_batched(somhip_codebook *cb, somhip_dataset *ds, const somh
     if (!e->lvq_ev[i]) HIPCHK(hipEventCreateWithFlags(&e->lvq_ev[i], hipEventDisableTiming));
   HIPCHK(hipMemsetAsync(dctl, 0, sizeof(LvqCtl), e->stream));
   std::vector<LvqStep> hst((size_t)BMAX);
-  std::vector<uint64_t> hfin;
-  const float ratio = (1 - p->winlen) / (1 + p->winlen);                  // lvq_rout.c:770, fp32
-  const bool olvq = p->kind == SOMHIP_OLVQ1;
   int64_t B = std::max<int64_t>(32, std::min<int64_t>(BMAX, e->lvq_batch_hint));   // what the previous call ended with
   int64_t off = 0;
   uint64_t n_sync_batches = 0;
-  auto fill_steps = [&](LvqStep *st, int64_t o, int64_t c) {
-    const int64_t it0 = p->start_iter + o, row0 = (p->data_first + o) % ds->n;
-    for (int64_t j = 0; j < c; j++) {
-      LvqStep s;
-      s.kind = p->kind;
-      s.alpha = alpha_at(p->alpha_type, it0 + j, p->length, p->alpha);
-      s.alpha_clamp = p->alpha;
-      s.win_ratio = ratio;
-      s.epsilon = p->epsilon;
-      s.label = ds->labels[(size_t)((row0 + j) % ds->n)];
-      st[(size_t)j] = s;
-    }
-  };
-  auto launch_front = [&](int64_t row0, int64_t c) -> int {   // candidate lists, their labels / rates, the OLVQ1 rate bound
-    CHK(scan_keys_topk<LVQ_K0>(cb, ds, row0, c, (uint64_t *)dcand, knn == 2 ? 1 : 0));
-    hipLaunchKernelGGL(k_lvq_cand_meta, dim3((unsigned)((c * LVQ_K0 + 255) / 256)), dim3(256), 0, e->stream, cb->v,
-                       (const uint64_t *)dcand, c * LVQ_K0, knn, (const int32_t *)cb->d_labels,
-                       olvq ? (const float *)cb->d_talpha : (const float *)nullptr, b.cand_lab, olvq ? b.cand_ta : (float *)nullptr);
-    if (olvq)
-      hipLaunchKernelGGL(k_lvq_amax, dim3(1), dim3(256), 0, e->stream, (const uint64_t *)dcand, c * LVQ_K0, (const float *)b.cand_ta,
-                         p->alpha, b.amax_dev);
-    HIPCHK(hipGetLastError());
+  // the c samples from offset o of the call: their step scalars (host, on their way to dst already) -> the front
+  // (candidate lists, their labels / rates, the OLVQ1 rate bound) -> the batch
+  auto front = [&](int64_t o, int64_t c, const LvqStep *st, uint64_t *fin, LvqBatch *bt) -> int {
+    const int64_t row0 = (p->data_first + o) % ds->n;
+    float *ta = pl.olvq ? b.cand_ta : (float *)nullptr;
+    CHK(scan_keys_topk<LVQ_K0>(cb, ds, row0, c, (uint64_t *)dcand, pl.knn == 2 ? 1 : 0));
+    CHK(lvq_cand_meta(cb, (const uint64_t *)dcand, c, pl.knn, pl.olvq, b.cand_lab, ta));
+    if (pl.olvq) CHK(lvq_rate_bound(e, (const uint64_t *)dcand, c, ta, p->alpha, b.amax_dev));
+    *bt = {row0, (int)c, (const LvqStep *)dst, (const uint64_t *)dcand, b.cand_lab, ta, nullptr, 0,
+           pl.olvq ? 0.0f : lvq_amax_of(st, (int)c), pl.olvq ? b.amax_dev : (float *)nullptr, fin};
     return 0;
   };
   struct Pending { int64_t off, c; int id; };
   Pending ring[RING];
   int head = 0, tail = 0, next_id = 1;                    // batches in flight: ring[tail % RING .. head % RING)
   int64_t launched = 0;                                   // samples launched so far (assuming every batch runs through)
+  LvqBatch bt;
   while (off < p->count) {
     if (nowait) {
       // ---- keep launching; look at the oldest read-back when the ring is full or nothing is left to launch
       if (launched < p->count && head - tail < RING) {
         const int64_t c = std::min(B, p->count - launched);
-        const int64_t row0 = (p->data_first + launched) % ds->n;
         void *hv; int slot;
         CHK(pin_acquire(e, sizeof(LvqStep) * (size_t)c, &hv, &slot));
-        fill_steps((LvqStep *)hv, launched, c);
+        lvq_fill_steps(ds, p, p->start_iter + launched, p->data_first + launched, c, (LvqStep *)hv);
         CHK(pin_upload(e, slot, dst, sizeof(LvqStep) * (size_t)c));
-        CHK(launch_front(row0, c));
-        const float amax = olvq ? 0.0f : lvq_amax_of((const LvqStep *)hv, (int)c);
-        // (a rate bound < 0 -- a NaN in the schedule -- makes the whole batch one component inside k_lvq_sample_rho)
+        CHK(front(launched, c, (const LvqStep *)hv, (uint64_t *)dfin + (want_trace ? 2 * launched : 0), &bt));
         const int id = next_id++;
-        CHK(lvq_walk_batch_nowait(cb, ds, b, (const LvqStep *)dst, row0, (int)c, knn, (const uint64_t *)dcand, b.cand_lab,
-                                  olvq ? b.cand_ta : (const float *)nullptr, amax, olvq,
-                                  (uint64_t *)dfin + (want_trace ? 2 * launched : 0), dctl, id));
+        CHK(lvq_batch_nowait(cb, ds, pl, b, bt, dctl, id));
         HIPCHK(hipMemcpyAsync(&e->lvq_hctl[head % RING], dctl, sizeof(LvqCtl), hipMemcpyDeviceToHost, e->stream));
         HIPCHK(hipEventRecord(e->lvq_ev[head % RING], e->stream));
         ring[head % RING] = {launched, c, id};
@@ -319,32 +389,17 @@ static int lvq_train_batched(somhip_codebook *cb, somhip_dataset *ds, const somh
       HIPCHK(hipMemsetAsync(dctl, 0, 4 * sizeof(int32_t), e->stream));    // clear the flag, keep the statistics
       B = pd.c;
     }
-    // ---- one batch the careful way (SOMHIP_LVQ_SYNC, or the redo of a batch that stopped early)
+    // ---- one batch the careful way (a plan without nowait, or the redo of a batch that stopped early)
     const int64_t c = std::min(B, p->count - off);
-    const int64_t row0 = (p->data_first + off) % ds->n;
-    fill_steps(hst.data(), off, c);
+    lvq_fill_steps(ds, p, p->start_iter + off, p->data_first + off, c, hst.data());
     HIPCHK(hipMemcpyAsync(dst, hst.data(), sizeof(LvqStep) * (size_t)c, hipMemcpyHostToDevice, e->stream));
-    CHK(launch_front(row0, c));
+    CHK(front(off, c, hst.data(), (uint64_t *)dfin + (nowait && want_trace ? 2 * off : 0), &bt));
     int consumed = 0, reason = 0;
-    int64_t nmod = 0;
-    uint64_t *fin_here = (uint64_t *)dfin + (nowait && want_trace ? 2 * off : 0);
-    CHK(lvq_walk_batch(cb, ds, b, (const LvqStep *)dst, row0, (int)c, knn, (const uint64_t *)dcand, b.cand_lab,
-                       olvq ? b.cand_ta : (const float *)nullptr, nullptr, 0, olvq ? 0.0f : lvq_amax_of(hst.data(), (int)c), olvq,
-                       fin_here, &consumed, &reason, &nmod));
+    CHK(lvq_batch_careful(cb, ds, pl, b, bt, &consumed, &reason));
     if (consumed <= 0)
       // cannot happen: with an empty cache every winner comes from the frozen list and one or two slots always fit
       return fail("somhip_lvq_train: batch made no progress (reason %d)", reason);
-    if (want_trace && !nowait) {
-      hfin.resize((size_t)BMAX * 2);
-      HIPCHK(hipMemcpy(hfin.data(), dfin, sizeof(uint64_t) * 2 * (size_t)consumed, hipMemcpyDeviceToHost));
-      for (int64_t j = 0; j < consumed; j++)
-        for (int k = 0; k < knn; k++) {
-          int32_t idx; float df;
-          decode_key(hfin[(size_t)(2 * j + k)], knn == 2, &idx, &df);
-          if (trace_index) trace_index[(off + j) * knn + k] = idx;
-          if (trace_diff) trace_diff[(off + j) * knn + k] = df;
-        }
-    }
+    if (want_trace && !nowait) CHK(lvq_trace_read((const uint64_t *)dfin, consumed, pl.knn, off, trace_index, trace_diff));
     off += consumed;
     launched = off;
     n_sync_batches++;
@@ -363,26 +418,82 @@ static int lvq_train_batched(somhip_codebook *cb, somhip_dataset *ds, const somh
   e->lvq_components += fin_ctl.comps;
   e->lvq_largest += fin_ctl.largest;
   for (int k = 0; k < 4; k++) e->lvq_cycles[k] += fin_ctl.cycles[k];
-  if (nowait && want_trace) {
-    hfin.resize((size_t)p->count * 2);
-    HIPCHK(hipMemcpy(hfin.data(), dfin, sizeof(uint64_t) * 2 * (size_t)p->count, hipMemcpyDeviceToHost));
-    for (int64_t j = 0; j < p->count; j++)
-      for (int k = 0; k < knn; k++) {
-        int32_t idx; float df;
-        decode_key(hfin[(size_t)(2 * j + k)], knn == 2, &idx, &df);
-        if (trace_index) trace_index[j * knn + k] = idx;
-        if (trace_diff) trace_diff[j * knn + k] = df;
-      }
-  }
+  if (nowait && want_trace) CHK(lvq_trace_read((const uint64_t *)dfin, p->count, pl.knn, 0, trace_index, trace_diff));
   e->lvq_batches += n_sync_batches + fin_ctl.batches;
   e->lvq_samples += (uint64_t)p->count;
   e->lvq_batch_hint = B;
   return 0;
 }
 
-// lvq*_training (include/somhip.h): the exact batched engine, masked data included (the sample's mask in the frozen
-// scan, in relation (*) and in the walk); else -- SOMHIP_LVQ_ONLINE=1, a patch-ordered codebook, a row too long for
-// the cache -- one k_lvq_online_step launch per iteration
+// The one-launch-per-iteration engine: k_lvq_online_step applies the previous iteration's correction and searches
+// the current sample's winners in one pass over the codebook.
+static int lvq_train_online(somhip_codebook *cb, somhip_dataset *ds, const somhip_lvq_params *p, const LvqPlan &pl,
+                            int32_t *trace_index, float *trace_diff) {
+  somhip_engine *e = cb->e;
+  cb->prep_valid = false;                                 // the per-iteration kernel rewrites rows in place
+  const int64_t CH = 4096;
+  const int nblk = (int)((cb->v.ngroups + 3) / 4);
+  const bool want_trace = trace_index || trace_diff;
+  void *dpart, *dfinal, *dst;
+  CHK(engine_scratch(e, SLOT_PARTIAL, sizeof(uint64_t) * (size_t)nblk * 2 * 2, &dpart));
+  CHK(engine_scratch(e, SLOT_CALL_A, sizeof(uint64_t) * (size_t)(CH + 1) * 2, &dfinal));
+  CHK(engine_scratch(e, SLOT_CALL_B, sizeof(LvqStep) * (size_t)(CH + 1), &dst));
+  uint64_t *part[2] = {(uint64_t *)dpart, (uint64_t *)dpart + (size_t)nblk * 2};
+  uint64_t *fin = (uint64_t *)dfinal;
+  LvqStep *st = (LvqStep *)dst;
+  std::vector<LvqStep> hst((size_t)CH + 1);
+  std::vector<uint64_t> hfin((size_t)(CH + 1) * 2);
+  int64_t prev_row = 0;
+  bool have_prev = false;
+  int flip = 0;
+  // one iteration: the correction of the sample before (if any) with its scalars st_j, the winners of data row cur_row
+  // (if has_cur); the merged winners of the sample before go to fin_j
+  auto step = [&](int64_t cur_row, int has_cur, uint64_t *fin_j, const LvqStep *st_j) {
+    LaunchTimer t(e, KID_LVQ_ONLINE_STEP);
+    (void)with_value<1, 0>(pl.masked, [&](auto m) {       // (a bool: always found)
+      hipLaunchKernelGGL(k_lvq_online_step<decltype(m)::value != 0>, dim3((unsigned)nblk), dim3(256), 0, e->stream, cb->v,
+                         ds->d_rows, (const uint8_t *)ds->d_mask, (const int32_t *)cb->d_labels, cb->d_talpha, prev_row, cur_row,
+                         have_prev ? 1 : 0, has_cur, pl.knn, (const uint64_t *)part[flip], nblk, part[flip ^ 1], fin_j, st_j);
+      return 0;
+    });
+    flip ^= 1;
+    prev_row = cur_row;
+    have_prev = true;
+  };
+  // fin[j] receives the merged winners of chunk-iteration j-1 when iteration j launches;
+  // the last one of a chunk lands in fin[c] when the next chunk's first launch (or the
+  // flush) runs, so traces are read one launch late.
+  for (int64_t off = 0; off < p->count; off += CH) {
+    const int64_t c = std::min(CH, p->count - off);
+    const int64_t row0 = (p->data_first + off) % ds->n;
+    lvq_fill_steps(ds, p, p->start_iter + off, row0, c, hst.data() + 1);
+    HIPCHK(hipMemcpyAsync(st + 1, hst.data() + 1, sizeof(LvqStep) * (size_t)c, hipMemcpyHostToDevice, e->stream));
+    for (int64_t j = 0; j < c; j++) step((row0 + j) % ds->n, 1, fin + 2 * j, st + j);
+    HIPCHK(hipGetLastError());
+    // winners of iterations (off-1 .. off+c-2) are now in fin[0..c-1]; fin[0] of the first chunk holds nothing
+    if (want_trace) {
+      HIPCHK(hipMemcpyAsync(hfin.data(), fin, sizeof(uint64_t) * 2 * (size_t)c, hipMemcpyDeviceToHost, e->stream));
+      HIPCHK(hipStreamSynchronize(e->stream));
+      const int64_t skip = off == 0 ? 1 : 0;
+      lvq_trace(hfin.data() + 2 * skip, c - skip, pl.knn, off - 1 + skip, trace_index, trace_diff);
+    }
+    HIPCHK(hipMemcpyAsync(st, st + c, sizeof(LvqStep), hipMemcpyDeviceToDevice, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+  }
+  // flush: apply the last iteration's correction; its winners land in fin[0]
+  step(prev_row, 0, fin, st);
+  HIPCHK(hipGetLastError());
+  if (want_trace) {
+    HIPCHK(hipMemcpyAsync(hfin.data(), fin, sizeof(uint64_t) * 2, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    lvq_trace(hfin.data(), 1, pl.knn, p->count - 1, trace_index, trace_diff);
+  }
+  return 0;
+}
+
+// lvq*_training (include/somhip.h): checks, the plan, the engine it names -- the exact batched engine, masked data
+// included (the sample's mask in the frozen scan, in relation (*) and in the walk); else (asked for, a patch-ordered
+// codebook, a row too long for the cache) one k_lvq_online_step launch per iteration
 extern "C" int somhip_lvq_train(somhip_codebook *cb, somhip_dataset *ds, const somhip_lvq_params *p,
                                 float *talpha, int32_t *trace_index, float *trace_diff) try {
   CHK(check_pair(cb, ds, "somhip_lvq_train"));
@@ -393,125 +504,17 @@ extern "C" int somhip_lvq_train(somhip_codebook *cb, somhip_dataset *ds, const s
   if (p->kind == SOMHIP_OLVQ1 && !talpha) return fail("somhip_lvq_train: OLVQ1 needs talpha");
   if (p->length <= 0 || p->count < 0 || p->start_iter + p->count > p->length)
     return fail("somhip_lvq_train: iterations outside schedule");
-  // masked data: a sample with every component masked has no winner, and the reference then adapts through a NULL
-  // winner (lvq_rout.c:542-545) -- refuse such a run before anything is trained
-  const bool masked = ds->d_mask != nullptr;
-  if (masked && !ds->all_masked.empty())
-    for (int64_t j = 0; j < std::min<int64_t>(p->count, ds->n); j++) {
-      const int64_t r = (p->data_first + j) % ds->n;
-      if (ds->all_masked[(size_t)r])
-        return fail("somhip_lvq_train: data row %lld has every component masked: no winner (the reference crashes here)",
-                    (long long)r);
-    }
+  CHK(lvq_refuse_all_masked(ds, p->data_first, p->count, "somhip_lvq_train"));
   if (cb->v.row_offset != 0 || cb->n_global != cb->v.n) return fail("somhip_lvq_train: sharded codebook not supported");
-  const int knn = (p->kind >= SOMHIP_LVQ2) ? 2 : 1;
-  if (knn == 2 && cb->v.n < 2) return fail("somhip_lvq_train: LVQ2/LVQ3 need at least two code rows");
+  const LvqPlan pl = lvq_plan(cb, ds, p, trace_index || trace_diff);
+  if (pl.knn == 2 && cb->v.n < 2) return fail("somhip_lvq_train: LVQ2/LVQ3 need at least two code rows");
   if (p->count == 0) return 0;
   somhip_engine *e = cb->e;
   HIPCHK(hipSetDevice(e->device));
-  if (p->kind == SOMHIP_OLVQ1) {
-    if (!cb->d_talpha) HIPCHK(hipMalloc((void **)&cb->d_talpha, sizeof(float) * (size_t)cb->v.n));
-    HIPCHK(hipMemcpyAsync(cb->d_talpha, talpha, sizeof(float) * (size_t)cb->v.n, hipMemcpyHostToDevice, e->stream));
-  }
-  // exact batched engine unless asked otherwise (SOMHIP_LVQ_ONLINE=1) or the row does not fit the cache
-  if (!getenv("SOMHIP_LVQ_ONLINE") && cb->v.patch_w == 0 && cb->v.d4 <= LVQ_BT && lvq_cache_slots(cb->v.d4) >= 8) {
-    int rc = lvq_train_batched(cb, ds, p, knn, talpha, trace_index, trace_diff);
-    if (rc) return rc;
-    if (p->kind == SOMHIP_OLVQ1)
-      HIPCHK(hipMemcpyAsync(talpha, cb->d_talpha, sizeof(float) * (size_t)cb->v.n, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return 0;
-  }
-  cb->prep_valid = false;                                 // the per-iteration kernel rewrites rows in place
-  auto step = masked ? k_lvq_online_step<true> : k_lvq_online_step<false>;
-  const int64_t CH = 4096;
-  const int nblk = (int)((cb->v.ngroups + 3) / 4);
-  void *dpart, *dfinal, *dst;
-  CHK(engine_scratch(e, SLOT_PARTIAL, sizeof(uint64_t) * (size_t)nblk * 2 * 2, &dpart));
-  CHK(engine_scratch(e, SLOT_CALL_A, sizeof(uint64_t) * (size_t)(CH + 1) * 2, &dfinal));
-  CHK(engine_scratch(e, SLOT_CALL_B, sizeof(LvqStep) * (size_t)(CH + 1), &dst));
-  uint64_t *part[2] = {(uint64_t *)dpart, (uint64_t *)dpart + (size_t)nblk * 2};
-  uint64_t *fin = (uint64_t *)dfinal;
-  LvqStep *st = (LvqStep *)dst;
-  std::vector<LvqStep> hst((size_t)CH + 1);
-  std::vector<uint64_t> hfin((size_t)(CH + 1) * 2);
-  const float ratio = (1 - p->winlen) / (1 + p->winlen);                  // lvq_rout.c:770, fp32
-  int64_t prev_row = 0;
-  bool have_prev = false;
-  int flip = 0;
-  // fin[j] receives the merged winners of chunk-iteration j-1 when iteration j launches;
-  // the last one of a chunk lands in fin[c] when the next chunk's first launch (or the
-  // flush) runs, so traces are read one launch late.
-  int64_t pending_trace = -1;   // global offset of the iteration whose winners arrive next
-  for (int64_t off = 0; off < p->count; off += CH) {
-    int64_t c = std::min(CH, p->count - off);
-    int64_t it0 = p->start_iter + off, row0 = (p->data_first + off) % ds->n;
-    for (int64_t j = 0; j < c; j++) {
-      int64_t r = (row0 + j) % ds->n;
-      LvqStep s;
-      s.kind = p->kind;
-      s.alpha = alpha_at(p->alpha_type, it0 + j, p->length, p->alpha);
-      s.alpha_clamp = p->alpha;
-      s.win_ratio = ratio;
-      s.epsilon = p->epsilon;
-      s.label = ds->labels[(size_t)r];
-      hst[(size_t)j + 1] = s;
-    }
-    HIPCHK(hipMemcpyAsync(st + 1, hst.data() + 1, sizeof(LvqStep) * (size_t)c, hipMemcpyHostToDevice, e->stream));
-    for (int64_t j = 0; j < c; j++) {
-      int64_t cur_row = (row0 + j) % ds->n;
-      {
-        LaunchTimer t(e, KID_LVQ_ONLINE_STEP);
-        hipLaunchKernelGGL(step, dim3((unsigned)nblk), dim3(256), 0, e->stream, cb->v,
-                           ds->d_rows, (const uint8_t *)ds->d_mask, (const int32_t *)cb->d_labels, cb->d_talpha,
-                           prev_row, cur_row, have_prev ? 1 : 0, 1, knn, (const uint64_t *)part[flip], nblk,
-                           part[flip ^ 1], fin + 2 * j, (const LvqStep *)(st + j));
-      }
-      flip ^= 1;
-      prev_row = cur_row;
-      have_prev = true;
-    }
-    HIPCHK(hipGetLastError());
-    // winners of iterations (off-1 .. off+c-2) are now in fin[0..c-1]
-    if (trace_index || trace_diff) {
-      HIPCHK(hipMemcpyAsync(hfin.data(), fin, sizeof(uint64_t) * 2 * (size_t)c, hipMemcpyDeviceToHost, e->stream));
-      HIPCHK(hipStreamSynchronize(e->stream));
-      for (int64_t j = 0; j < c; j++) {
-        int64_t it = off + j - 1;
-        if (it < 0) continue;
-        for (int k = 0; k < knn; k++) {
-          int32_t idx; float df;
-          decode_key(hfin[(size_t)(2 * j + k)], knn == 2, &idx, &df);
-          if (trace_index) trace_index[it * knn + k] = idx;
-          if (trace_diff) trace_diff[it * knn + k] = df;
-        }
-      }
-    }
-    HIPCHK(hipMemcpyAsync(st, st + c, sizeof(LvqStep), hipMemcpyDeviceToDevice, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    (void)pending_trace;
-  }
-  // flush: apply the last iteration's correction; its winners land in fin[0]
-  {
-    LaunchTimer t(e, KID_LVQ_ONLINE_STEP);
-    hipLaunchKernelGGL(step, dim3((unsigned)nblk), dim3(256), 0, e->stream, cb->v, ds->d_rows,
-                       (const uint8_t *)ds->d_mask, (const int32_t *)cb->d_labels, cb->d_talpha, prev_row, prev_row, 1,
-                       0, knn, (const uint64_t *)part[flip], nblk, part[flip ^ 1], fin, (const LvqStep *)st);
-  }
-  HIPCHK(hipGetLastError());
-  if (trace_index || trace_diff) {
-    HIPCHK(hipMemcpyAsync(hfin.data(), fin, sizeof(uint64_t) * 2, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    int64_t it = p->count - 1;
-    for (int k = 0; k < knn; k++) {
-      int32_t idx; float df;
-      decode_key(hfin[(size_t)k], knn == 2, &idx, &df);
-      if (trace_index) trace_index[it * knn + k] = idx;
-      if (trace_diff) trace_diff[it * knn + k] = df;
-    }
-  }
-  if (p->kind == SOMHIP_OLVQ1)
-    HIPCHK(hipMemcpyAsync(talpha, cb->d_talpha, sizeof(float) * (size_t)cb->v.n, hipMemcpyDeviceToHost, e->stream));
+  if (pl.olvq) CHK(lvq_rates_to_device(cb, talpha));
+  CHK(pl.batched ? lvq_train_batched(cb, ds, p, pl, trace_index, trace_diff)
+                 : lvq_train_online(cb, ds, p, pl, trace_index, trace_diff));
+  if (pl.olvq) CHK(lvq_rates_to_host(cb, talpha));
   HIPCHK(hipStreamSynchronize(e->stream));
   return 0;
 } ABI_CATCH(somhip_lvq_train)
@@ -525,8 +528,7 @@ extern "C" int somhip_lvq_rates_upload(somhip_codebook *cb, const float *talpha)
   if (!cb || !talpha) return fail("somhip_lvq_rates_upload: null argument");
   if (!cb->e) return fail("somhip_lvq_rates_upload: the engine of this codebook was destroyed");
   HIPCHK(hipSetDevice(cb->e->device));
-  if (!cb->d_talpha) HIPCHK(hipMalloc((void **)&cb->d_talpha, sizeof(float) * (size_t)cb->v.n));
-  HIPCHK(hipMemcpyAsync(cb->d_talpha, talpha, sizeof(float) * (size_t)cb->v.n, hipMemcpyHostToDevice, cb->e->stream));
+  CHK(lvq_rates_to_device(cb, talpha));
   HIPCHK(hipStreamSynchronize(cb->e->stream));
   return 0;
 } ABI_CATCH(somhip_lvq_rates_upload)
@@ -535,7 +537,7 @@ extern "C" int somhip_lvq_rates_download(somhip_codebook *cb, float *talpha) try
   if (!cb->e) return fail("somhip_lvq_rates_download: the engine of this codebook was destroyed");
   if (!cb->d_talpha) return fail("somhip_lvq_rates_download: no rates on this codebook");
   HIPCHK(hipSetDevice(cb->e->device));
-  HIPCHK(hipMemcpyAsync(talpha, cb->d_talpha, sizeof(float) * (size_t)cb->v.n, hipMemcpyDeviceToHost, cb->e->stream));
+  CHK(lvq_rates_to_host(cb, talpha));
   HIPCHK(hipStreamSynchronize(cb->e->stream));
   return 0;
 } ABI_CATCH(somhip_lvq_rates_download)
@@ -553,7 +555,6 @@ extern "C" int somhip_merge_topk_keys(somhip_engine *e, const uint64_t *dev_gath
     return 0;
   });
 } ABI_CATCH(somhip_merge_topk_keys)
-
 extern "C" int somhip_lvq_batch_candidates(somhip_codebook *cb, int64_t count, int kind, const uint64_t *dev_keys, int xrows,
                                            int32_t *dev_lab, float *dev_ta, float *dev_rows) try {
   if (!cb || !dev_keys || !dev_lab || !dev_rows) return fail("somhip_lvq_batch_candidates: null argument");
@@ -568,9 +569,7 @@ extern "C" int somhip_lvq_batch_candidates(somhip_codebook *cb, int64_t count, i
   somhip_engine *e = cb->e;
   HIPCHK(hipSetDevice(e->device));
   const int knn = kind >= SOMHIP_LVQ2 ? 2 : 1;
-  hipLaunchKernelGGL(k_lvq_cand_meta, dim3((unsigned)((count * LVQ_K0 + 255) / 256)), dim3(256), 0, e->stream, cb->v, dev_keys,
-                     count * LVQ_K0, knn, (const int32_t *)cb->d_labels, kind == SOMHIP_OLVQ1 ? (const float *)cb->d_talpha : (const float *)nullptr,
-                     dev_lab, dev_ta);
+  CHK(lvq_cand_meta(cb, dev_keys, count, knn, kind == SOMHIP_OLVQ1, dev_lab, dev_ta));
   hipLaunchKernelGGL(k_lvq_cand_rows, dim3((unsigned)(count * xrows)), dim3(256), 0, e->stream, cb->v, dev_keys, (int)count, xrows, knn,
                      reinterpret_cast<float4 *>(dev_rows));
   HIPCHK(hipGetLastError());
@@ -586,63 +585,33 @@ extern "C" int somhip_lvq_batch_apply(somhip_codebook *cb, somhip_dataset *ds, c
   if (p->kind < SOMHIP_LVQ1 || p->kind > SOMHIP_LVQ3) return fail("Unknown LVQ type %d", p->kind);
   if (ds->labels.empty()) return fail("somhip_lvq_batch_apply: data has no labels");
   if (count < 0 || count > LVQ_BMAX) return fail("somhip_lvq_batch_apply: at most %d samples per batch", LVQ_BMAX);
-  // masked data: a sample with every component masked has no winner (see somhip_lvq_train) -- refuse the batch
-  if (ds->d_mask && !ds->all_masked.empty())
-    for (int64_t j = 0; j < std::min<int64_t>(count, ds->n); j++) {
-      const int64_t r = (data_first + j) % ds->n;
-      if (ds->all_masked[(size_t)r])
-        return fail("somhip_lvq_batch_apply: data row %lld has every component masked: no winner (the reference crashes here)",
-                    (long long)r);
-    }
+  CHK(lvq_refuse_all_masked(ds, data_first, count, "somhip_lvq_batch_apply"));
   if (xrows < 1 || xrows > LVQ_K0) return fail("somhip_lvq_batch_apply: xrows must be 1..%d", LVQ_K0);
   if (p->kind == SOMHIP_OLVQ1 && (!cb->d_talpha || !dev_ta)) return fail("somhip_lvq_batch_apply: OLVQ1 needs rates (somhip_lvq_rates_upload)");
-  if (cb->v.patch_w != 0 || cb->v.d4 > LVQ_BT || lvq_cache_slots(cb->v.d4) < 8)
+  const LvqPlan pl = lvq_plan(cb, ds, p, false);          // (one batch, the careful way: the loop's form is the caller's)
+  if (!pl.fits)
     return fail("somhip_lvq_batch_apply: rows of %d components do not fit the on-chip cache of the batched engine", cb->v.d);
   *consumed = 0;
   if (count == 0) return 0;
   somhip_engine *e = cb->e;
   HIPCHK(hipSetDevice(e->device));
-  const int knn = p->kind >= SOMHIP_LVQ2 ? 2 : 1;
-  const bool olvq = p->kind == SOMHIP_OLVQ1;
   void *dst, *dfin;
   CHK(engine_scratch(e, SLOT_CALL_B, sizeof(LvqStep) * (size_t)LVQ_BMAX, &dst));
   CHK(engine_scratch(e, SLOT_LVQ_FINAL, sizeof(uint64_t) * (size_t)LVQ_BMAX * 2, &dfin));
   LvqBatchBufs b;
   CHK(lvq_batch_bufs(e, cb->v.d4, &b));
   std::vector<LvqStep> hst((size_t)count);
-  const float ratio = (1 - p->winlen) / (1 + p->winlen);                  // lvq_rout.c:770, fp32
   const int64_t row0 = data_first % ds->n;
-  for (int64_t j = 0; j < count; j++) {
-    LvqStep s;
-    s.kind = p->kind;
-    s.alpha = alpha_at(p->alpha_type, batch_start_iter + j, p->length, p->alpha);
-    s.alpha_clamp = p->alpha;
-    s.win_ratio = ratio;
-    s.epsilon = p->epsilon;
-    s.label = ds->labels[(size_t)((row0 + j) % ds->n)];
-    hst[(size_t)j] = s;
-  }
+  lvq_fill_steps(ds, p, batch_start_iter, row0, count, hst.data());
   HIPCHK(hipMemcpyAsync(dst, hst.data(), sizeof(LvqStep) * (size_t)count, hipMemcpyHostToDevice, e->stream));
-  if (olvq)
-    hipLaunchKernelGGL(k_lvq_amax, dim3(1), dim3(256), 0, e->stream, dev_keys, count * LVQ_K0, dev_ta, p->alpha, b.amax_dev);
-  HIPCHK(hipGetLastError());
+  if (pl.olvq) CHK(lvq_rate_bound(e, dev_keys, count, dev_ta, p->alpha, b.amax_dev));
+  const LvqBatch bt = {row0, (int)count, (const LvqStep *)dst, dev_keys, dev_lab, pl.olvq ? dev_ta : (const float *)nullptr,
+                       reinterpret_cast<const float4 *>(dev_rows), xrows, pl.olvq ? 0.0f : lvq_amax_of(hst.data(), (int)count),
+                       pl.olvq ? b.amax_dev : (float *)nullptr, (uint64_t *)dfin};
   int done = 0, reason = 0;
-  int64_t nmod = 0;
-  CHK(lvq_walk_batch(cb, ds, b, (const LvqStep *)dst, row0, (int)count, knn, dev_keys, dev_lab, olvq ? dev_ta : (const float *)nullptr,
-                     reinterpret_cast<const float4 *>(dev_rows), xrows, olvq ? 0.0f : lvq_amax_of(hst.data(), (int)count), olvq,
-                     (uint64_t *)dfin, &done, &reason, &nmod));
+  CHK(lvq_batch_careful(cb, ds, pl, b, bt, &done, &reason));
   if (done <= 0) return fail("somhip_lvq_batch_apply: batch made no progress (reason %d)", reason);
-  if (trace_index || trace_diff) {
-    std::vector<uint64_t> hfin((size_t)done * 2);
-    HIPCHK(hipMemcpy(hfin.data(), dfin, sizeof(uint64_t) * 2 * (size_t)done, hipMemcpyDeviceToHost));
-    for (int64_t j = 0; j < done; j++)
-      for (int k = 0; k < knn; k++) {
-        int32_t idx; float df;
-        decode_key(hfin[(size_t)(2 * j + k)], knn == 2, &idx, &df);
-        if (trace_index) trace_index[j * knn + k] = idx;
-        if (trace_diff) trace_diff[j * knn + k] = df;
-      }
-  }
+  if (trace_index || trace_diff) CHK(lvq_trace_read((const uint64_t *)dfin, done, pl.knn, 0, trace_index, trace_diff));
   if (reason == 1) e->lvq_stop_list++;
   if (reason == 2) e->lvq_stop_cache++;
   e->lvq_batches++;

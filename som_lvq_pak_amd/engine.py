@@ -392,6 +392,22 @@ def lvq_train(cb, ds, kind, length, alpha, alpha_type=ALPHA_LINEAR, winlen=0.0, 
     return talpha, ti, td
 
 
+LVQ_PAIRS = ("masked", "mfma", "direct")
+
+
+def lvq_plan(cb, ds, kind, length, alpha, alpha_type=ALPHA_LINEAR, winlen=0.0, epsilon=0.0, start_iter=0, count=None,
+             data_first=None, trace=True):
+    """The plan lvq_train would follow with these arguments under the current environment (somhip_debug_lvq_plan; host
+    arithmetic, no GPU work): a dict of the engine, the batched loop's form and the choices of a batch."""
+    count = length - start_iter if count is None else count
+    data_first = start_iter % ds.n if data_first is None else data_first
+    p = LvqParams(kind, length, alpha, alpha_type, winlen, epsilon, start_iter, count, data_first)
+    out = (C.c_int32 * 8)()
+    check(cb.e.lib.somhip_debug_lvq_plan(cb.h, ds.h, C.byref(p), int(trace), out))
+    return {"engine": "batched" if out[0] else "online", "loop": "nowait" if out[1] else "careful", "single": bool(out[2]),
+            "pairs": LVQ_PAIRS[out[3]], "masked": bool(out[4]), "knn": out[5], "slots": out[6], "dyn_lds": out[7]}
+
+
 def qerror_sum(diff, ret=None):
     """find_qerror's accumulation (reference som_rout.c:698-715): a float32 running sum of
     double square roots in data order -- O(n) host work on the winners the GPU returned."""

@@ -99,6 +99,26 @@ def test_product_never_touches_oracle():
                 assert "liboracle" not in txt and "oracle/_ref" not in txt and "ref_harness" not in txt, f
 
 
+def test_lvq_driver_plans_once_and_launches_each_kernel_once():
+    """The LVQ host driver decides in one place and launches each stage from one place: each SOMHIP_LVQ_* switch is read
+    by exactly one getenv under csrc/ (lvq_plan), and every LVQ kernel has exactly one launch site in host_lvq.inc (the
+    masked / unmasked instantiations of a template share their site)."""
+    csrc = os.path.join(ROOT, "som_lvq_pak_amd", "csrc")
+    text = {}
+    for dirpath, _, files in os.walk(csrc):
+        for f in files:
+            text[os.path.join(dirpath, f)] = open(os.path.join(dirpath, f), errors="replace").read()
+    for name in ("SOMHIP_LVQ_ONLINE", "SOMHIP_LVQ_SERIAL", "SOMHIP_LVQ_SYNC", "SOMHIP_LVQ_PAIRS_VALU"):
+        reads = {f: len(re.findall(r'getenv\s*\(\s*"%s"\s*\)' % name, t)) for f, t in text.items()}
+        assert sum(reads.values()) == 1, (name, {f: n for f, n in reads.items() if n})
+        assert reads[os.path.join(csrc, "host_lvq.inc")] == 1, name
+    lvq = text[os.path.join(csrc, "host_lvq.inc")]
+    for kernel in ("k_lvq_sample_rho", "k_lvq_pair_adj", "k_lvq_pair_adj_mfma", "k_lvq_components", "k_lvq_batch_apply",
+                   "k_lvq_commit", "k_lvq_cand_meta", "k_lvq_amax", "k_lvq_online_step", "k_prep_rows_bf16"):
+        sites = re.findall(r"hipLaunchKernelGGL\s*\(\s*\(?\s*%s\b" % kernel, lvq)
+        assert len(sites) == 1, (kernel, len(sites))
+
+
 def test_exact_kernels_have_no_fma(built, tmp_path):
     """distance = fp32 sub, mul, add; update = sub, mul, add -- three roundings each
     (reference lvq_pak.c:70-71, 348-349).  A contracted v_fma/v_fmac in those kernels would

@@ -615,6 +615,7 @@ def _lvq_both_engines(eng, E, oracle, kind, codes, clab, x, lab, length, alpha, 
         try:
             cb = E.Codebook(eng, codes, labels=clab)
             ds = E.Dataset(eng, x, labels=lab)
+            plan = E.lvq_plan(cb, ds, kind, length, alpha, **kw)
             before = eng.lvq_stats()
             tal, ti, td = E.lvq_train(cb, ds, kind, length, alpha, **kw)
             after = eng.lvq_stats()
@@ -624,6 +625,12 @@ def _lvq_both_engines(eng, E, oracle, kind, codes, clab, x, lab, length, alpha, 
             os.environ.pop("SOMHIP_LVQ_SERIAL", None)
             os.environ.pop("SOMHIP_LVQ_SYNC", None)
             os.environ.pop("SOMHIP_LVQ_PAIRS_VALU", None)
+        # the plan the run followed: the six modes differ in engine, loop form, forced single component, pair kernel
+        gram = x.shape[1] % 8 == 0 and mode != "batched_pairs_valu"
+        assert (plan["engine"], plan["loop"], plan["single"], plan["pairs"]) == (
+            "online" if mode == "online" else "batched",
+            "careful" if mode in ("batched_sync", "batched_serial") else "nowait",
+            mode == "batched_serial", "mfma" if gram else "direct"), (mode, plan)
         assert np.array_equal(ti, oi), mode
         assert np.array_equal(bits(td), bits(od)), mode
         assert np.array_equal(bits(cb.download()), bits(oc)), mode
@@ -678,6 +685,62 @@ def test_lvq_exact_batches_stop_conditions(eng, E, oracle, kind, shape):
     if shape == "many_codes":
         assert st["batches"] <= length // 20    # the speculation has to pay off somewhere
         assert stc["components"] > 4 * stc["batches"] and stc["batches"] <= st["batches"]   # 20 clusters walk side by side
+
+
+def _lvq_batch_constants():
+    """LVQ_BT, LVQ_DYN_LDS of kernels/lvq_batch.hpp, and lvq_cache_slots as host_lvq.inc states it"""
+    import re
+    from conftest import ROOT
+    csrc = os.path.join(ROOT, "som_lvq_pak_amd", "csrc")
+    hpp = open(os.path.join(csrc, "kernels", "lvq_batch.hpp")).read()
+    bt = int(re.search(r"constexpr int LVQ_BT = (\d+);", hpp).group(1))
+    m = re.search(r"constexpr int LVQ_DYN_LDS = (\d+) \* 1024;", hpp)
+    dyn = int(m.group(1)) * 1024
+    return bt, dyn, lambda d4: min((dyn - 3 * d4 * 16) // (d4 * 16), bt)
+
+
+def test_lvq_plan_thresholds(eng, E):
+    """lvq_plan on both sides of each of its thresholds, nothing launched: the expected side comes from the constants of
+    kernels/lvq_batch.hpp (a row fits the batched engine if its d4 float4s are at most LVQ_BT and at least 8 of them fit
+    LVQ_DYN_LDS beside the walk's three staging rows), the codebook's layout, the data's dimension and mask, and the
+    trace buffer's limit of 2^22 iterations."""
+    bt, dyn, slots = _lvq_batch_constants()
+    assert slots(bt) >= 8                       # the thread count binds before the cache does: d4 = LVQ_BT | LVQ_BT + 4
+    lab = np.array([1, 2, 1, 2], dtype=np.int32)
+
+    def plan(d, mask=False, count=None, trace=True, grid=None, length=100):
+        n = grid[0] * grid[1] if grid else 4
+        rows = np.zeros((n, d), dtype=np.float32)
+        x = np.ones((4, d), dtype=np.float32)
+        m = np.zeros((4, d), dtype=np.uint8)
+        m[0, 0] = 1
+        cb = (E.Codebook(eng, rows, E.TOPOL_HEXA, E.NEIGH_BUBBLE, grid[0], grid[1], labels=np.resize(lab, n)) if grid
+              else E.Codebook(eng, rows, labels=lab))
+        ds = E.Dataset(eng, x, labels=lab, mask=m if mask else None)
+        out = E.lvq_plan(cb, ds, E.LVQ1, length, 0.05, count=count, trace=trace)
+        cb.close()
+        ds.close()
+        return out
+
+    # ---- the row: d4 = 512 | 516
+    for d4 in (bt, bt + 4):
+        fits = d4 <= bt and slots(d4) >= 8
+        p = plan(4 * d4)
+        assert p["engine"] == ("batched" if fits else "online"), (d4, p)
+        assert p["slots"] == slots(d4) and p["dyn_lds"] == (d4 * slots(d4) + 3 * d4) * 16 and p["dyn_lds"] <= dyn, (d4, p)
+    assert plan(4 * bt)["engine"] == "batched" and plan(4 * (bt + 4))["engine"] == "online"
+    # ---- the layout: a labelled map with sides that are multiples of 8 is stored as 8x8 patches
+    assert plan(16, grid=(8, 8))["engine"] == "online" and plan(16, grid=(8, 7))["engine"] == "batched"
+    # ---- the pair kernel: Gram form only for dim % 8 == 0 and unmasked data
+    assert plan(16)["pairs"] == "mfma" and plan(12)["pairs"] == "direct" and plan(17)["pairs"] == "direct"
+    assert plan(16, mask=True)["pairs"] == "masked" and plan(16, mask=True)["masked"] and not plan(16)["masked"]
+    assert plan(12, mask=True)["pairs"] == "masked"
+    # ---- the loop: no waiting only while the winners of the whole call fit the trace buffer
+    big = 1 << 22
+    assert plan(16, count=big, length=big + 1)["loop"] == "nowait"
+    assert plan(16, count=big + 1, length=big + 1)["loop"] == "careful"
+    assert plan(16, count=big + 1, length=big + 1, trace=False)["loop"] == "nowait"
+    assert plan(16)["knn"] == 1 and not plan(16)["single"]
 
 
 # --------------------------------------------------------------------------- error behaviour
