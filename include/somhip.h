@@ -388,6 +388,25 @@ int  somhip_comm_allreduce_sum_u32(somhip_comm *c, uint32_t *dev_words, int64_t 
 int  somhip_comm_allgather(somhip_comm *c, const void *dev_send, void *dev_recv, int64_t bytes_per_rank);
 void somhip_comm_destroy(somhip_comm *c);
 
+/* ---- Sammon mapping of a codebook (SOM_PAK sammon.c) -------------------------------
+ * The codebook is a whole one (no shard).  Mirrors carry no masks: a host whose codebook has masked components refuses
+ * before it gets here (the tool and the reference differ there: vector_dist_euc would skip them).
+ *
+ * somhip_sammon_zero_pairs: the pairs of rows i < j whose distance dd(i, j) (vector_dist_euc, lvq_pak.c:291-316) is
+ * 0.0 -- what remove_identicals (sammon.c:84-128) asks.  That is the computed distance, not equality of the rows: the
+ * squares of small differences underflow.  pairs (may be NULL) has room for `cap` pairs {i, j}; *n_pairs is the number
+ * found, also when it is larger than cap (the first cap pairs in (i, j) order are then not guaranteed: call again
+ * with room for all).  The pairs returned are sorted by (i, j).
+ *
+ * somhip_sammon: rlen iterations of sammon.c:187-225 from the caller's initial table x[n_rows], y[n_rows] (in and
+ * out), bit for bit.  mapping_error: NULL, or [rlen] for the error after every iteration (sammon.c:227-240); that one
+ * number is summed in double by a tree where the reference adds in fp32 in sequence, so it is close, not bit-equal.
+ * Refused: fewer than 2 rows (the reference writes NaNs), a shard, and a zero distance left in the codebook (the
+ * reference would divide by it) -- remove those rows first.  The distance table is a full n_rows x n_rows fp32 matrix
+ * in device memory; if it cannot be allocated the call fails with a message that says how large it is. */
+int  somhip_sammon_zero_pairs(somhip_codebook *cb, uint32_t *pairs, int64_t cap, int64_t *n_pairs);
+int  somhip_sammon(somhip_codebook *cb, int64_t rlen, float *x, float *y, double *mapping_error);
+
 /* device scratch helpers for hosts without their own allocator */
 int  somhip_device_alloc(somhip_engine *e, int64_t bytes, void **dev_ptr);
 int  somhip_device_free(somhip_engine *e, void *dev_ptr);

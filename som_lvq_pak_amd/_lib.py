@@ -14,6 +14,7 @@ c_i32_p = C.POINTER(C.c_int32)
 c_i16_p = C.POINTER(C.c_int16)
 c_u8_p = C.POINTER(C.c_uint8)
 c_u64_p = C.POINTER(C.c_uint64)
+c_u32_p = C.POINTER(C.c_uint32)
 c_i64_p = C.POINTER(C.c_int64)
 c_double_p = C.POINTER(C.c_double)
 
@@ -100,6 +101,8 @@ SIGNATURES = {
     "somhip_comm_destroy": (None, [C.c_void_p]),
     "somhip_som_batch_update": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(SomParams), C.c_int64,
                                           C.c_int64, C.c_int64, C.c_void_p]),
+    "somhip_sammon_zero_pairs": (C.c_int, [C.c_void_p, c_u32_p, C.c_int64, c_i64_p]),
+    "somhip_sammon": (C.c_int, [C.c_void_p, C.c_int64, c_float_p, c_float_p, c_double_p]),
     "somhip_device_alloc": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]),
     "somhip_device_free": (C.c_int, [C.c_void_p, C.c_void_p]),
     "somhip_copy_to_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),

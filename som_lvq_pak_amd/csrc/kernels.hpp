@@ -33,3 +33,4 @@
 #include "kernels/lvq.hpp"
 #include "kernels/lvq_batch.hpp"
 #include "kernels/qerror2_lininit.hpp"
+#include "kernels/sammon.hpp"

@@ -84,13 +84,18 @@ enum KernelId {
   KID_SOM_UPDATE_GEMM,
   KID_DIST_L2,
   KID_L2_SELECT,
+  KID_SAMMON_DIST,
+  KID_SAMMON_SWEEP,
+  KID_SAMMON_CENTRE,
+  KID_SAMMON_ERROR,
   KID_COUNT
 };
 static const char *kKernelNames[KID_COUNT] = {
     "k_scan_exact", "k_som_update_run", "k_som_online_step", "k_lvq_online_step",
     "k_pack_samples", "k_merge_topk", "k_scan_masked", "k_layout", "k_decode_winners",
     "k_dist_mfma", "k_rerank", "k_norms_tau", "k_som_members",
-    "k_rerank_select", "k_rerank_pairs", "k_dist_mfma_bf16", "k_lvq_batch_apply", "k_som_update_bubble_s", "k_lvq_components", "k_som_update_gemm", "k_dist_l2", "k_l2_select"};
+    "k_rerank_select", "k_rerank_pairs", "k_dist_mfma_bf16", "k_lvq_batch_apply", "k_som_update_bubble_s", "k_lvq_components", "k_som_update_gemm", "k_dist_l2", "k_l2_select",
+    "k_sammon_dist", "k_sammon_sweep", "k_sammon_centre", "k_sammon_error"};
 extern "C" int somhip_kernel_count(void) { return KID_COUNT; }
 extern "C" const char *somhip_kernel_name(int i) { return (i >= 0 && i < KID_COUNT) ? kKernelNames[i] : ""; }
 
@@ -716,3 +721,4 @@ extern "C" void somhip_dataset_destroy(somhip_dataset *ds) try {
 #include "host_som.inc"
 #include "host_lvq.inc"
 #include "host_comm.inc"
+#include "host_sammon.inc"

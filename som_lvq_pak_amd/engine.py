@@ -433,3 +433,31 @@ def qerror2_sum(cb, ds, radius, first=0, count=None):
         if ret[i]:
             q = np.float32(q + out[i])
     return q
+
+
+def sammon_zero_pairs(cb):
+    """The pairs of rows (i, j), i < j, at reference distance 0.0 (somhip_sammon_zero_pairs): int64 [n, 2], sorted --
+    what sammon's remove_identicals (sammon.c:84-128) asks.  Distance 0 is not row equality: small squares underflow."""
+    n = C.c_int64(0)
+    cap = 16 * cb.n
+    pairs = np.empty((cap, 2), dtype=np.uint32)
+    check(cb.e.lib.somhip_sammon_zero_pairs(cb.h, _p(pairs, _lib.c_u32_p), cap, C.byref(n)))
+    if n.value > cap:                      # many identical rows: once more with room for all
+        cap = n.value
+        pairs = np.empty((cap, 2), dtype=np.uint32)
+        check(cb.e.lib.somhip_sammon_zero_pairs(cb.h, _p(pairs, _lib.c_u32_p), cap, C.byref(n)))
+    return pairs[:n.value].astype(np.int64)
+
+
+def sammon(cb, x0, y0, rlen, want_error=False):
+    """rlen iterations of SOM_PAK's Sammon mapping (sammon.c:187-225) of the codebook's rows from the initial table
+    (x0, y0), bit for bit: (x, y), and with want_error the mapping error after every iteration (float64 [rlen]; summed
+    by a tree, so close to the reference's fp32 running sum, not bit-equal).  Raises on a codebook with fewer than 2
+    rows or with a pair of rows at distance 0 (sammon_zero_pairs lists them)."""
+    x = np.ascontiguousarray(x0, dtype=np.float32).copy()
+    y = np.ascontiguousarray(y0, dtype=np.float32).copy()
+    if x.shape != (cb.n,) or y.shape != (cb.n,):
+        raise ValueError("sammon: the initial table must have one x and one y per row (%d)" % cb.n)
+    err = np.zeros(rlen, dtype=np.float64) if want_error else None
+    check(cb.e.lib.somhip_sammon(cb.h, rlen, _p(x, _lib.c_float_p), _p(y, _lib.c_float_p), _p(err, _lib.c_double_p)))
+    return (x, y, err) if want_error else (x, y)
