@@ -407,6 +407,19 @@ void somhip_comm_destroy(somhip_comm *c);
 int  somhip_sammon_zero_pairs(somhip_codebook *cb, uint32_t *pairs, int64_t cap, int64_t *n_pairs);
 int  somhip_sammon(somhip_codebook *cb, int64_t rlen, float *x, float *y, double *mapping_error);
 
+/* ---- within-class nearest neighbours of a data set (LVQ_PAK mindist / stddev / balance) ----
+ * The inner loop of med_distances / min_distances (lvq_rout.c:280-491) over a data set that has labels
+ * (somhip_dataset_create with labels, or somhip_dataset_generate with centres: the mixture ids):
+ *   min_sq[r] = the smallest squared distance from row r to a LATER row of the same label -- the fp32 sum of
+ *               vector_dist_euc (lvq_pak.c:291-316) before its root, bit for bit; a component masked in either row
+ *               is skipped.  The distance itself is (float) sqrt((double) min_sq[r]): the root is monotone.
+ *               +inf where no later row of the label is at a finite distance (the reference keeps FLT_MAX there)
+ *   state[r]  = 0 no later row of that label, 1 min_sq[r] valid,
+ *               2 some later row of the label shares no unmasked component with row r (vector_dist_euc returns -1
+ *                 there, and -1 wins the reference's `dist < dissf`)
+ * Both arrays are host memory, [n_rows].  Exact direct-form arithmetic on the vector ALU; work sum n_c^2 d / 2. */
+int  somhip_class_nearest_later(somhip_dataset *ds, float *min_sq, int32_t *state);
+
 /* device scratch helpers for hosts without their own allocator */
 int  somhip_device_alloc(somhip_engine *e, int64_t bytes, void **dev_ptr);
 int  somhip_device_free(somhip_engine *e, void *dev_ptr);

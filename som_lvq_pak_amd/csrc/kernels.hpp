@@ -34,3 +34,4 @@
 #include "kernels/lvq_batch.hpp"
 #include "kernels/qerror2_lininit.hpp"
 #include "kernels/sammon.hpp"
+#include "kernels/class_nearest.hpp"

@@ -88,6 +88,7 @@ enum KernelId {
   KID_SAMMON_SWEEP,
   KID_SAMMON_CENTRE,
   KID_SAMMON_ERROR,
+  KID_CLASS_NEAREST,
   KID_COUNT
 };
 static const char *kKernelNames[KID_COUNT] = {
@@ -95,7 +96,7 @@ static const char *kKernelNames[KID_COUNT] = {
     "k_pack_samples", "k_merge_topk", "k_scan_masked", "k_layout", "k_decode_winners",
     "k_dist_mfma", "k_rerank", "k_norms_tau", "k_som_members",
     "k_rerank_select", "k_rerank_pairs", "k_dist_mfma_bf16", "k_lvq_batch_apply", "k_som_update_bubble_s", "k_lvq_components", "k_som_update_gemm", "k_dist_l2", "k_l2_select",
-    "k_sammon_dist", "k_sammon_sweep", "k_sammon_centre", "k_sammon_error"};
+    "k_sammon_dist", "k_sammon_sweep", "k_sammon_centre", "k_sammon_error", "k_class_nearest"};
 extern "C" int somhip_kernel_count(void) { return KID_COUNT; }
 extern "C" const char *somhip_kernel_name(int i) { return (i >= 0 && i < KID_COUNT) ? kKernelNames[i] : ""; }
 
@@ -114,7 +115,9 @@ struct OnlineGraphKey {
 // Device scratch of an engine (engine_scratch): one buffer per slot, grown on demand and kept.  The owners of a slot
 // never hold it at the same time; the stages named below hold their slots together.
 enum ScratchSlot {
-  SLOT_STAGE = 0,          // staging of codebook upload / download; the SOM update's group order (k_order_groups)
+  SLOT_STAGE = 0,          // staging of codebook upload / download; the SOM update's group order (k_order_groups);
+                           // the class-ordered row tiles of somhip_class_nearest_later (which also holds SLOT_SAMPLES for the
+                           // mask tiles, SLOT_CALL_A / _B for order and segment ends, SLOT_PARTIAL / SLOT_PAIRS for its results)
   SLOT_SAMPLES,            // the packed sample tiles of a scan: direct scan, or the pre-filter from prepare to level 2
   SLOT_PARTIAL,            // partial top-K lists (top-K scans and re-rank), the LVQ online loop's, the online SOM's rows
   SLOT_CALL_A,             // a host call's own array around the scans it runs: keys, LVQ candidates, column sums
@@ -722,3 +725,4 @@ extern "C" void somhip_dataset_destroy(somhip_dataset *ds) try {
 #include "host_lvq.inc"
 #include "host_comm.inc"
 #include "host_sammon.inc"
+#include "host_class.inc"

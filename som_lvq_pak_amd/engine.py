@@ -435,6 +435,17 @@ def qerror2_sum(cb, ds, radius, first=0, count=None):
     return q
 
 
+def class_nearest_later(ds):
+    """Per row of a labelled data set: (min_sq, state) of somhip_class_nearest_later -- the squared distance (the
+    reference's fp32 sum, bit for bit) to the nearest LATER row of the same label, and 0 = no later row of the label,
+    1 = min_sq valid, 2 = some later row of the label shares no unmasked component with the row (distance -1).
+    The inner loop of med_distances (lvq_rout.c:384-491); the distance is float32(sqrt(float64(min_sq)))."""
+    min_sq = np.empty(ds.n, dtype=np.float32)
+    state = np.empty(ds.n, dtype=np.int32)
+    check(ds.e.lib.somhip_class_nearest_later(ds.h, _p(min_sq, _lib.c_float_p), _p(state, _lib.c_i32_p)))
+    return min_sq, state
+
+
 def sammon_zero_pairs(cb):
     """The pairs of rows (i, j), i < j, at reference distance 0.0 (somhip_sammon_zero_pairs): int64 [n, 2], sorted --
     what sammon's remove_identicals (sammon.c:84-128) asks.  Distance 0 is not row equality: small squares underflow."""

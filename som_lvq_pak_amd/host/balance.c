@@ -1,11 +1,9 @@
 /* balance -- even out the codebook by the medians of the shortest within-class distances
  * (LVQ_PAK balance.c:44-283): classes whose codes sit close together lose one, classes whose
  * codes are far apart gain one (picked from the data like eveninit does), then one OLVQ1 pass
- * over the data redistributes the codes.  The two heavy parts -- the k-NN vote behind the picking
- * and olvq1_training -- run on the MI355X engine; the medians are O(sum n_c^2 d) over the
- * codebook and stay on the host. */
-#include <float.h>
-#include <math.h>
+ * over the data redistributes the codes.  Everything heavy runs on the MI355X engine: the nearest
+ * later code of the same class behind the medians (med_distances, paklib.c, shared with mindist
+ * and stddev), the k-NN vote behind the picking, and olvq1_training. */
 #include <stdlib.h>
 #include <string.h>
 #include "pak.h"
@@ -16,63 +14,6 @@ static const char *usage =
     "balance - balances the number of entries in codebook by shortest distances (MI355X engine)\n"
     "Required:  -cin file  -din file  -cout file\n"
     "Optional:  -knn N (default 5, at most 8)  -rand seed  -selfuncs hip  -v level\n";
-
-/* vector_dist_euc, lvq_pak.c:291-316 */
-static float dist_euc(const struct data_entry *a, const struct data_entry *b, int dim)
-{
-  float diff, difference = 0.0;
-  int masked = 0;
-  for (int i = 0; i < dim; i++) {
-    if ((a->mask && a->mask[i]) || (b->mask && b->mask[i])) masked++;
-    else { diff = a->points[i] - b->points[i]; difference += diff * diff; }
-  }
-  if (masked == dim) return -1;
-  return sqrt(difference);
-}
-
-static int cmp_float(const void *a, const void *b)
-{
-  float x = *(const float *)a, y = *(const float *)b;
-  return x < y ? -1 : x > y ? 1 : 0;
-}
-
-struct mindists { long num_classes; long *cls; long *noe; float *dists; };
-
-/* med_distances, lvq_rout.c:373-491: per class (most frequent first), the median over its entries
- * of the distance to the nearest LATER entry of the same class */
-static struct mindists *med_distances(struct entries *codes)
-{
-  struct mindists *md = calloc(1, sizeof *md);
-  struct hitlist *classes = new_hitlist();
-  int dim = codes->dimension;
-  for (long r = 0; r < codes->num_entries; r++) add_hit(classes, get_entry_label(&codes->rows[r]));
-  long nol = classes->entries;
-  md->num_classes = nol;
-  md->cls = calloc(nol + 1, sizeof(long)); md->noe = calloc(nol + 1, sizeof(long)); md->dists = calloc(nol + 1, sizeof(float));
-  long mnoe = nol ? classes->freq[0] : 0;
-  float *meds = malloc(sizeof(float) * (mnoe + 1));
-  for (long i = 0; i < nol; i++) {
-    md->cls[i] = classes->label[i];
-    md->noe[i] = classes->freq[i];
-    long not = 0;
-    for (long r = 0; r < codes->num_entries; r++) {
-      if (get_entry_label(&codes->rows[r]) != md->cls[i]) continue;
-      float dissf = FLT_MAX;
-      int fou = 0;
-      for (long s = r + 1; s < codes->num_entries; s++)
-        if (get_entry_label(&codes->rows[s]) == md->cls[i]) {
-          fou = 1;
-          float dist = dist_euc(&codes->rows[s], &codes->rows[r], dim);
-          if (dist < dissf) dissf = dist;
-        }
-      if (fou) meds[not++] = dissf;
-    }
-    if (not > 0) { qsort(meds, not, sizeof(float), cmp_float); md->dists[i] = meds[not / 2]; }
-  }
-  free(meds); free_hitlist(classes);
-  return md;
-}
-static void free_mindists(struct mindists *md) { if (md) { free(md->cls); free(md->noe); free(md->dists); free(md); } }
 
 /* a + b as one new block (copies) */
 static struct entries *join_entries(struct entries *a, const long *arows, long na, struct entries *b,
@@ -123,6 +64,7 @@ int main(int argc, char **argv)
   /* balance_codes, balance.c:44-226 */
   ifverbose(2) fprintf(stderr, "Medians of the shortest distances are computed\n");
   struct mindists *md = med_distances(codes);
+  if (!md) exit(1);
   long nol = md->num_classes;
   long *noe = md->noe, *cls = md->cls;
   float *dists = md->dists;
@@ -201,6 +143,7 @@ int main(int argc, char **argv)
   ifverbose(2) fprintf(stderr, "Medians of the shortest distances are computed\n");
   free_mindists(md);
   md = med_distances(red);
+  if (!md) exit(1);
   verbose_level = 1;                                   /* `if (verbose(1) > 0)` at balance.c:214 sets the level */
   for (long i = 0; i < md->num_classes; i++)
     fprintf(stdout, "In class %9s %3d units, min dist.: %.3f\n", find_conv_to_lab((int)md->cls[i]), (int)md->noe[i],

@@ -132,6 +132,7 @@ uint64_t pak_splitmix64(uint64_t x);
 float pak_gen_z(uint64_t seed, uint64_t counter);
 void pak_gen_row(uint64_t seed, int k_centres, int dim, long row, float *out, int *centre);
 int pak_parse_gen(const char *spec, long *n, int *dim, int *k, uint64_t *seed, int *labels);
+int pak_gen_unlabelled(const char *name);          /* 1: a `gen:` source without labels=1 */
 void close_entries(struct entries *);
 void clear_entry_labels(struct entries *e, long row);
 void add_entry_label(struct entries *e, long row, int label);
@@ -166,6 +167,11 @@ unsigned char *knn_correct_all(struct entries *data, int knn);
 struct entries *pick_rows(struct entries *src, const long *rows, long n);
 struct entries *lininit_codes(struct entries *data, int topol, int neigh, int xdim, int ydim);
 struct entries *randinit_codes(struct entries *data, int topol, int neigh, int xdim, int ydim);
+/* ---- within-class distance statistics (balance, mindist, stddev; lvq_rout.c:384-491, 918-1004) ---- */
+struct mindists { long num_classes; long *cls; long *noe; float *dists; float *devs; };   /* devs: NULL until deviations() */
+struct mindists *med_distances(struct entries *codes);          /* the nearest-neighbour search runs on the engine */
+int deviations(struct entries *data, struct mindists *md);      /* 0, or 1 after naming a label of data md has no class for */
+void free_mindists(struct mindists *md);
 /* ---- what every tool does before the engine is involved ---- */
 struct pak_inputs { struct entries *data, *codes; };
 /* opens -din then -cin with the reference's messages; fmt strings take the file name.  need_map:

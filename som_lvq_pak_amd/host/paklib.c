@@ -419,6 +419,11 @@ int pak_parse_gen(const char *spec, long *n, int *dim, int *k, uint64_t *seed, i
   if (*n <= 0 || *dim <= 0 || *dim > 32767 || *k <= 0) { fprintf(stderr, "gen: needs n=, dim= (and k > 0)\n"); return -1; }
   return 1;
 }
+int pak_gen_unlabelled(const char *name)
+{
+  long n; int dim, k, labels; uint64_t seed;
+  return strncmp(name, "gen:", 4) == 0 && pak_parse_gen(name, &n, &dim, &k, &seed, &labels) > 0 && !labels;
+}
 int pak_gen_virtual_ok = 0;
 
 /* host rows of a virtual source (same stream, same bits as the device's) */
@@ -1714,4 +1719,109 @@ float find_qerror2(struct teach_params *teach)                /* som_rout.c:823-
   if (ds) somhip_dataset_destroy(ds);
   free(q); free(ret);
   return qerror;
+}
+
+/* ------------------------------------------------------------------ within-class distance statistics */
+static int cmp_float(const void *a, const void *b)          /* compar, lvq_rout.c:373-380 */
+{
+  float x = *(const float *)a, y = *(const float *)b;
+  return x < y ? -1 : x > y ? 1 : 0;
+}
+
+void free_mindists(struct mindists *md)
+{
+  if (md) { free(md->cls); free(md->noe); free(md->dists); free(md->devs); free(md); }
+}
+
+/* index of `label` among the classes of md, or -1 */
+static long mindists_class(const struct mindists *md, long label)
+{
+  for (long i = 0; i < md->num_classes; i++) if (md->cls[i] == label) return i;
+  return -1;
+}
+
+/* med_distances, lvq_rout.c:384-491: per class (add_hit's order: most frequent first), the median -- meds[not / 2] of the
+ * sorted values -- over its entries of the distance to the nearest LATER entry of the same class; 0 for a class in which
+ * no entry has a later one.  The nearest-neighbour search is the engine's (somhip_class_nearest_later: the reference's
+ * sums bit for bit); what is left here is one root per entry and the sort.  NULL after a message on failure. */
+struct mindists *med_distances(struct entries *codes)
+{
+  struct mindists *md = calloc(1, sizeof *md);
+  struct hitlist *classes = new_hitlist();
+  const long n = codes->num_entries;
+  for (long r = 0; r < n; r++) add_hit(classes, get_entry_label(&codes->rows[r]));
+  const long nol = classes->entries;
+  md->num_classes = nol;
+  md->cls = calloc(nol + 1, sizeof(long)); md->noe = calloc(nol + 1, sizeof(long)); md->dists = calloc(nol + 1, sizeof(float));
+  for (long i = 0; i < nol; i++) { md->cls[i] = classes->label[i]; md->noe[i] = classes->freq[i]; }
+  free_hitlist(classes);
+  if (n == 0) return md;
+
+  float *min_sq = malloc(sizeof(float) * n), *meds = malloc(sizeof(float) * n);
+  int32_t *state = malloc(sizeof(int32_t) * n);
+  somhip_dataset *ds = mirror_data(codes, 1);
+  int rc = 1;
+  if (ds) {
+    rc = somhip_class_nearest_later(ds, min_sq, state);
+    if (rc) fprintf(stderr, "%s\n", somhip_last_error());
+    somhip_dataset_destroy(ds);
+  }
+  if (!rc) {
+    long *start = calloc(nol + 1, sizeof(long)), *not = calloc(nol + 1, sizeof(long));
+    for (long i = 1; i < nol; i++) start[i] = start[i - 1] + md->noe[i - 1];
+    for (long r = 0; r < n; r++) {                          /* every class's values, in row order */
+      if (state[r] == 0) continue;                          /* `fou` stayed 0: no later entry of the class */
+      const long i = mindists_class(md, get_entry_label(&codes->rows[r]));
+      float dissf;
+      if (state[r] == 2) dissf = -1;                        /* vector_dist_euc's "nothing to compare" beats every distance */
+      else if (isinf(min_sq[r])) dissf = FLT_MAX;           /* no distance passed `dist < dissf` */
+      else dissf = sqrt(min_sq[r]);
+      meds[start[i] + not[i]++] = dissf;
+    }
+    for (long i = 0; i < nol; i++)
+      if (not[i] > 0) { qsort(meds + start[i], not[i], sizeof(float), cmp_float); md->dists[i] = meds[start[i] + not[i] / 2]; }
+    free(start); free(not);
+  }
+  free(min_sq); free(meds); free(state);
+  if (rc) { free_mindists(md); return NULL; }
+  return md;
+}
+
+/* deviations, lvq_rout.c:929-1004, on the host (one pass of n x dim additions): per class of md the fp32 column sums of
+ * `data` in row order, the row's masked components skipped, divided by md's class count -- the codebook's when md comes
+ * from a codebook, as the reference does it -- then per row devdist (lvq_rout.c:918-927: all components, no mask) added
+ * per class in row order, and sqrt(devs / noe).  The reference indexes past its arrays for a label md has no class for;
+ * here that is refused: returns 1 after a message that names the label. */
+int deviations(struct entries *data, struct mindists *md)
+{
+  const int dim = data->dimension;
+  const long nol = md->num_classes;
+  free(md->devs);
+  md->devs = calloc(nol + 1, sizeof(float));
+  float *avers = calloc((size_t)(nol + 1) * dim, sizeof(float));
+  long *cls_of = malloc(sizeof(long) * (data->num_entries + 1));
+  for (long r = 0; r < data->num_entries; r++) {
+    const int label = get_entry_label(&data->rows[r]);
+    if ((cls_of[r] = mindists_class(md, label)) < 0) {
+      const char *name = find_conv_to_lab(label);
+      fprintf(stderr, "deviations: label '%s' of the data (entry %ld) is carried by no codebook entry\n", name ? name : "", r + 1);
+      free(avers); free(cls_of);
+      return 1;
+    }
+    const struct data_entry *e = &data->rows[r];
+    float *a = avers + cls_of[r] * dim;
+    for (int j = 0; j < dim; j++)
+      if (!(e->mask && e->mask[j])) a[j] += e->points[j];
+  }
+  for (long i = 0; i < nol; i++)
+    for (int j = 0; j < dim; j++) avers[i * dim + j] /= md->noe[i];
+  for (long r = 0; r < data->num_entries; r++) {
+    const float *v1 = data->rows[r].points, *v2 = avers + cls_of[r] * dim;
+    float d = 0.0;
+    for (int j = 0; j < dim; j++) { float diff = v1[j] - v2[j]; d += diff * diff; }
+    md->devs[cls_of[r]] += d;
+  }
+  for (long i = 0; i < nol; i++) md->devs[i] = sqrt(md->devs[i] / md->noe[i]);
+  free(avers); free(cls_of);
+  return 0;
 }
