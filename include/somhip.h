@@ -92,6 +92,15 @@ int  somhip_scan_stats(somhip_engine *e, uint64_t out[8]);
 int  somhip_debug_prefilter(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count,
                             float *wmin, float *tau, int64_t *bpad);
 
+/* diagnostics (tests): run only the preparation and level 1 of the two-level pre-filter (bf16 scan mode) on data rows
+ * [first, first+count), by the persistent ring kernel (ring = 1) or by the wide-tile kernel followed by the pass over
+ * the group minima (ring = 0), and return wmin[ngroups][*bpad] (level 1's group minima of s~ = ||c||^2 - 2<c_hi,x_hi>)
+ * and gmin1[*bpad] (per sample the smallest of them, as an order-preserving uint32).  *bpad = count rounded up to 32.
+ * Refuses shapes that one of the two kernels does not take: rows that are not whole 64-dim steps, fewer than 225
+ * samples, more than 65535. */
+int  somhip_debug_level1(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count, int ring,
+                         float *wmin, uint32_t *gmin1, int64_t *bpad);
+
 /* diagnostics (tests): the route somhip_batch_winner_keys / somhip_batch_topk_keys / somhip_find_winners would take
  * for `count` samples and `want` (1, or the top-k width 2/4/8); host arithmetic only, no GPU work.  (somhip_find_winners
  * searches its run in pieces of at most 4096 samples: ask with the length of a piece.)

@@ -50,6 +50,7 @@ SIGNATURES = {
     "somhip_centered_products": (C.c_int, [C.c_void_p, c_float_p, c_float_p]),
     "somhip_qerror2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_int64, C.c_int64, c_float_p, c_i32_p]),
     "somhip_debug_prefilter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, c_float_p, c_float_p, c_i64_p]),
+    "somhip_debug_level1": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, c_float_p, c_u32_p, c_i64_p]),
     "somhip_debug_scan_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, c_i32_p]),
     "somhip_debug_update_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(SomParams), C.c_int64, C.c_int64, C.c_int64,
                                            c_i32_p]),

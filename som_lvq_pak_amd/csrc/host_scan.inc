@@ -71,6 +71,7 @@ struct ScanPlan {
   ScanRoute route;
   int want, kth;       // kth: level 1's window above the smallest group minimum (1) or the LVQ_K0-th (k_group_kth)
   bool bf16, l1_ring;  // split-bf16 GEMMs (else fp32 MFMA); level 1 by the persistent ring kernel
+  bool l1_wide;        // level 1 on 256 x 256 tiles (the ring kernel, k_dist_mfma_bf16_l1w16), else 128 x 256
   int64_t nsb, bpad;   // 32-sample tiles of the run, and the run padded to them
   int d8;              // 8-dim bf16 K-steps of a row
   bool by_group;       // top-K behind a pre-filter: exact re-rank filed by row group (k_topk_pairs_bygroup), else by pair
@@ -79,7 +80,7 @@ struct ScanPlan {
 };
 static ScanPlan scan_plan(const somhip_codebook *cb, const somhip_dataset *ds, int64_t count, int want) {
   const int64_t nsb = (count + SCAN_S - 1) / SCAN_S;
-  ScanPlan p = {ROUTE_DIRECT, want, 1, cb->e->scan_mode == SOMHIP_SCAN_MFMA_BF16, false, nsb, nsb * SCAN_S, (cb->v.d4 + 1) / 2};
+  ScanPlan p = {ROUTE_DIRECT, want, 1, cb->e->scan_mode == SOMHIP_SCAN_MFMA_BF16, false, false, nsb, nsb * SCAN_S, (cb->v.d4 + 1) / 2};
   const bool run_ok = count >= MFMA_MIN_SAMPLES && count <= (int64_t)PAIR_MAX_COLS * 32;   // longer runs: the direct scan
   bool prefilter = cb->e->scan_mode != SOMHIP_SCAN_DIRECT;
   if (want == 1) prefilter = prefilter && run_ok && cb->v.n >= 64;
@@ -105,6 +106,7 @@ static ScanPlan scan_plan(const somhip_codebook *cb, const somhip_dataset *ds, i
   // least one 256 x 256 tile per CU)
   const int64_t l1_tiles = ((nsb + 7) / 8) * ((cb->v.ngroups + 3) / 4);
   p.l1_ring = p.route == ROUTE_TWO_LEVEL && (cb->v.ngroups >= 512 || l1_tiles >= 256) && (p.d8 % 8) == 0;
+  p.l1_wide = cb->v.ngroups >= 512 || p.l1_ring;        // 256 x 256 tile: a third less L2 -> LDS traffic per MFMA
   // the re-rank behind a top-K pre-filter filed by row group when rows are whole float4s (64 KiB of LDS for the samples'
   // rows; a workgroup per group needs many groups to fill the chip)
   // (ngroups >= 512: on configs[2]'s 157 groups the by-group pass is faster than the pairs -- 100 against 117 us -- but the
@@ -224,7 +226,7 @@ static int pf_level1(somhip_codebook *cb, int64_t count, const ScanPlan &p, cons
   const bool l1_ring_gmin = p.l1_ring && p.kth != LVQ_K0;
   {
     LaunchTimer t(e, KID_DIST_MFMA_BF16);
-    if (ng >= 512 || p.l1_ring) {        // 256 x 256 tile: a third less L2 -> LDS traffic per MFMA
+    if (p.l1_wide) {
       dim3 gridw((unsigned)((nsb + 7) / 8), (unsigned)((ng + 3) / 4));
       if (p.l1_ring) {
         // persistent form over an LDS ring (kernels/prefilter_l1_ring.hpp): one workgroup per CU, a multiple of 8 of them
@@ -532,6 +534,34 @@ extern "C" int somhip_debug_prefilter(somhip_codebook *cb, somhip_dataset *ds, i
   if (bpad) *bpad = p.bpad;
   return 0;
 } ABI_CATCH(somhip_debug_prefilter)
+// prepare + level 1 alone, by the kernel the caller names: the ring kernel and the wide-tile kernel behind k_group_min
+// are two witnesses of the same group minima
+extern "C" int somhip_debug_level1(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count, int ring,
+                                   float *wmin, uint32_t *gmin1, int64_t *bpad) try {
+  CHK(check_pair(cb, ds, "somhip_debug_level1"));
+  if (!wmin || !gmin1) return fail("somhip_debug_level1: null output");
+  if (count <= 0 || first < 0 || first + count > ds->n) return fail("somhip_debug_level1: rows [%lld, +%lld) of %lld", (long long)first, (long long)count, (long long)ds->n);
+  somhip_engine *e = cb->e;
+  ScanPlan p = scan_plan(cb, ds, count, 1);
+  if (!p.bf16 || p.route == ROUTE_MASKED) return fail("somhip_debug_level1: no bf16 level 1 in this mode");
+  if ((p.d8 % 8) != 0 || p.nsb < 8 || p.bpad > 65535)
+    return fail("somhip_debug_level1: %d k-steps, %lld sample tiles: neither level-1 kernel takes this shape", p.d8, (long long)p.nsb);
+  p.route = ROUTE_TWO_LEVEL;
+  p.kth = 1;
+  p.l1_ring = ring != 0;
+  p.l1_wide = true;
+  HIPCHK(hipSetDevice(e->device));
+  e->xc_phase = XC_NONE;
+  PrefilterBufs b;
+  CHK(bind_prefilter(cb, p, false, &b));
+  CHK(pf_prepare(cb, ds, first, count, p, b, nullptr, false));
+  CHK(pf_level1(cb, count, p, b, nullptr));
+  HIPCHK(hipMemcpyAsync(wmin, b.wmin, sizeof(float) * (size_t)cb->v.ngroups * p.bpad, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipMemcpyAsync(gmin1, b.gmin1, sizeof(uint32_t) * (size_t)p.bpad, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  if (bpad) *bpad = p.bpad;
+  return 0;
+} ABI_CATCH(somhip_debug_level1)
 extern "C" int somhip_debug_scan_plan(somhip_codebook *cb, somhip_dataset *ds, int64_t count, int want, int32_t *out) try {
   CHK(check_pair(cb, ds, "somhip_debug_scan_plan"));
   if (!out) return fail("somhip_debug_scan_plan: null output");
