@@ -264,6 +264,25 @@ int  somhip_lvq_train(somhip_codebook *cb, somhip_dataset *ds, const somhip_lvq_
  * sample, out[6] = rows the walk's cache holds, out[7] = its dynamic LDS bytes */
 int  somhip_debug_lvq_plan(somhip_codebook *cb, somhip_dataset *ds, const somhip_lvq_params *p, int want_trace,
                            int32_t out[8]);
+/* diagnostics (tests): the front and the relation of ONE batch of the exact batched engine -- the top-8 scan, the
+ * candidates' labels / rates, OLVQ1's rate bound, rho, relation (*) over all pairs, its components -- made exactly as
+ * somhip_lvq_train makes them for the `count` (1..1024) iterations from p->start_iter on data rows data_first,
+ * data_first + 1, ... (mod n), under the plan of the current environment (SOMHIP_LVQ_PAIRS_VALU and SOMHIP_LVQ_SERIAL
+ * act as in training; p->count and p->data_first are not read).  Nothing is walked, trained or committed.  Host arrays:
+ * keys [count][8] the candidate keys (all-ones: no entry), rho [count], xnorm [count] (the fp32 ||x_j||^2 the Gram form
+ * uses), *amax the bound on |rate| used (< 0: unknown), adj [count][32] the adjacency bit rows (bit i % 32 of word i / 32
+ * of row j: samples j and i are related; words from ceil(count / 32) on belong to no pair and are returned 0), *ncomp,
+ * start [count + 1] (entries after start[ncomp]: -1) and comp_samples [count]: component c owns
+ * comp_samples[start[c] .. start[c + 1]).  Under a one-component plan rho, xnorm and adj are not made and come back 0.
+ * OLVQ1 takes its rates from somhip_lvq_rates_upload.  Refused with a message, before anything is launched: count outside
+ * 1..1024, a plan that is not the batched engine's, a codebook or data set without labels, OLVQ1 without rates. */
+int  somhip_debug_lvq_relation(somhip_codebook *cb, somhip_dataset *ds, const somhip_lvq_params *p, int64_t data_first,
+                               int64_t count, uint64_t *keys, float *rho, float *xnorm, float *amax, uint32_t *adj,
+                               int32_t *ncomp, int32_t *start, int32_t *comp_samples);
+/* ... and the components stage alone on adjacency rows adj [count][32] the caller made (single != 0: one component, the
+ * rows unread); ncomp, start [count + 1], comp_samples [count] as above */
+int  somhip_debug_lvq_components(somhip_engine *e, const uint32_t *adj, int64_t count, int single, int32_t *ncomp,
+                                 int32_t *start, int32_t *comp_samples);
 /* out[0] = codebook rescans (batches) done by somhip_lvq_train so far, out[1] = samples,
  * out[2] / out[3] = batches cut short because a sample's candidate list was exhausted /
  * the on-chip row cache was full, out[4..7] = 100 MHz ticks the in-order kernel spent in

@@ -185,34 +185,41 @@ static int lvq_rate_bound(somhip_engine *e, const uint64_t *d_keys, int64_t coun
   return 0;
 }
 
-// relation: rho_j of relation (*) for every sample (masked data: the sample's norm over its own components), the
-// relation over all pairs of the batch (the plan's kernel), its connected components
-static int lvq_relation(somhip_engine *e, somhip_dataset *ds, const LvqPlan &pl, const LvqBatchBufs &b, const LvqBatch &bt) {
-  LaunchTimer t(e, KID_LVQ_COMPONENTS);
-  if (!pl.single) {
-    const uint8_t *mask = (const uint8_t *)ds->d_mask;
-    const unsigned nt = (unsigned)((bt.c + 63) / 64);
-    (void)with_value<1, 0>(pl.masked, [&](auto m) {       // (a bool: always found)
-      hipLaunchKernelGGL(k_lvq_sample_rho<decltype(m)::value != 0>, dim3((unsigned)((bt.c + 3) / 4)), dim3(256), 0, e->stream,
-                         ds->d_rows, ds->n, ds->d, bt.row0, bt.c, bt.cand, bt.amax, bt.amax_dev, b.rho, b.xnorm, mask);
+// pairs: rho_j of relation (*) for every sample (masked data: the sample's norm over its own components), then the
+// relation over all pairs of the batch by the plan's kernel
+static int lvq_pairs(somhip_engine *e, somhip_dataset *ds, const LvqPlan &pl, const LvqBatchBufs &b, const LvqBatch &bt) {
+  const uint8_t *mask = (const uint8_t *)ds->d_mask;
+  const unsigned nt = (unsigned)((bt.c + 63) / 64);
+  (void)with_value<1, 0>(pl.masked, [&](auto m) {       // (a bool: always found)
+    hipLaunchKernelGGL(k_lvq_sample_rho<decltype(m)::value != 0>, dim3((unsigned)((bt.c + 3) / 4)), dim3(256), 0, e->stream,
+                       ds->d_rows, ds->n, ds->d, bt.row0, bt.c, bt.cand, bt.amax, bt.amax_dev, b.rho, b.xnorm, mask);
+    return 0;
+  });
+  HIPCHK(hipGetLastError());
+  if (pl.pairs == LVQ_PAIRS_MFMA)
+    hipLaunchKernelGGL(k_lvq_pair_adj_mfma, dim3(nt, nt), dim3(256), 0, e->stream, ds->d_rows, ds->n, ds->d, bt.row0, bt.c,
+                       (const float *)b.rho, (const float *)b.xnorm, b.adj);
+  else
+    (void)with_value<1, 0>(pl.masked, [&](auto m) {
+      hipLaunchKernelGGL(k_lvq_pair_adj<decltype(m)::value != 0>, dim3(nt, nt), dim3(256), 0, e->stream, ds->d_rows, ds->n,
+                         ds->d, bt.row0, bt.c, (const float *)b.rho, b.adj, mask);
       return 0;
     });
-    HIPCHK(hipGetLastError());
-    if (pl.pairs == LVQ_PAIRS_MFMA)
-      hipLaunchKernelGGL(k_lvq_pair_adj_mfma, dim3(nt, nt), dim3(256), 0, e->stream, ds->d_rows, ds->n, ds->d, bt.row0, bt.c,
-                         (const float *)b.rho, (const float *)b.xnorm, b.adj);
-    else
-      (void)with_value<1, 0>(pl.masked, [&](auto m) {
-        hipLaunchKernelGGL(k_lvq_pair_adj<decltype(m)::value != 0>, dim3(nt, nt), dim3(256), 0, e->stream, ds->d_rows, ds->n,
-                           ds->d, bt.row0, bt.c, (const float *)b.rho, b.adj, mask);
-        return 0;
-      });
-    HIPCHK(hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_lvq_components, dim3(1), dim3(LVQ_BMAX), (size_t)bt.c * LVQ_AW * 4, e->stream, (const uint32_t *)b.adj, bt.c,
-                     pl.single ? 1 : 0, b.comp_samples, b.out);
   HIPCHK(hipGetLastError());
   return 0;
+}
+// components: the connected components of the adjacency rows of c samples (single: one component, the rows unread)
+static int lvq_components(somhip_engine *e, const LvqBatchBufs &b, int c, bool single) {
+  hipLaunchKernelGGL(k_lvq_components, dim3(1), dim3(LVQ_BMAX), (size_t)c * LVQ_AW * 4, e->stream, (const uint32_t *)b.adj, c,
+                     single ? 1 : 0, b.comp_samples, b.out);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+// relation: the pairs stage (unless the plan makes the batch one component) and the components stage
+static int lvq_relation(somhip_engine *e, somhip_dataset *ds, const LvqPlan &pl, const LvqBatchBufs &b, const LvqBatch &bt) {
+  LaunchTimer t(e, KID_LVQ_COMPONENTS);
+  if (!pl.single) CHK(lvq_pairs(e, ds, pl, b, bt));
+  return lvq_components(e, b, bt.c, pl.single);
 }
 
 // walk: one workgroup per component walks its samples < limit in order (k_lvq_batch_apply<true> stages the sample's
@@ -518,6 +525,88 @@ extern "C" int somhip_lvq_train(somhip_codebook *cb, somhip_dataset *ds, const s
   HIPCHK(hipStreamSynchronize(e->stream));
   return 0;
 } ABI_CATCH(somhip_lvq_train)
+
+// diagnostics (include/somhip.h): one batch's front and relation exactly as lvq_train_batched makes them, under the plan
+// of the current environment, through the stage functions above; nothing is walked or committed
+static int lvq_read_components(somhip_engine *e, const LvqBatchBufs &b, int count, int32_t *ncomp, int32_t *start,
+                               int32_t *comp_samples) {
+  std::vector<char> hbuf(sizeof(LvqBatchOut));
+  LvqBatchOut *ho = reinterpret_cast<LvqBatchOut *>(hbuf.data());
+  HIPCHK(hipMemcpyAsync(ho, b.out, sizeof(LvqBatchOut), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipMemcpyAsync(comp_samples, b.comp_samples, sizeof(int32_t) * (size_t)count, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  *ncomp = ho->ncomp;
+  const int nc = std::max(0, std::min(ho->ncomp, count));  // (a wrong count is the caller's finding; read inside the block)
+  for (int k = 0; k <= count; k++) start[k] = k <= nc ? ho->start[k] : -1;
+  return 0;
+}
+extern "C" int somhip_debug_lvq_relation(somhip_codebook *cb, somhip_dataset *ds, const somhip_lvq_params *p, int64_t data_first,
+                                         int64_t count, uint64_t *keys, float *rho, float *xnorm, float *amax, uint32_t *adj,
+                                         int32_t *ncomp, int32_t *start, int32_t *comp_samples) try {
+  CHK(check_pair(cb, ds, "somhip_debug_lvq_relation"));
+  if (!p || !keys || !rho || !xnorm || !amax || !adj || !ncomp || !start || !comp_samples)
+    return fail("somhip_debug_lvq_relation: null argument");
+  if (p->kind < SOMHIP_LVQ1 || p->kind > SOMHIP_LVQ3) return fail("Unknown LVQ type %d", p->kind);
+  if (count < 1 || count > LVQ_BMAX) return fail("somhip_debug_lvq_relation: a batch has 1..%d samples, not %lld", LVQ_BMAX, (long long)count);
+  if (!cb->d_labels) return fail("somhip_debug_lvq_relation: codebook has no labels");
+  if (ds->labels.empty()) return fail("somhip_debug_lvq_relation: data has no labels");
+  if (data_first < 0) return fail("somhip_debug_lvq_relation: data_first %lld < 0", (long long)data_first);
+  if (p->length <= 0 || p->start_iter < 0 || p->start_iter + count > p->length)
+    return fail("somhip_debug_lvq_relation: iterations outside schedule");
+  if (p->kind == SOMHIP_OLVQ1 && !cb->d_talpha) return fail("somhip_debug_lvq_relation: OLVQ1 needs rates (somhip_lvq_rates_upload)");
+  if (cb->v.row_offset != 0 || cb->n_global != cb->v.n) return fail("somhip_debug_lvq_relation: sharded codebook not supported");
+  CHK(lvq_refuse_all_masked(ds, data_first, count, "somhip_debug_lvq_relation"));
+  const LvqPlan pl = lvq_plan(cb, ds, p, false);
+  if (!pl.batched)
+    return fail("somhip_debug_lvq_relation: this plan does not run the batched engine (%d components per row, SOMHIP_LVQ_ONLINE)", cb->v.d);
+  if (pl.knn == 2 && cb->v.n < 2) return fail("somhip_debug_lvq_relation: LVQ2/LVQ3 need at least two code rows");
+  somhip_engine *e = cb->e;
+  HIPCHK(hipSetDevice(e->device));
+  void *dcand;
+  CHK(engine_scratch(e, SLOT_CALL_A, sizeof(uint64_t) * (size_t)LVQ_BMAX * LVQ_K0, &dcand));
+  LvqBatchBufs b;
+  CHK(lvq_batch_bufs(e, cb->v.d4, &b));
+  const int c = (int)count;
+  const int64_t row0 = data_first % ds->n;
+  std::vector<LvqStep> hst((size_t)c);
+  lvq_fill_steps(ds, p, p->start_iter, row0, c, hst.data());
+  float *ta = pl.olvq ? b.cand_ta : (float *)nullptr;
+  CHK(scan_keys_topk<LVQ_K0>(cb, ds, row0, c, (uint64_t *)dcand, pl.knn == 2 ? 1 : 0));
+  CHK(lvq_cand_meta(cb, (const uint64_t *)dcand, c, pl.knn, pl.olvq, b.cand_lab, ta));
+  if (pl.olvq) CHK(lvq_rate_bound(e, (const uint64_t *)dcand, c, ta, p->alpha, b.amax_dev));
+  const LvqBatch bt = {row0, c, nullptr, (const uint64_t *)dcand, b.cand_lab, ta, nullptr, 0,
+                       pl.olvq ? 0.0f : lvq_amax_of(hst.data(), c), pl.olvq ? b.amax_dev : (float *)nullptr, nullptr};
+  CHK(lvq_relation(e, ds, pl, b, bt));
+  HIPCHK(hipMemcpyAsync(keys, dcand, sizeof(uint64_t) * (size_t)c * LVQ_K0, hipMemcpyDeviceToHost, e->stream));
+  *amax = bt.amax;
+  if (pl.olvq) HIPCHK(hipMemcpyAsync(amax, b.amax_dev, sizeof(float), hipMemcpyDeviceToHost, e->stream));
+  if (pl.single) {                                        // no pairs stage: nothing of it to report
+    std::fill(rho, rho + c, 0.0f);
+    std::fill(xnorm, xnorm + c, 0.0f);
+    std::fill(adj, adj + (size_t)c * LVQ_AW, 0u);
+  } else {
+    HIPCHK(hipMemcpyAsync(rho, b.rho, sizeof(float) * (size_t)c, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(xnorm, b.xnorm, sizeof(float) * (size_t)c, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(adj, b.adj, sizeof(uint32_t) * (size_t)c * LVQ_AW, hipMemcpyDeviceToHost, e->stream));
+  }
+  CHK(lvq_read_components(e, b, c, ncomp, start, comp_samples));
+  // words past the batch's last sample belong to no pair: no kernel writes or reads them
+  if (!pl.single)
+    for (int j = 0; j < c; j++) std::fill(adj + (size_t)j * LVQ_AW + (c + 31) / 32, adj + (size_t)(j + 1) * LVQ_AW, 0u);
+  return 0;
+} ABI_CATCH(somhip_debug_lvq_relation)
+// the components stage alone on adjacency rows the caller made
+extern "C" int somhip_debug_lvq_components(somhip_engine *e, const uint32_t *adj, int64_t count, int single, int32_t *ncomp,
+                                           int32_t *start, int32_t *comp_samples) try {
+  if (!e || !adj || !ncomp || !start || !comp_samples) return fail("somhip_debug_lvq_components: null argument");
+  if (count < 1 || count > LVQ_BMAX) return fail("somhip_debug_lvq_components: a batch has 1..%d samples, not %lld", LVQ_BMAX, (long long)count);
+  HIPCHK(hipSetDevice(e->device));
+  LvqBatchBufs b;
+  CHK(lvq_batch_bufs(e, 1, &b));
+  HIPCHK(hipMemcpyAsync(b.adj, adj, sizeof(uint32_t) * (size_t)count * LVQ_AW, hipMemcpyHostToDevice, e->stream));
+  CHK(lvq_components(e, b, (int)count, single != 0));
+  return lvq_read_components(e, b, (int)count, ncomp, start, comp_samples);
+} ABI_CATCH(somhip_debug_lvq_components)
 
 
 // ---------------------------------------------------------------------------------

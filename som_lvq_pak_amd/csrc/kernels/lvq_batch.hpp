@@ -154,6 +154,7 @@ __global__ __launch_bounds__(256) void k_lvq_amax(const uint64_t *__restrict__ c
 // row stores there), so the difference of a pair is a NaN exactly where either side masks, and fmaxf(t * t, 0)
 // makes such a term 0 (maxNum returns the operand that is a number).  An empty intersection gives 0: an edge.
 // A NaN among a sample's UNMASKED values is dropped the same way, which can only shorten the sum, i.e. add edges.
+// <false>: such a NaN makes the sum a NaN, and the test "not (sum > ...)" makes that an edge.
 __device__ __forceinline__ float4 lvq_nan_masked(float4 v, uint32_t m) {      // m: 4 mask bytes, component x lowest
   const float nan = __builtin_nanf("");
   return make_float4((m & 0xFFu) ? nan : v.x, (m & 0xFF00u) ? nan : v.y, (m & 0xFF0000u) ? nan : v.z, (m & 0xFF000000u) ? nan : v.w);
@@ -232,7 +233,7 @@ __global__ __launch_bounds__(256) void k_lvq_pair_adj(const float *__restrict__ 
       bool on = false;
       if (j < count && i < count && j != i) {
         const double lhs = sqrt(static_cast<double>(acc[a][b])) * (1.0 - 1.0 / 4096.0);
-        on = lhs <= static_cast<double>(rho[j]) + static_cast<double>(rho[i]);
+        on = !(lhs > static_cast<double>(rho[j]) + static_cast<double>(rho[i]));   // (a NaN sum separates nothing: an edge)
       }
       sadj[ty * 4 + a][tx * 4 + b] = on ? 1 : 0;
     }
@@ -256,7 +257,8 @@ __global__ __launch_bounds__(256) void k_lvq_pair_adj(const float *__restrict__ 
 // (fp32 products, fp32 accumulation in any order, the two wave-summed norms), so "computed <= (rho_j + rho_i)^2
 // (1 + 2^-10) + 8 (d + 8) u (n_j + n_i)" holds for every pair that satisfies (*).  The inner products are
 // bit-symmetric in (j, i) (same products, same order), hence so is the matrix; every tile of it is computed
-// (no mirror writes).  Needs d % 8 == 0; other shapes, and every masked batch, use k_lvq_pair_adj.
+// (no mirror writes).  The test is written as "not (computed > ...)": where the norms or the products are not finite the
+// pair cannot be shown to be apart and is an edge (tests/test_lvq_relation.py, the huge and NaN cases).  Needs d % 8 == 0; other shapes, and every masked batch, use k_lvq_pair_adj.
 __global__ __launch_bounds__(256) void k_lvq_pair_adj_mfma(const float *__restrict__ rows, int64_t n_rows, int d,
                                                            int64_t first, int count, const float *__restrict__ rho,
                                                            const float *__restrict__ xnorm, uint32_t *__restrict__ adj) {
@@ -305,7 +307,10 @@ __global__ __launch_bounds__(256) void k_lvq_pair_adj_mfma(const float *__restri
       const double nj = static_cast<double>(xnorm[jr]), rj = static_cast<double>(rho[jr]);
       const double d2 = nj + ni - 2.0 * static_cast<double>(acc[v]);
       const double r = rj + ri;
-      on = d2 <= r * r * (1.0 + 1.0 / 1024.0) + slack_unit * (nj + ni);      // (rho = +inf: always)
+      // no edge only where the pair is PROVABLY apart.  Norms that overflow fp32 (components around 1e19: +inf here and
+      // in acc, d2 = inf - inf) or a NaN among the values leave nothing to prove it with: the test fails, an edge
+      // (rho = +inf: always, whatever d2 is)
+      on = !(d2 > r * r * (1.0 + 1.0 / 1024.0) + slack_unit * (nj + ni));
     }
     const unsigned long long bal = __ballot(on);
     const int j0 = tj * 64 + wr * 32 + (v >> 2) * 8 + (v & 3);               // the row of half 0; half 1: + 4
@@ -436,7 +441,8 @@ __global__ __launch_bounds__(LVQ_BMAX) void k_lvq_components(const uint32_t *__r
   }
   __syncthreads();
   if (j == 0) { out->ncomp = nc; out->pad = 0; for (int c = 0; c < 4; c++) out->cycles[c] = 0; }
-  if (j <= nc) out->start[j] = s_start[j];
+  if (j < nc) out->start[j + 1] = s_start[j + 1];         // nc + 1 entries from nc <= LVQ_BMAX threads: 1024 singletons
+  if (j == 0) out->start[0] = 0;                          // have an entry start[1024], which "j <= nc" never wrote
 }
 
 // ---- phase 2: one workgroup walks one component ------------------------------------------------

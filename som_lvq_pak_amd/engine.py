@@ -408,6 +408,54 @@ def lvq_plan(cb, ds, kind, length, alpha, alpha_type=ALPHA_LINEAR, winlen=0.0, e
             "pairs": LVQ_PAIRS[out[3]], "masked": bool(out[4]), "knn": out[5], "slots": out[6], "dyn_lds": out[7]}
 
 
+LVQ_BMAX, LVQ_AW = 1024, 32     # samples per batch of the exact batched engine; adjacency words per sample
+
+
+def lvq_relation(cb, ds, kind, length, alpha, alpha_type=ALPHA_LINEAR, winlen=0.0, epsilon=0.0, start_iter=0, data_first=0,
+                 count=1):
+    """The front and the relation of one batch of the exact batched engine (somhip_debug_lvq_relation): iterations
+    [start_iter, start_iter + count) on data rows data_first, data_first + 1, ... (mod n), made as lvq_train makes them
+    under the current environment; nothing is trained.  A dict of numpy arrays: keys [count, 8] uint64, rho [count],
+    xnorm [count], amax (float32 scalar; < 0: unknown), adj [count, 32] uint32, ncomp, start [ncomp + 1],
+    comp_samples [count].  OLVQ1 reads the rates of lvq_rates_upload."""
+    p = LvqParams(kind, length, alpha, alpha_type, winlen, epsilon, start_iter, count, data_first)
+    n = max(int(count), 0)
+    keys = np.zeros((n, 8), dtype=np.uint64)
+    rho, xnorm = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.float32)
+    amax = np.zeros(1, dtype=np.float32)
+    adj = np.zeros((n, LVQ_AW), dtype=np.uint32)
+    ncomp, start, comp = np.zeros(1, dtype=np.int32), np.zeros(n + 1, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    check(cb.e.lib.somhip_debug_lvq_relation(cb.h, ds.h, C.byref(p), data_first, count, _p(keys, _lib.c_u64_p),
+                                             _p(rho, _lib.c_float_p), _p(xnorm, _lib.c_float_p), _p(amax, _lib.c_float_p),
+                                             _p(adj, _lib.c_u32_p), _p(ncomp, _lib.c_i32_p), _p(start, _lib.c_i32_p),
+                                             _p(comp, _lib.c_i32_p)))
+    nc = int(ncomp[0])
+    return {"keys": keys, "rho": rho, "xnorm": xnorm, "amax": amax[0], "adj": adj, "ncomp": nc,
+            "start": start[:max(0, min(nc, n)) + 1].copy(), "comp_samples": comp}
+
+
+def lvq_components(eng, adj, count, single=False):
+    """k_lvq_components alone on adjacency rows adj [count, 32] uint32 (somhip_debug_lvq_components):
+    (ncomp, start [ncomp + 1], comp_samples [count])."""
+    n = max(int(count), 0)
+    adj = np.ascontiguousarray(adj, dtype=np.uint32)
+    if adj.shape != (n, LVQ_AW):
+        raise ValueError("lvq_components: adj must be [count, %d]" % LVQ_AW)
+    ncomp, start, comp = np.zeros(1, dtype=np.int32), np.zeros(n + 1, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    check(eng.lib.somhip_debug_lvq_components(eng.h, _p(adj, _lib.c_u32_p), count, int(single), _p(ncomp, _lib.c_i32_p),
+                                              _p(start, _lib.c_i32_p), _p(comp, _lib.c_i32_p)))
+    nc = int(ncomp[0])
+    return nc, start[:max(0, min(nc, n)) + 1].copy(), comp
+
+
+def lvq_rates_upload(cb, talpha):
+    """OLVQ1's per-row rates to the device (somhip_lvq_rates_upload)."""
+    ta = np.ascontiguousarray(talpha, dtype=np.float32)
+    if ta.shape != (cb.n,):
+        raise ValueError("lvq_rates_upload: one rate per code row (%d)" % cb.n)
+    check(cb.e.lib.somhip_lvq_rates_upload(cb.h, _p(ta, _lib.c_float_p)))
+
+
 def qerror_sum(diff, ret=None):
     """find_qerror's accumulation (reference som_rout.c:698-715): a float32 running sum of
     double square roots in data order -- O(n) host work on the winners the GPU returned."""
