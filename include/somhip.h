@@ -448,6 +448,19 @@ int  somhip_sammon(somhip_codebook *cb, int64_t rlen, float *x, float *y, double
  * Both arrays are host memory, [n_rows].  Exact direct-form arithmetic on the vector ALU; work sum n_c^2 d / 2. */
 int  somhip_class_nearest_later(somhip_dataset *ds, float *min_sq, int32_t *state);
 
+/* ---- the U-matrix of a map (SOM_PAK umat: map.c calc_umatrix, average_umatrix, median_umatrix) ----
+ * The distances between neighbouring model vectors of a whole hexa or rect map, the medians at the units' own
+ * positions, the scaling to [0, 1] and the optional filters, bit for bit, from the rows as they are on the device now
+ * (after training included); no data set and no host copy of the rows is involved.
+ *   u       host, [uy][ux] floats with ux = 2 xdim - 1, uy = 2 ydim - 1: u[y * ux + x] = the reference's uvalue[x][y]
+ *           after calc_umatrix, then average_umatrix (SOMHIP_UMAT_AVERAGE), then median_umatrix (SOMHIP_UMAT_MEDIAN)
+ *   minmax  NULL, or the smallest and the largest entry before the scaling (map.c:474-485)
+ * Refused before any launch: a codebook that is not a map, a shard (contiguous or interleaved), a side below 2 (the
+ * reference reads outside its arrays there), unknown filter bits; after the reduction: max == min (the reference
+ * divides by zero there). */
+enum { SOMHIP_UMAT_AVERAGE = 1, SOMHIP_UMAT_MEDIAN = 2 };
+int  somhip_umatrix(somhip_codebook *cb, int filters, float *u, double minmax[2]);
+
 /* device scratch helpers for hosts without their own allocator */
 int  somhip_device_alloc(somhip_engine *e, int64_t bytes, void **dev_ptr);
 int  somhip_device_free(somhip_engine *e, void *dev_ptr);

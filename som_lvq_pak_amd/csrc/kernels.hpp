@@ -35,3 +35,4 @@
 #include "kernels/qerror2_lininit.hpp"
 #include "kernels/sammon.hpp"
 #include "kernels/class_nearest.hpp"
+#include "kernels/umat.hpp"

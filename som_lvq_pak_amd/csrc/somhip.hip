@@ -89,6 +89,12 @@ enum KernelId {
   KID_SAMMON_CENTRE,
   KID_SAMMON_ERROR,
   KID_CLASS_NEAREST,
+  KID_UMAT_DIST,
+  KID_UMAT_UNITS,
+  KID_UMAT_MINMAX,
+  KID_UMAT_SCALE,
+  KID_UMAT_AVERAGE,
+  KID_UMAT_MEDIAN,
   KID_COUNT
 };
 static const char *kKernelNames[KID_COUNT] = {
@@ -96,7 +102,8 @@ static const char *kKernelNames[KID_COUNT] = {
     "k_pack_samples", "k_merge_topk", "k_scan_masked", "k_layout", "k_decode_winners",
     "k_dist_mfma", "k_rerank", "k_norms_tau", "k_som_members",
     "k_rerank_select", "k_rerank_pairs", "k_dist_mfma_bf16", "k_lvq_batch_apply", "k_som_update_bubble_s", "k_lvq_components", "k_som_update_gemm", "k_dist_l2", "k_l2_select",
-    "k_sammon_dist", "k_sammon_sweep", "k_sammon_centre", "k_sammon_error", "k_class_nearest"};
+    "k_sammon_dist", "k_sammon_sweep", "k_sammon_centre", "k_sammon_error", "k_class_nearest",
+    "k_umat_dist", "k_umat_units", "k_umat_minmax", "k_umat_scale", "k_umat_average", "k_umat_median"};
 extern "C" int somhip_kernel_count(void) { return KID_COUNT; }
 extern "C" const char *somhip_kernel_name(int i) { return (i >= 0 && i < KID_COUNT) ? kKernelNames[i] : ""; }
 
@@ -120,7 +127,8 @@ enum ScratchSlot {
                            // mask tiles, SLOT_CALL_A / _B for order and segment ends, SLOT_PARTIAL / SLOT_PAIRS for its results)
   SLOT_SAMPLES,            // the packed sample tiles of a scan: direct scan, or the pre-filter from prepare to level 2
   SLOT_PARTIAL,            // partial top-K lists (top-K scans and re-rank), the LVQ online loop's, the online SOM's rows
-  SLOT_CALL_A,             // a host call's own array around the scans it runs: keys, LVQ candidates, column sums
+  SLOT_CALL_A,             // a host call's own array around the scans it runs: keys, LVQ candidates, column sums;
+                           // somhip_umatrix: the matrix (SLOT_CALL_B its out-of-place copy, SLOT_PARTIAL min and max)
   SLOT_CALL_B,             // ... and its second one: step scalars, LvqStep, column counts, products
   SLOT_TAU,                // pre-filter: per-sample window, from prepare to the re-rank
   SLOT_WMIN,               // pre-filter: per (group, sample) minimum, from level 1 / one level to the re-rank
@@ -726,3 +734,4 @@ extern "C" void somhip_dataset_destroy(somhip_dataset *ds) try {
 #include "host_comm.inc"
 #include "host_sammon.inc"
 #include "host_class.inc"
+#include "host_umat.inc"

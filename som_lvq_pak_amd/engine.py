@@ -14,6 +14,7 @@ NEIGH_BUBBLE, NEIGH_GAUSSIAN = 1, 2
 ALPHA_LINEAR, ALPHA_INVERSE_T = 1, 2
 LVQ1, OLVQ1, LVQ2, LVQ3 = 1, 2, 3, 4
 TIE_FIRST, TIE_KNN = 0, 1
+UMAT_AVERAGE, UMAT_MEDIAN = 1, 2
 
 
 def _p(a, typ):
@@ -492,6 +493,18 @@ def class_nearest_later(ds):
     state = np.empty(ds.n, dtype=np.int32)
     check(ds.e.lib.somhip_class_nearest_later(ds.h, _p(min_sq, _lib.c_float_p), _p(state, _lib.c_i32_p)))
     return min_sq, state
+
+
+def umatrix(cb, average=False, median=False):
+    """The U-matrix of a whole hexa / rect map from the rows on the device (somhip_umatrix): (u, (min, max)).
+    u is float32 [2 ydim - 1, 2 xdim - 1], u[y, x] = SOM_PAK's uvalue[x][y] after calc_umatrix (map.c:130-500), then
+    average_umatrix and median_umatrix when asked for, bit for bit; min and max are those of map.c:474-485, before
+    the scaling to [0, 1].  Raises on a codebook that is not a map, on a shard, on a side below 2 and on max == min."""
+    u = np.empty((max(2 * cb.ydim - 1, 1), max(2 * cb.xdim - 1, 1)), dtype=np.float32)
+    mm = np.zeros(2, dtype=np.float64)
+    check(cb.e.lib.somhip_umatrix(cb.h, (UMAT_AVERAGE if average else 0) | (UMAT_MEDIAN if median else 0),
+                                  _p(u, _lib.c_float_p), _p(mm, _lib.c_double_p)))
+    return u, (float(mm[0]), float(mm[1]))
 
 
 def sammon_zero_pairs(cb):
