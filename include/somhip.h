@@ -101,6 +101,35 @@ int  somhip_debug_prefilter(somhip_codebook *cb, somhip_dataset *ds, int64_t fir
 int  somhip_debug_level1(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count, int ring,
                          float *wmin, uint32_t *gmin1, int64_t *bpad);
 
+/* diagnostics (tests): run only the preparation of a nearest-row search (bf16 scan mode, a pre-filter route) on data rows
+ * [first, first+count) and return what it leaves on the device; every output but info may be null.  With d8 = the
+ * 8-dim k-blocks of a row (dims rounded up to 8), ngroups = rows rounded up to 64 over 64, nsb = count rounded up to 32
+ * over 32, bf16 values as uint16:
+ *   chi, clo [ngroups][d8][64][8]   hi and lo pieces of the codebook's rows (row r of group g at [g][kb][r])
+ *   cn [ngroups * 64]               squared row norms, 3.0e38 for padding rows
+ *   rowmajor [ngroups * 64][d]      the row-major copy of the rows, where the search makes one (info[0])
+ *   xhi, xlo [nsb][d8][32][8]       hi and lo pieces of the samples; xlo only where a kernel reads it (info[1])
+ *   xrow [nsb * 32][d8][2][8]       the same pieces sample by sample, hi then lo (two-level route: info[2])
+ *   tau [count], tau1 [count]       the windows of the re-rank and of level 1 (tau1: two-level route)
+ * info[0] = rowmajor was written, info[1] = xlo was written, info[2] = the route has two levels, info[3] = d8. */
+int  somhip_debug_prepared(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count,
+                           uint16_t *chi, uint16_t *clo, float *cn, float *rowmajor, uint16_t *xhi, uint16_t *xlo,
+                           uint16_t *xrow, float *tau, float *tau1, int32_t info[4]);
+
+/* diagnostics (tests): the nearest-row search of data rows [first, first+count) on a pre-filter route, with the pairs of
+ * the exact re-rank selected from level 2's lists (from_lists = 1, two-level route only: what the search itself does
+ * there) or from the whole matrix of group minima (from_lists = 0).  Returns, with *bpad = count rounded up to 32 and
+ * ncols = *bpad / 32: wmin, wmask [ngroups][*bpad] (the pre-filter's group minima and row masks as the selection found
+ * them), gmin [*bpad] (per-sample minimum, order-preserving uint32), tau [count], colcount [4][ncols] (per 32-sample
+ * column: pairs, row groups, rows, largest group count of one sample), *overflow (above ncols * 16384 when a column's
+ * 16384-pair segment was full and the whole run went through the group-granular re-rank), pairs [*npairs][2] ((sample,
+ * row) of every column's segment, one column after another, at most 16384 of a column; an error if more than pairs_cap)
+ * and keys [count] (the search's result). */
+int  somhip_debug_rerank_pairs(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count, int from_lists,
+                               float *wmin, uint64_t *wmask, uint32_t *gmin, float *tau, uint32_t *colcount,
+                               uint32_t *overflow, uint32_t *pairs, int64_t pairs_cap, int64_t *npairs,
+                               uint64_t *keys, int64_t *bpad);
+
 /* diagnostics (tests): the route somhip_batch_winner_keys / somhip_batch_topk_keys / somhip_find_winners would take
  * for `count` samples and `want` (1, or the top-k width 2/4/8); host arithmetic only, no GPU work.  (somhip_find_winners
  * searches its run in pieces of at most 4096 samples: ask with the length of a piece.)

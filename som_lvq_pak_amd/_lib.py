@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("SOMHIP_LIB", os.path.join(HERE, "libsomhip.so"))   # 
 c_float_p = C.POINTER(C.c_float)
 c_i32_p = C.POINTER(C.c_int32)
 c_i16_p = C.POINTER(C.c_int16)
+c_u16_p = C.POINTER(C.c_uint16)
 c_u8_p = C.POINTER(C.c_uint8)
 c_u64_p = C.POINTER(C.c_uint64)
 c_u32_p = C.POINTER(C.c_uint32)
@@ -51,6 +52,10 @@ SIGNATURES = {
     "somhip_qerror2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_int64, C.c_int64, c_float_p, c_i32_p]),
     "somhip_debug_prefilter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, c_float_p, c_float_p, c_i64_p]),
     "somhip_debug_level1": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, c_float_p, c_u32_p, c_i64_p]),
+    "somhip_debug_prepared": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, c_u16_p, c_u16_p, c_float_p, c_float_p,
+                                        c_u16_p, c_u16_p, c_u16_p, c_float_p, c_float_p, c_i32_p]),
+    "somhip_debug_rerank_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, c_float_p, c_u64_p, c_u32_p,
+                                            c_float_p, c_u32_p, c_u32_p, c_u32_p, C.c_int64, c_i64_p, c_u64_p, c_i64_p]),
     "somhip_debug_scan_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, c_i32_p]),
     "somhip_debug_update_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(SomParams), C.c_int64, C.c_int64, C.c_int64,
                                            c_i32_p]),

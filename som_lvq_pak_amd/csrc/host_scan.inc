@@ -130,7 +130,7 @@ static dim3 group_chunks(int64_t ngroups, int64_t bpad, int64_t per, int64_t *ch
 struct PrefilterBufs {
   float *tau, *wmin; uint64_t *wmask;     // per-sample window; per (group, sample) minimum and candidate mask
   void *xt; uint4 *xhi, *xlo, *xrow;      // tiles: fp32 xt[sb][q][32][4] or bf16 hi | lo [sb][kb][32][8]; xrow: sample-major
-  uint32_t *gmin, *gcount, *colcount, *paircount;            // re-rank counters (preset by k_sample_tau)
+  uint32_t *gmin, *gcount, *colcount, *paircount;            // re-rank counters (preset in pf_prepare: rerank_presets)
   float *tau1; uint32_t *gmin1, *l2cnt; uint16_t *l2list;   // two levels: level 1's window and minimum, level 2's lists
   float *xw;                              // shard exchange: delta1, max(delta1, 3 delta3), delta3 per sample
 };
@@ -139,7 +139,10 @@ static int bind_prefilter(somhip_codebook *cb, const ScanPlan &p, bool exchange,
   const int64_t bpad = p.bpad, ng = cb->v.ngroups;
   if (!cb->d_cn) {
     HIPCHK(hipMalloc((void **)&cb->d_cn, sizeof(float) * (size_t)ng * WAVE));
-    HIPCHK(hipMalloc((void **)&cb->d_cnmax, sizeof(unsigned int)));
+    HIPCHK(hipMalloc((void **)&cb->d_cnmax, 2 * sizeof(unsigned int)));      // two words in turn (pf_prepare)
+    HIPCHK(hipMemsetAsync(cb->d_cnmax, 0, 2 * sizeof(unsigned int), e->stream));
+    cb->cnmax_sel = 0;
+    cb->cnmax_clean = true;
   }
   if (p.bf16 && !cb->d_chi) {
     HIPCHK(hipMalloc((void **)&cb->d_chi, sizeof(uint4) * (size_t)ng * p.d8 * WAVE));
@@ -168,7 +171,9 @@ static int bind_prefilter(somhip_codebook *cb, const ScanPlan &p, bool exchange,
   }
   return 0;
 }
-// prepare: the sample tiles, the codebook's norms or bf16 split, the windows and the re-rank's presets (k_sample_tau).
+// prepare: the codebook's norms or bf16 split, the sample tiles, the windows and the re-rank's presets.  The windows need
+// the codebook's largest norm: on the bf16 route the codebook pass runs first and k_pack_samples_bf16 forms the windows
+// and the presets from the rows it packs; on the fp32 route k_sample_tau does, behind k_row_norms.
 // d_keys: the nearest-row keys it presets (nullptr: top-K or bare pre-filter), as INT64_MAX under nonneg_keys (above
 // every real key, and what a signed MIN all-reduce needs -- saves somhip_batch_winner_keys a pass over the keys)
 static int pf_prepare(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count, const ScanPlan &p,
@@ -176,46 +181,70 @@ static int pf_prepare(somhip_codebook *cb, somhip_dataset *ds, int64_t first, in
   somhip_engine *e = cb->e;
   const bool two = p.route == ROUTE_TWO_LEVEL;
   const int d8 = p.d8;
-  {
-    LaunchTimer t(e, KID_PACK_SAMPLES);
-    if (p.bf16)
-      hipLaunchKernelGGL(k_pack_samples_bf16, dim3((unsigned)p.nsb, (unsigned)(d8 >= 32 ? 8 : d8 >= 8 ? 2 : 1)), dim3(256), 0, e->stream, ds->d_rows, ds->n, ds->d,
-                         d8, first, count, b.xhi, b.xlo, cb->d_cnmax, b.xrow);
-    else
-      hipLaunchKernelGGL(k_pack_samples<SCAN_S>, dim3((unsigned)p.nsb), dim3(256), 0, e->stream, ds->d_rows, ds->n,
-                         ds->d, cb->v.d4, first, count, (float4 *)b.xt);
-  }
-  HIPCHK(hipGetLastError());
+  // the lo tiles are read by the one-level GEMMs and by level 2 from global memory (k_dist_l2); level 2 in LDS takes both
+  // pieces of a sample from xrow, and level 1 reads the hi tiles only
+  const bool pack_lo = !two || p.l2_global;
   // the bf16 tiles and norms of an unchanged codebook are reused (read-only scans chunk by chunk; the LVQ engine
   // re-splits exactly the rows it corrected); every writer of the rows clears the flag
   const bool prep_was_current = p.bf16 && cb->prep_valid;
-  if (!p.bf16) HIPCHK(hipMemsetAsync(cb->d_cnmax, 0, sizeof(unsigned int), e->stream));   // (the bf16 pack kernel zeroes it)
   const RerankInit rinit = {d_keys, b.gmin, b.paircount, p.bpad, (int)(p.bpad / 32), nonneg_keys ? 0x7FFFFFFFFFFFFFFFull : KEY_NONE,
                             b.gmin1, b.l2cnt, two ? cb->v.ngroups : 0};
   double l1_prod = 0.0, l1_sq = 0.0, err_prod = 0.0, err_sq = 0.0;
   prefilter_err3(e, ds->d, &err_prod, &err_sq);
   if (two) prefilter_err_l1(ds->d, &l1_prod, &l1_sq);
-  LaunchTimer t(e, KID_NORMS);
-  if (prep_was_current) {
-    // tiles and norms are current (unchanged codebook, or the LVQ engine re-split the rows it corrected): only the maximum is due
-    hipLaunchKernelGGL(k_max_norm, dim3(64), dim3(256), 0, e->stream, cb->v, (const float *)cb->d_cn, cb->d_cnmax);
-  } else if (p.bf16) {
-    // with the tiles a row-major copy of the rows for the exact re-rank of single rows (k_rerank_pairs), where that
-    // kernel will run behind this pre-filter on a long enough run (a shard of a map included)
-    // (the copy costs ~55 us at 65536 x 512 and saves 36 us of re-rank per 4096 vectors: from 8192 vectors per run on)
-    const bool want_rm = p.want == 1 && (cb->v.d & 3) == 0 && cb->v.ngroups >= 64 && count >= 8192;
-    if (want_rm && !cb->d_rowmajor) HIPCHK(hipMalloc((void **)&cb->d_rowmajor, sizeof(float) * (size_t)cb->v.ngroups * WAVE * cb->v.d));
-    hipLaunchKernelGGL(k_prep_codes_bf16, dim3((unsigned)cb->v.ngroups), dim3(d8 >= 16 ? 1024 : d8 >= 4 ? 256 : 64), 0,
-                       e->stream, cb->v, d8, cb->d_cn, cb->d_cnmax, cb->d_chi, cb->d_clo, want_rm ? cb->d_rowmajor : (float *)nullptr);
-    cb->prep_valid = true;
-    cb->rowmajor_valid = want_rm;
-  } else
-    hipLaunchKernelGGL(k_row_norms, dim3((unsigned)((cb->v.ngroups + 3) / 4)), dim3(256), 0, e->stream,
-                       cb->v, cb->d_cn, cb->d_cnmax);
-  hipLaunchKernelGGL(k_sample_tau, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, e->stream,
-                     ds->d_rows, ds->n, ds->d, first, count, (const unsigned int *)cb->d_cnmax,
-                     err_prod, err_sq, b.tau, rinit, l1_prod, l1_sq, b.tau1, b.xw);
+  // the word the codebook pass folds its largest norm into must be zero before it.  Two words in turn: the bf16 pack
+  // kernel, the last reader of this search's word, clears the word of the NEXT search -- no launch of its own for that.
+  // (cnmax_clean: this search's word is known to be zero; not so after an fp32 search or an error)
+  unsigned int *cnmax = cb->d_cnmax + cb->cnmax_sel;
+  if (!p.bf16 || !cb->cnmax_clean) HIPCHK(hipMemsetAsync(cnmax, 0, sizeof(unsigned int), e->stream));
+  cb->cnmax_clean = false;
+  if (!p.bf16) {
+    LaunchTimer t(e, KID_PACK_SAMPLES);
+    hipLaunchKernelGGL(k_pack_samples<SCAN_S>, dim3((unsigned)p.nsb), dim3(256), 0, e->stream, ds->d_rows, ds->n,
+                       ds->d, cb->v.d4, first, count, (float4 *)b.xt);
+  }
+  {
+    LaunchTimer t(e, KID_NORMS);
+    if (prep_was_current) {
+      // tiles and norms are current (unchanged codebook, or the LVQ engine re-split the rows it corrected): only the maximum is due
+      hipLaunchKernelGGL(k_max_norm, dim3(64), dim3(256), 0, e->stream, cb->v, (const float *)cb->d_cn, cnmax);
+    } else if (p.bf16) {
+      // with the tiles a row-major copy of the rows for the exact re-rank of single rows (k_rerank_pairs), where that
+      // kernel will run behind this pre-filter on a long enough run (a shard of a map included)
+      // (the copy saves 36 us of re-rank per 4096 vectors at 65536 x 512: from 8192 vectors per run on)
+      const bool want_rm = p.want == 1 && (cb->v.d & 3) == 0 && cb->v.ngroups >= 64 && count >= 8192;
+      if (want_rm && !cb->d_rowmajor) HIPCHK(hipMalloc((void **)&cb->d_rowmajor, sizeof(float) * (size_t)cb->v.ngroups * WAVE * cb->v.d));
+      const int prep_threads = d8 >= 16 ? 1024 : d8 >= 4 ? 256 : 64;
+      if (want_rm) {
+        if (!e->prep_rm_attr_set) {
+          HIPCHK(hipFuncSetAttribute((const void *)k_prep_codes_bf16<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PREP_RM_LDS(16)));
+          e->prep_rm_attr_set = true;
+        }
+        hipLaunchKernelGGL(k_prep_codes_bf16<true>, dim3((unsigned)cb->v.ngroups), dim3(prep_threads), PREP_RM_LDS(prep_threads / 64),
+                           e->stream, cb->v, d8, cb->d_cn, cnmax, cb->d_chi, cb->d_clo, cb->d_rowmajor);
+      } else
+        hipLaunchKernelGGL(k_prep_codes_bf16<false>, dim3((unsigned)cb->v.ngroups), dim3(prep_threads), 0,
+                           e->stream, cb->v, d8, cb->d_cn, cnmax, cb->d_chi, cb->d_clo, (float *)nullptr);
+      cb->prep_valid = true;
+      cb->rowmajor_valid = want_rm;
+    } else {
+      hipLaunchKernelGGL(k_row_norms, dim3((unsigned)((cb->v.ngroups + 3) / 4)), dim3(256), 0, e->stream,
+                         cb->v, cb->d_cn, cnmax);
+      hipLaunchKernelGGL(k_sample_tau, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, e->stream,
+                         ds->d_rows, ds->n, ds->d, first, count, (const unsigned int *)cnmax,
+                         err_prod, err_sq, b.tau, rinit, l1_prod, l1_sq, b.tau1, b.xw);
+    }
+  }
   HIPCHK(hipGetLastError());
+  if (p.bf16) {
+    LaunchTimer t(e, KID_PACK_SAMPLES);
+    hipLaunchKernelGGL(k_pack_samples_bf16, dim3((unsigned)p.nsb), dim3(PACK_THREADS), 0, e->stream, ds->d_rows, ds->n, ds->d,
+                       d8, first, count, b.xhi, pack_lo ? b.xlo : (uint4 *)nullptr, cb->d_cnmax + (cb->cnmax_sel ^ 1), b.xrow,
+                       (const unsigned int *)cnmax, TauCoef{err_prod, err_sq, l1_prod, l1_sq}, b.tau, b.tau1, b.xw, rinit);
+    HIPCHK(hipGetLastError());
+    cb->cnmax_sel ^= 1;
+    cb->cnmax_clean = true;
+  }
   return 0;
 }
 // level 1 (K2c): one bf16 product per (group, sample); per sample the smallest group minimum (k_group_min or the ring
@@ -342,8 +371,9 @@ static int pf_filter(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int
 // the nearest-row re-rank: row-granular pairs for the usual few candidates (a segment per 32-sample column), k_rerank
 // for flagged samples.  gmin_ready: the per-sample minimum is formed (else k_group_min).  xbound (shard exchange): the
 // rows of the groups whose three-product minimum is <= (MIN over the shards of their bounds) + delta3.
+// from_lists: the selection walks level 2's lists (k_rerank_select_lists; two levels only) instead of the whole wmin matrix
 static int pf_rerank(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count, const ScanPlan &p,
-                     const PrefilterBufs &b, uint64_t *d_keys, bool gmin_ready, const float *xbound) {
+                     const PrefilterBufs &b, uint64_t *d_keys, bool gmin_ready, const float *xbound, bool from_lists) {
   somhip_engine *e = cb->e;
   const int64_t ng = cb->v.ngroups, bpad = p.bpad;
   const uint32_t ncols = (uint32_t)(bpad / 32);
@@ -357,9 +387,15 @@ static int pf_rerank(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int
     LaunchTimer t(e, KID_RERANK_SELECT);
     if (!gmin_ready)
       hipLaunchKernelGGL(k_group_min, sgrid, dim3(256), 0, e->stream, ng, bpad, chunk, (const float *)b.wmin, b.gmin);
-    hipLaunchKernelGGL(k_rerank_select, sgrid, dim3(256), 0, e->stream, cb->v, count, bpad, chunk,
-                       (const float *)b.wmin, (const uint64_t *)b.wmask, xbound ? (const float *)(b.xw + 2 * bpad) : (const float *)b.tau,
-                       (const uint32_t *)b.gmin, b.gcount, cap, cap_col, (uint2 *)dpairs, b.colcount, b.paircount, e->d_stats, xbound);
+    const float *win = xbound ? (const float *)(b.xw + 2 * bpad) : (const float *)b.tau;
+    if (from_lists)
+      hipLaunchKernelGGL(k_rerank_select_lists, dim3((unsigned)ng, 4), dim3(256), 0, e->stream, cb->v, count, bpad,
+                         (const uint32_t *)b.l2cnt, (const uint16_t *)b.l2list, (const float *)b.wmin, (const uint64_t *)b.wmask, win,
+                         (const uint32_t *)b.gmin, b.gcount, cap, cap_col, (uint2 *)dpairs, b.colcount, b.paircount, xbound);
+    else
+      hipLaunchKernelGGL(k_rerank_select, sgrid, dim3(256), 0, e->stream, cb->v, count, bpad, chunk,
+                         (const float *)b.wmin, (const uint64_t *)b.wmask, win,
+                         (const uint32_t *)b.gmin, b.gcount, cap, cap_col, (uint2 *)dpairs, b.colcount, b.paircount, e->d_stats, xbound);
   }
   {
     LaunchTimer t(e, KID_RERANK_PAIRS);
@@ -413,7 +449,7 @@ static int scan_keys_top1(somhip_codebook *cb, somhip_dataset *ds, int64_t first
   somhip_engine *e = cb->e;
   const ScanPlan p = scan_plan(cb, ds, count, 1);
   if (p.route == ROUTE_MASKED || p.route == ROUTE_DIRECT)
-    HIPCHK(hipMemsetAsync(d_keys, 0xFF, sizeof(uint64_t) * (size_t)count, e->stream));   // (else k_sample_tau presets them)
+    HIPCHK(hipMemsetAsync(d_keys, 0xFF, sizeof(uint64_t) * (size_t)count, e->stream));   // (else pf_prepare presets them)
   if (p.route == ROUTE_MASKED)
     return masked_columns(e, ds, first, count, [&](int64_t off, int64_t f, int64_t c) {
       hipLaunchKernelGGL(k_scan_masked, dim3((unsigned)((cb->v.ngroups + 3) / 4), (unsigned)c), dim3(256), 0, e->stream, cb->v,
@@ -424,7 +460,7 @@ static int scan_keys_top1(somhip_codebook *cb, somhip_dataset *ds, int64_t first
   if (nonneg_keys) *nonneg_keys = true;
   PrefilterBufs b;
   CHK(pf_filter(cb, ds, first, count, p, &b, d_keys, nonneg_keys != nullptr, p.fused_gmin));
-  return pf_rerank(cb, ds, first, count, p, b, d_keys, p.fused_gmin, nullptr);
+  return pf_rerank(cb, ds, first, count, p, b, d_keys, p.fused_gmin, nullptr, p.route == ROUTE_TWO_LEVEL);
 }
 template <int K>
 static int scan_keys_topk(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count,
@@ -562,6 +598,83 @@ extern "C" int somhip_debug_level1(somhip_codebook *cb, somhip_dataset *ds, int6
   if (bpad) *bpad = p.bpad;
   return 0;
 } ABI_CATCH(somhip_debug_level1)
+// what pf_prepare leaves behind for a nearest-row search of these rows, on the bf16 pre-filter routes
+extern "C" int somhip_debug_prepared(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count,
+                                     uint16_t *chi, uint16_t *clo, float *cn, float *rowmajor, uint16_t *xhi, uint16_t *xlo,
+                                     uint16_t *xrow, float *tau, float *tau1, int32_t *info) try {
+  CHK(check_pair(cb, ds, "somhip_debug_prepared"));
+  if (!info) return fail("somhip_debug_prepared: null output");
+  if (count <= 0 || first < 0 || first >= ds->n) return fail("somhip_debug_prepared: rows [%lld, +%lld) of %lld", (long long)first, (long long)count, (long long)ds->n);   // (the window may wrap)
+  somhip_engine *e = cb->e;
+  const ScanPlan p = scan_plan(cb, ds, count, 1);
+  if (!p.bf16 || (p.route != ROUTE_ONE_LEVEL && p.route != ROUTE_TWO_LEVEL)) return fail("somhip_debug_prepared: no bf16 pre-filter for this search");
+  HIPCHK(hipSetDevice(e->device));
+  e->xc_phase = XC_NONE;
+  const bool two = p.route == ROUTE_TWO_LEVEL;
+  PrefilterBufs b;
+  CHK(bind_prefilter(cb, p, false, &b));
+  cb->prep_valid = false;                                // the codebook pass itself is what the caller asks about
+  CHK(pf_prepare(cb, ds, first, count, p, b, nullptr, false));
+  const size_t ctile = sizeof(uint4) * (size_t)cb->v.ngroups * p.d8 * WAVE, xtile = sizeof(uint4) * (size_t)p.nsb * p.d8 * 32;
+  const bool has_lo = !two || p.l2_global;
+  auto get = [&](void *dst, const void *src, size_t bytes) { return dst && src ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, e->stream) : hipSuccess; };
+  HIPCHK(get(chi, cb->d_chi, ctile));
+  HIPCHK(get(clo, cb->d_clo, ctile));
+  HIPCHK(get(cn, cb->d_cn, sizeof(float) * (size_t)cb->v.ngroups * WAVE));
+  HIPCHK(get(rowmajor, cb->rowmajor_valid ? cb->d_rowmajor : nullptr, sizeof(float) * (size_t)cb->v.ngroups * WAVE * cb->v.d));
+  HIPCHK(get(xhi, b.xhi, xtile));
+  HIPCHK(get(xlo, has_lo ? b.xlo : nullptr, xtile));
+  HIPCHK(get(xrow, two ? b.xrow : nullptr, 2 * xtile));
+  HIPCHK(get(tau, b.tau, sizeof(float) * (size_t)count));
+  HIPCHK(get(tau1, two ? b.tau1 : nullptr, sizeof(float) * (size_t)count));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  info[0] = cb->rowmajor_valid; info[1] = has_lo; info[2] = two; info[3] = p.d8;
+  return 0;
+} ABI_CATCH(somhip_debug_prepared)
+// the nearest-row search of these rows with the selection of the re-rank's pairs by the kernel the caller names
+extern "C" int somhip_debug_rerank_pairs(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count, int from_lists,
+                                         float *wmin, uint64_t *wmask, uint32_t *gmin, float *tau, uint32_t *colcount,
+                                         uint32_t *overflow, uint32_t *pairs, int64_t pairs_cap, int64_t *npairs,
+                                         uint64_t *keys, int64_t *bpad) try {
+  CHK(check_pair(cb, ds, "somhip_debug_rerank_pairs"));
+  if (!wmin || !wmask || !gmin || !tau || !colcount || !overflow || !pairs || !npairs || !keys) return fail("somhip_debug_rerank_pairs: null output");
+  if (count <= 0 || first < 0 || first >= ds->n) return fail("somhip_debug_rerank_pairs: rows [%lld, +%lld) of %lld", (long long)first, (long long)count, (long long)ds->n);   // (the window may wrap)
+  somhip_engine *e = cb->e;
+  const ScanPlan p = scan_plan(cb, ds, count, 1);
+  if (p.route != ROUTE_ONE_LEVEL && p.route != ROUTE_TWO_LEVEL) return fail("somhip_debug_rerank_pairs: no pre-filter for this search");
+  if (from_lists && p.route != ROUTE_TWO_LEVEL) return fail("somhip_debug_rerank_pairs: no level-2 lists on the one-level route");
+  HIPCHK(hipSetDevice(e->device));
+  void *dk;
+  CHK(engine_scratch(e, SLOT_CALL_A, sizeof(uint64_t) * (size_t)count, &dk));
+  e->samples_searched += (uint64_t)count;
+  PrefilterBufs b;
+  CHK(pf_filter(cb, ds, first, count, p, &b, (uint64_t *)dk, false, p.fused_gmin));
+  CHK(pf_rerank(cb, ds, first, count, p, b, (uint64_t *)dk, p.fused_gmin, nullptr, from_lists != 0));
+  const size_t cells = (size_t)cb->v.ngroups * p.bpad;
+  const uint32_t ncols = (uint32_t)(p.bpad / 32), cap_col = 16384;     // (pf_rerank's segments)
+  void *dpairs;
+  CHK(engine_scratch(e, SLOT_PAIRS, sizeof(uint2) * (size_t)ncols * cap_col + 16, &dpairs));
+  HIPCHK(hipMemcpyAsync(wmin, b.wmin, sizeof(float) * cells, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipMemcpyAsync(wmask, b.wmask, sizeof(uint64_t) * cells, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipMemcpyAsync(gmin, b.gmin, sizeof(uint32_t) * (size_t)p.bpad, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipMemcpyAsync(tau, b.tau, sizeof(float) * (size_t)count, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipMemcpyAsync(colcount, b.colcount, sizeof(uint32_t) * 4 * (size_t)ncols, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipMemcpyAsync(overflow, b.paircount, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipMemcpyAsync(keys, dk, sizeof(uint64_t) * (size_t)count, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  // the segments' filled parts, one after another
+  int64_t total = 0;
+  for (uint32_t c = 0; c < ncols; c++) {
+    const int64_t n = std::min<uint32_t>(colcount[c], cap_col);
+    if (total + n > pairs_cap) return fail("somhip_debug_rerank_pairs: %lld pairs and more, room for %lld", (long long)(total + n), (long long)pairs_cap);
+    if (n) HIPCHK(hipMemcpyAsync(pairs + 2 * total, (const uint2 *)dpairs + (size_t)c * cap_col, sizeof(uint2) * (size_t)n, hipMemcpyDeviceToHost, e->stream));
+    total += n;
+  }
+  HIPCHK(hipStreamSynchronize(e->stream));
+  *npairs = total;
+  if (bpad) *bpad = p.bpad;
+  return 0;
+} ABI_CATCH(somhip_debug_rerank_pairs)
 extern "C" int somhip_debug_scan_plan(somhip_codebook *cb, somhip_dataset *ds, int64_t count, int want, int32_t *out) try {
   CHK(check_pair(cb, ds, "somhip_debug_scan_plan"));
   if (!out) return fail("somhip_debug_scan_plan: null output");
@@ -631,7 +744,7 @@ extern "C" int somhip_shard_winner_refine(somhip_codebook *cb, somhip_dataset *d
 extern "C" int somhip_shard_winner_finish(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count,
                                           const float *dev_bound, uint64_t *dev_keys) try {
   return shard_call(cb, ds, first, count, XC_REFINED, dev_bound && dev_keys, "somhip_shard_winner_finish", [&](const ScanPlan &p, const PrefilterBufs &b) {
-    return pf_rerank(cb, ds, first, count, p, b, dev_keys, true, dev_bound);      // (refine formed the group minima)
+    return pf_rerank(cb, ds, first, count, p, b, dev_keys, true, dev_bound, true);      // (refine formed the group minima; an exchange is two-level)
   });
 } ABI_CATCH(somhip_shard_winner_finish)
 

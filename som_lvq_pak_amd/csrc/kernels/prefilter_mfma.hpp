@@ -63,6 +63,57 @@ struct RerankInit {
   uint32_t *l2_cnt;      // ... and the survivor count of every row group (preset to 0); null when one level runs
   int64_t l2_ngroups;
 };
+// the presets of RerankInit by thread t of nthreads (nthreads >= bpad + 4 * ncols)
+__device__ __forceinline__ void rerank_presets(const RerankInit &init, int64_t t, int64_t nthreads, int64_t count) {
+  if (!init.gmin) return;
+  if (t < count && init.keys) init.keys[t] = init.key_init;
+  if (t < init.bpad) { init.gmin[t] = 0xFFFFFFFFu; init.gmin[init.bpad + t] = 0u; }
+  if (t < 4 * static_cast<int64_t>(init.ncols)) init.gmin[2 * init.bpad + t] = 0u;
+  if (t == 0) *init.pair_count = 0u;
+  if (init.l2_cnt) {
+    if (t < init.bpad) init.l2_gmin1[t] = 0xFFFFFFFFu;
+    for (int64_t k = t; k < init.l2_ngroups; k += nthreads) init.l2_cnt[k] = 0u;
+  }
+}
+// the windows of sample b from its squared norm acc (double) and the codebook's largest squared row norm
+struct TauCoef { double err_prod, err_sq, l1_prod, l1_sq; };
+__device__ __forceinline__ void sample_windows(double acc, unsigned int cn_max_bits, int d, const TauCoef &co, int64_t b,
+                                               int64_t bpad, float *__restrict__ tau, float *__restrict__ tau1,
+                                               float *__restrict__ xw) {
+  // |s~ + ||x||^2 - d| <= err_prod ||x|| ||c|| + err_sq (||x|| + ||c||)^2 =: delta3 for the GEMM in use (host:
+  // prefilter_err3); tau = 2 delta3
+  const double u = 5.9604644775390625e-08;                         // 2^-24
+  const double cmax = sqrt(static_cast<double>(__uint_as_float(cn_max_bits)) * (1.0 + 4.0 * d * u));
+  const double a = sqrt(acc), s = a + cmax;
+  // every value of the GEMM forms (cn, the dot products, s~ and their partial sums) is at most ~(||x|| + ||c||)^2; past
+  // 2^126 one may overflow fp32 (inf - inf = NaN in s~) while the direct-form distance does not, and a NaN component
+  // makes the bound itself NaN: such a sample gets tau = +inf -- the re-rank (k_rerank / k_rerank_topk) then takes
+  // every row of the codebook for it with the reference's arithmetic, whatever the pre-filter kept
+  const bool all_rows = !(s * s <= 0x1p126);
+  const double t = all_rows ? static_cast<double>(INFINITY) : 2.0 * (co.err_prod * a * cmax + co.err_sq * s * s) * 1.001;
+  float tf = static_cast<float>(t);
+  if (static_cast<double>(tf) < t) tf = __uint_as_float(__float_as_uint(tf) + 1);   // round up
+  tau[b] = tf;
+  if (tau1) {                                          // the level-1 (one-product) window of the two-level pre-filter:
+    // |s~1 - s| <= l1_prod ||x|| ||c|| + l1_sq (||x|| + ||c||)^2 =: delta1 (host: prefilter_err_l1).  The window W above
+    // the smallest level-1 group minimum has to (i) hold the exact winner's group: W >= 2 delta1, and (ii) leave
+    // every group outside it with a level-1 minimum beyond what the re-rank looks at, min3 + tau <= s_min + 3 delta3,
+    // i.e. W >= delta1 + 3 delta3 (a group outside has wmin1 > min1 + W >= s_min - delta1 + W).  delta1 >= 3 delta3 in
+    // every ordinary case (the dropped lo parts dwarf the accumulation error), but not for a codebook of tiny norm.
+    const double d1 = all_rows ? static_cast<double>(INFINITY) : (co.l1_prod * a * cmax + co.l1_sq * s * s) * 1.001,
+                 d3 = 0.5 * static_cast<double>(tf);
+    const double t1 = d1 + (d1 > 3.0 * d3 ? d1 : 3.0 * d3);
+    float t1f = static_cast<float>(t1);
+    if (static_cast<double>(t1f) < t1) t1f = __uint_as_float(__float_as_uint(t1f) + 1);
+    tau1[b] = t1f;
+    if (xw) {
+      auto up = [](double v) { float f = static_cast<float>(v); if (static_cast<double>(f) < v) f = __uint_as_float(__float_as_uint(f) + 1); return f; };
+      xw[b] = up(d1);
+      xw[bpad + b] = up(d1 > 3.0 * d3 ? d1 : 3.0 * d3);
+      xw[2 * bpad + b] = up(d3);
+    }
+  }
+}
 __global__ void k_sample_tau(const float *__restrict__ rows, int64_t n_rows, int d, int64_t first,
                              int64_t count, const unsigned int *__restrict__ cn_max_bits,
                              double err_prod, double err_sq, float *__restrict__ tau, RerankInit init,
@@ -71,59 +122,15 @@ __global__ void k_sample_tau(const float *__restrict__ rows, int64_t n_rows, int
   // xw (shard exchange, K2x below): [0, bpad) delta1, [bpad, 2 bpad) max(delta1, 3 delta3), [2 bpad, 3 bpad) delta3, each rounded up
   const int64_t b = static_cast<int64_t>(blockIdx.x) * (blockDim.x >> 6) + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
-  if (init.gmin) {                                       // 64 * count threads >= bpad + 4 * ncols
-    const int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (t < count && init.keys) init.keys[t] = init.key_init;
-    if (t < init.bpad) { init.gmin[t] = 0xFFFFFFFFu; init.gmin[init.bpad + t] = 0u; }
-    if (t < 4 * static_cast<int64_t>(init.ncols)) init.gmin[2 * init.bpad + t] = 0u;
-    if (t == 0) *init.pair_count = 0u;
-    if (init.l2_cnt) {
-      if (t < init.bpad) init.l2_gmin1[t] = 0xFFFFFFFFu;
-      const int64_t nthreads = static_cast<int64_t>(gridDim.x) * blockDim.x;
-      for (int64_t k = t; k < init.l2_ngroups; k += nthreads) init.l2_cnt[k] = 0u;
-    }
-  }
+  // 64 * count threads >= bpad + 4 * ncols
+  rerank_presets(init, static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x, static_cast<int64_t>(gridDim.x) * blockDim.x, count);
   if (b >= count) return;
   const float *x = rows + ((first + b) % n_rows) * d;
   double acc = 0.0;
   for (int i = lane; i < d; i += WAVE) { double v = x[i]; acc += v * v; }
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, WAVE);
-  if (lane == 0) {
-    // |s~ + ||x||^2 - d| <= err_prod ||x|| ||c|| + err_sq (||x|| + ||c||)^2 =: delta3 for the GEMM in use (host:
-    // prefilter_err3); tau = 2 delta3
-    const double u = 5.9604644775390625e-08;                         // 2^-24
-    const double cmax = sqrt(static_cast<double>(__uint_as_float(*cn_max_bits)) * (1.0 + 4.0 * d * u));
-    const double a = sqrt(acc), s = a + cmax;
-    // every value of the GEMM forms (cn, the dot products, s~ and their partial sums) is at most ~(||x|| + ||c||)^2; past
-    // 2^126 one may overflow fp32 (inf - inf = NaN in s~) while the direct-form distance does not, and a NaN component
-    // makes the bound itself NaN: such a sample gets tau = +inf -- the re-rank (k_rerank / k_rerank_topk) then takes
-    // every row of the codebook for it with the reference's arithmetic, whatever the pre-filter kept
-    const bool all_rows = !(s * s <= 0x1p126);
-    const double t = all_rows ? static_cast<double>(INFINITY) : 2.0 * (err_prod * a * cmax + err_sq * s * s) * 1.001;
-    float tf = static_cast<float>(t);
-    if (static_cast<double>(tf) < t) tf = __uint_as_float(__float_as_uint(tf) + 1);   // round up
-    tau[b] = tf;
-    if (tau1) {                                          // the level-1 (one-product) window of the two-level pre-filter:
-      // |s~1 - s| <= l1_prod ||x|| ||c|| + l1_sq (||x|| + ||c||)^2 =: delta1 (host: prefilter_err_l1).  The window W above
-      // the smallest level-1 group minimum has to (i) hold the exact winner's group: W >= 2 delta1, and (ii) leave
-      // every group outside it with a level-1 minimum beyond what the re-rank looks at, min3 + tau <= s_min + 3 delta3,
-      // i.e. W >= delta1 + 3 delta3 (a group outside has wmin1 > min1 + W >= s_min - delta1 + W).  delta1 >= 3 delta3 in
-      // every ordinary case (the dropped lo parts dwarf the accumulation error), but not for a codebook of tiny norm.
-      const double d1 = all_rows ? static_cast<double>(INFINITY) : (l1_prod * a * cmax + l1_sq * s * s) * 1.001,
-                   d3 = 0.5 * static_cast<double>(tf);
-      const double t1 = d1 + (d1 > 3.0 * d3 ? d1 : 3.0 * d3);
-      float t1f = static_cast<float>(t1);
-      if (static_cast<double>(t1f) < t1) t1f = __uint_as_float(__float_as_uint(t1f) + 1);
-      tau1[b] = t1f;
-      if (xw) {
-        auto up = [](double v) { float f = static_cast<float>(v); if (static_cast<double>(f) < v) f = __uint_as_float(__float_as_uint(f) + 1); return f; };
-        xw[b] = up(d1);
-        xw[init.bpad + b] = up(d1 > 3.0 * d3 ? d1 : 3.0 * d3);
-        xw[2 * init.bpad + b] = up(d3);
-      }
-    }
-  }
+  if (lane == 0) sample_windows(acc, *cn_max_bits, d, TauCoef{err_prod, err_sq, l1_prod, l1_sq}, b, init.bpad, tau, tau1, xw);
 }
 
 // Epilogue shared by the fp32 and the split-bf16 distance GEMMs (same C/D register layout):
@@ -308,30 +315,67 @@ __device__ __forceinline__ void split8(const float4 a, const float4 b, uint4 &hi
 // squared norms (fp32) + bf16 hi/lo tiles of the codebook, one pass.  One workgroup per row group; its
 // blockDim/64 waves (up to 16) take the k-blocks round-robin and their partial norms are added in wave order
 // (the bound tau is built from holds for any summation order, and this one is fixed).
-// rowmajor (may be null): a row-major fp32 copy of the rows, [ngroups * 64][d] -- every lane stores the 32 bytes of its row
-// it holds anyway; the 64 lanes of a store go to 64 rows, but the lines come together in L2 (a row group's 64 rows are
-// written by the waves of one workgroup) and leave it whole.  The exact re-rank of single rows reads from it.
+// RM: with them a row-major fp32 copy of the rows, [ngroups * 64][d] (d % 4 == 0), for the exact re-rank of single
+// rows.  A lane holds 32 bytes of ITS row per k-block, so a store straight from the registers puts 64 rows x 32 bytes
+// into one instruction.  Instead the k-blocks of one round (k-block = round * waves + wave) go through LDS: every lane
+// writes its two float4 at [row][chunk ^ (row & 7)] (the eight lanes of a ds_write_b128 group then fall on eight
+// different 16-byte slots of the 128-byte bank row), and after the round's barrier each store instruction takes
+// 64 / (2 waves) whole pieces of 32 waves bytes -- 2 rows x 512 bytes with 16 waves.  Two buffers: a round's barrier
+// also tells that everyone has read the buffer the next round writes.  Dynamic LDS: PREP_RM_LDS(waves) bytes; the
+// partial norms take its place after the last round.
+constexpr size_t PREP_RM_LDS(int waves) { return sizeof(float4) * 2 * WAVE * 2 * (waves > 1 ? waves : 2); }
+template <bool RM>
 __global__ void k_prep_codes_bf16(CbView cb, int d8, float *__restrict__ cn,
                                   unsigned int *__restrict__ cn_max_bits, uint4 *__restrict__ chi,
                                   uint4 *__restrict__ clo, float *__restrict__ rowmajor = nullptr) {
-  __shared__ float s_part[16][WAVE];
+  extern __shared__ float4 s_rm[];                        // RM: [2][64 rows][2 waves chunks]
+  float (*s_part)[WAVE];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
   const int64_t g = blockIdx.x;
   float acc = 0.0f;
-  for (int kb = wave; kb < d8; kb += nw) {
-    const float4 a = *tile_ptr(cb, g, 2 * kb, lane);
-    const float4 b = (2 * kb + 1 < cb.d4) ? *tile_ptr(cb, g, 2 * kb + 1, lane) : make_float4(0.f, 0.f, 0.f, 0.f);
-    acc += a.x * a.x; acc += a.y * a.y; acc += a.z * a.z; acc += a.w * a.w;
-    acc += b.x * b.x; acc += b.y * b.y; acc += b.z * b.z; acc += b.w * b.w;
-    uint4 hi, lo;
-    split8(a, b, hi, lo);
-    chi[(g * d8 + kb) * WAVE + lane] = hi;
-    clo[(g * d8 + kb) * WAVE + lane] = lo;
-    if (rowmajor) {                                       // (d % 4 == 0: the host asks for the copy only then)
-      float4 *dst = reinterpret_cast<float4 *>(rowmajor + (g * WAVE + lane) * cb.d) + 2 * kb;
-      dst[0] = a;
-      if (2 * kb + 1 < cb.d4) dst[1] = b;
+  if constexpr (!RM) {
+    __shared__ float s_part_static[16][WAVE];
+    s_part = s_part_static;
+    for (int kb = wave; kb < d8; kb += nw) {
+      const float4 a = *tile_ptr(cb, g, 2 * kb, lane);
+      const float4 b = (2 * kb + 1 < cb.d4) ? *tile_ptr(cb, g, 2 * kb + 1, lane) : make_float4(0.f, 0.f, 0.f, 0.f);
+      acc += a.x * a.x; acc += a.y * a.y; acc += a.z * a.z; acc += a.w * a.w;
+      acc += b.x * b.x; acc += b.y * b.y; acc += b.z * b.z; acc += b.w * b.w;
+      uint4 hi, lo;
+      split8(a, b, hi, lo);
+      chi[(g * d8 + kb) * WAVE + lane] = hi;
+      clo[(g * d8 + kb) * WAVE + lane] = lo;
     }
+  } else {
+    const int ch = 2 * nw, swz = lane & (ch - 1) & 7;     // chunks (float4) of a row per round; ch is 2, 8 or 32
+    const int rows_per = WAVE / ch < 1 ? 1 : WAVE / ch;   // rows one store instruction covers (ch <= 64)
+    const int nrounds = (d8 + nw - 1) / nw;
+    for (int r = 0; r < nrounds; r++) {
+      const int kb = r * nw + wave;
+      float4 *buf = s_rm + (r & 1) * WAVE * ch;
+      if (kb < d8) {
+        const float4 a = *tile_ptr(cb, g, 2 * kb, lane);
+        const float4 b = (2 * kb + 1 < cb.d4) ? *tile_ptr(cb, g, 2 * kb + 1, lane) : make_float4(0.f, 0.f, 0.f, 0.f);
+        acc += a.x * a.x; acc += a.y * a.y; acc += a.z * a.z; acc += a.w * a.w;
+        acc += b.x * b.x; acc += b.y * b.y; acc += b.z * b.z; acc += b.w * b.w;
+        uint4 hi, lo;
+        split8(a, b, hi, lo);
+        chi[(g * d8 + kb) * WAVE + lane] = hi;
+        clo[(g * d8 + kb) * WAVE + lane] = lo;
+        buf[lane * ch + ((2 * wave) ^ swz)] = a;
+        buf[lane * ch + ((2 * wave + 1) ^ swz)] = b;
+      }
+      __syncthreads();
+      // the round's 64 rows x ch chunks: instruction i of the workgroup takes rows [i rows_per, +rows_per)
+      for (int i = wave; i * rows_per < WAVE; i += nw) {
+        const int row = i * rows_per + lane / ch, c = lane % ch;
+        const int q = r * ch + c;                         // the chunk's place in the row
+        if (q < cb.d4)
+          reinterpret_cast<float4 *>(rowmajor + (g * WAVE + row) * cb.d)[q] = buf[row * ch + (c ^ (row & (ch - 1) & 7))];
+      }
+    }
+    __syncthreads();                                       // (the partial norms take the buffers' place)
+    s_part = reinterpret_cast<float (*)[WAVE]>(s_rm);
   }
   s_part[wave][lane] = acc;
   __syncthreads();
@@ -386,41 +430,72 @@ __global__ __launch_bounds__(256) void k_max_norm(CbView cb, const float *__rest
   if ((threadIdx.x & 63) == 0) atomicMax(cn_max_bits, __float_as_uint(m));
 }
 
-// a run of samples -> bf16 hi/lo sample tiles xt[sb][kb][32][8].  grid = (32-sample tiles, slices of the k-blocks)
-__global__ void k_pack_samples_bf16(const float *__restrict__ rows, int64_t n_rows, int d, int d8,
+// a run of samples -> bf16 hi/lo sample tiles xt[sb][kb][32][8], and with them what k_sample_tau makes on the other
+// routes: the samples' windows and the re-rank's presets.  One workgroup (PACK_THREADS) per 32-sample tile holds WHOLE
+// rows: thread e takes (k-block e / 32, sample e % 32), PACK_U elements with their loads in flight together, and adds the
+// squares of what it holds in double; the PACK_THREADS / 32 partial sums of a sample are added in thread order.  (The
+// order differs from k_sample_tau's; the 1.001 and the round-up in the windows cover a reordered DOUBLE sum many times
+// over.)  cn_max_bits: the codebook pass ran BEFORE this kernel; zero_word: the word the next search's codebook pass
+// accumulates into.
+constexpr int PACK_THREADS = 512, PACK_U = 4;
+__global__ __launch_bounds__(PACK_THREADS) void k_pack_samples_bf16(const float *__restrict__ rows, int64_t n_rows, int d, int d8,
                                     int64_t first, int64_t count, uint4 *__restrict__ xhi,
                                     uint4 *__restrict__ xlo, unsigned int *__restrict__ zero_word,
-                                    uint4 *__restrict__ xrow = nullptr) {
+                                    uint4 *__restrict__ xrow, const unsigned int *__restrict__ cn_max_bits,
+                                    TauCoef co, float *__restrict__ tau, float *__restrict__ tau1,
+                                    float *__restrict__ xw, RerankInit init) {
   // xrow (level 2 of the two-level pre-filter gathers single samples): the same pieces sample by sample,
   // xrow[(sample * d8 + kb) * 2 + {hi, lo}] -- a sample's operands of consecutive K-steps are then consecutive bytes
+  // xlo (may be null): the lo tiles, where a GEMM reads them
+  __shared__ double s_sq[PACK_THREADS / 32][32];
   const int64_t sb = blockIdx.x;
-  if (zero_word && sb == 0 && blockIdx.y == 0 && threadIdx.x == 0) *zero_word = 0u;   // max ||c||^2 accumulator of the next kernel
-  const int per = (d8 + gridDim.y - 1) / gridDim.y;
-  const int kb_lo = blockIdx.y * per, kb_hi = kb_lo + per < d8 ? kb_lo + per : d8;
+  if (zero_word && sb == 0 && threadIdx.x == 0) *zero_word = 0u;
+  rerank_presets(init, sb * PACK_THREADS + threadIdx.x, static_cast<int64_t>(gridDim.x) * PACK_THREADS, count);
   const bool vec = (d & 7) == 0 && (reinterpret_cast<uintptr_t>(rows) & 15) == 0;   // two aligned float4 per k-block
-  for (int e = threadIdx.x; e < (kb_hi - kb_lo) * 32; e += blockDim.x) {
-    const int kb = kb_lo + e / 32, sidx = e % 32;
-    const int64_t smp = sb * 32 + sidx;
-    float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
-    if (smp < count) {
-      const float *x = rows + ((first + smp) % n_rows) * d;
-      if (vec) {
-        a = reinterpret_cast<const float4 *>(x)[2 * kb];
-        b = reinterpret_cast<const float4 *>(x)[2 * kb + 1];
-      } else {
-        float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  const int sidx = threadIdx.x % 32;
+  const int64_t smp = sb * 32 + sidx;
+  const float *x = rows + ((first + (smp < count ? smp : 0)) % n_rows) * d;
+  const int nel = d8 * 32;
+  double acc = 0.0;
+  for (int e0 = threadIdx.x; e0 < nel; e0 += PACK_THREADS * PACK_U) {
+    float4 a[PACK_U], b[PACK_U];
 #pragma unroll
-        for (int j = 0; j < 8; j++) if (kb * 8 + j < d) v[j] = x[kb * 8 + j];
-        a = make_float4(v[0], v[1], v[2], v[3]);
-        b = make_float4(v[4], v[5], v[6], v[7]);
+    for (int u = 0; u < PACK_U; u++) {
+      const int kb = (e0 + u * PACK_THREADS) / 32;
+      a[u] = make_float4(0.f, 0.f, 0.f, 0.f); b[u] = a[u];
+      if (smp < count && kb < d8) {
+        if (vec) {
+          a[u] = reinterpret_cast<const float4 *>(x)[2 * kb];
+          b[u] = reinterpret_cast<const float4 *>(x)[2 * kb + 1];
+        } else {
+          float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int j = 0; j < 8; j++) if (kb * 8 + j < d) v[j] = x[kb * 8 + j];
+          a[u] = make_float4(v[0], v[1], v[2], v[3]);
+          b[u] = make_float4(v[4], v[5], v[6], v[7]);
+        }
       }
     }
-    uint4 hi, lo;
-    split8(a, b, hi, lo);
-    xhi[(sb * d8 + kb) * 32 + sidx] = hi;
-    xlo[(sb * d8 + kb) * 32 + sidx] = lo;
-    if (xrow) { xrow[(smp * d8 + kb) * 2] = hi; xrow[(smp * d8 + kb) * 2 + 1] = lo; }
+#pragma unroll
+    for (int u = 0; u < PACK_U; u++) {
+      const int kb = (e0 + u * PACK_THREADS) / 32;
+      if (kb >= d8) continue;
+      const float v[8] = {a[u].x, a[u].y, a[u].z, a[u].w, b[u].x, b[u].y, b[u].z, b[u].w};
+#pragma unroll
+      for (int j = 0; j < 8; j++) { const double w = v[j]; acc += w * w; }
+      uint4 hi, lo;
+      split8(a[u], b[u], hi, lo);
+      xhi[(sb * d8 + kb) * 32 + sidx] = hi;
+      if (xlo) xlo[(sb * d8 + kb) * 32 + sidx] = lo;
+      if (xrow) { xrow[(smp * d8 + kb) * 2] = hi; xrow[(smp * d8 + kb) * 2 + 1] = lo; }
+    }
   }
+  s_sq[threadIdx.x / 32][sidx] = acc;
+  __syncthreads();
+  if (threadIdx.x >= 32 || smp >= count) return;
+  acc = s_sq[0][sidx];
+  for (int k = 1; k < PACK_THREADS / 32; k++) acc += s_sq[k][sidx];
+  sample_windows(acc, *cn_max_bits, d, co, smp, init.bpad, tau, tau1, xw);
 }
 
 __global__ __launch_bounds__(256, 2) void k_dist_mfma_bf16(CbView cb, int d8,

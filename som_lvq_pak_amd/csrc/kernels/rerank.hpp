@@ -668,6 +668,67 @@ __global__ __launch_bounds__(256) void k_rerank_select(CbView cb, int64_t count,
   (void)stats;
 }
 
+// K2s behind the two-level pre-filter: the same pairs, counters and overflow rule from level 2's lists instead of the
+// whole wmin matrix.  A (group, sample) pair outside the lists cannot pass wmin <= gmin + tau ("Why
+// the pre-filter results are still bit-exact": a group that level 1 leaves out keeps a level-1 value above anything the
+// re-rank looks at; under a shard-exchange bound k_l2_select writes 3.4e38 over it), so only list[g][0 .. cnt[g]) is
+// walked: one entry per thread, the row group in blockIdx.x, its entries dealt to the gridDim.y workgroups of the row.
+// An entry that passes reserves its rows' room in the segment of its 32-sample column itself (a few dozen
+// reservations per segment and launch, spread over all the segments); the order inside a segment is free, K2p folds
+// with an atomic minimum.  Per-column statistics and gcount as in k_rerank_select: the per-column maximum is the
+// largest running count any sample's atomicAdd has seen, which is the sample's final count whatever the order.
+__global__ __launch_bounds__(256) void k_rerank_select_lists(CbView cb, int64_t count, int64_t bpad,
+                                                             const uint32_t *__restrict__ l2cnt,
+                                                             const uint16_t *__restrict__ l2list,
+                                                             const float *__restrict__ wmin,
+                                                             const uint64_t *__restrict__ wmask,
+                                                             const float *__restrict__ tau,
+                                                             const uint32_t *__restrict__ gmin,
+                                                             uint32_t *__restrict__ gcount,
+                                                             uint32_t cap, uint32_t cap_col,
+                                                             uint2 *__restrict__ pairs,
+                                                             uint32_t *__restrict__ col_count,
+                                                             uint32_t *__restrict__ pair_count,
+                                                             const float *__restrict__ xub = nullptr) {
+  const int64_t g = blockIdx.x;
+  const uint32_t ncols = static_cast<uint32_t>(bpad / 32);
+  const uint32_t n = l2cnt[g] < static_cast<uint32_t>(bpad) ? l2cnt[g] : static_cast<uint32_t>(bpad);
+  // padding rows of the last group: bit 32h+16i+r is row 32i + (r&3) + 8(r>>2) + 4h (k_rerank_select's rule)
+  unsigned long long keep = ~0ull;
+  if ((g + 1) * WAVE > cb.n) {
+    keep = 0;
+    for (int t = 0; t < 64; t++) {
+      const int h = t >> 5, i = (t >> 4) & 1, r = t & 15;
+      if (g * WAVE + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * h < cb.n) keep |= 1ull << t;
+    }
+  }
+  for (uint32_t e = blockIdx.y * blockDim.x + threadIdx.x; e < n; e += gridDim.y * blockDim.x) {
+    const int64_t b = l2list[g * bpad + e];
+    if (b >= count) continue;                            // (k_l2_select files live samples only)
+    const float thr = (xub ? xub[b] : ordered_to_float(gmin[b])) + tau[b];
+    if (!(wmin[g * bpad + b] <= thr)) continue;
+    unsigned long long mm = wmask[g * bpad + b] & keep;
+    const unsigned c = __popcll(mm);
+    if (c == 0) continue;
+    const uint32_t col = static_cast<uint32_t>(b >> 5);
+    unsigned at = atomicAdd(col_count + col, c);
+    if (at + c > cap_col) atomicMax(pair_count, cap + 1);
+    atomicAdd(col_count + ncols * 1 + col, 1u);
+    atomicAdd(col_count + ncols * 2 + col, c);
+    const unsigned before = atomicAdd(gcount + b, 1u);
+    atomicMax(col_count + ncols * 3 + col, before + 1u);
+    uint2 *seg = pairs + static_cast<size_t>(col) * cap_col;
+    while (mm) {
+      const int t = __builtin_ctzll(mm);
+      mm &= mm - 1;
+      const int h = t >> 5, i = (t >> 4) & 1, r = t & 15;
+      if (at < cap_col)
+        seg[at] = make_uint2(static_cast<uint32_t>(b), static_cast<uint32_t>(g * WAVE + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * h));
+      at++;
+    }
+  }
+}
+
 constexpr int PAIR_MAX_COLS = 4096;     // 32-sample columns per run (131 072 samples)
 
 __global__ __launch_bounds__(256) void k_rerank_pairs(CbView cb, const float *__restrict__ rows,

@@ -137,7 +137,7 @@ enum ScratchSlot {
   SLOT_MEMBER_COUNT,       // SOM update: members per row group
   SLOT_MEMBER_LIST,        // SOM update: the member lists
   SLOT_PAIRS,              // top-1 re-rank: candidate pairs; top-K re-rank: its pair list
-  SLOT_RERANK_COUNT,       // pre-filter: re-rank counters preset by k_sample_tau, from prepare to the re-rank
+  SLOT_RERANK_COUNT,       // pre-filter: re-rank counters preset in pf_prepare, from prepare to the re-rank
   SLOT_LVQ_FINAL,          // exact LVQ batches: the final keys
   SLOT_XBOUND,             // shard exchange: the deltas behind the exchanged bounds, from begin to finish
   SLOT_TOPK_SPAN,          // top-K re-rank: each sample's span of the pair list
@@ -151,8 +151,8 @@ enum ScratchSlot {
   SLOT_LVQ_STAGE_TA,       // ... their rates
   SLOT_LVQ_CAND_LAB,       // ... the candidates' labels
   SLOT_LVQ_CAND_TA,        // ... the candidates' rates
-  SLOT_L2_STATE,           // two-level pre-filter: level 1's window and minimum, level 2's counts, from prepare to level 2
-  SLOT_L2_LIST,            // two-level pre-filter: level 2's group lists, from level 1 to level 2
+  SLOT_L2_STATE,           // two-level pre-filter: level 1's window and minimum, level 2's counts, from prepare to the re-rank
+  SLOT_L2_LIST,            // two-level pre-filter: level 2's group lists, from level 1 to the re-rank (k_rerank_select_lists)
   SLOT_LVQ_CTL,            // exact LVQ loop: its control block
   SLOT_TOPK_GROUPS,        // top-K re-rank by row group: the groups' lists and the passes
   SLOT_TAIL_START,         // GEMM update: where each group's list tail starts
@@ -201,6 +201,7 @@ struct somhip_engine {
   bool lvq_apply_attr_set = false;             // hipFuncSetAttribute(k_lvq_batch_apply, ...) done on this device
   bool l2_lds_attr_set = false;                // ... and for k_dist_l2_lds
   bool l1r_attr_set = false;                   // ... and for k_dist_mfma_bf16_l1r
+  bool prep_rm_attr_set = false;               // ... and for k_prep_codes_bf16<true>
   int n_cus = 0;                               // compute units of the device (grid of the persistent kernels)
   LvqCtl *lvq_hctl = nullptr;                  // pinned: read-backs of the LVQ batch loop's control block, one per batch in flight
   hipEvent_t lvq_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -428,7 +429,9 @@ struct somhip_codebook {
   int32_t *d_labels = nullptr;     // [n] local rows
   float *d_talpha = nullptr;       // [n] OLVQ1 rates
   float *d_cn = nullptr;           // [ngroups*64] squared row norms (MFMA pre-filter)
-  unsigned int *d_cnmax = nullptr; // bits of max squared norm
+  unsigned int *d_cnmax = nullptr; // bits of max squared norm: two words, used in turn by successive searches (pf_prepare)
+  int cnmax_sel = 0;               // the word of the next search
+  bool cnmax_clean = false;        // ... which is known to be zero
   uint4 *d_chi = nullptr, *d_clo = nullptr;   // bf16 hi/lo tiles [ngroups][d8][64] (bf16 pre-filter)
   bool prep_valid = false;         // d_cn / d_chi / d_clo describe the rows as they are now (set by a full k_prep_codes_bf16,
                                    // kept by the LVQ engine when it re-splits exactly the rows it corrected, cleared by every other writer)

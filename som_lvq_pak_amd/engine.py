@@ -326,6 +326,56 @@ def scan_plan(cb, ds, count, want=1):
             "by_group": bool(out[4]), "l2_global": bool(out[5]), "fused_gmin": bool(out[6])}
 
 
+def debug_prepared(cb, ds, first, count):
+    """What the preparation of a nearest-row search of data rows [first, first + count) leaves on the device
+    (somhip_debug_prepared; bf16 scan mode on a pre-filter route): a dict of numpy arrays, bf16 values as uint16;
+    `rowmajor`, `xlo`, `xrow` and `tau1` are None where the search makes none."""
+    d8 = (cb.dim + 7) // 8
+    ng, nsb = (cb.n + 63) // 64, (count + 31) // 32
+    out = {"chi": np.zeros((ng, d8, 64, 8), np.uint16), "clo": np.zeros((ng, d8, 64, 8), np.uint16),
+           "cn": np.zeros(ng * 64, np.float32), "rowmajor": np.zeros((ng * 64, cb.dim), np.float32),
+           "xhi": np.zeros((nsb, d8, 32, 8), np.uint16), "xlo": np.zeros((nsb, d8, 32, 8), np.uint16),
+           "xrow": np.zeros((nsb * 32, d8, 2, 8), np.uint16), "tau": np.zeros(count, np.float32),
+           "tau1": np.zeros(count, np.float32)}
+    info = (C.c_int32 * 4)()
+    u16, f32 = _lib.c_u16_p, _lib.c_float_p
+    check(cb.e.lib.somhip_debug_prepared(cb.h, ds.h, first, count, _p(out["chi"], u16), _p(out["clo"], u16), _p(out["cn"], f32),
+                                         _p(out["rowmajor"], f32), _p(out["xhi"], u16), _p(out["xlo"], u16),
+                                         _p(out["xrow"], u16), _p(out["tau"], f32), _p(out["tau1"], f32), info))
+    assert info[3] == d8
+    if not info[0]:
+        out["rowmajor"] = None
+    if not info[1]:
+        out["xlo"] = None
+    if not info[2]:
+        out["xrow"] = out["tau1"] = None
+    return out
+
+
+def debug_rerank_pairs(cb, ds, first, count, from_lists, pairs_cap=None):
+    """The nearest-row search of data rows [first, first + count) with the re-rank's pairs selected from level 2's lists
+    (from_lists) or from the whole matrix of group minima (somhip_debug_rerank_pairs): a dict of what the selection read
+    (wmin, wmask [ngroups, bpad], gmin [bpad], tau [count]), what it wrote (colcount [4, ncols], overflow, pairs [n, 2] as
+    (sample, row)) and the search's keys [count]."""
+    ng, bp = (cb.n + 63) // 64, (count + 31) // 32 * 32
+    ncols = bp // 32
+    pairs_cap = pairs_cap if pairs_cap is not None else min(ncols * 16384, max(1 << 20, 64 * count))
+    out = {"wmin": np.zeros((ng, bp), np.float32), "wmask": np.zeros((ng, bp), np.uint64), "gmin": np.zeros(bp, np.uint32),
+           "tau": np.zeros(count, np.float32), "colcount": np.zeros((4, ncols), np.uint32),
+           "keys": np.zeros(count, np.uint64)}
+    pairs = np.zeros((pairs_cap, 2), np.uint32)
+    overflow, npairs, bpad = np.zeros(1, np.uint32), C.c_int64(0), C.c_int64(0)
+    check(cb.e.lib.somhip_debug_rerank_pairs(cb.h, ds.h, first, count, int(bool(from_lists)), _p(out["wmin"], _lib.c_float_p),
+                                             _p(out["wmask"], _lib.c_u64_p), _p(out["gmin"], _lib.c_u32_p),
+                                             _p(out["tau"], _lib.c_float_p), _p(out["colcount"], _lib.c_u32_p),
+                                             _p(overflow, _lib.c_u32_p), _p(pairs, _lib.c_u32_p), pairs_cap, C.byref(npairs),
+                                             _p(out["keys"], _lib.c_u64_p), C.byref(bpad)))
+    assert bpad.value == bp
+    out["overflow"] = int(overflow[0])
+    out["pairs"] = pairs[:npairs.value].copy()
+    return out
+
+
 UPDATE_APPLY = ("gemm", "gauss_h", "gauss_s", "bubble_s", "run")
 UPDATE_ENTRY = ("sample", "float4", "byte")
 
