@@ -490,6 +490,21 @@ int  somhip_class_nearest_later(somhip_dataset *ds, float *min_sq, int32_t *stat
 enum { SOMHIP_UMAT_AVERAGE = 1, SOMHIP_UMAT_MEDIAN = 2 };
 int  somhip_umatrix(somhip_codebook *cb, int filters, float *u, double minmax[2]);
 
+/* ---- grey-scaled component planes of a codebook (SOM_PAK planes: planes.c print_plane) ----
+ * For the n_planes components from first_plane on, from the rows as they are on the device now, without a host copy
+ * of the rows:
+ *   lo, hi  NULL, or [n_planes]: minval and maxval of the component over all rows (planes.c:146-157).  Of rows that
+ *           compare equal (+0.0 and -0.0) the first one's bits are kept, as the reference's comparisons keep them.
+ *   grey    host, [n_planes][n_rows], plane-major: grey[j * n_rows + k] is the grey level of component first_plane + j
+ *           of row k (the reference's row order), bit for bit
+ *             (float)(0.05 + 0.9 * (double)(float)(p - minval) / (double)(float)(maxval - minval))
+ *           and 0.5 where the float difference maxval - minval is zero (planes.c:172-176).
+ * Any topology is taken.  A caller bounds what both sides hold at once by asking for the planes in windows.
+ * Refused before any launch: null arguments, a codebook whose engine was destroyed, a shard (contiguous or
+ * interleaved), n_planes < 1, a window that is not inside [0, dim).  Non-finite components: a NaN takes no part in
+ * minval and maxval, as in the reference; what follows from there is not specified. */
+int  somhip_planes(somhip_codebook *cb, int first_plane, int n_planes, float *grey, float *lo, float *hi);
+
 /* device scratch helpers for hosts without their own allocator */
 int  somhip_device_alloc(somhip_engine *e, int64_t bytes, void **dev_ptr);
 int  somhip_device_free(somhip_engine *e, void *dev_ptr);

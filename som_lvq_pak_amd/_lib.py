@@ -114,6 +114,7 @@ SIGNATURES = {
     "somhip_sammon": (C.c_int, [C.c_void_p, C.c_int64, c_float_p, c_float_p, c_double_p]),
     "somhip_class_nearest_later": (C.c_int, [C.c_void_p, c_float_p, c_i32_p]),
     "somhip_umatrix": (C.c_int, [C.c_void_p, C.c_int, c_float_p, c_double_p]),
+    "somhip_planes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_float_p, c_float_p, c_float_p]),
     "somhip_device_alloc": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]),
     "somhip_device_free": (C.c_int, [C.c_void_p, C.c_void_p]),
     "somhip_copy_to_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),

@@ -36,3 +36,4 @@
 #include "kernels/sammon.hpp"
 #include "kernels/class_nearest.hpp"
 #include "kernels/umat.hpp"
+#include "kernels/planes.hpp"

@@ -128,7 +128,8 @@ enum ScratchSlot {
   SLOT_SAMPLES,            // the packed sample tiles of a scan: direct scan, or the pre-filter from prepare to level 2
   SLOT_PARTIAL,            // partial top-K lists (top-K scans and re-rank), the LVQ online loop's, the online SOM's rows
   SLOT_CALL_A,             // a host call's own array around the scans it runs: keys, LVQ candidates, column sums;
-                           // somhip_umatrix: the matrix (SLOT_CALL_B its out-of-place copy, SLOT_PARTIAL min and max)
+                           // somhip_umatrix: the matrix (SLOT_CALL_B its out-of-place copy, SLOT_PARTIAL min and max);
+                           // somhip_planes: the grey levels (SLOT_PARTIAL the slabs' keys, SLOT_CALL_B lo and hi)
   SLOT_CALL_B,             // ... and its second one: step scalars, LvqStep, column counts, products
   SLOT_TAU,                // pre-filter: per-sample window, from prepare to the re-rank
   SLOT_WMIN,               // pre-filter: per (group, sample) minimum, from level 1 / one level to the re-rank
@@ -738,3 +739,4 @@ extern "C" void somhip_dataset_destroy(somhip_dataset *ds) try {
 #include "host_sammon.inc"
 #include "host_class.inc"
 #include "host_umat.inc"
+#include "host_planes.inc"

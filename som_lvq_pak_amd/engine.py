@@ -557,6 +557,20 @@ def umatrix(cb, average=False, median=False):
     return u, (float(mm[0]), float(mm[1]))
 
 
+def planes(cb, first=0, count=None):
+    """Grey-scaled component planes of a whole codebook from the rows on the device (somhip_planes): (grey, lo, hi).
+    grey is float32 [count, n], grey[j, k] = SOM_PAK's cv (planes.c:172-176) of component first + j of row k, bit for
+    bit; lo and hi are float32 [count], the component's minval and maxval over the rows.  count=None: every component
+    from `first` on.  Raises on a shard and on a window outside [0, dim)."""
+    count = cb.dim - first if count is None else count
+    grey = np.empty((max(count, 0), cb.n), dtype=np.float32)
+    lo = np.empty(max(count, 0), dtype=np.float32)
+    hi = np.empty(max(count, 0), dtype=np.float32)
+    check(cb.e.lib.somhip_planes(cb.h, first, count, _p(grey, _lib.c_float_p), _p(lo, _lib.c_float_p),
+                                 _p(hi, _lib.c_float_p)))
+    return grey, lo, hi
+
+
 def sammon_zero_pairs(cb):
     """The pairs of rows (i, j), i < j, at reference distance 0.0 (somhip_sammon_zero_pairs): int64 [n, 2], sorted --
     what sammon's remove_identicals (sammon.c:84-128) asks.  Distance 0 is not row equality: small squares underflow."""
