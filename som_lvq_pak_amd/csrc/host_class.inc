@@ -44,13 +44,13 @@ extern "C" int somhip_class_nearest_later(somhip_dataset *ds, float *min_sq, int
   if (chunks > 65535) return fail("somhip_class_nearest_later: a class of %lld rows is more than this path indexes", (long long)o.largest);
   const bool masked = ds->d_mask != nullptr;
 
-  void *d_perm, *d_end, *d_tiles, *d_mtiles = nullptr, *d_min, *d_flag;
-  CHK(engine_scratch(e, SLOT_CALL_A, sizeof(int32_t) * (size_t)n, &d_perm));
-  CHK(engine_scratch(e, SLOT_CALL_B, sizeof(int32_t) * (size_t)padded, &d_end));
-  CHK(engine_scratch(e, SLOT_STAGE, sizeof(float4) * (size_t)padded * d4, &d_tiles));
-  if (masked) CHK(engine_scratch(e, SLOT_SAMPLES, sizeof(uint32_t) * (size_t)padded * d4, &d_mtiles));
-  CHK(engine_scratch(e, SLOT_PARTIAL, sizeof(uint32_t) * (size_t)padded, &d_min));
-  CHK(engine_scratch(e, SLOT_PAIRS, sizeof(uint32_t) * (size_t)padded, &d_flag));
+  int32_t *d_perm, *d_end; float4 *d_tiles; uint32_t *d_mtiles = nullptr, *d_min, *d_flag;
+  CHK(scratch(e, SLOT_CALL_A, (size_t)n, &d_perm));
+  CHK(scratch(e, SLOT_CALL_B, (size_t)padded, &d_end));
+  CHK(scratch(e, SLOT_STAGE, (size_t)padded * d4, &d_tiles));
+  if (masked) CHK(scratch(e, SLOT_SAMPLES, (size_t)padded * d4, &d_mtiles));
+  CHK(scratch(e, SLOT_PARTIAL, (size_t)padded, &d_min));
+  CHK(scratch(e, SLOT_PAIRS, (size_t)padded, &d_flag));
   HIPCHK(hipMemcpyAsync(d_perm, o.perm.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, e->stream));
   HIPCHK(hipMemcpyAsync(d_end, o.seg_end.data(), sizeof(int32_t) * (size_t)padded, hipMemcpyHostToDevice, e->stream));
   HIPCHK(hipMemsetD32Async((hipDeviceptr_t)d_min, (int)CLASS_NONE_BITS, (size_t)padded, e->stream));
@@ -59,10 +59,10 @@ extern "C" int somhip_class_nearest_later(somhip_dataset *ds, float *min_sq, int
     LaunchTimer t(e, KID_LAYOUT);
     if (masked)
       hipLaunchKernelGGL(k_class_layout<true>, dim3((unsigned)groups), dim3(256), 0, e->stream, ds->d_rows, (const uint8_t *)ds->d_mask,
-                         (const int32_t *)d_perm, n, d, d4, (float4 *)d_tiles, (uint32_t *)d_mtiles);
+                         (const int32_t *)d_perm, n, d, d4, d_tiles, d_mtiles);
     else
       hipLaunchKernelGGL(k_class_layout<false>, dim3((unsigned)groups), dim3(256), 0, e->stream, ds->d_rows, (const uint8_t *)nullptr,
-                         (const int32_t *)d_perm, n, d, d4, (float4 *)d_tiles, (uint32_t *)nullptr);
+                         (const int32_t *)d_perm, n, d, d4, d_tiles, (uint32_t *)nullptr);
   }
   HIPCHK(hipGetLastError());
   {
@@ -70,10 +70,10 @@ extern "C" int somhip_class_nearest_later(somhip_dataset *ds, float *min_sq, int
     const dim3 grid((unsigned)blocks, (unsigned)chunks);
     if (masked)
       hipLaunchKernelGGL((k_class_nearest<CLASS_S_MASKED, true>), grid, dim3(256), 0, e->stream, (const float4 *)d_tiles,
-                         (const uint32_t *)d_mtiles, (const int32_t *)d_end, n, d, d4, (uint32_t *)d_min, (uint32_t *)d_flag);
+                         (const uint32_t *)d_mtiles, (const int32_t *)d_end, n, d, d4, d_min, d_flag);
     else
       hipLaunchKernelGGL((k_class_nearest<CLASS_S, false>), grid, dim3(256), 0, e->stream, (const float4 *)d_tiles,
-                         (const uint32_t *)nullptr, (const int32_t *)d_end, n, d, d4, (uint32_t *)d_min, (uint32_t *)d_flag);
+                         (const uint32_t *)nullptr, (const int32_t *)d_end, n, d, d4, d_min, d_flag);
   }
   HIPCHK(hipGetLastError());
   std::vector<uint32_t> hmin((size_t)n), hflag((size_t)n);

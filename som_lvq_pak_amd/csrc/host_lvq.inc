@@ -84,24 +84,20 @@ struct LvqBatch {
 
 // the engine's scratch slots behind LvqBatchBufs; the first use on an engine also raises two kernels' dynamic LDS limit
 static int lvq_batch_bufs(somhip_engine *e, int d4, LvqBatchBufs *b) {
-  void *p;
-  CHK(engine_scratch(e, SLOT_LVQ_RHO, sizeof(float) * 2 * LVQ_BMAX + 16, &p)); b->rho = (float *)p; b->xnorm = b->rho + LVQ_BMAX; b->amax_dev = b->xnorm + LVQ_BMAX;
-  CHK(engine_scratch(e, SLOT_LVQ_ADJ, sizeof(uint32_t) * LVQ_BMAX * LVQ_AW, &p)); b->adj = (uint32_t *)p;
-  CHK(engine_scratch(e, SLOT_LVQ_COMP, sizeof(int32_t) * LVQ_BMAX, &p)); b->comp_samples = (int32_t *)p;
-  CHK(engine_scratch(e, SLOT_LVQ_OUT, sizeof(LvqBatchOut), &p)); b->out = (LvqBatchOut *)p;
-  CHK(engine_scratch(e, SLOT_LVQ_STAGE_ROWS, sizeof(float4) * 2 * LVQ_BMAX * (size_t)d4, &p)); b->stage_rows = (float4 *)p;
-  CHK(engine_scratch(e, SLOT_LVQ_STAGE_ROWID, sizeof(int32_t) * 2 * LVQ_BMAX, &p)); b->stage_rowid = (int32_t *)p;
-  CHK(engine_scratch(e, SLOT_LVQ_STAGE_TA, sizeof(float) * 2 * LVQ_BMAX, &p)); b->stage_ta = (float *)p;
-  CHK(engine_scratch(e, SLOT_LVQ_CAND_LAB, sizeof(int32_t) * LVQ_BMAX * LVQ_K0, &p)); b->cand_lab = (int32_t *)p;
-  CHK(engine_scratch(e, SLOT_LVQ_CAND_TA, sizeof(float) * LVQ_BMAX * LVQ_K0, &p)); b->cand_ta = (float *)p;
-  CHK(engine_scratch(e, SLOT_LVQ_MOD, sizeof(int32_t) * (2 * LVQ_BMAX + 4), &p)); b->mod_rows = (int32_t *)p; b->mod_count = b->mod_rows + 2 * LVQ_BMAX;
+  CHK(scratch(e, SLOT_LVQ_RHO, (size_t)2 * LVQ_BMAX + 4, &b->rho)); b->xnorm = b->rho + LVQ_BMAX; b->amax_dev = b->xnorm + LVQ_BMAX;
+  CHK(scratch(e, SLOT_LVQ_ADJ, (size_t)LVQ_BMAX * LVQ_AW, &b->adj));
+  CHK(scratch(e, SLOT_LVQ_COMP, (size_t)LVQ_BMAX, &b->comp_samples));
+  CHK(scratch(e, SLOT_LVQ_OUT, 1, &b->out));
+  CHK(scratch(e, SLOT_LVQ_STAGE_ROWS, 2 * LVQ_BMAX * (size_t)d4, &b->stage_rows));
+  CHK(scratch(e, SLOT_LVQ_STAGE_ROWID, (size_t)2 * LVQ_BMAX, &b->stage_rowid));
+  CHK(scratch(e, SLOT_LVQ_STAGE_TA, (size_t)2 * LVQ_BMAX, &b->stage_ta));
+  CHK(scratch(e, SLOT_LVQ_CAND_LAB, (size_t)LVQ_BMAX * LVQ_K0, &b->cand_lab));
+  CHK(scratch(e, SLOT_LVQ_CAND_TA, (size_t)LVQ_BMAX * LVQ_K0, &b->cand_ta));
+  CHK(scratch(e, SLOT_LVQ_MOD, (size_t)2 * LVQ_BMAX + 4, &b->mod_rows)); b->mod_count = b->mod_rows + 2 * LVQ_BMAX;
   // the walk's row cache and the component kernel's adjacency rows need more dynamic LDS than the default limit
-  if (e->lvq_apply_attr_set) return 0;                    // per engine (= per device), not per process
-  HIPCHK(hipFuncSetAttribute((const void *)k_lvq_batch_apply<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LVQ_DYN_LDS));
-  HIPCHK(hipFuncSetAttribute((const void *)k_lvq_batch_apply<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LVQ_DYN_LDS));
-  HIPCHK(hipFuncSetAttribute((const void *)k_lvq_components, hipFuncAttributeMaxDynamicSharedMemorySize, LVQ_BMAX * LVQ_AW * 4));
-  e->lvq_apply_attr_set = true;
-  return 0;
+  CHK(raise_lds_limit(e, LDS_LVQ_APPLY, (const void *)k_lvq_batch_apply<false>, LVQ_DYN_LDS));
+  CHK(raise_lds_limit(e, LDS_LVQ_APPLY_MASKED, (const void *)k_lvq_batch_apply<true>, LVQ_DYN_LDS));
+  return raise_lds_limit(e, LDS_LVQ_COMPONENTS, (const void *)k_lvq_components, LVQ_BMAX * LVQ_AW * 4);
 }
 
 // ---- small jobs every LVQ entry point shares --------------------------------------------------------------------
@@ -328,15 +324,14 @@ static int lvq_train_batched(somhip_codebook *cb, somhip_dataset *ds, const somh
                              int32_t *trace_index, float *trace_diff) {
   somhip_engine *e = cb->e;
   const int64_t BMAX = LVQ_BMAX;
-  constexpr int RING = 8;
-  void *dcand, *dfin, *dst, *dctl_v;
+  constexpr int RING = LVQ_EV_RING;
+  uint64_t *dcand, *dfin; LvqStep *dst; LvqCtl *dctl;
   const bool want_trace = trace_index || trace_diff;
   const bool nowait = pl.nowait;
-  CHK(engine_scratch(e, SLOT_CALL_A, sizeof(uint64_t) * (size_t)BMAX * LVQ_K0, &dcand));
-  CHK(engine_scratch(e, SLOT_CALL_B, sizeof(LvqStep) * (size_t)BMAX, &dst));
-  CHK(engine_scratch(e, SLOT_LVQ_FINAL, sizeof(uint64_t) * 2 * (size_t)(nowait && want_trace ? std::max<int64_t>(p->count, BMAX) : BMAX), &dfin));
-  CHK(engine_scratch(e, SLOT_LVQ_CTL, sizeof(LvqCtl), &dctl_v));
-  LvqCtl *dctl = (LvqCtl *)dctl_v;
+  CHK(scratch(e, SLOT_CALL_A, (size_t)BMAX * LVQ_K0, &dcand));
+  CHK(scratch(e, SLOT_CALL_B, (size_t)BMAX, &dst));
+  CHK(scratch(e, SLOT_LVQ_FINAL, 2 * (size_t)(nowait && want_trace ? std::max<int64_t>(p->count, BMAX) : BMAX), &dfin));
+  CHK(scratch(e, SLOT_LVQ_CTL, 1, &dctl));
   LvqBatchBufs b;
   CHK(lvq_batch_bufs(e, cb->v.d4, &b));
   if (!e->lvq_hctl) HIPCHK(hipHostMalloc((void **)&e->lvq_hctl, sizeof(LvqCtl) * RING, hipHostMallocDefault));
@@ -352,7 +347,7 @@ static int lvq_train_batched(somhip_codebook *cb, somhip_dataset *ds, const somh
   auto front = [&](int64_t o, int64_t c, const LvqStep *st, uint64_t *fin, LvqBatch *bt) -> int {
     const int64_t row0 = (p->data_first + o) % ds->n;
     float *ta = pl.olvq ? b.cand_ta : (float *)nullptr;
-    CHK(scan_keys_topk<LVQ_K0>(cb, ds, row0, c, (uint64_t *)dcand, pl.knn == 2 ? 1 : 0));
+    CHK(scan_keys_topk<LVQ_K0>(cb, ds, row0, c, dcand, pl.knn == 2 ? 1 : 0));
     CHK(lvq_cand_meta(cb, (const uint64_t *)dcand, c, pl.knn, pl.olvq, b.cand_lab, ta));
     if (pl.olvq) CHK(lvq_rate_bound(e, (const uint64_t *)dcand, c, ta, p->alpha, b.amax_dev));
     *bt = {row0, (int)c, (const LvqStep *)dst, (const uint64_t *)dcand, b.cand_lab, ta, nullptr, 0,
@@ -373,7 +368,7 @@ static int lvq_train_batched(somhip_codebook *cb, somhip_dataset *ds, const somh
         CHK(pin_acquire(e, sizeof(LvqStep) * (size_t)c, &hv, &slot));
         lvq_fill_steps(ds, p, p->start_iter + launched, p->data_first + launched, c, (LvqStep *)hv);
         CHK(pin_upload(e, slot, dst, sizeof(LvqStep) * (size_t)c));
-        CHK(front(launched, c, (const LvqStep *)hv, (uint64_t *)dfin + (want_trace ? 2 * launched : 0), &bt));
+        CHK(front(launched, c, (const LvqStep *)hv, dfin + (want_trace ? 2 * launched : 0), &bt));
         const int id = next_id++;
         CHK(lvq_batch_nowait(cb, ds, pl, b, bt, dctl, id));
         HIPCHK(hipMemcpyAsync(&e->lvq_hctl[head % RING], dctl, sizeof(LvqCtl), hipMemcpyDeviceToHost, e->stream));
@@ -400,7 +395,7 @@ static int lvq_train_batched(somhip_codebook *cb, somhip_dataset *ds, const somh
     const int64_t c = std::min(B, p->count - off);
     lvq_fill_steps(ds, p, p->start_iter + off, p->data_first + off, c, hst.data());
     HIPCHK(hipMemcpyAsync(dst, hst.data(), sizeof(LvqStep) * (size_t)c, hipMemcpyHostToDevice, e->stream));
-    CHK(front(off, c, hst.data(), (uint64_t *)dfin + (nowait && want_trace ? 2 * off : 0), &bt));
+    CHK(front(off, c, hst.data(), dfin + (nowait && want_trace ? 2 * off : 0), &bt));
     int consumed = 0, reason = 0;
     CHK(lvq_batch_careful(cb, ds, pl, b, bt, &consumed, &reason));
     if (consumed <= 0)
@@ -441,13 +436,11 @@ static int lvq_train_online(somhip_codebook *cb, somhip_dataset *ds, const somhi
   const int64_t CH = 4096;
   const int nblk = (int)((cb->v.ngroups + 3) / 4);
   const bool want_trace = trace_index || trace_diff;
-  void *dpart, *dfinal, *dst;
-  CHK(engine_scratch(e, SLOT_PARTIAL, sizeof(uint64_t) * (size_t)nblk * 2 * 2, &dpart));
-  CHK(engine_scratch(e, SLOT_CALL_A, sizeof(uint64_t) * (size_t)(CH + 1) * 2, &dfinal));
-  CHK(engine_scratch(e, SLOT_CALL_B, sizeof(LvqStep) * (size_t)(CH + 1), &dst));
-  uint64_t *part[2] = {(uint64_t *)dpart, (uint64_t *)dpart + (size_t)nblk * 2};
-  uint64_t *fin = (uint64_t *)dfinal;
-  LvqStep *st = (LvqStep *)dst;
+  uint64_t *dpart, *fin; LvqStep *st;
+  CHK(scratch(e, SLOT_PARTIAL, (size_t)nblk * 2 * 2, &dpart));
+  CHK(scratch(e, SLOT_CALL_A, (size_t)(CH + 1) * 2, &fin));
+  CHK(scratch(e, SLOT_CALL_B, (size_t)(CH + 1), &st));
+  uint64_t *part[2] = {dpart, dpart + (size_t)nblk * 2};
   std::vector<LvqStep> hst((size_t)CH + 1);
   std::vector<uint64_t> hfin((size_t)(CH + 1) * 2);
   int64_t prev_row = 0;
@@ -562,8 +555,8 @@ extern "C" int somhip_debug_lvq_relation(somhip_codebook *cb, somhip_dataset *ds
   if (pl.knn == 2 && cb->v.n < 2) return fail("somhip_debug_lvq_relation: LVQ2/LVQ3 need at least two code rows");
   somhip_engine *e = cb->e;
   HIPCHK(hipSetDevice(e->device));
-  void *dcand;
-  CHK(engine_scratch(e, SLOT_CALL_A, sizeof(uint64_t) * (size_t)LVQ_BMAX * LVQ_K0, &dcand));
+  uint64_t *dcand;
+  CHK(scratch(e, SLOT_CALL_A, (size_t)LVQ_BMAX * LVQ_K0, &dcand));
   LvqBatchBufs b;
   CHK(lvq_batch_bufs(e, cb->v.d4, &b));
   const int c = (int)count;
@@ -571,7 +564,7 @@ extern "C" int somhip_debug_lvq_relation(somhip_codebook *cb, somhip_dataset *ds
   std::vector<LvqStep> hst((size_t)c);
   lvq_fill_steps(ds, p, p->start_iter, row0, c, hst.data());
   float *ta = pl.olvq ? b.cand_ta : (float *)nullptr;
-  CHK(scan_keys_topk<LVQ_K0>(cb, ds, row0, c, (uint64_t *)dcand, pl.knn == 2 ? 1 : 0));
+  CHK(scan_keys_topk<LVQ_K0>(cb, ds, row0, c, dcand, pl.knn == 2 ? 1 : 0));
   CHK(lvq_cand_meta(cb, (const uint64_t *)dcand, c, pl.knn, pl.olvq, b.cand_lab, ta));
   if (pl.olvq) CHK(lvq_rate_bound(e, (const uint64_t *)dcand, c, ta, p->alpha, b.amax_dev));
   const LvqBatch bt = {row0, c, nullptr, (const uint64_t *)dcand, b.cand_lab, ta, nullptr, 0,
@@ -684,9 +677,9 @@ extern "C" int somhip_lvq_batch_apply(somhip_codebook *cb, somhip_dataset *ds, c
   if (count == 0) return 0;
   somhip_engine *e = cb->e;
   HIPCHK(hipSetDevice(e->device));
-  void *dst, *dfin;
-  CHK(engine_scratch(e, SLOT_CALL_B, sizeof(LvqStep) * (size_t)LVQ_BMAX, &dst));
-  CHK(engine_scratch(e, SLOT_LVQ_FINAL, sizeof(uint64_t) * (size_t)LVQ_BMAX * 2, &dfin));
+  LvqStep *dst; uint64_t *dfin;
+  CHK(scratch(e, SLOT_CALL_B, (size_t)LVQ_BMAX, &dst));
+  CHK(scratch(e, SLOT_LVQ_FINAL, (size_t)LVQ_BMAX * 2, &dfin));
   LvqBatchBufs b;
   CHK(lvq_batch_bufs(e, cb->v.d4, &b));
   std::vector<LvqStep> hst((size_t)count);
@@ -696,7 +689,7 @@ extern "C" int somhip_lvq_batch_apply(somhip_codebook *cb, somhip_dataset *ds, c
   if (pl.olvq) CHK(lvq_rate_bound(e, dev_keys, count, dev_ta, p->alpha, b.amax_dev));
   const LvqBatch bt = {row0, (int)count, (const LvqStep *)dst, dev_keys, dev_lab, pl.olvq ? dev_ta : (const float *)nullptr,
                        reinterpret_cast<const float4 *>(dev_rows), xrows, pl.olvq ? 0.0f : lvq_amax_of(hst.data(), (int)count),
-                       pl.olvq ? b.amax_dev : (float *)nullptr, (uint64_t *)dfin};
+                       pl.olvq ? b.amax_dev : (float *)nullptr, dfin};
   int done = 0, reason = 0;
   CHK(lvq_batch_careful(cb, ds, pl, b, bt, &done, &reason));
   if (done <= 0) return fail("somhip_lvq_batch_apply: batch made no progress (reason %d)", reason);

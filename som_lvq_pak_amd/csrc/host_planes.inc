@@ -25,21 +25,21 @@ extern "C" int somhip_planes(somhip_codebook *cb, int first_plane, int n_planes,
   // in its own column of the table of partial keys
   const int64_t want = std::max<int64_t>(1, (int64_t)(e->n_cus > 0 ? e->n_cus : 256) * 8 / chunk_blocks);
   const int n_slabs = (int)std::min<int64_t>(cb->v.ngroups, want);
-  void *d_grey, *d_part, *d_lohi;
-  CHK(engine_scratch(e, SLOT_CALL_A, sizeof(float) * total, &d_grey));
-  CHK(engine_scratch(e, SLOT_PARTIAL, sizeof(uint64_t) * 2 * (size_t)n_planes * (size_t)n_slabs, &d_part));
-  CHK(engine_scratch(e, SLOT_CALL_B, sizeof(float) * 2 * (size_t)n_planes, &d_lohi));
-  float *d_lo = (float *)d_lohi, *d_hi = d_lo + n_planes;
+  float *d_grey, *d_lo; unsigned long long *d_part;
+  CHK(scratch(e, SLOT_CALL_A, total, &d_grey));
+  CHK(scratch(e, SLOT_PARTIAL, 2 * (size_t)n_planes * (size_t)n_slabs, &d_part));
+  CHK(scratch(e, SLOT_CALL_B, 2 * (size_t)n_planes, &d_lo));      // the planes' lo, then their hi
+  float *d_hi = d_lo + n_planes;
   const int64_t grey_blocks = (int64_t)chunk_blocks * cb->v.ngroups;
   if (grey_blocks > 0x7FFFFFFFll) return fail("somhip_planes: %lld workgroups are more than one launch takes", (long long)grey_blocks);
   hipLaunchKernelGGL(k_planes_minmax, dim3((unsigned)(chunk_blocks * n_slabs)), dim3(256), 0, e->stream, cb->v, first_plane, n_planes,
-                     chunk_blocks, n_slabs, (unsigned long long *)d_part);
+                     chunk_blocks, n_slabs, d_part);
   HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(k_planes_bounds, dim3((unsigned)((n_planes + 3) / 4)), dim3(256), 0, e->stream, cb->v, first_plane, n_planes, n_slabs,
                      (const unsigned long long *)d_part, d_lo, d_hi);
   HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(k_planes_grey, dim3((unsigned)grey_blocks), dim3(256), 0, e->stream, cb->v, first_plane, n_planes, chunk_blocks,
-                     (const float *)d_lo, (const float *)d_hi, (float *)d_grey);
+                     (const float *)d_lo, (const float *)d_hi, d_grey);
   HIPCHK(hipGetLastError());
   if (lo) HIPCHK(hipMemcpyAsync(lo, d_lo, sizeof(float) * (size_t)n_planes, hipMemcpyDeviceToHost, e->stream));
   if (hi) HIPCHK(hipMemcpyAsync(hi, d_hi, sizeof(float) * (size_t)n_planes, hipMemcpyDeviceToHost, e->stream));

@@ -27,14 +27,14 @@ static int sammon_check_codebook(const char *who, somhip_codebook *cb) {
 // the rows in unit order, row-major, in SLOT_STAGE
 static int sammon_stage_rows(somhip_codebook *cb, const float **rows) {
   somhip_engine *e = cb->e;
-  void *stage;
-  CHK(engine_scratch(e, SLOT_STAGE, sizeof(float) * (size_t)cb->v.n * cb->v.d, &stage));
+  float *stage;
+  CHK(scratch(e, SLOT_STAGE, (size_t)cb->v.n * cb->v.d, &stage));
   {
     LaunchTimer t(e, KID_LAYOUT);
-    hipLaunchKernelGGL(k_tiles_to_rows, dim3((unsigned)cb->v.ngroups), dim3(256), 0, e->stream, (float *)stage, cb->v);
+    hipLaunchKernelGGL(k_tiles_to_rows, dim3((unsigned)cb->v.ngroups), dim3(256), 0, e->stream, stage, cb->v);
   }
   HIPCHK(hipGetLastError());
-  *rows = (const float *)stage;
+  *rows = stage;
   return 0;
 }
 
@@ -42,14 +42,14 @@ static int sammon_stage_rows(somhip_codebook *cb, const float **rows) {
 static int sammon_distances(somhip_codebook *cb, const float *rows, float *D, int64_t ld, uint32_t *d_pairs, int64_t cap,
                             unsigned long long *n_zero) {
   somhip_engine *e = cb->e;
-  void *d_count;
-  CHK(engine_scratch(e, SLOT_CALL_A, sizeof(unsigned long long), &d_count));
+  unsigned long long *d_count;
+  CHK(scratch(e, SLOT_CALL_A, 1, &d_count));
   HIPCHK(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), e->stream));
   const unsigned tiles = (unsigned)((cb->v.n + SAMMON_TILE - 1) / SAMMON_TILE);
   {
     LaunchTimer t(e, KID_SAMMON_DIST);
     hipLaunchKernelGGL(k_sammon_dist, dim3(tiles, tiles), dim3(256), 0, e->stream, rows, (int)cb->v.n, cb->v.d, D, ld,
-                       d_pairs, (unsigned long long)cap, (unsigned long long *)d_count);
+                       d_pairs, (unsigned long long)cap, d_count);
   }
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(n_zero, d_count, sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
@@ -65,10 +65,10 @@ extern "C" int somhip_sammon_zero_pairs(somhip_codebook *cb, uint32_t *pairs, in
   if (!pairs) cap = 0;
   const float *rows;
   CHK(sammon_stage_rows(cb, &rows));
-  void *d_pairs = nullptr;
-  if (cap > 0) CHK(engine_scratch(e, SLOT_PAIRS, sizeof(uint32_t) * 2 * (size_t)cap, &d_pairs));
+  uint32_t *d_pairs = nullptr;
+  if (cap > 0) CHK(scratch(e, SLOT_PAIRS, 2 * (size_t)cap, &d_pairs));
   unsigned long long found = 0;
-  CHK(sammon_distances(cb, rows, nullptr, 0, (uint32_t *)d_pairs, cap, &found));
+  CHK(sammon_distances(cb, rows, nullptr, 0, d_pairs, cap, &found));
   *n_pairs = (int64_t)found;
   const int64_t have = std::min<int64_t>((int64_t)found, cap);
   if (have > 0) {

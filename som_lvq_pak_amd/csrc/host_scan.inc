@@ -149,23 +149,22 @@ static int bind_prefilter(somhip_codebook *cb, const ScanPlan &p, bool exchange,
     HIPCHK(hipMalloc((void **)&cb->d_clo, sizeof(uint4) * (size_t)ng * p.d8 * WAVE));
   }
   *b = PrefilterBufs{};
-  void *q;
-  CHK(engine_scratch(e, SLOT_TAU, sizeof(float) * (size_t)bpad, &q)); b->tau = (float *)q;
-  CHK(engine_scratch(e, SLOT_WMIN, sizeof(float) * (size_t)ng * bpad, &q)); b->wmin = (float *)q;
-  CHK(engine_scratch(e, SLOT_WMASK, sizeof(uint64_t) * (size_t)ng * bpad, &q)); b->wmask = (uint64_t *)q;
+  CHK(scratch(e, SLOT_TAU, (size_t)bpad, &b->tau));
+  CHK(scratch(e, SLOT_WMIN, (size_t)ng * bpad, &b->wmin));
+  CHK(scratch(e, SLOT_WMASK, (size_t)ng * bpad, &b->wmask));
   const size_t xt_bytes = p.bf16 ? 2 * sizeof(uint4) * (size_t)p.nsb * p.d8 * 32 : sizeof(float4) * (size_t)p.nsb * cb->v.d4 * SCAN_S;
   CHK(engine_scratch(e, SLOT_SAMPLES, xt_bytes, &b->xt));
   b->xhi = (uint4 *)b->xt;
   b->xlo = b->xhi + (size_t)p.nsb * p.d8 * 32;
-  CHK(engine_scratch(e, SLOT_RERANK_COUNT, sizeof(uint32_t) * (2 * (size_t)bpad + 4 * (size_t)(bpad / 32)), &q)); b->gmin = (uint32_t *)q;
+  CHK(scratch(e, SLOT_RERANK_COUNT, 2 * (size_t)bpad + 4 * (size_t)(bpad / 32), &b->gmin));
   b->gcount = b->gmin + bpad;
   b->colcount = b->gcount + bpad;
-  b->paircount = reinterpret_cast<uint32_t *>(e->d_stats + 6);   // stays 0 unless a segment overflows
-  if (exchange) { CHK(engine_scratch(e, SLOT_XBOUND, sizeof(float) * 3 * (size_t)bpad, &q)); b->xw = (float *)q; }
+  b->paircount = reinterpret_cast<uint32_t *>(e->d_stats + STAT_PAIR_OVERFLOW);   // stays 0 unless a segment overflows
+  if (exchange) CHK(scratch(e, SLOT_XBOUND, 3 * (size_t)bpad, &b->xw));
   if (p.route == ROUTE_TWO_LEVEL) {
-    CHK(engine_scratch(e, SLOT_SAMPLE_ROWS, xt_bytes, &q)); b->xrow = (uint4 *)q;
-    CHK(engine_scratch(e, SLOT_L2_STATE, sizeof(float) * (size_t)bpad + sizeof(uint32_t) * ((size_t)bpad + (size_t)ng), &q)); b->tau1 = (float *)q;
-    CHK(engine_scratch(e, SLOT_L2_LIST, sizeof(uint16_t) * (size_t)ng * bpad, &q)); b->l2list = (uint16_t *)q;
+    CHK(scratch(e, SLOT_SAMPLE_ROWS, xt_bytes / sizeof(uint4), &b->xrow));      // (two levels: bf16 tiles)
+    CHK(scratch(e, SLOT_L2_STATE, 2 * (size_t)bpad + (size_t)ng, &b->tau1));    // 32-bit words: tau1 | gmin1 | l2cnt
+    CHK(scratch(e, SLOT_L2_LIST, (size_t)ng * bpad, &b->l2list));
     b->gmin1 = reinterpret_cast<uint32_t *>(b->tau1 + bpad);
     b->l2cnt = b->gmin1 + bpad;
   }
@@ -216,10 +215,7 @@ static int pf_prepare(somhip_codebook *cb, somhip_dataset *ds, int64_t first, in
       if (want_rm && !cb->d_rowmajor) HIPCHK(hipMalloc((void **)&cb->d_rowmajor, sizeof(float) * (size_t)cb->v.ngroups * WAVE * cb->v.d));
       const int prep_threads = d8 >= 16 ? 1024 : d8 >= 4 ? 256 : 64;
       if (want_rm) {
-        if (!e->prep_rm_attr_set) {
-          HIPCHK(hipFuncSetAttribute((const void *)k_prep_codes_bf16<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PREP_RM_LDS(16)));
-          e->prep_rm_attr_set = true;
-        }
+        CHK(raise_lds_limit(e, LDS_PREP_ROWMAJOR, (const void *)k_prep_codes_bf16<true>, PREP_RM_LDS(16)));
         hipLaunchKernelGGL(k_prep_codes_bf16<true>, dim3((unsigned)cb->v.ngroups), dim3(prep_threads), PREP_RM_LDS(prep_threads / 64),
                            e->stream, cb->v, d8, cb->d_cn, cnmax, cb->d_chi, cb->d_clo, cb->d_rowmajor);
       } else
@@ -259,10 +255,7 @@ static int pf_level1(somhip_codebook *cb, int64_t count, const ScanPlan &p, cons
       dim3 gridw((unsigned)((nsb + 7) / 8), (unsigned)((ng + 3) / 4));
       if (p.l1_ring) {
         // persistent form over an LDS ring (kernels/prefilter_l1_ring.hpp): one workgroup per CU, a multiple of 8 of them
-        if (!e->l1r_attr_set) {
-          HIPCHK(hipFuncSetAttribute((const void *)k_dist_mfma_bf16_l1r, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L1R_LDS_BYTES));
-          e->l1r_attr_set = true;
-        }
+        CHK(raise_lds_limit(e, LDS_L1_RING, (const void *)k_dist_mfma_bf16_l1r, L1R_LDS_BYTES));
         if (!e->n_cus) {
           int v = 0;
           HIPCHK(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, e->device));
@@ -317,19 +310,16 @@ static int pf_level2(somhip_codebook *cb, int64_t count, const ScanPlan &p, cons
     uint32_t *l2_gmin = fused_gmin ? b.gmin : nullptr;
     if (!p.l2_global) {
       const size_t a_bytes = sizeof(uint4) * 2 * (size_t)d8 * 64;
-      if (!e->l2_lds_attr_set) {
-        HIPCHK(hipFuncSetAttribute((const void *)k_dist_l2_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-        e->l2_lds_attr_set = true;
-      }
+      CHK(raise_lds_limit(e, LDS_DIST_L2, (const void *)k_dist_l2_lds, 128 * 1024));
       hipLaunchKernelGGL(k_dist_l2_lds, dim3((unsigned)ng, 4), dim3(64 * L2_WAVES), a_bytes, e->stream, cb->v, d8, (const uint4 *)cb->d_chi,
                          (const uint4 *)cb->d_clo, (const uint4 *)b.xrow, (const float *)cb->d_cn,
                          (const float *)b.tau, bpad, (const uint32_t *)b.l2cnt, (const uint16_t *)b.l2list, b.wmin,
-                         b.wmask, e->d_stats + 8 + 128 + 8, l2_gmin);
+                         b.wmask, e->d_stats + STAT_L2_PAIRS, l2_gmin);
     } else
       hipLaunchKernelGGL(k_dist_l2, dim3((unsigned)ng, 8), dim3(256), 0, e->stream, cb->v, d8, (const uint4 *)cb->d_chi,
                          (const uint4 *)cb->d_clo, (const uint4 *)b.xhi, (const uint4 *)b.xlo, (const float *)cb->d_cn,
                          (const float *)b.tau, bpad, (const uint32_t *)b.l2cnt, (const uint16_t *)b.l2list, b.wmin,
-                         b.wmask, e->d_stats + 8 + 128 + 8, (const uint4 *)b.xrow, l2_gmin);
+                         b.wmask, e->d_stats + STAT_L2_PAIRS, (const uint4 *)b.xrow, l2_gmin);
   }
   HIPCHK(hipGetLastError());
   if (xbound) {
@@ -368,6 +358,14 @@ static int pf_filter(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int
   CHK(pf_level1(cb, count, p, *b, nullptr));
   return pf_level2(cb, count, p, *b, fused_gmin, nullptr);
 }
+// the nearest-row re-rank's pair list (SLOT_PAIRS): a segment of cap_col pairs per 32-sample column, cap pairs in all
+struct RerankPairs { uint2 *pairs; uint32_t ncols, cap_col, cap; };
+static int bind_rerank_pairs(somhip_engine *e, int64_t bpad, RerankPairs *r) {
+  r->ncols = (uint32_t)(bpad / 32);
+  r->cap_col = 16384;   // 512 per sample on average; a full segment -> K2r
+  r->cap = (uint32_t)std::min<int64_t>((int64_t)r->ncols * r->cap_col, 0x7FFFFFF0);
+  return scratch(e, SLOT_PAIRS, (size_t)r->ncols * r->cap_col + 2, &r->pairs);   // (16 spare bytes)
+}
 // the nearest-row re-rank: row-granular pairs for the usual few candidates (a segment per 32-sample column), k_rerank
 // for flagged samples.  gmin_ready: the per-sample minimum is formed (else k_group_min).  xbound (shard exchange): the
 // rows of the groups whose three-product minimum is <= (MIN over the shards of their bounds) + delta3.
@@ -376,11 +374,8 @@ static int pf_rerank(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int
                      const PrefilterBufs &b, uint64_t *d_keys, bool gmin_ready, const float *xbound, bool from_lists) {
   somhip_engine *e = cb->e;
   const int64_t ng = cb->v.ngroups, bpad = p.bpad;
-  const uint32_t ncols = (uint32_t)(bpad / 32);
-  const uint32_t cap_col = 16384;   // 512 per sample on average; a full segment -> K2r
-  const uint32_t cap = (uint32_t)std::min<int64_t>((int64_t)ncols * cap_col, 0x7FFFFFF0);
-  void *dpairs;
-  CHK(engine_scratch(e, SLOT_PAIRS, sizeof(uint2) * (size_t)ncols * cap_col + 16, &dpairs));
+  RerankPairs pl;
+  CHK(bind_rerank_pairs(e, bpad, &pl));
   {
     int64_t chunk;
     const dim3 sgrid = group_chunks(ng, bpad, 128, &chunk);
@@ -391,23 +386,23 @@ static int pf_rerank(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int
     if (from_lists)
       hipLaunchKernelGGL(k_rerank_select_lists, dim3((unsigned)ng, 4), dim3(256), 0, e->stream, cb->v, count, bpad,
                          (const uint32_t *)b.l2cnt, (const uint16_t *)b.l2list, (const float *)b.wmin, (const uint64_t *)b.wmask, win,
-                         (const uint32_t *)b.gmin, b.gcount, cap, cap_col, (uint2 *)dpairs, b.colcount, b.paircount, xbound);
+                         (const uint32_t *)b.gmin, b.gcount, pl.cap, pl.cap_col, pl.pairs, b.colcount, b.paircount, xbound);
     else
       hipLaunchKernelGGL(k_rerank_select, sgrid, dim3(256), 0, e->stream, cb->v, count, bpad, chunk,
                          (const float *)b.wmin, (const uint64_t *)b.wmask, win,
-                         (const uint32_t *)b.gmin, b.gcount, cap, cap_col, (uint2 *)dpairs, b.colcount, b.paircount, e->d_stats, xbound);
+                         (const uint32_t *)b.gmin, b.gcount, pl.cap, pl.cap_col, pl.pairs, b.colcount, b.paircount, e->d_stats, xbound);
   }
   {
     LaunchTimer t(e, KID_RERANK_PAIRS);
     hipLaunchKernelGGL(k_rerank_pairs, dim3(4096), dim3(256), 0, e->stream, cb->v, ds->d_rows,
-                       ds->n, first, cap, cap_col, (int)ncols, (const uint2 *)dpairs, (const uint32_t *)b.colcount,
+                       ds->n, first, pl.cap, pl.cap_col, (int)pl.ncols, (const uint2 *)pl.pairs, (const uint32_t *)b.colcount,
                        (const uint32_t *)b.paircount, d_keys, e->d_stats,
                        p.bf16 && cb->prep_valid && cb->rowmajor_valid ? (const float *)cb->d_rowmajor : (const float *)nullptr);
   }
   LaunchTimer t(e, KID_RERANK);
   hipLaunchKernelGGL(k_rerank, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, e->stream, cb->v,
                      ds->d_rows, ds->n, first, count, bpad, (const float *)b.wmin,
-                     (const uint64_t *)b.wmask, (const float *)b.tau, (const uint32_t *)b.paircount, cap, d_keys,
+                     (const uint64_t *)b.wmask, (const float *)b.tau, (const uint32_t *)b.paircount, pl.cap, d_keys,
                      e->d_stats);
   HIPCHK(hipGetLastError());
   return 0;
@@ -417,12 +412,12 @@ template <int K>
 static int scan_exact(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count, const ScanPlan &p,
                       int tie_knn, uint64_t *keys, uint64_t *part) {
   somhip_engine *e = cb->e;
-  void *xt;
-  CHK(engine_scratch(e, SLOT_SAMPLES, sizeof(float4) * (size_t)p.nsb * cb->v.d4 * SCAN_S, &xt));
+  float4 *xt;
+  CHK(scratch(e, SLOT_SAMPLES, (size_t)p.nsb * cb->v.d4 * SCAN_S, &xt));
   {
     LaunchTimer t(e, KID_PACK_SAMPLES);
     hipLaunchKernelGGL(k_pack_samples<SCAN_S>, dim3((unsigned)p.nsb), dim3(256), 0, e->stream,
-                       ds->d_rows, ds->n, ds->d, cb->v.d4, first, count, (float4 *)xt);
+                       ds->d_rows, ds->n, ds->d, cb->v.d4, first, count, xt);
   }
   HIPCHK(hipGetLastError());
   LaunchTimer t(e, KID_SCAN_EXACT);
@@ -462,6 +457,20 @@ static int scan_keys_top1(somhip_codebook *cb, somhip_dataset *ds, int64_t first
   CHK(pf_filter(cb, ds, first, count, p, &b, d_keys, nonneg_keys != nullptr, p.fused_gmin));
   return pf_rerank(cb, ds, first, count, p, b, d_keys, p.fused_gmin, nullptr, p.route == ROUTE_TWO_LEVEL);
 }
+// the by-group top-K re-rank's buffers, carved from SLOT_TOPK_GROUPS with the counts and the pass counter zeroed:
+// [lists of the groups][their counts][the pass counter, padded][the passes: at most one per filed sample]
+struct TopkGroupBufs { uint2 *glist; uint32_t *gcnt, *wcount; uint2 *work; };
+static int bind_topk_groups(somhip_engine *e, int64_t ngroups, uint32_t cap_g, uint32_t cap, TopkGroupBufs *g) {
+  const size_t words = (size_t)ngroups + 4 + (ngroups & 1);   // counts and counter, padded to whole uint2s
+  void *p;
+  CHK(engine_scratch(e, SLOT_TOPK_GROUPS, sizeof(uint2) * (size_t)ngroups * cap_g + sizeof(uint32_t) * words + sizeof(uint2) * (size_t)cap, &p));
+  g->glist = (uint2 *)p;
+  g->gcnt = reinterpret_cast<uint32_t *>(g->glist + (size_t)ngroups * cap_g);
+  g->wcount = g->gcnt + ngroups;
+  g->work = reinterpret_cast<uint2 *>(g->gcnt + words);
+  HIPCHK(hipMemsetAsync(g->gcnt, 0, sizeof(uint32_t) * ((size_t)ngroups + 4), e->stream));
+  return 0;
+}
 template <int K>
 static int scan_keys_topk(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count,
                           uint64_t *d_keys /*[count][K]*/, int tie_knn = 1) {
@@ -469,15 +478,15 @@ static int scan_keys_topk(somhip_codebook *cb, somhip_dataset *ds, int64_t first
   const ScanPlan p = scan_plan(cb, ds, count, K);
   if (p.route == ROUTE_MASKED || p.route == ROUTE_DIRECT) {
     const int nblk = (int)((cb->v.ngroups + 3) / 4);
-    void *part;
-    CHK(engine_scratch(e, SLOT_PARTIAL, sizeof(uint64_t) * (size_t)count * nblk * K, &part));
+    uint64_t *part;
+    CHK(scratch(e, SLOT_PARTIAL, (size_t)count * nblk * K, &part));
     if (p.route == ROUTE_MASKED)
       CHK(masked_columns(e, ds, first, count, [&](int64_t off, int64_t f, int64_t c) {
         hipLaunchKernelGGL(k_scan_masked_topk<K>, dim3((unsigned)nblk, (unsigned)c), dim3(256), 0, e->stream, cb->v, ds->d_rows,
-                           (const uint8_t *)ds->d_mask, ds->n, f, tie_knn, (uint64_t *)part + (size_t)off * nblk * K);
+                           (const uint8_t *)ds->d_mask, ds->n, f, tie_knn, part + (size_t)off * nblk * K);
       }));
     else
-      CHK(scan_exact<K>(cb, ds, first, count, p, tie_knn, (uint64_t *)nullptr, (uint64_t *)part));
+      CHK(scan_exact<K>(cb, ds, first, count, p, tie_knn, (uint64_t *)nullptr, part));
     LaunchTimer t(e, KID_MERGE_TOPK);
     hipLaunchKernelGGL(k_merge_topk<K>, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, e->stream,
                        (const uint64_t *)part, nblk, count, d_keys);
@@ -488,11 +497,11 @@ static int scan_keys_topk(somhip_codebook *cb, somhip_dataset *ds, int64_t first
   CHK(pf_filter(cb, ds, first, count, p, &b, nullptr, false, false));
   // pair-parallel re-rank (three launches); the one-wave-per-sample kernel only if the list overflows
   const uint32_t cap = (uint32_t)std::min<int64_t>(count * 128 + 4096, 0x3FFFFFF0);
-  void *dpairs, *dspan, *dpart;
-  CHK(engine_scratch(e, SLOT_PAIRS, sizeof(uint2) * (size_t)cap, &dpairs));
-  CHK(engine_scratch(e, SLOT_PARTIAL, sizeof(uint64_t) * (size_t)cap * K, &dpart));
-  CHK(engine_scratch(e, SLOT_TOPK_SPAN, sizeof(TopkSpan) * (size_t)count + 16, &dspan));
-  uint32_t *dcounter = reinterpret_cast<uint32_t *>(e->d_stats + 7);
+  uint2 *dpairs; TopkSpan *dspan; uint64_t *dpart;
+  CHK(scratch(e, SLOT_PAIRS, (size_t)cap, &dpairs));
+  CHK(scratch(e, SLOT_PARTIAL, (size_t)cap * K, &dpart));
+  CHK(scratch(e, SLOT_TOPK_SPAN, (size_t)count + 2, &dspan));   // (16 spare bytes)
+  uint32_t *dcounter = reinterpret_cast<uint32_t *>(e->d_stats + STAT_TOPK_LIST);
   HIPCHK(hipMemsetAsync(dcounter, 0, 2 * sizeof(uint32_t), e->stream));
   LaunchTimer t(e, KID_RERANK);
   // pairs filed by row group (scan_plan: by_group): the group's tile is then streamed once per four samples
@@ -501,34 +510,23 @@ static int scan_keys_topk(somhip_codebook *cb, somhip_dataset *ds, int64_t first
   // (then a crowded group sends the run to the overflow path)
   const uint32_t cap_g = (uint64_t)cb->v.ngroups * (uint64_t)count <= (8ull << 20)
                              ? (uint32_t)count : (uint32_t)std::max<uint64_t>(64, (8ull << 20) / (uint64_t)cb->v.ngroups);
-  uint32_t *dgcnt = nullptr, *dwcount = nullptr;
-  uint2 *dglist = nullptr, *dwork = nullptr;
-  if (by_group) {
-    void *pg;
-    // [lists of the groups][their counts][the pass counter, padded][the passes: at most one per filed sample]
-    CHK(engine_scratch(e, SLOT_TOPK_GROUPS, sizeof(uint2) * (size_t)cb->v.ngroups * cap_g + sizeof(uint32_t) * ((size_t)cb->v.ngroups + 4 + (cb->v.ngroups & 1)) +
-                                            sizeof(uint2) * (size_t)cap, &pg));
-    dglist = (uint2 *)pg;
-    dgcnt = reinterpret_cast<uint32_t *>(dglist + (size_t)cb->v.ngroups * cap_g);
-    dwcount = dgcnt + cb->v.ngroups;
-    dwork = reinterpret_cast<uint2 *>(dgcnt + cb->v.ngroups + 4 + (cb->v.ngroups & 1));
-    HIPCHK(hipMemsetAsync(dgcnt, 0, sizeof(uint32_t) * ((size_t)cb->v.ngroups + 4), e->stream));
-  }
+  TopkGroupBufs g{};
+  if (by_group) CHK(bind_topk_groups(e, cb->v.ngroups, cap_g, cap, &g));
   hipLaunchKernelGGL(k_topk_select<K>, dim3((unsigned)((count + TOPK_NB - 1) / TOPK_NB)), dim3(1024), 0, e->stream, cb->v, count, p.bpad,
-                     (const float *)b.wmin, (const float *)b.tau, cap, (uint2 *)dpairs, (TopkSpan *)dspan, dcounter, dgcnt, dglist, cap_g);
+                     (const float *)b.wmin, (const float *)b.tau, cap, dpairs, dspan, dcounter, g.gcnt, g.glist, cap_g);
   if (by_group) {
     hipLaunchKernelGGL(k_topk_worklist<4>, dim3((unsigned)std::min<int64_t>((cb->v.ngroups + 255) / 256, 256)), dim3(256), 0, e->stream,
-                       cb->v.ngroups, (const uint32_t *)dgcnt, cap_g, (const uint32_t *)dcounter, dwcount, dwork, cap);
+                       cb->v.ngroups, (const uint32_t *)g.gcnt, cap_g, (const uint32_t *)dcounter, g.wcount, g.work, cap);
     hipLaunchKernelGGL(k_topk_pairs_bygroup<K>, dim3(8192), dim3(64), 0, e->stream, cb->v, ds->d_rows, ds->n,
-                       first, tie_knn, (const uint32_t *)dgcnt, (const uint2 *)dglist, cap_g, (const uint32_t *)dcounter,
-                       (const uint32_t *)dwcount, (const uint2 *)dwork, cap, (uint64_t *)dpart);
+                       first, tie_knn, (const uint32_t *)g.gcnt, (const uint2 *)g.glist, cap_g, (const uint32_t *)dcounter,
+                       (const uint32_t *)g.wcount, (const uint2 *)g.work, cap, dpart);
   }
   else
     hipLaunchKernelGGL(k_topk_pairs<K>, dim3(1024), dim3(256), 0, e->stream, cb->v, ds->d_rows, ds->n, first, tie_knn,
-                       (const uint2 *)dpairs, (const uint32_t *)dcounter, (uint64_t *)dpart);
+                       (const uint2 *)dpairs, (const uint32_t *)dcounter, dpart);
   hipLaunchKernelGGL(k_topk_merge<K>, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, e->stream, count,
                      (const TopkSpan *)dspan, (const uint64_t *)dpart, (const uint32_t *)dcounter, d_keys,
-                     e->d_stats + 8 + 128 + 8 + 1);
+                     e->d_stats + STAT_TOPK_PAIRS);
   // list full (dcounter[1] != 0, seen on the device: no host round trip): every sample through the one-wave kernel
   hipLaunchKernelGGL(k_rerank_topk<K>, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, e->stream, cb->v, ds->d_rows,
                      ds->n, first, count, p.bpad, (const float *)b.wmin, (const float *)b.tau, tie_knn, d_keys,
@@ -644,30 +642,29 @@ extern "C" int somhip_debug_rerank_pairs(somhip_codebook *cb, somhip_dataset *ds
   if (p.route != ROUTE_ONE_LEVEL && p.route != ROUTE_TWO_LEVEL) return fail("somhip_debug_rerank_pairs: no pre-filter for this search");
   if (from_lists && p.route != ROUTE_TWO_LEVEL) return fail("somhip_debug_rerank_pairs: no level-2 lists on the one-level route");
   HIPCHK(hipSetDevice(e->device));
-  void *dk;
-  CHK(engine_scratch(e, SLOT_CALL_A, sizeof(uint64_t) * (size_t)count, &dk));
+  uint64_t *dk;
+  CHK(scratch(e, SLOT_CALL_A, (size_t)count, &dk));
   e->samples_searched += (uint64_t)count;
   PrefilterBufs b;
-  CHK(pf_filter(cb, ds, first, count, p, &b, (uint64_t *)dk, false, p.fused_gmin));
-  CHK(pf_rerank(cb, ds, first, count, p, b, (uint64_t *)dk, p.fused_gmin, nullptr, from_lists != 0));
+  CHK(pf_filter(cb, ds, first, count, p, &b, dk, false, p.fused_gmin));
+  CHK(pf_rerank(cb, ds, first, count, p, b, dk, p.fused_gmin, nullptr, from_lists != 0));
   const size_t cells = (size_t)cb->v.ngroups * p.bpad;
-  const uint32_t ncols = (uint32_t)(p.bpad / 32), cap_col = 16384;     // (pf_rerank's segments)
-  void *dpairs;
-  CHK(engine_scratch(e, SLOT_PAIRS, sizeof(uint2) * (size_t)ncols * cap_col + 16, &dpairs));
+  RerankPairs pl;                                  // the list pf_rerank filled
+  CHK(bind_rerank_pairs(e, p.bpad, &pl));
   HIPCHK(hipMemcpyAsync(wmin, b.wmin, sizeof(float) * cells, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipMemcpyAsync(wmask, b.wmask, sizeof(uint64_t) * cells, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipMemcpyAsync(gmin, b.gmin, sizeof(uint32_t) * (size_t)p.bpad, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipMemcpyAsync(tau, b.tau, sizeof(float) * (size_t)count, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipMemcpyAsync(colcount, b.colcount, sizeof(uint32_t) * 4 * (size_t)ncols, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipMemcpyAsync(colcount, b.colcount, sizeof(uint32_t) * 4 * (size_t)pl.ncols, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipMemcpyAsync(overflow, b.paircount, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipMemcpyAsync(keys, dk, sizeof(uint64_t) * (size_t)count, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
   // the segments' filled parts, one after another
   int64_t total = 0;
-  for (uint32_t c = 0; c < ncols; c++) {
-    const int64_t n = std::min<uint32_t>(colcount[c], cap_col);
+  for (uint32_t c = 0; c < pl.ncols; c++) {
+    const int64_t n = std::min<uint32_t>(colcount[c], pl.cap_col);
     if (total + n > pairs_cap) return fail("somhip_debug_rerank_pairs: %lld pairs and more, room for %lld", (long long)(total + n), (long long)pairs_cap);
-    if (n) HIPCHK(hipMemcpyAsync(pairs + 2 * total, (const uint2 *)dpairs + (size_t)c * cap_col, sizeof(uint2) * (size_t)n, hipMemcpyDeviceToHost, e->stream));
+    if (n) HIPCHK(hipMemcpyAsync(pairs + 2 * total, pl.pairs + (size_t)c * pl.cap_col, sizeof(uint2) * (size_t)n, hipMemcpyDeviceToHost, e->stream));
     total += n;
   }
   HIPCHK(hipStreamSynchronize(e->stream));
@@ -791,14 +788,14 @@ extern "C" int somhip_find_winners(somhip_codebook *cb, somhip_dataset *ds, int6
   const int64_t CH = 4096;
   return with_topk_width(knn, nullptr, [&](auto width) {
     constexpr int KK = decltype(width)::value;
-    void *dk;
-    CHK(engine_scratch(e, SLOT_CALL_A, sizeof(uint64_t) * (size_t)std::min(CH, count) * KK, &dk));
+    uint64_t *dk;
+    CHK(scratch(e, SLOT_CALL_A, (size_t)std::min(CH, count) * KK, &dk));
     std::vector<uint64_t> hk((size_t)std::min(CH, count) * KK);
     for (int64_t off = 0; off < count; off += CH) {
       int64_t c = std::min(CH, count - off);
       int64_t f = (first + off) % ds->n;
-      if constexpr (KK == 1) CHK(scan_keys_top1(cb, ds, f, c, (uint64_t *)dk));
-      else CHK(scan_keys_topk<KK>(cb, ds, f, c, (uint64_t *)dk));
+      if constexpr (KK == 1) CHK(scan_keys_top1(cb, ds, f, c, dk));
+      else CHK(scan_keys_topk<KK>(cb, ds, f, c, dk));
       HIPCHK(hipMemcpyAsync(hk.data(), dk, sizeof(uint64_t) * (size_t)c * KK, hipMemcpyDeviceToHost, e->stream));
       HIPCHK(hipStreamSynchronize(e->stream));
       for (int64_t i = 0; i < c; i++) {
@@ -825,11 +822,11 @@ extern "C" int somhip_column_sums(somhip_dataset *ds, float *sum, int64_t *count
   if (!ds->e) return fail("somhip_column_sums: the engine of this data set was destroyed");
   somhip_engine *e = ds->e;
   HIPCHK(hipSetDevice(e->device));
-  void *dsum, *dcnt;
-  CHK(engine_scratch(e, SLOT_CALL_A, sizeof(float) * (size_t)ds->d, &dsum));
-  CHK(engine_scratch(e, SLOT_CALL_B, sizeof(unsigned long long) * (size_t)ds->d, &dcnt));
+  float *dsum; unsigned long long *dcnt;
+  CHK(scratch(e, SLOT_CALL_A, (size_t)ds->d, &dsum));
+  CHK(scratch(e, SLOT_CALL_B, (size_t)ds->d, &dcnt));
   hipLaunchKernelGGL(k_column_sums, dim3((unsigned)((ds->d + 255) / 256)), dim3(256), 0, e->stream, ds->d_rows,
-                     (const uint8_t *)ds->d_mask, ds->n, ds->d, (float *)dsum, (unsigned long long *)dcnt);
+                     (const uint8_t *)ds->d_mask, ds->n, ds->d, dsum, dcnt);
   HIPCHK(hipGetLastError());
   std::vector<unsigned long long> hc((size_t)ds->d);
   HIPCHK(hipMemcpyAsync(sum, dsum, sizeof(float) * (size_t)ds->d, hipMemcpyDeviceToHost, e->stream));
@@ -845,14 +842,14 @@ extern "C" int somhip_centered_products(somhip_dataset *ds, const float *mean, f
   somhip_engine *e = ds->e;
   HIPCHK(hipSetDevice(e->device));
   const size_t dd = (size_t)ds->d * ds->d;
-  void *dmean, *dr;
-  CHK(engine_scratch(e, SLOT_CALL_A, sizeof(float) * (size_t)ds->d, &dmean));
-  CHK(engine_scratch(e, SLOT_CALL_B, sizeof(float) * dd, &dr));
+  float *dmean, *dr;
+  CHK(scratch(e, SLOT_CALL_A, (size_t)ds->d, &dmean));
+  CHK(scratch(e, SLOT_CALL_B, dd, &dr));
   HIPCHK(hipMemcpyAsync(dmean, mean, sizeof(float) * (size_t)ds->d, hipMemcpyHostToDevice, e->stream));
   HIPCHK(hipMemsetAsync(dr, 0, sizeof(float) * dd, e->stream));
   const unsigned nb = (unsigned)((ds->d + 15) / 16);
   hipLaunchKernelGGL(k_centered_products, dim3(nb, nb), dim3(256), 0, e->stream, ds->d_rows,
-                     (const uint8_t *)ds->d_mask, ds->n, ds->d, (const float *)dmean, (float *)dr);
+                     (const uint8_t *)ds->d_mask, ds->n, ds->d, (const float *)dmean, dr);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(r, dr, sizeof(float) * dd, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
@@ -867,22 +864,21 @@ extern "C" int somhip_column_minmax(somhip_dataset *ds, float *lo, float *hi, in
   if (!ds->e) return fail("somhip_column_minmax: the engine of this data set was destroyed");
   somhip_engine *e = ds->e;
   HIPCHK(hipSetDevice(e->device));
-  void *dmm, *dcnt;
-  CHK(engine_scratch(e, SLOT_CALL_A, sizeof(uint32_t) * 2 * (size_t)ds->d, &dmm));
-  CHK(engine_scratch(e, SLOT_CALL_B, sizeof(unsigned long long) * (size_t)ds->d, &dcnt));
-  uint32_t *dmin = (uint32_t *)dmm, *dmax = dmin + ds->d;
+  uint32_t *dmin; unsigned long long *dcnt;
+  CHK(scratch(e, SLOT_CALL_A, 2 * (size_t)ds->d, &dmin));      // the minima, then the maxima
+  CHK(scratch(e, SLOT_CALL_B, (size_t)ds->d, &dcnt));
+  uint32_t *dmax = dmin + ds->d;
   HIPCHK(hipMemsetAsync(dmin, 0xFF, sizeof(uint32_t) * (size_t)ds->d, e->stream));
   HIPCHK(hipMemsetAsync(dmax, 0, sizeof(uint32_t) * (size_t)ds->d, e->stream));
   HIPCHK(hipMemsetAsync(dcnt, 0, sizeof(unsigned long long) * (size_t)ds->d, e->stream));
   const int64_t nblk = std::max<int64_t>(1, std::min<int64_t>(2048, (ds->n + 255) / 256));
   const int64_t per = (ds->n + nblk - 1) / nblk;
   hipLaunchKernelGGL(k_column_minmax, dim3((unsigned)((ds->d + 255) / 256), (unsigned)((ds->n + per - 1) / per)), dim3(256), 0,
-                     e->stream, ds->d_rows, (const uint8_t *)ds->d_mask, ds->n, ds->d, per, dmin, dmax,
-                     (unsigned long long *)dcnt);
+                     e->stream, ds->d_rows, (const uint8_t *)ds->d_mask, ds->n, ds->d, per, dmin, dmax, dcnt);
   HIPCHK(hipGetLastError());
   std::vector<uint32_t> hm(2 * (size_t)ds->d);
   std::vector<unsigned long long> hc((size_t)ds->d);
-  HIPCHK(hipMemcpyAsync(hm.data(), dmm, sizeof(uint32_t) * 2 * (size_t)ds->d, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipMemcpyAsync(hm.data(), dmin, sizeof(uint32_t) * 2 * (size_t)ds->d, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipMemcpyAsync(hc.data(), dcnt, sizeof(unsigned long long) * (size_t)ds->d, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
   auto back = [](uint32_t o) { uint32_t b = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o; float f; memcpy(&f, &b, 4); return f; };
@@ -910,16 +906,16 @@ extern "C" int somhip_qerror2(somhip_codebook *cb, somhip_dataset *ds, float rad
   double reach = radius > 0.0f ? (double)radius / (cb->v.topol == SOMHIP_TOPOL_RECT ? 1.0 : 0.8660254037844386) + 1.0 : 1.0;
   const int ireach = reach > 1e6 ? 1000000 : (int)reach;
   const int64_t CH = 4096;
-  void *dk, *dq;
-  CHK(engine_scratch(e, SLOT_CALL_A, sizeof(uint64_t) * (size_t)std::min(CH, count), &dk));
-  CHK(engine_scratch(e, SLOT_CALL_B, sizeof(float) * (size_t)std::min(CH, count), &dq));
+  uint64_t *dk; float *dq;
+  CHK(scratch(e, SLOT_CALL_A, (size_t)std::min(CH, count), &dk));
+  CHK(scratch(e, SLOT_CALL_B, (size_t)std::min(CH, count), &dq));
   const size_t dyn = (size_t)cb->v.d * 5 + 16;
   for (int64_t off = 0; off < count; off += CH) {
     const int64_t c = std::min(CH, count - off);
     const int64_t f = (first + off) % ds->n;
-    CHK(scan_keys_top1(cb, ds, f, c, (uint64_t *)dk));
+    CHK(scan_keys_top1(cb, ds, f, c, dk));
     hipLaunchKernelGGL(gauss ? k_qerror2<true> : k_qerror2<false>, dim3((unsigned)c), dim3(256), dyn, e->stream, cb->v, cb->ydim,
-                       ds->d_rows, ds->d_mask, ds->n, f, (const uint64_t *)dk, radius, thresh, ireach, (float *)dq);
+                       ds->d_rows, ds->d_mask, ds->n, f, (const uint64_t *)dk, radius, thresh, ireach, dq);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out + off, dq, sizeof(float) * (size_t)c, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));

@@ -92,14 +92,11 @@ static int som_train_online(somhip_codebook *cb, somhip_dataset *ds, const somhi
   cb->prep_valid = false;
   const int64_t CH = ONLINE_CHUNK;
   const bool G = cb->v.neigh == SOMHIP_NEIGH_GAUSSIAN, M = ds->d_mask != nullptr;
-  void *dslot, *dsc, *drow;
+  uint64_t *slot; StepScalars *sc; int64_t *rowidx;
   // entry 0 of the arrays carries the last iteration of the previous chunk
-  CHK(engine_scratch(e, SLOT_CALL_A, sizeof(uint64_t) * (size_t)(CH + 1), &dslot));
-  CHK(engine_scratch(e, SLOT_CALL_B, sizeof(StepScalars) * (size_t)(CH + 1), &dsc));
-  CHK(engine_scratch(e, SLOT_PARTIAL, sizeof(int64_t) * (size_t)(CH + 1), &drow));
-  uint64_t *slot = (uint64_t *)dslot;
-  StepScalars *sc = (StepScalars *)dsc;
-  int64_t *rowidx = (int64_t *)drow;
+  CHK(scratch(e, SLOT_CALL_A, (size_t)(CH + 1), &slot));
+  CHK(scratch(e, SLOT_CALL_B, (size_t)(CH + 1), &sc));
+  CHK(scratch(e, SLOT_PARTIAL, (size_t)(CH + 1), &rowidx));
   std::vector<StepScalars> hsc((size_t)CH + 1);
   std::vector<uint64_t> hslot((size_t)CH + 1);
   std::vector<int64_t> hrow((size_t)CH + 1);
@@ -293,17 +290,17 @@ static UpdatePlan som_update_plan(const somhip_codebook *cb, const somhip_datase
 // each stage takes its scratch slots where it starts: the lists' here, the tail starts (members) and the group order (order)
 struct UpdateBufs { int2 *bxy; uint32_t *cnt; MemberEntry *lists; uint32_t *lstart, *order; };
 static int bind_update(somhip_engine *e, const somhip_codebook *cb, int64_t count, UpdateBufs *b) {
-  void *xy, *cnt, *region;
-  CHK(engine_scratch(e, SLOT_MEMBER_XY, sizeof(int2) * (size_t)count, &xy));
-  CHK(engine_scratch(e, SLOT_MEMBER_COUNT, sizeof(uint32_t) * (size_t)cb->v.ngroups, &cnt));
+  *b = UpdateBufs{};
+  CHK(scratch(e, SLOT_MEMBER_XY, (size_t)count, &b->bxy));
+  CHK(scratch(e, SLOT_MEMBER_COUNT, (size_t)cb->v.ngroups, &b->cnt));
   // the lists start GEMM_FRONT_PAD entries into their region: K4m's scalar quarter loads may start before a list
-  CHK(engine_scratch(e, SLOT_MEMBER_LIST, sizeof(MemberEntry) * ((size_t)cb->v.ngroups * (size_t)list_stride(count) + GEMM_FRONT_PAD), &region));
-  *b = {(int2 *)xy, (uint32_t *)cnt, (MemberEntry *)region + GEMM_FRONT_PAD, nullptr, nullptr};
+  CHK(scratch(e, SLOT_MEMBER_LIST, (size_t)cb->v.ngroups * (size_t)list_stride(count) + GEMM_FRONT_PAD, &b->lists));
+  b->lists += GEMM_FRONT_PAD;
   return 0;
 }
 static int update_members(somhip_engine *e, const somhip_codebook *cb, const somhip_dataset *ds, const UpdatePlan &p,
                           int64_t data_first, int64_t count, const uint64_t *d_keys, const StepScalars *d_sc, UpdateBufs &b) {
-  if (p.tail) { void *ls; CHK(engine_scratch(e, SLOT_TAIL_START, sizeof(uint32_t) * (size_t)cb->v.ngroups, &ls)); b.lstart = (uint32_t *)ls; }
+  if (p.tail) CHK(scratch(e, SLOT_TAIL_START, (size_t)cb->v.ngroups, &b.lstart));
   LaunchTimer t(e, KID_MEMBERS);
   const int rc = with_value<1, 0>(cb->v.neigh == SOMHIP_NEIGH_GAUSSIAN, [&](auto g) { return with_value<1024, 256>(p.members_nt, [&](auto nt) {
     return with_value<8, 4>(p.members_rr, [&](auto rr) {
@@ -361,7 +358,7 @@ static int som_update_run(somhip_codebook *cb, somhip_dataset *ds, int64_t data_
   }
   CHK(update_members(e, cb, ds, p, data_first, count, d_keys, d_sc, b));
   if (p.order) {
-    void *ord; CHK(engine_scratch(e, SLOT_STAGE, sizeof(uint32_t) * (size_t)cb->v.ngroups, &ord)); b.order = (uint32_t *)ord;
+    CHK(scratch(e, SLOT_STAGE, (size_t)cb->v.ngroups, &b.order));
     LaunchTimer t(e, KID_DECODE);                          // (timed with k_decode_winners)
     hipLaunchKernelGGL(k_order_groups, dim3((unsigned)((cb->v.ngroups * 8 + 255) / 256)), dim3(256), 0, e->stream, b.cnt, (int)cb->v.ngroups, b.order);
     HIPCHK(hipGetLastError());
@@ -391,9 +388,9 @@ extern "C" int somhip_som_batch_update(somhip_codebook *cb, somhip_dataset *ds,
   if (count <= 0) return 0;
   somhip_engine *e = cb->e;
   HIPCHK(hipSetDevice(e->device));
-  void *dsc, *hsc;
+  StepScalars *dsc; void *hsc;
   int slot;
-  CHK(engine_scratch(e, SLOT_CALL_B, sizeof(StepScalars) * (size_t)count, &dsc));
+  CHK(scratch(e, SLOT_CALL_B, (size_t)count, &dsc));
   CHK(pin_acquire(e, sizeof(StepScalars) * (size_t)count, &hsc, &slot));
   CHK(som_scalars(cb, ds, p, batch_start_iter, count, data_first % ds->n, (StepScalars *)hsc));
   CHK(pin_upload(e, slot, dsc, sizeof(StepScalars) * (size_t)count));
@@ -485,9 +482,9 @@ static int som_train_batched(somhip_codebook *cb, somhip_dataset *ds, const somh
   const bool auto_b = p->batch == SOMHIP_BATCH_AUTO;
   const AutoPlan plan = auto_b ? som_auto_plan(p, cb->n_global, cb->v.topol, cb->v.neigh) : AutoPlan();
   const int64_t B = auto_b ? AUTO_B_LONG : p->batch;        // the longest batch of the run
-  void *dkeys, *dsc;
-  CHK(engine_scratch(e, SLOT_CALL_A, sizeof(uint64_t) * (size_t)B, &dkeys));
-  CHK(engine_scratch(e, SLOT_CALL_B, sizeof(StepScalars) * (size_t)B, &dsc));
+  uint64_t *dkeys; StepScalars *dsc;
+  CHK(scratch(e, SLOT_CALL_A, (size_t)B, &dkeys));
+  CHK(scratch(e, SLOT_CALL_B, (size_t)B, &dsc));
   std::vector<uint64_t> hk((size_t)B);
   const bool trace = trace_index || trace_diff;
   // batches are aligned to the schedule (iteration 0, B, 2B, ...), as in the oracle; the host runs
@@ -504,7 +501,7 @@ static int som_train_batched(somhip_codebook *cb, somhip_dataset *ds, const somh
     StepScalars *hsc = (StepScalars *)hscv;
     CHK(som_scalars(cb, ds, p, it0, c, row0, hsc));
     CHK(pin_upload(e, slot, dsc, sizeof(StepScalars) * (size_t)c));
-    CHK(scan_keys_top1(cb, ds, row0, c, (uint64_t *)dkeys));
+    CHK(scan_keys_top1(cb, ds, row0, c, dkeys));
     CHK(som_update_run(cb, ds, row0, c, (const uint64_t *)dkeys, (const StepScalars *)dsc, hsc));
     if (trace) {
       HIPCHK(hipMemcpyAsync(hk.data(), dkeys, sizeof(uint64_t) * (size_t)c, hipMemcpyDeviceToHost, e->stream));

@@ -19,11 +19,10 @@ extern "C" int somhip_umatrix(somhip_codebook *cb, int filters, float *u, double
   UmatDims m;
   m.mx = mx; m.my = my; m.ux = 2 * mx - 1; m.uy = 2 * my - 1; m.topol = cb->v.topol;
   const int64_t count = (int64_t)m.ux * m.uy;
-  void *d_a, *d_b, *d_mm;
-  CHK(engine_scratch(e, SLOT_CALL_A, sizeof(float) * (size_t)count, &d_a));
-  CHK(engine_scratch(e, SLOT_CALL_B, sizeof(float) * (size_t)count, &d_b));
-  CHK(engine_scratch(e, SLOT_PARTIAL, sizeof(uint32_t) * 2, &d_mm));
-  float *cur = (float *)d_a, *other = (float *)d_b;
+  float *cur, *other; uint32_t *d_mm;
+  CHK(scratch(e, SLOT_CALL_A, (size_t)count, &cur));
+  CHK(scratch(e, SLOT_CALL_B, (size_t)count, &other));
+  CHK(scratch(e, SLOT_PARTIAL, 2, &d_mm));
   const uint32_t preset[2] = {FLT_MAX_BITS, 0u};
   HIPCHK(hipMemcpyAsync(d_mm, preset, sizeof preset, hipMemcpyHostToDevice, e->stream));
   const unsigned per_entry = (unsigned)((count + 255) / 256);
@@ -39,8 +38,7 @@ extern "C" int somhip_umatrix(somhip_codebook *cb, int filters, float *u, double
   HIPCHK(hipGetLastError());
   {
     LaunchTimer t(e, KID_UMAT_MINMAX);
-    hipLaunchKernelGGL(k_umat_minmax, dim3(std::min(per_entry, 128u)), dim3(256), 0, e->stream, (const float *)cur, count,
-                       (uint32_t *)d_mm);
+    hipLaunchKernelGGL(k_umat_minmax, dim3(std::min(per_entry, 128u)), dim3(256), 0, e->stream, (const float *)cur, count, d_mm);
   }
   HIPCHK(hipGetLastError());
   uint32_t bits[2];

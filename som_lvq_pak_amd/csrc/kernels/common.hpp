@@ -12,6 +12,26 @@ constexpr int WAVE = 64;
 constexpr uint64_t KEY_NONE = 0xFFFFFFFFFFFFFFFFull;
 constexpr uint32_t FLT_MAX_BITS = 0x7F7FFFFFu;
 
+// The engine's device statistics block (somhip_engine::d_stats): 64-bit words, zeroed when the engine is created.
+// Host and kernels index it by these names only; a kernel that counts into several words gets the block's base.
+constexpr int STAT_UPDATE_PAIRS = 64;        // {rows, pairs} counter pairs of the SOM update, a power of two (one pair
+                                             // took ~8 000 same-address atomics): summed by somhip_scan_stats
+constexpr int STAT_GEMM_WALKS = 8;           // counters of the GEMM update's list walk, a power of two: summed likewise
+enum StatWord {
+  STAT_RERANK_GROUPS = 0,                    // groups re-ranked
+  STAT_RERANK_ROWS = 1,                      // rows re-ranked
+  STAT_RERANK_MAX_GROUPS = 2,                // most groups re-ranked for one sample
+  //         3 .. 5                             unused
+  STAT_PAIR_OVERFLOW = 6,                    // low uint32: the nearest-row pair list's overflow flag (PrefilterBufs::paircount)
+  STAT_TOPK_LIST = 7,                        // two uint32: the top-K pair list's fill and overflow
+  STAT_UPDATE = 8,                           // STAT_UPDATE_PAIRS {rows, pairs} pairs
+  STAT_GEMM_WALK = STAT_UPDATE + 2 * STAT_UPDATE_PAIRS,
+  STAT_L2_PAIRS = STAT_GEMM_WALK + STAT_GEMM_WALKS,   // (group, sample) pairs level 2 computed
+  STAT_TOPK_PAIRS,                           // pairs of the top-K re-rank
+  STAT_WORDS
+};
+static_assert(STAT_WORDS == 146 && STAT_GEMM_WALK == 136 && STAT_L2_PAIRS == 144, "layout of the statistics block");
+
 struct CbView {
   float *tiles;         // [ngroups][d4][64][4]
   int64_t n;            // local rows

@@ -9,7 +9,7 @@ namespace somhip {
 // K2r: exact re-rank.  One wave per sample: global minimum of the group minima, then
 // for every group within tau of it, the masked rows' distances with the reference's
 // arithmetic (lane = row, dims in order, sub/mul/add), exact (distance, index) minimum.
-// stats[0] += groups re-ranked, stats[1] += rows re-ranked, stats[2] = max groups/sample.
+// Counts into STAT_RERANK_GROUPS, _ROWS and _MAX_GROUPS of the statistics block (common.hpp).
 // =====================================================================================
 __global__ __launch_bounds__(256) void k_rerank(CbView cb, const float *__restrict__ rows,
                                                 int64_t n_rows, int64_t first, int64_t count,
@@ -63,9 +63,9 @@ __global__ __launch_bounds__(256) void k_rerank(CbView cb, const float *__restri
   best = wave_min_u64(best);
   if (lane == 0) {
     atomicMin(reinterpret_cast<unsigned long long *>(keys + b), static_cast<unsigned long long>(best));
-    atomicAdd(stats + 0, static_cast<unsigned long long>(ngroups_done));
-    atomicAdd(stats + 1, static_cast<unsigned long long>(nrows_done));
-    atomicMax(stats + 2, static_cast<unsigned long long>(ngroups_done));
+    atomicAdd(stats + STAT_RERANK_GROUPS, static_cast<unsigned long long>(ngroups_done));
+    atomicAdd(stats + STAT_RERANK_ROWS, static_cast<unsigned long long>(nrows_done));
+    atomicMax(stats + STAT_RERANK_MAX_GROUPS, static_cast<unsigned long long>(ngroups_done));
   }
 }
 
@@ -758,8 +758,8 @@ __global__ __launch_bounds__(256) void k_rerank_pairs(CbView cb, const float *__
   if (blockIdx.x == 0 && *pair_count <= cap) {            // the columns' statistics, once
     for (int c = tid; c < ncols; c += 256) {
       const uint32_t g = col_count[ncols * 1 + c], r = col_count[ncols * 2 + c];
-      if (r) { atomicAdd(stats + 0, static_cast<unsigned long long>(g)); atomicAdd(stats + 1, static_cast<unsigned long long>(r)); }
-      atomicMax(stats + 2, static_cast<unsigned long long>(col_count[ncols * 3 + c]));
+      if (r) { atomicAdd(stats + STAT_RERANK_GROUPS, static_cast<unsigned long long>(g)); atomicAdd(stats + STAT_RERANK_ROWS, static_cast<unsigned long long>(r)); }
+      atomicMax(stats + STAT_RERANK_MAX_GROUPS, static_cast<unsigned long long>(col_count[ncols * 3 + c]));
     }
   }
   if (*pair_count > cap) return;                         // a segment overflowed: K2r does the whole run

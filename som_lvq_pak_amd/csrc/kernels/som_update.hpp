@@ -325,8 +325,8 @@ __global__ __launch_bounds__(NT) void k_som_members(CbView cb, int64_t count,
     rows_total += __shfl_xor(rows_total, off, WAVE);
     pairs_total += __shfl_xor(pairs_total, off, WAVE);
   }
-  if (lane == 0 && stats) {     // 64 counter pairs (summed by the host): one pair took ~8 000 same-address atomics
-    unsigned long long *st = stats + 8 + 2 * (g & 63);
+  if (lane == 0 && stats) {     // many counter pairs (summed by the host): one pair took ~8 000 same-address atomics
+    unsigned long long *st = stats + STAT_UPDATE + 2 * (g & (STAT_UPDATE_PAIRS - 1));
     if (rows_total) atomicAdd(st, rows_total);
     if (pairs_total) atomicAdd(st + 1, pairs_total);
   }

@@ -311,7 +311,7 @@ __global__ __launch_bounds__(256, 2) void k_som_update_gemm(CbView cb, const flo
         *tp[i][f] = make_float4(pu[t] * c.x + o[0], pu[t] * c.y + o[1], pu[t] * c.z + o[2], pu[t] * c.w + o[3]);
       }
   }
-  if (stats && tid == 0 && d0 == 0) atomicAdd(stats + 8 + 2 * 64 + (g & 7), processed);   // entries walked for this group
+  if (stats && tid == 0 && d0 == 0) atomicAdd(stats + STAT_GEMM_WALK + (g & (STAT_GEMM_WALKS - 1)), processed);   // entries walked for this group
 }
 
 }  // namespace somhip

@@ -61,49 +61,31 @@ extern "C" int somhip_version(void) { return SOMHIP_VERSION; }
 // ---------------------------------------------------------------------------------
 // kernel ids for the timing table
 // ---------------------------------------------------------------------------------
+// the list: X(id, the name somhip_kernel_name reports); a new kernel id goes at its end
+#define SOMHIP_KERNEL_IDS(X) \
+  X(SCAN_EXACT, "k_scan_exact") X(SOM_UPDATE_RUN, "k_som_update_run") X(SOM_ONLINE_STEP, "k_som_online_step") \
+  X(LVQ_ONLINE_STEP, "k_lvq_online_step") X(PACK_SAMPLES, "k_pack_samples") X(MERGE_TOPK, "k_merge_topk") \
+  X(SCAN_MASKED, "k_scan_masked") X(LAYOUT, "k_layout") X(DECODE, "k_decode_winners") \
+  X(DIST_MFMA, "k_dist_mfma") X(RERANK, "k_rerank") X(NORMS, "k_norms_tau") \
+  X(MEMBERS, "k_som_members") X(RERANK_SELECT, "k_rerank_select") X(RERANK_PAIRS, "k_rerank_pairs") \
+  X(DIST_MFMA_BF16, "k_dist_mfma_bf16") X(LVQ_BATCH_APPLY, "k_lvq_batch_apply") X(SOM_UPDATE_BUBBLE_S, "k_som_update_bubble_s") \
+  X(LVQ_COMPONENTS, "k_lvq_components") X(SOM_UPDATE_GEMM, "k_som_update_gemm") X(DIST_L2, "k_dist_l2") \
+  X(L2_SELECT, "k_l2_select") X(SAMMON_DIST, "k_sammon_dist") X(SAMMON_SWEEP, "k_sammon_sweep") \
+  X(SAMMON_CENTRE, "k_sammon_centre") X(SAMMON_ERROR, "k_sammon_error") X(CLASS_NEAREST, "k_class_nearest") \
+  X(UMAT_DIST, "k_umat_dist") X(UMAT_UNITS, "k_umat_units") X(UMAT_MINMAX, "k_umat_minmax") \
+  X(UMAT_SCALE, "k_umat_scale") X(UMAT_AVERAGE, "k_umat_average") X(UMAT_MEDIAN, "k_umat_median")
 enum KernelId {
-  KID_SCAN_EXACT = 0,
-  KID_SOM_UPDATE_RUN,
-  KID_SOM_ONLINE_STEP,
-  KID_LVQ_ONLINE_STEP,
-  KID_PACK_SAMPLES,
-  KID_MERGE_TOPK,
-  KID_SCAN_MASKED,
-  KID_LAYOUT,
-  KID_DECODE,
-  KID_DIST_MFMA,
-  KID_RERANK,
-  KID_NORMS,
-  KID_MEMBERS,
-  KID_RERANK_SELECT,
-  KID_RERANK_PAIRS,
-  KID_DIST_MFMA_BF16,
-  KID_LVQ_BATCH_APPLY,
-  KID_SOM_UPDATE_BUBBLE_S,
-  KID_LVQ_COMPONENTS,
-  KID_SOM_UPDATE_GEMM,
-  KID_DIST_L2,
-  KID_L2_SELECT,
-  KID_SAMMON_DIST,
-  KID_SAMMON_SWEEP,
-  KID_SAMMON_CENTRE,
-  KID_SAMMON_ERROR,
-  KID_CLASS_NEAREST,
-  KID_UMAT_DIST,
-  KID_UMAT_UNITS,
-  KID_UMAT_MINMAX,
-  KID_UMAT_SCALE,
-  KID_UMAT_AVERAGE,
-  KID_UMAT_MEDIAN,
+#define X(id, name) KID_##id,
+  SOMHIP_KERNEL_IDS(X)
+#undef X
   KID_COUNT
 };
 static const char *kKernelNames[KID_COUNT] = {
-    "k_scan_exact", "k_som_update_run", "k_som_online_step", "k_lvq_online_step",
-    "k_pack_samples", "k_merge_topk", "k_scan_masked", "k_layout", "k_decode_winners",
-    "k_dist_mfma", "k_rerank", "k_norms_tau", "k_som_members",
-    "k_rerank_select", "k_rerank_pairs", "k_dist_mfma_bf16", "k_lvq_batch_apply", "k_som_update_bubble_s", "k_lvq_components", "k_som_update_gemm", "k_dist_l2", "k_l2_select",
-    "k_sammon_dist", "k_sammon_sweep", "k_sammon_centre", "k_sammon_error", "k_class_nearest",
-    "k_umat_dist", "k_umat_units", "k_umat_minmax", "k_umat_scale", "k_umat_average", "k_umat_median"};
+#define X(id, name) name,
+  SOMHIP_KERNEL_IDS(X)
+#undef X
+};
+static_assert(KID_COUNT <= 64, "somhip_timing_select's mask has one bit per kernel id");
 extern "C" int somhip_kernel_count(void) { return KID_COUNT; }
 extern "C" const char *somhip_kernel_name(int i) { return (i >= 0 && i < KID_COUNT) ? kKernelNames[i] : ""; }
 
@@ -119,7 +101,7 @@ struct OnlineGraphKey {
   }
 };
 
-// Device scratch of an engine (engine_scratch): one buffer per slot, grown on demand and kept.  The owners of a slot
+// Device scratch of an engine (scratch / engine_scratch): one buffer per slot, grown on demand and kept.  The owners of a slot
 // never hold it at the same time; the stages named below hold their slots together.
 enum ScratchSlot {
   SLOT_STAGE = 0,          // staging of codebook upload / download; the SOM update's group order (k_order_groups);
@@ -137,7 +119,7 @@ enum ScratchSlot {
   SLOT_MEMBER_XY,          // SOM update: the winners' lattice positions
   SLOT_MEMBER_COUNT,       // SOM update: members per row group
   SLOT_MEMBER_LIST,        // SOM update: the member lists
-  SLOT_PAIRS,              // top-1 re-rank: candidate pairs; top-K re-rank: its pair list
+  SLOT_PAIRS,              // top-1 re-rank: candidate pairs in segments (bind_rerank_pairs); top-K re-rank: its pair list
   SLOT_RERANK_COUNT,       // pre-filter: re-rank counters preset in pf_prepare, from prepare to the re-rank
   SLOT_LVQ_FINAL,          // exact LVQ batches: the final keys
   SLOT_XBOUND,             // shard exchange: the deltas behind the exchanged bounds, from begin to finish
@@ -155,11 +137,16 @@ enum ScratchSlot {
   SLOT_L2_STATE,           // two-level pre-filter: level 1's window and minimum, level 2's counts, from prepare to the re-rank
   SLOT_L2_LIST,            // two-level pre-filter: level 2's group lists, from level 1 to the re-rank (k_rerank_select_lists)
   SLOT_LVQ_CTL,            // exact LVQ loop: its control block
-  SLOT_TOPK_GROUPS,        // top-K re-rank by row group: the groups' lists and the passes
+  SLOT_TOPK_GROUPS,        // top-K re-rank by row group: the groups' lists and the passes (bind_topk_groups)
   SLOT_TAIL_START,         // GEMM update: where each group's list tail starts
   SLOT_SAMPLE_ROWS,        // two-level pre-filter: the sample-major copy of the tiles, from prepare to level 2
   SLOT_COUNT
 };
+
+// the kernels whose dynamic LDS limit an engine raises before their first launch (raise_lds_limit): bits of lds_raised
+enum LdsKernel { LDS_LVQ_APPLY, LDS_LVQ_APPLY_MASKED, LDS_LVQ_COMPONENTS, LDS_DIST_L2, LDS_L1_RING, LDS_PREP_ROWMAJOR };
+constexpr int PIN_RING = 4;       // pinned staging buffers of pin_acquire, a power of two
+constexpr int LVQ_EV_RING = 8;    // batches of the exact LVQ loop in flight (lvq_train_batched)
 
 enum XcState { XC_NONE, XC_BEGUN, XC_REFINED };   // a shard-exchanged search: the last of its calls that ran
 
@@ -170,7 +157,7 @@ struct somhip_engine {
   uint64_t timing_mask = ~0ull;              // which kernel ids get events when timing is on
   int scan_mode = SOMHIP_SCAN_MFMA_BF16;
   int update_mode = SOMHIP_UPDATE_EXACT;
-  unsigned long long *d_stats = nullptr;     // [4] re-rank statistics (device)
+  unsigned long long *d_stats = nullptr;     // [STAT_WORDS] the statistics block (device; kernels/common.hpp StatWord)
   uint64_t samples_searched = 0;
   // somhip_shard_winner_begin / _refine / _finish: which search is under way on this engine, and how far it got
   int xc_phase = 0;                          // XC_NONE, XC_BEGUN, XC_REFINED
@@ -181,9 +168,9 @@ struct somhip_engine {
   int64_t lvq_batch_hint = 256;                   // batch size the exact LVQ engine starts its next call with
   uint64_t lvq_components = 0, lvq_largest = 0;   // independent components walked, and the sum of the largest one's size per batch
   // ring of pinned host staging buffers for per-batch scalars (H2D without a host sync)
-  void *pin_buf[4] = {nullptr, nullptr, nullptr, nullptr};
-  size_t pin_bytes[4] = {0, 0, 0, 0};
-  hipEvent_t pin_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  void *pin_buf[PIN_RING] = {nullptr};
+  size_t pin_bytes[PIN_RING] = {0};
+  hipEvent_t pin_ev[PIN_RING] = {nullptr};
   int pin_next = 0;
   hipGraphExec_t online_graph_exec = nullptr;   // one chunk of k_som_online_step launches
   OnlineGraphKey online_graph_key{};
@@ -199,14 +186,13 @@ struct somhip_engine {
   // them (their own destroy then only frees the host struct; any other call on them fails with a message)
   std::vector<somhip_codebook *> codebooks;
   std::vector<somhip_dataset *> datasets;
-  bool lvq_apply_attr_set = false;             // hipFuncSetAttribute(k_lvq_batch_apply, ...) done on this device
-  bool l2_lds_attr_set = false;                // ... and for k_dist_l2_lds
-  bool l1r_attr_set = false;                   // ... and for k_dist_mfma_bf16_l1r
-  bool prep_rm_attr_set = false;               // ... and for k_prep_codes_bf16<true>
+  unsigned lds_raised = 0;                     // bit LdsKernel: that kernel's dynamic LDS limit is raised on this device
   int n_cus = 0;                               // compute units of the device (grid of the persistent kernels)
   LvqCtl *lvq_hctl = nullptr;                  // pinned: read-backs of the LVQ batch loop's control block, one per batch in flight
-  hipEvent_t lvq_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t lvq_ev[LVQ_EV_RING] = {nullptr};
 };
+
+static int check_engine(const somhip_engine *e, const char *who) { return e ? 0 : fail("%s: null engine", who); }
 
 static int engine_scratch(somhip_engine *e, ScratchSlot slot, size_t bytes, void **out) {
   if (e->scratch_bytes[slot] < bytes) {
@@ -220,11 +206,22 @@ static int engine_scratch(somhip_engine *e, ScratchSlot slot, size_t bytes, void
   *out = e->scratch[slot];
   return 0;
 }
+template <class T>   // ... as room for `count` elements of T
+static int scratch(somhip_engine *e, ScratchSlot slot, size_t count, T **out) {
+  return engine_scratch(e, slot, sizeof(T) * count, reinterpret_cast<void **>(out));
+}
+// once per engine (= per device, not per process) and before the kernel's first launch: more dynamic LDS than the default limit
+static int raise_lds_limit(somhip_engine *e, LdsKernel which, const void *kernel, size_t bytes) {
+  if ((e->lds_raised >> which) & 1u) return 0;
+  HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  e->lds_raised |= 1u << which;
+  return 0;
+}
 
 // next pinned staging buffer of the ring (waits only if its previous copy is still in flight)
 static int pin_acquire(somhip_engine *e, size_t bytes, void **host, int *slot) {
   int i = e->pin_next;
-  e->pin_next = (i + 1) & 3;
+  e->pin_next = (i + 1) & (PIN_RING - 1);
   if (!e->pin_ev[i]) HIPCHK(hipEventCreateWithFlags(&e->pin_ev[i], hipEventDisableTiming));
   else HIPCHK(hipEventSynchronize(e->pin_ev[i]));
   if (e->pin_bytes[i] < bytes) {
@@ -299,8 +296,8 @@ extern "C" int somhip_engine_create(int device, somhip_engine **out) try {
   e->device = device;
   auto init = [&]() -> int {
     HIPCHK(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-    HIPCHK(hipMalloc((void **)&e->d_stats, (8 + 128 + 8 + 2) * sizeof(unsigned long long)));   // + 64 {rows, pairs} update counters + 8 gemm-walk counters + level-2 pairs + top-k pairs
-    HIPCHK(hipMemset(e->d_stats, 0, (8 + 128 + 8 + 2) * sizeof(unsigned long long)));
+    HIPCHK(hipMalloc((void **)&e->d_stats, STAT_WORDS * sizeof(unsigned long long)));
+    HIPCHK(hipMemset(e->d_stats, 0, STAT_WORDS * sizeof(unsigned long long)));
     if (const char *um = getenv("SOMHIP_UPDATE_MODE")) e->update_mode = strcmp(um, "gemm") == 0 ? SOMHIP_UPDATE_GEMM : SOMHIP_UPDATE_EXACT;
     return 0;
   };
@@ -318,15 +315,15 @@ extern "C" void somhip_engine_destroy(somhip_engine *e) try {
   for (auto *ds : e->datasets) dataset_release(ds);
   for (auto &p : e->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
   for (auto ev : e->pool) (void)hipEventDestroy(ev);
-  for (int i = 0; i < 32; i++) if (e->scratch[i]) (void)hipFree(e->scratch[i]);
+  for (int i = 0; i < SLOT_COUNT; i++) if (e->scratch[i]) (void)hipFree(e->scratch[i]);
   if (e->d_stats) (void)hipFree(e->d_stats);
   if (e->online_graph_exec) (void)hipGraphExecDestroy(e->online_graph_exec);
-  for (int i = 0; i < 4; i++) {
+  for (int i = 0; i < PIN_RING; i++) {
     if (e->pin_buf[i]) (void)hipHostFree(e->pin_buf[i]);
     if (e->pin_ev[i]) (void)hipEventDestroy(e->pin_ev[i]);
   }
   if (e->lvq_hctl) (void)hipHostFree(e->lvq_hctl);
-  for (int i = 0; i < 8; i++) if (e->lvq_ev[i]) (void)hipEventDestroy(e->lvq_ev[i]);
+  for (int i = 0; i < LVQ_EV_RING; i++) if (e->lvq_ev[i]) (void)hipEventDestroy(e->lvq_ev[i]);
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
 } ABI_CATCH_VOID(somhip_engine_destroy)
@@ -340,31 +337,33 @@ extern "C" int somhip_device_count(int *count) try {
 } ABI_CATCH(somhip_device_count)
 extern "C" void *somhip_engine_stream(somhip_engine *e) { return e ? (void *)e->stream : nullptr; }
 extern "C" int somhip_engine_sync(somhip_engine *e) try {
-  if (!e) return fail("somhip_engine_sync: null engine");
+  CHK(check_engine(e, "somhip_engine_sync"));
   HIPCHK(hipSetDevice(e->device));
   HIPCHK(hipStreamSynchronize(e->stream));
   return 0;
 } ABI_CATCH(somhip_engine_sync)
 extern "C" int somhip_engine_set_scan_mode(somhip_engine *e, int mode) try {
+  CHK(check_engine(e, "somhip_engine_set_scan_mode"));
   if (mode != SOMHIP_SCAN_DIRECT && mode != SOMHIP_SCAN_MFMA && mode != SOMHIP_SCAN_MFMA_BF16) return fail("somhip_engine_set_scan_mode: bad mode %d", mode);
   e->scan_mode = mode;
   return 0;
 } ABI_CATCH(somhip_engine_set_scan_mode)
 extern "C" int somhip_engine_set_update_mode(somhip_engine *e, int mode) try {
-  if (!e) return fail("somhip_engine_set_update_mode: null engine");
+  CHK(check_engine(e, "somhip_engine_set_update_mode"));
   if (mode != SOMHIP_UPDATE_EXACT && mode != SOMHIP_UPDATE_GEMM) return fail("somhip_engine_set_update_mode: bad mode %d", mode);
   e->update_mode = mode;
   return 0;
 } ABI_CATCH(somhip_engine_set_update_mode)
 extern "C" int somhip_scan_stats(somhip_engine *e, uint64_t out[8]) try {
-  unsigned long long h[8 + 128 + 8 + 1];
+  CHK(check_engine(e, "somhip_scan_stats"));
+  unsigned long long h[STAT_WORDS];
   HIPCHK(hipMemcpyAsync(h, e->d_stats, sizeof h, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
-  for (int k = 0; k < 64; k++) { h[3] += h[8 + 2 * k]; h[4] += h[8 + 2 * k + 1]; }
-  out[0] = h[0]; out[1] = h[1]; out[2] = h[2]; out[3] = e->samples_searched; out[4] = h[3]; out[5] = h[4];
-  out[6] = 0;
-  for (int k = 0; k < 8; k++) out[6] += h[8 + 128 + k];
-  out[7] = h[8 + 128 + 8];
+  uint64_t rows = 0, pairs = 0, walked = 0;
+  for (int k = 0; k < STAT_UPDATE_PAIRS; k++) { rows += h[STAT_UPDATE + 2 * k]; pairs += h[STAT_UPDATE + 2 * k + 1]; }
+  for (int k = 0; k < STAT_GEMM_WALKS; k++) walked += h[STAT_GEMM_WALK + k];
+  out[0] = h[STAT_RERANK_GROUPS]; out[1] = h[STAT_RERANK_ROWS]; out[2] = h[STAT_RERANK_MAX_GROUPS]; out[3] = e->samples_searched;
+  out[4] = rows; out[5] = pairs; out[6] = walked; out[7] = h[STAT_L2_PAIRS];
   return 0;
 } ABI_CATCH(somhip_scan_stats)
 extern "C" int somhip_lvq_stats(somhip_engine *e, uint64_t out[12]) try {
@@ -374,24 +373,31 @@ extern "C" int somhip_lvq_stats(somhip_engine *e, uint64_t out[12]) try {
   unsigned long long pairs = 0;                            // counted on the device (the top-k search does not wait for the host)
   uint32_t topk_counter[2] = {0, 0};                       // the last pre-filtered top-k search's pair list: [0] fill, [1] overflow
   HIPCHK(hipSetDevice(e->device));
-  HIPCHK(hipMemcpyAsync(&pairs, e->d_stats + 8 + 128 + 8 + 1, sizeof pairs, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipMemcpyAsync(topk_counter, e->d_stats + 7, sizeof topk_counter, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipMemcpyAsync(&pairs, e->d_stats + STAT_TOPK_PAIRS, sizeof pairs, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipMemcpyAsync(topk_counter, e->d_stats + STAT_TOPK_LIST, sizeof topk_counter, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
   out[8] = e->lvq_components; out[9] = e->lvq_largest; out[10] = pairs; out[11] = topk_counter[1] != 0 ? 1 : 0;
   return 0;
 } ABI_CATCH(somhip_lvq_stats)
 extern "C" int somhip_timing_enable(somhip_engine *e, int on) try {
+  CHK(check_engine(e, "somhip_timing_enable"));
   CHK(timing_flush(e));
   e->timing = on != 0;
   return 0;
 } ABI_CATCH(somhip_timing_enable)
-extern "C" int somhip_timing_select(somhip_engine *e, uint64_t kernel_mask) { e->timing_mask = kernel_mask; return 0; }
+extern "C" int somhip_timing_select(somhip_engine *e, uint64_t kernel_mask) try {
+  CHK(check_engine(e, "somhip_timing_select"));
+  e->timing_mask = kernel_mask;
+  return 0;
+} ABI_CATCH(somhip_timing_select)
 extern "C" int somhip_timing_reset(somhip_engine *e) try {
+  CHK(check_engine(e, "somhip_timing_reset"));
   CHK(timing_flush(e));
   for (int i = 0; i < KID_COUNT; i++) { e->launches[i] = 0; e->total_ms[i] = 0; }
   return 0;
 } ABI_CATCH(somhip_timing_reset)
 extern "C" int somhip_timing_get(somhip_engine *e, int k, int64_t *launches, double *total_ms) try {
+  CHK(check_engine(e, "somhip_timing_get"));
   if (k < 0 || k >= KID_COUNT) return fail("somhip_timing_get: bad kernel id %d", k);
   CHK(timing_flush(e));
   if (launches) *launches = e->launches[k];
@@ -399,21 +405,25 @@ extern "C" int somhip_timing_get(somhip_engine *e, int k, int64_t *launches, dou
   return 0;
 } ABI_CATCH(somhip_timing_get)
 extern "C" int somhip_device_alloc(somhip_engine *e, int64_t bytes, void **p) try {
+  CHK(check_engine(e, "somhip_device_alloc"));
   HIPCHK(hipSetDevice(e->device));
   HIPCHK(hipMalloc(p, (size_t)std::max<int64_t>(bytes, 16)));
   return 0;
 } ABI_CATCH(somhip_device_alloc)
 extern "C" int somhip_device_free(somhip_engine *e, void *p) try {
+  CHK(check_engine(e, "somhip_device_free"));
   HIPCHK(hipSetDevice(e->device));
   HIPCHK(hipFree(p));
   return 0;
 } ABI_CATCH(somhip_device_free)
 extern "C" int somhip_copy_to_host(somhip_engine *e, void *dst, const void *src, int64_t bytes) try {
+  CHK(check_engine(e, "somhip_copy_to_host"));
   HIPCHK(hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
   return 0;
 } ABI_CATCH(somhip_copy_to_host)
 extern "C" int somhip_copy_to_device(somhip_engine *e, void *dst, const void *src, int64_t bytes) try {
+  CHK(check_engine(e, "somhip_copy_to_device"));
   HIPCHK(hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyHostToDevice, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
   return 0;
@@ -456,9 +466,9 @@ struct somhip_dataset {
 static int upload_rows(somhip_codebook *cb, const float *rows) {
   somhip_engine *e = cb->e;
   cb->prep_valid = false;
-  void *stage;
+  float *stage;
   size_t bytes = sizeof(float) * (size_t)cb->v.n * cb->v.d;
-  CHK(engine_scratch(e, SLOT_STAGE, bytes, &stage));
+  CHK(scratch(e, SLOT_STAGE, (size_t)cb->v.n * cb->v.d, &stage));
   HIPCHK(hipMemcpyAsync(stage, rows, bytes, hipMemcpyHostToDevice, e->stream));
   {
     LaunchTimer t(e, KID_LAYOUT);
@@ -570,9 +580,9 @@ extern "C" int somhip_codebook_download(somhip_codebook *cb, float *rows) try {
   if (!cb->e) return fail("somhip_codebook_download: the engine of this codebook was destroyed");
   somhip_engine *e = cb->e;
   HIPCHK(hipSetDevice(e->device));
-  void *stage;
+  float *stage;
   size_t bytes = sizeof(float) * (size_t)cb->v.n * cb->v.d;
-  CHK(engine_scratch(e, SLOT_STAGE, bytes, &stage));
+  CHK(scratch(e, SLOT_STAGE, (size_t)cb->v.n * cb->v.d, &stage));
   {
     LaunchTimer t(e, KID_LAYOUT);
     hipLaunchKernelGGL(k_tiles_to_rows, dim3((unsigned)cb->v.ngroups), dim3(256), 0, e->stream,
