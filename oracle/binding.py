@@ -250,6 +250,11 @@ class RefHarness(_Base):
         self._randseq = L("rand_seq", None, [C.c_int, C.c_long, c_long_p])
         self._randinit = L("randinit", C.c_int, [c_float_p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int,
                                                   C.c_int, C.c_int, c_float_p])
+        # the newest entry: a libref_harness.so built from an earlier ref_harness.c (and not rebuildable where the
+        # reference's sources are absent) serves every other method; has_find_eigenvectors tells the two apart
+        self.has_find_eigenvectors = hasattr(self.lib, "ref_find_eigenvectors")
+        self._eigen = (L("find_eigenvectors", C.c_int, [c_float_p, C.c_long, C.c_int, c_ubyte_p, C.c_int, c_float_p])
+                       if self.has_find_eigenvectors else None)
         self.last_seconds = 0.0
 
     def som_train(self, codes, xdim, ydim, topol, neigh, data, length, alpha, radius,
@@ -379,6 +384,19 @@ class RefHarness(_Base):
         out = np.zeros(count, dtype=np.int64)
         self._randseq(seed, count, _ptr(out, c_long_p))
         return out
+
+    def find_eigenvectors(self, data, seed, mask=None):
+        """find_eigenvectors (som_rout.c:211) after init_random(seed): float32[3, dim] = the mean and the two scaled
+        axes, or None where the reference gives up (fewer than 3 rows, mu == 0)."""
+        if self._eigen is None:
+            raise RuntimeError("oracle/_ref/libref_harness.so has no ref_find_eigenvectors: rebuild it (make -C oracle ref)")
+        data = _f32(data)
+        mask = _opt(mask, np.uint8)
+        out = np.zeros((3, data.shape[1]), dtype=np.float32)
+        rc = self._eigen(_ptr(data, c_float_p), data.shape[0], data.shape[1], _ptr(mask, c_ubyte_p), seed,
+                         _ptr(out, c_float_p))
+        assert rc in (0, 1)
+        return out if rc == 0 else None
 
     def randinit(self, data, xdim, ydim, seed, topol=3, neigh=1):
         data = _f32(data)

@@ -300,6 +300,30 @@ void ref_rand_seq(int seed, long count, long *out)
   for (i = 0; i < count; i++) out[i] = orand();
 }
 
+/* find_eigenvectors (som_rout.c:211; not in som_rout.h, but an external symbol of som_rout.o) on
+ * in-memory data, after init_random(seed).  out[3][dim]: the mean and the two scaled axes, the
+ * floats of the three entries it returns.  1 = it returned NULL (fewer than 3 rows, or mu == 0). */
+struct data_entry *find_eigenvectors(struct entries *data);
+
+int ref_find_eigenvectors(const float *data, long ndata, int dim, const unsigned char *mask,
+                          int seed, float *out)
+{
+  struct entries *de;
+  struct data_entry *m, *d;
+  int i;
+  label_not_needed(1);
+  de = list_from_dense(data, ndata, dim, NULL, NULL, NULL, mask, TOPOL_DATA, 0, 0, 0);
+  if (!de) return 2;
+  init_random(seed);
+  m = find_eigenvectors(de);
+  if (!m) { close_entries(de); return 1; }
+  for (i = 0, d = m; i < 3 && d; i++, d = d->next)
+    memcpy(out + (long)i * dim, d->points, sizeof(float) * dim);
+  free_entrys(m);
+  close_entries(de);
+  return i == 3 ? 0 : 2;
+}
+
 /* randinit_codes (som_rout.c:34) on in-memory data, after init_random(seed). */
 int ref_randinit(const float *data, long ndata, int dim, int topol, int neigh, int xdim, int ydim,
                  int seed, float *codes_out)

@@ -264,6 +264,26 @@ def column_minmax(ds):
     return lo, hi, cnt
 
 
+def column_sums(ds):
+    """lininit's first data pass (somhip_column_sums): per component the fp32 sum of the unmasked values, rows in
+    order, and how many there are: (sum float32[dim], count int64[dim])."""
+    s = np.empty(ds.dim, dtype=np.float32)
+    cnt = np.empty(ds.dim, dtype=np.int64)
+    check(ds.e.lib.somhip_column_sums(ds.h, _p(s, _lib.c_float_p), _p(cnt, _lib.c_i64_p)))
+    return s, cnt
+
+
+def centered_products(ds, mean):
+    """lininit's second data pass (somhip_centered_products): R[i, j] = sum over the rows, in order and in fp32, of
+    (x[r, i] - mean[i]) * (x[r, j] - mean[j]) where both components are unmasked.  float32[dim, dim] as the ABI
+    returns it: j >= i filled, j < i left 0."""
+    mean = _arr(mean, np.float32)
+    assert mean.shape == (ds.dim,)
+    r = np.empty((ds.dim, ds.dim), dtype=np.float32)
+    check(ds.e.lib.somhip_centered_products(ds.h, _p(mean, _lib.c_float_p), _p(r, _lib.c_float_p)))
+    return r
+
+
 def orand_stream(seed, count):
     """The reference's LCG (lvq_pak.c:459-473: next = next * 23 % 100000001, value = next % 32767) as a numpy
     array of `count` draws after init_random(seed): state_k = seed * 23^k mod M, evaluated blockwise."""

@@ -130,6 +130,48 @@ def lininit_golden(exp, d):
             run("lininit", "-din", d(data), "-cout", out, *args)
             res[tag] = {"data": data, "args": [str(a) for a in args], "md5": md5(out)}
     exp["som"]["lininit"] = res
+    exp["som"]["lininit_edges"] = lininit_edges_golden()
+
+
+def lininit_edges_golden():
+    """lininit at the tile edges of its two data passes (tests/lininit_replay.py: GEN_CASES of the generator stream,
+    written as %.9g text for the reference as in c2_full_golden, and TEXT_CASES of the seeded masked text), both
+    topologies and two seeds each; and on two rows, where the reference gives up.  Only md5s and messages are kept:
+    the tests regenerate the data from the same specs."""
+    import tempfile
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import lininit_replay as LR
+    from som_lvq_pak_amd import engine as E
+    res = {"data": {}}
+    with tempfile.TemporaryDirectory() as tmp:
+        sources = []
+        for dim, n in LR.GEN_CASES:
+            seed, k = LR.gen_spec(dim, n)
+            dat = os.path.join(tmp, "gen_%dx%d.dat" % (dim, n))
+            LR.write_text(dat, E.gen_rows(seed, k, dim, 0, n)[0])
+            sources.append(("gen_%dx%d" % (dim, n), dat, {"gen": "gen:k=%d,dim=%d,n=%d,seed=%d" % (k, dim, n, seed)}))
+        for dim, n in LR.TEXT_CASES:
+            dat = os.path.join(tmp, "masked_%dx%d.dat" % (dim, n))
+            LR.write_masked_text(dat, dim, n)
+            sources.append(("masked_%dx%d" % (dim, n), dat, {"masked_text": [dim, n]}))
+        for tag, dat, src in sources:
+            runs = []
+            for args in (["-xdim", 6, "-ydim", 4, "-topol", "hexa", "-neigh", "bubble", "-rand", 123],
+                         ["-xdim", 5, "-ydim", 7, "-topol", "rect", "-neigh", "gaussian", "-rand", 5]):
+                out = os.path.join(tmp, "out.cod")
+                run("lininit", "-din", dat, "-cout", out, *args)
+                runs.append({"args": [str(a) for a in args], "md5": md5(out)})
+            res["data"][tag] = dict(src, runs=runs)
+        dat, out = os.path.join(tmp, "two.dat"), os.path.join(tmp, "two.cod")
+        LR.write_text(dat, E.gen_rows(1, 2, 4, 0, 2)[0])
+        two = {}
+        for tool, extra in (("lininit", []), ("mapinit", ["-init", "lin"])):
+            p = subprocess.run([ref_tool(tool)] + extra + ["-din", dat, "-cout", out, "-xdim", "4", "-ydim", "3", "-topol", "hexa",
+                                                           "-neigh", "bubble", "-rand", "3", "-v", "0"],
+                               stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+            two[tool] = {"returncode": p.returncode, "stderr_lines": p.stderr.splitlines(), "wrote_file": os.path.exists(out)}
+        res["two_rows"] = two
+    return res
 
 
 def lvq_tool_goldens(exp, d):
@@ -229,6 +271,12 @@ def main():
         build()
         exp = json.load(open(os.path.join(CLI, "expected.json")))
         c2_full_golden(exp)
+        json.dump(exp, open(os.path.join(CLI, "expected.json"), "w"), indent=1, sort_keys=True)
+        return
+    if "--lininit" in sys.argv:            # refresh only that section of expected.json
+        build()
+        exp = json.load(open(os.path.join(CLI, "expected.json")))
+        lininit_golden(exp, lambda f: os.path.join(DATA, f))
         json.dump(exp, open(os.path.join(CLI, "expected.json"), "w"), indent=1, sort_keys=True)
         return
     if "--lvq-tools" in sys.argv:          # refresh only that section of expected.json

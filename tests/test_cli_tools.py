@@ -360,6 +360,43 @@ def test_lininit_matches_reference(tools, tmp_path):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("tag", sorted(EXPECTED["som"]["lininit_edges"]["data"]))
+def test_lininit_matches_reference_at_tile_edges(tools, tmp_path, tag):
+    """lininit where its two data passes have second blocks, skipped blocks and ragged row blocks (dim 17 .. 512):
+    `-din gen:...` sources and the seeded masked text of tests/lininit_replay.py, both topologies and two seeds --
+    the bytes the real reference wrote for the same rows (it read the generator stream as %.9g text)"""
+    import lininit_replay as LR
+    ex = EXPECTED["som"]["lininit_edges"]["data"][tag]
+    if "gen" in ex:
+        din = ex["gen"]
+    else:
+        din = tmp_path / (tag + ".dat")
+        LR.write_masked_text(din, *ex["masked_text"])
+    for k, r in enumerate(ex["runs"]):
+        out = tmp_path / ("%s_%d.cod" % (tag, k))
+        run("lininit", "-din", din, "-cout", out, *r["args"], "-v", 0)
+        assert md5(out) == r["md5"], (tag, r["args"])
+
+
+@pytest.mark.gpu
+def test_lininit_gives_up_on_two_rows_like_the_reference(tools, tmp_path):
+    """fewer than three rows (som_rout.c:256): both tools print the reference's message, exit 1 and write no file"""
+    import lininit_replay as LR
+    from som_lvq_pak_amd import engine as E
+    want = EXPECTED["som"]["lininit_edges"]["two_rows"]
+    dat = tmp_path / "two.dat"
+    LR.write_text(dat, E.gen_rows(1, 2, 4, 0, 2)[0])
+    for tool, extra in (("lininit", []), ("mapinit", ["-init", "lin"])):
+        out = tmp_path / (tool + ".cod")
+        p = run(tool, *extra, "-din", dat, "-cout", out, "-xdim", 4, "-ydim", 3, "-topol", "hexa", "-neigh", "bubble",
+                "-rand", 3, "-v", 0, check=False)
+        assert want[tool]["returncode"] == 1 and not want[tool]["wrote_file"]
+        assert p.returncode == 1 and not os.path.exists(out)
+        assert "lininit_codes: Can't find eigenvectors" in p.stderr.splitlines()
+        assert "lininit_codes: Can't find eigenvectors" in want[tool]["stderr_lines"]
+
+
+@pytest.mark.gpu
 def test_whole_somexample_on_these_tools(tools, tmp_path):
     """reference Makefile:195-205 end to end with these binaries only:
     randinit -> vsom -> vsom -> qerror -> vcal -> visual"""
