@@ -132,6 +132,7 @@ struct PrefilterBufs {
   void *xt; uint4 *xhi, *xlo, *xrow;      // tiles: fp32 xt[sb][q][32][4] or bf16 hi | lo [sb][kb][32][8]; xrow: sample-major
   uint32_t *gmin, *gcount, *colcount, *paircount;            // re-rank counters (preset in pf_prepare: rerank_presets)
   float *tau1; uint32_t *gmin1, *l2cnt; uint16_t *l2list;   // two levels: level 1's window and minimum, level 2's lists
+  uint4 *l2out;                           // two levels, nearest row: level 2's (mask, minimum) per list slot, else null
   float *xw;                              // shard exchange: delta1, max(delta1, 3 delta3), delta3 per sample
 };
 static int bind_prefilter(somhip_codebook *cb, const ScanPlan &p, bool exchange, PrefilterBufs *b) {
@@ -165,6 +166,7 @@ static int bind_prefilter(somhip_codebook *cb, const ScanPlan &p, bool exchange,
     CHK(scratch(e, SLOT_SAMPLE_ROWS, xt_bytes / sizeof(uint4), &b->xrow));      // (two levels: bf16 tiles)
     CHK(scratch(e, SLOT_L2_STATE, 2 * (size_t)bpad + (size_t)ng, &b->tau1));    // 32-bit words: tau1 | gmin1 | l2cnt
     CHK(scratch(e, SLOT_L2_LIST, (size_t)ng * bpad, &b->l2list));
+    if (p.want == 1) CHK(scratch(e, SLOT_L2_OUT, (size_t)ng * bpad, &b->l2out));   // (top-K, LVQ: nothing reads it)
     b->gmin1 = reinterpret_cast<uint32_t *>(b->tau1 + bpad);
     b->l2cnt = b->gmin1 + bpad;
   }
@@ -301,7 +303,8 @@ static int pf_level2(somhip_codebook *cb, int64_t count, const ScanPlan &p, cons
   const dim3 sgrid = group_chunks(ng, bpad, 32, &chunk);
   {
     LaunchTimer t(e, KID_L2_SELECT);
-    hipLaunchKernelGGL(k_l2_select, dim3((unsigned)((bpad + 255) / 256), sgrid.y), dim3(256), 0, e->stream, ng, count, bpad, chunk,
+    // (a workgroup: 1024 samples x a chunk of groups)
+    hipLaunchKernelGGL(k_l2_select, dim3((unsigned)((bpad + 1023) / 1024), sgrid.y), dim3(256), 0, e->stream, ng, count, bpad, chunk,
                        (const float *)b.wmin, (const uint32_t *)b.gmin1, xbound ? (const float *)(b.xw + bpad) : (const float *)b.tau1,
                        b.l2cnt, b.l2list, xbound ? b.wmin : (float *)nullptr, (const float *)xbound);
   }
@@ -314,12 +317,12 @@ static int pf_level2(somhip_codebook *cb, int64_t count, const ScanPlan &p, cons
       hipLaunchKernelGGL(k_dist_l2_lds, dim3((unsigned)ng, 4), dim3(64 * L2_WAVES), a_bytes, e->stream, cb->v, d8, (const uint4 *)cb->d_chi,
                          (const uint4 *)cb->d_clo, (const uint4 *)b.xrow, (const float *)cb->d_cn,
                          (const float *)b.tau, bpad, (const uint32_t *)b.l2cnt, (const uint16_t *)b.l2list, b.wmin,
-                         b.wmask, e->d_stats + STAT_L2_PAIRS, l2_gmin);
+                         b.wmask, e->d_stats + STAT_L2_PAIRS, l2_gmin, b.l2out);
     } else
       hipLaunchKernelGGL(k_dist_l2, dim3((unsigned)ng, 8), dim3(256), 0, e->stream, cb->v, d8, (const uint4 *)cb->d_chi,
                          (const uint4 *)cb->d_clo, (const uint4 *)b.xhi, (const uint4 *)b.xlo, (const float *)cb->d_cn,
                          (const float *)b.tau, bpad, (const uint32_t *)b.l2cnt, (const uint16_t *)b.l2list, b.wmin,
-                         b.wmask, e->d_stats + STAT_L2_PAIRS, (const uint4 *)b.xrow, l2_gmin);
+                         b.wmask, e->d_stats + STAT_L2_PAIRS, (const uint4 *)b.xrow, l2_gmin, b.l2out);
   }
   HIPCHK(hipGetLastError());
   if (xbound) {
@@ -383,9 +386,10 @@ static int pf_rerank(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int
     if (!gmin_ready)
       hipLaunchKernelGGL(k_group_min, sgrid, dim3(256), 0, e->stream, ng, bpad, chunk, (const float *)b.wmin, b.gmin);
     const float *win = xbound ? (const float *)(b.xw + 2 * bpad) : (const float *)b.tau;
+    if (from_lists && !b.l2out) return fail("pf_rerank: no level-2 results in list order for this search");
     if (from_lists)
       hipLaunchKernelGGL(k_rerank_select_lists, dim3((unsigned)ng, 4), dim3(256), 0, e->stream, cb->v, count, bpad,
-                         (const uint32_t *)b.l2cnt, (const uint16_t *)b.l2list, (const float *)b.wmin, (const uint64_t *)b.wmask, win,
+                         (const uint32_t *)b.l2cnt, (const uint16_t *)b.l2list, (const uint4 *)b.l2out, win,
                          (const uint32_t *)b.gmin, b.gcount, pl.cap, pl.cap_col, pl.pairs, b.colcount, b.paircount, xbound);
     else
       hipLaunchKernelGGL(k_rerank_select, sgrid, dim3(256), 0, e->stream, cb->v, count, bpad, chunk,

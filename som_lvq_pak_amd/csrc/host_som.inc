@@ -225,7 +225,9 @@ static UpdatePlan som_update_plan(const somhip_codebook *cb, const somhip_datase
   p.gauss_gemm = G && gemm_form;
   // the winners' lattice coordinates: K4b decodes them itself from the keys (a division per (sample, row group), but no
   // launch) in a short run; a long run pays for the launch many times over (1024 groups x 32768 samples: members 201 -> 180 us, the decode launch 6)
-  p.decode = G || count >= 16384;                         // (the gaussian update needs the decoded winners itself)
+  // ... and from 8192 samples on where the map has 512 row groups and more: the 4 us of the launch are paid back per group
+  // (1024 groups x 8192 samples at radius 20 -> 1: members 121 -> 42 us with the two-phase form in one trip of 1024 x 8)
+  p.decode = G || count >= 16384 || (count >= 8192 && cb->v.ngroups >= 512);   // (the gaussian update needs the decoded winners itself)
   // the GEMM update walks a list from its end and stops once every unit's decay is below GEMM_CUT: K4b then makes only
   // the tail that walk can reach -- until it holds `tail_need` entries with every live unit in them: (1 - a_min)^need <
   // GEMM_CUT for the smallest rate a_min of the run, + one chunk so that the walk's last, whole chunk is there too
@@ -249,9 +251,9 @@ static UpdatePlan som_update_plan(const somhip_codebook *cb, const somhip_datase
     wide = p.tail_need == 0 || (double)p.tail_need > 3.0 * 1024.0 * full;
   }
   p.members_nt = wide ? 1024 : 256;
-  // (decoded winners, long run, lists not cut short: 8 samples per thread -- four trips over a 32768-vector run; what a
+  // (decoded winners, long run, lists not cut short: 8 samples per thread -- four trips over a 32768-vector run, one over 8192; what a
   // trip costs besides the membership arithmetic of the queued samples is its barriers and dependent loads)
-  p.members_rr = wide && !G && p.decode && p.reach_max >= 0 && count >= 16384 ? 8 : 4;
+  p.members_rr = wide && !G && p.decode && p.reach_max >= 0 && count >= 8192 ? 8 : 4;
   p.order = cb->v.ngroups <= 8192;                        // (k_order_groups holds the counts in LDS)
   if (gemm_form) {
     p.apply = APPLY_GEMM;

@@ -1010,9 +1010,14 @@ __global__ __launch_bounds__(512, 2) void k_dist_mfma_bf16_l1w16(CbView cb, int 
   }
 }
 
-// survivors of level 1, gathered by row group: list[g][0 .. cnt[g]) = the samples b with wmin1[g][b] <= gmin1[b] + tau1[b].
-// Grid: (256-sample columns, chunks of groups); thread = sample, a wave = 64 consecutive samples of one group per trip
-// (256 contiguous bytes of wmin; four groups' loads in flight), one list reservation per wave and group.
+// survivors of level 1, gathered by row group: list[g][0 .. cnt[g]) = the samples b with wmin1[g][b] <= gmin1[b] + tau1[b],
+// in no particular order.  Grid: (1024-sample blocks, chunks of groups).  A thread holds four consecutive samples: one
+// 16-byte load per group row (bpad is a multiple of 32, so the rows and every quad are aligned; count need not be a
+// multiple of 4: a quad may be partly live), a wave covers 1 KiB of a row per load and keeps sixteen rows' loads in flight
+// (16 KiB), one list reservation per wave and group.  The form before it -- a sample per thread, 256 bytes of a row per
+// wave and load, four times the waves and workgroups -- read the 128 MiB of a 32768-vector search in 53 us with one wave
+// resident per SIMD; this one takes 37 (profiles/members_selects_vs_parent.txt, with the variants that did no better:
+// 16-group chunks, a grid of 2 to 8 workgroups per CU walking several blocks each, the next trip's loads issued early).
 __global__ __launch_bounds__(256) void k_l2_select(int64_t ngroups, int64_t count, int64_t bpad, int64_t chunk,
                                                    const float *wmin, const uint32_t *__restrict__ gmin1,
                                                    const float *__restrict__ tau1, uint32_t *__restrict__ cnt,
@@ -1023,41 +1028,62 @@ __global__ __launch_bounds__(256) void k_l2_select(int64_t ngroups, int64_t coun
   // minimum -- with a bound from another shard a shard may keep no group at all for a sample, and what is left out must
   // never look like a candidate to the re-rank
   const int lane = threadIdx.x & 63;
-  const int64_t b = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  const int64_t b0 = (static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x) * 4;
   const int64_t g_lo = static_cast<int64_t>(blockIdx.y) * chunk;
   const int64_t g_hi = g_lo + chunk < ngroups ? g_lo + chunk : ngroups;
-  float thr = -3.4e38f;
-  if (b < count) {
-    const uint32_t o = gmin1[b];                         // order-preserving image of the float minimum (float_to_ordered)
-    thr = (xub ? xub[b] : __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o)) + tau1[b];
+  const bool inrow = b0 < bpad;                          // the quad lies inside the rows of wmin (count <= bpad), live or not
+  bool live[4];
+  float thr[4];
+#pragma unroll
+  for (int c = 0; c < 4; c++) { live[c] = b0 + c < count; thr[c] = -3.4e38f; }
+  if (inrow) {
+    const uint4 o4 = *reinterpret_cast<const uint4 *>(gmin1 + b0);   // order-preserving images of the float minima (float_to_ordered)
+    const float4 t4 = *reinterpret_cast<const float4 *>(tau1 + b0);
+    const uint32_t ov[4] = {o4.x, o4.y, o4.z, o4.w};
+    const float tv[4] = {t4.x, t4.y, t4.z, t4.w};
+#pragma unroll
+    for (int c = 0; c < 4; c++)
+      if (live[c]) thr[c] = (xub ? xub[b0 + c] : __uint_as_float((ov[c] & 0x80000000u) ? (ov[c] & 0x7FFFFFFFu) : ~ov[c])) + tv[c];
   }
-  const bool live = b < count;                           // (count <= bpad: the loads stay inside the rows of wmin)
   // sixteen groups per trip: their loads in flight together, and ONE vector atomic for the sixteen list reservations (lane k
-  // reserves for group g0 + k) -- a reservation per group and wave, each waited for in turn, was this kernel's time
+  // reserves for group g0 + k) -- a reservation per group and wave, each waited for in turn, was once this kernel's time
   // (64 round trips per wave: 90 us per 32768 samples whatever the size of the shard)
   const unsigned long long below = (1ull << lane) - 1ull;
   constexpr int GT = 16;
   for (int64_t g0 = g_lo; g0 < g_hi; g0 += GT) {
-    float v[GT];
+    float4 v[GT];
 #pragma unroll
-    for (int k = 0; k < GT; k++) v[k] = (live && g0 + k < g_hi) ? wmin[(g0 + k) * bpad + b] : 3.4e38f;
-    unsigned long long bal[GT];
+    for (int k = 0; k < GT; k++)
+      v[k] = (inrow && g0 + k < g_hi) ? *reinterpret_cast<const float4 *>(wmin + (g0 + k) * bpad + b0)
+                                      : make_float4(3.4e38f, 3.4e38f, 3.4e38f, 3.4e38f);
+    unsigned long long bal[GT][4];                       // [group][sample of the quad]
     uint32_t mine = 0;
 #pragma unroll
     for (int k = 0; k < GT; k++) {
-      const bool valid = live && g0 + k < g_hi;
-      const bool in = valid && v[k] <= thr;
-      bal[k] = __ballot(in);
-      if (mark && valid && !in) mark[(g0 + k) * bpad + b] = 3.4e38f;
-      if (lane == k) mine = static_cast<uint32_t>(__popcll(bal[k]));
+      const float vv[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
+      uint32_t n = 0;
+#pragma unroll
+      for (int c = 0; c < 4; c++) {
+        const bool valid = live[c] && g0 + k < g_hi;
+        const bool in = valid && vv[c] <= thr[c];
+        bal[k][c] = __ballot(in);
+        n += static_cast<uint32_t>(__popcll(bal[k][c]));
+        if (mark && valid && !in) mark[(g0 + k) * bpad + b0 + c] = 3.4e38f;
+      }
+      if (lane == k) mine = n;
     }
     uint32_t base = 0;
     if (mine) base = atomicAdd(&cnt[g0 + lane], mine);   // (mine != 0 only in lanes 0..15 and only for groups below g_hi)
 #pragma unroll
     for (int k = 0; k < GT; k++) {
-      if (bal[k] == 0ull) continue;                      // wave-uniform
-      const uint32_t at = __shfl(base, k, WAVE);
-      if ((bal[k] >> lane) & 1ull) list[(g0 + k) * bpad + at + __popcll(bal[k] & below)] = static_cast<uint16_t>(b);
+      if ((bal[k][0] | bal[k][1] | bal[k][2] | bal[k][3]) == 0ull) continue;   // wave-uniform
+      uint32_t at = __shfl(base, k, WAVE);               // the wave's entries of group g0 + k: first samples b0, then b0 + 1, ...
+      uint16_t *lg = list + (g0 + k) * bpad;
+#pragma unroll
+      for (int c = 0; c < 4; c++) {
+        if ((bal[k][c] >> lane) & 1ull) lg[at + __popcll(bal[k][c] & below)] = static_cast<uint16_t>(b0 + c);
+        at += static_cast<uint32_t>(__popcll(bal[k][c]));
+      }
     }
   }
 }
@@ -1065,7 +1091,8 @@ __global__ __launch_bounds__(256) void k_l2_select(int64_t ngroups, int64_t coun
 // level 2: the three-product GEMM of one row group against tiles of 32 of ITS surviving samples; one wave per tile,
 // operands straight from global memory (each lane loads the 16-byte pieces the MFMA wants from it: for B the piece
 // of its own gathered sample, from the sample-major copy xrow of k_pack_samples_bf16 -- consecutive bytes per sample,
-// so whole cache lines are used).  Writes wmin / wmask of the (group, sample) pairs it covers.
+// so whole cache lines are used).  Writes wmin / wmask of the (group, sample) pairs it covers and, where lout is given, the
+// same minimum and mask at the pair's slot of the group's list (lout[g][slot] = mask lo, mask hi, minimum, 0).
 // (The host always passes xrow.  The select on it below stays: without it hipcc schedules the k-step loop with one more
 // full wait for memory, and the kernel measured 0.066-0.069 ms per launch against 0.061-0.062 at the configs[4] shape.)
 __global__ __launch_bounds__(256) void k_dist_l2(CbView cb, int d8, const uint4 *__restrict__ chi, const uint4 *__restrict__ clo,
@@ -1074,7 +1101,7 @@ __global__ __launch_bounds__(256) void k_dist_l2(CbView cb, int d8, const uint4 
                                                  const uint32_t *__restrict__ cnt, const uint16_t *__restrict__ list,
                                                  float *__restrict__ wmin, uint64_t *__restrict__ wmask,
                                                  unsigned long long *__restrict__ stats, const uint4 *__restrict__ xrow,
-                                                 uint32_t *__restrict__ gmin = nullptr) {
+                                                 uint32_t *__restrict__ gmin = nullptr, uint4 *__restrict__ lout = nullptr) {
   constexpr int DEPTH = 2;             // k-steps whose operands are requested together (configs[4] shape: 62 us per launch against 65 at 4)
   const int64_t g = blockIdx.x;
   const int n = static_cast<int>(cnt[g]);
@@ -1145,6 +1172,9 @@ __global__ __launch_bounds__(256) void k_dist_l2(CbView cb, int d8, const uint4 
     if (half == 0 && valid) {
       wmin[g * bpad + b] = m;
       wmask[g * bpad + b] = static_cast<uint64_t>(bits) | (static_cast<uint64_t>(other) << 32);
+      // lout (nearest-row search): the same two results once more at the entry's own list slot, a coalesced 16-byte store
+      // per lane -- k_rerank_select_lists reads list, minimum and mask in a row instead of gathering wmin and wmask by sample
+      if (lout) lout[g * bpad + slot] = make_uint4(bits, other, __float_as_uint(m), 0u);
       // the sample's smallest three-product minimum (what k_group_min would find: a group that level 1 left out keeps a
       // level-1 value above it, see the window's condition (ii)); ordered image of the float, no value returned
       if (gmin) { const uint32_t u = __float_as_uint(m); atomicMin(gmin + b, (u & 0x80000000u) ? ~u : (u | 0x80000000u)); }
@@ -1170,7 +1200,8 @@ __global__ __launch_bounds__(64 * L2_WAVES, 1) void k_dist_l2_lds(CbView cb, int
                                                         const float *__restrict__ cn, const float *__restrict__ tau, int64_t bpad,
                                                         const uint32_t *__restrict__ cnt, const uint16_t *__restrict__ list,
                                                         float *__restrict__ wmin, uint64_t *__restrict__ wmask,
-                                                        unsigned long long *__restrict__ stats, uint32_t *__restrict__ gmin = nullptr) {
+                                                        unsigned long long *__restrict__ stats, uint32_t *__restrict__ gmin = nullptr,
+                                                        uint4 *__restrict__ lout = nullptr) {
   extern __shared__ uint4 s_l2a[];                         // [hi | lo][d8][64]
   typedef __attribute__((address_space(3))) void lds_void;
   typedef const __attribute__((address_space(1))) void glb_void;
@@ -1259,6 +1290,9 @@ __global__ __launch_bounds__(64 * L2_WAVES, 1) void k_dist_l2_lds(CbView cb, int
     if (half == 0 && valid) {
       wmin[g * bpad + b] = m;
       wmask[g * bpad + b] = static_cast<uint64_t>(bits) | (static_cast<uint64_t>(other) << 32);
+      // lout (nearest-row search): the same two results once more at the entry's own list slot, a coalesced 16-byte store
+      // per lane -- k_rerank_select_lists reads list, minimum and mask in a row instead of gathering wmin and wmask by sample
+      if (lout) lout[g * bpad + slot] = make_uint4(bits, other, __float_as_uint(m), 0u);
       // the sample's smallest three-product minimum (what k_group_min would find: a group that level 1 left out keeps a
       // level-1 value above it, see the window's condition (ii)); ordered image of the float, no value returned
       if (gmin) { const uint32_t u = __float_as_uint(m); atomicMin(gmin + b, (u & 0x80000000u) ? ~u : (u | 0x80000000u)); }

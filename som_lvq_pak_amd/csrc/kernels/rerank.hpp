@@ -673,15 +673,21 @@ __global__ __launch_bounds__(256) void k_rerank_select(CbView cb, int64_t count,
 // the pre-filter results are still bit-exact": a group that level 1 leaves out keeps a level-1 value above anything the
 // re-rank looks at; under a shard-exchange bound k_l2_select writes 3.4e38 over it), so only list[g][0 .. cnt[g]) is
 // walked: one entry per thread, the row group in blockIdx.x, its entries dealt to the gridDim.y workgroups of the row.
-// An entry that passes reserves its rows' room in the segment of its 32-sample column itself (a few dozen
-// reservations per segment and launch, spread over all the segments); the order inside a segment is free, K2p folds
-// with an atomic minimum.  Per-column statistics and gcount as in k_rerank_select: the per-column maximum is the
-// largest running count any sample's atomicAdd has seen, which is the sample's final count whatever the order.
+// Level 2 has left each entry's minimum and mask at the entry's own slot (lout[g][slot] = mask lo, mask hi, minimum), so
+// list and results are read in a row; only gmin[b] and tau[b] (or xub[b]) are gathered.
+// Atomics: the entries of a wave that pass and lie in the same 32-sample column act together -- the lowest lane among
+// them (the column's leader) reserves their rows' room in the column's segment with ONE atomic and adds their group and
+// row totals; the members take their places behind the leader's base in lane order.  Who leads whom, the offsets and
+// the totals are worked out with ballots and scalar lane reads before any atomic is issued, so a wave issues one
+// reservation instruction (the leaders' lanes) and, with it, one instruction for the samples' own counts gcount[b] (a
+// group's list holds a sample once: distinct addresses) and waits for both once.  The order inside a segment is free,
+// K2p folds with an atomic minimum.  The per-column maximum is the largest running count any sample's atomicAdd has
+// seen, which is the sample's final count whatever the order; a leader folds its members' values first.  An overflow:
+// base + the column's total of the wave > cap_col, which is the last member's own test.
 __global__ __launch_bounds__(256) void k_rerank_select_lists(CbView cb, int64_t count, int64_t bpad,
                                                              const uint32_t *__restrict__ l2cnt,
                                                              const uint16_t *__restrict__ l2list,
-                                                             const float *__restrict__ wmin,
-                                                             const uint64_t *__restrict__ wmask,
+                                                             const uint4 *__restrict__ lout,
                                                              const float *__restrict__ tau,
                                                              const uint32_t *__restrict__ gmin,
                                                              uint32_t *__restrict__ gcount,
@@ -691,6 +697,7 @@ __global__ __launch_bounds__(256) void k_rerank_select_lists(CbView cb, int64_t 
                                                              uint32_t *__restrict__ pair_count,
                                                              const float *__restrict__ xub = nullptr) {
   const int64_t g = blockIdx.x;
+  const int lane = threadIdx.x & 63;
   const uint32_t ncols = static_cast<uint32_t>(bpad / 32);
   const uint32_t n = l2cnt[g] < static_cast<uint32_t>(bpad) ? l2cnt[g] : static_cast<uint32_t>(bpad);
   // padding rows of the last group: bit 32h+16i+r is row 32i + (r&3) + 8(r>>2) + 4h (k_rerank_select's rule)
@@ -702,29 +709,77 @@ __global__ __launch_bounds__(256) void k_rerank_select_lists(CbView cb, int64_t 
       if (g * WAVE + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * h < cb.n) keep |= 1ull << t;
     }
   }
-  for (uint32_t e = blockIdx.y * blockDim.x + threadIdx.x; e < n; e += gridDim.y * blockDim.x) {
-    const int64_t b = l2list[g * bpad + e];
-    if (b >= count) continue;                            // (k_l2_select files live samples only)
-    const float thr = (xub ? xub[b] : ordered_to_float(gmin[b])) + tau[b];
-    if (!(wmin[g * bpad + b] <= thr)) continue;
-    unsigned long long mm = wmask[g * bpad + b] & keep;
-    const unsigned c = __popcll(mm);
-    if (c == 0) continue;
+  // (e0 is the same for the whole workgroup: every lane of a wave takes part in the ballots below)
+  for (uint32_t e0 = blockIdx.y * blockDim.x; e0 < n; e0 += gridDim.y * blockDim.x) {
+    const uint32_t e = e0 + threadIdx.x;
+    int64_t b = 0;
+    unsigned long long mm = 0;
+    if (e < n) {
+      b = l2list[g * bpad + e];
+      const uint4 o = lout[g * bpad + e];
+      if (b < count) {                                   // (k_l2_select files live samples only)
+        const float thr = (xub ? xub[b] : ordered_to_float(gmin[b])) + tau[b];
+        if (__uint_as_float(o.z) <= thr) mm = (static_cast<unsigned long long>(o.x) | (static_cast<unsigned long long>(o.y) << 32)) & keep;
+      }
+    }
+    const uint32_t c = static_cast<uint32_t>(__popcll(mm));
+    const bool pass = c != 0;
+    const unsigned long long passing = __ballot(pass);
+    if (passing == 0ull) continue;                       // wave-uniform
     const uint32_t col = static_cast<uint32_t>(b >> 5);
-    unsigned at = atomicAdd(col_count + col, c);
-    if (at + c > cap_col) atomicMax(pair_count, cap + 1);
-    atomicAdd(col_count + ncols * 1 + col, 1u);
-    atomicAdd(col_count + ncols * 2 + col, c);
-    const unsigned before = atomicAdd(gcount + b, 1u);
-    atomicMax(col_count + ncols * 3 + col, before + 1u);
-    uint2 *seg = pairs + static_cast<size_t>(col) * cap_col;
-    while (mm) {
-      const int t = __builtin_ctzll(mm);
-      mm &= mm - 1;
-      const int h = t >> 5, i = (t >> 4) & 1, r = t & 15;
-      if (at < cap_col)
-        seg[at] = make_uint2(static_cast<uint32_t>(b), static_cast<uint32_t>(g * WAVE + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * h));
-      at++;
+    // the wave's distinct columns, one per turn: leader, members' offsets in lane order, totals
+    uint32_t off = 0, tot = 0, members = 0;
+    int leader = lane;
+    for (unsigned long long todo = passing; todo;) {
+      const int L = __builtin_ctzll(todo);
+      const uint32_t lcol = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(col), L));
+      const bool mine = pass && col == lcol;
+      const unsigned long long same = __ballot(mine);
+      uint32_t run = 0;
+      for (unsigned long long sset = same; sset; sset &= sset - 1) {
+        const int j = __builtin_ctzll(sset);
+        if (j == lane) off = run;
+        run += static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(c), j));
+      }
+      if (mine) { tot = run; members = static_cast<uint32_t>(__popcll(same)); leader = L; }
+      todo &= ~same;
+    }
+    const bool leads = pass && leader == lane;
+    uint32_t base = 0, before = 0;
+    if (leads) base = atomicAdd(col_count + col, tot);
+    if (pass) before = atomicAdd(gcount + b, 1u);
+    if (leads) {
+      atomicAdd(col_count + ncols * 1 + col, members);
+      atomicAdd(col_count + ncols * 2 + col, tot);
+      if (base + tot > cap_col) atomicMax(pair_count, cap + 1);
+    }
+    // the largest count seen in each column of the wave, folded by its leader
+    uint32_t most = 0;
+    for (unsigned long long todo = passing; todo;) {
+      const int L = __builtin_ctzll(todo);
+      const uint32_t lcol = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(col), L));
+      const unsigned long long same = __ballot(pass && col == lcol);
+      uint32_t m = 0;
+      for (unsigned long long sset = same; sset; sset &= sset - 1) {
+        const uint32_t v = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(before), __builtin_ctzll(sset))) + 1u;
+        m = v > m ? v : m;
+      }
+      if (lane == L) most = m;
+      todo &= ~same;
+    }
+    if (leads) atomicMax(col_count + ncols * 3 + col, most);
+    const unsigned lbase = static_cast<unsigned>(__shfl(static_cast<int>(base), leader, WAVE));   // (every lane takes part)
+    if (pass) {
+      unsigned at = lbase + off;
+      uint2 *seg = pairs + static_cast<size_t>(col) * cap_col;
+      while (mm) {
+        const int t = __builtin_ctzll(mm);
+        mm &= mm - 1;
+        const int h = t >> 5, i = (t >> 4) & 1, r = t & 15;
+        if (at < cap_col)
+          seg[at] = make_uint2(static_cast<uint32_t>(b), static_cast<uint32_t>(g * WAVE + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * h));
+        at++;
+      }
     }
   }
 }

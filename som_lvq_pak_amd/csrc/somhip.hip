@@ -140,6 +140,8 @@ enum ScratchSlot {
   SLOT_TOPK_GROUPS,        // top-K re-rank by row group: the groups' lists and the passes (bind_topk_groups)
   SLOT_TAIL_START,         // GEMM update: where each group's list tail starts
   SLOT_SAMPLE_ROWS,        // two-level pre-filter: the sample-major copy of the tiles, from prepare to level 2
+  SLOT_L2_OUT,             // two-level pre-filter, nearest row: level 2's minimum and mask of every list entry at the entry's
+                           // own slot, from level 2 to the re-rank's selection (k_rerank_select_lists)
   SLOT_COUNT
 };
 
