@@ -261,6 +261,41 @@ int  somhip_som_train(somhip_codebook *cb, somhip_dataset *ds, const somhip_som_
 int  somhip_som_auto_batch(const somhip_som_params *p, int64_t n_units, int topol, int neigh, int64_t iter,
                            int64_t *batch_start, int64_t *batch_len);
 
+/* ---- map sets: many maps of one shape, trained at once ---------------------------
+ * What vfind does: N maps that share shape, data and schedule and differ only in their initial rows.  The online
+ * algorithm on ONE small map is one launch per iteration and the launch is the cost (a 12x8x5 map is one workgroup of
+ * a 256-CU chip).  A map set keeps every map on the device, row-major [n_maps][n_rows][dim]; training gives each map a
+ * workgroup that holds it in LDS for a whole chunk of iterations (kernels/mapset.hpp), so a chunk is one launch however
+ * many maps there are.  Every map comes out as somhip_som_train(batch 1) on a codebook of its rows leaves it, bit for
+ * bit, traces included.
+ * Shapes: hexa / rect maps whose LDS image, dim x (n_rows rounded up to 64) x 4 bytes, is at most 128 KiB (of the CU's
+ * 160 KiB); somhip_mapset_create refuses larger ones with both numbers in its message, and somhip_debug_mapset_plan
+ * answers the same question without a GPU.
+ * A set whose engine was destroyed keeps a valid handle for somhip_mapset_destroy only (as codebooks do). */
+typedef struct somhip_mapset somhip_mapset;
+int  somhip_mapset_create(somhip_engine *e, const float *rows /*[n_maps][n_rows][dim]*/, int n_maps, int64_t n_rows,
+                          int dim, int topol, int neigh, int xdim, int ydim, somhip_mapset **out);
+int  somhip_mapset_download(somhip_mapset *ms, int first_map, int n_maps, float *rows);
+int  somhip_mapset_upload(somhip_mapset *ms, int first_map, int n_maps, const float *rows);
+void somhip_mapset_destroy(somhip_mapset *ms);
+/* som_training (som_rout.c:556-671), batch 1, for every map of the set at once; p->batch must be 1.  start_iter, count
+ * and data_first as in somhip_som_train: a run continued across calls equals one call.
+ * trace_index / trace_diff: NULL or [n_maps][p->count], with -2 / -3 as somhip_som_train */
+int  somhip_mapset_train(somhip_mapset *ms, somhip_dataset *ds, const somhip_som_params *p,
+                         int32_t *trace_index, float *trace_diff);
+/* find_winner_euc of data rows [first, first+count) against every map: index / diff / ret [n_maps][count] (ret may be
+ * NULL); a sample with every component masked gives ret 0 and index -2, as somhip_find_winners */
+int  somhip_mapset_winners(somhip_mapset *ms, somhip_dataset *ds, int64_t first, int64_t count,
+                           int32_t *index, float *diff, int32_t *ret);
+/* host arithmetic only, no GPU: out[0] = the shape fits, out[1] = threads per workgroup, out[2] = units per thread,
+ * out[3] = LDS bytes per workgroup, out[4] = iterations per launch, out[5] = masked data, out[6..7] = 0
+ * (out[1..3] are 0 where the shape does not fit) */
+int  somhip_debug_mapset_plan(int64_t n_rows, int dim, int masked, int32_t out[8]);
+/* HIP-event totals of the two set kernels since somhip_timing_reset, while somhip_timing_enable is on: [0] k_mapset_train,
+ * [1] k_mapset_winners.  (The table of somhip_kernel_count / somhip_kernel_name is closed -- callers index it -- so these
+ * two are not in it.) */
+int  somhip_mapset_timing(somhip_engine *e, int64_t launches[2], double total_ms[2]);
+
 /* ---- lvq1/olvq1/lvq2/lvq3_training (lvq_rout.c:498,584,702,808) --------------
  * kind = SOMHIP_LVQ1..LVQ3.  talpha (host, [n_rows], in/out) = OLVQ1's per-code
  * rates, initialised by the caller the way lvq_rout.c:614-627 does; `alpha` is also

@@ -83,6 +83,15 @@ SIGNATURES = {
     "somhip_find_winners": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int,
                                       c_i32_p, c_float_p, c_i32_p]),
     "somhip_som_train": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(SomParams), c_i32_p, c_float_p]),
+    "somhip_mapset_create": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.POINTER(C.c_void_p)]),
+    "somhip_mapset_download": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_float_p]),
+    "somhip_mapset_upload": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_float_p]),
+    "somhip_mapset_destroy": (None, [C.c_void_p]),
+    "somhip_mapset_train": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(SomParams), c_i32_p, c_float_p]),
+    "somhip_mapset_winners": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, c_i32_p, c_float_p, c_i32_p]),
+    "somhip_debug_mapset_plan": (C.c_int, [C.c_int64, C.c_int, C.c_int, c_i32_p]),
+    "somhip_mapset_timing": (C.c_int, [C.c_void_p, c_i64_p, c_double_p]),
     "somhip_som_auto_batch": (C.c_int, [C.POINTER(SomParams), C.c_int64, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_int64),
                                         C.POINTER(C.c_int64)]),
     "somhip_lvq_train": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(LvqParams), c_float_p, c_i32_p,

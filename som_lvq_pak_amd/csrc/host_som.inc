@@ -25,10 +25,13 @@ struct ThreshCache {
   }
 };
 
-static int som_scalars(const somhip_codebook *cb, const somhip_dataset *ds, const somhip_som_params *p,
+// what the scalars need to know of the map: a codebook's lattice, or a map set's
+struct MapLattice { int topol, neigh, xdim, ydim; };
+static MapLattice lattice_of(const somhip_codebook *cb) { return MapLattice{cb->v.topol, cb->v.neigh, cb->v.xdim, cb->ydim}; }
+static int som_scalars(const MapLattice &lat, const somhip_dataset *ds, const somhip_som_params *p,
                        int64_t it0, int64_t cnt, int64_t row0, StepScalars *out) {
-  const bool gauss = cb->v.neigh == SOMHIP_NEIGH_GAUSSIAN;
-  const bool small_map = cb->v.xdim <= 1024 && cb->ydim <= 1024;
+  const bool gauss = lat.neigh == SOMHIP_NEIGH_GAUSSIAN;
+  const bool small_map = lat.xdim <= 1024 && lat.ydim <= 1024;
   ThreshCache tc;
   for (int64_t j = 0; j < cnt; j++) {
     int64_t le = it0 + j, r = (row0 + j) % ds->n;
@@ -42,7 +45,7 @@ static int som_scalars(const somhip_codebook *cb, const somhip_dataset *ds, cons
     s.fixed = -1;
     // lattice rows a neighbourhood of this radius can span: hexa rows are sqrt(0.75)
     // apart (som_rout.c:451), rect rows 1 apart; +1 keeps it conservative
-    double reach = gauss ? 1e9 : (trad > 0.0f ? (double)trad / (cb->v.topol == SOMHIP_TOPOL_RECT ? 1.0 : 0.8660254037844386) + 1.0 : 1.0);
+    double reach = gauss ? 1e9 : (trad > 0.0f ? (double)trad / (lat.topol == SOMHIP_TOPOL_RECT ? 1.0 : 0.8660254037844386) + 1.0 : 1.0);
     s.reach = reach > 1e6 ? 1000000 : (int32_t)reach;
     if (!ds->all_masked.empty() && ds->all_masked[(size_t)r]) s.reach = -1;
     if (p->use_fixed && !ds->fixed_xy.empty() && ds->fixed_xy[(size_t)(2 * r)] >= 0) {
@@ -135,7 +138,7 @@ static int som_train_online(somhip_codebook *cb, somhip_dataset *ds, const somhi
   for (int64_t off = 0; off < p->count; off += CH) {
     int64_t c = std::min(CH, p->count - off);
     int64_t it0 = p->start_iter + off, row0 = (p->data_first + off) % ds->n;
-    CHK(som_scalars(cb, ds, p, it0, c, row0, hsc.data() + 1));
+    CHK(som_scalars(lattice_of(cb), ds, p, it0, c, row0, hsc.data() + 1));
     for (int64_t j = 0; j < c; j++) hrow[(size_t)j + 1] = (row0 + j) % ds->n;
     HIPCHK(hipMemcpyAsync(sc + 1, hsc.data() + 1, sizeof(StepScalars) * (size_t)c, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipMemcpyAsync(rowidx + 1, hrow.data() + 1, sizeof(int64_t) * (size_t)c, hipMemcpyHostToDevice, e->stream));
@@ -374,7 +377,7 @@ extern "C" int somhip_debug_update_plan(somhip_codebook *cb, somhip_dataset *ds,
   if (cb->v.topol < SOMHIP_TOPOL_HEXA) return fail("somhip_debug_update_plan: codebook is not a map");
   if (!p || !out || count <= 0) return fail("somhip_debug_update_plan: null argument, or count %lld < 1", (long long)count);
   std::vector<StepScalars> sc((size_t)count);
-  CHK(som_scalars(cb, ds, p, batch_start_iter, count, data_first % ds->n, sc.data()));
+  CHK(som_scalars(lattice_of(cb), ds, p, batch_start_iter, count, data_first % ds->n, sc.data()));
   const UpdatePlan u = som_update_plan(cb, ds, data_first % ds->n, count, sc.data());
   const int32_t v[16] = {u.apply, u.qw, u.off32, u.ntw, u.decode, u.members_nt, u.members_rr, u.entry, u.gauss_gemm, u.tail,
                          (int32_t)u.tail_need, u.reach_max, u.order, (int32_t)u.grid.x, (int32_t)u.block.x, 0};
@@ -394,7 +397,7 @@ extern "C" int somhip_som_batch_update(somhip_codebook *cb, somhip_dataset *ds,
   int slot;
   CHK(scratch(e, SLOT_CALL_B, (size_t)count, &dsc));
   CHK(pin_acquire(e, sizeof(StepScalars) * (size_t)count, &hsc, &slot));
-  CHK(som_scalars(cb, ds, p, batch_start_iter, count, data_first % ds->n, (StepScalars *)hsc));
+  CHK(som_scalars(lattice_of(cb), ds, p, batch_start_iter, count, data_first % ds->n, (StepScalars *)hsc));
   CHK(pin_upload(e, slot, dsc, sizeof(StepScalars) * (size_t)count));
   return som_update_run(cb, ds, data_first % ds->n, count, dev_keys, (const StepScalars *)dsc, (const StepScalars *)hsc);   // asynchronous
 } ABI_CATCH(somhip_som_batch_update)
@@ -501,7 +504,7 @@ static int som_train_batched(somhip_codebook *cb, somhip_dataset *ds, const somh
     int slot;
     CHK(pin_acquire(e, sizeof(StepScalars) * (size_t)c, &hscv, &slot));
     StepScalars *hsc = (StepScalars *)hscv;
-    CHK(som_scalars(cb, ds, p, it0, c, row0, hsc));
+    CHK(som_scalars(lattice_of(cb), ds, p, it0, c, row0, hsc));
     CHK(pin_upload(e, slot, dsc, sizeof(StepScalars) * (size_t)c));
     CHK(scan_keys_top1(cb, ds, row0, c, dkeys));
     CHK(som_update_run(cb, ds, row0, c, (const uint64_t *)dkeys, (const StepScalars *)dsc, hsc));

@@ -28,6 +28,7 @@
 #include "kernels/som_update.hpp"
 #include "kernels/som_update_gemm.hpp"
 #include "kernels/som_online.hpp"
+#include "kernels/mapset.hpp"
 #include "kernels/rerank.hpp"
 #include "kernels/prefilter_l1_ring.hpp"
 #include "kernels/lvq.hpp"

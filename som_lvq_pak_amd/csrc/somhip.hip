@@ -85,7 +85,11 @@ static const char *kKernelNames[KID_COUNT] = {
   SOMHIP_KERNEL_IDS(X)
 #undef X
 };
-static_assert(KID_COUNT <= 64, "somhip_timing_select's mask has one bit per kernel id");
+// The table above is what somhip_kernel_count / somhip_kernel_name publish, and it is closed: callers index it and select
+// from it by bit.  Kernels added since are timed by LaunchTimer all the same, under ids that follow the table; an entry
+// point of their own reports them (somhip_mapset_timing).
+enum TimedOnlyId { KID_MAPSET_TRAIN = KID_COUNT, KID_MAPSET_WINNERS, KID_TIMED };
+static_assert(KID_TIMED <= 64, "somhip_timing_select's mask has one bit per kernel id");
 extern "C" int somhip_kernel_count(void) { return KID_COUNT; }
 extern "C" const char *somhip_kernel_name(int i) { return (i >= 0 && i < KID_COUNT) ? kKernelNames[i] : ""; }
 
@@ -146,7 +150,8 @@ enum ScratchSlot {
 };
 
 // the kernels whose dynamic LDS limit an engine raises before their first launch (raise_lds_limit): bits of lds_raised
-enum LdsKernel { LDS_LVQ_APPLY, LDS_LVQ_APPLY_MASKED, LDS_LVQ_COMPONENTS, LDS_DIST_L2, LDS_L1_RING, LDS_PREP_ROWMAJOR };
+enum LdsKernel { LDS_LVQ_APPLY, LDS_LVQ_APPLY_MASKED, LDS_LVQ_COMPONENTS, LDS_DIST_L2, LDS_L1_RING, LDS_PREP_ROWMAJOR,
+                 LDS_MAPSET_TRAIN /* + 2 GAUSS + MASKED: four bits */, LDS_MAPSET_WINNERS = LDS_MAPSET_TRAIN + 4 /* + MASKED: two bits */ };
 constexpr int PIN_RING = 4;       // pinned staging buffers of pin_acquire, a power of two
 constexpr int LVQ_EV_RING = 8;    // batches of the exact LVQ loop in flight (lvq_train_batched)
 
@@ -179,8 +184,8 @@ struct somhip_engine {
   struct Pending { int kid; hipEvent_t a, b; };
   std::vector<Pending> pending;
   std::vector<hipEvent_t> pool;
-  int64_t launches[KID_COUNT] = {0};
-  double total_ms[KID_COUNT] = {0};
+  int64_t launches[KID_TIMED] = {0};
+  double total_ms[KID_TIMED] = {0};
   // reusable device scratch
   void *scratch[SLOT_COUNT] = {nullptr};
   size_t scratch_bytes[SLOT_COUNT] = {0};
@@ -188,6 +193,7 @@ struct somhip_engine {
   // them (their own destroy then only frees the host struct; any other call on them fails with a message)
   std::vector<somhip_codebook *> codebooks;
   std::vector<somhip_dataset *> datasets;
+  std::vector<somhip_mapset *> mapsets;
   unsigned lds_raised = 0;                     // bit LdsKernel: that kernel's dynamic LDS limit is raised on this device
   int n_cus = 0;                               // compute units of the device (grid of the persistent kernels)
   LvqCtl *lvq_hctl = nullptr;                  // pinned: read-backs of the LVQ batch loop's control block, one per batch in flight
@@ -284,6 +290,7 @@ struct LaunchTimer {   // HIP events on the engine's own stream around one launc
 // ---------------------------------------------------------------------------------
 static void codebook_release(somhip_codebook *cb);   // device memory of a mirror (defined with the mirrors below)
 static void dataset_release(somhip_dataset *ds);
+static void mapset_release(somhip_mapset *ms);
 
 extern "C" int somhip_engine_create(int device, somhip_engine **out) try {
   if (!out) return fail("somhip_engine_create: null out");
@@ -315,6 +322,7 @@ extern "C" void somhip_engine_destroy(somhip_engine *e) try {
   // for somhip_codebook_destroy / somhip_dataset_destroy (any order of the destroy calls is fine)
   for (auto *cb : e->codebooks) codebook_release(cb);     // (these also clear the mirror's engine pointer)
   for (auto *ds : e->datasets) dataset_release(ds);
+  for (auto *ms : e->mapsets) mapset_release(ms);
   for (auto &p : e->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
   for (auto ev : e->pool) (void)hipEventDestroy(ev);
   for (int i = 0; i < SLOT_COUNT; i++) if (e->scratch[i]) (void)hipFree(e->scratch[i]);
@@ -395,7 +403,7 @@ extern "C" int somhip_timing_select(somhip_engine *e, uint64_t kernel_mask) try 
 extern "C" int somhip_timing_reset(somhip_engine *e) try {
   CHK(check_engine(e, "somhip_timing_reset"));
   CHK(timing_flush(e));
-  for (int i = 0; i < KID_COUNT; i++) { e->launches[i] = 0; e->total_ms[i] = 0; }
+  for (int i = 0; i < KID_TIMED; i++) { e->launches[i] = 0; e->total_ms[i] = 0; }
   return 0;
 } ABI_CATCH(somhip_timing_reset)
 extern "C" int somhip_timing_get(somhip_engine *e, int k, int64_t *launches, double *total_ms) try {
@@ -746,6 +754,7 @@ extern "C" void somhip_dataset_destroy(somhip_dataset *ds) try {
 // the rest of the host side, by stage (same translation unit)
 #include "host_scan.inc"
 #include "host_som.inc"
+#include "host_mapset.inc"
 #include "host_lvq.inc"
 #include "host_comm.inc"
 #include "host_sammon.inc"

@@ -101,6 +101,13 @@ class Engine:
             out[self.lib.somhip_kernel_name(i).decode()] = (n.value, ms.value)
         return out
 
+    def mapset_timing(self):
+        """(launches, ms) of the map-set kernels while timing is on (somhip_mapset_timing; they are not in timing_table)"""
+        n = (C.c_int64 * 2)()
+        ms = (C.c_double * 2)()
+        check(self.lib.somhip_mapset_timing(self.h, n, ms))
+        return {"k_mapset_train": (n[0], ms[0]), "k_mapset_winners": (n[1], ms[1])}
+
     def device_alloc(self, nbytes):
         p = C.c_void_p()
         check(self.lib.somhip_device_alloc(self.h, nbytes, C.byref(p)))
@@ -426,6 +433,76 @@ def som_train(cb, ds, length, alpha, radius, alpha_type=ALPHA_LINEAR, use_fixed=
     td = np.empty(count, dtype=np.float32) if trace else None
     check(cb.e.lib.somhip_som_train(cb.h, ds.h, C.byref(p), _p(ti, _lib.c_i32_p), _p(td, _lib.c_float_p)))
     return ti, td
+
+
+def mapset_plan(n_rows, dim, masked=False, lib=None):
+    """What a map set of this shape would be (somhip_debug_mapset_plan; host arithmetic, no GPU): a dict of whether its
+    LDS image fits the budget, the workgroup's threads, units per thread, LDS bytes and the iterations per launch."""
+    lib = lib or _lib.load()
+    out = (C.c_int32 * 8)()
+    check(lib.somhip_debug_mapset_plan(n_rows, dim, int(bool(masked)), out))
+    return {"fits": bool(out[0]), "threads": out[1], "units_per_thread": out[2], "lds_bytes": out[3], "chunk": out[4],
+            "masked": bool(out[5])}
+
+
+class MapSet:
+    """Many maps of one shape on the device (somhip_mapset): rows[T, n, d]; every map is trained as som_train(batch=1)
+    would train a Codebook of its rows, all of them at once, each in one workgroup's LDS."""
+
+    def __init__(self, engine, rows, topol, neigh, xdim, ydim):
+        self.e = engine
+        rows = _arr(rows, np.float32)
+        assert rows.ndim == 3, "rows[T, n, d]"
+        self.n_maps, self.n, self.dim = rows.shape
+        self.topol, self.neigh, self.xdim, self.ydim = topol, neigh, xdim, ydim
+        h = C.c_void_p()
+        check(engine.lib.somhip_mapset_create(engine.h, _p(rows, _lib.c_float_p), self.n_maps, self.n, self.dim, topol, neigh,
+                                              xdim, ydim, C.byref(h)))
+        self.h = h
+        engine._adopt(self)
+
+    def train(self, ds, length, alpha, radius, alpha_type=ALPHA_LINEAR, use_fixed=0, use_weights=0, start_iter=0, count=None,
+              data_first=None, trace=False):
+        """som_training, batch 1, for every map; (trace_index, trace_diff) [T, count], or (None, None)."""
+        count = length - start_iter if count is None else count
+        data_first = start_iter % ds.n if data_first is None else data_first
+        p = SomParams(length, alpha, radius, alpha_type, use_fixed, use_weights, 1, start_iter, count, data_first)
+        ti = np.empty((self.n_maps, count), dtype=np.int32) if trace else None
+        td = np.empty((self.n_maps, count), dtype=np.float32) if trace else None
+        check(self.e.lib.somhip_mapset_train(self.h, ds.h, C.byref(p), _p(ti, _lib.c_i32_p), _p(td, _lib.c_float_p)))
+        return ti, td
+
+    def winners(self, ds, first=0, count=None):
+        """find_winner_euc of data rows [first, first + count) against every map: (index, diff, ret) [T, count]."""
+        count = ds.n if count is None else count
+        idx = np.empty((self.n_maps, count), dtype=np.int32)
+        diff = np.empty((self.n_maps, count), dtype=np.float32)
+        ret = np.empty((self.n_maps, count), dtype=np.int32)
+        check(self.e.lib.somhip_mapset_winners(self.h, ds.h, first, count, _p(idx, _lib.c_i32_p), _p(diff, _lib.c_float_p),
+                                               _p(ret, _lib.c_i32_p)))
+        return idx, diff, ret
+
+    def download(self, first_map=0, n_maps=None):
+        n_maps = self.n_maps - first_map if n_maps is None else n_maps
+        out = np.empty((n_maps, self.n, self.dim), dtype=np.float32)
+        check(self.e.lib.somhip_mapset_download(self.h, first_map, n_maps, _p(out, _lib.c_float_p)))
+        return out
+
+    def upload(self, rows, first_map=0):
+        rows = _arr(rows, np.float32)
+        assert rows.ndim == 3 and rows.shape[1:] == (self.n, self.dim)
+        check(self.e.lib.somhip_mapset_upload(self.h, first_map, rows.shape[0], _p(rows, _lib.c_float_p)))
+
+    def close(self):
+        if self.h and self.e.h:
+            self.e.lib.somhip_mapset_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 BATCH_AUTO = -1          # somhip.h SOMHIP_BATCH_AUTO: the engine's own mini-batch sizes along the schedule

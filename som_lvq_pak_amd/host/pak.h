@@ -157,6 +157,14 @@ struct entries *lvq1_training(struct teach_params *teach);
 struct entries *olvq1_training(struct teach_params *teach, const char *infile, const char *outfile);
 struct entries *lvq2_training(struct teach_params *teach, float winlen);
 struct entries *lvq3_training(struct teach_params *teach, float epsilon, float winlen);
+/* som_training of many maps of one shape at once (a somhip map set; vfind's trials): every map comes out as som_training
+ * leaves it, bit for bit.  teach gives the data, the schedule's alpha_type and, through teach->codes, the lattice of ONE
+ * such map; rows [n_maps][units][dim] are trained in place through the parts in turn (length, alpha, radius each).
+ * qerror, if not NULL, receives find_qerror of every trained map on testdata.  0, or 1 after a message. */
+struct som_part { long length; float alpha, radius; };
+int som_mapset_fits(long n_units, int dim);         /* 1: maps of this shape can be trained as a set (their image fits on chip) */
+int som_training_mapset(struct teach_params *teach, float *rows, int n_maps, const struct som_part *parts, int n_parts,
+                        struct entries *testdata, float *qerror);
 float find_qerror(struct teach_params *teach);
 float find_qerror2(struct teach_params *teach);   /* qerror -qetype 1 (som_rout.c:823) */
 /* winners of every data row (the scan behind compute_accuracy / find_labels) */

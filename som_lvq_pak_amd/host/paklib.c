@@ -1003,6 +1003,70 @@ done:
   return ret;
 }
 
+/* ------------------------------------------------------------------ som_training of a set of maps (vfind)
+ * The trials of vfind share data, shape and schedule; on the one-map engine every iteration of every trial is a launch
+ * of one workgroup.  A map set trains them all in one launch per chunk of iterations (include/somhip.h, map sets). */
+int som_mapset_fits(long n_units, int dim)
+{
+  int32_t plan[8];
+  return n_units > 0 && dim > 0 && somhip_debug_mapset_plan(n_units, dim, 0, plan) == 0 && plan[0] != 0;
+}
+
+int som_training_mapset(struct teach_params *teach, float *rows, int n_maps, const struct som_part *parts, int n_parts,
+                        struct entries *testdata, float *qerror)
+{
+  struct entries *codes = teach->codes, *data = teach->data;
+  if (set_som_params(teach)) { fprintf(stderr, "som_training: can't set SOM parameters\n"); return 1; }
+  if (!data || data->num_entries <= 0) { fprintf(stderr, "som_training: can't get data\n"); return 1; }
+  if (data->dimension != codes->dimension) {
+    fprintf(stderr, "code dimension (%d) != data dimension (%d)\n", codes->dimension, data->dimension);
+    return 1;
+  }
+  somhip_engine *en = engine();
+  if (!en) return 1;
+  somhip_mapset *ms = NULL;
+  somhip_dataset *ds = NULL, *ts = NULL;
+  int32_t *idx = NULL, *ret = NULL;
+  float *diff = NULL;
+  int rc = 1;
+  if (somhip_mapset_create(en, rows, n_maps, codes->num_entries, codes->dimension, codes->topol, codes->neigh, codes->xdim,
+                           codes->ydim, &ms)) { fprintf(stderr, "som_training: %s\n", somhip_last_error()); goto done; }
+  if (!(ds = mirror_data(data, 0))) goto done;
+  for (int p = 0; p < n_parts; p++) {
+    if (parts[p].length <= 0) continue;                /* (som_training's loop runs no iteration) */
+    somhip_som_params sp = { parts[p].length, parts[p].alpha, parts[p].radius, teach->alpha_type, use_fixed_level, use_weights_level,
+                             1, 0, parts[p].length, 0 };
+    if (somhip_mapset_train(ms, ds, &sp, NULL, NULL)) { fprintf(stderr, "som_training: %s\n", somhip_last_error()); goto done; }
+  }
+  if (somhip_mapset_download(ms, 0, n_maps, rows)) { fprintf(stderr, "som_training: %s\n", somhip_last_error()); goto done; }
+  if (qerror) {                                        /* find_qerror (som_rout.c:678-731) of every map */
+    const long n = testdata ? testdata->num_entries : 0;
+    if (n <= 0) { fprintf(stderr, "find_qerror: can't get data\n"); goto done; }
+    if (testdata->dimension != codes->dimension) {
+      fprintf(stderr, "code dimension (%d) != data dimension (%d)\n", codes->dimension, testdata->dimension);
+      goto done;
+    }
+    if (!(ts = mirror_data(testdata, 0))) goto done;
+    idx = malloc(sizeof(int32_t) * n * n_maps); ret = malloc(sizeof(int32_t) * n * n_maps); diff = malloc(sizeof(float) * n * n_maps);
+    if (somhip_mapset_winners(ms, ts, 0, n, idx, diff, ret)) { fprintf(stderr, "find_qerror: %s\n", somhip_last_error()); goto done; }
+    for (int m = 0; m < n_maps; m++) {
+      float q = 0.0f;
+      for (long i = 0; i < n; i++) {
+        if (ret[m * n + i] == 0) continue;             /* ignore empty vectors, :712 */
+        q += sqrt((double)diff[m * n + i]);            /* float accumulator, :715 */
+      }
+      qerror[m] = q;
+    }
+  }
+  rc = 0;
+done:
+  free(idx); free(ret); free(diff);
+  if (ms) somhip_mapset_destroy(ms);
+  if (ds) somhip_dataset_destroy(ds);
+  if (ts) somhip_dataset_destroy(ts);
+  return rc;
+}
+
 /* ------------------------------------------------------------------ som_training on G GPUs (vsom -gpus G)
  * One process per GPU: the parent -- which has parsed the arguments and read the files, and has not
  * touched a GPU -- forks G ranks; rank r takes device r % (visible GPUs), holds every G-th 8x8-unit patch of the map
