@@ -131,8 +131,9 @@ int  somhip_debug_rerank_pairs(somhip_codebook *cb, somhip_dataset *ds, int64_t 
                                uint64_t *keys, int64_t *bpad);
 
 /* diagnostics (tests): the route somhip_batch_winner_keys / somhip_batch_topk_keys / somhip_find_winners would take
- * for `count` samples and `want` (1, or the top-k width 2/4/8); host arithmetic only, no GPU work.  (somhip_find_winners
- * searches its run in pieces of at most 4096 samples: ask with the length of a piece.)
+ * for `count` samples and `want` (1, the top-k width 2/4/8, or a knn of 9 .. SOMHIP_KNN_MAX); host arithmetic only, no
+ * GPU work.  (somhip_find_winners searches its run in pieces of at most 4096 samples: ask with the length of a piece.)
+ * want 9 .. SOMHIP_KNN_MAX: out[0] = 4 (the wide k-NN route), out[1] = samples per chunk, out[2] as below, the rest 0.
  * out[0] = route (0 masked scan, 1 direct scan, 2 one-level pre-filter, 3 two-level pre-filter), out[1] = kth (level 1's
  * window above the smallest group minimum: 1, or above the 8th smallest), out[2] = split-bf16 GEMMs (else fp32 MFMA),
  * out[3] = level 1 by the persistent ring kernel, out[4] = top-k re-rank filed by row group (else by pair), out[5] =
@@ -208,7 +209,10 @@ void somhip_dataset_destroy(somhip_dataset *ds);
 
 /* ---- winner scans: WINNER_FUNCTION over a run of samples (lvq_pak.h:146) -----
  * find_winner_euc (lvq_pak.c:41) when tie == SOMHIP_TIE_FIRST and knn == 1,
- * find_winner_knn (lvq_pak.c:152) when tie == SOMHIP_TIE_KNN (1 <= knn <= 8).
+ * find_winner_knn (lvq_pak.c:152) when tie == SOMHIP_TIE_KNN (1 <= knn <= SOMHIP_KNN_MAX).
+ * knn <= 8 takes the top-k scans (direct, or behind the MFMA pre-filter on big codebooks); 9 <= knn <= SOMHIP_KNN_MAX
+ * takes the wide route in every scan mode: exact distances of a chunk of samples to every row, then a select of the
+ * knn smallest per sample -- no pre-filter, so its cost is that of the direct scan plus the select.
  * Samples are data rows [first, first+count).  Outputs are host arrays
  * [count][knn]: index = global row (or -1: nothing beat FLT_MAX), diff = SQUARED
  * distance exactly as the reference's fp32 left-to-right sum gives it; ret[i] = the
@@ -216,9 +220,16 @@ void somhip_dataset_destroy(somhip_dataset *ds);
  * Masked data sets (somhip_dataset_create with a mask) work for every knn: only the sample's
  * mask counts (lvq_pak.c:179-186), a code row's own masked components take part with their
  * stored value; a sample with every component masked gets ret 0 and index -2 in all knn slots.
- * Masked runs always take the exact direct-form scan (no MFMA pre-filter). */
+ * Masked runs always take the exact direct-form scan (no MFMA pre-filter).
+ * A row shard answers with its own knn nearest rows under global unit indices; a host merges the shards' lists by
+ * (diff, later row first). */
+#define SOMHIP_KNN_MAX 256
+int  somhip_knn_max(void);   /* SOMHIP_KNN_MAX of the library in use */
 int  somhip_find_winners(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count,
                          int knn, int tie, int32_t *index, float *diff, int32_t *ret);
+/* HIP-event totals of the wide route's two stages since somhip_timing_reset, while somhip_timing_enable is on (they are
+ * not in the table of somhip_kernel_count): [0] the distance stage, [1] the select stage; one launch of each per chunk */
+int  somhip_knn_timing(somhip_engine *e, int64_t launches[2], double total_ms[2]);
 
 /* ---- som_training (som_rout.c:556-671) --------------------------------------
  * Runs iterations [start_iter, start_iter+count) of a schedule of `length`

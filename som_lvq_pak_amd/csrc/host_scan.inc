@@ -66,7 +66,8 @@ static void prefilter_err_l1(int d, double *prod, double *sq) {
 }
 
 // The route of a search, for every caller.  want: 1 = the nearest row, K (2, 4, 8) = the K nearest, 0 = bare pre-filter
-enum ScanRoute { ROUTE_MASKED, ROUTE_DIRECT, ROUTE_ONE_LEVEL, ROUTE_TWO_LEVEL };
+//   9 .. SOMHIP_KNN_MAX = that many nearest rows by the wide k-NN route (K1w)
+enum ScanRoute { ROUTE_MASKED, ROUTE_DIRECT, ROUTE_ONE_LEVEL, ROUTE_TWO_LEVEL, ROUTE_WIDE };
 struct ScanPlan {
   ScanRoute route;
   int want, kth;       // kth: level 1's window above the smallest group minimum (1) or the LVQ_K0-th (k_group_kth)
@@ -77,10 +78,23 @@ struct ScanPlan {
   bool by_group;       // top-K behind a pre-filter: exact re-rank filed by row group (k_topk_pairs_bygroup), else by pair
   bool l2_global;      // two levels: level 2's sample operand from global memory (k_dist_l2), else from LDS (k_dist_l2_lds)
   bool fused_gmin;     // two levels, nearest row: the per-sample minimum comes out of level 2 (else k_group_min)
+  int64_t chunk;       // wide k-NN: samples per chunk (knn_wide_chunk)
 };
+// Wide k-NN: the samples of a chunk.  The distance matrix of a chunk, 4 * ngroups * 64 bytes per sample, stays within
+// KNN_DIST_BYTES: whole sample tiles, at most 4096 samples, at least one tile.
+constexpr int64_t KNN_DIST_BYTES = 256ll << 20;
+static int64_t knn_wide_chunk(const somhip_codebook *cb) {
+  const int64_t fit = KNN_DIST_BYTES / ((int64_t)sizeof(float) * cb->v.ngroups * WAVE) / SCAN_S * SCAN_S;
+  return std::max<int64_t>(SCAN_S, std::min<int64_t>(4096, fit));
+}
 static ScanPlan scan_plan(const somhip_codebook *cb, const somhip_dataset *ds, int64_t count, int want) {
   const int64_t nsb = (count + SCAN_S - 1) / SCAN_S;
   ScanPlan p = {ROUTE_DIRECT, want, 1, cb->e->scan_mode == SOMHIP_SCAN_MFMA_BF16, false, false, nsb, nsb * SCAN_S, (cb->v.d4 + 1) / 2};
+  if (want > 8) {                                  // masked or not, in every scan mode: exact, no pre-filter
+    p.route = ROUTE_WIDE;
+    p.chunk = knn_wide_chunk(cb);
+    return p;
+  }
   const bool run_ok = count >= MFMA_MIN_SAMPLES && count <= (int64_t)PAIR_MAX_COLS * 32;   // longer runs: the direct scan
   bool prefilter = cb->e->scan_mode != SOMHIP_SCAN_DIRECT;
   if (want == 1) prefilter = prefilter && run_ok && cb->v.n >= 64;
@@ -679,11 +693,14 @@ extern "C" int somhip_debug_rerank_pairs(somhip_codebook *cb, somhip_dataset *ds
 extern "C" int somhip_debug_scan_plan(somhip_codebook *cb, somhip_dataset *ds, int64_t count, int want, int32_t *out) try {
   CHK(check_pair(cb, ds, "somhip_debug_scan_plan"));
   if (!out) return fail("somhip_debug_scan_plan: null output");
-  if (want != 1 && want != 2 && want != 4 && want != 8) return fail("somhip_debug_scan_plan: want %d is not 1, 2, 4 or 8", want);
+  const bool wide = want > 8 && want <= SOMHIP_KNN_MAX;
+  if (want != 1 && want != 2 && want != 4 && want != 8 && !wide)
+    return fail("somhip_debug_scan_plan: want %d is not 1, 2, 4, 8 or 9 .. %d", want, SOMHIP_KNN_MAX);
   if (count <= 0) return fail("somhip_debug_scan_plan: count %lld < 1", (long long)count);
   const ScanPlan p = scan_plan(cb, ds, count, want);
   out[0] = (int32_t)p.route; out[1] = p.kth; out[2] = p.bf16; out[3] = p.l1_ring;
   out[4] = p.by_group; out[5] = p.l2_global; out[6] = p.fused_gmin; out[7] = 0;
+  if (wide) out[1] = (int32_t)p.chunk;
   return 0;
 } ABI_CATCH(somhip_debug_scan_plan)
 extern "C" int somhip_batch_winner_keys(somhip_codebook *cb, somhip_dataset *ds, int64_t first,
@@ -775,13 +792,87 @@ static void decode_key(uint64_t k, bool inverted, int32_t *index, float *diff) {
   memcpy(diff, &bits, 4);
 }
 
+// the outputs of one sample of somhip_find_winners from its knn keys (empty: every component masked)
+static void decode_sample(const uint64_t *k, int knn, bool knn_rule, bool empty, int32_t *index, float *diff, int32_t *ret) {
+  for (int j = 0; j < knn; j++) {
+    if (empty) { index[j] = -2; diff[j] = -1.0f; }
+    else decode_key(k[j], knn_rule, index + j, diff + j);
+  }
+  if (ret) *ret = empty ? 0 : knn;
+}
+
+extern "C" int somhip_knn_max(void) { return SOMHIP_KNN_MAX; }
+static_assert(SOMHIP_KNN_MAX == KNN_WIDE_MAX, "the select stage's pool is laid out for SOMHIP_KNN_MAX neighbours");
+
+// find_winner_knn for 9 <= knn <= SOMHIP_KNN_MAX (K1w), masked data or not: per chunk of samples (ScanPlan::chunk) pack
+// the samples, every distance, the select, one copy of the chunk's keys, decode
+static int find_winners_wide(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count, int knn,
+                             int32_t *index, float *diff, int32_t *ret) {
+  somhip_engine *e = cb->e;
+  const ScanPlan p = scan_plan(cb, ds, count, knn);
+  const int64_t CH = std::min(p.chunk, count), ld = cb->v.ngroups * WAVE;
+  const unsigned nblk = (unsigned)((cb->v.ngroups + 3) / 4);
+  float *dist; uint64_t *dk;
+  CHK(scratch(e, SLOT_KNN_DIST, (size_t)CH * ld, &dist));
+  CHK(scratch(e, SLOT_CALL_A, (size_t)CH * knn, &dk));
+  std::vector<uint64_t> hk((size_t)CH * knn);
+  for (int64_t off = 0; off < count; off += CH) {
+    const int64_t c = std::min(CH, count - off);
+    const int64_t f = (first + off) % ds->n;
+    if (ds->d_mask) {
+      LaunchTimer t(e, KID_KNN_DIST);
+      hipLaunchKernelGGL(k_knn_dist_masked, dim3(nblk, (unsigned)c), dim3(256), 0, e->stream, cb->v, ds->d_rows,
+                         (const uint8_t *)ds->d_mask, ds->n, f, ld, dist);
+    } else {
+      const int64_t nsb = (c + SCAN_S - 1) / SCAN_S;
+      float4 *xt;
+      CHK(scratch(e, SLOT_SAMPLES, (size_t)nsb * cb->v.d4 * SCAN_S, &xt));
+      {
+        LaunchTimer t(e, KID_PACK_SAMPLES);
+        hipLaunchKernelGGL(k_pack_samples<SCAN_S>, dim3((unsigned)nsb), dim3(256), 0, e->stream,
+                           ds->d_rows, ds->n, ds->d, cb->v.d4, f, c, xt);
+      }
+      LaunchTimer t(e, KID_KNN_DIST);
+      hipLaunchKernelGGL(k_knn_dist<SCAN_S>, dim3((unsigned)nsb, nblk), dim3(256), 0, e->stream, cb->v,
+                         (const float4 *)xt, c, ld, dist);
+      e->samples_searched += (uint64_t)c;
+    }
+    HIPCHK(hipGetLastError());
+    {
+      LaunchTimer t(e, KID_KNN_SELECT);
+      hipLaunchKernelGGL(k_knn_select, dim3((unsigned)c), dim3(KNN_THREADS), 0, e->stream, cb->v, (const float *)dist, ld, knn, dk);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(hk.data(), dk, sizeof(uint64_t) * (size_t)c * knn, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    for (int64_t i = 0; i < c; i++) {
+      const int64_t r = (f + i) % ds->n;
+      const bool empty = !ds->all_masked.empty() && ds->all_masked[(size_t)r];
+      decode_sample(hk.data() + (size_t)i * knn, knn, true, empty, index + (off + i) * knn, diff + (off + i) * knn,
+                    ret ? ret + off + i : nullptr);
+    }
+  }
+  return 0;
+}
+// HIP-event totals of the wide route's two stages since somhip_timing_reset, while somhip_timing_enable is on (timed under
+// ids of their own, like the map-set kernels): [0] the distance stage (k_knn_dist / k_knn_dist_masked), [1] k_knn_select
+extern "C" int somhip_knn_timing(somhip_engine *e, int64_t launches[2], double total_ms[2]) try {
+  CHK(check_engine(e, "somhip_knn_timing"));
+  if (!launches || !total_ms) return fail("somhip_knn_timing: null output");
+  CHK(timing_flush(e));
+  launches[0] = e->launches[KID_KNN_DIST]; launches[1] = e->launches[KID_KNN_SELECT];
+  total_ms[0] = e->total_ms[KID_KNN_DIST]; total_ms[1] = e->total_ms[KID_KNN_SELECT];
+  return 0;
+} ABI_CATCH(somhip_knn_timing)
+
 // find_winner_euc / find_winner_knn over a run of samples (include/somhip.h); masked data sets take K1m / K1mk for
-// every knn, and a fully masked sample reports ret 0, index -2 (lvq_pak.c:65-69 / :188-189 return 0 neighbours)
+// knn <= 8, and a fully masked sample reports ret 0, index -2 (lvq_pak.c:65-69 / :188-189 return 0 neighbours);
+// knn 9 .. SOMHIP_KNN_MAX: the wide route (find_winners_wide)
 extern "C" int somhip_find_winners(somhip_codebook *cb, somhip_dataset *ds, int64_t first,
                                    int64_t count, int knn, int tie, int32_t *index, float *diff,
                                    int32_t *ret) try {
   CHK(check_pair(cb, ds, "somhip_find_winners"));
-  if (knn < 1 || knn > 8) return fail("somhip_find_winners: knn %d not in 1..8", knn);
+  if (knn < 1 || knn > SOMHIP_KNN_MAX) return fail("somhip_find_winners: knn %d not in 1..%d", knn, SOMHIP_KNN_MAX);
   if (!index || !diff) return fail("somhip_find_winners: null output");
   if (count <= 0) return 0;
   somhip_engine *e = cb->e;
@@ -789,6 +880,7 @@ extern "C" int somhip_find_winners(somhip_codebook *cb, somhip_dataset *ds, int6
   // find_winner_knn(knn == 1) IS find_winner_euc (lvq_pak.c:160-161)
   const bool knn_rule = (tie == SOMHIP_TIE_KNN) && knn >= 2;
   if (!knn_rule && knn != 1) return fail("somhip_find_winners: knn > 1 needs SOMHIP_TIE_KNN");
+  if (knn > 8) return find_winners_wide(cb, ds, first, count, knn, index, diff, ret);
   const int64_t CH = 4096;
   return with_topk_width(knn, nullptr, [&](auto width) {
     constexpr int KK = decltype(width)::value;
@@ -805,13 +897,8 @@ extern "C" int somhip_find_winners(somhip_codebook *cb, somhip_dataset *ds, int6
       for (int64_t i = 0; i < c; i++) {
         int64_t r = (f + i) % ds->n;
         bool empty = !ds->all_masked.empty() && ds->all_masked[(size_t)r];
-        for (int k = 0; k < knn; k++) {
-          int32_t *pi = index + (off + i) * knn + k;
-          float *pd = diff + (off + i) * knn + k;
-          if (empty) { *pi = -2; *pd = -1.0f; }
-          else decode_key(hk[(size_t)i * KK + k], knn_rule, pi, pd);
-        }
-        if (ret) ret[off + i] = empty ? 0 : knn;
+        decode_sample(hk.data() + (size_t)i * KK, knn, knn_rule, empty, index + (off + i) * knn, diff + (off + i) * knn,
+                      ret ? ret + off + i : nullptr);
       }
     }
     return 0;

@@ -87,8 +87,8 @@ static const char *kKernelNames[KID_COUNT] = {
 };
 // The table above is what somhip_kernel_count / somhip_kernel_name publish, and it is closed: callers index it and select
 // from it by bit.  Kernels added since are timed by LaunchTimer all the same, under ids that follow the table; an entry
-// point of their own reports them (somhip_mapset_timing).
-enum TimedOnlyId { KID_MAPSET_TRAIN = KID_COUNT, KID_MAPSET_WINNERS, KID_TIMED };
+// point of their own reports them (somhip_mapset_timing, somhip_knn_timing).
+enum TimedOnlyId { KID_MAPSET_TRAIN = KID_COUNT, KID_MAPSET_WINNERS, KID_KNN_DIST, KID_KNN_SELECT, KID_TIMED };
 static_assert(KID_TIMED <= 64, "somhip_timing_select's mask has one bit per kernel id");
 extern "C" int somhip_kernel_count(void) { return KID_COUNT; }
 extern "C" const char *somhip_kernel_name(int i) { return (i >= 0 && i < KID_COUNT) ? kKernelNames[i] : ""; }
@@ -146,6 +146,7 @@ enum ScratchSlot {
   SLOT_SAMPLE_ROWS,        // two-level pre-filter: the sample-major copy of the tiles, from prepare to level 2
   SLOT_L2_OUT,             // two-level pre-filter, nearest row: level 2's minimum and mask of every list entry at the entry's
                            // own slot, from level 2 to the re-rank's selection (k_rerank_select_lists)
+  SLOT_KNN_DIST,           // wide k-NN: the distances of a chunk of samples to every row, from the distance stage to the select
   SLOT_COUNT
 };
 

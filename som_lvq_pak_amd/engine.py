@@ -17,6 +17,12 @@ TIE_FIRST, TIE_KNN = 0, 1
 UMAT_AVERAGE, UMAT_MEDIAN = 1, 2
 
 
+def __getattr__(name):
+    if name == "KNN_MAX":                   # most neighbours find_winners takes: asked of the library, when first wanted
+        return _lib.load().somhip_knn_max()
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
+
+
 def _p(a, typ):
     return None if a is None else a.ctypes.data_as(typ)
 
@@ -107,6 +113,14 @@ class Engine:
         ms = (C.c_double * 2)()
         check(self.lib.somhip_mapset_timing(self.h, n, ms))
         return {"k_mapset_train": (n[0], ms[0]), "k_mapset_winners": (n[1], ms[1])}
+
+    def knn_timing(self):
+        """(launches, ms) of the wide k-NN route's two stages while timing is on (somhip_knn_timing; they are not in
+        timing_table): one launch of each per chunk of samples"""
+        n = (C.c_int64 * 2)()
+        ms = (C.c_double * 2)()
+        check(self.lib.somhip_knn_timing(self.h, n, ms))
+        return {"k_knn_dist": (n[0], ms[0]), "k_knn_select": (n[1], ms[1])}
 
     def device_alloc(self, nbytes):
         p = C.c_void_p()
@@ -330,7 +344,9 @@ def randinit_from_bbox(lo, hi, cnt, xdim, ydim, seed):
 def find_winners(cb, ds, first=0, count=None, knn=1, tie=TIE_FIRST):
     """WINNER_FUNCTION over data rows [first, first+count): (index, diff, ret).
 
-    Masked data sets (Dataset(..., mask=...)) work for every knn (1..8): only the sample's mask counts
+    knn 1..8 takes the top-k scans; knn 9..KNN_MAX (with TIE_KNN) the wide route: exact distances to every row, then a
+    select per sample, in chunks of samples (scan_plan(cb, ds, count, knn)["chunk"]).
+    Masked data sets (Dataset(..., mask=...)) work for every knn (1..KNN_MAX): only the sample's mask counts
     (lvq_pak.c:179-186); a sample with every component masked gives ret 0 and index -2."""
     count = ds.n if count is None else count
     idx = np.empty((count, knn), dtype=np.int32)
@@ -341,14 +357,17 @@ def find_winners(cb, ds, first=0, count=None, knn=1, tie=TIE_FIRST):
     return idx, diff, ret
 
 
-ROUTES = ("masked", "direct", "one_level", "two_level")
+ROUTES = ("masked", "direct", "one_level", "two_level", "wide")
 
 
 def scan_plan(cb, ds, count, want=1):
     """The plan of a winner search of `count` samples for the nearest row (want 1) or the top-k width `want` (2, 4, 8)
-    (somhip_debug_scan_plan; host arithmetic, no GPU work): a dict of the route and the stage choices behind it."""
+    (somhip_debug_scan_plan; host arithmetic, no GPU work): a dict of the route and the stage choices behind it.
+    want 9..KNN_MAX (a knn of the wide route): {"route": "wide", "chunk": samples per chunk}."""
     out = (C.c_int32 * 8)()
     check(cb.e.lib.somhip_debug_scan_plan(cb.h, ds.h, count, want, out))
+    if ROUTES[out[0]] == "wide":
+        return {"route": "wide", "chunk": out[1]}
     return {"route": ROUTES[out[0]], "kth": out[1], "bf16": bool(out[2]), "l1_ring": bool(out[3]),
             "by_group": bool(out[4]), "l2_global": bool(out[5]), "fused_gmin": bool(out[6])}
 

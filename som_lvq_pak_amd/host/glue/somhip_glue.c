@@ -250,7 +250,7 @@ static long tab_find(struct data_entry *sample)
 static int hip_winner(struct entries *codes, struct data_entry *sample, struct winner_info *win, int knn)
 {
   long i, k;
-  if (!hip_selected || knn < 1 || knn > 8) return cpu_winner(codes, sample, win, knn);
+  if (!hip_selected || knn < 1 || knn > somhip_knn_max()) return cpu_winner(codes, sample, win, knn);   /* (beyond the engine's limit: the reference's own loop) */
   if (tab.valid && !tab.dirty && tab.codes == codes && tab.ncodes == codes->num_entries && tab.knn == knn) {
     /* one code row per call is compared with what was scanned: a codebook changed behind vector_adapt's back is noticed */
     const long r = tab.calls++ % tab.ncodes;
