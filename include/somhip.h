@@ -230,6 +230,21 @@ int  somhip_find_winners(somhip_codebook *cb, somhip_dataset *ds, int64_t first,
 /* HIP-event totals of the wide route's two stages since somhip_timing_reset, while somhip_timing_enable is on (they are
  * not in the table of somhip_kernel_count): [0] the distance stage, [1] the select stage; one launch of each per chunk */
 int  somhip_knn_timing(somhip_engine *e, int64_t launches[2], double total_ms[2]);
+/* The class vote over find_winner_knn's neighbours (knn == 1: find_winner_euc's), formed on the device behind the keys of
+ * the search somhip_find_winners would run (same routes, chunks, row wrap and masked data): what knntest.c:101-108,
+ * setlabel.c:73-80, correct_by_knn (lvq_rout.c:38-78) and elimin.c:87-101 take from the neighbours.  Host arrays [count]:
+ *   found  neighbours found: min(knn, rows) unless every component of the sample is masked (0)
+ *   label  the head of the reference's hit list after add_hit (labels.c:370-410) of the found neighbours' labels, nearest
+ *          first: the label whose count first reaches the largest count; -1 when found is 0
+ *   freq   its count (0 when found is 0)
+ *   own    neighbours whose label equals the sample's own label; -1 if the data set was created without labels
+ * freq, own and found may be NULL.  The codebook needs labels and must be a whole one: a row shard does not hold the
+ * other shards' labels. */
+int  somhip_knn_vote(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count, int knn,
+                     int32_t *label, int32_t *freq, int32_t *own, int32_t *found);
+/* HIP-event total of the vote kernel since somhip_timing_reset, while somhip_timing_enable is on (like the wide stages,
+ * not in the table of somhip_kernel_count); one launch per chunk */
+int  somhip_knn_vote_timing(somhip_engine *e, int64_t *launches, double *total_ms);
 
 /* ---- som_training (som_rout.c:556-671) --------------------------------------
  * Runs iterations [start_iter, start_iter+count) of a schedule of `length`

@@ -84,6 +84,8 @@ SIGNATURES = {
                                       c_i32_p, c_float_p, c_i32_p]),
     "somhip_knn_max": (C.c_int, []),
     "somhip_knn_timing": (C.c_int, [C.c_void_p, c_i64_p, c_double_p]),
+    "somhip_knn_vote": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, c_i32_p, c_i32_p, c_i32_p, c_i32_p]),
+    "somhip_knn_vote_timing": (C.c_int, [C.c_void_p, c_i64_p, c_double_p]),
     "somhip_som_train": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(SomParams), c_i32_p, c_float_p]),
     "somhip_mapset_create": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.POINTER(C.c_void_p)]),

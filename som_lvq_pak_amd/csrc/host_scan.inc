@@ -804,18 +804,36 @@ static void decode_sample(const uint64_t *k, int knn, bool knn_rule, bool empty,
 extern "C" int somhip_knn_max(void) { return SOMHIP_KNN_MAX; }
 static_assert(SOMHIP_KNN_MAX == KNN_WIDE_MAX, "the select stage's pool is laid out for SOMHIP_KNN_MAX neighbours");
 
-// find_winner_knn for 9 <= knn <= SOMHIP_KNN_MAX (K1w), masked data or not: per chunk of samples (ScanPlan::chunk) pack
-// the samples, every distance, the select, one copy of the chunk's keys, decode
-static int find_winners_wide(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count, int knn,
-                             int32_t *index, float *diff, int32_t *ret) {
+// The device keys of a k-NN search over a run of samples, chunk by chunk: what somhip_find_winners and somhip_knn_vote
+// share.  knn 1: the nearest row (scan_keys_top1, plain tags); 2 .. 8: the top-K routes with K = 2, 4 or 8 keys per sample
+// (with_topk_width), chunks of 4096; 9 .. SOMHIP_KNN_MAX: the wide route (K1w), masked data or not -- pack the samples,
+// every distance, the select -- in chunks of ScanPlan::chunk.  use(off, f, c, dk, stride) runs per chunk behind the
+// launches that leave keys dk[c][stride] (ascending, the first knn count) in SLOT_CALL_A for the c samples from data
+// row f on, the run's samples off .. off + c - 1; it returns 0 or an error.
+template <class Use>
+static int knn_chunk_keys(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count, int knn, Use use) {
   somhip_engine *e = cb->e;
+  if (knn <= 8)
+    return with_topk_width(knn, nullptr, [&](auto width) {
+      constexpr int KK = decltype(width)::value;
+      const int64_t CH = std::min<int64_t>(4096, count);
+      uint64_t *dk;
+      CHK(scratch(e, SLOT_CALL_A, (size_t)CH * KK, &dk));
+      for (int64_t off = 0; off < count; off += CH) {
+        const int64_t c = std::min(CH, count - off);
+        const int64_t f = (first + off) % ds->n;
+        if constexpr (KK == 1) CHK(scan_keys_top1(cb, ds, f, c, dk));
+        else CHK(scan_keys_topk<KK>(cb, ds, f, c, dk));
+        CHK(use(off, f, c, dk, KK));
+      }
+      return 0;
+    });
   const ScanPlan p = scan_plan(cb, ds, count, knn);
   const int64_t CH = std::min(p.chunk, count), ld = cb->v.ngroups * WAVE;
   const unsigned nblk = (unsigned)((cb->v.ngroups + 3) / 4);
   float *dist; uint64_t *dk;
   CHK(scratch(e, SLOT_KNN_DIST, (size_t)CH * ld, &dist));
   CHK(scratch(e, SLOT_CALL_A, (size_t)CH * knn, &dk));
-  std::vector<uint64_t> hk((size_t)CH * knn);
   for (int64_t off = 0; off < count; off += CH) {
     const int64_t c = std::min(CH, count - off);
     const int64_t f = (first + off) % ds->n;
@@ -843,14 +861,7 @@ static int find_winners_wide(somhip_codebook *cb, somhip_dataset *ds, int64_t fi
       hipLaunchKernelGGL(k_knn_select, dim3((unsigned)c), dim3(KNN_THREADS), 0, e->stream, cb->v, (const float *)dist, ld, knn, dk);
     }
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(hk.data(), dk, sizeof(uint64_t) * (size_t)c * knn, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    for (int64_t i = 0; i < c; i++) {
-      const int64_t r = (f + i) % ds->n;
-      const bool empty = !ds->all_masked.empty() && ds->all_masked[(size_t)r];
-      decode_sample(hk.data() + (size_t)i * knn, knn, true, empty, index + (off + i) * knn, diff + (off + i) * knn,
-                    ret ? ret + off + i : nullptr);
-    }
+    CHK(use(off, f, c, dk, knn));
   }
   return 0;
 }
@@ -867,7 +878,7 @@ extern "C" int somhip_knn_timing(somhip_engine *e, int64_t launches[2], double t
 
 // find_winner_euc / find_winner_knn over a run of samples (include/somhip.h); masked data sets take K1m / K1mk for
 // knn <= 8, and a fully masked sample reports ret 0, index -2 (lvq_pak.c:65-69 / :188-189 return 0 neighbours);
-// knn 9 .. SOMHIP_KNN_MAX: the wide route (find_winners_wide)
+// knn 9 .. SOMHIP_KNN_MAX: the wide route.  Per chunk (knn_chunk_keys): the keys, one copy of them, decode
 extern "C" int somhip_find_winners(somhip_codebook *cb, somhip_dataset *ds, int64_t first,
                                    int64_t count, int knn, int tie, int32_t *index, float *diff,
                                    int32_t *ret) try {
@@ -880,30 +891,75 @@ extern "C" int somhip_find_winners(somhip_codebook *cb, somhip_dataset *ds, int6
   // find_winner_knn(knn == 1) IS find_winner_euc (lvq_pak.c:160-161)
   const bool knn_rule = (tie == SOMHIP_TIE_KNN) && knn >= 2;
   if (!knn_rule && knn != 1) return fail("somhip_find_winners: knn > 1 needs SOMHIP_TIE_KNN");
-  if (knn > 8) return find_winners_wide(cb, ds, first, count, knn, index, diff, ret);
-  const int64_t CH = 4096;
-  return with_topk_width(knn, nullptr, [&](auto width) {
-    constexpr int KK = decltype(width)::value;
-    uint64_t *dk;
-    CHK(scratch(e, SLOT_CALL_A, (size_t)std::min(CH, count) * KK, &dk));
-    std::vector<uint64_t> hk((size_t)std::min(CH, count) * KK);
-    for (int64_t off = 0; off < count; off += CH) {
-      int64_t c = std::min(CH, count - off);
-      int64_t f = (first + off) % ds->n;
-      if constexpr (KK == 1) CHK(scan_keys_top1(cb, ds, f, c, dk));
-      else CHK(scan_keys_topk<KK>(cb, ds, f, c, dk));
-      HIPCHK(hipMemcpyAsync(hk.data(), dk, sizeof(uint64_t) * (size_t)c * KK, hipMemcpyDeviceToHost, e->stream));
-      HIPCHK(hipStreamSynchronize(e->stream));
-      for (int64_t i = 0; i < c; i++) {
-        int64_t r = (f + i) % ds->n;
-        bool empty = !ds->all_masked.empty() && ds->all_masked[(size_t)r];
-        decode_sample(hk.data() + (size_t)i * KK, knn, knn_rule, empty, index + (off + i) * knn, diff + (off + i) * knn,
-                      ret ? ret + off + i : nullptr);
-      }
+  std::vector<uint64_t> hk;
+  return knn_chunk_keys(cb, ds, first, count, knn, [&](int64_t off, int64_t f, int64_t c, const uint64_t *dk, int stride) {
+    if (hk.empty()) hk.resize((size_t)c * stride);                      // (the first chunk is the longest)
+    HIPCHK(hipMemcpyAsync(hk.data(), dk, sizeof(uint64_t) * (size_t)c * stride, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    for (int64_t i = 0; i < c; i++) {
+      const int64_t r = (f + i) % ds->n;
+      const bool empty = !ds->all_masked.empty() && ds->all_masked[(size_t)r];
+      decode_sample(hk.data() + (size_t)i * stride, knn, knn_rule, empty, index + (off + i) * knn, diff + (off + i) * knn,
+                    ret ? ret + off + i : nullptr);
     }
     return 0;
   });
 } ABI_CATCH(somhip_find_winners)
+
+// K1v: the class vote of find_winner_knn's neighbours over a run of samples (include/somhip.h).  Per chunk
+// (knn_chunk_keys, so the routes, the chunks, the wrap and masked data are somhip_find_winners'): the keys, k_knn_vote
+// behind them, one copy of 16 bytes per sample.  A sample with every component masked has no neighbours, whatever its keys say.
+extern "C" int somhip_knn_vote(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count, int knn,
+                               int32_t *label, int32_t *freq, int32_t *own, int32_t *found) try {
+  CHK(check_pair(cb, ds, "somhip_knn_vote"));
+  if (knn < 1 || knn > SOMHIP_KNN_MAX) return fail("somhip_knn_vote: knn %d not in 1..%d", knn, SOMHIP_KNN_MAX);
+  if (!label) return fail("somhip_knn_vote: null output");
+  if (!cb->d_labels) return fail("somhip_knn_vote: codebook has no labels");
+  if (cb->v.row_offset != 0 || cb->n_global != cb->v.n)
+    return fail("somhip_knn_vote: sharded codebook not supported (a shard does not hold the other shards' labels)");
+  if (first < 0) return fail("somhip_knn_vote: first row %lld < 0", (long long)first);
+  if (count <= 0) return 0;
+  somhip_engine *e = cb->e;
+  HIPCHK(hipSetDevice(e->device));
+  if (!ds->labels.empty() && !ds->d_labels) {                           // the device copy of the rows' labels, when first wanted
+    HIPCHK(hipMalloc((void **)&ds->d_labels, sizeof(int32_t) * (size_t)ds->n));
+    HIPCHK(hipMemcpy(ds->d_labels, ds->labels.data(), sizeof(int32_t) * (size_t)ds->n, hipMemcpyHostToDevice));
+  }
+  std::vector<int32_t> hv;
+  return knn_chunk_keys(cb, ds, first, count, knn, [&](int64_t off, int64_t f, int64_t c, const uint64_t *dk, int stride) {
+    int4 *dv;
+    CHK(scratch(e, SLOT_CALL_B, (size_t)c, &dv));
+    {
+      LaunchTimer t(e, KID_KNN_VOTE);
+      hipLaunchKernelGGL(k_knn_vote, dim3((unsigned)((c + VOTE_SAMPLES - 1) / VOTE_SAMPLES)), dim3(VOTE_SAMPLES * WAVE), 0,
+                         e->stream, dk, stride, knn, knn >= 2 ? 1 : 0, (const int32_t *)cb->d_labels, cb->v.row_offset, cb->v.n,
+                         (const int32_t *)ds->d_labels, f, ds->n, c, dv);
+    }
+    HIPCHK(hipGetLastError());
+    if (hv.empty()) hv.resize(4 * (size_t)c);                           // (the first chunk is the longest)
+    HIPCHK(hipMemcpyAsync(hv.data(), dv, sizeof(int4) * (size_t)c, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    for (int64_t i = 0; i < c; i++) {
+      const int32_t *v = hv.data() + 4 * (size_t)i;
+      const bool empty = !ds->all_masked.empty() && ds->all_masked[(size_t)((f + i) % ds->n)];
+      label[off + i] = empty ? -1 : v[0];
+      if (freq) freq[off + i] = empty ? 0 : v[1];
+      if (own) own[off + i] = ds->d_labels ? (empty ? 0 : v[2]) : -1;
+      if (found) found[off + i] = empty ? 0 : v[3];
+    }
+    return 0;
+  });
+} ABI_CATCH(somhip_knn_vote)
+// HIP-event total of k_knn_vote since somhip_timing_reset, while somhip_timing_enable is on (an id of its own behind the
+// published table, like the wide route's stages)
+extern "C" int somhip_knn_vote_timing(somhip_engine *e, int64_t *launches, double *total_ms) try {
+  CHK(check_engine(e, "somhip_knn_vote_timing"));
+  if (!launches || !total_ms) return fail("somhip_knn_vote_timing: null output");
+  CHK(timing_flush(e));
+  *launches = e->launches[KID_KNN_VOTE];
+  *total_ms = e->total_ms[KID_KNN_VOTE];
+  return 0;
+} ABI_CATCH(somhip_knn_vote_timing)
 
 // lininit's data passes (find_eigenvectors, som_rout.c:211-289): per-component sums / counts over the
 // unmasked entries, then the upper triangle (j >= i) of sum_r (x_ri - mean_i)(x_rj - mean_j); every

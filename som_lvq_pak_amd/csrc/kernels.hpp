@@ -26,6 +26,7 @@
 #include "kernels/prefilter_mfma.hpp"
 #include "kernels/scan_masked.hpp"
 #include "kernels/knn_wide.hpp"
+#include "kernels/knn_vote.hpp"
 #include "kernels/som_update.hpp"
 #include "kernels/som_update_gemm.hpp"
 #include "kernels/som_online.hpp"

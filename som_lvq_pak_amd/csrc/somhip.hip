@@ -87,8 +87,8 @@ static const char *kKernelNames[KID_COUNT] = {
 };
 // The table above is what somhip_kernel_count / somhip_kernel_name publish, and it is closed: callers index it and select
 // from it by bit.  Kernels added since are timed by LaunchTimer all the same, under ids that follow the table; an entry
-// point of their own reports them (somhip_mapset_timing, somhip_knn_timing).
-enum TimedOnlyId { KID_MAPSET_TRAIN = KID_COUNT, KID_MAPSET_WINNERS, KID_KNN_DIST, KID_KNN_SELECT, KID_TIMED };
+// point of their own reports them (somhip_mapset_timing, somhip_knn_timing, somhip_knn_vote_timing).
+enum TimedOnlyId { KID_MAPSET_TRAIN = KID_COUNT, KID_MAPSET_WINNERS, KID_KNN_DIST, KID_KNN_SELECT, KID_KNN_VOTE, KID_TIMED };
 static_assert(KID_TIMED <= 64, "somhip_timing_select's mask has one bit per kernel id");
 extern "C" int somhip_kernel_count(void) { return KID_COUNT; }
 extern "C" const char *somhip_kernel_name(int i) { return (i >= 0 && i < KID_COUNT) ? kKernelNames[i] : ""; }
@@ -468,6 +468,7 @@ struct somhip_dataset {
   int64_t n = 0;
   int d = 0;
   uint8_t *d_mask = nullptr;
+  int32_t *d_labels = nullptr;       // device copy of labels, made by the first somhip_knn_vote that wants it
   std::vector<uint8_t> all_masked;   // host: 1 if every component of the row is masked
   std::vector<int32_t> labels;       // host copies of the per-row scalars
   std::vector<int16_t> weight;
@@ -737,8 +738,10 @@ extern "C" int somhip_dataset_download_rows(somhip_dataset *ds, int64_t first, i
 static void dataset_release(somhip_dataset *ds) {
   if (ds->owns_rows && ds->d_rows) (void)hipFree((void *)ds->d_rows);
   if (ds->d_mask) (void)hipFree(ds->d_mask);
+  if (ds->d_labels) (void)hipFree(ds->d_labels);
   ds->d_rows = nullptr;
   ds->d_mask = nullptr;
+  ds->d_labels = nullptr;
   ds->e = nullptr;
 }
 extern "C" void somhip_dataset_destroy(somhip_dataset *ds) try {

@@ -122,6 +122,14 @@ class Engine:
         check(self.lib.somhip_knn_timing(self.h, n, ms))
         return {"k_knn_dist": (n[0], ms[0]), "k_knn_select": (n[1], ms[1])}
 
+    def knn_vote_timing(self):
+        """(launches, ms) of k_knn_vote while timing is on (somhip_knn_vote_timing; it is not in timing_table): one launch
+        per chunk of samples"""
+        n = C.c_int64(0)
+        ms = C.c_double(0)
+        check(self.lib.somhip_knn_vote_timing(self.h, C.byref(n), C.byref(ms)))
+        return {"k_knn_vote": (n.value, ms.value)}
+
     def device_alloc(self, nbytes):
         p = C.c_void_p()
         check(self.lib.somhip_device_alloc(self.h, nbytes, C.byref(p)))
@@ -355,6 +363,19 @@ def find_winners(cb, ds, first=0, count=None, knn=1, tie=TIE_FIRST):
     check(cb.e.lib.somhip_find_winners(cb.h, ds.h, first, count, knn, tie, _p(idx, _lib.c_i32_p),
                                        _p(diff, _lib.c_float_p), _p(ret, _lib.c_i32_p)))
     return idx, diff, ret
+
+
+def knn_vote(cb, ds, first=0, count=None, knn=5):
+    """The class vote of the knn nearest rows of data rows [first, first+count), formed on the device behind the search
+    find_winners would run (somhip_knn_vote): (label, freq, own, found), int32 arrays of `count`.
+
+    found: neighbours found (fewer than knn on a small codebook, 0 if every component of the sample is masked); label: the
+    head of the reference's hit list over their labels, nearest first (-1 if found is 0); freq: its count; own: neighbours
+    with the sample's own label (-1 for a Dataset without labels).  The codebook needs labels and must be a whole one."""
+    count = ds.n if count is None else count
+    out = [np.empty(count, dtype=np.int32) for _ in range(4)]
+    check(cb.e.lib.somhip_knn_vote(cb.h, ds.h, first, count, knn, *[_p(a, _lib.c_i32_p) for a in out]))
+    return tuple(out)
 
 
 ROUTES = ("masked", "direct", "one_level", "two_level", "wide")

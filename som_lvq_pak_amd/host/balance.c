@@ -13,7 +13,7 @@
 static const char *usage =
     "balance - balances the number of entries in codebook by shortest distances (MI355X engine)\n"
     "Required:  -cin file  -din file  -cout file\n"
-    "Optional:  -knn N (default 5, at most 8)  -rand seed  -selfuncs hip  -v level\n";
+    "Optional:  -knn N (default 5, at most 256)  -rand seed  -selfuncs hip  -v level\n";
 
 /* a + b as one new block (copies) */
 static struct entries *join_entries(struct entries *a, const long *arows, long na, struct entries *b,

@@ -1,15 +1,16 @@
 /* elimin -- keep only the data entries that a k-NN vote over the whole data set classifies
  * correctly (LVQ_PAK elimin.c:40-169): more same-label than other-label neighbours among the k
- * nearest, the entry itself included.  One all-pairs k-NN pass on the MI355X engine. */
+ * nearest, the entry itself included.  One all-pairs k-NN pass on the MI355X engine, which also
+ * counts the same-label neighbours. */
 #include <stdlib.h>
 #include <string.h>
 #include "pak.h"
 
-#define KNN 10        /* the reference's own limit (elimin.c:30); this engine stops at 8 */
+#define KNN 10        /* the reference's own limit (elimin.c:30) */
 
 static const char *usage =
     "elimin - eliminates those entries that are incorrectly classified by knn (MI355X engine)\n"
-    "Required:  -din file  -cout file\nOptional:  -knn N (default 5, at most 8)  -v level\n";
+    "Required:  -din file  -cout file\nOptional:  -knn N (default 5, at most 10)  -v level\n";
 
 int main(int argc, char **argv)
 {
@@ -26,27 +27,17 @@ int main(int argc, char **argv)
   if (!data) { fprintf(stderr, "Can't open data file '%s'\n", in_data_file); exit(1); }
   ifverbose(2) fprintf(stderr, "Extra codes are eliminated\n");
   long n = data->num_entries, nkeep = 0;
-  int32_t *idx = malloc(sizeof(int32_t) * (n * knn + 1));
-  float *diff = malloc(sizeof(float) * (n * knn + 1));
+  int32_t *label = malloc(sizeof(int32_t) * (n + 1)), *own = malloc(sizeof(int32_t) * (n + 1));
+  int32_t *found = malloc(sizeof(int32_t) * (n + 1));
   long *keep = malloc(sizeof(long) * (n + 1));
-  if (find_all_knn(data, data, knn, idx, diff)) { fprintf(stderr, "Elimination failed!\n"); exit(1); }
-  for (long r = 0; r < n; r++) {                    /* eliminate_codes, elimin.c:76-106 */
-    long correct = 0, incorrect = 0;
-    int found = 1;
-    for (int k = 0; k < knn; k++) if (idx[r * knn + k] < 0) found = 0;
-    if (!found) continue;                            /* did not find winners */
-    int datalabel = get_entry_label(&data->rows[r]);
-    for (int k = 0; k < knn; k++) {
-      if (get_entry_label(&data->rows[idx[r * knn + k]]) == datalabel) correct++;
-      else incorrect++;
-    }
-    if (correct > incorrect) keep[nkeep++] = r;
-  }
+  if (knn_vote_all(data, data, knn, label, NULL, own, found)) { fprintf(stderr, "Elimination failed!\n"); exit(1); }
+  for (long r = 0; r < n; r++)                      /* eliminate_codes, elimin.c:76-106: correct > incorrect of knn winners */
+    if (found[r] == knn && 2 * own[r] > knn) keep[nkeep++] = r;
   struct entries *codes = pick_rows(data, keep, nkeep);
   ifverbose(2) fprintf(stderr, "Codebook entries are saved to file %s\n", out_code_file);
   save_entries(codes, out_code_file);
   invalidate_alphafile(out_code_file);
-  free(idx); free(diff); free(keep);
+  free(label); free(own); free(found); free(keep);
   close_entries(codes); close_entries(data);
   pak_shutdown();
   return 0;

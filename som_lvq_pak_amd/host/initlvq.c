@@ -12,7 +12,7 @@
 static const char *usage =
     "eveninit/propinit - initial codebook for LVQ (MI355X engine)\n"
     "Required:  -din file  -cout file  -noc N\n"
-    "Optional:  -type eveninit|propinit  -knn N (default 5, at most 8)  -rand seed  -v level\n";
+    "Optional:  -type eveninit|propinit  -knn N (default 5, at most 256)  -rand seed  -v level\n";
 
 /* pick_inside_codes: at most need[c] entries of each class, from the beginning of the data,
  * that are correctly classified by k-NN; appends row indices to out */

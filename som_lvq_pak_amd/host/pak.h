@@ -169,8 +169,12 @@ float find_qerror(struct teach_params *teach);
 float find_qerror2(struct teach_params *teach);   /* qerror -qetype 1 (som_rout.c:823) */
 /* winners of every data row (the scan behind compute_accuracy / find_labels) */
 int find_all_winners(struct teach_params *teach, int32_t *index, float *diff, int32_t *ret);
-/* k-NN consumers (eveninit/propinit, knntest, classify): k <= 8 */
+/* the k nearest codes of every data row (knntest): k <= 8 */
 int find_all_knn(struct entries *codes, struct entries *data, int knn, int32_t *index, float *diff);
+/* the class vote over them, formed on the engine (setlabel, elimin; eveninit/propinit and balance through
+ * knn_correct_all): k <= SOMHIP_KNN_MAX */
+int knn_vote_all(struct entries *codes, struct entries *data, int knn, int32_t *label, int32_t *freq, int32_t *own,
+                 int32_t *found);
 unsigned char *knn_correct_all(struct entries *data, int knn);
 struct entries *pick_rows(struct entries *src, const long *rows, long n);
 struct entries *lininit_codes(struct entries *data, int topol, int neigh, int xdim, int ydim);

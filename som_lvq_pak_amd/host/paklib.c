@@ -1683,29 +1683,41 @@ int find_all_knn(struct entries *codes, struct entries *data, int knn, int32_t *
   return rc;
 }
 
+/* The class vote of every data row's knn nearest codes (1 <= knn <= SOMHIP_KNN_MAX), formed on the engine behind the
+ * search find_all_knn would run (somhip_knn_vote): arrays of data->num_entries.  found = neighbours found; label / freq =
+ * head of the hit list after add_hit of their first labels, nearest first (-1 / 0 with no neighbour); own = neighbours
+ * with the data row's own first label.  freq, own and found may be NULL.  0, or 1 after a message. */
+int knn_vote_all(struct entries *codes, struct entries *data, int knn, int32_t *label, int32_t *freq, int32_t *own,
+                 int32_t *found)
+{
+  if (knn < 1) knn = 1;
+  if (knn > SOMHIP_KNN_MAX) { fprintf(stderr, "this engine finds at most %d nearest neighbours (-knn %d)\n", SOMHIP_KNN_MAX, knn); return 1; }
+  somhip_codebook *cb = mirror_codes(codes, 1);
+  somhip_dataset *ds = mirror_data(data, own != NULL);               /* the rows' own labels: only `own` reads them */
+  int rc = 1;
+  if (cb && ds) {
+    rc = somhip_knn_vote(cb, ds, 0, data->num_entries, knn, label, freq, own, found);
+    if (rc) fprintf(stderr, "%s\n", somhip_last_error());
+  }
+  if (cb) somhip_codebook_destroy(cb);
+  if (ds) somhip_dataset_destroy(ds);
+  return rc;
+}
+
 /* correct_by_knn (lvq_rout.c:38-78) for every row of `data` against `data` itself: the majority
  * label (head of the hit list built nearest-first) equals the row's own first label. */
 unsigned char *knn_correct_all(struct entries *data, int knn)
 {
   long n = data->num_entries;
   if (knn < 1) knn = 1;
-  int32_t *idx = malloc(sizeof(int32_t) * n * knn);
-  float *diff = malloc(sizeof(float) * n * knn);
+  int32_t *label = malloc(sizeof(int32_t) * (n + 1)), *found = malloc(sizeof(int32_t) * (n + 1));
   unsigned char *ok = calloc(n, 1);
-  if (find_all_knn(data, data, knn, idx, diff)) { free(idx); free(diff); free(ok); return NULL; }
+  if (knn_vote_all(data, data, knn, label, NULL, NULL, found)) { free(label); free(found); free(ok); return NULL; }
   for (long r = 0; r < n; r++) {
-    struct hitlist *hits = new_hitlist();
-    int found = 1;
-    for (int k = 0; k < knn; k++) {
-      long w = idx[r * knn + k];
-      if (w < 0) { found = 0; break; }
-      add_hit(hits, get_entry_label(&data->rows[w]));
-    }
-    if (!found) { fprintf(stderr, "correct_by_knn: can't find winners\n"); ok[r] = 1; }   /* -1 is "true" at :182 */
-    else ok[r] = hits->entries > 0 && hits->label[0] == get_entry_label(&data->rows[r]);
-    free_hitlist(hits);
+    if (found[r] < knn) { fprintf(stderr, "correct_by_knn: can't find winners\n"); ok[r] = 1; }   /* -1 is "true" at :182 */
+    else ok[r] = label[r] == get_entry_label(&data->rows[r]);
   }
-  free(idx); free(diff);
+  free(label); free(found);
   return ok;
 }
 

@@ -1,13 +1,13 @@
 /* setlabel -- label every codebook vector by the majority of its k nearest DATA vectors
  * (LVQ_PAK setlabel.c:43-161): here the data set plays the codebook and the codes are the samples
- * of one k-NN pass on the MI355X engine. */
+ * of one k-NN pass on the MI355X engine, which also forms the vote. */
 #include <stdlib.h>
 #include <string.h>
 #include "pak.h"
 
 static const char *usage =
     "setlabel - sets the labels of entries by the majority voting (MI355X engine)\n"
-    "Required:  -cin file  -din file  -cout file\nOptional:  -knn N (default 5, at most 8)  -selfuncs hip  -v level\n";
+    "Required:  -cin file  -din file  -cout file\nOptional:  -knn N (default 5, at most 256)  -selfuncs hip  -v level\n";
 
 int main(int argc, char **argv)
 {
@@ -30,22 +30,16 @@ int main(int argc, char **argv)
     close_entries(data); close_entries(codes); exit(1);
   }
   long noc = codes->num_entries;
-  int32_t *idx = malloc(sizeof(int32_t) * (noc * knn + 1));
-  float *diff = malloc(sizeof(float) * (noc * knn + 1));
-  if (find_all_knn(data, codes, knn, idx, diff)) exit(1);             /* "codebook" = data, samples = codes */
-  for (long r = 0; r < noc; r++) {                                    /* find_labels, setlabel.c:68-90 */
-    struct hitlist *hits = new_hitlist();
-    for (int k = 0; k < knn; k++)
-      if (idx[r * knn + k] >= 0) add_hit(hits, get_entry_label(&data->rows[idx[r * knn + k]]));
-    if (hits->entries > 0) {
+  int32_t *label = malloc(sizeof(int32_t) * (noc + 1)), *found = malloc(sizeof(int32_t) * (noc + 1));
+  if (knn_vote_all(data, codes, knn, label, NULL, NULL, found)) exit(1);   /* "codebook" = data, samples = codes */
+  for (long r = 0; r < noc; r++)                                      /* find_labels, setlabel.c:68-90 */
+    if (found[r] > 0) {
       clear_entry_labels(codes, r);
-      if (hits->label[0] != LABEL_EMPTY) add_entry_label(codes, r, (int)hits->label[0]);
+      if (label[r] != LABEL_EMPTY) add_entry_label(codes, r, label[r]);
     }
-    free_hitlist(hits);
-  }
   ifverbose(2) fprintf(stderr, "Codebook entries are saved to file %s\n", out_code_file);
   save_entries(codes, out_code_file);
-  free(idx); free(diff);
+  free(label); free(found);
   close_entries(data); close_entries(codes);
   pak_shutdown();
   return 0;
