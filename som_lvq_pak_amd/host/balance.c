@@ -2,7 +2,7 @@
  * (LVQ_PAK balance.c:44-283): classes whose codes sit close together lose one, classes whose
  * codes are far apart gain one (picked from the data like eveninit does), then one OLVQ1 pass
  * over the data redistributes the codes.  Everything heavy runs on the MI355X engine: the nearest
- * later code of the same class behind the medians (med_distances, paklib.c, shared with mindist
+ * later code of the same class behind the medians (med_distances, pak_engine.c, shared with mindist
  * and stddev), the k-NN vote behind the picking, and olvq1_training. */
 #include <stdlib.h>
 #include <string.h>

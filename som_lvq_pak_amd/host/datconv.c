@@ -1,5 +1,5 @@
 /* datconv -- convert a data or code file between the text format of SOM_PAK / LVQ_PAK (datafile.c:396-447,
- * 552-748) and the raw fp32 side format every tool of this package also reads ("#!somf32", paklib.c), or
+ * 552-748) and the raw fp32 side format every tool of this package also reads ("#!somf32", pak_io.c), or
  * materialise the seeded generator stream (-din gen:k=..,dim=..,n=..,seed=..) as a file.  No GPU involved.
  * at 40 MB/s the text parser, not the engine, is the wall for anything beyond C3. */
 #include <stdlib.h>

@@ -20,7 +20,7 @@
  * loads in the same order as the reference's loop makes them, the -rand shuffle of every buffer included.  `-batch B` /
  * `-batch auto` (the engine's mini-batch schedules) is read from the command line with the
  * reference's own extract_parameter.  Not bound here: `-gpus` (one process per GPU needs the host program to fork before
- * any GPU use: som_lvq_pak_amd/host/paklib.c, pak_run_ranks). */
+ * any GPU use: som_lvq_pak_amd/host/pak_ranks.c, pak_run_ranks). */
 #define _GNU_SOURCE
 #include <math.h>
 #include <stdio.h>

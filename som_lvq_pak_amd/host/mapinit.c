@@ -1,7 +1,7 @@
 /* mapinit / randinit / lininit -- initial map codebook (SOM_PAK mapinit.c:53-182): random in the
  * bounding box of the data (randinit_codes som_rout.c:34-162, host only) or laid out on the plane
  * of the two principal axes (lininit_codes som_rout.c:322-429: the two O(n dim^2) data passes run
- * on the MI355X engine, see paklib.c). */
+ * on the MI355X engine, see pak_engine.c). */
 #include <float.h>
 #include <stdlib.h>
 #include <string.h>

@@ -1,7 +1,7 @@
 /* mindist -- the medians of the shortest within-class distances of a codebook (LVQ_PAK mindist.c:41-116), and with
  * -din the per-class standard deviations of a data file around the class means (deviations, lvq_rout.c:929-1004).
  * The nearest later entry of the same class of every codebook entry comes from the MI355X engine (med_distances,
- * paklib.c); the deviations are one pass over the data on the host. */
+ * pak_engine.c); the deviations are one pass over the data on the host. */
 #include <stdlib.h>
 #include <string.h>
 #include "pak.h"

@@ -57,7 +57,8 @@ struct entries {
   unsigned long long gen_seed;  /*   (vsom / qerror / randinit / lininit, see pak_gen_virtual_ok); pak_materialize() */
   int gen_k;                    /*   makes the host rows when something needs them after all                        */
   void *userdata;               /* device mirror handle (as lvq_pak.h:112) */
-  unsigned long mirror_generation;   /* host-row generation the mirror was uploaded at (paklib.c, per-sample surface) */
+  void (*drop_mirror)(struct entries *);   /* set by whoever sets userdata (pak_engine.c, per-sample surface): close_entries calls it */
+  unsigned long mirror_generation;   /* host-row generation the mirror was uploaded at (pak_engine.c, per-sample surface) */
 };
 
 struct winner_info { long index; struct data_entry *winner; float diff; };
@@ -119,7 +120,7 @@ int pak_parse_float(const char *s, float *out);     /* = sscanf(s, "%f", out) > 
 struct entries *open_entries(const char *name, int labels_needed, int skip_empty);
 int save_entries_wcomments(struct entries *codes, const char *name, const char *comments);
 #define save_entries(c, n) save_entries_wcomments((c), (n), NULL)
-/* raw fp32 side format ("#!somf32", paklib.c) -- open_entries reads it transparently, this writes it */
+/* raw fp32 side format ("#!somf32", pak_io.c) -- open_entries reads it transparently, this writes it */
 int save_entries_f32(struct entries *c, const char *name);
 /* `-din gen:...` without a host copy: tools whose whole use of the data is epoch-level calls of the engine set this
  * before open_entries(); the rows are then generated in HBM by somhip_dataset_generate when the mirror is made (a
@@ -127,7 +128,7 @@ int save_entries_f32(struct entries *c, const char *name);
  * later need for host rows (-rand, -buffer), materialise as before. */
 extern int pak_gen_virtual_ok;
 int pak_materialize(struct entries *e);
-/* the seeded Gaussian-mixture stream behind `-din gen:k=..,dim=..,n=..,seed=..[,labels=1]` (paklib.c) */
+/* the seeded Gaussian-mixture stream behind `-din gen:k=..,dim=..,n=..,seed=..[,labels=1]` (pak_io.c) */
 uint64_t pak_splitmix64(uint64_t x);
 float pak_gen_z(uint64_t seed, uint64_t counter);
 void pak_gen_row(uint64_t seed, int k_centres, int dim, long row, float *out, int *centre);
@@ -203,10 +204,10 @@ void pak_train_cli(int argc, char **argv, struct pak_train_cli *o);
  * reshuffling when -buffer is smaller than the file (datafile.c:237-344) */
 void pak_apply_rand(struct entries *data, const char *rand_s, long buffer);
 void pak_shutdown(void);
-/* vsom -gpus G: one process per GPU, codebook sharded, RCCL all-reduce of the winner keys (paklib.c).  Must be called
+/* vsom -gpus G: one process per GPU, codebook sharded, RCCL all-reduce of the winner keys (pak_ranks.c).  Must be called
  * before this process has used a GPU; rank 0 runs after(teach, arg) (save the codebook) when training succeeded. */
 int som_training_multi(struct teach_params *teach, int gpus, int (*after)(struct teach_params *, void *), void *arg);
-/* lvqtrain -gpus G: rows of the codebook sharded over the ranks, exact (paklib.c) */
+/* lvqtrain -gpus G: rows of the codebook sharded over the ranks, exact (pak_ranks.c) */
 int lvq_training_multi(struct teach_params *teach, int kind, float winlen, float epsilon, float clamp, float *talpha, int gpus,
                        int (*after)(struct teach_params *, void *), void *arg);
 /* the launcher behind it, for tools that spread independent work over the GPUs (vfind -gpus G: trials as replicas) */

@@ -1,7 +1,7 @@
 /* stddev -- per class of a data file, the median of the shortest within-class distances and the standard deviation
  * around the class mean (LVQ_PAK stddev.c:40-88).  The nearest later entry of the same class of every data entry -- a
  * self-join of sum n_c^2 dim / 2 distance terms, hours on one core for a large file -- comes from the MI355X engine
- * (med_distances, paklib.c); the deviations are one pass over the data on the host. */
+ * (med_distances, pak_engine.c); the deviations are one pass over the data on the host. */
 #include <stdlib.h>
 #include <string.h>
 #include "pak.h"

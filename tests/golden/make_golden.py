@@ -215,7 +215,7 @@ def lvq_tool_goldens(exp, d):
 
 def c2_full_golden(exp):
     """BASELINE.json configs[1] at full size through the REAL reference: 100 000 vectors x 128 of the seeded
-    generator stream (engine.gen_rows == paklib.c pak_gen_row == k_gen_mixture), written as text with %.9g (exact
+    generator stream (engine.gen_rows == pak_io.c pak_gen_row == k_gen_mixture), written as text with %.9g (exact
     round trip through sscanf("%f")), randinit 32x32 hexa bubble -rand 7, vsom -rlen 100000 -alpha 0.05 -radius 10,
     qerror.  Only hashes and stdout are kept; the GPU test regenerates the data from the same spec."""
     import tempfile

@@ -1,4 +1,4 @@
-/* hitlist_heads.c -- paklib.c's hit list on label sequences read from a file: one sequence per line, labels separated
+/* hitlist_heads.c -- pak_io.c's hit list on label sequences read from a file: one sequence per line, labels separated
  * by blanks (an empty line is an empty sequence).  Per sequence one line "label:freq label:freq ..." -- the whole list,
  * head first, after add_hit of every label in order.  tests/test_knn_vote.py compares it with a Python replay of the
  * reference's list (labels.c:370-410). */

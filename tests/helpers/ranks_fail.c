@@ -1,4 +1,4 @@
-/* ranks_fail.c -- pak_run_ranks (paklib.c) when a rank dies: rank 1 fails at once (mode "exit": returns 1; "signal":
+/* ranks_fail.c -- pak_run_ranks (pak_ranks.c) when a rank dies: rank 1 fails at once (mode "exit": returns 1; "signal":
  * raises SIGSEGV) while the other ranks block for ever -- rank 0 in a read from a rank that is still alive (the socket
  * of a dead peer would return EOF; a rank waiting inside a collective of RCCL sees nothing of the kind), the rest in
  * pause().  The call must come back with 1 within seconds and leave no child behind; mode "ok": all ranks return 0.

@@ -1,4 +1,4 @@
-/* row_funcs_check.c -- the per-sample dist / vector_adapt of the "hip" registry row (paklib.c) against the oracle's
+/* row_funcs_check.c -- the per-sample dist / vector_adapt of the "hip" registry row (pak_engine.c) against the oracle's
  * restatement of vector_dist_euc / adapt_vector (lvq_pak.c:291-316, 339-351) on generated rows with masks: bits.
  * CPU only (set_teach_params does not touch the GPU).  Prints "mismatches N". */
 #include <stdio.h>

@@ -56,9 +56,7 @@ def test_fast_number_parser_equals_sscanf(tools, tmp_path):
     exe = str(tmp_path / "parse_check")
     host = os.path.join(ROOT, "som_lvq_pak_amd", "host")
     subprocess.check_call(["gcc", "-O2", "-I", host, "-I", os.path.join(ROOT, "include"), "-o", exe,
-                           os.path.join(ROOT, "tests", "helpers", "parse_check.c"), os.path.join(host, "paklib.c"),
-                           "-L", os.path.join(ROOT, "som_lvq_pak_amd"), "-lsomhip",
-                           "-Wl,-rpath," + os.path.join(ROOT, "som_lvq_pak_amd"), "-lm"])
+                           os.path.join(ROOT, "tests", "helpers", "parse_check.c"), os.path.join(host, "pak_io.c"), "-lm"])
     p = subprocess.run([exe, "400000"], stdout=subprocess.PIPE, text=True)
     assert p.returncode == 0 and p.stdout.strip().endswith("mismatches 0"), p.stdout
 
@@ -71,7 +69,7 @@ def test_registry_row_dist_and_adapt_equal_the_oracle(tools, tmp_path):
     orc = os.path.join(ROOT, "oracle")
     subprocess.check_call(["make", "-s", "-C", orc, "oracle"])
     subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-fopenmp", "-I", host, "-I", os.path.join(ROOT, "include"), "-I", orc, "-o", exe,
-                           os.path.join(ROOT, "tests", "helpers", "row_funcs_check.c"), os.path.join(host, "paklib.c"),
+                           os.path.join(ROOT, "tests", "helpers", "row_funcs_check.c"), os.path.join(host, "pak_io.c"), os.path.join(host, "pak_engine.c"),
                            "-L", os.path.join(ROOT, "som_lvq_pak_amd"), "-lsomhip", "-L", orc, "-loracle",
                            "-Wl,-rpath," + os.path.join(ROOT, "som_lvq_pak_amd"), "-Wl,-rpath," + orc, "-lm"])
     p = subprocess.run([exe], stdout=subprocess.PIPE, text=True)
@@ -79,13 +77,14 @@ def test_registry_row_dist_and_adapt_equal_the_oracle(tools, tmp_path):
 
 
 def test_a_failing_rank_ends_the_others(tools, tmp_path):
-    """pak_run_ranks (paklib.c; `vsom/lvqtrain/vfind -gpus G`): a rank that exits non-zero or dies of a signal while
+    """pak_run_ranks (pak_ranks.c; `vsom/lvqtrain/vfind -gpus G`): a rank that exits non-zero or dies of a signal while
     the others block (rank 0 in a read from a live peer, the rest in pause() -- as a rank inside an RCCL collective
     would) ends them all: the call returns 1 within seconds and no child is left"""
     exe = str(tmp_path / "ranks_fail")
     host = os.path.join(ROOT, "som_lvq_pak_amd", "host")
     subprocess.check_call(["gcc", "-O2", "-fopenmp", "-I", host, "-I", os.path.join(ROOT, "include"), "-o", exe,
-                           os.path.join(ROOT, "tests", "helpers", "ranks_fail.c"), os.path.join(host, "paklib.c"),
+                           os.path.join(ROOT, "tests", "helpers", "ranks_fail.c"),
+                           os.path.join(host, "pak_io.c"), os.path.join(host, "pak_engine.c"), os.path.join(host, "pak_ranks.c"),
                            "-L", os.path.join(ROOT, "som_lvq_pak_amd"), "-lsomhip",
                            "-Wl,-rpath," + os.path.join(ROOT, "som_lvq_pak_amd"), "-lm"])
     for mode, world, want in (("ok", 4, 0), ("exit", 3, 1), ("signal", 4, 1), ("exit", 2, 1)):
@@ -454,7 +453,7 @@ def test_datconv_raw_fp32_roundtrip(tools, tmp_path):
 
 
 def test_generator_source_equals_its_restatement(tools, tmp_path):
-    """-din gen:... (paklib.c pak_gen_row) against the numpy restatement in engine.gen_rows, bit for bit, and
+    """-din gen:... (pak_io.c pak_gen_row) against the numpy restatement in engine.gen_rows, bit for bit, and
     the stream does not depend on where a window starts."""
     import numpy as np
     from som_lvq_pak_amd import engine as E

@@ -1083,7 +1083,7 @@ def test_random_parity_sweep_short():
 
 def test_device_generator_equals_host_stream(eng, E, oracle):
     """somhip_dataset_generate (k_gen_mixture) against the host form of the stream (engine.gen_rows, itself pinned to
-    paklib.c's pak_gen_row on the CPU): mixture ids equal, and the winners of the generated rows on a codebook --
+    pak_io.c's pak_gen_row on the CPU): mixture ids equal, and the winners of the generated rows on a codebook --
     index and distance bits -- equal those of the host rows uploaded the ordinary way, windows included."""
     seed, k, dim, n = 20251, 9, 24, 3000
     hx, hc = E.gen_rows(seed, k, dim, 0, n)

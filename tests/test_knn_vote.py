@@ -4,7 +4,7 @@ hit list (labels.c:370-410).  label, freq, own and found must be equal as intege
 
 The replay is the list itself -- [label, count] entries, a new label appended, a bumped entry swapped towards the head
 while its predecessor's count is strictly smaller -- not the closed form the kernel uses ("the label whose count first
-reaches the final maximum"); without a GPU it is compared with paklib.c's list through tests/helpers/hitlist_heads.c."""
+reaches the final maximum"); without a GPU it is compared with pak_io.c's list through tests/helpers/hitlist_heads.c."""
 import ctypes as C
 import os
 import subprocess
@@ -74,13 +74,11 @@ def test_null_handles_are_errors_not_crashes(built):
 
 
 def test_replay_equals_the_tools_hit_list(built, tmp_path):
-    """random label sequences (few classes: many ties; label 0; negative and large labels) through paklib.c's add_hit"""
+    """random label sequences (few classes: many ties; label 0; negative and large labels) through pak_io.c's add_hit"""
     exe = str(tmp_path / "hitlist_heads")
     host = os.path.join(ROOT, "som_lvq_pak_amd", "host")
     subprocess.check_call(["gcc", "-O2", "-I", host, "-I", os.path.join(ROOT, "include"), "-o", exe,
-                           os.path.join(ROOT, "tests", "helpers", "hitlist_heads.c"), os.path.join(host, "paklib.c"),
-                           "-L", os.path.join(ROOT, "som_lvq_pak_amd"), "-lsomhip",
-                           "-Wl,-rpath," + os.path.join(ROOT, "som_lvq_pak_amd"), "-lm"])
+                           os.path.join(ROOT, "tests", "helpers", "hitlist_heads.c"), os.path.join(host, "pak_io.c"), "-lm"])
     rs = np.random.RandomState(3)
     seqs = [[], [0], [7, 7], [5, 7, 2, 9, 7, 2, 9, 5]]
     for _ in range(400):

@@ -4,8 +4,7 @@
  * (profiles/class_nearest_vs_host.txt): prints the class table `stddev` prints for the medians, and its wall time.
  *
  *   gcc -O3 -ffp-contract=off -fopenmp -Iinclude -Isom_lvq_pak_amd/host -o build/med_distances_host_loop \
- *       tools/med_distances_host_loop.c som_lvq_pak_amd/host/paklib.c -Lsom_lvq_pak_amd -lsomhip \
- *       -Wl,-rpath,'$ORIGIN/../som_lvq_pak_amd' -lm
+ *       tools/med_distances_host_loop.c som_lvq_pak_amd/host/pak_io.c -lm
  *   build/med_distances_host_loop gen:k=16,dim=128,n=65536,seed=1,labels=1
  */
 #include <float.h>
