@@ -80,7 +80,8 @@ enum { SOMHIP_UPDATE_EXACT = 0, SOMHIP_UPDATE_GEMM = 1 };
 int  somhip_engine_set_update_mode(somhip_engine *e, int mode);
 /* cumulative re-rank statistics of the MFMA path since engine creation:
  * out[0] = row groups re-ranked, out[1] = rows re-ranked, out[2] = max groups for one sample,
- * out[3] = samples searched, out[4] = (row, iteration) updates applied by mini-batch runs,
+ * out[3] = samples searched (fewer than the samples trained where somhip_som_train searched only the end of a run, see
+ * there), out[4] = (row, iteration) updates applied by mini-batch runs,
  * out[5] = (row group, iteration) pairs with at least one update, out[6] = list entries ((row group, iteration)
  * pairs) the GEMM-form update walked (it stops where the weights have decayed away), out[7] = (row group, sample) pairs
  * that survived level 1 of the two-level pre-filter and went through the three-product level 2 */
@@ -259,7 +260,16 @@ int  somhip_knn_vote_timing(somhip_engine *e, int64_t *launches, double *total_m
  *             has not been measured against the online engine (small maps, short runs).  Measured at configs[3]'s
  *             real length on three seed pairs (profiles/r03_conformity_*.jsonl).
  * trace_index/trace_diff (host, [count], may be NULL): winner of every iteration;
- * -2 = skipped (sample fully masked), -3 = fixed-point sample (no search). */
+ * -2 = skipped (sample fully masked), -3 = fixed-point sample (no search).
+ * Lazy search: with no trace wanted, update mode gemm and a bubble neighbourhood that covers a good part of the map, a
+ *             run's winners are searched only for its last M samples (whole trips of k_som_members, at most half the
+ *             run): the GEMM update reads each row group's list from its end and stops where the weights have decayed
+ *             below 2^-24, so the samples in front of every group's tail change nothing.  k_som_members counts the
+ *             groups whose tail did not fill within M; the host reads that word (the loop's only host wait) and, if it
+ *             is not zero, searches the rest of the run and makes the lists again.  The codebook, and the update
+ *             statistics of somhip_scan_stats, are those of the full search, bit for bit; `samples searched` is
+ *             smaller.  With a trace, and through somhip_batch_winner_keys + somhip_som_batch_update, every sample is
+ *             searched. */
 #define SOMHIP_BATCH_AUTO (-1)
 typedef struct somhip_som_params {
   int64_t length;        /* teach_params.length  (lvq_pak.h:198) */

@@ -304,19 +304,21 @@ static int bind_update(somhip_engine *e, const somhip_codebook *cb, int64_t coun
   return 0;
 }
 static int update_members(somhip_engine *e, const somhip_codebook *cb, const somhip_dataset *ds, const UpdatePlan &p,
-                          int64_t data_first, int64_t count, const uint64_t *d_keys, const StepScalars *d_sc, UpdateBufs &b) {
+                          int64_t data_first, int64_t count, const uint64_t *d_keys, const StepScalars *d_sc, UpdateBufs &b,
+                          int64_t lazy_trips = 0) {
   if (p.tail) CHK(scratch(e, SLOT_TAIL_START, (size_t)cb->v.ngroups, &b.lstart));
   LaunchTimer t(e, KID_MEMBERS);
   const int rc = with_value<1, 0>(cb->v.neigh == SOMHIP_NEIGH_GAUSSIAN, [&](auto g) { return with_value<1024, 256>(p.members_nt, [&](auto nt) {
-    return with_value<8, 4>(p.members_rr, [&](auto rr) {
-      constexpr bool GG = decltype(g)::value != 0; constexpr int NT = decltype(nt)::value, RR = decltype(rr)::value;
-      if constexpr (RR == 4 || (!GG && NT == 1024)) {    // (8 samples per thread: bubble, 1024 threads only)
-        hipLaunchKernelGGL((k_som_members<GG, NT, RR>), dim3((unsigned)cb->v.ngroups), dim3(NT), 0, e->stream, cb->v, count,
+    return with_value<8, 4>(p.members_rr, [&](auto rr) { return with_value<1, 0>(lazy_trips > 0, [&](auto lz) {
+      constexpr bool GG = decltype(g)::value != 0, LZ = decltype(lz)::value != 0; constexpr int NT = decltype(nt)::value, RR = decltype(rr)::value;
+      // (8 samples per thread: bubble, 1024 threads only; lazy: bubble only -- the plan's tail mode is)
+      if constexpr ((RR == 4 || (!GG && NT == 1024)) && !(GG && LZ)) {
+        hipLaunchKernelGGL((k_som_members<GG, NT, RR, LZ>), dim3((unsigned)cb->v.ngroups), dim3(NT), 0, e->stream, cb->v, count,
                            p.decode ? b.bxy : nullptr, p.decode ? nullptr : d_keys, d_sc, b.cnt, b.lists, e->d_stats,
                            p.entry == ENTRY_SAMPLE ? (int64_t)-1 : data_first, ds->n, p.entry == ENTRY_BYTE ? 4 * cb->v.d : cb->v.d >> 2,
-                           p.tail_need, b.lstart, p.gauss_gemm ? 1 : 0, p.reach_max); return 0;
-      } else return fail("update_members: no k_som_members<%d, %d, %d> is built", (int)GG, NT, RR);
-  }); }); });
+                           p.tail_need, b.lstart, p.gauss_gemm ? 1 : 0, p.reach_max, lazy_trips); return 0;
+      } else return fail("update_members: no k_som_members<%d, %d, %d, %d> is built", (int)GG, NT, RR, (int)LZ);
+  }); }); }); });
   CHK(rc); HIPCHK(hipGetLastError());
   return 0;
 }
@@ -350,25 +352,113 @@ static int update_apply(somhip_engine *e, const somhip_codebook *cb, const somhi
   CHK(rc); HIPCHK(hipGetLastError());
   return 0;
 }
-static int som_update_run(somhip_codebook *cb, somhip_dataset *ds, int64_t data_first, int64_t count,
-                          const uint64_t *d_keys, const StepScalars *d_sc, const StepScalars *h_sc) {
-  somhip_engine *e = cb->e;
-  cb->prep_valid = false;
-  const UpdatePlan p = som_update_plan(cb, ds, data_first, count, h_sc);
-  UpdateBufs b; CHK(bind_update(e, cb, count, &b));
-  if (p.decode) {
-    LaunchTimer t(e, KID_DECODE);
-    hipLaunchKernelGGL(k_decode_winners, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, e->stream, d_keys, d_sc, count, cb->v.xdim, b.bxy);
-    HIPCHK(hipGetLastError());
-  }
-  CHK(update_members(e, cb, ds, p, data_first, count, d_keys, d_sc, b));
+// K4a over samples [from, from + n) of a run (keys, scalars and coordinates all indexed by the run's sample)
+static int update_decode(somhip_engine *e, const somhip_codebook *cb, int64_t from, int64_t n, const uint64_t *d_keys,
+                         const StepScalars *d_sc, const UpdateBufs &b) {
+  LaunchTimer t(e, KID_DECODE);
+  hipLaunchKernelGGL(k_decode_winners, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, d_keys + from, d_sc + from, n, cb->v.xdim, b.bxy + from);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+// K4c (fold_held: a lazy members pass is kept, what it counted goes into the statistics) and the apply kernel
+static int update_order_apply(somhip_engine *e, const somhip_codebook *cb, const somhip_dataset *ds, const UpdatePlan &p,
+                              int64_t data_first, int64_t count, const StepScalars *d_sc, UpdateBufs &b, bool fold_held) {
   if (p.order) {
     CHK(scratch(e, SLOT_STAGE, (size_t)cb->v.ngroups, &b.order));
     LaunchTimer t(e, KID_DECODE);                          // (timed with k_decode_winners)
-    hipLaunchKernelGGL(k_order_groups, dim3((unsigned)((cb->v.ngroups * 8 + 255) / 256)), dim3(256), 0, e->stream, b.cnt, (int)cb->v.ngroups, b.order);
+    const dim3 grid((unsigned)((cb->v.ngroups * 8 + 255) / 256));
+    if (fold_held) hipLaunchKernelGGL(k_order_groups<true>, grid, dim3(256), 0, e->stream, b.cnt, (int)cb->v.ngroups, b.order, e->d_stats);
+    else hipLaunchKernelGGL(k_order_groups<false>, grid, dim3(256), 0, e->stream, b.cnt, (int)cb->v.ngroups, b.order, nullptr);
+    HIPCHK(hipGetLastError());
+  } else if (fold_held) {
+    hipLaunchKernelGGL(k_fold_update_stats, dim3(1), dim3(256), 0, e->stream, e->d_stats);
     HIPCHK(hipGetLastError());
   }
   return update_apply(e, cb, ds, p, data_first, count, d_sc, b);
+}
+static int som_update_planned(somhip_codebook *cb, somhip_dataset *ds, const UpdatePlan &p, int64_t data_first, int64_t count,
+                              const uint64_t *d_keys, const StepScalars *d_sc) {
+  somhip_engine *e = cb->e;
+  cb->prep_valid = false;
+  UpdateBufs b; CHK(bind_update(e, cb, count, &b));
+  if (p.decode) CHK(update_decode(e, cb, 0, count, d_keys, d_sc, b));
+  CHK(update_members(e, cb, ds, p, data_first, count, d_keys, d_sc, b));
+  return update_order_apply(e, cb, ds, p, data_first, count, d_sc, b, false);
+}
+static int som_update_run(somhip_codebook *cb, somhip_dataset *ds, int64_t data_first, int64_t count,
+                          const uint64_t *d_keys, const StepScalars *d_sc, const StepScalars *h_sc) {
+  return som_update_planned(cb, ds, som_update_plan(cb, ds, data_first, count, h_sc), data_first, count, d_keys, d_sc);
+}
+
+// ---------------------------------------------------------------------------------
+// Lazy search (som_train_batched): winners only for the end of a run.
+//
+// With the GEMM update in tail mode nothing reads the winner of a sample that lies in front of every row group's list
+// tail: K4b walks the run from its end in trips and a group stops after the trip in which its tail holds tail_need
+// entries with every live unit; K4m starts at the list's end and stops inside that tail.  So the run's last M samples
+// are searched, M whole trips, and K4b runs over exactly those trips (k_som_members, lazy_trips) -- with the whole run's
+// plan, count, scalars and data offsets, the keys and the decoded coordinates at the run's own indices.  A group that
+// has `enough` after trip k <= M / trip has seen the same samples in the same trips as with every winner known: the same
+// entries at the same places, the same count and the same lstart, and K4m's walk over them is the same walk -- the
+// codebook the run leaves is the same, bit for bit, and so are the lists the statistics describe.  K4b counts the groups
+// that left WITHOUT `enough`; the host reads that one word (the only host wait of the training loop, and only in lazy
+// runs).  Zero: on to K4c and K4m.  Otherwise the other count - M samples are searched against the same codebook (the
+// prepared copies are still valid: nothing has written it) and decode and K4b run again over the whole run, as in a
+// run that was never lazy; what the first pass had counted is dropped.  A group that no winner comes near never has
+// `enough`: a map whose winners all keep away from some patch -- data in one corner of a map wider than the radius,
+// clustered data early in a schedule -- takes that second path in every lazy run, and pays one members pass and one
+// host wait per run (about 0.15 ms at the benchmark's shape) for nothing.
+//
+// M: a corner patch decides -- it sees a quarter of the disc of winners that cover it whole.  With the winners spread
+// evenly, the share of samples that fill a corner patch is a quarter of the plan's own `full` (area(radius - 6) /
+// units), so tail_need of them are expected within tail_need / (full / 4) samples; times LAZY_MARGIN; then whole trips.
+// Lazy only if that is at most half the run.  Winners are not spread evenly -- every group has to fill, and the slowest
+// one needs several times what the average one does -- hence the margin.  It is TUNED ON ONE DATA SET: the benchmark's
+// 10 M-vector schedule on the 65536 x 512 map, partly from a table computed from measured per-batch needs
+// (profiles/lazy_search_vs_parent.txt has the measurements and the other margins).  On maps of 512 row groups and
+// more, trips of 1024 x 8 are never lazy with it (the plan takes them where tail_need > 3 x 1024 x full, and M would be
+// above the longest run the GEMM update takes); maps below 512 row groups take such trips from 16384 samples on
+// whatever the radius, and are lazy there with M = 8192.
+// ---------------------------------------------------------------------------------
+constexpr double LAZY_MARGIN = 7.0;
+static int64_t som_lazy_samples(const somhip_codebook *cb, const UpdatePlan &p, int64_t count, const StepScalars *h_sc) {
+  if (p.apply != APPLY_GEMM || !p.tail || p.tail_need == 0) return 0;
+  const int64_t trip = (int64_t)p.members_nt * p.members_rr;
+  const double r = std::sqrt((double)std::max(h_sc[count - 1].thresh, 0.0f)) - 6.0;     // (the run's smallest radius)
+  if (!(r > 0.0)) return 0;
+  const double quarter = std::min(1.0, 0.25 * 3.6276 * r * r / std::max<double>(1.0, (double)cb->v.xdim * cb->ydim));
+  const double want = LAZY_MARGIN * (double)p.tail_need / quarter;
+  if (!(want <= (double)count)) return 0;
+  const int64_t m = ((int64_t)std::ceil(want) + trip - 1) / trip * trip;
+  return 2 * m <= count ? m : 0;
+}
+// one lazy run: d_keys has room for the run's keys + 4 in front and, behind `spare`, for the run's keys again
+static int som_lazy_run(somhip_codebook *cb, somhip_dataset *ds, const UpdatePlan &p, int64_t row0, int64_t count, int64_t m,
+                        uint64_t *d_keys, uint64_t *spare, const StepScalars *d_sc) {
+  somhip_engine *e = cb->e;
+  // the run's key array starts so that its searched end is aligned like the buffer itself (4 keys = 32 bytes: m is whole 1024s)
+  uint64_t *kv = d_keys + ((4 - count % 4) & 3);
+  const int64_t head = count - m;
+  if (!e->lazy_hflag) HIPCHK(hipHostMalloc((void **)&e->lazy_hflag, sizeof(unsigned long long), hipHostMallocDefault));
+  // (the held counts and the short-tail word start at zero whatever an earlier call left: an error between a members pass and its fold)
+  HIPCHK(hipMemsetAsync(e->d_stats + STAT_UPDATE_HELD, 0, sizeof(unsigned long long) * (2 * STAT_UPDATE_PAIRS + 1), e->stream));
+  CHK(scan_keys_top1(cb, ds, (row0 + head) % ds->n, m, kv + head));
+  UpdateBufs b; CHK(bind_update(e, cb, count, &b));
+  if (p.decode) CHK(update_decode(e, cb, head, m, kv, d_sc, b));
+  CHK(update_members(e, cb, ds, p, row0, count, kv, d_sc, b, m / ((int64_t)p.members_nt * p.members_rr)));
+  HIPCHK(hipMemcpyAsync(e->lazy_hflag, e->d_stats + STAT_LAZY_SHORT, sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  const bool redo = *e->lazy_hflag != 0;
+  if (redo) {
+    // (into the spare keys, then copied: the head of the run's key array is not aligned like the buffer)
+    HIPCHK(hipMemsetAsync(e->d_stats + STAT_UPDATE_HELD, 0, sizeof(unsigned long long) * (2 * STAT_UPDATE_PAIRS + 1), e->stream));
+    CHK(scan_keys_top1(cb, ds, row0, head, spare));
+    HIPCHK(hipMemcpyAsync(kv, spare, sizeof(uint64_t) * (size_t)head, hipMemcpyDeviceToDevice, e->stream));
+    if (p.decode) CHK(update_decode(e, cb, 0, head, kv, d_sc, b));
+    CHK(update_members(e, cb, ds, p, row0, count, kv, d_sc, b));
+  }
+  cb->prep_valid = false;
+  return update_order_apply(e, cb, ds, p, row0, count, d_sc, b, !redo);
 }
 // the plan som_update_run makes for a run (somhip.h): the same checks as somhip_som_batch_update, host arithmetic only
 extern "C" int somhip_debug_update_plan(somhip_codebook *cb, somhip_dataset *ds, const somhip_som_params *p, int64_t batch_start_iter,
@@ -488,7 +578,8 @@ static int som_train_batched(somhip_codebook *cb, somhip_dataset *ds, const somh
   const AutoPlan plan = auto_b ? som_auto_plan(p, cb->n_global, cb->v.topol, cb->v.neigh) : AutoPlan();
   const int64_t B = auto_b ? AUTO_B_LONG : p->batch;        // the longest batch of the run
   uint64_t *dkeys; StepScalars *dsc;
-  CHK(scratch(e, SLOT_CALL_A, (size_t)B, &dkeys));
+  const size_t kspare = ((size_t)B + 4 + 31) & ~(size_t)31;   // (lazy runs: som_lazy_run)
+  CHK(scratch(e, SLOT_CALL_A, kspare + (size_t)B, &dkeys));
   CHK(scratch(e, SLOT_CALL_B, (size_t)B, &dsc));
   std::vector<uint64_t> hk((size_t)B);
   const bool trace = trace_index || trace_diff;
@@ -506,8 +597,14 @@ static int som_train_batched(somhip_codebook *cb, somhip_dataset *ds, const somh
     StepScalars *hsc = (StepScalars *)hscv;
     CHK(som_scalars(lattice_of(cb), ds, p, it0, c, row0, hsc));
     CHK(pin_upload(e, slot, dsc, sizeof(StepScalars) * (size_t)c));
-    CHK(scan_keys_top1(cb, ds, row0, c, dkeys));
-    CHK(som_update_run(cb, ds, row0, c, (const uint64_t *)dkeys, (const StepScalars *)dsc, hsc));
+    const UpdatePlan up = som_update_plan(cb, ds, row0, c, hsc);
+    // no trace wanted and the update reads only the end of the run: only that end is searched (som_lazy_run)
+    const int64_t lazy_m = trace ? 0 : som_lazy_samples(cb, up, c, hsc);
+    if (lazy_m > 0) CHK(som_lazy_run(cb, ds, up, row0, c, lazy_m, dkeys, dkeys + kspare, (const StepScalars *)dsc));
+    else {
+      CHK(scan_keys_top1(cb, ds, row0, c, dkeys));
+      CHK(som_update_planned(cb, ds, up, row0, c, (const uint64_t *)dkeys, (const StepScalars *)dsc));
+    }
     if (trace) {
       HIPCHK(hipMemcpyAsync(hk.data(), dkeys, sizeof(uint64_t) * (size_t)c, hipMemcpyDeviceToHost, e->stream));
       HIPCHK(hipStreamSynchronize(e->stream));

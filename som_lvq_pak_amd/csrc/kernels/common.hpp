@@ -28,9 +28,14 @@ enum StatWord {
   STAT_GEMM_WALK = STAT_UPDATE + 2 * STAT_UPDATE_PAIRS,
   STAT_L2_PAIRS = STAT_GEMM_WALK + STAT_GEMM_WALKS,   // (group, sample) pairs level 2 computed
   STAT_TOPK_PAIRS,                           // pairs of the top-K re-rank
+  // a lazy run of som_train_batched (host_som.inc): what its first members pass counted, not yet in STAT_UPDATE.  The
+  // pass that is kept has them folded in (fold_update_stats); one that is redone over the whole run has them zeroed.
+  STAT_UPDATE_HELD,                          // STAT_UPDATE_PAIRS {rows, pairs} pairs
+  STAT_LAZY_SHORT = STAT_UPDATE_HELD + 2 * STAT_UPDATE_PAIRS,   // row groups whose tail was not full within the samples searched
   STAT_WORDS
 };
-static_assert(STAT_WORDS == 146 && STAT_GEMM_WALK == 136 && STAT_L2_PAIRS == 144, "layout of the statistics block");
+static_assert(STAT_WORDS == 275 && STAT_GEMM_WALK == 136 && STAT_L2_PAIRS == 144 && STAT_UPDATE_HELD == 146,
+              "layout of the statistics block");
 
 struct CbView {
   float *tiles;         // [ngroups][d4][64][4]

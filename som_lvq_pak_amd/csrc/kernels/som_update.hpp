@@ -46,8 +46,9 @@ struct MemberEntry { uint32_t sample; float alpha; unsigned long long mask; };  
 constexpr int LIST_PAD = 8;
 __host__ __device__ __forceinline__ int64_t list_stride(int64_t count) { return count + LIST_PAD; }
 
-template <bool GAUSS, int NT, int RRT = 4>   // NT threads: 256, or 1024 when a small shard has few row groups to spread / the lists
-                                             // will not be cut short; RRT samples per thread and trip
+template <bool GAUSS, int NT, int RRT = 4, bool LAZY = false>   // NT threads: 256, or 1024 when a small shard has few row groups to
+                                             // spread / the lists will not be cut short; RRT samples per thread and trip;
+                                             // LAZY: the first members pass of a lazy run (lazy_trips, below)
 __global__ __launch_bounds__(NT) void k_som_members(CbView cb, int64_t count,
                                                      const int2 *__restrict__ bxy,
                                                      const uint64_t *__restrict__ keys,
@@ -58,7 +59,7 @@ __global__ __launch_bounds__(NT) void k_som_members(CbView cb, int64_t count,
                                                      int64_t xoff_first = -1, int64_t xoff_rows = 0,
                                                      int xoff_scale = 0, uint32_t tail_need = 0,
                                                      uint32_t *__restrict__ lstart = nullptr, int gauss_gemm = 0,
-                                                     int reach_max = -1) {
+                                                     int reach_max = -1, int64_t lazy_trips = 0) {
   // reach_max >= 0 (with decoded winners, bubble): the largest `reach` of the run's iterations.  A winner whose box of
   // that reach misses the group is dropped on its 8 bytes of coordinates alone -- the 16 bytes of its step scalars are
   // only fetched for the samples that pass.  (With small neighbourhoods every workgroup otherwise reads the scalars of
@@ -111,7 +112,14 @@ __global__ __launch_bounds__(NT) void k_som_members(CbView cb, int64_t count,
   const bool prepass = !GAUSS && !keys && reach_max >= 0;
   const bool tail = tail_need != 0u;
   uint32_t pos_end = static_cast<uint32_t>(count);
-  const int64_t ntrips = (count + NT * RR - 1) / (NT * RR);
+  // LAZY (lazy_trips > 0, tail mode; a lazy run of som_train_batched): only the last lazy_trips trips' samples have winners.
+  // The trips are the whole run's -- anchored at its end, indexed and written as ever -- so a group that has `enough`
+  // within them leaves the list, the count and the start it would leave with every winner known.  One that has not
+  // (a group no winner came near included) is counted in STAT_LAZY_SHORT: the host then searches the rest of the run
+  // and makes the lists again.  What this pass counts is held apart (STAT_UPDATE_HELD) until the host knows which.
+  const int64_t ntrips_run = (count + NT * RR - 1) / (NT * RR);
+  const int64_t ntrips = LAZY && lazy_trips < ntrips_run ? lazy_trips : ntrips_run;
+  bool full_tail = false;
 
   for (int64_t trip = 0; trip < ntrips; trip++) {
     const int64_t b0 = tail ? count - (trip + 1) * (NT * RR) : trip * (NT * RR);   // (tail: may start below 0)
@@ -314,8 +322,9 @@ __global__ __launch_bounds__(NT) void k_som_members(CbView cb, int64_t count,
     if (tail) pos_end -= s_wcount[RR * NW]; else base += s_wcount[RR * NW];
     const bool enough = tail && s_full >= tail_need;
     __syncthreads();
-    if (enough) break;
+    if (enough) { if (LAZY) full_tail = true; break; }
   }
+  if (LAZY && tid == 0 && !full_tail && stats) atomicAdd(stats + STAT_LAZY_SHORT, 1ull);
   if (tail) base = static_cast<uint32_t>(count) - pos_end;
   if (tid == 0) { cnt[g] = base; if (lstart) lstart[g] = tail ? pos_end : 0u; }
   if (tid < LIST_PAD) { MemberEntry z; z.sample = 0u; z.alpha = 0.0f; z.mask = 0ull; out[(tail ? static_cast<uint32_t>(count) : base) + tid] = z; }
@@ -326,7 +335,7 @@ __global__ __launch_bounds__(NT) void k_som_members(CbView cb, int64_t count,
     pairs_total += __shfl_xor(pairs_total, off, WAVE);
   }
   if (lane == 0 && stats) {     // many counter pairs (summed by the host): one pair took ~8 000 same-address atomics
-    unsigned long long *st = stats + STAT_UPDATE + 2 * (g & (STAT_UPDATE_PAIRS - 1));
+    unsigned long long *st = stats + (LAZY ? STAT_UPDATE_HELD : STAT_UPDATE) + 2 * (g & (STAT_UPDATE_PAIRS - 1));
     if (rows_total) atomicAdd(st, rows_total);
     if (pairs_total) atomicAdd(st + 1, pairs_total);
   }
@@ -335,9 +344,22 @@ __global__ __launch_bounds__(NT) void k_som_members(CbView cb, int64_t count,
 // K4c: launch order for K4 -- row groups by member count, heaviest first, so the long
 // workgroups start early and the tail of the launch is made of short ones (rank by counting;
 // ties by index).  order[rank] = group.
+// FOLD (after a lazy members pass that is kept): STAT_UPDATE_HELD of the statistics block goes into STAT_UPDATE
+__device__ __forceinline__ void fold_update_stats(unsigned long long *__restrict__ stats, int t) {
+  if (t < 2 * STAT_UPDATE_PAIRS) {
+    const unsigned long long v = stats[STAT_UPDATE_HELD + t];
+    if (v) { atomicAdd(stats + STAT_UPDATE + t, v); stats[STAT_UPDATE_HELD + t] = 0ull; }
+  }
+}
+__global__ __launch_bounds__(256) void k_fold_update_stats(unsigned long long *__restrict__ stats) {   // (no k_order_groups to ride on)
+  fold_update_stats(stats, static_cast<int>(threadIdx.x));
+}
+template <bool FOLD = false>
 __global__ __launch_bounds__(256) void k_order_groups(const uint32_t *__restrict__ cnt, int ngroups,
-                                                      uint32_t *__restrict__ order) {
+                                                      uint32_t *__restrict__ order,
+                                                      unsigned long long *__restrict__ stats = nullptr) {
   __shared__ uint32_t s_cnt[8192];                     // host guarantees ngroups <= 8192
+  if (FOLD && blockIdx.x == 0) fold_update_stats(stats, static_cast<int>(threadIdx.x));
   for (int k = threadIdx.x; k < ngroups; k += blockDim.x) s_cnt[k] = cnt[k];
   __syncthreads();
   // 8 lanes share one group's ranking (an eighth of the comparisons each)

@@ -199,6 +199,7 @@ struct somhip_engine {
   int n_cus = 0;                               // compute units of the device (grid of the persistent kernels)
   LvqCtl *lvq_hctl = nullptr;                  // pinned: read-backs of the LVQ batch loop's control block, one per batch in flight
   hipEvent_t lvq_ev[LVQ_EV_RING] = {nullptr};
+  unsigned long long *lazy_hflag = nullptr;    // pinned: read-back of STAT_LAZY_SHORT, one per lazy run of som_train_batched
 };
 
 static int check_engine(const somhip_engine *e, const char *who) { return e ? 0 : fail("%s: null engine", who); }
@@ -334,6 +335,7 @@ extern "C" void somhip_engine_destroy(somhip_engine *e) try {
     if (e->pin_ev[i]) (void)hipEventDestroy(e->pin_ev[i]);
   }
   if (e->lvq_hctl) (void)hipHostFree(e->lvq_hctl);
+  if (e->lazy_hflag) (void)hipHostFree(e->lazy_hflag);
   for (int i = 0; i < LVQ_EV_RING; i++) if (e->lvq_ev[i]) (void)hipEventDestroy(e->lvq_ev[i]);
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
