@@ -156,6 +156,10 @@ struct somhip_som_params;                          /* (below, with somhip_som_tr
 int  somhip_debug_update_plan(somhip_codebook *cb, somhip_dataset *ds, const struct somhip_som_params *p,
                               int64_t batch_start_iter, int64_t count, int64_t data_first, int32_t out[16]);
 
+/* diagnostics (tests): the device addresses a cached graph of online SOM iterations is keyed by: out[0] = the
+ * codebook's tiles, out[1] = the data rows, out[2] = the data mask (0: none) */
+int  somhip_debug_device_ptrs(somhip_codebook *cb, somhip_dataset *ds, uint64_t out[3]);
+
 /* ---- codebook mirror -------------------------------------------------------
  * rows: host, row-major [n_rows][dim] fp32, row k = list position k of the
  * reference's codebook (datafile.c:781,836) = map unit (k % xdim, k / xdim)

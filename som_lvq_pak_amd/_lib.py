@@ -59,6 +59,7 @@ SIGNATURES = {
     "somhip_debug_scan_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, c_i32_p]),
     "somhip_debug_update_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(SomParams), C.c_int64, C.c_int64, C.c_int64,
                                            c_i32_p]),
+    "somhip_debug_device_ptrs": (C.c_int, [C.c_void_p, C.c_void_p, c_u64_p]),
     "somhip_debug_lvq_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(LvqParams), C.c_int, c_i32_p]),
     "somhip_debug_lvq_relation": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(LvqParams), C.c_int64, C.c_int64, c_u64_p,
                                             c_float_p, c_float_p, c_float_p, c_u32_p, c_i32_p, c_i32_p, c_i32_p]),

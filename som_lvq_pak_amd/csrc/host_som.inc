@@ -171,6 +171,15 @@ static int som_train_online(somhip_codebook *cb, somhip_dataset *ds, const somhi
   return 0;
 }
 
+// diagnostics (include/somhip.h): the device addresses the cached graph's key compares, for the tests that train a
+// second codebook or data set on an engine that holds a graph
+extern "C" int somhip_debug_device_ptrs(somhip_codebook *cb, somhip_dataset *ds, uint64_t *out) try {
+  CHK(check_pair(cb, ds, "somhip_debug_device_ptrs"));
+  if (!out) return fail("somhip_debug_device_ptrs: null argument");
+  out[0] = (uint64_t)(uintptr_t)cb->v.tiles; out[1] = (uint64_t)(uintptr_t)ds->d_rows; out[2] = (uint64_t)(uintptr_t)ds->d_mask;
+  return 0;
+} ABI_CATCH(somhip_debug_device_ptrs)
+
 // The mini-batch update of one run: som_update_plan makes every choice, the stages only read it -- decode (K4a) ->
 // members (K4b) -> order (K4c) -> apply.  K4b writes its entries for the apply kernel the plan picks: what an entry
 // carries (`entry`), its mask field holding packed winner coordinates (`gauss_gemm`) and only a list's tail (`tail`).

@@ -102,7 +102,9 @@ __global__ __launch_bounds__(256) void k_lvq_online_step(CbView cb, const float 
       }
     }
   }
-  const int64_t grow = row + cb.row_offset;
+  // the row's unit index: what the keys carry and what labels and rates are indexed by (a labelled map stored as 8x8
+  // patches keeps its rows in another order than its units)
+  const int64_t grow = static_cast<int64_t>(unit_of_row(cb, row));
   // which (if any) correction applies to this lane's row; if both name the same row
   // (cannot happen: two distinct neighbours) the first wins
   int which = -1;

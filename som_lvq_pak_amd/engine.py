@@ -475,6 +475,14 @@ def som_train(cb, ds, length, alpha, radius, alpha_type=ALPHA_LINEAR, use_fixed=
     return ti, td
 
 
+def device_ptrs(cb, ds):
+    """(tiles, rows, mask) device addresses of a codebook and a data set (somhip_debug_device_ptrs; mask 0: none): what
+    the cached graph of online SOM iterations is keyed by."""
+    out = (C.c_uint64 * 3)()
+    check(cb.e.lib.somhip_debug_device_ptrs(cb.h, ds.h, out))
+    return int(out[0]), int(out[1]), int(out[2])
+
+
 def mapset_plan(n_rows, dim, masked=False, lib=None):
     """What a map set of this shape would be (somhip_debug_mapset_plan; host arithmetic, no GPU): a dict of whether its
     LDS image fits the budget, the workgroup's threads, units per thread, LDS bytes and the iterations per launch."""
