@@ -414,8 +414,9 @@ int  somhip_column_minmax(somhip_dataset *ds, float *lo, float *hi, int64_t *cou
 /* ---- find_qerror2 (som_rout.c:823-885; bubble_qerror :734-772, gaussian_qerror :775-818):
  * out[i] = sum over the neighbourhood of sample first+i's winner of (h *) d*d, d =
  * vector_dist_euc (lvq_pak.c:291-316), accumulated in fp32 in unit order exactly as the
- * reference does; ret[i] = 0 for samples with every component masked (the reference skips
- * them, :858).  The caller adds out[] in data order (the reference's float accumulator). */
+ * reference does; ret[i] = 0 and out[i] = 0 for samples with every component masked (the
+ * reference skips them, :858).  The caller adds out[] in data order (the reference's float
+ * accumulator). */
 int  somhip_qerror2(somhip_codebook *cb, somhip_dataset *ds, float radius, int64_t first,
                     int64_t count, float *out, int32_t *ret);
 

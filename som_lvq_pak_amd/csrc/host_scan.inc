@@ -1066,11 +1066,14 @@ extern "C" int somhip_qerror2(somhip_codebook *cb, somhip_dataset *ds, float rad
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out + off, dq, sizeof(float) * (size_t)c, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
-    if (ret)
-      for (int64_t i = 0; i < c; i++) {
-        const int64_t r = (f + i) % ds->n;
-        ret[off + i] = (!ds->all_masked.empty() && ds->all_masked[(size_t)r]) ? 0 : 1;
-      }
+    // a sample with every component masked has no winner, whatever its key says (every distance is an empty sum, 0):
+    // the kernel's sum over zero distances is 0 too, except where the rate itself is NaN (gaussian, radius 0)
+    for (int64_t i = 0; i < c; i++) {
+      const int64_t r = (f + i) % ds->n;
+      const bool empty = !ds->all_masked.empty() && ds->all_masked[(size_t)r];
+      if (empty) out[off + i] = 0.0f;
+      if (ret) ret[off + i] = empty ? 0 : 1;
+    }
   }
   return 0;
 } ABI_CATCH(somhip_qerror2)

@@ -20,7 +20,9 @@
 //     65 000;
 //   * y <= -104: e^y < 2^-150, the float is +0 (as the reference's cast of libm's tiny double); -104 < y < -87 (the
 //     float would be subnormal: the rounding point moves), a NaN or a den that is not a normal number: library chain.
-// Host-compilable (tests/helpers/gauss_rate_check.c runs it against glibc over 10^8 arguments).
+// Host-compilable: tests/helpers/gauss_rate_check.c runs it against glibc, in the suite over 1.6 10^7 arguments (test_build:
+// two seeds of 8 10^6).  The device build's own parts -- the scalar-register coefficients, v_ldexp_f64, the library
+// chain behind a call -- are met case by case in tests/test_gauss_tail.py.
 #pragma once
 #if defined(__HIPCC__)
 #define GR_FN __host__ __device__ __forceinline__
