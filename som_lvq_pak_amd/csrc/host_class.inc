@@ -28,8 +28,7 @@ static ClassOrder class_order(const std::vector<int32_t> &labels, int64_t groups
 }
 
 extern "C" int somhip_class_nearest_later(somhip_dataset *ds, float *min_sq, int32_t *state) try {
-  if (!ds || !min_sq || !state) return fail("somhip_class_nearest_later: null argument");
-  if (!ds->e) return fail("somhip_class_nearest_later: the engine of this data set was destroyed");
+  CHK(check_dataset(ds, min_sq && state, "somhip_class_nearest_later"));
   if (ds->labels.empty()) return fail("somhip_class_nearest_later: the data set has no labels");
   const int64_t n = ds->n;
   if (n > 0x7FFFFFFFll - 2 * CLASS_CHUNK) return fail("somhip_class_nearest_later: %lld rows are more than this path indexes", (long long)n);
@@ -51,35 +50,22 @@ extern "C" int somhip_class_nearest_later(somhip_dataset *ds, float *min_sq, int
   if (masked) CHK(scratch(e, SLOT_SAMPLES, (size_t)padded * d4, &d_mtiles));
   CHK(scratch(e, SLOT_PARTIAL, (size_t)padded, &d_min));
   CHK(scratch(e, SLOT_PAIRS, (size_t)padded, &d_flag));
-  HIPCHK(hipMemcpyAsync(d_perm, o.perm.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipMemcpyAsync(d_end, o.seg_end.data(), sizeof(int32_t) * (size_t)padded, hipMemcpyHostToDevice, e->stream));
+  CHK(to_device(e, d_perm, o.perm.data(), (size_t)n));
+  CHK(to_device(e, d_end, o.seg_end.data(), (size_t)padded));
   HIPCHK(hipMemsetD32Async((hipDeviceptr_t)d_min, (int)CLASS_NONE_BITS, (size_t)padded, e->stream));
   HIPCHK(hipMemsetAsync(d_flag, 0, sizeof(uint32_t) * (size_t)padded, e->stream));
-  {
-    LaunchTimer t(e, KID_LAYOUT);
-    if (masked)
-      hipLaunchKernelGGL(k_class_layout<true>, dim3((unsigned)groups), dim3(256), 0, e->stream, ds->d_rows, (const uint8_t *)ds->d_mask,
-                         (const int32_t *)d_perm, n, d, d4, d_tiles, d_mtiles);
-    else
-      hipLaunchKernelGGL(k_class_layout<false>, dim3((unsigned)groups), dim3(256), 0, e->stream, ds->d_rows, (const uint8_t *)nullptr,
-                         (const int32_t *)d_perm, n, d, d4, d_tiles, (uint32_t *)nullptr);
-  }
-  HIPCHK(hipGetLastError());
-  {
-    LaunchTimer t(e, KID_CLASS_NEAREST);
-    const dim3 grid((unsigned)blocks, (unsigned)chunks);
-    if (masked)
-      hipLaunchKernelGGL((k_class_nearest<CLASS_S_MASKED, true>), grid, dim3(256), 0, e->stream, (const float4 *)d_tiles,
-                         (const uint32_t *)d_mtiles, (const int32_t *)d_end, n, d, d4, d_min, d_flag);
-    else
-      hipLaunchKernelGGL((k_class_nearest<CLASS_S, false>), grid, dim3(256), 0, e->stream, (const float4 *)d_tiles,
-                         (const uint32_t *)nullptr, (const int32_t *)d_end, n, d, d4, d_min, d_flag);
-  }
-  HIPCHK(hipGetLastError());
+  if (masked)
+    CHK(LAUNCH_TIMED(e, KID_LAYOUT, k_class_layout<true>, dim3((unsigned)groups), dim3(256), 0, ds->d_rows, ds->d_mask, d_perm, n, d, d4, d_tiles, d_mtiles));
+  else
+    CHK(LAUNCH_TIMED(e, KID_LAYOUT, k_class_layout<false>, dim3((unsigned)groups), dim3(256), 0, ds->d_rows, nullptr, d_perm, n, d, d4, d_tiles, nullptr));
+  const dim3 grid((unsigned)blocks, (unsigned)chunks);
+  if (masked)
+    CHK(LAUNCH_TIMED(e, KID_CLASS_NEAREST, (k_class_nearest<CLASS_S_MASKED, true>), grid, dim3(256), 0, d_tiles, d_mtiles, d_end, n, d, d4, d_min, d_flag));
+  else
+    CHK(LAUNCH_TIMED(e, KID_CLASS_NEAREST, (k_class_nearest<CLASS_S, false>), grid, dim3(256), 0, d_tiles, nullptr, d_end, n, d, d4, d_min, d_flag));
   std::vector<uint32_t> hmin((size_t)n), hflag((size_t)n);
-  HIPCHK(hipMemcpyAsync(hmin.data(), d_min, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipMemcpyAsync(hflag.data(), d_flag, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
+  CHK(to_host(e, hmin.data(), d_min, (size_t)n));
+  CHK(to_host_sync(e, hflag.data(), d_flag, (size_t)n));
   for (int64_t p = 0; p < n; p++) {
     const int64_t r = o.perm[(size_t)p];
     memcpy(&min_sq[r], &hmin[(size_t)p], sizeof(float));

@@ -82,7 +82,7 @@ struct somhip_comm {
   int rank = 0, world = 1;
   ncclComm_t nccl = nullptr;          // RCCL transport
   std::vector<int> fds;               // socket transport: rank 0 holds world-1 descriptors (peer r at [r-1]), the others one
-  std::vector<char> stage, stage2;
+  std::vector<uint8_t> stage, stage2;
 };
 
 extern "C" int somhip_comm_unique_id(void *id128) try {
@@ -152,14 +152,13 @@ extern "C" int somhip_comm_allreduce_min_keys(somhip_comm *c, uint64_t *dev_keys
     return 0;
   }
   c->stage.resize(sizeof(uint64_t) * (size_t)count);
-  HIPCHK(hipMemcpyAsync(c->stage.data(), dev_keys, c->stage.size(), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
+  CHK(to_host_sync(e, c->stage.data(), reinterpret_cast<const uint8_t *>(dev_keys), c->stage.size()));
   CHK(star_allreduce(c, c->stage.data(), c->stage.size(), [count](void *a, const void *b) {
     uint64_t *x = static_cast<uint64_t *>(a);
     const uint64_t *y = static_cast<const uint64_t *>(b);
     for (int64_t i = 0; i < count; i++) x[i] = y[i] < x[i] ? y[i] : x[i];
   }));
-  HIPCHK(hipMemcpyAsync(dev_keys, c->stage.data(), c->stage.size(), hipMemcpyHostToDevice, e->stream));
+  CHK(to_device(e, reinterpret_cast<uint8_t *>(dev_keys), c->stage.data(), c->stage.size()));
   HIPCHK(hipStreamSynchronize(e->stream));
   return 0;
 } ABI_CATCH(somhip_comm_allreduce_min_keys)
@@ -174,14 +173,13 @@ extern "C" int somhip_comm_allreduce_min_f32(somhip_comm *c, float *dev_values, 
     return 0;
   }
   c->stage.resize(sizeof(float) * (size_t)count);
-  HIPCHK(hipMemcpyAsync(c->stage.data(), dev_values, c->stage.size(), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
+  CHK(to_host_sync(e, c->stage.data(), reinterpret_cast<const uint8_t *>(dev_values), c->stage.size()));
   CHK(star_allreduce(c, c->stage.data(), c->stage.size(), [count](void *a, const void *b) {
     float *x = static_cast<float *>(a);
     const float *y = static_cast<const float *>(b);
     for (int64_t i = 0; i < count; i++) x[i] = y[i] < x[i] ? y[i] : x[i];
   }));
-  HIPCHK(hipMemcpyAsync(dev_values, c->stage.data(), c->stage.size(), hipMemcpyHostToDevice, e->stream));
+  CHK(to_device(e, reinterpret_cast<uint8_t *>(dev_values), c->stage.data(), c->stage.size()));
   HIPCHK(hipStreamSynchronize(e->stream));
   return 0;
 } ABI_CATCH(somhip_comm_allreduce_min_f32)
@@ -196,14 +194,13 @@ extern "C" int somhip_comm_allreduce_sum_u32(somhip_comm *c, uint32_t *dev_words
     return 0;
   }
   c->stage.resize(sizeof(uint32_t) * (size_t)count);
-  HIPCHK(hipMemcpyAsync(c->stage.data(), dev_words, c->stage.size(), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
+  CHK(to_host_sync(e, c->stage.data(), reinterpret_cast<const uint8_t *>(dev_words), c->stage.size()));
   CHK(star_allreduce(c, c->stage.data(), c->stage.size(), [count](void *a, const void *b) {
     uint32_t *x = static_cast<uint32_t *>(a);
     const uint32_t *y = static_cast<const uint32_t *>(b);
     for (int64_t i = 0; i < count; i++) x[i] += y[i];
   }));
-  HIPCHK(hipMemcpyAsync(dev_words, c->stage.data(), c->stage.size(), hipMemcpyHostToDevice, e->stream));
+  CHK(to_device(e, reinterpret_cast<uint8_t *>(dev_words), c->stage.data(), c->stage.size()));
   HIPCHK(hipStreamSynchronize(e->stream));
   return 0;
 } ABI_CATCH(somhip_comm_allreduce_sum_u32)
@@ -219,8 +216,7 @@ extern "C" int somhip_comm_allgather(somhip_comm *c, const void *dev_send, void 
   }
   const size_t per = (size_t)bytes_per_rank;
   c->stage.resize(per * (size_t)c->world);
-  HIPCHK(hipMemcpyAsync(c->stage.data() + per * (size_t)c->rank, dev_send, per, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
+  CHK(to_host_sync(e, c->stage.data() + per * (size_t)c->rank, static_cast<const uint8_t *>(dev_send), per));
   if (c->world > 1) {
     if (c->rank == 0) {
       for (int r = 1; r < c->world; r++) if (read_all(c->fds[(size_t)r - 1], c->stage.data() + per * (size_t)r, per)) return fail("somhip_comm: rank %d went away", r);
@@ -230,7 +226,7 @@ extern "C" int somhip_comm_allgather(somhip_comm *c, const void *dev_send, void 
         return fail("somhip_comm: rank 0 went away");
     }
   }
-  HIPCHK(hipMemcpyAsync(dev_recv, c->stage.data(), c->stage.size(), hipMemcpyHostToDevice, e->stream));
+  CHK(to_device(e, static_cast<uint8_t *>(dev_recv), c->stage.data(), c->stage.size()));
   HIPCHK(hipStreamSynchronize(e->stream));
   return 0;
 } ABI_CATCH(somhip_comm_allgather)

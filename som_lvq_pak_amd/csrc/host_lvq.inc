@@ -146,10 +146,10 @@ static int lvq_trace_read(const uint64_t *d_keys, int64_t c, int knn, int64_t it
 // masked data: a sample with every component masked has no winner, and the reference then adapts through a NULL
 // winner (lvq_rout.c:542-545) -- refuse a run over such a row before anything is trained
 static int lvq_refuse_all_masked(const somhip_dataset *ds, int64_t data_first, int64_t count, const char *who) {
-  if (!ds->d_mask || ds->all_masked.empty()) return 0;
+  if (!ds->d_mask) return 0;
   for (int64_t j = 0; j < std::min<int64_t>(count, ds->n); j++) {
     const int64_t r = (data_first + j) % ds->n;
-    if (ds->all_masked[(size_t)r])
+    if (sample_is_empty(ds, r))
       return fail("%s: data row %lld has every component masked: no winner (the reference crashes here)", who, (long long)r);
   }
   return 0;
@@ -157,59 +157,41 @@ static int lvq_refuse_all_masked(const somhip_dataset *ds, int64_t data_first, i
 // OLVQ1's per-row rates to the device and back, on the engine's stream (the caller waits)
 static int lvq_rates_to_device(somhip_codebook *cb, const float *talpha) {
   if (!cb->d_talpha) HIPCHK(hipMalloc((void **)&cb->d_talpha, sizeof(float) * (size_t)cb->v.n));
-  HIPCHK(hipMemcpyAsync(cb->d_talpha, talpha, sizeof(float) * (size_t)cb->v.n, hipMemcpyHostToDevice, cb->e->stream));
-  return 0;
+  return to_device(cb->e, cb->d_talpha, talpha, (size_t)cb->v.n);
 }
 static int lvq_rates_to_host(somhip_codebook *cb, float *talpha) {
-  HIPCHK(hipMemcpyAsync(talpha, cb->d_talpha, sizeof(float) * (size_t)cb->v.n, hipMemcpyDeviceToHost, cb->e->stream));
-  return 0;
+  return to_host(cb->e, talpha, cb->d_talpha, (size_t)cb->v.n);
 }
 
 // ---- the stages of one batch (kernels/lvq_batch.hpp), each launched from here only ----------------------------------
 // front: labels and (OLVQ1; ta may be null otherwise) rates of the listed rows ...
 static int lvq_cand_meta(somhip_codebook *cb, const uint64_t *d_keys, int64_t count, int knn, bool olvq, int32_t *d_lab, float *d_ta) {
-  hipLaunchKernelGGL(k_lvq_cand_meta, dim3((unsigned)((count * LVQ_K0 + 255) / 256)), dim3(256), 0, cb->e->stream, cb->v, d_keys,
-                     count * LVQ_K0, knn, (const int32_t *)cb->d_labels, olvq ? (const float *)cb->d_talpha : (const float *)nullptr,
-                     d_lab, d_ta);
-  HIPCHK(hipGetLastError());
-  return 0;
+  return LAUNCH(cb->e, k_lvq_cand_meta, dim3((unsigned)((count * LVQ_K0 + 255) / 256)), dim3(256), 0, cb->v, d_keys, count * LVQ_K0, knn,
+                cb->d_labels, olvq ? cb->d_talpha : nullptr, d_lab, d_ta);
 }
 // ... and OLVQ1's bound on |rate| of the batch's corrections, from the listed rows' rates
 static int lvq_rate_bound(somhip_engine *e, const uint64_t *d_keys, int64_t count, const float *d_ta, float clamp, float *amax_dev) {
-  hipLaunchKernelGGL(k_lvq_amax, dim3(1), dim3(256), 0, e->stream, d_keys, count * LVQ_K0, d_ta, clamp, amax_dev);
-  HIPCHK(hipGetLastError());
-  return 0;
+  return LAUNCH(e, k_lvq_amax, dim3(1), dim3(256), 0, d_keys, count * LVQ_K0, d_ta, clamp, amax_dev);
 }
 
 // pairs: rho_j of relation (*) for every sample (masked data: the sample's norm over its own components), then the
 // relation over all pairs of the batch by the plan's kernel
 static int lvq_pairs(somhip_engine *e, somhip_dataset *ds, const LvqPlan &pl, const LvqBatchBufs &b, const LvqBatch &bt) {
-  const uint8_t *mask = (const uint8_t *)ds->d_mask;
   const unsigned nt = (unsigned)((bt.c + 63) / 64);
-  (void)with_value<1, 0>(pl.masked, [&](auto m) {       // (a bool: always found)
-    hipLaunchKernelGGL(k_lvq_sample_rho<decltype(m)::value != 0>, dim3((unsigned)((bt.c + 3) / 4)), dim3(256), 0, e->stream,
-                       ds->d_rows, ds->n, ds->d, bt.row0, bt.c, bt.cand, bt.amax, bt.amax_dev, b.rho, b.xnorm, mask);
-    return 0;
-  });
-  HIPCHK(hipGetLastError());
+  CHK((with_value<1, 0>(pl.masked, [&](auto m) {
+    return LAUNCH(e, k_lvq_sample_rho<decltype(m)::value != 0>, dim3((unsigned)((bt.c + 3) / 4)), dim3(256), 0, ds->d_rows, ds->n, ds->d, bt.row0, bt.c,
+                  bt.cand, bt.amax, bt.amax_dev, b.rho, b.xnorm, ds->d_mask);
+  })));
   if (pl.pairs == LVQ_PAIRS_MFMA)
-    hipLaunchKernelGGL(k_lvq_pair_adj_mfma, dim3(nt, nt), dim3(256), 0, e->stream, ds->d_rows, ds->n, ds->d, bt.row0, bt.c,
-                       (const float *)b.rho, (const float *)b.xnorm, b.adj);
-  else
-    (void)with_value<1, 0>(pl.masked, [&](auto m) {
-      hipLaunchKernelGGL(k_lvq_pair_adj<decltype(m)::value != 0>, dim3(nt, nt), dim3(256), 0, e->stream, ds->d_rows, ds->n,
-                         ds->d, bt.row0, bt.c, (const float *)b.rho, b.adj, mask);
-      return 0;
-    });
-  HIPCHK(hipGetLastError());
-  return 0;
+    return LAUNCH(e, k_lvq_pair_adj_mfma, dim3(nt, nt), dim3(256), 0, ds->d_rows, ds->n, ds->d, bt.row0, bt.c, b.rho, b.xnorm, b.adj);
+  return with_value<1, 0>(pl.masked, [&](auto m) {
+    return LAUNCH(e, k_lvq_pair_adj<decltype(m)::value != 0>, dim3(nt, nt), dim3(256), 0, ds->d_rows, ds->n, ds->d, bt.row0, bt.c, b.rho, b.adj,
+                  ds->d_mask);
+  });
 }
 // components: the connected components of the adjacency rows of c samples (single: one component, the rows unread)
 static int lvq_components(somhip_engine *e, const LvqBatchBufs &b, int c, bool single) {
-  hipLaunchKernelGGL(k_lvq_components, dim3(1), dim3(LVQ_BMAX), (size_t)c * LVQ_AW * 4, e->stream, (const uint32_t *)b.adj, c,
-                     single ? 1 : 0, b.comp_samples, b.out);
-  HIPCHK(hipGetLastError());
-  return 0;
+  return LAUNCH(e, k_lvq_components, dim3(1), dim3(LVQ_BMAX), (size_t)c * LVQ_AW * 4, b.adj, c, single ? 1 : 0, b.comp_samples, b.out);
 }
 // relation: the pairs stage (unless the plan makes the batch one component) and the components stage
 static int lvq_relation(somhip_engine *e, somhip_dataset *ds, const LvqPlan &pl, const LvqBatchBufs &b, const LvqBatch &bt) {
@@ -222,14 +204,10 @@ static int lvq_relation(somhip_engine *e, somhip_dataset *ds, const LvqPlan &pl,
 // mask row beside the sample)
 static int lvq_walk(somhip_codebook *cb, somhip_dataset *ds, const LvqPlan &pl, const LvqBatchBufs &b, const LvqBatch &bt, int limit) {
   somhip_engine *e = cb->e;
-  LaunchTimer t(e, KID_LVQ_BATCH_APPLY);
   return with_value<1, 0>(pl.masked, [&](auto m) {
-    hipLaunchKernelGGL(k_lvq_batch_apply<decltype(m)::value != 0>, dim3((unsigned)bt.c), dim3(LVQ_BT), pl.dyn, e->stream, cb->v,
-                       ds->d_rows, ds->n, bt.row0, limit, bt.lab, bt.ta, bt.xrows, bt.xc, bt.cand, bt.st, pl.knn, pl.slots,
-                       (const int32_t *)b.comp_samples, bt.fin, b.stage_rows, b.stage_rowid, b.stage_ta, b.out,
-                       (const uint8_t *)ds->d_mask);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return LAUNCH_TIMED(e, KID_LVQ_BATCH_APPLY, k_lvq_batch_apply<decltype(m)::value != 0>, dim3((unsigned)bt.c), dim3(LVQ_BT), pl.dyn, cb->v, ds->d_rows,
+                        ds->n, bt.row0, limit, bt.lab, bt.ta, bt.xrows, bt.xc, bt.cand, bt.st, pl.knn, pl.slots, b.comp_samples, bt.fin, b.stage_rows,
+                        b.stage_rowid, b.stage_ta, b.out, ds->d_mask);
   });
 }
 
@@ -239,13 +217,8 @@ static int lvq_commit(somhip_codebook *cb, const LvqPlan &pl, const LvqBatchBufs
                       int batch_id) {
   somhip_engine *e = cb->e;
   HIPCHK(hipMemsetAsync(b.mod_count, 0, sizeof(int32_t), e->stream));
-  LaunchTimer t(e, KID_LVQ_BATCH_APPLY);
-  hipLaunchKernelGGL(k_lvq_commit, dim3((unsigned)ncomp), dim3(256), 0, e->stream, cb->v, (const LvqBatchOut *)b.out,
-                     (const float4 *)b.stage_rows, (const int32_t *)b.stage_rowid, (const float *)b.stage_ta,
-                     pl.knn == 1 && bt.ta ? cb->d_talpha : (float *)nullptr, b.mod_rows, b.mod_count, d_ctl, batch_id,
-                     d_ctl ? bt.c : 0);
-  HIPCHK(hipGetLastError());
-  return 0;
+  return LAUNCH_TIMED(e, KID_LVQ_BATCH_APPLY, k_lvq_commit, dim3((unsigned)ncomp), dim3(256), 0, cb->v, b.out, b.stage_rows, b.stage_rowid, b.stage_ta,
+                      pl.knn == 1 && bt.ta ? cb->d_talpha : nullptr, b.mod_rows, b.mod_count, d_ctl, batch_id, d_ctl ? bt.c : 0);
 }
 
 // refresh of prepared rows: the bf16 copies / norms of exactly the rows this batch corrected (at most `bound` of them;
@@ -255,9 +228,8 @@ static int lvq_commit(somhip_codebook *cb, const LvqPlan &pl, const LvqBatchBufs
 static int lvq_refresh_prepared(somhip_codebook *cb, const LvqBatchBufs &b, int bound, const int32_t *skip) {
   somhip_engine *e = cb->e;
   if (!cb->prep_valid || !cb->d_chi || !cb->d_cn || e->scan_mode != SOMHIP_SCAN_MFMA_BF16) { cb->prep_valid = false; return 0; }
-  hipLaunchKernelGGL(k_prep_rows_bf16, dim3((unsigned)((bound + 3) / 4)), dim3(256), 0, e->stream, cb->v, (cb->v.d4 + 1) / 2,
-                     (const int32_t *)b.mod_rows, bound, (const int32_t *)b.mod_count, cb->d_cn, cb->d_chi, cb->d_clo, skip);
-  HIPCHK(hipGetLastError());
+  CHK(LAUNCH(e, k_prep_rows_bf16, dim3((unsigned)((bound + 3) / 4)), dim3(256), 0, cb->v, (cb->v.d4 + 1) / 2, b.mod_rows, bound, b.mod_count,
+      cb->d_cn, cb->d_chi, cb->d_clo, skip));
   cb->rowmajor_valid = false;                             // (the row-major copy is not re-split row by row)
   return 0;
 }
@@ -275,8 +247,7 @@ static int lvq_batch_careful(somhip_codebook *cb, somhip_dataset *ds, const LvqP
   int limit = bt.c;
   for (int pass = 0; pass < 2; pass++) {
     CHK(lvq_walk(cb, ds, pl, b, bt, limit));
-    HIPCHK(hipMemcpyAsync(ho, b.out, sizeof(LvqBatchOut), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
+    CHK(to_host_sync(e, ho, b.out, 1));
     if (ho->ncomp < 1 || ho->ncomp > bt.c) return fail("somhip_lvq_train: bad component count %d", ho->ncomp);
     int first_stop = 0x7FFFFFFF, why = 0;
     for (int k = 0; k < ho->ncomp; k++)
@@ -367,11 +338,11 @@ static int lvq_train_batched(somhip_codebook *cb, somhip_dataset *ds, const somh
         void *hv; int slot;
         CHK(pin_acquire(e, sizeof(LvqStep) * (size_t)c, &hv, &slot));
         lvq_fill_steps(ds, p, p->start_iter + launched, p->data_first + launched, c, (LvqStep *)hv);
-        CHK(pin_upload(e, slot, dst, sizeof(LvqStep) * (size_t)c));
+        CHK(pin_upload(e, slot, dst, (size_t)c));
         CHK(front(launched, c, (const LvqStep *)hv, dfin + (want_trace ? 2 * launched : 0), &bt));
         const int id = next_id++;
         CHK(lvq_batch_nowait(cb, ds, pl, b, bt, dctl, id));
-        HIPCHK(hipMemcpyAsync(&e->lvq_hctl[head % RING], dctl, sizeof(LvqCtl), hipMemcpyDeviceToHost, e->stream));
+        CHK(to_host(e, &e->lvq_hctl[head % RING], dctl, 1));
         HIPCHK(hipEventRecord(e->lvq_ev[head % RING], e->stream));
         ring[head % RING] = {launched, c, id};
         head++;
@@ -394,7 +365,7 @@ static int lvq_train_batched(somhip_codebook *cb, somhip_dataset *ds, const somh
     // ---- one batch the careful way (a plan without nowait, or the redo of a batch that stopped early)
     const int64_t c = std::min(B, p->count - off);
     lvq_fill_steps(ds, p, p->start_iter + off, p->data_first + off, c, hst.data());
-    HIPCHK(hipMemcpyAsync(dst, hst.data(), sizeof(LvqStep) * (size_t)c, hipMemcpyHostToDevice, e->stream));
+    CHK(to_device(e, dst, hst.data(), (size_t)c));
     CHK(front(off, c, hst.data(), dfin + (nowait && want_trace ? 2 * off : 0), &bt));
     int consumed = 0, reason = 0;
     CHK(lvq_batch_careful(cb, ds, pl, b, bt, &consumed, &reason));
@@ -414,8 +385,7 @@ static int lvq_train_batched(somhip_codebook *cb, somhip_dataset *ds, const somh
   }
   // statistics of the batches that never came back to the host; the winners of the whole call
   LvqCtl fin_ctl;
-  HIPCHK(hipMemcpyAsync(&fin_ctl, dctl, sizeof fin_ctl, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
+  CHK(to_host_sync(e, &fin_ctl, dctl, 1));
   if (fin_ctl.poison) return fail("somhip_lvq_train: a stopped batch was left behind (batch %d)", fin_ctl.batch);
   e->lvq_components += fin_ctl.comps;
   e->lvq_largest += fin_ctl.largest;
@@ -448,17 +418,16 @@ static int lvq_train_online(somhip_codebook *cb, somhip_dataset *ds, const somhi
   int flip = 0;
   // one iteration: the correction of the sample before (if any) with its scalars st_j, the winners of data row cur_row
   // (if has_cur); the merged winners of the sample before go to fin_j
-  auto step = [&](int64_t cur_row, int has_cur, uint64_t *fin_j, const LvqStep *st_j) {
-    LaunchTimer t(e, KID_LVQ_ONLINE_STEP);
-    (void)with_value<1, 0>(pl.masked, [&](auto m) {       // (a bool: always found)
-      hipLaunchKernelGGL(k_lvq_online_step<decltype(m)::value != 0>, dim3((unsigned)nblk), dim3(256), 0, e->stream, cb->v,
-                         ds->d_rows, (const uint8_t *)ds->d_mask, (const int32_t *)cb->d_labels, cb->d_talpha, prev_row, cur_row,
-                         have_prev ? 1 : 0, has_cur, pl.knn, (const uint64_t *)part[flip], nblk, part[flip ^ 1], fin_j, st_j);
-      return 0;
-    });
+  auto step = [&](int64_t cur_row, int has_cur, uint64_t *fin_j, const LvqStep *st_j) -> int {
+    CHK((with_value<1, 0>(pl.masked, [&](auto m) {
+      return LAUNCH_TIMED(e, KID_LVQ_ONLINE_STEP, k_lvq_online_step<decltype(m)::value != 0>, dim3((unsigned)nblk), dim3(256), 0, cb->v, ds->d_rows,
+                          ds->d_mask, cb->d_labels, cb->d_talpha, prev_row, cur_row, have_prev ? 1 : 0, has_cur, pl.knn, part[flip], nblk,
+                          part[flip ^ 1], fin_j, st_j);
+    })));
     flip ^= 1;
     prev_row = cur_row;
     have_prev = true;
+    return 0;
   };
   // fin[j] receives the merged winners of chunk-iteration j-1 when iteration j launches;
   // the last one of a chunk lands in fin[c] when the next chunk's first launch (or the
@@ -467,25 +436,21 @@ static int lvq_train_online(somhip_codebook *cb, somhip_dataset *ds, const somhi
     const int64_t c = std::min(CH, p->count - off);
     const int64_t row0 = (p->data_first + off) % ds->n;
     lvq_fill_steps(ds, p, p->start_iter + off, row0, c, hst.data() + 1);
-    HIPCHK(hipMemcpyAsync(st + 1, hst.data() + 1, sizeof(LvqStep) * (size_t)c, hipMemcpyHostToDevice, e->stream));
-    for (int64_t j = 0; j < c; j++) step((row0 + j) % ds->n, 1, fin + 2 * j, st + j);
-    HIPCHK(hipGetLastError());
+    CHK(to_device(e, st + 1, hst.data() + 1, (size_t)c));
+    for (int64_t j = 0; j < c; j++) CHK(step((row0 + j) % ds->n, 1, fin + 2 * j, st + j));
     // winners of iterations (off-1 .. off+c-2) are now in fin[0..c-1]; fin[0] of the first chunk holds nothing
     if (want_trace) {
-      HIPCHK(hipMemcpyAsync(hfin.data(), fin, sizeof(uint64_t) * 2 * (size_t)c, hipMemcpyDeviceToHost, e->stream));
-      HIPCHK(hipStreamSynchronize(e->stream));
+      CHK(to_host_sync(e, hfin.data(), fin, 2 * (size_t)c));
       const int64_t skip = off == 0 ? 1 : 0;
       lvq_trace(hfin.data() + 2 * skip, c - skip, pl.knn, off - 1 + skip, trace_index, trace_diff);
     }
-    HIPCHK(hipMemcpyAsync(st, st + c, sizeof(LvqStep), hipMemcpyDeviceToDevice, e->stream));
+    CHK(on_device(e, st, st + c, 1));
     HIPCHK(hipStreamSynchronize(e->stream));
   }
   // flush: apply the last iteration's correction; its winners land in fin[0]
-  step(prev_row, 0, fin, st);
-  HIPCHK(hipGetLastError());
+  CHK(step(prev_row, 0, fin, st));
   if (want_trace) {
-    HIPCHK(hipMemcpyAsync(hfin.data(), fin, sizeof(uint64_t) * 2, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
+    CHK(to_host_sync(e, hfin.data(), fin, 2));
     lvq_trace(hfin.data(), 1, pl.knn, p->count - 1, trace_index, trace_diff);
   }
   return 0;
@@ -505,7 +470,7 @@ extern "C" int somhip_lvq_train(somhip_codebook *cb, somhip_dataset *ds, const s
   if (p->length <= 0 || p->count < 0 || p->start_iter + p->count > p->length)
     return fail("somhip_lvq_train: iterations outside schedule");
   CHK(lvq_refuse_all_masked(ds, p->data_first, p->count, "somhip_lvq_train"));
-  if (cb->v.row_offset != 0 || cb->n_global != cb->v.n) return fail("somhip_lvq_train: sharded codebook not supported");
+  if (is_shard(cb)) return fail("somhip_lvq_train: sharded codebook not supported");
   const LvqPlan pl = lvq_plan(cb, ds, p, trace_index || trace_diff);
   if (pl.knn == 2 && cb->v.n < 2) return fail("somhip_lvq_train: LVQ2/LVQ3 need at least two code rows");
   if (p->count == 0) return 0;
@@ -525,9 +490,8 @@ static int lvq_read_components(somhip_engine *e, const LvqBatchBufs &b, int coun
                                int32_t *comp_samples) {
   std::vector<char> hbuf(sizeof(LvqBatchOut));
   LvqBatchOut *ho = reinterpret_cast<LvqBatchOut *>(hbuf.data());
-  HIPCHK(hipMemcpyAsync(ho, b.out, sizeof(LvqBatchOut), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipMemcpyAsync(comp_samples, b.comp_samples, sizeof(int32_t) * (size_t)count, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
+  CHK(to_host(e, ho, b.out, 1));
+  CHK(to_host_sync(e, comp_samples, b.comp_samples, (size_t)count));
   *ncomp = ho->ncomp;
   const int nc = std::max(0, std::min(ho->ncomp, count));  // (a wrong count is the caller's finding; read inside the block)
   for (int k = 0; k <= count; k++) start[k] = k <= nc ? ho->start[k] : -1;
@@ -547,7 +511,7 @@ extern "C" int somhip_debug_lvq_relation(somhip_codebook *cb, somhip_dataset *ds
   if (p->length <= 0 || p->start_iter < 0 || p->start_iter + count > p->length)
     return fail("somhip_debug_lvq_relation: iterations outside schedule");
   if (p->kind == SOMHIP_OLVQ1 && !cb->d_talpha) return fail("somhip_debug_lvq_relation: OLVQ1 needs rates (somhip_lvq_rates_upload)");
-  if (cb->v.row_offset != 0 || cb->n_global != cb->v.n) return fail("somhip_debug_lvq_relation: sharded codebook not supported");
+  if (is_shard(cb)) return fail("somhip_debug_lvq_relation: sharded codebook not supported");
   CHK(lvq_refuse_all_masked(ds, data_first, count, "somhip_debug_lvq_relation"));
   const LvqPlan pl = lvq_plan(cb, ds, p, false);
   if (!pl.batched)
@@ -570,17 +534,17 @@ extern "C" int somhip_debug_lvq_relation(somhip_codebook *cb, somhip_dataset *ds
   const LvqBatch bt = {row0, c, nullptr, (const uint64_t *)dcand, b.cand_lab, ta, nullptr, 0,
                        pl.olvq ? 0.0f : lvq_amax_of(hst.data(), c), pl.olvq ? b.amax_dev : (float *)nullptr, nullptr};
   CHK(lvq_relation(e, ds, pl, b, bt));
-  HIPCHK(hipMemcpyAsync(keys, dcand, sizeof(uint64_t) * (size_t)c * LVQ_K0, hipMemcpyDeviceToHost, e->stream));
+  CHK(to_host(e, keys, dcand, (size_t)c * LVQ_K0));
   *amax = bt.amax;
-  if (pl.olvq) HIPCHK(hipMemcpyAsync(amax, b.amax_dev, sizeof(float), hipMemcpyDeviceToHost, e->stream));
+  if (pl.olvq) CHK(to_host(e, amax, b.amax_dev, 1));
   if (pl.single) {                                        // no pairs stage: nothing of it to report
     std::fill(rho, rho + c, 0.0f);
     std::fill(xnorm, xnorm + c, 0.0f);
     std::fill(adj, adj + (size_t)c * LVQ_AW, 0u);
   } else {
-    HIPCHK(hipMemcpyAsync(rho, b.rho, sizeof(float) * (size_t)c, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(xnorm, b.xnorm, sizeof(float) * (size_t)c, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(adj, b.adj, sizeof(uint32_t) * (size_t)c * LVQ_AW, hipMemcpyDeviceToHost, e->stream));
+    CHK(to_host(e, rho, b.rho, (size_t)c));
+    CHK(to_host(e, xnorm, b.xnorm, (size_t)c));
+    CHK(to_host(e, adj, b.adj, (size_t)c * LVQ_AW));
   }
   CHK(lvq_read_components(e, b, c, ncomp, start, comp_samples));
   // words past the batch's last sample belong to no pair: no kernel writes or reads them
@@ -596,7 +560,7 @@ extern "C" int somhip_debug_lvq_components(somhip_engine *e, const uint32_t *adj
   HIPCHK(hipSetDevice(e->device));
   LvqBatchBufs b;
   CHK(lvq_batch_bufs(e, 1, &b));
-  HIPCHK(hipMemcpyAsync(b.adj, adj, sizeof(uint32_t) * (size_t)count * LVQ_AW, hipMemcpyHostToDevice, e->stream));
+  CHK(to_device(e, b.adj, adj, (size_t)count * LVQ_AW));
   CHK(lvq_components(e, b, (int)count, single != 0));
   return lvq_read_components(e, b, (int)count, ncomp, start, comp_samples);
 } ABI_CATCH(somhip_debug_lvq_components)
@@ -607,16 +571,14 @@ extern "C" int somhip_debug_lvq_components(somhip_engine *e, const uint32_t *adj
 // collectives between them (include/somhip.h)
 // ---------------------------------------------------------------------------------
 extern "C" int somhip_lvq_rates_upload(somhip_codebook *cb, const float *talpha) try {
-  if (!cb || !talpha) return fail("somhip_lvq_rates_upload: null argument");
-  if (!cb->e) return fail("somhip_lvq_rates_upload: the engine of this codebook was destroyed");
+  CHK(check_codebook(cb, talpha, "somhip_lvq_rates_upload"));
   HIPCHK(hipSetDevice(cb->e->device));
   CHK(lvq_rates_to_device(cb, talpha));
   HIPCHK(hipStreamSynchronize(cb->e->stream));
   return 0;
 } ABI_CATCH(somhip_lvq_rates_upload)
 extern "C" int somhip_lvq_rates_download(somhip_codebook *cb, float *talpha) try {
-  if (!cb || !talpha) return fail("somhip_lvq_rates_download: null argument");
-  if (!cb->e) return fail("somhip_lvq_rates_download: the engine of this codebook was destroyed");
+  CHK(check_codebook(cb, talpha, "somhip_lvq_rates_download"));
   if (!cb->d_talpha) return fail("somhip_lvq_rates_download: no rates on this codebook");
   HIPCHK(hipSetDevice(cb->e->device));
   CHK(lvq_rates_to_host(cb, talpha));
@@ -631,16 +593,13 @@ extern "C" int somhip_merge_topk_keys(somhip_engine *e, const uint64_t *dev_gath
   if (count == 0) return 0;
   HIPCHK(hipSetDevice(e->device));
   return with_topk_width(knn, "somhip_merge_topk_keys", [&](auto k) {
-    hipLaunchKernelGGL(k_merge_shard_topk<decltype(k)::value>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, e->stream,
-                       dev_gathered, n_shards, count, dev_keys);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return LAUNCH(e, k_merge_shard_topk<decltype(k)::value>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, dev_gathered, n_shards, count,
+                  dev_keys);
   });
 } ABI_CATCH(somhip_merge_topk_keys)
 extern "C" int somhip_lvq_batch_candidates(somhip_codebook *cb, int64_t count, int kind, const uint64_t *dev_keys, int xrows,
                                            int32_t *dev_lab, float *dev_ta, float *dev_rows) try {
-  if (!cb || !dev_keys || !dev_lab || !dev_rows) return fail("somhip_lvq_batch_candidates: null argument");
-  if (!cb->e) return fail("somhip_lvq_batch_candidates: the engine of this codebook was destroyed");
+  CHK(check_codebook(cb, dev_keys && dev_lab && dev_rows, "somhip_lvq_batch_candidates"));
   if (kind < SOMHIP_LVQ1 || kind > SOMHIP_LVQ3) return fail("Unknown LVQ type %d", kind);
   if (count < 0 || count > LVQ_BMAX) return fail("somhip_lvq_batch_candidates: at most %d samples per batch", LVQ_BMAX);
   if (xrows < 1 || xrows > LVQ_K0) return fail("somhip_lvq_batch_candidates: xrows must be 1..%d", LVQ_K0);
@@ -652,10 +611,8 @@ extern "C" int somhip_lvq_batch_candidates(somhip_codebook *cb, int64_t count, i
   HIPCHK(hipSetDevice(e->device));
   const int knn = kind >= SOMHIP_LVQ2 ? 2 : 1;
   CHK(lvq_cand_meta(cb, dev_keys, count, knn, kind == SOMHIP_OLVQ1, dev_lab, dev_ta));
-  hipLaunchKernelGGL(k_lvq_cand_rows, dim3((unsigned)(count * xrows)), dim3(256), 0, e->stream, cb->v, dev_keys, (int)count, xrows, knn,
-                     reinterpret_cast<float4 *>(dev_rows));
-  HIPCHK(hipGetLastError());
-  return 0;
+  return LAUNCH(e, k_lvq_cand_rows, dim3((unsigned)(count * xrows)), dim3(256), 0, cb->v, dev_keys, (int)count, xrows, knn,
+                reinterpret_cast<float4 *>(dev_rows));
 } ABI_CATCH(somhip_lvq_batch_candidates)
 
 extern "C" int somhip_lvq_batch_apply(somhip_codebook *cb, somhip_dataset *ds, const somhip_lvq_params *p,
@@ -685,7 +642,7 @@ extern "C" int somhip_lvq_batch_apply(somhip_codebook *cb, somhip_dataset *ds, c
   std::vector<LvqStep> hst((size_t)count);
   const int64_t row0 = data_first % ds->n;
   lvq_fill_steps(ds, p, batch_start_iter, row0, count, hst.data());
-  HIPCHK(hipMemcpyAsync(dst, hst.data(), sizeof(LvqStep) * (size_t)count, hipMemcpyHostToDevice, e->stream));
+  CHK(to_device(e, dst, hst.data(), (size_t)count));
   if (pl.olvq) CHK(lvq_rate_bound(e, dev_keys, count, dev_ta, p->alpha, b.amax_dev));
   const LvqBatch bt = {row0, (int)count, (const LvqStep *)dst, dev_keys, dev_lab, pl.olvq ? dev_ta : (const float *)nullptr,
                        reinterpret_cast<const float4 *>(dev_rows), xrows, pl.olvq ? 0.0f : lvq_amax_of(hst.data(), (int)count),

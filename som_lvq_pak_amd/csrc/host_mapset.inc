@@ -115,8 +115,7 @@ extern "C" int somhip_mapset_download(somhip_mapset *ms, int first_map, int n_ma
   if (n_maps == 0) return 0;
   const size_t per = (size_t)ms->n * ms->d;
   HIPCHK(hipSetDevice(ms->e->device));
-  HIPCHK(hipMemcpyAsync(rows, ms->d_rows + per * first_map, sizeof(float) * per * n_maps, hipMemcpyDeviceToHost, ms->e->stream));
-  HIPCHK(hipStreamSynchronize(ms->e->stream));
+  CHK(to_host_sync(ms->e, rows, ms->d_rows + per * first_map, per * n_maps));
   return 0;
 } ABI_CATCH(somhip_mapset_download)
 extern "C" int somhip_mapset_upload(somhip_mapset *ms, int first_map, int n_maps, const float *rows) try {
@@ -126,7 +125,7 @@ extern "C" int somhip_mapset_upload(somhip_mapset *ms, int first_map, int n_maps
   if (n_maps == 0) return 0;
   const size_t per = (size_t)ms->n * ms->d;
   HIPCHK(hipSetDevice(ms->e->device));
-  HIPCHK(hipMemcpyAsync(ms->d_rows + per * first_map, rows, sizeof(float) * per * n_maps, hipMemcpyHostToDevice, ms->e->stream));
+  CHK(to_device(ms->e, ms->d_rows + per * first_map, rows, per * n_maps));
   HIPCHK(hipStreamSynchronize(ms->e->stream));
   return 0;
 } ABI_CATCH(somhip_mapset_upload)
@@ -157,24 +156,21 @@ static int mapset_train(somhip_mapset *ms, somhip_dataset *ds, const somhip_som_
     int64_t *hrow = (int64_t *)(hsc + c);
     CHK(som_scalars(ms->lat, ds, p, it0, c, row0, hsc));
     for (int64_t j = 0; j < c; j++) hrow[j] = (row0 + j) % ds->n;
-    HIPCHK(hipMemcpyAsync(sc, hsc, sizeof(StepScalars) * (size_t)c, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(rowidx, hrow, sizeof(int64_t) * (size_t)c, hipMemcpyHostToDevice, e->stream));
+    CHK(to_device(e, sc, hsc, (size_t)c));
+    CHK(to_device(e, rowidx, hrow, (size_t)c));
     HIPCHK(hipEventRecord(e->pin_ev[slot], e->stream));
     {
       LaunchTimer t(e, KID_MAPSET_TRAIN);
       const int rc = with_value<1, 0>(G, [&](auto g) { return with_value<1, 0>(M, [&](auto m) {
         constexpr bool GG = decltype(g)::value != 0, MM = decltype(m)::value != 0;
         CHK(raise_lds_limit(e, (LdsKernel)(LDS_MAPSET_TRAIN + 2 * GG + MM), (const void *)(k_mapset_train<GG, MM>), MAPSET_LDS_LIMIT));
-        hipLaunchKernelGGL((k_mapset_train<GG, MM>), dim3((unsigned)ms->n_maps), dim3((unsigned)ms->plan.threads), (size_t)ms->plan.lds_bytes,
-                           e->stream, shape, ms->d_rows, ds->d_rows, (const uint8_t *)ds->d_mask, (const StepScalars *)sc,
-                           (const int64_t *)rowidx, (int)c, keys); return 0;
+        return LAUNCH(e, (k_mapset_train<GG, MM>), dim3((unsigned)ms->n_maps), dim3((unsigned)ms->plan.threads), (size_t)ms->plan.lds_bytes, shape,
+                      ms->d_rows, ds->d_rows, ds->d_mask, sc, rowidx, (int)c, keys);
       }); });
       CHK(rc);
     }
-    HIPCHK(hipGetLastError());
     if (trace) {
-      HIPCHK(hipMemcpyAsync(hkeys.data(), keys, sizeof(uint64_t) * (size_t)c * ms->n_maps, hipMemcpyDeviceToHost, e->stream));
-      HIPCHK(hipStreamSynchronize(e->stream));   // (hsc is still this chunk's: the ring has not come round)
+      CHK(to_host_sync(e, hkeys.data(), keys, (size_t)c * ms->n_maps));   // (hsc is still this chunk's: the ring has not come round)
       for (int m = 0; m < ms->n_maps; m++)
         som_trace(hsc, hkeys.data() + (size_t)m * c, c, (int64_t)m * p->count + off, trace_index, trace_diff);
     }
@@ -218,17 +214,15 @@ extern "C" int somhip_mapset_winners(somhip_mapset *ms, somhip_dataset *ds, int6
       const int rc = with_value<1, 0>(M, [&](auto m) {
         constexpr bool MM = decltype(m)::value != 0;
         CHK(raise_lds_limit(e, (LdsKernel)(LDS_MAPSET_WINNERS + MM), (const void *)(k_mapset_winners<MM>), MAPSET_LDS_LIMIT));
-        hipLaunchKernelGGL((k_mapset_winners<MM>), dim3((unsigned)ms->n_maps, (unsigned)((c + MAPSET_WINNER_SAMPLES - 1) / MAPSET_WINNER_SAMPLES)),
-                           dim3((unsigned)ms->plan.threads), (size_t)ms->plan.lds_bytes, e->stream, shape, (const float *)ms->d_rows,
-                           ds->d_rows, (const uint8_t *)ds->d_mask, ds->n, f, c, MAPSET_WINNER_SAMPLES, keys); return 0;
+        return LAUNCH(e, (k_mapset_winners<MM>), dim3((unsigned)ms->n_maps, (unsigned)((c + MAPSET_WINNER_SAMPLES - 1) / MAPSET_WINNER_SAMPLES)),
+                      dim3((unsigned)ms->plan.threads), (size_t)ms->plan.lds_bytes, shape, ms->d_rows, ds->d_rows, ds->d_mask, ds->n, f, c,
+                      MAPSET_WINNER_SAMPLES, keys);
       });
       CHK(rc);
     }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(hk.data(), keys, sizeof(uint64_t) * (size_t)c * ms->n_maps, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
+    CHK(to_host_sync(e, hk.data(), keys, (size_t)c * ms->n_maps));
     for (int64_t i = 0; i < c; i++) {
-      const bool empty = !ds->all_masked.empty() && ds->all_masked[(size_t)((f + i) % ds->n)];
+      const bool empty = sample_is_empty(ds, (f + i) % ds->n);
       for (int m = 0; m < ms->n_maps; m++) {
         const size_t o = (size_t)m * count + off + i;
         if (empty) { index[o] = -2; diff[o] = -1.0f; }

@@ -5,9 +5,8 @@
 // carry no LaunchTimer; tools/planes_measure.py times them from a kernel trace.
 
 extern "C" int somhip_planes(somhip_codebook *cb, int first_plane, int n_planes, float *grey, float *lo, float *hi) try {
-  if (!cb || !grey) return fail("somhip_planes: null argument");
-  if (!cb->e) return fail("somhip_planes: the engine of this codebook was destroyed");
-  if (cb->v.patch_stride > 1 || cb->v.row_offset != 0 || cb->v.n != cb->n_global)
+  CHK(check_codebook(cb, grey, "somhip_planes"));
+  if (is_shard(cb))
     return fail("somhip_planes: the codebook is a shard (%lld of %lld rows); the planes need every row",
                 (long long)cb->v.n, (long long)cb->n_global);
   if (n_planes < 1) return fail("somhip_planes: %d planes asked for (at least 1)", n_planes);
@@ -32,18 +31,11 @@ extern "C" int somhip_planes(somhip_codebook *cb, int first_plane, int n_planes,
   float *d_hi = d_lo + n_planes;
   const int64_t grey_blocks = (int64_t)chunk_blocks * cb->v.ngroups;
   if (grey_blocks > 0x7FFFFFFFll) return fail("somhip_planes: %lld workgroups are more than one launch takes", (long long)grey_blocks);
-  hipLaunchKernelGGL(k_planes_minmax, dim3((unsigned)(chunk_blocks * n_slabs)), dim3(256), 0, e->stream, cb->v, first_plane, n_planes,
-                     chunk_blocks, n_slabs, d_part);
-  HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(k_planes_bounds, dim3((unsigned)((n_planes + 3) / 4)), dim3(256), 0, e->stream, cb->v, first_plane, n_planes, n_slabs,
-                     (const unsigned long long *)d_part, d_lo, d_hi);
-  HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(k_planes_grey, dim3((unsigned)grey_blocks), dim3(256), 0, e->stream, cb->v, first_plane, n_planes, chunk_blocks,
-                     (const float *)d_lo, (const float *)d_hi, d_grey);
-  HIPCHK(hipGetLastError());
-  if (lo) HIPCHK(hipMemcpyAsync(lo, d_lo, sizeof(float) * (size_t)n_planes, hipMemcpyDeviceToHost, e->stream));
-  if (hi) HIPCHK(hipMemcpyAsync(hi, d_hi, sizeof(float) * (size_t)n_planes, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipMemcpyAsync(grey, d_grey, sizeof(float) * total, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  return 0;
+  CHK(LAUNCH(e, k_planes_minmax, dim3((unsigned)(chunk_blocks * n_slabs)), dim3(256), 0, cb->v, first_plane, n_planes, chunk_blocks, n_slabs,
+      d_part));
+  CHK(LAUNCH(e, k_planes_bounds, dim3((unsigned)((n_planes + 3) / 4)), dim3(256), 0, cb->v, first_plane, n_planes, n_slabs, d_part, d_lo, d_hi));
+  CHK(LAUNCH(e, k_planes_grey, dim3((unsigned)grey_blocks), dim3(256), 0, cb->v, first_plane, n_planes, chunk_blocks, d_lo, d_hi, d_grey));
+  if (lo) CHK(to_host(e, lo, d_lo, (size_t)n_planes));
+  if (hi) CHK(to_host(e, hi, d_hi, (size_t)n_planes));
+  return to_host_sync(e, grey, d_grey, total);
 } ABI_CATCH(somhip_planes)

@@ -16,7 +16,7 @@ static SammonTable sammon_table(int64_t noc) {
 static int sammon_check_codebook(const char *who, somhip_codebook *cb) {
   if (!cb) return fail("%s: null codebook", who);
   if (!cb->e) return fail("%s: the engine of this codebook was destroyed", who);
-  if (cb->v.patch_stride > 1 || cb->v.row_offset != 0 || cb->v.n != cb->n_global)
+  if (is_shard(cb))
     return fail("%s: the codebook is a shard (%lld of %lld rows); the Sammon mapping needs the whole one", who,
                 (long long)cb->v.n, (long long)cb->n_global);
   if (cb->v.n > (int64_t)SAMMON_TILE * 65535)             // the pair tiles are a two-dimensional grid
@@ -29,11 +29,7 @@ static int sammon_stage_rows(somhip_codebook *cb, const float **rows) {
   somhip_engine *e = cb->e;
   float *stage;
   CHK(scratch(e, SLOT_STAGE, (size_t)cb->v.n * cb->v.d, &stage));
-  {
-    LaunchTimer t(e, KID_LAYOUT);
-    hipLaunchKernelGGL(k_tiles_to_rows, dim3((unsigned)cb->v.ngroups), dim3(256), 0, e->stream, stage, cb->v);
-  }
-  HIPCHK(hipGetLastError());
+  CHK(LAUNCH_TIMED(e, KID_LAYOUT, k_tiles_to_rows, dim3((unsigned)cb->v.ngroups), dim3(256), 0, stage, cb->v));
   *rows = stage;
   return 0;
 }
@@ -46,15 +42,9 @@ static int sammon_distances(somhip_codebook *cb, const float *rows, float *D, in
   CHK(scratch(e, SLOT_CALL_A, 1, &d_count));
   HIPCHK(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), e->stream));
   const unsigned tiles = (unsigned)((cb->v.n + SAMMON_TILE - 1) / SAMMON_TILE);
-  {
-    LaunchTimer t(e, KID_SAMMON_DIST);
-    hipLaunchKernelGGL(k_sammon_dist, dim3(tiles, tiles), dim3(256), 0, e->stream, rows, (int)cb->v.n, cb->v.d, D, ld,
-                       d_pairs, (unsigned long long)cap, d_count);
-  }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(n_zero, d_count, sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  return 0;
+  CHK(LAUNCH_TIMED(e, KID_SAMMON_DIST, k_sammon_dist, dim3(tiles, tiles), dim3(256), 0, rows, (int)cb->v.n, cb->v.d, D, ld, d_pairs,
+      (unsigned long long)cap, d_count));
+  return to_host_sync(e, n_zero, d_count, 1);
 }
 
 extern "C" int somhip_sammon_zero_pairs(somhip_codebook *cb, uint32_t *pairs, int64_t cap, int64_t *n_pairs) try {
@@ -72,8 +62,7 @@ extern "C" int somhip_sammon_zero_pairs(somhip_codebook *cb, uint32_t *pairs, in
   *n_pairs = (int64_t)found;
   const int64_t have = std::min<int64_t>((int64_t)found, cap);
   if (have > 0) {
-    HIPCHK(hipMemcpyAsync(pairs, d_pairs, sizeof(uint32_t) * 2 * (size_t)have, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
+    CHK(to_host_sync(e, pairs, d_pairs, 2 * (size_t)have));
     std::vector<uint64_t> keys((size_t)have);                  // sort by (i, j): the kernel appends in no order
     for (int64_t t = 0; t < have; t++) keys[(size_t)t] = ((uint64_t)pairs[2 * t] << 32) | pairs[2 * t + 1];
     std::sort(keys.begin(), keys.end());
@@ -122,35 +111,21 @@ extern "C" int somhip_sammon(somhip_codebook *cb, int64_t rlen, float *x, float 
   CHK(sammon_distances(cb, rows, b.D, pl.ld, nullptr, 0, &n_zero));
   if (n_zero) return fail("somhip_sammon: %llu pair(s) of rows at distance 0 (somhip_sammon_zero_pairs lists them): the "
                           "iteration would divide by it -- remove the identical rows first", n_zero);
-  HIPCHK(hipMemcpyAsync(dx, x, sizeof(float) * (size_t)noc, hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipMemcpyAsync(dy, y, sizeof(float) * (size_t)noc, hipMemcpyHostToDevice, e->stream));
+  CHK(to_device(e, dx, x, (size_t)noc));
+  CHK(to_device(e, dy, y, (size_t)noc));
   for (int64_t it = 0; it < rlen; it++) {
-    {
-      LaunchTimer t(e, KID_SAMMON_SWEEP);
-      hipLaunchKernelGGL(k_sammon_sweep, dim3((unsigned)((noc + SAMMON_JB - 1) / SAMMON_JB)), dim3(256), 0, e->stream,
-                         (const float *)b.D, pl.ld, noc, (const float *)dx, (const float *)dy, dxu, dyu);
-    }
-    HIPCHK(hipGetLastError());
-    {
-      LaunchTimer t(e, KID_SAMMON_CENTRE);
-      hipLaunchKernelGGL(k_sammon_centre, dim3(1), dim3(256), 0, e->stream, dxu, dyu, dx, dy, noc);
-    }
-    HIPCHK(hipGetLastError());
+    CHK(LAUNCH_TIMED(e, KID_SAMMON_SWEEP, k_sammon_sweep, dim3((unsigned)((noc + SAMMON_JB - 1) / SAMMON_JB)), dim3(256), 0, b.D, pl.ld, noc, dx, dy,
+        dxu, dyu));
+    CHK(LAUNCH_TIMED(e, KID_SAMMON_CENTRE, k_sammon_centre, dim3(1), dim3(256), 0, dxu, dyu, dx, dy, noc));
     if (mapping_error) {
-      {
-        LaunchTimer t(e, KID_SAMMON_ERROR);
-        hipLaunchKernelGGL(k_sammon_error, dim3(err_blocks), dim3(256), 0, e->stream, b.D, pl.ld, noc, dx, dy, b.part);
-      }
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipMemcpyAsync(part.data(), b.part, sizeof(double) * part.size(), hipMemcpyDeviceToHost, e->stream));
-      HIPCHK(hipStreamSynchronize(e->stream));
+      CHK(LAUNCH_TIMED(e, KID_SAMMON_ERROR, k_sammon_error, dim3(err_blocks), dim3(256), 0, b.D, pl.ld, noc, dx, dy, b.part));
+      CHK(to_host_sync(e, part.data(), b.part, part.size()));
       double es = 0.0, tot = 0.0;
       for (unsigned k = 0; k < err_blocks; k++) { es += part[2 * k]; tot += part[2 * k + 1]; }
       mapping_error[it] = es / tot;
     }
   }
-  HIPCHK(hipMemcpyAsync(x, dx, sizeof(float) * (size_t)noc, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipMemcpyAsync(y, dy, sizeof(float) * (size_t)noc, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
+  CHK(to_host(e, x, dx, (size_t)noc));
+  CHK(to_host_sync(e, y, dy, (size_t)noc));
   return 0;
 } ABI_CATCH(somhip_sammon)

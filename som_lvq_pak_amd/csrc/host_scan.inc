@@ -213,16 +213,14 @@ static int pf_prepare(somhip_codebook *cb, somhip_dataset *ds, int64_t first, in
   unsigned int *cnmax = cb->d_cnmax + cb->cnmax_sel;
   if (!p.bf16 || !cb->cnmax_clean) HIPCHK(hipMemsetAsync(cnmax, 0, sizeof(unsigned int), e->stream));
   cb->cnmax_clean = false;
-  if (!p.bf16) {
-    LaunchTimer t(e, KID_PACK_SAMPLES);
-    hipLaunchKernelGGL(k_pack_samples<SCAN_S>, dim3((unsigned)p.nsb), dim3(256), 0, e->stream, ds->d_rows, ds->n,
-                       ds->d, cb->v.d4, first, count, (float4 *)b.xt);
-  }
+  if (!p.bf16)
+    CHK(LAUNCH_TIMED(e, KID_PACK_SAMPLES, k_pack_samples<SCAN_S>, dim3((unsigned)p.nsb), dim3(256), 0, ds->d_rows, ds->n, ds->d, cb->v.d4, first, count,
+        (float4 *)b.xt));
   {
     LaunchTimer t(e, KID_NORMS);
     if (prep_was_current) {
       // tiles and norms are current (unchanged codebook, or the LVQ engine re-split the rows it corrected): only the maximum is due
-      hipLaunchKernelGGL(k_max_norm, dim3(64), dim3(256), 0, e->stream, cb->v, (const float *)cb->d_cn, cnmax);
+      CHK(LAUNCH(e, k_max_norm, dim3(64), dim3(256), 0, cb->v, cb->d_cn, cnmax));
     } else if (p.bf16) {
       // with the tiles a row-major copy of the rows for the exact re-rank of single rows (k_rerank_pairs), where that
       // kernel will run behind this pre-filter on a long enough run (a shard of a map included)
@@ -232,28 +230,23 @@ static int pf_prepare(somhip_codebook *cb, somhip_dataset *ds, int64_t first, in
       const int prep_threads = d8 >= 16 ? 1024 : d8 >= 4 ? 256 : 64;
       if (want_rm) {
         CHK(raise_lds_limit(e, LDS_PREP_ROWMAJOR, (const void *)k_prep_codes_bf16<true>, PREP_RM_LDS(16)));
-        hipLaunchKernelGGL(k_prep_codes_bf16<true>, dim3((unsigned)cb->v.ngroups), dim3(prep_threads), PREP_RM_LDS(prep_threads / 64),
-                           e->stream, cb->v, d8, cb->d_cn, cnmax, cb->d_chi, cb->d_clo, cb->d_rowmajor);
+        CHK(LAUNCH(e, k_prep_codes_bf16<true>, dim3((unsigned)cb->v.ngroups), dim3(prep_threads), PREP_RM_LDS(prep_threads / 64), cb->v, d8, cb->d_cn,
+            cnmax, cb->d_chi, cb->d_clo, cb->d_rowmajor));
       } else
-        hipLaunchKernelGGL(k_prep_codes_bf16<false>, dim3((unsigned)cb->v.ngroups), dim3(prep_threads), 0,
-                           e->stream, cb->v, d8, cb->d_cn, cnmax, cb->d_chi, cb->d_clo, (float *)nullptr);
+        CHK(LAUNCH(e, k_prep_codes_bf16<false>, dim3((unsigned)cb->v.ngroups), dim3(prep_threads), 0, cb->v, d8, cb->d_cn, cnmax, cb->d_chi,
+            cb->d_clo, nullptr));
       cb->prep_valid = true;
       cb->rowmajor_valid = want_rm;
     } else {
-      hipLaunchKernelGGL(k_row_norms, dim3((unsigned)((cb->v.ngroups + 3) / 4)), dim3(256), 0, e->stream,
-                         cb->v, cb->d_cn, cnmax);
-      hipLaunchKernelGGL(k_sample_tau, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, e->stream,
-                         ds->d_rows, ds->n, ds->d, first, count, (const unsigned int *)cnmax,
-                         err_prod, err_sq, b.tau, rinit, l1_prod, l1_sq, b.tau1, b.xw);
+      CHK(LAUNCH(e, k_row_norms, dim3((unsigned)((cb->v.ngroups + 3) / 4)), dim3(256), 0, cb->v, cb->d_cn, cnmax));
+      CHK(LAUNCH(e, k_sample_tau, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, ds->d_rows, ds->n, ds->d, first, count, cnmax, err_prod, err_sq,
+          b.tau, rinit, l1_prod, l1_sq, b.tau1, b.xw));
     }
   }
-  HIPCHK(hipGetLastError());
   if (p.bf16) {
-    LaunchTimer t(e, KID_PACK_SAMPLES);
-    hipLaunchKernelGGL(k_pack_samples_bf16, dim3((unsigned)p.nsb), dim3(PACK_THREADS), 0, e->stream, ds->d_rows, ds->n, ds->d,
-                       d8, first, count, b.xhi, pack_lo ? b.xlo : (uint4 *)nullptr, cb->d_cnmax + (cb->cnmax_sel ^ 1), b.xrow,
-                       (const unsigned int *)cnmax, TauCoef{err_prod, err_sq, l1_prod, l1_sq}, b.tau, b.tau1, b.xw, rinit);
-    HIPCHK(hipGetLastError());
+    CHK(LAUNCH_TIMED(e, KID_PACK_SAMPLES, k_pack_samples_bf16, dim3((unsigned)p.nsb), dim3(PACK_THREADS), 0, ds->d_rows, ds->n, ds->d, d8, first, count,
+        b.xhi, pack_lo ? b.xlo : nullptr, cb->d_cnmax + (cb->cnmax_sel ^ 1), b.xrow, cnmax, TauCoef{err_prod, err_sq, l1_prod, l1_sq}, b.tau, b.tau1,
+        b.xw, rinit));
     cb->cnmax_sel ^= 1;
     cb->cnmax_clean = true;
   }
@@ -280,29 +273,25 @@ static int pf_level1(somhip_codebook *cb, int64_t count, const ScanPlan &p, cons
         int nwg = e->n_cus >= 8 ? e->n_cus / 8 * 8 : e->n_cus;
         const int64_t ntiles = (int64_t)gridw.x * gridw.y;
         if (ntiles < nwg) nwg = (int)ntiles;
-        hipLaunchKernelGGL(k_dist_mfma_bf16_l1r, dim3((unsigned)nwg), dim3(512), L1R_LDS_BYTES, e->stream, cb->v, p.d8, (const uint4 *)cb->d_chi,
-                           (const uint4 *)b.xhi, (const float *)cb->d_cn, p.bpad, b.wmin, l1_ring_gmin ? b.gmin1 : (uint32_t *)nullptr,
-                           (int)gridw.x, (int)gridw.y);
+        CHK(LAUNCH(e, k_dist_mfma_bf16_l1r, dim3((unsigned)nwg), dim3(512), L1R_LDS_BYTES, cb->v, p.d8, cb->d_chi, b.xhi, cb->d_cn, p.bpad, b.wmin,
+            l1_ring_gmin ? b.gmin1 : nullptr, (int)gridw.x, (int)gridw.y));
       } else
-        hipLaunchKernelGGL((k_dist_mfma_bf16_l1w16<4>), dim3(gridw.x * gridw.y), dim3(512), 0, e->stream, cb->v, p.d8, (const uint4 *)cb->d_chi,
-                           (const uint4 *)b.xhi, (const float *)cb->d_cn, p.bpad, b.wmin, (int)gridw.x, (int)gridw.y);
+        CHK(LAUNCH(e, (k_dist_mfma_bf16_l1w16<4>), dim3(gridw.x * gridw.y), dim3(512), 0, cb->v, p.d8, cb->d_chi, b.xhi, cb->d_cn, p.bpad, b.wmin,
+            (int)gridw.x, (int)gridw.y));
     } else {
       dim3 gridw((unsigned)((nsb + 7) / 8), (unsigned)((ng + 1) / 2));
-      hipLaunchKernelGGL((k_dist_mfma_bf16_l1<4>), gridw, dim3(256), 0, e->stream, cb->v, p.d8, (const uint4 *)cb->d_chi,
-                         (const uint4 *)b.xhi, (const float *)cb->d_cn, p.bpad, b.wmin);
+      CHK(LAUNCH(e, (k_dist_mfma_bf16_l1<4>), gridw, dim3(256), 0, cb->v, p.d8, cb->d_chi, b.xhi, cb->d_cn, p.bpad, b.wmin));
     }
   }
   LaunchTimer t(e, KID_DIST_L2);
   int64_t chunk;
   const dim3 sgrid = group_chunks(ng, p.bpad, 32, &chunk);
   if (p.kth == LVQ_K0)
-    hipLaunchKernelGGL(k_group_kth<LVQ_K0>, dim3((unsigned)(p.bpad / 32)), dim3(1024), 0, e->stream, ng, p.bpad,
-                       (const float *)b.wmin, b.gmin1);
+    CHK(LAUNCH(e, k_group_kth<LVQ_K0>, dim3((unsigned)(p.bpad / 32)), dim3(1024), 0, ng, p.bpad, b.wmin, b.gmin1));
   else if (!l1_ring_gmin)                            // (the ring kernel's epilogue has folded the minima into gmin1 itself)
-    hipLaunchKernelGGL(k_group_min, sgrid, dim3(256), 0, e->stream, ng, p.bpad, chunk, (const float *)b.wmin, b.gmin1);
+    CHK(LAUNCH(e, k_group_min, sgrid, dim3(256), 0, ng, p.bpad, chunk, b.wmin, b.gmin1));
   if (xbound)
-    hipLaunchKernelGGL(k_shard_bound, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, e->stream, count, (const uint32_t *)b.gmin1, (const float *)b.xw, xbound);
-  HIPCHK(hipGetLastError());
+    CHK(LAUNCH(e, k_shard_bound, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, count, b.gmin1, b.xw, xbound));
   return 0;
 }
 // level 2 (K2c): the three-product split for the groups level 1 keeps.  fused_gmin: the per-sample minimum behind it
@@ -315,35 +304,25 @@ static int pf_level2(somhip_codebook *cb, int64_t count, const ScanPlan &p, cons
   const int d8 = p.d8;
   int64_t chunk;
   const dim3 sgrid = group_chunks(ng, bpad, 32, &chunk);
-  {
-    LaunchTimer t(e, KID_L2_SELECT);
-    // (a workgroup: 1024 samples x a chunk of groups)
-    hipLaunchKernelGGL(k_l2_select, dim3((unsigned)((bpad + 1023) / 1024), sgrid.y), dim3(256), 0, e->stream, ng, count, bpad, chunk,
-                       (const float *)b.wmin, (const uint32_t *)b.gmin1, xbound ? (const float *)(b.xw + bpad) : (const float *)b.tau1,
-                       b.l2cnt, b.l2list, xbound ? b.wmin : (float *)nullptr, (const float *)xbound);
-  }
+  // (a workgroup: 1024 samples x a chunk of groups)
+  CHK(LAUNCH_TIMED(e, KID_L2_SELECT, k_l2_select, dim3((unsigned)((bpad + 1023) / 1024), sgrid.y), dim3(256), 0, ng, count, bpad, chunk, b.wmin, b.gmin1,
+      xbound ? b.xw + bpad : b.tau1, b.l2cnt, b.l2list, xbound ? b.wmin : nullptr, xbound));
   {
     LaunchTimer t(e, KID_DIST_L2);
     uint32_t *l2_gmin = fused_gmin ? b.gmin : nullptr;
     if (!p.l2_global) {
       const size_t a_bytes = sizeof(uint4) * 2 * (size_t)d8 * 64;
       CHK(raise_lds_limit(e, LDS_DIST_L2, (const void *)k_dist_l2_lds, 128 * 1024));
-      hipLaunchKernelGGL(k_dist_l2_lds, dim3((unsigned)ng, 4), dim3(64 * L2_WAVES), a_bytes, e->stream, cb->v, d8, (const uint4 *)cb->d_chi,
-                         (const uint4 *)cb->d_clo, (const uint4 *)b.xrow, (const float *)cb->d_cn,
-                         (const float *)b.tau, bpad, (const uint32_t *)b.l2cnt, (const uint16_t *)b.l2list, b.wmin,
-                         b.wmask, e->d_stats + STAT_L2_PAIRS, l2_gmin, b.l2out);
+      CHK(LAUNCH(e, k_dist_l2_lds, dim3((unsigned)ng, 4), dim3(64 * L2_WAVES), a_bytes, cb->v, d8, cb->d_chi, cb->d_clo, b.xrow, cb->d_cn, b.tau,
+          bpad, b.l2cnt, b.l2list, b.wmin, b.wmask, e->d_stats + STAT_L2_PAIRS, l2_gmin, b.l2out));
     } else
-      hipLaunchKernelGGL(k_dist_l2, dim3((unsigned)ng, 8), dim3(256), 0, e->stream, cb->v, d8, (const uint4 *)cb->d_chi,
-                         (const uint4 *)cb->d_clo, (const uint4 *)b.xhi, (const uint4 *)b.xlo, (const float *)cb->d_cn,
-                         (const float *)b.tau, bpad, (const uint32_t *)b.l2cnt, (const uint16_t *)b.l2list, b.wmin,
-                         b.wmask, e->d_stats + STAT_L2_PAIRS, (const uint4 *)b.xrow, l2_gmin, b.l2out);
+      CHK(LAUNCH(e, k_dist_l2, dim3((unsigned)ng, 8), dim3(256), 0, cb->v, d8, cb->d_chi, cb->d_clo, b.xhi, b.xlo, cb->d_cn, b.tau, bpad, b.l2cnt,
+          b.l2list, b.wmin, b.wmask, e->d_stats + STAT_L2_PAIRS, b.xrow, l2_gmin, b.l2out));
   }
-  HIPCHK(hipGetLastError());
   if (xbound) {
     LaunchTimer t(e, KID_RERANK_SELECT);
-    if (!fused_gmin) hipLaunchKernelGGL(k_group_min, sgrid, dim3(256), 0, e->stream, ng, bpad, chunk, (const float *)b.wmin, b.gmin);
-    hipLaunchKernelGGL(k_shard_bound, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, e->stream, count, (const uint32_t *)b.gmin, (const float *)(b.xw + 2 * bpad), xbound);
-    HIPCHK(hipGetLastError());
+    if (!fused_gmin) CHK(LAUNCH(e, k_group_min, sgrid, dim3(256), 0, ng, bpad, chunk, b.wmin, b.gmin));
+    CHK(LAUNCH(e, k_shard_bound, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, count, b.gmin, b.xw + 2 * bpad, xbound));
   }
   return 0;
 }
@@ -357,13 +336,10 @@ static int pf_one_level(somhip_codebook *cb, int64_t count, const ScanPlan &p, c
     const bool wide = (p.d8 % 2) == 0 && nsb >= 8;
     if (wide) grid = dim3((unsigned)((nsb + 7) / 8), (unsigned)((ng + 1) / 2));
     auto kern = wide ? k_dist_mfma_bf16_wide<2> : (p.d8 % 4) == 0 ? k_dist_mfma_bf16_dma<4, 2> : k_dist_mfma_bf16;
-    hipLaunchKernelGGL(kern, grid, dim3(256), 0, e->stream, cb->v, p.d8, (const uint4 *)cb->d_chi, (const uint4 *)cb->d_clo,
-                       (const uint4 *)b.xhi, (const uint4 *)b.xlo, (const float *)cb->d_cn, (const float *)b.tau, count, p.bpad, b.wmin, b.wmask);
-  } else
-    hipLaunchKernelGGL(k_dist_mfma, grid, dim3(256), 0, e->stream, cb->v, (const float4 *)b.xt, (const float *)cb->d_cn,
-                       (const float *)b.tau, count, p.bpad, b.wmin, b.wmask);
-  HIPCHK(hipGetLastError());
-  return 0;
+    return launch(e, "k_dist_mfma_bf16", kern, grid, dim3(256), 0, cb->v, p.d8, cb->d_chi, cb->d_clo, b.xhi, b.xlo, cb->d_cn, b.tau, count, p.bpad, b.wmin,
+                  b.wmask);
+  }
+  return LAUNCH(e, k_dist_mfma, grid, dim3(256), 0, cb->v, (const float4 *)b.xt, cb->d_cn, b.tau, count, p.bpad, b.wmin, b.wmask);
 }
 // the pre-filter of a whole search: prepare -> level 1 -> level 2, or prepare -> one level
 static int pf_filter(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count, const ScanPlan &p,
@@ -398,32 +374,20 @@ static int pf_rerank(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int
     const dim3 sgrid = group_chunks(ng, bpad, 128, &chunk);
     LaunchTimer t(e, KID_RERANK_SELECT);
     if (!gmin_ready)
-      hipLaunchKernelGGL(k_group_min, sgrid, dim3(256), 0, e->stream, ng, bpad, chunk, (const float *)b.wmin, b.gmin);
-    const float *win = xbound ? (const float *)(b.xw + 2 * bpad) : (const float *)b.tau;
+      CHK(LAUNCH(e, k_group_min, sgrid, dim3(256), 0, ng, bpad, chunk, b.wmin, b.gmin));
+    const float *win = xbound ? b.xw + 2 * bpad : b.tau;
     if (from_lists && !b.l2out) return fail("pf_rerank: no level-2 results in list order for this search");
     if (from_lists)
-      hipLaunchKernelGGL(k_rerank_select_lists, dim3((unsigned)ng, 4), dim3(256), 0, e->stream, cb->v, count, bpad,
-                         (const uint32_t *)b.l2cnt, (const uint16_t *)b.l2list, (const uint4 *)b.l2out, win,
-                         (const uint32_t *)b.gmin, b.gcount, pl.cap, pl.cap_col, pl.pairs, b.colcount, b.paircount, xbound);
+      CHK(LAUNCH(e, k_rerank_select_lists, dim3((unsigned)ng, 4), dim3(256), 0, cb->v, count, bpad, b.l2cnt, b.l2list, b.l2out, win, b.gmin, b.gcount,
+          pl.cap, pl.cap_col, pl.pairs, b.colcount, b.paircount, xbound));
     else
-      hipLaunchKernelGGL(k_rerank_select, sgrid, dim3(256), 0, e->stream, cb->v, count, bpad, chunk,
-                         (const float *)b.wmin, (const uint64_t *)b.wmask, win,
-                         (const uint32_t *)b.gmin, b.gcount, pl.cap, pl.cap_col, pl.pairs, b.colcount, b.paircount, e->d_stats, xbound);
+      CHK(LAUNCH(e, k_rerank_select, sgrid, dim3(256), 0, cb->v, count, bpad, chunk, b.wmin, b.wmask, win, b.gmin, b.gcount, pl.cap, pl.cap_col,
+          pl.pairs, b.colcount, b.paircount, e->d_stats, xbound));
   }
-  {
-    LaunchTimer t(e, KID_RERANK_PAIRS);
-    hipLaunchKernelGGL(k_rerank_pairs, dim3(4096), dim3(256), 0, e->stream, cb->v, ds->d_rows,
-                       ds->n, first, pl.cap, pl.cap_col, (int)pl.ncols, (const uint2 *)pl.pairs, (const uint32_t *)b.colcount,
-                       (const uint32_t *)b.paircount, d_keys, e->d_stats,
-                       p.bf16 && cb->prep_valid && cb->rowmajor_valid ? (const float *)cb->d_rowmajor : (const float *)nullptr);
-  }
-  LaunchTimer t(e, KID_RERANK);
-  hipLaunchKernelGGL(k_rerank, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, e->stream, cb->v,
-                     ds->d_rows, ds->n, first, count, bpad, (const float *)b.wmin,
-                     (const uint64_t *)b.wmask, (const float *)b.tau, (const uint32_t *)b.paircount, pl.cap, d_keys,
-                     e->d_stats);
-  HIPCHK(hipGetLastError());
-  return 0;
+  CHK(LAUNCH_TIMED(e, KID_RERANK_PAIRS, k_rerank_pairs, dim3(4096), dim3(256), 0, cb->v, ds->d_rows, ds->n, first, pl.cap, pl.cap_col, (int)pl.ncols,
+      pl.pairs, b.colcount, b.paircount, d_keys, e->d_stats, p.bf16 && cb->prep_valid && cb->rowmajor_valid ? cb->d_rowmajor : nullptr));
+  return LAUNCH_TIMED(e, KID_RERANK, k_rerank, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, cb->v, ds->d_rows, ds->n, first, count, bpad, b.wmin,
+                      b.wmask, b.tau, b.paircount, pl.cap, d_keys, e->d_stats);
 }
 // the direct scan (K1): packed sample tiles against every row group; keys (top-1) or per-block top-K lists in part
 template <int K>
@@ -432,28 +396,19 @@ static int scan_exact(somhip_codebook *cb, somhip_dataset *ds, int64_t first, in
   somhip_engine *e = cb->e;
   float4 *xt;
   CHK(scratch(e, SLOT_SAMPLES, (size_t)p.nsb * cb->v.d4 * SCAN_S, &xt));
-  {
-    LaunchTimer t(e, KID_PACK_SAMPLES);
-    hipLaunchKernelGGL(k_pack_samples<SCAN_S>, dim3((unsigned)p.nsb), dim3(256), 0, e->stream,
-                       ds->d_rows, ds->n, ds->d, cb->v.d4, first, count, xt);
-  }
-  HIPCHK(hipGetLastError());
-  LaunchTimer t(e, KID_SCAN_EXACT);
+  CHK(LAUNCH_TIMED(e, KID_PACK_SAMPLES, k_pack_samples<SCAN_S>, dim3((unsigned)p.nsb), dim3(256), 0, ds->d_rows, ds->n, ds->d, cb->v.d4, first, count,
+      xt));
   dim3 grid((unsigned)p.nsb, (unsigned)((cb->v.ngroups + 3) / 4));
-  hipLaunchKernelGGL((k_scan_exact<SCAN_S, 1, K>), grid, dim3(256), 0, e->stream, cb->v,
-                     (const float4 *)xt, count, tie_knn, keys, part);
-  HIPCHK(hipGetLastError());
-  return 0;
+  return LAUNCH_TIMED(e, KID_SCAN_EXACT, (k_scan_exact<SCAN_S, 1, K>), grid, dim3(256), 0, cb->v, xt, count, tie_knn, keys, part);
 }
-// masked samples (K1m / K1mk), one launch column each: launch(offset, first sample, columns) per 32768 (grid.y limit)
+// masked samples (K1m / K1mk), one launch column each: column(offset, first sample, columns), 0 or an error, per 32768 (grid.y limit)
 template <class Launch>
-static int masked_columns(somhip_engine *e, const somhip_dataset *ds, int64_t first, int64_t count, Launch launch) {
+static int masked_columns(somhip_engine *e, const somhip_dataset *ds, int64_t first, int64_t count, Launch column) {
   for (int64_t off = 0; off < count; off += 32768) {
     const int64_t c = std::min<int64_t>(32768, count - off);
     LaunchTimer t(e, KID_SCAN_MASKED);
-    launch(off, (first + off) % ds->n, c);
+    CHK(column(off, (first + off) % ds->n, c));
   }
-  HIPCHK(hipGetLastError());
   return 0;
 }
 // keys[count] <- exact nearest row per sample, FIRST tie rule, local shard
@@ -465,8 +420,8 @@ static int scan_keys_top1(somhip_codebook *cb, somhip_dataset *ds, int64_t first
     HIPCHK(hipMemsetAsync(d_keys, 0xFF, sizeof(uint64_t) * (size_t)count, e->stream));   // (else pf_prepare presets them)
   if (p.route == ROUTE_MASKED)
     return masked_columns(e, ds, first, count, [&](int64_t off, int64_t f, int64_t c) {
-      hipLaunchKernelGGL(k_scan_masked, dim3((unsigned)((cb->v.ngroups + 3) / 4), (unsigned)c), dim3(256), 0, e->stream, cb->v,
-                         ds->d_rows, ds->d_mask, ds->n, f, c, 0, d_keys + off);
+      return LAUNCH(e, k_scan_masked, dim3((unsigned)((cb->v.ngroups + 3) / 4), (unsigned)c), dim3(256), 0, cb->v, ds->d_rows, ds->d_mask, ds->n, f, c,
+                    0, d_keys + off);
     });
   e->samples_searched += (uint64_t)count;
   if (p.route == ROUTE_DIRECT) return scan_exact<1>(cb, ds, first, count, p, 0, d_keys, (uint64_t *)nullptr);
@@ -500,16 +455,12 @@ static int scan_keys_topk(somhip_codebook *cb, somhip_dataset *ds, int64_t first
     CHK(scratch(e, SLOT_PARTIAL, (size_t)count * nblk * K, &part));
     if (p.route == ROUTE_MASKED)
       CHK(masked_columns(e, ds, first, count, [&](int64_t off, int64_t f, int64_t c) {
-        hipLaunchKernelGGL(k_scan_masked_topk<K>, dim3((unsigned)nblk, (unsigned)c), dim3(256), 0, e->stream, cb->v, ds->d_rows,
-                           (const uint8_t *)ds->d_mask, ds->n, f, tie_knn, part + (size_t)off * nblk * K);
+        return LAUNCH(e, k_scan_masked_topk<K>, dim3((unsigned)nblk, (unsigned)c), dim3(256), 0, cb->v, ds->d_rows, ds->d_mask, ds->n, f, tie_knn,
+                      part + (size_t)off * nblk * K);
       }));
     else
       CHK(scan_exact<K>(cb, ds, first, count, p, tie_knn, (uint64_t *)nullptr, part));
-    LaunchTimer t(e, KID_MERGE_TOPK);
-    hipLaunchKernelGGL(k_merge_topk<K>, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, e->stream,
-                       (const uint64_t *)part, nblk, count, d_keys);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return LAUNCH_TIMED(e, KID_MERGE_TOPK, k_merge_topk<K>, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, part, nblk, count, d_keys);
   }
   PrefilterBufs b;
   CHK(pf_filter(cb, ds, first, count, p, &b, nullptr, false, false));
@@ -530,27 +481,21 @@ static int scan_keys_topk(somhip_codebook *cb, somhip_dataset *ds, int64_t first
                              ? (uint32_t)count : (uint32_t)std::max<uint64_t>(64, (8ull << 20) / (uint64_t)cb->v.ngroups);
   TopkGroupBufs g{};
   if (by_group) CHK(bind_topk_groups(e, cb->v.ngroups, cap_g, cap, &g));
-  hipLaunchKernelGGL(k_topk_select<K>, dim3((unsigned)((count + TOPK_NB - 1) / TOPK_NB)), dim3(1024), 0, e->stream, cb->v, count, p.bpad,
-                     (const float *)b.wmin, (const float *)b.tau, cap, dpairs, dspan, dcounter, g.gcnt, g.glist, cap_g);
+  CHK(LAUNCH(e, k_topk_select<K>, dim3((unsigned)((count + TOPK_NB - 1) / TOPK_NB)), dim3(1024), 0, cb->v, count, p.bpad, b.wmin, b.tau, cap, dpairs,
+      dspan, dcounter, g.gcnt, g.glist, cap_g));
   if (by_group) {
-    hipLaunchKernelGGL(k_topk_worklist<4>, dim3((unsigned)std::min<int64_t>((cb->v.ngroups + 255) / 256, 256)), dim3(256), 0, e->stream,
-                       cb->v.ngroups, (const uint32_t *)g.gcnt, cap_g, (const uint32_t *)dcounter, g.wcount, g.work, cap);
-    hipLaunchKernelGGL(k_topk_pairs_bygroup<K>, dim3(8192), dim3(64), 0, e->stream, cb->v, ds->d_rows, ds->n,
-                       first, tie_knn, (const uint32_t *)g.gcnt, (const uint2 *)g.glist, cap_g, (const uint32_t *)dcounter,
-                       (const uint32_t *)g.wcount, (const uint2 *)g.work, cap, dpart);
+    CHK(LAUNCH(e, k_topk_worklist<4>, dim3((unsigned)std::min<int64_t>((cb->v.ngroups + 255) / 256, 256)), dim3(256), 0, cb->v.ngroups, g.gcnt, cap_g,
+        dcounter, g.wcount, g.work, cap));
+    CHK(LAUNCH(e, k_topk_pairs_bygroup<K>, dim3(8192), dim3(64), 0, cb->v, ds->d_rows, ds->n, first, tie_knn, g.gcnt, g.glist, cap_g, dcounter,
+        g.wcount, g.work, cap, dpart));
   }
   else
-    hipLaunchKernelGGL(k_topk_pairs<K>, dim3(1024), dim3(256), 0, e->stream, cb->v, ds->d_rows, ds->n, first, tie_knn,
-                       (const uint2 *)dpairs, (const uint32_t *)dcounter, dpart);
-  hipLaunchKernelGGL(k_topk_merge<K>, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, e->stream, count,
-                     (const TopkSpan *)dspan, (const uint64_t *)dpart, (const uint32_t *)dcounter, d_keys,
-                     e->d_stats + STAT_TOPK_PAIRS);
+    CHK(LAUNCH(e, k_topk_pairs<K>, dim3(1024), dim3(256), 0, cb->v, ds->d_rows, ds->n, first, tie_knn, dpairs, dcounter, dpart));
+  CHK(LAUNCH(e, k_topk_merge<K>, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, count, dspan, dpart, dcounter, d_keys,
+      e->d_stats + STAT_TOPK_PAIRS));
   // list full (dcounter[1] != 0, seen on the device: no host round trip): every sample through the one-wave kernel
-  hipLaunchKernelGGL(k_rerank_topk<K>, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, e->stream, cb->v, ds->d_rows,
-                     ds->n, first, count, p.bpad, (const float *)b.wmin, (const float *)b.tau, tie_knn, d_keys,
-                     (const uint32_t *)(dcounter + 1));
-  HIPCHK(hipGetLastError());
-  return 0;
+  return LAUNCH(e, k_rerank_topk<K>, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, cb->v, ds->d_rows, ds->n, first, count, p.bpad, b.wmin, b.tau,
+                tie_knn, d_keys, dcounter + 1);
 }
 
 // f(integral_constant<int, K>) for the top-K width K (1, 2, 4, 8) holding knn (1..8) neighbours; who: knn must be K
@@ -580,9 +525,8 @@ extern "C" int somhip_debug_prefilter(somhip_codebook *cb, somhip_dataset *ds, i
   HIPCHK(hipSetDevice(e->device));
   PrefilterBufs b;
   CHK(pf_filter(cb, ds, first, count, p, &b, nullptr, false, false));
-  HIPCHK(hipMemcpyAsync(wmin, b.wmin, sizeof(float) * (size_t)cb->v.ngroups * p.bpad, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipMemcpyAsync(tau, b.tau, sizeof(float) * (size_t)count, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
+  CHK(to_host(e, wmin, b.wmin, (size_t)cb->v.ngroups * p.bpad));
+  CHK(to_host_sync(e, tau, b.tau, (size_t)count));
   if (bpad) *bpad = p.bpad;
   return 0;
 } ABI_CATCH(somhip_debug_prefilter)
@@ -608,9 +552,8 @@ extern "C" int somhip_debug_level1(somhip_codebook *cb, somhip_dataset *ds, int6
   CHK(bind_prefilter(cb, p, false, &b));
   CHK(pf_prepare(cb, ds, first, count, p, b, nullptr, false));
   CHK(pf_level1(cb, count, p, b, nullptr));
-  HIPCHK(hipMemcpyAsync(wmin, b.wmin, sizeof(float) * (size_t)cb->v.ngroups * p.bpad, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipMemcpyAsync(gmin1, b.gmin1, sizeof(uint32_t) * (size_t)p.bpad, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
+  CHK(to_host(e, wmin, b.wmin, (size_t)cb->v.ngroups * p.bpad));
+  CHK(to_host_sync(e, gmin1, b.gmin1, (size_t)p.bpad));
   if (bpad) *bpad = p.bpad;
   return 0;
 } ABI_CATCH(somhip_debug_level1)
@@ -633,16 +576,16 @@ extern "C" int somhip_debug_prepared(somhip_codebook *cb, somhip_dataset *ds, in
   CHK(pf_prepare(cb, ds, first, count, p, b, nullptr, false));
   const size_t ctile = sizeof(uint4) * (size_t)cb->v.ngroups * p.d8 * WAVE, xtile = sizeof(uint4) * (size_t)p.nsb * p.d8 * 32;
   const bool has_lo = !two || p.l2_global;
-  auto get = [&](void *dst, const void *src, size_t bytes) { return dst && src ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, e->stream) : hipSuccess; };
-  HIPCHK(get(chi, cb->d_chi, ctile));
-  HIPCHK(get(clo, cb->d_clo, ctile));
-  HIPCHK(get(cn, cb->d_cn, sizeof(float) * (size_t)cb->v.ngroups * WAVE));
-  HIPCHK(get(rowmajor, cb->rowmajor_valid ? cb->d_rowmajor : nullptr, sizeof(float) * (size_t)cb->v.ngroups * WAVE * cb->v.d));
-  HIPCHK(get(xhi, b.xhi, xtile));
-  HIPCHK(get(xlo, has_lo ? b.xlo : nullptr, xtile));
-  HIPCHK(get(xrow, two ? b.xrow : nullptr, 2 * xtile));
-  HIPCHK(get(tau, b.tau, sizeof(float) * (size_t)count));
-  HIPCHK(get(tau1, two ? b.tau1 : nullptr, sizeof(float) * (size_t)count));
+  auto get = [&](void *dst, const void *src, size_t bytes) { return dst && src ? to_host(e, (uint8_t *)dst, (const uint8_t *)src, bytes) : 0; };
+  CHK(get(chi, cb->d_chi, ctile));
+  CHK(get(clo, cb->d_clo, ctile));
+  CHK(get(cn, cb->d_cn, sizeof(float) * (size_t)cb->v.ngroups * WAVE));
+  CHK(get(rowmajor, cb->rowmajor_valid ? cb->d_rowmajor : nullptr, sizeof(float) * (size_t)cb->v.ngroups * WAVE * cb->v.d));
+  CHK(get(xhi, b.xhi, xtile));
+  CHK(get(xlo, has_lo ? b.xlo : nullptr, xtile));
+  CHK(get(xrow, two ? b.xrow : nullptr, 2 * xtile));
+  CHK(get(tau, b.tau, sizeof(float) * (size_t)count));
+  CHK(get(tau1, two ? b.tau1 : nullptr, sizeof(float) * (size_t)count));
   HIPCHK(hipStreamSynchronize(e->stream));
   info[0] = cb->rowmajor_valid; info[1] = has_lo; info[2] = two; info[3] = p.d8;
   return 0;
@@ -669,20 +612,19 @@ extern "C" int somhip_debug_rerank_pairs(somhip_codebook *cb, somhip_dataset *ds
   const size_t cells = (size_t)cb->v.ngroups * p.bpad;
   RerankPairs pl;                                  // the list pf_rerank filled
   CHK(bind_rerank_pairs(e, p.bpad, &pl));
-  HIPCHK(hipMemcpyAsync(wmin, b.wmin, sizeof(float) * cells, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipMemcpyAsync(wmask, b.wmask, sizeof(uint64_t) * cells, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipMemcpyAsync(gmin, b.gmin, sizeof(uint32_t) * (size_t)p.bpad, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipMemcpyAsync(tau, b.tau, sizeof(float) * (size_t)count, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipMemcpyAsync(colcount, b.colcount, sizeof(uint32_t) * 4 * (size_t)pl.ncols, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipMemcpyAsync(overflow, b.paircount, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipMemcpyAsync(keys, dk, sizeof(uint64_t) * (size_t)count, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
+  CHK(to_host(e, wmin, b.wmin, cells));
+  CHK(to_host(e, wmask, b.wmask, cells));
+  CHK(to_host(e, gmin, b.gmin, (size_t)p.bpad));
+  CHK(to_host(e, tau, b.tau, (size_t)count));
+  CHK(to_host(e, colcount, b.colcount, 4 * (size_t)pl.ncols));
+  CHK(to_host(e, overflow, b.paircount, 1));
+  CHK(to_host_sync(e, keys, dk, (size_t)count));
   // the segments' filled parts, one after another
   int64_t total = 0;
   for (uint32_t c = 0; c < pl.ncols; c++) {
     const int64_t n = std::min<uint32_t>(colcount[c], pl.cap_col);
     if (total + n > pairs_cap) return fail("somhip_debug_rerank_pairs: %lld pairs and more, room for %lld", (long long)(total + n), (long long)pairs_cap);
-    if (n) HIPCHK(hipMemcpyAsync(pairs + 2 * total, pl.pairs + (size_t)c * pl.cap_col, sizeof(uint2) * (size_t)n, hipMemcpyDeviceToHost, e->stream));
+    if (n) CHK(to_host(e, pairs + 2 * total, reinterpret_cast<const uint32_t *>(pl.pairs + (size_t)c * pl.cap_col), 2 * (size_t)n));
     total += n;
   }
   HIPCHK(hipStreamSynchronize(e->stream));
@@ -711,8 +653,7 @@ extern "C" int somhip_batch_winner_keys(somhip_codebook *cb, somhip_dataset *ds,
   bool nonneg = false;
   CHK(scan_keys_top1(cb, ds, first, count, dev_keys, &nonneg));
   if (!nonneg)
-    hipLaunchKernelGGL(k_clamp_keys, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, cb->e->stream, dev_keys, count);
-  HIPCHK(hipGetLastError());
+    CHK(LAUNCH(cb->e, k_clamp_keys, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, dev_keys, count));
   return 0;
 } ABI_CATCH(somhip_batch_winner_keys)
 
@@ -838,29 +779,16 @@ static int knn_chunk_keys(somhip_codebook *cb, somhip_dataset *ds, int64_t first
     const int64_t c = std::min(CH, count - off);
     const int64_t f = (first + off) % ds->n;
     if (ds->d_mask) {
-      LaunchTimer t(e, KID_KNN_DIST);
-      hipLaunchKernelGGL(k_knn_dist_masked, dim3(nblk, (unsigned)c), dim3(256), 0, e->stream, cb->v, ds->d_rows,
-                         (const uint8_t *)ds->d_mask, ds->n, f, ld, dist);
+      CHK(LAUNCH_TIMED(e, KID_KNN_DIST, k_knn_dist_masked, dim3(nblk, (unsigned)c), dim3(256), 0, cb->v, ds->d_rows, ds->d_mask, ds->n, f, ld, dist));
     } else {
       const int64_t nsb = (c + SCAN_S - 1) / SCAN_S;
       float4 *xt;
       CHK(scratch(e, SLOT_SAMPLES, (size_t)nsb * cb->v.d4 * SCAN_S, &xt));
-      {
-        LaunchTimer t(e, KID_PACK_SAMPLES);
-        hipLaunchKernelGGL(k_pack_samples<SCAN_S>, dim3((unsigned)nsb), dim3(256), 0, e->stream,
-                           ds->d_rows, ds->n, ds->d, cb->v.d4, f, c, xt);
-      }
-      LaunchTimer t(e, KID_KNN_DIST);
-      hipLaunchKernelGGL(k_knn_dist<SCAN_S>, dim3((unsigned)nsb, nblk), dim3(256), 0, e->stream, cb->v,
-                         (const float4 *)xt, c, ld, dist);
+      CHK(LAUNCH_TIMED(e, KID_PACK_SAMPLES, k_pack_samples<SCAN_S>, dim3((unsigned)nsb), dim3(256), 0, ds->d_rows, ds->n, ds->d, cb->v.d4, f, c, xt));
+      CHK(LAUNCH_TIMED(e, KID_KNN_DIST, k_knn_dist<SCAN_S>, dim3((unsigned)nsb, nblk), dim3(256), 0, cb->v, xt, c, ld, dist));
       e->samples_searched += (uint64_t)c;
     }
-    HIPCHK(hipGetLastError());
-    {
-      LaunchTimer t(e, KID_KNN_SELECT);
-      hipLaunchKernelGGL(k_knn_select, dim3((unsigned)c), dim3(KNN_THREADS), 0, e->stream, cb->v, (const float *)dist, ld, knn, dk);
-    }
-    HIPCHK(hipGetLastError());
+    CHK(LAUNCH_TIMED(e, KID_KNN_SELECT, k_knn_select, dim3((unsigned)c), dim3(KNN_THREADS), 0, cb->v, dist, ld, knn, dk));
     CHK(use(off, f, c, dk, knn));
   }
   return 0;
@@ -894,11 +822,9 @@ extern "C" int somhip_find_winners(somhip_codebook *cb, somhip_dataset *ds, int6
   std::vector<uint64_t> hk;
   return knn_chunk_keys(cb, ds, first, count, knn, [&](int64_t off, int64_t f, int64_t c, const uint64_t *dk, int stride) {
     if (hk.empty()) hk.resize((size_t)c * stride);                      // (the first chunk is the longest)
-    HIPCHK(hipMemcpyAsync(hk.data(), dk, sizeof(uint64_t) * (size_t)c * stride, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
+    CHK(to_host_sync(e, hk.data(), dk, (size_t)c * stride));
     for (int64_t i = 0; i < c; i++) {
-      const int64_t r = (f + i) % ds->n;
-      const bool empty = !ds->all_masked.empty() && ds->all_masked[(size_t)r];
+      const bool empty = sample_is_empty(ds, (f + i) % ds->n);
       decode_sample(hk.data() + (size_t)i * stride, knn, knn_rule, empty, index + (off + i) * knn, diff + (off + i) * knn,
                     ret ? ret + off + i : nullptr);
     }
@@ -915,7 +841,7 @@ extern "C" int somhip_knn_vote(somhip_codebook *cb, somhip_dataset *ds, int64_t 
   if (knn < 1 || knn > SOMHIP_KNN_MAX) return fail("somhip_knn_vote: knn %d not in 1..%d", knn, SOMHIP_KNN_MAX);
   if (!label) return fail("somhip_knn_vote: null output");
   if (!cb->d_labels) return fail("somhip_knn_vote: codebook has no labels");
-  if (cb->v.row_offset != 0 || cb->n_global != cb->v.n)
+  if (is_shard(cb))
     return fail("somhip_knn_vote: sharded codebook not supported (a shard does not hold the other shards' labels)");
   if (first < 0) return fail("somhip_knn_vote: first row %lld < 0", (long long)first);
   if (count <= 0) return 0;
@@ -929,19 +855,13 @@ extern "C" int somhip_knn_vote(somhip_codebook *cb, somhip_dataset *ds, int64_t 
   return knn_chunk_keys(cb, ds, first, count, knn, [&](int64_t off, int64_t f, int64_t c, const uint64_t *dk, int stride) {
     int4 *dv;
     CHK(scratch(e, SLOT_CALL_B, (size_t)c, &dv));
-    {
-      LaunchTimer t(e, KID_KNN_VOTE);
-      hipLaunchKernelGGL(k_knn_vote, dim3((unsigned)((c + VOTE_SAMPLES - 1) / VOTE_SAMPLES)), dim3(VOTE_SAMPLES * WAVE), 0,
-                         e->stream, dk, stride, knn, knn >= 2 ? 1 : 0, (const int32_t *)cb->d_labels, cb->v.row_offset, cb->v.n,
-                         (const int32_t *)ds->d_labels, f, ds->n, c, dv);
-    }
-    HIPCHK(hipGetLastError());
+    CHK(LAUNCH_TIMED(e, KID_KNN_VOTE, k_knn_vote, dim3((unsigned)((c + VOTE_SAMPLES - 1) / VOTE_SAMPLES)), dim3(VOTE_SAMPLES * WAVE), 0, dk, stride,
+        knn, knn >= 2 ? 1 : 0, cb->d_labels, cb->v.row_offset, cb->v.n, ds->d_labels, f, ds->n, c, dv));
     if (hv.empty()) hv.resize(4 * (size_t)c);                           // (the first chunk is the longest)
-    HIPCHK(hipMemcpyAsync(hv.data(), dv, sizeof(int4) * (size_t)c, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
+    CHK(to_host_sync(e, hv.data(), reinterpret_cast<const int32_t *>(dv), 4 * (size_t)c));
     for (int64_t i = 0; i < c; i++) {
       const int32_t *v = hv.data() + 4 * (size_t)i;
-      const bool empty = !ds->all_masked.empty() && ds->all_masked[(size_t)((f + i) % ds->n)];
+      const bool empty = sample_is_empty(ds, (f + i) % ds->n);
       label[off + i] = empty ? -1 : v[0];
       if (freq) freq[off + i] = empty ? 0 : v[1];
       if (own) own[off + i] = ds->d_labels ? (empty ? 0 : v[2]) : -1;
@@ -965,41 +885,33 @@ extern "C" int somhip_knn_vote_timing(somhip_engine *e, int64_t *launches, doubl
 // unmasked entries, then the upper triangle (j >= i) of sum_r (x_ri - mean_i)(x_rj - mean_j); every
 // element accumulated over the rows in file order, in fp32, like the reference.
 extern "C" int somhip_column_sums(somhip_dataset *ds, float *sum, int64_t *count) try {
-  if (!ds || !sum || !count) return fail("somhip_column_sums: null argument");
-  if (!ds->e) return fail("somhip_column_sums: the engine of this data set was destroyed");
+  CHK(check_dataset(ds, sum && count, "somhip_column_sums"));
   somhip_engine *e = ds->e;
   HIPCHK(hipSetDevice(e->device));
   float *dsum; unsigned long long *dcnt;
   CHK(scratch(e, SLOT_CALL_A, (size_t)ds->d, &dsum));
   CHK(scratch(e, SLOT_CALL_B, (size_t)ds->d, &dcnt));
-  hipLaunchKernelGGL(k_column_sums, dim3((unsigned)((ds->d + 255) / 256)), dim3(256), 0, e->stream, ds->d_rows,
-                     (const uint8_t *)ds->d_mask, ds->n, ds->d, dsum, dcnt);
-  HIPCHK(hipGetLastError());
+  CHK(LAUNCH(e, k_column_sums, dim3((unsigned)((ds->d + 255) / 256)), dim3(256), 0, ds->d_rows, ds->d_mask, ds->n, ds->d, dsum, dcnt));
   std::vector<unsigned long long> hc((size_t)ds->d);
-  HIPCHK(hipMemcpyAsync(sum, dsum, sizeof(float) * (size_t)ds->d, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipMemcpyAsync(hc.data(), dcnt, sizeof(unsigned long long) * (size_t)ds->d, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
+  CHK(to_host(e, sum, dsum, (size_t)ds->d));
+  CHK(to_host_sync(e, hc.data(), dcnt, (size_t)ds->d));
   for (int i = 0; i < ds->d; i++) count[i] = (int64_t)hc[(size_t)i];
   return 0;
 } ABI_CATCH(somhip_column_sums)
 
 extern "C" int somhip_centered_products(somhip_dataset *ds, const float *mean, float *r) try {
-  if (!ds || !mean || !r) return fail("somhip_centered_products: null argument");
-  if (!ds->e) return fail("somhip_centered_products: the engine of this data set was destroyed");
+  CHK(check_dataset(ds, mean && r, "somhip_centered_products"));
   somhip_engine *e = ds->e;
   HIPCHK(hipSetDevice(e->device));
   const size_t dd = (size_t)ds->d * ds->d;
   float *dmean, *dr;
   CHK(scratch(e, SLOT_CALL_A, (size_t)ds->d, &dmean));
   CHK(scratch(e, SLOT_CALL_B, dd, &dr));
-  HIPCHK(hipMemcpyAsync(dmean, mean, sizeof(float) * (size_t)ds->d, hipMemcpyHostToDevice, e->stream));
+  CHK(to_device(e, dmean, mean, (size_t)ds->d));
   HIPCHK(hipMemsetAsync(dr, 0, sizeof(float) * dd, e->stream));
   const unsigned nb = (unsigned)((ds->d + 15) / 16);
-  hipLaunchKernelGGL(k_centered_products, dim3(nb, nb), dim3(256), 0, e->stream, ds->d_rows,
-                     (const uint8_t *)ds->d_mask, ds->n, ds->d, (const float *)dmean, dr);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(r, dr, sizeof(float) * dd, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
+  CHK(LAUNCH(e, k_centered_products, dim3(nb, nb), dim3(256), 0, ds->d_rows, ds->d_mask, ds->n, ds->d, dmean, dr));
+  CHK(to_host_sync(e, r, dr, dd));
   return 0;
 } ABI_CATCH(somhip_centered_products)
 
@@ -1007,8 +919,7 @@ extern "C" int somhip_centered_products(somhip_dataset *ds, const float *mean, f
 // per component.  The reference's seeds (FLT_MIN for the maximum, FLT_MAX for the minimum, :108-111) are the
 // caller's business; components without data come back as lo = +FLT_MAX, hi = -FLT_MAX, count 0.
 extern "C" int somhip_column_minmax(somhip_dataset *ds, float *lo, float *hi, int64_t *count) try {
-  if (!ds || !lo || !hi) return fail("somhip_column_minmax: null argument");
-  if (!ds->e) return fail("somhip_column_minmax: the engine of this data set was destroyed");
+  CHK(check_dataset(ds, lo && hi, "somhip_column_minmax"));
   somhip_engine *e = ds->e;
   HIPCHK(hipSetDevice(e->device));
   uint32_t *dmin; unsigned long long *dcnt;
@@ -1020,14 +931,12 @@ extern "C" int somhip_column_minmax(somhip_dataset *ds, float *lo, float *hi, in
   HIPCHK(hipMemsetAsync(dcnt, 0, sizeof(unsigned long long) * (size_t)ds->d, e->stream));
   const int64_t nblk = std::max<int64_t>(1, std::min<int64_t>(2048, (ds->n + 255) / 256));
   const int64_t per = (ds->n + nblk - 1) / nblk;
-  hipLaunchKernelGGL(k_column_minmax, dim3((unsigned)((ds->d + 255) / 256), (unsigned)((ds->n + per - 1) / per)), dim3(256), 0,
-                     e->stream, ds->d_rows, (const uint8_t *)ds->d_mask, ds->n, ds->d, per, dmin, dmax, dcnt);
-  HIPCHK(hipGetLastError());
+  CHK(LAUNCH(e, k_column_minmax, dim3((unsigned)((ds->d + 255) / 256), (unsigned)((ds->n + per - 1) / per)), dim3(256), 0, ds->d_rows, ds->d_mask,
+      ds->n, ds->d, per, dmin, dmax, dcnt));
   std::vector<uint32_t> hm(2 * (size_t)ds->d);
   std::vector<unsigned long long> hc((size_t)ds->d);
-  HIPCHK(hipMemcpyAsync(hm.data(), dmin, sizeof(uint32_t) * 2 * (size_t)ds->d, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipMemcpyAsync(hc.data(), dcnt, sizeof(unsigned long long) * (size_t)ds->d, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
+  CHK(to_host(e, hm.data(), dmin, 2 * (size_t)ds->d));
+  CHK(to_host_sync(e, hc.data(), dcnt, (size_t)ds->d));
   auto back = [](uint32_t o) { uint32_t b = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o; float f; memcpy(&f, &b, 4); return f; };
   for (int i = 0; i < ds->d; i++) {
     if (hc[(size_t)i]) { lo[i] = back(hm[(size_t)i]); hi[i] = back(hm[(size_t)ds->d + i]); }
@@ -1044,7 +953,7 @@ extern "C" int somhip_qerror2(somhip_codebook *cb, somhip_dataset *ds, float rad
   CHK(check_pair(cb, ds, "somhip_qerror2"));
   if (!out) return fail("somhip_qerror2: null output");
   if (cb->v.topol != SOMHIP_TOPOL_HEXA && cb->v.topol != SOMHIP_TOPOL_RECT) return fail("somhip_qerror2: can't set SOM parameters");
-  if (cb->v.row_offset != 0 || cb->n_global != cb->v.n) return fail("somhip_qerror2: sharded codebook not supported");
+  if (is_shard(cb)) return fail("somhip_qerror2: sharded codebook not supported");
   if (count <= 0) return 0;
   somhip_engine *e = cb->e;
   HIPCHK(hipSetDevice(e->device));
@@ -1061,16 +970,13 @@ extern "C" int somhip_qerror2(somhip_codebook *cb, somhip_dataset *ds, float rad
     const int64_t c = std::min(CH, count - off);
     const int64_t f = (first + off) % ds->n;
     CHK(scan_keys_top1(cb, ds, f, c, dk));
-    hipLaunchKernelGGL(gauss ? k_qerror2<true> : k_qerror2<false>, dim3((unsigned)c), dim3(256), dyn, e->stream, cb->v, cb->ydim,
-                       ds->d_rows, ds->d_mask, ds->n, f, (const uint64_t *)dk, radius, thresh, ireach, dq);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out + off, dq, sizeof(float) * (size_t)c, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
+    CHK(launch(e, "k_qerror2", gauss ? k_qerror2<true> : k_qerror2<false>, dim3((unsigned)c), dim3(256), dyn, cb->v, cb->ydim, ds->d_rows, ds->d_mask,
+               ds->n, f, dk, radius, thresh, ireach, dq));
+    CHK(to_host_sync(e, out + off, dq, (size_t)c));
     // a sample with every component masked has no winner, whatever its key says (every distance is an empty sum, 0):
     // the kernel's sum over zero distances is 0 too, except where the rate itself is NaN (gaussian, radius 0)
     for (int64_t i = 0; i < c; i++) {
-      const int64_t r = (f + i) % ds->n;
-      const bool empty = !ds->all_masked.empty() && ds->all_masked[(size_t)r];
+      const bool empty = sample_is_empty(ds, (f + i) % ds->n);
       if (empty) out[off + i] = 0.0f;
       if (ret) ret[off + i] = empty ? 0 : 1;
     }

@@ -47,7 +47,7 @@ static int som_scalars(const MapLattice &lat, const somhip_dataset *ds, const so
     // apart (som_rout.c:451), rect rows 1 apart; +1 keeps it conservative
     double reach = gauss ? 1e9 : (trad > 0.0f ? (double)trad / (lat.topol == SOMHIP_TOPOL_RECT ? 1.0 : 0.8660254037844386) + 1.0 : 1.0);
     s.reach = reach > 1e6 ? 1000000 : (int32_t)reach;
-    if (!ds->all_masked.empty() && ds->all_masked[(size_t)r]) s.reach = -1;
+    if (sample_is_empty(ds, r)) s.reach = -1;
     if (p->use_fixed && !ds->fixed_xy.empty() && ds->fixed_xy[(size_t)(2 * r)] >= 0) {
       int fx = ds->fixed_xy[(size_t)(2 * r)], fy = ds->fixed_xy[(size_t)(2 * r + 1)];
       // the reference hands xfix / yfix to the neighbourhood function as they are (som_rout.c:628-632), also when
@@ -62,16 +62,15 @@ static int som_scalars(const MapLattice &lat, const somhip_dataset *ds, const so
 }
 
 constexpr int ONLINE_U = 8;    // chunks (KiB) per register buffer; two buffers per wave
-static void launch_online_any(somhip_engine *e, const somhip_codebook *cb, const somhip_dataset *ds, bool G, bool M,
+static int launch_online_any(somhip_engine *e, const somhip_codebook *cb, const somhip_dataset *ds, bool G, bool M,
                               const int64_t *prev_row, const int64_t *cur_row, int has_prev, int has_cur, const uint64_t *prev_slot,
                               uint64_t *cur_slot, const StepScalars *prev_sc, const StepScalars *cur_sc) {
-  LaunchTimer t(e, KID_SOM_ONLINE_STEP);
   // chunks (KiB) per register buffer: a wave is alone on its SIMD here (one wave per 64 rows: 1024 waves on 1024 SIMDs at
   // 65536 rows), so registers are free and what bounds the kernel is how many bytes it keeps in flight
-  (void)with_value<1, 0>(G, [&](auto g) { return with_value<1, 0>(M, [&](auto m) {    // (two bools: always found)
-    hipLaunchKernelGGL((k_som_online_step<decltype(g)::value != 0, decltype(m)::value != 0, ONLINE_U>),
-                       dim3((unsigned)((cb->v.ngroups + 3) / 4)), dim3(256), 0, e->stream, cb->v, ds->d_rows,
-                       (const uint8_t *)ds->d_mask, prev_row, cur_row, has_prev, has_cur, prev_slot, cur_slot, prev_sc, cur_sc); return 0;
+  return with_value<1, 0>(G, [&](auto g) { return with_value<1, 0>(M, [&](auto m) {
+    constexpr bool GG = decltype(g)::value != 0, MM = decltype(m)::value != 0;
+    return LAUNCH_TIMED(e, KID_SOM_ONLINE_STEP, (k_som_online_step<GG, MM, ONLINE_U>), dim3((unsigned)((cb->v.ngroups + 3) / 4)), dim3(256), 0, cb->v,
+                        ds->d_rows, ds->d_mask, prev_row, cur_row, has_prev, has_cur, prev_slot, cur_slot, prev_sc, cur_sc);
   }); });
 }
 // the winner trace of iterations [off, off + c): a fixed point (-3, -1), a skipped sample (-2, -1), else the key's row and distance
@@ -106,8 +105,8 @@ static int som_train_online(somhip_codebook *cb, somhip_dataset *ds, const somhi
   // entry 0 before the first iteration: "teaches nothing" (reach < 0), so has_prev can always be 1
   hsc[0].alpha = 0.f; hsc[0].thresh = -1.f; hsc[0].fixed = -1; hsc[0].reach = -1;
   hrow[0] = 0;
-  HIPCHK(hipMemcpyAsync(sc, hsc.data(), sizeof(StepScalars), hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipMemcpyAsync(rowidx, hrow.data(), sizeof(int64_t), hipMemcpyHostToDevice, e->stream));
+  CHK(to_device(e, sc, hsc.data(), 1));
+  CHK(to_device(e, rowidx, hrow.data(), 1));
   HIPCHK(hipMemsetAsync(slot, 0xFF, sizeof(uint64_t), e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
 
@@ -119,14 +118,14 @@ static int som_train_online(somhip_codebook *cb, somhip_dataset *ds, const somhi
     if (e->online_graph_exec) { (void)hipGraphExecDestroy(e->online_graph_exec); e->online_graph_exec = nullptr; }
     hipGraph_t graph = nullptr;
     HIPCHK(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
-    for (int64_t j = 0; j < CH; j++)
-      launch_online_any(e, cb, ds, G, M, rowidx + j, rowidx + j + 1, 1, 1, slot + j, slot + j + 1, sc + j, sc + j + 1);
+    int launch_rc = 0;
+    for (int64_t j = 0; j < CH && !launch_rc; j++)
+      launch_rc = launch_online_any(e, cb, ds, G, M, rowidx + j, rowidx + j + 1, 1, 1, slot + j, slot + j + 1, sc + j, sc + j + 1);
     // the capture is always ended -- a stream left capturing would fail every later call on this engine
-    const hipError_t launch_err = hipGetLastError();
     const hipError_t end_err = hipStreamEndCapture(e->stream, &graph);
-    if (launch_err != hipSuccess || end_err != hipSuccess) {
+    if (launch_rc || end_err != hipSuccess) {
       if (graph) (void)hipGraphDestroy(graph);
-      return fail("som_training: capturing the online chunk failed: %s", hipGetErrorString(launch_err != hipSuccess ? launch_err : end_err));
+      return launch_rc ? launch_rc : fail("som_training: capturing the online chunk failed: %s", hipGetErrorString(end_err));
     }
     const hipError_t inst_err = hipGraphInstantiate(&e->online_graph_exec, graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
@@ -140,33 +139,29 @@ static int som_train_online(somhip_codebook *cb, somhip_dataset *ds, const somhi
     int64_t it0 = p->start_iter + off, row0 = (p->data_first + off) % ds->n;
     CHK(som_scalars(lattice_of(cb), ds, p, it0, c, row0, hsc.data() + 1));
     for (int64_t j = 0; j < c; j++) hrow[(size_t)j + 1] = (row0 + j) % ds->n;
-    HIPCHK(hipMemcpyAsync(sc + 1, hsc.data() + 1, sizeof(StepScalars) * (size_t)c, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(rowidx + 1, hrow.data() + 1, sizeof(int64_t) * (size_t)c, hipMemcpyHostToDevice, e->stream));
+    CHK(to_device(e, sc + 1, hsc.data() + 1, (size_t)c));
+    CHK(to_device(e, rowidx + 1, hrow.data() + 1, (size_t)c));
     HIPCHK(hipMemsetAsync(slot + 1, 0xFF, sizeof(uint64_t) * (size_t)c, e->stream));
     if (want_graph && c == CH) {
       HIPCHK(hipGraphLaunch(e->online_graph_exec, e->stream));
     } else {
       for (int64_t j = 0; j < c; j++)
-        launch_online_any(e, cb, ds, G, M, rowidx + j, rowidx + j + 1, 1, 1, slot + j, slot + j + 1, sc + j, sc + j + 1);
+        CHK(launch_online_any(e, cb, ds, G, M, rowidx + j, rowidx + j + 1, 1, 1, slot + j, slot + j + 1, sc + j, sc + j + 1));
     }
-    HIPCHK(hipGetLastError());
     have_prev = true;
     if (trace_index || trace_diff) {
-      HIPCHK(hipMemcpyAsync(hslot.data(), slot + 1, sizeof(uint64_t) * (size_t)c, hipMemcpyDeviceToHost, e->stream));
-      HIPCHK(hipStreamSynchronize(e->stream));
+      CHK(to_host_sync(e, hslot.data(), slot + 1, (size_t)c));
       som_trace(hsc.data() + 1, hslot.data(), c, off, trace_index, trace_diff);
     }
     // carry the last iteration's slot + scalars + row into entry 0 for the next chunk / the flush
-    HIPCHK(hipMemcpyAsync(slot, slot + c, sizeof(uint64_t), hipMemcpyDeviceToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(sc, sc + c, sizeof(StepScalars), hipMemcpyDeviceToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(rowidx, rowidx + c, sizeof(int64_t), hipMemcpyDeviceToDevice, e->stream));
+    CHK(on_device(e, slot, slot + c, 1));
+    CHK(on_device(e, sc, sc + c, 1));
+    CHK(on_device(e, rowidx, rowidx + c, 1));
     // the host staging vectors are reused by the next chunk
     HIPCHK(hipStreamSynchronize(e->stream));
   }
-  if (have_prev) {   // flush: apply the last iteration's update
-    launch_online_any(e, cb, ds, G, M, rowidx, rowidx, 1, 0, slot, slot, sc, sc);
-    HIPCHK(hipGetLastError());
-  }
+  if (have_prev)   // flush: apply the last iteration's update
+    CHK(launch_online_any(e, cb, ds, G, M, rowidx, rowidx, 1, 0, slot, slot, sc, sc));
   HIPCHK(hipStreamSynchronize(e->stream));
   return 0;
 }
@@ -317,57 +312,47 @@ static int update_members(somhip_engine *e, const somhip_codebook *cb, const som
                           int64_t lazy_trips = 0) {
   if (p.tail) CHK(scratch(e, SLOT_TAIL_START, (size_t)cb->v.ngroups, &b.lstart));
   LaunchTimer t(e, KID_MEMBERS);
-  const int rc = with_value<1, 0>(cb->v.neigh == SOMHIP_NEIGH_GAUSSIAN, [&](auto g) { return with_value<1024, 256>(p.members_nt, [&](auto nt) {
+  return with_value<1, 0>(cb->v.neigh == SOMHIP_NEIGH_GAUSSIAN, [&](auto g) { return with_value<1024, 256>(p.members_nt, [&](auto nt) {
     return with_value<8, 4>(p.members_rr, [&](auto rr) { return with_value<1, 0>(lazy_trips > 0, [&](auto lz) {
       constexpr bool GG = decltype(g)::value != 0, LZ = decltype(lz)::value != 0; constexpr int NT = decltype(nt)::value, RR = decltype(rr)::value;
       // (8 samples per thread: bubble, 1024 threads only; lazy: bubble only -- the plan's tail mode is)
       if constexpr ((RR == 4 || (!GG && NT == 1024)) && !(GG && LZ)) {
-        hipLaunchKernelGGL((k_som_members<GG, NT, RR, LZ>), dim3((unsigned)cb->v.ngroups), dim3(NT), 0, e->stream, cb->v, count,
-                           p.decode ? b.bxy : nullptr, p.decode ? nullptr : d_keys, d_sc, b.cnt, b.lists, e->d_stats,
-                           p.entry == ENTRY_SAMPLE ? (int64_t)-1 : data_first, ds->n, p.entry == ENTRY_BYTE ? 4 * cb->v.d : cb->v.d >> 2,
-                           p.tail_need, b.lstart, p.gauss_gemm ? 1 : 0, p.reach_max, lazy_trips); return 0;
+        return LAUNCH(e, (k_som_members<GG, NT, RR, LZ>), dim3((unsigned)cb->v.ngroups), dim3(NT), 0, cb->v, count, p.decode ? b.bxy : nullptr,
+                      p.decode ? nullptr : d_keys, d_sc, b.cnt, b.lists, e->d_stats, p.entry == ENTRY_SAMPLE ? (int64_t)-1 : data_first, ds->n,
+                      p.entry == ENTRY_BYTE ? 4 * cb->v.d : cb->v.d >> 2, p.tail_need, b.lstart, p.gauss_gemm ? 1 : 0, p.reach_max, lazy_trips);
       } else return fail("update_members: no k_som_members<%d, %d, %d, %d> is built", (int)GG, NT, RR, (int)LZ);
   }); }); }); });
-  CHK(rc); HIPCHK(hipGetLastError());
-  return 0;
 }
 static int update_apply(somhip_engine *e, const somhip_codebook *cb, const somhip_dataset *ds, const UpdatePlan &p,
                         int64_t data_first, int64_t count, const StepScalars *d_sc, const UpdateBufs &b) {
   const bool G = cb->v.neigh == SOMHIP_NEIGH_GAUSSIAN, M = ds->d_mask != nullptr;
   LaunchTimer t(e, p.apply == APPLY_GEMM ? KID_SOM_UPDATE_GEMM : p.apply == APPLY_BUBBLE_S ? KID_SOM_UPDATE_BUBBLE_S : KID_SOM_UPDATE_RUN);
-  int rc = 0;                                             // (with_value: a plan value no launch was built for)
+  // (with_value fails where the plan holds a value no launch was built for)
   if (p.apply == APPLY_GEMM)
-    rc = with_value<4, 2, 1>(p.ntw, [&](auto n) { return with_value<1, 0>(G, [&](auto g) {
-      hipLaunchKernelGGL((k_som_update_gemm<decltype(n)::value, decltype(g)::value != 0>), p.grid, p.block, 0, e->stream, cb->v,
-                         ds->d_rows, ds->n, data_first, count, b.cnt, b.lists, b.order, e->d_stats, b.lstart); return 0;
+    return with_value<4, 2, 1>(p.ntw, [&](auto n) { return with_value<1, 0>(G, [&](auto g) {
+      return LAUNCH(e, (k_som_update_gemm<decltype(n)::value, decltype(g)::value != 0>), p.grid, p.block, 0, cb->v, ds->d_rows, ds->n, data_first, count,
+                    b.cnt, b.lists, b.order, e->d_stats, b.lstart);
     }); });
-  else if (p.apply == APPLY_GAUSS_H)
-    hipLaunchKernelGGL(k_som_update_gauss_h, p.grid, p.block, 0, e->stream, cb->v, ds->d_rows + data_first % ds->n * cb->v.d,
-                       count, b.bxy, d_sc, b.cnt, b.lists, b.order);
-  else if (p.apply == APPLY_GAUSS_S)
-    hipLaunchKernelGGL((k_som_update_gauss_s<4>), p.grid, p.block, 0, e->stream, cb->v, ds->d_rows, ds->n, data_first, count,
-                       b.bxy, d_sc, b.cnt, b.lists, b.order);
-  else if (p.apply == APPLY_BUBBLE_S)
-    rc = with_value<4, 2>(p.qw, [&](auto q) { return with_value<1, 0>(p.off32, [&](auto o) {
-      hipLaunchKernelGGL((k_som_update_bubble_s<decltype(q)::value, decltype(o)::value != 0>), p.grid, p.block, 0, e->stream,
-                         cb->v, ds->d_rows, ds->n, data_first, count, b.cnt, b.lists, b.order); return 0;
+  if (p.apply == APPLY_GAUSS_H)
+    return LAUNCH(e, k_som_update_gauss_h, p.grid, p.block, 0, cb->v, ds->d_rows + data_first % ds->n * cb->v.d, count, b.bxy, d_sc, b.cnt, b.lists,
+                  b.order);
+  if (p.apply == APPLY_GAUSS_S)
+    return LAUNCH(e, (k_som_update_gauss_s<4>), p.grid, p.block, 0, cb->v, ds->d_rows, ds->n, data_first, count, b.bxy, d_sc, b.cnt, b.lists, b.order);
+  if (p.apply == APPLY_BUBBLE_S)
+    return with_value<4, 2>(p.qw, [&](auto q) { return with_value<1, 0>(p.off32, [&](auto o) {
+      return LAUNCH(e, (k_som_update_bubble_s<decltype(q)::value, decltype(o)::value != 0>), p.grid, p.block, 0, cb->v, ds->d_rows, ds->n, data_first,
+                    count, b.cnt, b.lists, b.order);
     }); });
-  else
-    rc = with_value<4, 2>(p.qw, [&](auto q) { return with_value<1, 0>(G, [&](auto g) { return with_value<1, 0>(M, [&](auto m) {
-      hipLaunchKernelGGL((k_som_update_run<decltype(q)::value, 32, decltype(g)::value != 0, decltype(m)::value != 0>), p.grid,
-                         p.block, 0, e->stream, cb->v, ds->d_rows, (const uint8_t *)ds->d_mask, ds->n, data_first, count, b.bxy,
-                         d_sc, b.cnt, b.lists, b.order); return 0;
-    }); }); });
-  CHK(rc); HIPCHK(hipGetLastError());
-  return 0;
+  return with_value<4, 2>(p.qw, [&](auto q) { return with_value<1, 0>(G, [&](auto g) { return with_value<1, 0>(M, [&](auto m) {
+    return LAUNCH(e, (k_som_update_run<decltype(q)::value, 32, decltype(g)::value != 0, decltype(m)::value != 0>), p.grid, p.block, 0, cb->v,
+                  ds->d_rows, ds->d_mask, ds->n, data_first, count, b.bxy, d_sc, b.cnt, b.lists, b.order);
+  }); }); });
 }
 // K4a over samples [from, from + n) of a run (keys, scalars and coordinates all indexed by the run's sample)
 static int update_decode(somhip_engine *e, const somhip_codebook *cb, int64_t from, int64_t n, const uint64_t *d_keys,
                          const StepScalars *d_sc, const UpdateBufs &b) {
-  LaunchTimer t(e, KID_DECODE);
-  hipLaunchKernelGGL(k_decode_winners, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, d_keys + from, d_sc + from, n, cb->v.xdim, b.bxy + from);
-  HIPCHK(hipGetLastError());
-  return 0;
+  return LAUNCH_TIMED(e, KID_DECODE, k_decode_winners, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, d_keys + from, d_sc + from, n, cb->v.xdim,
+                      b.bxy + from);
 }
 // K4c (fold_held: a lazy members pass is kept, what it counted goes into the statistics) and the apply kernel
 static int update_order_apply(somhip_engine *e, const somhip_codebook *cb, const somhip_dataset *ds, const UpdatePlan &p,
@@ -376,12 +361,10 @@ static int update_order_apply(somhip_engine *e, const somhip_codebook *cb, const
     CHK(scratch(e, SLOT_STAGE, (size_t)cb->v.ngroups, &b.order));
     LaunchTimer t(e, KID_DECODE);                          // (timed with k_decode_winners)
     const dim3 grid((unsigned)((cb->v.ngroups * 8 + 255) / 256));
-    if (fold_held) hipLaunchKernelGGL(k_order_groups<true>, grid, dim3(256), 0, e->stream, b.cnt, (int)cb->v.ngroups, b.order, e->d_stats);
-    else hipLaunchKernelGGL(k_order_groups<false>, grid, dim3(256), 0, e->stream, b.cnt, (int)cb->v.ngroups, b.order, nullptr);
-    HIPCHK(hipGetLastError());
+    if (fold_held) CHK(LAUNCH(e, k_order_groups<true>, grid, dim3(256), 0, b.cnt, (int)cb->v.ngroups, b.order, e->d_stats));
+    else CHK(LAUNCH(e, k_order_groups<false>, grid, dim3(256), 0, b.cnt, (int)cb->v.ngroups, b.order, nullptr));
   } else if (fold_held) {
-    hipLaunchKernelGGL(k_fold_update_stats, dim3(1), dim3(256), 0, e->stream, e->d_stats);
-    HIPCHK(hipGetLastError());
+    CHK(LAUNCH(e, k_fold_update_stats, dim3(1), dim3(256), 0, e->d_stats));
   }
   return update_apply(e, cb, ds, p, data_first, count, d_sc, b);
 }
@@ -455,14 +438,13 @@ static int som_lazy_run(somhip_codebook *cb, somhip_dataset *ds, const UpdatePla
   UpdateBufs b; CHK(bind_update(e, cb, count, &b));
   if (p.decode) CHK(update_decode(e, cb, head, m, kv, d_sc, b));
   CHK(update_members(e, cb, ds, p, row0, count, kv, d_sc, b, m / ((int64_t)p.members_nt * p.members_rr)));
-  HIPCHK(hipMemcpyAsync(e->lazy_hflag, e->d_stats + STAT_LAZY_SHORT, sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
+  CHK(to_host_sync(e, e->lazy_hflag, e->d_stats + STAT_LAZY_SHORT, 1));
   const bool redo = *e->lazy_hflag != 0;
   if (redo) {
     // (into the spare keys, then copied: the head of the run's key array is not aligned like the buffer)
     HIPCHK(hipMemsetAsync(e->d_stats + STAT_UPDATE_HELD, 0, sizeof(unsigned long long) * (2 * STAT_UPDATE_PAIRS + 1), e->stream));
     CHK(scan_keys_top1(cb, ds, row0, head, spare));
-    HIPCHK(hipMemcpyAsync(kv, spare, sizeof(uint64_t) * (size_t)head, hipMemcpyDeviceToDevice, e->stream));
+    CHK(on_device(e, kv, spare, (size_t)head));
     if (p.decode) CHK(update_decode(e, cb, 0, head, kv, d_sc, b));
     CHK(update_members(e, cb, ds, p, row0, count, kv, d_sc, b));
   }
@@ -497,7 +479,7 @@ extern "C" int somhip_som_batch_update(somhip_codebook *cb, somhip_dataset *ds,
   CHK(scratch(e, SLOT_CALL_B, (size_t)count, &dsc));
   CHK(pin_acquire(e, sizeof(StepScalars) * (size_t)count, &hsc, &slot));
   CHK(som_scalars(lattice_of(cb), ds, p, batch_start_iter, count, data_first % ds->n, (StepScalars *)hsc));
-  CHK(pin_upload(e, slot, dsc, sizeof(StepScalars) * (size_t)count));
+  CHK(pin_upload(e, slot, dsc, (size_t)count));
   return som_update_run(cb, ds, data_first % ds->n, count, dev_keys, (const StepScalars *)dsc, (const StepScalars *)hsc);   // asynchronous
 } ABI_CATCH(somhip_som_batch_update)
 
@@ -605,7 +587,7 @@ static int som_train_batched(somhip_codebook *cb, somhip_dataset *ds, const somh
     CHK(pin_acquire(e, sizeof(StepScalars) * (size_t)c, &hscv, &slot));
     StepScalars *hsc = (StepScalars *)hscv;
     CHK(som_scalars(lattice_of(cb), ds, p, it0, c, row0, hsc));
-    CHK(pin_upload(e, slot, dsc, sizeof(StepScalars) * (size_t)c));
+    CHK(pin_upload(e, slot, dsc, (size_t)c));
     const UpdatePlan up = som_update_plan(cb, ds, row0, c, hsc);
     // no trace wanted and the update reads only the end of the run: only that end is searched (som_lazy_run)
     const int64_t lazy_m = trace ? 0 : som_lazy_samples(cb, up, c, hsc);
@@ -615,8 +597,7 @@ static int som_train_batched(somhip_codebook *cb, somhip_dataset *ds, const somh
       CHK(som_update_planned(cb, ds, up, row0, c, (const uint64_t *)dkeys, (const StepScalars *)dsc));
     }
     if (trace) {
-      HIPCHK(hipMemcpyAsync(hk.data(), dkeys, sizeof(uint64_t) * (size_t)c, hipMemcpyDeviceToHost, e->stream));
-      HIPCHK(hipStreamSynchronize(e->stream));
+      CHK(to_host_sync(e, hk.data(), dkeys, (size_t)c));
       som_trace(hsc, hk.data(), c, off, trace_index, trace_diff);
     }
     off += c;
@@ -634,7 +615,7 @@ extern "C" int somhip_som_train(somhip_codebook *cb, somhip_dataset *ds, const s
   if (p->length <= 0 || p->count < 0 || p->start_iter < 0 || p->start_iter + p->count > p->length)
     return fail("somhip_som_train: iterations [%lld,%lld) outside schedule of %lld",
                 (long long)p->start_iter, (long long)(p->start_iter + p->count), (long long)p->length);
-  if (cb->v.row_offset != 0 || cb->n_global != cb->v.n)
+  if (is_shard(cb))
     return fail("somhip_som_train: sharded codebook -- use somhip_batch_winner_keys + somhip_som_batch_update");
   if (p->count == 0) return 0;
   HIPCHK(hipSetDevice(cb->e->device));

@@ -2,11 +2,10 @@
 // (part of somhip.hip: same translation unit)
 
 extern "C" int somhip_umatrix(somhip_codebook *cb, int filters, float *u, double minmax[2]) try {
-  if (!cb || !u) return fail("somhip_umatrix: null argument");
-  if (!cb->e) return fail("somhip_umatrix: the engine of this codebook was destroyed");
+  CHK(check_codebook(cb, u, "somhip_umatrix"));
   if (cb->v.topol != SOMHIP_TOPOL_HEXA && cb->v.topol != SOMHIP_TOPOL_RECT)
     return fail("somhip_umatrix: the codebook is not a map (topology %d): only hexa and rect maps have a U-matrix", cb->v.topol);
-  if (cb->v.patch_stride > 1 || cb->v.row_offset != 0 || cb->v.n != cb->n_global)
+  if (is_shard(cb))
     return fail("somhip_umatrix: the codebook is a shard (%lld of %lld rows); the U-matrix needs the whole map",
                 (long long)cb->v.n, (long long)cb->n_global);
   const int mx = cb->v.xdim, my = cb->ydim;
@@ -24,26 +23,13 @@ extern "C" int somhip_umatrix(somhip_codebook *cb, int filters, float *u, double
   CHK(scratch(e, SLOT_CALL_B, (size_t)count, &other));
   CHK(scratch(e, SLOT_PARTIAL, 2, &d_mm));
   const uint32_t preset[2] = {FLT_MAX_BITS, 0u};
-  HIPCHK(hipMemcpyAsync(d_mm, preset, sizeof preset, hipMemcpyHostToDevice, e->stream));
+  CHK(to_device(e, d_mm, preset, 2));
   const unsigned per_entry = (unsigned)((count + 255) / 256);
-  {
-    LaunchTimer t(e, KID_UMAT_DIST);
-    hipLaunchKernelGGL(k_umat_dist, dim3((unsigned)((cb->v.n + 255) / 256), 3), dim3(256), 0, e->stream, cb->v, m, cur);
-  }
-  HIPCHK(hipGetLastError());
-  {
-    LaunchTimer t(e, KID_UMAT_UNITS);
-    hipLaunchKernelGGL(k_umat_units, dim3((unsigned)((cb->v.n + 255) / 256)), dim3(256), 0, e->stream, m, cur);
-  }
-  HIPCHK(hipGetLastError());
-  {
-    LaunchTimer t(e, KID_UMAT_MINMAX);
-    hipLaunchKernelGGL(k_umat_minmax, dim3(std::min(per_entry, 128u)), dim3(256), 0, e->stream, (const float *)cur, count, d_mm);
-  }
-  HIPCHK(hipGetLastError());
+  CHK(LAUNCH_TIMED(e, KID_UMAT_DIST, k_umat_dist, dim3((unsigned)((cb->v.n + 255) / 256), 3), dim3(256), 0, cb->v, m, cur));
+  CHK(LAUNCH_TIMED(e, KID_UMAT_UNITS, k_umat_units, dim3((unsigned)((cb->v.n + 255) / 256)), dim3(256), 0, m, cur));
+  CHK(LAUNCH_TIMED(e, KID_UMAT_MINMAX, k_umat_minmax, dim3(std::min(per_entry, 128u)), dim3(256), 0, cur, count, d_mm));
   uint32_t bits[2];
-  HIPCHK(hipMemcpyAsync(bits, d_mm, sizeof bits, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
+  CHK(to_host_sync(e, bits, d_mm, 2));
   float fmin, fmax;
   memcpy(&fmin, &bits[0], sizeof fmin);
   memcpy(&fmax, &bits[1], sizeof fmax);
@@ -51,28 +37,14 @@ extern "C" int somhip_umatrix(somhip_codebook *cb, int filters, float *u, double
   if (minmax) { minmax[0] = lo; minmax[1] = hi; }
   if (hi == lo)
     return fail("somhip_umatrix: every distance between neighbouring units is %g: the scaling to [0, 1] would divide by zero", lo);
-  {
-    LaunchTimer t(e, KID_UMAT_SCALE);
-    hipLaunchKernelGGL(k_umat_scale, dim3(per_entry), dim3(256), 0, e->stream, cur, count, lo, hi - lo);
-  }
-  HIPCHK(hipGetLastError());
+  CHK(LAUNCH_TIMED(e, KID_UMAT_SCALE, k_umat_scale, dim3(per_entry), dim3(256), 0, cur, count, lo, hi - lo));
   if (filters & SOMHIP_UMAT_AVERAGE) {
-    {
-      LaunchTimer t(e, KID_UMAT_AVERAGE);
-      hipLaunchKernelGGL(k_umat_average, dim3(per_entry), dim3(256), 0, e->stream, m, (const float *)cur, other);
-    }
-    HIPCHK(hipGetLastError());
+    CHK(LAUNCH_TIMED(e, KID_UMAT_AVERAGE, k_umat_average, dim3(per_entry), dim3(256), 0, m, cur, other));
     std::swap(cur, other);
   }
   if (filters & SOMHIP_UMAT_MEDIAN) {
-    {
-      LaunchTimer t(e, KID_UMAT_MEDIAN);
-      hipLaunchKernelGGL(k_umat_median, dim3(per_entry), dim3(256), 0, e->stream, m, (const float *)cur, other);
-    }
-    HIPCHK(hipGetLastError());
+    CHK(LAUNCH_TIMED(e, KID_UMAT_MEDIAN, k_umat_median, dim3(per_entry), dim3(256), 0, m, cur, other));
     std::swap(cur, other);
   }
-  HIPCHK(hipMemcpyAsync(u, cur, sizeof(float) * (size_t)count, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  return 0;
+  return to_host_sync(e, u, cur, (size_t)count);
 } ABI_CATCH(somhip_umatrix)

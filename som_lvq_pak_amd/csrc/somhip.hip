@@ -228,6 +228,30 @@ static int raise_lds_limit(somhip_engine *e, LdsKernel which, const void *kernel
   return 0;
 }
 
+template <class T> struct identity { using type = T; };   // T in a context no template argument is deduced from
+
+// Copies of `count` elements of T on the engine's stream: the byte count follows from the pointers' type.  Asynchronous
+// unless the name says otherwise; to_host_sync also waits for the stream (everything queued before the copy included).
+template <class T>
+static int copy_async(somhip_engine *e, T *dst, const T *src, size_t count, hipMemcpyKind kind) {
+  HIPCHK(hipMemcpyAsync(dst, src, sizeof(T) * count, kind, e->stream));
+  return 0;
+}
+template <class T> static int to_host(somhip_engine *e, T *dst, const typename identity<T>::type *src, size_t count) {
+  return copy_async(e, dst, src, count, hipMemcpyDeviceToHost);
+}
+template <class T> static int to_device(somhip_engine *e, T *dst, const typename identity<T>::type *src, size_t count) {
+  return copy_async(e, dst, src, count, hipMemcpyHostToDevice);
+}
+template <class T> static int on_device(somhip_engine *e, T *dst, const typename identity<T>::type *src, size_t count) {
+  return copy_async(e, dst, src, count, hipMemcpyDeviceToDevice);
+}
+template <class T> static int to_host_sync(somhip_engine *e, T *dst, const typename identity<T>::type *src, size_t count) {
+  CHK(to_host(e, dst, src, count));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  return 0;
+}
+
 // next pinned staging buffer of the ring (waits only if its previous copy is still in flight)
 static int pin_acquire(somhip_engine *e, size_t bytes, void **host, int *slot) {
   int i = e->pin_next;
@@ -245,8 +269,9 @@ static int pin_acquire(somhip_engine *e, size_t bytes, void **host, int *slot) {
   *slot = i;
   return 0;
 }
-static int pin_upload(somhip_engine *e, int slot, void *dev, size_t bytes) {
-  HIPCHK(hipMemcpyAsync(dev, e->pin_buf[slot], bytes, hipMemcpyHostToDevice, e->stream));
+template <class T>   // (`count` elements of T: what the caller wrote into the buffer)
+static int pin_upload(somhip_engine *e, int slot, T *dev, size_t count) {
+  CHK(to_device(e, dev, static_cast<const T *>(e->pin_buf[slot]), count));
   HIPCHK(hipEventRecord(e->pin_ev[slot], e->stream));
   return 0;
 }
@@ -286,6 +311,25 @@ struct LaunchTimer {   // HIP events on the engine's own stream around one launc
     if (e->pending.size() >= 2048) (void)timing_flush(e);
   }
 };
+
+// Every kernel launch of the engine: on its stream, checked at once, a failure reported under the kernel's name.  The
+// arguments convert to the kernel's own parameter types (the pack is not deduced from them), so a call site casts nothing
+// and writes nullptr plainly; a kernel's default arguments do not reach through the pointer and are spelled out.
+template <class... P>
+static int launch(somhip_engine *e, const char *name, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds_bytes,
+                  typename identity<P>::type... args) {
+  hipLaunchKernelGGL(kernel, grid, block, lds_bytes, e->stream, args...);
+  const hipError_t err = hipGetLastError();
+  return err == hipSuccess ? 0 : fail("%s: launch failed: %s", name, hipGetErrorString(err));
+}
+template <class... P>   // ... as the one launch of a LaunchTimer scope
+static int launch_timed(somhip_engine *e, int kid, const char *name, void (*kernel)(P...), dim3 grid, dim3 block,
+                        size_t lds_bytes, typename identity<P>::type... args) {
+  LaunchTimer t(e, kid);
+  return launch(e, name, kernel, grid, block, lds_bytes, args...);
+}
+#define LAUNCH(e, kernel, ...) launch(e, #kernel, kernel, __VA_ARGS__)
+#define LAUNCH_TIMED(e, kid, kernel, ...) launch_timed(e, kid, #kernel, kernel, __VA_ARGS__)
 
 // ---------------------------------------------------------------------------------
 // engine
@@ -370,8 +414,7 @@ extern "C" int somhip_engine_set_update_mode(somhip_engine *e, int mode) try {
 extern "C" int somhip_scan_stats(somhip_engine *e, uint64_t out[8]) try {
   CHK(check_engine(e, "somhip_scan_stats"));
   unsigned long long h[STAT_WORDS];
-  HIPCHK(hipMemcpyAsync(h, e->d_stats, sizeof h, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
+  CHK(to_host_sync(e, h, e->d_stats, STAT_WORDS));
   uint64_t rows = 0, pairs = 0, walked = 0;
   for (int k = 0; k < STAT_UPDATE_PAIRS; k++) { rows += h[STAT_UPDATE + 2 * k]; pairs += h[STAT_UPDATE + 2 * k + 1]; }
   for (int k = 0; k < STAT_GEMM_WALKS; k++) walked += h[STAT_GEMM_WALK + k];
@@ -386,9 +429,8 @@ extern "C" int somhip_lvq_stats(somhip_engine *e, uint64_t out[12]) try {
   unsigned long long pairs = 0;                            // counted on the device (the top-k search does not wait for the host)
   uint32_t topk_counter[2] = {0, 0};                       // the last pre-filtered top-k search's pair list: [0] fill, [1] overflow
   HIPCHK(hipSetDevice(e->device));
-  HIPCHK(hipMemcpyAsync(&pairs, e->d_stats + STAT_TOPK_PAIRS, sizeof pairs, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipMemcpyAsync(topk_counter, e->d_stats + STAT_TOPK_LIST, sizeof topk_counter, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
+  CHK(to_host(e, &pairs, e->d_stats + STAT_TOPK_PAIRS, 1));
+  CHK(to_host_sync(e, topk_counter, reinterpret_cast<const uint32_t *>(e->d_stats + STAT_TOPK_LIST), 2));
   out[8] = e->lvq_components; out[9] = e->lvq_largest; out[10] = pairs; out[11] = topk_counter[1] != 0 ? 1 : 0;
   return 0;
 } ABI_CATCH(somhip_lvq_stats)
@@ -431,13 +473,12 @@ extern "C" int somhip_device_free(somhip_engine *e, void *p) try {
 } ABI_CATCH(somhip_device_free)
 extern "C" int somhip_copy_to_host(somhip_engine *e, void *dst, const void *src, int64_t bytes) try {
   CHK(check_engine(e, "somhip_copy_to_host"));
-  HIPCHK(hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
+  CHK(to_host_sync(e, (uint8_t *)dst, (const uint8_t *)src, (size_t)bytes));
   return 0;
 } ABI_CATCH(somhip_copy_to_host)
 extern "C" int somhip_copy_to_device(somhip_engine *e, void *dst, const void *src, int64_t bytes) try {
   CHK(check_engine(e, "somhip_copy_to_device"));
-  HIPCHK(hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyHostToDevice, e->stream));
+  CHK(to_device(e, (uint8_t *)dst, (const uint8_t *)src, (size_t)bytes));
   HIPCHK(hipStreamSynchronize(e->stream));
   return 0;
 } ABI_CATCH(somhip_copy_to_device)
@@ -477,19 +518,31 @@ struct somhip_dataset {
   std::vector<int16_t> fixed_xy;
 };
 
+// The two refusals an entry point on one mirror begins with.  args: its other pointer arguments are all there.
+static int check_codebook(const somhip_codebook *cb, bool args, const char *who) {
+  if (!cb || !args) return fail("%s: null argument", who);
+  if (!cb->e) return fail("%s: the engine of this codebook was destroyed", who);
+  return 0;
+}
+static int check_dataset(const somhip_dataset *ds, bool args, const char *who) {
+  if (!ds || !args) return fail("%s: null argument", who);
+  if (!ds->e) return fail("%s: the engine of this data set was destroyed", who);
+  return 0;
+}
+// The codebook holds some of its rows only: a block of them (row_offset, n < n_global) or every patch_stride-th 8x8 patch
+// of a map.  The interleaved kind starts at row 0 but, with patch_stride > 1, always has n < n_global as well.
+static bool is_shard(const somhip_codebook *cb) { return cb->v.row_offset != 0 || cb->n_global != cb->v.n; }
+// every component of this row is masked: it has no distance to anything, so no winner
+static bool sample_is_empty(const somhip_dataset *ds, int64_t row) { return !ds->all_masked.empty() && ds->all_masked[(size_t)row]; }
+
 static int upload_rows(somhip_codebook *cb, const float *rows) {
   somhip_engine *e = cb->e;
   cb->prep_valid = false;
   float *stage;
-  size_t bytes = sizeof(float) * (size_t)cb->v.n * cb->v.d;
-  CHK(scratch(e, SLOT_STAGE, (size_t)cb->v.n * cb->v.d, &stage));
-  HIPCHK(hipMemcpyAsync(stage, rows, bytes, hipMemcpyHostToDevice, e->stream));
-  {
-    LaunchTimer t(e, KID_LAYOUT);
-    hipLaunchKernelGGL(k_rows_to_tiles, dim3((unsigned)cb->v.ngroups), dim3(256), 0, e->stream,
-                       (const float *)stage, cb->v);
-  }
-  HIPCHK(hipGetLastError());
+  const size_t count = (size_t)cb->v.n * cb->v.d;
+  CHK(scratch(e, SLOT_STAGE, count, &stage));
+  CHK(to_device(e, stage, rows, count));
+  CHK(LAUNCH_TIMED(e, KID_LAYOUT, k_rows_to_tiles, dim3((unsigned)cb->v.ngroups), dim3(256), 0, stage, cb->v));
   HIPCHK(hipStreamSynchronize(e->stream));
   return 0;
 }
@@ -584,27 +637,19 @@ extern "C" int somhip_codebook_create_interleaved(somhip_engine *e, const float 
                          shard_count > 1 ? shard_count : 1, shard_count > 1 ? shard_index : 0, out);
 } ABI_CATCH(somhip_codebook_create_interleaved)
 extern "C" int somhip_codebook_upload(somhip_codebook *cb, const float *rows) try {
-  if (!cb || !rows) return fail("somhip_codebook_upload: null argument");
-  if (!cb->e) return fail("somhip_codebook_upload: the engine of this codebook was destroyed");
+  CHK(check_codebook(cb, rows, "somhip_codebook_upload"));
   HIPCHK(hipSetDevice(cb->e->device));
   return upload_rows(cb, rows);
 } ABI_CATCH(somhip_codebook_upload)
 extern "C" int somhip_codebook_download(somhip_codebook *cb, float *rows) try {
-  if (!cb || !rows) return fail("somhip_codebook_download: null argument");
-  if (!cb->e) return fail("somhip_codebook_download: the engine of this codebook was destroyed");
+  CHK(check_codebook(cb, rows, "somhip_codebook_download"));
   somhip_engine *e = cb->e;
   HIPCHK(hipSetDevice(e->device));
   float *stage;
-  size_t bytes = sizeof(float) * (size_t)cb->v.n * cb->v.d;
-  CHK(scratch(e, SLOT_STAGE, (size_t)cb->v.n * cb->v.d, &stage));
-  {
-    LaunchTimer t(e, KID_LAYOUT);
-    hipLaunchKernelGGL(k_tiles_to_rows, dim3((unsigned)cb->v.ngroups), dim3(256), 0, e->stream,
-                       (float *)stage, cb->v);
-  }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(rows, stage, bytes, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
+  const size_t count = (size_t)cb->v.n * cb->v.d;
+  CHK(scratch(e, SLOT_STAGE, count, &stage));
+  CHK(LAUNCH_TIMED(e, KID_LAYOUT, k_tiles_to_rows, dim3((unsigned)cb->v.ngroups), dim3(256), 0, stage, cb->v));
+  CHK(to_host_sync(e, rows, stage, count));
   return 0;
 } ABI_CATCH(somhip_codebook_download)
 static void codebook_release(somhip_codebook *cb) {
@@ -708,14 +753,9 @@ extern "C" int somhip_dataset_generate(somhip_engine *e, uint64_t seed, int k_ce
   if (centres) HIPCHK(hipMalloc((void **)&dcen, sizeof(int32_t) * (size_t)n_rows));
   const int64_t total = n_rows * dim;
   const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 65536);
-  {
-    LaunchTimer t(e, KID_LAYOUT);
-    hipLaunchKernelGGL(k_gen_mixture, dim3(blocks), dim3(256), 0, e->stream, seed, k_centres, dim, first_row, n_rows, rows, dcen);
-  }
-  HIPCHK(hipGetLastError());
+  CHK(LAUNCH_TIMED(e, KID_LAYOUT, k_gen_mixture, dim3(blocks), dim3(256), 0, seed, k_centres, dim, first_row, n_rows, rows, dcen));
   if (centres) {
-    HIPCHK(hipMemcpyAsync(centres, dcen, sizeof(int32_t) * (size_t)n_rows, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
+    CHK(to_host_sync(e, centres, dcen, (size_t)n_rows));
     ds->labels.assign(centres, centres + n_rows);
   }
   return 0;
@@ -727,14 +767,12 @@ extern "C" int somhip_dataset_generate(somhip_engine *e, uint64_t seed, int k_ce
   return 0;
 } ABI_CATCH(somhip_dataset_generate)
 extern "C" int somhip_dataset_download_rows(somhip_dataset *ds, int64_t first, int64_t count, float *rows) try {
-  if (!ds || !rows) return fail("somhip_dataset_download_rows: null argument");
-  if (!ds->e) return fail("somhip_dataset_download_rows: the engine of this data set was destroyed");
+  CHK(check_dataset(ds, rows, "somhip_dataset_download_rows"));
   if (first < 0 || count < 0 || first + count > ds->n) return fail("somhip_dataset_download_rows: rows [%lld,%lld) outside %lld",
                                                                  (long long)first, (long long)(first + count), (long long)ds->n);
   if (count == 0) return 0;
   HIPCHK(hipSetDevice(ds->e->device));
-  HIPCHK(hipMemcpyAsync(rows, ds->d_rows + first * ds->d, sizeof(float) * (size_t)count * ds->d, hipMemcpyDeviceToHost, ds->e->stream));
-  HIPCHK(hipStreamSynchronize(ds->e->stream));
+  CHK(to_host_sync(ds->e, rows, ds->d_rows + first * ds->d, (size_t)count * ds->d));
   return 0;
 } ABI_CATCH(somhip_dataset_download_rows)
 static void dataset_release(somhip_dataset *ds) {

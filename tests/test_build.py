@@ -115,7 +115,7 @@ def test_lvq_driver_plans_once_and_launches_each_kernel_once():
     lvq = text[os.path.join(csrc, "host_lvq.inc")]
     for kernel in ("k_lvq_sample_rho", "k_lvq_pair_adj", "k_lvq_pair_adj_mfma", "k_lvq_components", "k_lvq_batch_apply",
                    "k_lvq_commit", "k_lvq_cand_meta", "k_lvq_amax", "k_lvq_online_step", "k_prep_rows_bf16"):
-        sites = re.findall(r"hipLaunchKernelGGL\s*\(\s*\(?\s*%s\b" % kernel, lvq)
+        sites = re.findall(r"\bLAUNCH(?:_TIMED\s*\(\s*[\w>-]+\s*,\s*\w+|\s*\(\s*[\w>-]+)\s*,\s*\(?\s*%s\b" % kernel, lvq)
         assert len(sites) == 1, (kernel, len(sites))
 
 

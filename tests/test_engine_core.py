@@ -80,3 +80,51 @@ def test_engine_destroy_counts_no_slots_by_hand():
     body = re.search(r'extern "C" void somhip_engine_destroy\(.*?ABI_CATCH_VOID\(somhip_engine_destroy\)', text, flags=re.S).group(0)
     assert "SLOT_COUNT" in body
     assert not re.search(r"\b32\b", _code(body)), body
+
+
+def _csrc_code():
+    """path -> text without comments, for every file under csrc/"""
+    out = {}
+    for dirpath, _, files in os.walk(CSRC):
+        for f in sorted(files):
+            path = os.path.join(dirpath, f)
+            out[os.path.relpath(path, CSRC)] = _code(open(path).read())
+    return out
+
+
+def _function_body(code, head):
+    """the text of the function whose definition starts with `head`, braces matched"""
+    start = code.index(head)
+    i = code.index("{", start)
+    depth = 0
+    for j in range(i, len(code)):
+        depth += code[j] == "{"
+        depth -= code[j] == "}"
+        if depth == 0:
+            return code[start:j + 1]
+    raise AssertionError(head)
+
+
+def test_kernels_are_launched_from_one_place():
+    sites = {f: len(re.findall(r"\bhipLaunchKernelGGL\b", t)) for f, t in _csrc_code().items()}
+    assert sum(sites.values()) == 1, {f: n for f, n in sites.items() if n}
+    body = _function_body(_csrc_code()["somhip.hip"], "static int launch(somhip_engine *e")
+    assert "hipLaunchKernelGGL" in body and "hipGetLastError" in body and "launch failed" in body
+
+
+def test_stream_copies_go_through_the_typed_helpers():
+    sites = {f: len(re.findall(r"\bhipMemcpyAsync\b", t)) for f, t in _csrc_code().items()}
+    assert sum(sites.values()) == 1, {f: n for f, n in sites.items() if n}
+    body = _function_body(_csrc_code()["somhip.hip"], "static int copy_async(somhip_engine *e")
+    assert "hipMemcpyAsync" in body and "sizeof(T) * count" in body
+
+
+def test_shard_and_empty_sample_predicates_are_written_once():
+    code = _csrc_code()
+    create = _function_body(code["somhip.hip"], 'extern "C" int somhip_dataset_create(')
+    rest = "".join(code.values()).replace(create, "")
+    assert len(re.findall(r"all_masked\s*\.\s*empty\s*\(\s*\)", rest)) == 1
+    # a mirror's n_global compared with its row count, either operand first (codebook_create checks its n_global
+    # ARGUMENT against the map's sides before any mirror exists: that is no shard test)
+    assert len(re.findall(r"->\s*n_global\s*!=|!=\s*\w+\s*->\s*n_global\b", rest)) == 1
+    assert "is_shard" in _function_body(code["somhip.hip"], "static bool is_shard(")
