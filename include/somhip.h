@@ -250,6 +250,29 @@ int  somhip_knn_vote(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int
 /* HIP-event total of the vote kernel since somhip_timing_reset, while somhip_timing_enable is on (like the wide stages,
  * not in the table of somhip_kernel_count); one launch per chunk */
 int  somhip_knn_vote_timing(somhip_engine *e, int64_t *launches, double *total_ms);
+/* Map quality (K1q): the topographic error and per-unit statistics of a map over data rows (first + s) % n_rows,
+ * s = 0 .. count-1, formed on the device behind the top-2 search under SOMHIP_TIE_FIRST (same routes, chunks, row wrap and
+ * masked data as somhip_batch_topk_keys).  A sample is searched unless every component of it is masked (find_qerror skips
+ * those, som_rout.c:712).  b1, d1: find_winner_euc's winner and its squared distance; b2: the winner among the other
+ * rows, lowest index on equal distances (not find_winner_knn's order); b1 and b2 are adjacent when the squared lattice
+ * distance of hexa_dist / rect_dist (som_rout.c:434) is <= 1: the units a bubble of radius 1 around b1 teaches.
+ *   out->searched      searched samples
+ *   out->topo_defined  ... that have a b2 (none on a map of one unit)
+ *   out->topo_errors   ... whose b1 and b2 are not adjacent
+ *   out->qerror        find_qerror's float chain (som_rout.c:715) continued from qerror_in over the searched samples in
+ *                      data order: the float the qerror tool sums, bit for bit
+ *   hits[u]           += searched samples with b1 == u
+ *   qsum[u]           += sqrt((double)d1) of those samples, one fp64 addition each, in data order
+ * hits and qsum (host arrays of n_rows of the codebook, either may be NULL) are read, continued and written back, so a run
+ * cut into several calls at any point -- passing the arrays and the last out->qerror on -- gives the bits of one call.
+ * The codebook must be a whole map (xdim * ydim rows, hexa or rect); count >= 2^32 is refused; count <= 0 does nothing. */
+typedef struct { int64_t searched, topo_defined, topo_errors; float qerror; } somhip_quality_totals;
+int  somhip_map_quality(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count,
+                        uint32_t *hits /*[n_rows] in/out or NULL*/, double *qsum /*[n_rows] in/out or NULL*/,
+                        float qerror_in, somhip_quality_totals *out);
+/* HIP-event totals of its two kernels since somhip_timing_reset, while somhip_timing_enable is on (not in the table of
+ * somhip_kernel_count): [0] the pair pass, [1] the unit pass; one launch of each per chunk */
+int  somhip_map_quality_timing(somhip_engine *e, int64_t launches[2], double total_ms[2]);
 
 /* ---- som_training (som_rout.c:556-671) --------------------------------------
  * Runs iterations [start_iter, start_iter+count) of a schedule of `length`

@@ -33,6 +33,10 @@ class LvqParams(C.Structure):
                 ("start_iter", C.c_int64), ("count", C.c_int64), ("data_first", C.c_int64)]
 
 
+class QualityTotals(C.Structure):
+    _fields_ = [("searched", C.c_int64), ("topo_defined", C.c_int64), ("topo_errors", C.c_int64), ("qerror", C.c_float)]
+
+
 # name -> (restype, argtypes); exactly the symbols include/somhip.h declares
 SIGNATURES = {
     "somhip_last_error": (C.c_char_p, []),
@@ -87,6 +91,9 @@ SIGNATURES = {
     "somhip_knn_timing": (C.c_int, [C.c_void_p, c_i64_p, c_double_p]),
     "somhip_knn_vote": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, c_i32_p, c_i32_p, c_i32_p, c_i32_p]),
     "somhip_knn_vote_timing": (C.c_int, [C.c_void_p, c_i64_p, c_double_p]),
+    "somhip_map_quality": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, c_u32_p, c_double_p, C.c_float,
+                                     C.POINTER(QualityTotals)]),
+    "somhip_map_quality_timing": (C.c_int, [C.c_void_p, c_i64_p, c_double_p]),
     "somhip_som_train": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(SomParams), c_i32_p, c_float_p]),
     "somhip_mapset_create": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.POINTER(C.c_void_p)]),

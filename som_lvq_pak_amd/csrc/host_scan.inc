@@ -750,9 +750,11 @@ static_assert(SOMHIP_KNN_MAX == KNN_WIDE_MAX, "the select stage's pool is laid o
 // (with_topk_width), chunks of 4096; 9 .. SOMHIP_KNN_MAX: the wide route (K1w), masked data or not -- pack the samples,
 // every distance, the select -- in chunks of ScanPlan::chunk.  use(off, f, c, dk, stride) runs per chunk behind the
 // launches that leave keys dk[c][stride] (ascending, the first knn count) in SLOT_CALL_A for the c samples from data
-// row f on, the run's samples off .. off + c - 1; it returns 0 or an error.
+// row f on, the run's samples off .. off + c - 1; it returns 0 or an error.  tie_knn: the order of equal distances for
+// knn 2 .. 8 -- 1: find_winner_knn's, tags ~unit; 0: SOMHIP_TIE_FIRST, plain tags (somhip_map_quality).  The wide route
+// has find_winner_knn's order only.
 template <class Use>
-static int knn_chunk_keys(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count, int knn, Use use) {
+static int knn_chunk_keys(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count, int knn, int tie_knn, Use use) {
   somhip_engine *e = cb->e;
   if (knn <= 8)
     return with_topk_width(knn, nullptr, [&](auto width) {
@@ -764,7 +766,7 @@ static int knn_chunk_keys(somhip_codebook *cb, somhip_dataset *ds, int64_t first
         const int64_t c = std::min(CH, count - off);
         const int64_t f = (first + off) % ds->n;
         if constexpr (KK == 1) CHK(scan_keys_top1(cb, ds, f, c, dk));
-        else CHK(scan_keys_topk<KK>(cb, ds, f, c, dk));
+        else CHK(scan_keys_topk<KK>(cb, ds, f, c, dk, tie_knn));
         CHK(use(off, f, c, dk, KK));
       }
       return 0;
@@ -820,7 +822,7 @@ extern "C" int somhip_find_winners(somhip_codebook *cb, somhip_dataset *ds, int6
   const bool knn_rule = (tie == SOMHIP_TIE_KNN) && knn >= 2;
   if (!knn_rule && knn != 1) return fail("somhip_find_winners: knn > 1 needs SOMHIP_TIE_KNN");
   std::vector<uint64_t> hk;
-  return knn_chunk_keys(cb, ds, first, count, knn, [&](int64_t off, int64_t f, int64_t c, const uint64_t *dk, int stride) {
+  return knn_chunk_keys(cb, ds, first, count, knn, 1, [&](int64_t off, int64_t f, int64_t c, const uint64_t *dk, int stride) {
     if (hk.empty()) hk.resize((size_t)c * stride);                      // (the first chunk is the longest)
     CHK(to_host_sync(e, hk.data(), dk, (size_t)c * stride));
     for (int64_t i = 0; i < c; i++) {
@@ -852,7 +854,7 @@ extern "C" int somhip_knn_vote(somhip_codebook *cb, somhip_dataset *ds, int64_t 
     HIPCHK(hipMemcpy(ds->d_labels, ds->labels.data(), sizeof(int32_t) * (size_t)ds->n, hipMemcpyHostToDevice));
   }
   std::vector<int32_t> hv;
-  return knn_chunk_keys(cb, ds, first, count, knn, [&](int64_t off, int64_t f, int64_t c, const uint64_t *dk, int stride) {
+  return knn_chunk_keys(cb, ds, first, count, knn, 1, [&](int64_t off, int64_t f, int64_t c, const uint64_t *dk, int stride) {
     int4 *dv;
     CHK(scratch(e, SLOT_CALL_B, (size_t)c, &dv));
     CHK(LAUNCH_TIMED(e, KID_KNN_VOTE, k_knn_vote, dim3((unsigned)((c + VOTE_SAMPLES - 1) / VOTE_SAMPLES)), dim3(VOTE_SAMPLES * WAVE), 0, dk, stride,

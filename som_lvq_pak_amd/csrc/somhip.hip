@@ -87,8 +87,9 @@ static const char *kKernelNames[KID_COUNT] = {
 };
 // The table above is what somhip_kernel_count / somhip_kernel_name publish, and it is closed: callers index it and select
 // from it by bit.  Kernels added since are timed by LaunchTimer all the same, under ids that follow the table; an entry
-// point of their own reports them (somhip_mapset_timing, somhip_knn_timing, somhip_knn_vote_timing).
-enum TimedOnlyId { KID_MAPSET_TRAIN = KID_COUNT, KID_MAPSET_WINNERS, KID_KNN_DIST, KID_KNN_SELECT, KID_KNN_VOTE, KID_TIMED };
+// point of their own reports them (somhip_mapset_timing, somhip_knn_timing, somhip_knn_vote_timing, somhip_map_quality_timing).
+enum TimedOnlyId { KID_MAPSET_TRAIN = KID_COUNT, KID_MAPSET_WINNERS, KID_KNN_DIST, KID_KNN_SELECT, KID_KNN_VOTE, KID_QUALITY_PAIRS,
+                   KID_QUALITY_UNITS, KID_TIMED };
 static_assert(KID_TIMED <= 64, "somhip_timing_select's mask has one bit per kernel id");
 extern "C" int somhip_kernel_count(void) { return KID_COUNT; }
 extern "C" const char *somhip_kernel_name(int i) { return (i >= 0 && i < KID_COUNT) ? kKernelNames[i] : ""; }
@@ -147,6 +148,8 @@ enum ScratchSlot {
   SLOT_L2_OUT,             // two-level pre-filter, nearest row: level 2's minimum and mask of every list entry at the entry's
                            // own slot, from level 2 to the re-rank's selection (k_rerank_select_lists)
   SLOT_KNN_DIST,           // wide k-NN: the distances of a chunk of samples to every row, from the distance stage to the select
+  SLOT_QUALITY,            // somhip_map_quality: the run's qsum, totals and hits, around the searches of its chunks (SLOT_CALL_A the
+                           // chunk's keys, SLOT_CALL_B its per-sample terms, units and distances)
   SLOT_COUNT
 };
 
@@ -512,6 +515,7 @@ struct somhip_dataset {
   int d = 0;
   uint8_t *d_mask = nullptr;
   int32_t *d_labels = nullptr;       // device copy of labels, made by the first somhip_knn_vote that wants it
+  uint8_t *d_all_masked = nullptr;   // device copy of all_masked, made by the first somhip_map_quality that wants it
   std::vector<uint8_t> all_masked;   // host: 1 if every component of the row is masked
   std::vector<int32_t> labels;       // host copies of the per-row scalars
   std::vector<int16_t> weight;
@@ -779,9 +783,11 @@ static void dataset_release(somhip_dataset *ds) {
   if (ds->owns_rows && ds->d_rows) (void)hipFree((void *)ds->d_rows);
   if (ds->d_mask) (void)hipFree(ds->d_mask);
   if (ds->d_labels) (void)hipFree(ds->d_labels);
+  if (ds->d_all_masked) (void)hipFree(ds->d_all_masked);
   ds->d_rows = nullptr;
   ds->d_mask = nullptr;
   ds->d_labels = nullptr;
+  ds->d_all_masked = nullptr;
   ds->e = nullptr;
 }
 extern "C" void somhip_dataset_destroy(somhip_dataset *ds) try {
@@ -805,3 +811,4 @@ extern "C" void somhip_dataset_destroy(somhip_dataset *ds) try {
 #include "host_class.inc"
 #include "host_umat.inc"
 #include "host_planes.inc"
+#include "host_quality.inc"

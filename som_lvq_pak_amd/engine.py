@@ -130,6 +130,14 @@ class Engine:
         check(self.lib.somhip_knn_vote_timing(self.h, C.byref(n), C.byref(ms)))
         return {"k_knn_vote": (n.value, ms.value)}
 
+    def map_quality_timing(self):
+        """(launches, ms) of map_quality's two kernels while timing is on (somhip_map_quality_timing; they are not in
+        timing_table): one launch of each per chunk of samples"""
+        n = (C.c_int64 * 2)()
+        ms = (C.c_double * 2)()
+        check(self.lib.somhip_map_quality_timing(self.h, n, ms))
+        return {"k_quality_pairs": (n[0], ms[0]), "k_quality_units": (n[1], ms[1])}
+
     def device_alloc(self, nbytes):
         p = C.c_void_p()
         check(self.lib.somhip_device_alloc(self.h, nbytes, C.byref(p)))
@@ -376,6 +384,26 @@ def knn_vote(cb, ds, first=0, count=None, knn=5):
     out = [np.empty(count, dtype=np.int32) for _ in range(4)]
     check(cb.e.lib.somhip_knn_vote(cb.h, ds.h, first, count, knn, *[_p(a, _lib.c_i32_p) for a in out]))
     return tuple(out)
+
+
+def map_quality(cb, ds, first=0, count=None, hits=None, qsum=None, qerror=0.0):
+    """Topographic error and per-unit statistics of a map over data rows (first + s) % ds.n, s < count, formed on the
+    device behind the top-2 search (somhip_map_quality): (totals, hits, qsum).
+
+    totals: {"searched", "topo_defined", "topo_errors", "qerror"} -- the samples with an unmasked component, those with a
+    second-best unit, those whose best and second-best units are not lattice neighbours, and find_qerror's float sum
+    continued from `qerror`.  hits (uint32[cb.n]): samples won per unit; qsum (float64[cb.n]): the sum of their distances
+    in data order.  Arrays passed in are not changed: the returned ones continue them, so a run cut into several calls
+    (hits, qsum and totals["qerror"] handed on) gives the bits of one call."""
+    count = ds.n if count is None else count
+    hits = np.zeros(cb.n, dtype=np.uint32) if hits is None else np.array(hits, dtype=np.uint32)
+    qsum = np.zeros(cb.n, dtype=np.float64) if qsum is None else np.array(qsum, dtype=np.float64)
+    assert hits.shape == (cb.n,) and qsum.shape == (cb.n,)
+    tot = _lib.QualityTotals()
+    check(cb.e.lib.somhip_map_quality(cb.h, ds.h, first, count, _p(hits, _lib.c_u32_p), _p(qsum, _lib.c_double_p),
+                                      float(np.float32(qerror)), C.byref(tot)))
+    return ({"searched": tot.searched, "topo_defined": tot.topo_defined, "topo_errors": tot.topo_errors,
+             "qerror": np.float32(tot.qerror)}, hits, qsum)
 
 
 ROUTES = ("masked", "direct", "one_level", "two_level", "wide")

@@ -168,6 +168,11 @@ int som_training_mapset(struct teach_params *teach, float *rows, int n_maps, con
                         struct entries *testdata, float *qerror);
 float find_qerror(struct teach_params *teach);
 float find_qerror2(struct teach_params *teach);   /* qerror -qetype 1 (som_rout.c:823) */
+/* find_qerror's sum together with the topographic error and the per-unit statistics of the map (somhip_map_quality), the
+ * data taken `buffer` rows per engine call (<= 0: at once) with the same result.  hits / qsum: arrays of the codebook's
+ * entries, the caller's to free.  0, or 1 after a message. */
+struct map_quality { float qerror; long searched, topo_defined, topo_errors; uint32_t *hits; double *qsum; };
+int find_map_quality(struct teach_params *teach, long buffer, struct map_quality *q);
 /* winners of every data row (the scan behind compute_accuracy / find_labels) */
 int find_all_winners(struct teach_params *teach, int32_t *index, float *diff, int32_t *ret);
 /* the k nearest codes of every data row (knntest): k <= 8 */

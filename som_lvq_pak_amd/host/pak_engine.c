@@ -640,6 +640,29 @@ float find_qerror(struct teach_params *teach)                 /* som_rout.c:678-
   return qerror;
 }
 
+int find_map_quality(struct teach_params *teach, long buffer, struct map_quality *q)
+{
+  memset(q, 0, sizeof *q);
+  if (set_som_params(teach)) { fprintf(stderr, "find_map_quality: can't set SOM parameters\n"); return 1; }
+  const long n = teach->data->num_entries, noc = teach->codes->num_entries;
+  if (n <= 0) { fprintf(stderr, "find_map_quality: can't get data\n"); return 1; }
+  if (buffer <= 0 || buffer > n) buffer = n;
+  q->hits = calloc(noc + 1, sizeof *q->hits);
+  q->qsum = calloc(noc + 1, sizeof *q->qsum);
+  struct mirrors m;
+  int rc = mirrors_open(&m, teach->codes, 0, teach->data, 0);
+  for (long first = 0; !rc && first < n; first += buffer) {      /* hits, qsum and the float chain go from buffer to buffer */
+    somhip_quality_totals t;
+    rc = said(somhip_map_quality(m.cb, m.ds, first, buffer < n - first ? buffer : n - first, q->hits, q->qsum, q->qerror, &t));
+    if (rc) break;
+    q->qerror = t.qerror;
+    q->searched += t.searched; q->topo_defined += t.topo_defined; q->topo_errors += t.topo_errors;
+  }
+  mirrors_close(&m);
+  if (rc) { free(q->hits); free(q->qsum); q->hits = NULL; q->qsum = NULL; }
+  return rc;
+}
+
 float find_qerror2(struct teach_params *teach)                /* som_rout.c:823-885 */
 {
   if (set_som_params(teach)) { fprintf(stderr, "find_qerror2: can't set SOM parameters\n"); return -1; }

@@ -1,0 +1,65 @@
+/* somqual -- quality of a trained map on a data set: the quantization error (the qerror tool's own line), the
+ * topographic error (the share of samples whose best and second-best matching units are not neighbours on the lattice)
+ * and, per unit, how many samples it wins and their mean distance.  Everything is formed on the MI355X engine
+ * (somhip_map_quality); the host prints. */
+#include <stdlib.h>
+#include <string.h>
+#include "pak.h"
+
+static const char *usage =
+    "somqual - quantization error, topographic error and per-unit statistics of a map (MI355X engine)\n"
+    "Required:  -cin file  -din file (.dat, raw fp32 or gen:)\n"
+    "Optional:  -uout file (one line per unit: x y hits mean)  -buffer N (data rows per engine call)\n"
+    "           -selfuncs hip  -v level\n";
+
+int main(int argc, char **argv)
+{
+  struct teach_params teach;
+  struct pak_inputs io;
+  struct map_quality q;
+  memset(&teach, 0, sizeof teach);
+  global_options(argc, argv);
+  if (extract_parameter(argc, argv, "-help", OPTION2)) { fputs(usage, stdout); exit(0); }
+  char *din = extract_parameter(argc, argv, "-din", ALWAYS), *cin = extract_parameter(argc, argv, "-cin", ALWAYS);
+  char *uout = extract_parameter(argc, argv, "-uout", OPTION);
+  char *funcname = extract_parameter(argc, argv, "-selfuncs", OPTION);
+  long buffer = oatoi(extract_parameter(argc, argv, "-buffer", OPTION), 0);
+
+  pak_gen_virtual_ok = 1;                                /* a gen: source is generated in HBM, never on the host */
+  if (pak_open_inputs(din, 0, "Can't open data file '%s'\n", cin, 0, "Can't open code file '%s'\n", 2, &io)) exit(1);
+  if (io.codes->masks) {
+    fprintf(stderr, "somqual: codebook %s has masked components (x); the quality of masked codebooks is not supported\n", cin);
+    exit(1);
+  }
+  set_teach_params(&teach, io.codes, io.data, funcname);
+  if (find_map_quality(&teach, buffer, &q)) exit(1);
+  long nod = io.data->num_entries, noc = io.codes->num_entries, dead = 0;
+  ifverbose(1)
+    fprintf(stdout, "Quantization error of %s with map %s is %f per sample (%ld samples)\n", din, cin, q.qerror / (float)nod, nod);
+  else
+    fprintf(stdout, "%f\n", q.qerror / (float)nod);
+  if (q.topo_defined > 0)
+    fprintf(stdout, "Topographic error is %f (%ld of %ld samples)\n", (double)q.topo_errors / (double)q.topo_defined,
+            q.topo_errors, q.topo_defined);
+  else
+    fprintf(stdout, "Topographic error is undefined (0 of 0 samples)\n");
+  for (long u = 0; u < noc; u++) dead += q.hits[u] == 0;
+  fprintf(stdout, "%ld of %ld units were hit by no sample\n", dead, noc);
+  int rc = 0;
+  if (uout) {
+    FILE *fp = fopen(uout, "w");
+    if (!fp) { fprintf(stderr, "somqual: can't write %s\n", uout); rc = 1; }
+    else {
+      for (long u = 0; u < noc; u++) {
+        fprintf(fp, "%ld %ld %lu ", u % io.codes->xdim, u / io.codes->xdim, (unsigned long)q.hits[u]);
+        if (q.hits[u]) fprintf(fp, "%f\n", q.qsum[u] / (double)q.hits[u]);
+        else fprintf(fp, "0\n");
+      }
+      if (fclose(fp)) { fprintf(stderr, "somqual: can't write %s\n", uout); rc = 1; }
+    }
+  }
+  free(q.hits); free(q.qsum);
+  close_entries(io.data); close_entries(io.codes);
+  pak_shutdown();
+  return rc;
+}
