@@ -324,6 +324,48 @@ int  somhip_som_train(somhip_codebook *cb, somhip_dataset *ds, const somhip_som_
 int  somhip_som_auto_batch(const somhip_som_params *p, int64_t n_units, int topol, int neigh, int64_t iter,
                            int64_t *batch_start, int64_t *batch_len);
 
+/* ---- the batch map (K8; no reference function) -----------------------------------
+ * Kohonen's batch map: every epoch finds the winners of the whole data set against the frozen codebook and replaces
+ * every model vector by the neighbourhood-weighted mean of the data.  No learning rate, no dependence on the order of
+ * the data.  (batch > 1 of somhip_som_train is something else: mini-batches of the ONLINE rule.)
+ * One call runs epochs t = start_epoch .. start_epoch + count - 1 of a run of T = epochs epochs over data rows
+ * (first + s) % n_rows, s = 0 .. n-1.  Per epoch:
+ *   1. r_t = 1.0f + (radius - 1.0f) * (float)(T - t) / (float)T, in float (som_rout.c:615 with le -> t, length -> T)
+ *   2. c(s) = find_winner_euc of sample s against the codebook as the epoch found it: the lowest index among equal
+ *      distances (SOMHIP_TIE_FIRST)
+ *   3. hits[j] = the samples with c(s) = j (uint32); S[j][k] = the sum of (double)x_s[k] over them, ONE chain of fp64
+ *      additions from +0.0 in data order: the same bits on every run, no floating-point atomics
+ *   4. h(i, j) from the units' lattice positions with hexa_dist / rect_dist.  bubble: 1 where the online kernels'
+ *      membership test holds (bit-equal with dist <= r_t, som_rout.c:496), else 0; gaussian:
+ *      exp((double)(-dd * dd / (2.0 * r_t * r_t))), dd the float lattice distance (som_rout.c:808)
+ *   5. N[i][k] = sum_j h(i,j) S[j][k], D[i] = sum_j h(i,j) hits[j] in fp64 (v_mfma_f64_16x16x4_f64; the order over j is
+ *      the storage order of the rows, a function of the shape alone); m_i[k] = (float)(N[i][k] / D[i]) where D[i] > 0, a
+ *      row with D[i] == 0 keeps its bits
+ * qerror_out (host, [count], or NULL): per epoch the quantization error of the codebook the epoch started from, the
+ * float chain of find_qerror over the winners' distances in data order (as somhip_map_quality forms it).  NULL: no
+ * per-sample copy leaves the device.
+ * Refused, with a message that names the entry point, before anything is launched: data with x components, sharded
+ * codebooks, codebooks without a lattice, n >= 2^32, n <= 0, first < 0, epochs < 1, radius < 1, epochs outside
+ * [0, epochs).  Fixed points and weights are not taken. */
+typedef struct somhip_batchmap_params {
+  int64_t epochs;        /* T */
+  float   radius;        /* the radius the run starts from */
+  int64_t start_epoch, count;
+  int64_t first, n;      /* the data rows of every epoch */
+} somhip_batchmap_params;
+int  somhip_som_batchmap(somhip_codebook *cb, somhip_dataset *ds, const somhip_batchmap_params *p,
+                         float *qerror_out /*[count] or NULL*/);
+/* The two stages somhip_som_batchmap is made of, each on its own.  _sums: steps 2-3 -- hits[n_rows of the codebook],
+ * sums[n_rows][dim] to the host.  _combine: steps 4-5 at radius r (>= 0) on host-supplied hits and sums; it writes the
+ * codebook. */
+int  somhip_debug_batchmap_sums(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, uint32_t *hits,
+                                double *sums);
+int  somhip_debug_batchmap_combine(somhip_codebook *cb, float r, const uint32_t *hits, const double *sums);
+/* HIP-event totals of its stages since somhip_timing_reset, while somhip_timing_enable is on (not in the table of
+ * somhip_kernel_count): [0] group (the winners pass per chunk, the scan of the counts, the sort by winner), [1] the
+ * sums, [2] the combine (with the gaussian table) */
+int  somhip_batchmap_timing(somhip_engine *e, int64_t launches[3], double total_ms[3]);
+
 /* ---- map sets: many maps of one shape, trained at once ---------------------------
  * What vfind does: N maps that share shape, data and schedule and differ only in their initial rows.  The online
  * algorithm on ONE small map is one launch per iteration and the launch is the cost (a 12x8x5 map is one workgroup of

@@ -37,6 +37,11 @@ class QualityTotals(C.Structure):
     _fields_ = [("searched", C.c_int64), ("topo_defined", C.c_int64), ("topo_errors", C.c_int64), ("qerror", C.c_float)]
 
 
+class BatchmapParams(C.Structure):
+    _fields_ = [("epochs", C.c_int64), ("radius", C.c_float), ("start_epoch", C.c_int64), ("count", C.c_int64),
+                ("first", C.c_int64), ("n", C.c_int64)]
+
+
 # name -> (restype, argtypes); exactly the symbols include/somhip.h declares
 SIGNATURES = {
     "somhip_last_error": (C.c_char_p, []),
@@ -95,6 +100,10 @@ SIGNATURES = {
                                      C.POINTER(QualityTotals)]),
     "somhip_map_quality_timing": (C.c_int, [C.c_void_p, c_i64_p, c_double_p]),
     "somhip_som_train": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(SomParams), c_i32_p, c_float_p]),
+    "somhip_som_batchmap": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(BatchmapParams), c_float_p]),
+    "somhip_debug_batchmap_sums": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, c_u32_p, c_double_p]),
+    "somhip_debug_batchmap_combine": (C.c_int, [C.c_void_p, C.c_float, c_u32_p, c_double_p]),
+    "somhip_batchmap_timing": (C.c_int, [C.c_void_p, c_i64_p, c_double_p]),
     "somhip_mapset_create": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.POINTER(C.c_void_p)]),
     "somhip_mapset_download": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_float_p]),

@@ -87,9 +87,10 @@ static const char *kKernelNames[KID_COUNT] = {
 };
 // The table above is what somhip_kernel_count / somhip_kernel_name publish, and it is closed: callers index it and select
 // from it by bit.  Kernels added since are timed by LaunchTimer all the same, under ids that follow the table; an entry
-// point of their own reports them (somhip_mapset_timing, somhip_knn_timing, somhip_knn_vote_timing, somhip_map_quality_timing).
+// point of their own reports them (somhip_mapset_timing, somhip_knn_timing, somhip_knn_vote_timing, somhip_map_quality_timing,
+// somhip_batchmap_timing).
 enum TimedOnlyId { KID_MAPSET_TRAIN = KID_COUNT, KID_MAPSET_WINNERS, KID_KNN_DIST, KID_KNN_SELECT, KID_KNN_VOTE, KID_QUALITY_PAIRS,
-                   KID_QUALITY_UNITS, KID_TIMED };
+                   KID_QUALITY_UNITS, KID_BATCHMAP_GROUP, KID_BATCHMAP_SUMS, KID_BATCHMAP_COMBINE, KID_TIMED };
 static_assert(KID_TIMED <= 64, "somhip_timing_select's mask has one bit per kernel id");
 extern "C" int somhip_kernel_count(void) { return KID_COUNT; }
 extern "C" const char *somhip_kernel_name(int i) { return (i >= 0 && i < KID_COUNT) ? kKernelNames[i] : ""; }
@@ -150,6 +151,9 @@ enum ScratchSlot {
   SLOT_KNN_DIST,           // wide k-NN: the distances of a chunk of samples to every row, from the distance stage to the select
   SLOT_QUALITY,            // somhip_map_quality: the run's qsum, totals and hits, around the searches of its chunks (SLOT_CALL_A the
                            // chunk's keys, SLOT_CALL_B its per-sample terms, units and distances)
+  SLOT_BATCHMAP,           // the batch map (host_batchmap.inc): per unit -- the sums and counts, the gaussian table, hits and starts
+  SLOT_BATCHMAP_LIST,      // ... per sample -- winners, sample numbers, their sorted copies, the sort's room (SLOT_CALL_A the
+                           // chunk's keys, SLOT_CALL_B its distances)
   SLOT_COUNT
 };
 
@@ -812,3 +816,4 @@ extern "C" void somhip_dataset_destroy(somhip_dataset *ds) try {
 #include "host_umat.inc"
 #include "host_planes.inc"
 #include "host_quality.inc"
+#include "host_batchmap.inc"

@@ -138,6 +138,14 @@ class Engine:
         check(self.lib.somhip_map_quality_timing(self.h, n, ms))
         return {"k_quality_pairs": (n[0], ms[0]), "k_quality_units": (n[1], ms[1])}
 
+    def batchmap_timing(self):
+        """(launches, ms) of the batch map's stages while timing is on (somhip_batchmap_timing; they are not in
+        timing_table): group = the winners pass per chunk, the scan of the counts and the sort by winner"""
+        n = (C.c_int64 * 3)()
+        ms = (C.c_double * 3)()
+        check(self.lib.somhip_batchmap_timing(self.h, n, ms))
+        return {"group": (n[0], ms[0]), "k_batchmap_sums": (n[1], ms[1]), "k_batchmap_combine": (n[2], ms[2])}
+
     def device_alloc(self, nbytes):
         p = C.c_void_p()
         check(self.lib.somhip_device_alloc(self.h, nbytes, C.byref(p)))
@@ -501,6 +509,44 @@ def som_train(cb, ds, length, alpha, radius, alpha_type=ALPHA_LINEAR, use_fixed=
     td = np.empty(count, dtype=np.float32) if trace else None
     check(cb.e.lib.somhip_som_train(cb.h, ds.h, C.byref(p), _p(ti, _lib.c_i32_p), _p(td, _lib.c_float_p)))
     return ti, td
+
+
+def batchmap_radius(radius, epochs, t):
+    """r_t of epoch t of a batch-map run of `epochs` epochs from `radius`: the float the engine forms"""
+    f = np.float32
+    return f(f(1.0) + f(f(f(radius) - f(1.0)) * f(epochs - t)) / f(epochs))
+
+
+def som_batchmap(cb, ds, epochs, radius, start_epoch=0, count=None, first=0, n=None, qerror=True):
+    """Epochs [start_epoch, start_epoch + count) of Kohonen's batch map over data rows (first + s) % ds.n, s < n
+    (somhip_som_batchmap): every epoch replaces each model vector by the neighbourhood-weighted mean of the data at the
+    radius batchmap_radius(radius, epochs, t).  Returns float32[count], per epoch the quantization error (find_qerror's
+    float sum) of the codebook the epoch started from, or None with qerror=False (no per-sample copy leaves the device)."""
+    count = epochs - start_epoch if count is None else count
+    n = ds.n if n is None else n
+    p = _lib.BatchmapParams(epochs, radius, start_epoch, count, first, n)
+    q = np.zeros(max(count, 0), dtype=np.float32) if qerror else None
+    check(cb.e.lib.somhip_som_batchmap(cb.h, ds.h, C.byref(p), _p(q, _lib.c_float_p)))
+    return q
+
+
+def batchmap_sums(cb, ds, first=0, n=None):
+    """The first stage of a batch-map epoch alone (somhip_debug_batchmap_sums): (hits uint32[cb.n], sums float64[cb.n, dim])
+    -- per unit the samples it wins and the sum of their rows, one chain of fp64 additions in data order"""
+    n = ds.n if n is None else n
+    hits = np.zeros(cb.n, dtype=np.uint32)
+    sums = np.zeros((cb.n, cb.dim), dtype=np.float64)
+    check(cb.e.lib.somhip_debug_batchmap_sums(cb.h, ds.h, first, n, _p(hits, _lib.c_u32_p), _p(sums, _lib.c_double_p)))
+    return hits, sums
+
+
+def batchmap_combine(cb, r, hits, sums):
+    """The second stage alone (somhip_debug_batchmap_combine): the codebook's rows become the neighbourhood-weighted means
+    of `sums` over `hits` at radius r; a row whose neighbourhood holds no sample keeps its bits"""
+    hits = np.ascontiguousarray(hits, dtype=np.uint32)
+    sums = np.ascontiguousarray(sums, dtype=np.float64)
+    assert hits.shape == (cb.n,) and sums.shape == (cb.n, cb.dim)
+    check(cb.e.lib.somhip_debug_batchmap_combine(cb.h, float(np.float32(r)), _p(hits, _lib.c_u32_p), _p(sums, _lib.c_double_p)))
 
 
 def device_ptrs(cb, ds):

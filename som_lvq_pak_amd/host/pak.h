@@ -173,6 +173,10 @@ float find_qerror2(struct teach_params *teach);   /* qerror -qetype 1 (som_rout.
  * entries, the caller's to free.  0, or 1 after a message. */
 struct map_quality { float qerror; long searched, topo_defined, topo_errors; uint32_t *hits; double *qsum; };
 int find_map_quality(struct teach_params *teach, long buffer, struct map_quality *q);
+/* Kohonen's batch map (somhip_som_batchmap): `epochs` epochs over all of teach->data from teach->radius down to 1, the
+ * lattice and neighbourhood of teach->codes, whose vectors it replaces.  qerror: NULL, or [epochs] for the quantization error
+ * (find_qerror's sum) of the map every epoch started from.  0, or 1 after a message. */
+int som_batchmap_training(struct teach_params *teach, long epochs, float *qerror);
 /* winners of every data row (the scan behind compute_accuracy / find_labels) */
 int find_all_winners(struct teach_params *teach, int32_t *index, float *diff, int32_t *ret);
 /* the k nearest codes of every data row (knntest): k <= 8 */

@@ -663,6 +663,20 @@ int find_map_quality(struct teach_params *teach, long buffer, struct map_quality
   return rc;
 }
 
+int som_batchmap_training(struct teach_params *teach, long epochs, float *qerror)
+{
+  if (set_som_params(teach)) { fprintf(stderr, "som_batchmap_training: can't set SOM parameters\n"); return 1; }
+  if (teach->data->num_entries <= 0) { fprintf(stderr, "som_batchmap_training: can't get data\n"); return 1; }
+  struct mirrors m;
+  int rc = mirrors_open(&m, teach->codes, 0, teach->data, 0);
+  if (!rc) {
+    somhip_batchmap_params p = {epochs, teach->radius, 0, epochs, 0, teach->data->num_entries};
+    rc = said(somhip_som_batchmap(m.cb, m.ds, &p, qerror)) || said(somhip_codebook_download(m.cb, teach->codes->points));
+  }
+  mirrors_close(&m);
+  return rc;
+}
+
 float find_qerror2(struct teach_params *teach)                /* som_rout.c:823-885 */
 {
   if (set_som_params(teach)) { fprintf(stderr, "find_qerror2: can't set SOM parameters\n"); return -1; }
