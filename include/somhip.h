@@ -365,6 +365,36 @@ int  somhip_debug_batchmap_combine(somhip_codebook *cb, float r, const uint32_t 
  * somhip_kernel_count): [0] group (the winners pass per chunk, the scan of the counts, the sort by winner), [1] the
  * sums, [2] the combine (with the gaussian table) */
 int  somhip_batchmap_timing(somhip_engine *e, int64_t launches[3], double total_ms[3]);
+/* The same epoch over data that comes in pieces.  S[j][k] is a chain of additions, and a chain can be continued: where a
+ * piece's sums start from the S the pieces before it left instead of from +0.0, any cut of the data -- into buffers, into
+ * calls, into the row blocks of G ranks -- leaves the bits of one call.  Only the sums are serial across the pieces; the
+ * winner search runs per piece.
+ *   _begin       allocates, or re-zeroes, a state the codebook owns (not engine scratch: other engine calls between the
+ *                pieces leave it alone): [S | hits] as n_rows x (dim + 1) doubles, all +0.0, and a tail of 16 bytes
+ *                {float q; uint32 unused; uint64 samples}
+ *   _accumulate  steps 2-3 over rows (first + s) % n_rows, s < n, of ds, a data set of the codebook's engine and dimension
+ *                (the pieces may come from different data sets; each wraps inside its own): the chains go on from S, the
+ *                counts grow (exact in fp64); want_qerror: find_qerror's float chain goes on over the piece as well
+ *   _finish      steps 4-5 at radius r (>= 0) for the destination row groups (64 rows of the codebook's storage order)
+ *                [group_first, group_first + group_count) of (n_rows + 63) / 64; rows of other groups keep their bits.  It
+ *                reads S, not the rows, so it may be called again for other ranges; qerror_out (or NULL) gets the q chain.
+ *                After the first _finish further pieces are refused ("the codebook has moved") until the next _begin.
+ *   _end         frees the state (somhip_codebook_destroy does too)
+ *   _state       the device address and the size of the one blob that is the whole state -- the engine keeps nothing of
+ *                an accumulation on the host between calls.  Copied into another codebook of the same shape, on this or
+ *                another engine, whose own state _begin has opened, it continues the accumulation there.
+ * begin, accumulate over the pieces in order, finish(r, 0, ngroups, &q) leaves the codebook and q with the bits one epoch
+ * of somhip_som_batchmap at radius r leaves, over a data set whose rows are the pieces' rows in that order.
+ * Refused by name before anything is launched, codebook and state untouched: what somhip_som_batchmap refuses (masked
+ * data, sharded codebooks, codebooks without a lattice, n <= 0, first < 0); _accumulate / _finish / _state without _begin; a
+ * piece of another dimension; a piece that would take the total to 2^32 samples; r < 0; a group range outside
+ * [0, ngroups].  A call that writes the codebook's rows while a state is open (upload, the trainings,
+ * somhip_som_batchmap) closes the state.  The launches count under the three ids of somhip_batchmap_timing. */
+int  somhip_batchmap_begin(somhip_codebook *cb);
+int  somhip_batchmap_accumulate(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, int want_qerror);
+int  somhip_batchmap_finish(somhip_codebook *cb, float r, int64_t group_first, int64_t group_count, float *qerror_out);
+int  somhip_batchmap_end(somhip_codebook *cb);
+int  somhip_batchmap_state(somhip_codebook *cb, void **dev_state, int64_t *bytes);
 
 /* ---- map sets: many maps of one shape, trained at once ---------------------------
  * What vfind does: N maps that share shape, data and schedule and differ only in their initial rows.  The online
@@ -584,7 +614,23 @@ int  somhip_comm_allreduce_min_keys(somhip_comm *c, uint64_t *dev_keys, int64_t 
 int  somhip_comm_allreduce_min_f32(somhip_comm *c, float *dev_values, int64_t count);   /* the bounds of somhip_shard_winner_* */
 int  somhip_comm_allreduce_sum_u32(somhip_comm *c, uint32_t *dev_words, int64_t count);
 int  somhip_comm_allgather(somhip_comm *c, const void *dev_send, void *dev_recv, int64_t bytes_per_rank);
+/* dev_buf of rank root to every rank's dev_buf: ncclBroadcast on the engine's stream, or through rank 0's star */
+int  somhip_comm_broadcast(somhip_comm *c, void *dev_buf, int64_t bytes, int root);
 void somhip_comm_destroy(somhip_comm *c);
+/* The batch map (K8) with the DATA divided over the ranks: every rank holds the whole map (an ordinary codebook, the same
+ * rows on every rank) and its own block of the data; p->first / p->n select rows of the block, and a rank whose block is
+ * empty passes n == 0 (block is then not looked at).  Per epoch: (1) every rank runs the group stage -- the winner search,
+ * the expensive part -- on its block at the same time; (2) for root = 0 .. G-1, rank root continues the sums and the q chain
+ * (somhip_batchmap_accumulate's kernel) and the state blob is broadcast from it, so that after the last turn every rank
+ * holds the full state; (3) rank r runs the combine for its ceil(ngroups / G) consecutive row groups; (4) the ranks
+ * all-gather those groups' tiles.  Every rank ends every epoch with the same rows: bit for bit what somhip_som_batchmap
+ * leaves on one GPU over the blocks concatenated in rank order, and the same qerror_out (asked for on every rank or on
+ * none: the chain goes through all of them).  Refused before anything is launched: what somhip_som_batchmap refuses of the
+ * codebook, the epochs, the radius and (where n > 0) the block, a communicator of another engine, and -- on every rank
+ * alike, after one all-reduce of the counts -- blocks whose rows together number 2^32 or more.  An error later on (a peer
+ * that went away) may leave this rank's rows part-way through an epoch; the state is closed and freed on every way out. */
+int  somhip_som_batchmap_ranks(somhip_codebook *cb, somhip_dataset *block, const somhip_batchmap_params *p,
+                               somhip_comm *c, float *qerror_out /*[count] or NULL*/);
 
 /* ---- Sammon mapping of a codebook (SOM_PAK sammon.c) -------------------------------
  * The codebook is a whole one (no shard).  Mirrors carry no masks: a host whose codebook has masked components refuses

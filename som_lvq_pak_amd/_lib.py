@@ -104,6 +104,12 @@ SIGNATURES = {
     "somhip_debug_batchmap_sums": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, c_u32_p, c_double_p]),
     "somhip_debug_batchmap_combine": (C.c_int, [C.c_void_p, C.c_float, c_u32_p, c_double_p]),
     "somhip_batchmap_timing": (C.c_int, [C.c_void_p, c_i64_p, c_double_p]),
+    "somhip_batchmap_begin": (C.c_int, [C.c_void_p]),
+    "somhip_batchmap_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int]),
+    "somhip_batchmap_finish": (C.c_int, [C.c_void_p, C.c_float, C.c_int64, C.c_int64, c_float_p]),
+    "somhip_batchmap_end": (C.c_int, [C.c_void_p]),
+    "somhip_batchmap_state": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), c_i64_p]),
+    "somhip_som_batchmap_ranks": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(BatchmapParams), C.c_void_p, c_float_p]),
     "somhip_mapset_create": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.POINTER(C.c_void_p)]),
     "somhip_mapset_download": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_float_p]),
@@ -137,6 +143,7 @@ SIGNATURES = {
     "somhip_comm_allreduce_sum_u32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "somhip_comm_allreduce_min_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "somhip_comm_allgather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "somhip_comm_broadcast": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int]),
     "somhip_comm_destroy": (None, [C.c_void_p]),
     "somhip_som_batch_update": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(SomParams), C.c_int64,
                                           C.c_int64, C.c_int64, C.c_void_p]),

@@ -1,5 +1,7 @@
 // host_batchmap.inc -- K8, the batch map: per epoch the winners of every sample against the frozen codebook, the per-unit
-// ordered fp64 sums (stage 1) and the neighbourhood combine on the fp64 MFMA (stage 2)
+// ordered fp64 sums (stage 1) and the neighbourhood combine on the fp64 MFMA (stage 2); the same epoch over data in pieces
+// (somhip_batchmap_begin / _accumulate / _finish: the sums' chains continued from piece to piece) and over the row blocks
+// of G ranks (somhip_som_batchmap_ranks)
 // (included by somhip.hip: one translation unit, shared static helpers)
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -15,14 +17,15 @@ struct BatchmapBufs {
 static size_t batchmap_table_len(const somhip_codebook *cb) {
   return cb->v.neigh == SOMHIP_NEIGH_GAUSSIAN ? 2 * (size_t)(2 * cb->v.xdim - 1) * (size_t)(2 * cb->ydim - 1) : 0;
 }
-// n: the samples of a sums stage, 0 where only the combine runs
-static int batchmap_bind(somhip_codebook *cb, int64_t n, BatchmapBufs *b) {
+// n: the samples of a sums stage, 0 where only the combine runs.  state (or null): S is the codebook's own continued
+// accumulation, not engine scratch, and the slot holds the rest only.
+static int batchmap_bind(somhip_codebook *cb, int64_t n, BatchmapBufs *b, double *state = nullptr) {
   somhip_engine *e = cb->e;
-  const size_t units = (size_t)cb->v.n, ns = (size_t)n, s_len = units * (size_t)(cb->v.d + 1), t_len = batchmap_table_len(cb);
+  const size_t units = (size_t)cb->v.n, ns = (size_t)n, s_len = state ? 0 : units * (size_t)(cb->v.d + 1), t_len = batchmap_table_len(cb);
   void *p;
   CHK(engine_scratch(e, SLOT_BATCHMAP, sizeof(double) * (s_len + t_len) + sizeof(uint32_t) * (2 * units + 1), &p));
-  b->S = (double *)p;
-  b->table = b->S + s_len;
+  b->S = state ? state : (double *)p;
+  b->table = (double *)p + s_len;
   b->hits = reinterpret_cast<uint32_t *>(b->table + t_len);
   b->starts = b->hits + units;
   if (n <= 0) return 0;
@@ -39,27 +42,37 @@ static int batchmap_bind(somhip_codebook *cb, int64_t n, BatchmapBufs *b) {
   return 0;
 }
 
-// Stage 1 (steps 2-3 of the definition, include/somhip.h): b.S <- [S | hits], b.hits <- hits, of data rows (first + s) %
-// n_rows, s < n, against the codebook as it stands.  Per chunk (knn_chunk_keys with knn 1, SOMHIP_TIE_FIRST): the keys,
-// k_batchmap_winners behind them; then the scan, the stable sort by winner and the sums.  qerror (or null: no per-sample
-// copy leaves the device): find_qerror's float chain over the winners' distances in data order, as somhip_map_quality forms it.
-static int batchmap_sums_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, const BatchmapBufs &b, float *qerror) {
+// find_qerror's float chain over one sample's winner distance (d1 < 0: an empty vector, or one without a winner, as kept by
+// batchmap_group_stage)
+static inline void batchmap_q_step(float &q, float d1) { q += sqrt((double)d1); }   // float accumulator, som_rout.c:715
+
+// Stage 1 (steps 2-3 of the definition, include/somhip.h), the group half: the winners of data rows (first + s) % n_rows,
+// s < n, against the codebook as it stands, counted into b.hits and listed per unit in data order.  Per chunk
+// (knn_chunk_keys with knn 1, SOMHIP_TIE_FIRST): the keys, k_batchmap_winners behind them; then the scan and the stable
+// sort by winner.  q (or null: no per-sample copy leaves the device): find_qerror's float chain over the winners' distances
+// in data order, as somhip_map_quality forms it, continued from *q.  keep (with q): the chain is not run; the distances
+// it would take are kept in data order instead (-1 for a sample it skips), for a caller that learns where the chain
+// starts only later.
+static int batchmap_group_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, const BatchmapBufs &b, float *q,
+                                std::vector<float> *keep = nullptr) {
   somhip_engine *e = cb->e;
   const uint32_t units = (uint32_t)cb->v.n;
   HIPCHK(hipMemsetAsync(b.hits, 0, sizeof(uint32_t) * (size_t)units, e->stream));
-  float q = 0.0f;
+  float chain = q ? *q : 0.0f;
   std::vector<float> hd;
+  if (keep) keep->clear();
   CHK(knn_chunk_keys(cb, ds, first, n, 1, 0, [&](int64_t off, int64_t f, int64_t c, const uint64_t *dk, int stride) {
     float *dd1 = nullptr;
-    if (qerror) CHK(scratch(e, SLOT_CALL_B, (size_t)c, &dd1));
+    if (q) CHK(scratch(e, SLOT_CALL_B, (size_t)c, &dd1));
     CHK(LAUNCH_TIMED(e, KID_BATCHMAP_GROUP, k_batchmap_winners, dim3((unsigned)((c + BM_THREADS - 1) / BM_THREADS)), dim3(BM_THREADS), 0, dk,
         stride, off, c, units, b.win, b.idx, dd1, b.hits));
-    if (!qerror) return 0;
+    if (!q) return 0;
     if (hd.empty()) hd.resize((size_t)c);                               // (the first chunk is the longest)
     CHK(to_host_sync(e, hd.data(), dd1, (size_t)c));
     for (int64_t i = 0; i < c; i++) {
-      if (sample_is_empty(ds, (f + i) % ds->n)) continue;               // ignore empty vectors, som_rout.c:712
-      q += sqrt((double)hd[(size_t)i]);                                 // float accumulator, :715
+      const bool skip = sample_is_empty(ds, (f + i) % ds->n);           // ignore empty vectors, som_rout.c:712
+      if (keep) keep->push_back(skip ? -1.0f : hd[(size_t)i]);
+      else if (!skip) batchmap_q_step(chain, hd[(size_t)i]);
     }
     return 0;
   }));
@@ -70,27 +83,43 @@ static int batchmap_sums_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t 
     const hipError_t er = rocprim::radix_sort_pairs(b.sort_tmp, bytes, b.win, b.win_sorted, b.idx, b.list, (size_t)n, 0u, b.sort_bits, e->stream);
     if (er != hipSuccess) return fail("batch map: the sort by winner failed: %s", hipGetErrorString(er));
   }
-  CHK(LAUNCH_TIMED(e, KID_BATCHMAP_SUMS, k_batchmap_sums, dim3(units, (unsigned)((cb->v.d + 1 + BM_SUM_DIMS - 1) / BM_SUM_DIMS)), dim3(BM_SUM_DIMS), 0,
-      ds->d_rows, ds->n, ds->d, first % ds->n, b.list, b.starts, b.S));
-  if (qerror) *qerror = q;
+  if (q) *q = chain;
   return 0;
 }
+// ... and the sums half: b.S <- [S | hits] from the lists.  cont: the chains and counts go on from what b.S holds.
+static int batchmap_sums_launch(somhip_codebook *cb, somhip_dataset *ds, int64_t first, const BatchmapBufs &b, bool cont) {
+  somhip_engine *e = cb->e;
+  const dim3 grid((unsigned)cb->v.n, (unsigned)((cb->v.d + 1 + BM_SUM_DIMS - 1) / BM_SUM_DIMS));
+  if (cont)
+    return LAUNCH_TIMED(e, KID_BATCHMAP_SUMS, k_batchmap_sums<true>, grid, dim3(BM_SUM_DIMS), 0, ds->d_rows, ds->n, ds->d, first % ds->n, b.list,
+                        b.starts, b.S);
+  return LAUNCH_TIMED(e, KID_BATCHMAP_SUMS, k_batchmap_sums<false>, grid, dim3(BM_SUM_DIMS), 0, ds->d_rows, ds->n, ds->d, first % ds->n, b.list,
+                      b.starts, b.S);
+}
+static int batchmap_sums_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, const BatchmapBufs &b, float *qerror) {
+  if (qerror) *qerror = 0.0f;
+  CHK(batchmap_group_stage(cb, ds, first, n, b, qerror));
+  return batchmap_sums_launch(cb, ds, first, b, false);
+}
 
-// Stage 2 (steps 4-5): the codebook's rows <- (float)(N / D) from b.S at radius r, where D > 0.
-static int batchmap_combine_stage(somhip_codebook *cb, float r, const BatchmapBufs &b) {
+// Stage 2 (steps 4-5): the codebook's rows <- (float)(N / D) from b.S at radius r, where D > 0, for the destination row
+// groups [g0, g0 + groups) (groups < 0: all of them); rows of other groups keep their bits.
+static int batchmap_combine_stage(somhip_codebook *cb, float r, const BatchmapBufs &b, int64_t g0 = 0, int64_t groups = -1) {
   somhip_engine *e = cb->e;
   const bool gauss = cb->v.neigh == SOMHIP_NEIGH_GAUSSIAN;
   const int small_map = cb->v.xdim <= 1024 && cb->ydim <= 1024;         // (lattice_sq_small's condition)
-  const dim3 grid((unsigned)cb->v.ngroups, (unsigned)((cb->v.d + BM_COLS - 1) / BM_COLS));
+  if (groups < 0) groups = cb->v.ngroups;
+  if (groups == 0) return 0;
+  const dim3 grid((unsigned)groups, (unsigned)((cb->v.d + BM_COLS - 1) / BM_COLS));
   cb->prep_valid = false;
   if (gauss) {
     const size_t t_len = batchmap_table_len(cb);
     CHK(LAUNCH_TIMED(e, KID_BATCHMAP_COMBINE, k_batchmap_gauss_table, dim3((unsigned)((t_len + BM_THREADS - 1) / BM_THREADS)), dim3(BM_THREADS), 0,
         cb->v.topol, cb->v.xdim, cb->ydim, r, b.table));
-    return LAUNCH_TIMED(e, KID_BATCHMAP_COMBINE, k_batchmap_combine<true>, grid, dim3(256), 0, cb->v, cb->ydim, b.S, r, small_map, b.table);
+    return LAUNCH_TIMED(e, KID_BATCHMAP_COMBINE, k_batchmap_combine<true>, grid, dim3(256), 0, cb->v, cb->ydim, b.S, r, small_map, b.table, g0);
   }
   return LAUNCH_TIMED(e, KID_BATCHMAP_COMBINE, k_batchmap_combine<false>, grid, dim3(256), 0, cb->v, cb->ydim, b.S, bubble_threshold(r), small_map,
-                      nullptr);
+                      nullptr, g0);
 }
 
 // what every batch-map entry point refuses before anything is launched
@@ -121,6 +150,7 @@ extern "C" int somhip_som_batchmap(somhip_codebook *cb, somhip_dataset *ds, cons
                 (long long)p->epochs);
   somhip_engine *e = cb->e;
   HIPCHK(hipSetDevice(e->device));
+  cb->bm_open = false;                                                  // (the rows move: an open accumulation is over)
   BatchmapBufs b;
   CHK(batchmap_bind(cb, p->n, &b));
   const float T = (float)p->epochs;
@@ -157,6 +187,7 @@ extern "C" int somhip_debug_batchmap_combine(somhip_codebook *cb, float r, const
   if (!(r >= 0.0f)) return fail("somhip_debug_batchmap_combine: radius %g < 0", (double)r);
   somhip_engine *e = cb->e;
   HIPCHK(hipSetDevice(e->device));
+  cb->bm_open = false;
   BatchmapBufs b;
   CHK(batchmap_bind(cb, 0, &b));
   const size_t units = (size_t)cb->v.n, d = (size_t)cb->v.d;
@@ -182,3 +213,199 @@ extern "C" int somhip_batchmap_timing(somhip_engine *e, int64_t launches[3], dou
   for (int i = 0; i < 3; i++) { launches[i] = e->launches[kid[i]]; total_ms[i] = e->total_ms[kid[i]]; }
   return 0;
 } ABI_CATCH(somhip_batchmap_timing)
+
+// ---------------------------------------------------------------------------------
+// The epoch over data in pieces.  The state is one device blob the codebook owns: [S | counts] as units x (dim + 1)
+// doubles, then the tail -- find_qerror's float so far and the samples taken.  Nothing of an accumulation lives on the
+// host between calls, so the blob copied into another codebook of the same shape (its own state opened by _begin)
+// continues there: that is what hands a chain from rank to rank.
+// ---------------------------------------------------------------------------------
+struct BatchmapTail { float q; uint32_t unused; uint64_t samples; };
+static_assert(sizeof(BatchmapTail) == 16, "the tail of the batch map's state is two words of 8 bytes");
+static size_t batchmap_state_doubles(const somhip_codebook *cb) { return (size_t)cb->v.n * (size_t)(cb->v.d + 1); }
+static size_t batchmap_state_bytes(const somhip_codebook *cb) { return sizeof(double) * batchmap_state_doubles(cb) + sizeof(BatchmapTail); }
+static BatchmapTail *batchmap_tail(const somhip_codebook *cb) { return reinterpret_cast<BatchmapTail *>(cb->bm_state + batchmap_state_doubles(cb)); }
+
+// opens the state as all +0.0 (bits of zero throughout, the tail included)
+static int batchmap_state_open(somhip_codebook *cb) {
+  somhip_engine *e = cb->e;
+  if (!cb->bm_state) HIPCHK(hipMalloc((void **)&cb->bm_state, batchmap_state_bytes(cb)));
+  HIPCHK(hipMemsetAsync(cb->bm_state, 0, batchmap_state_bytes(cb), e->stream));
+  cb->bm_open = true;
+  cb->bm_moved = false;
+  return 0;
+}
+static int batchmap_check_open(const somhip_codebook *cb, const char *who) {
+  return cb->bm_open && cb->bm_state ? 0 : fail("%s: no accumulation is open on this codebook (somhip_batchmap_begin first; a call that writes "
+                                                 "the rows closes it)", who);
+}
+// The tail as the pieces so far left it, and the refusal of a piece of n samples that would take the total to 2^32: a copy
+// and a comparison, before anything is bound or launched.
+static int batchmap_read_tail(somhip_codebook *cb, int64_t n, const char *who, BatchmapTail *tail) {
+  CHK(to_host_sync(cb->e, tail, batchmap_tail(cb), 1));
+  if (tail->samples + (uint64_t)n >= (uint64_t)1 << 32)
+    return fail("%s: %llu + %lld samples do not fit the 32-bit hit counts", who, (unsigned long long)tail->samples, (long long)n);
+  return 0;
+}
+// One piece into the open state, whose tail the caller has just read: the chains, the counts and the tail go on, the tail
+// is written back.  dist (or null): the piece's group stage has run already (batchmap_group_stage with keep) and these are
+// its distances.
+static int batchmap_take_piece(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, const BatchmapBufs &b, bool want_q,
+                               const std::vector<float> *dist, BatchmapTail tail) {
+  somhip_engine *e = cb->e;
+  if (dist) { if (want_q) for (float d1 : *dist) if (!(d1 < 0.0f)) batchmap_q_step(tail.q, d1); }
+  else CHK(batchmap_group_stage(cb, ds, first, n, b, want_q ? &tail.q : nullptr));
+  CHK(batchmap_sums_launch(cb, ds, first, b, true));
+  tail.samples += (uint64_t)n;
+  CHK(to_device(e, batchmap_tail(cb), &tail, 1));
+  HIPCHK(hipStreamSynchronize(e->stream));                              // (tail is read until the copy has run)
+  return 0;
+}
+
+extern "C" int somhip_batchmap_begin(somhip_codebook *cb) try {
+  CHK(check_codebook(cb, true, "somhip_batchmap_begin"));
+  CHK(batchmap_check_codebook(cb, "somhip_batchmap_begin"));
+  HIPCHK(hipSetDevice(cb->e->device));
+  CHK(batchmap_state_open(cb));
+  HIPCHK(hipStreamSynchronize(cb->e->stream));
+  return 0;
+} ABI_CATCH(somhip_batchmap_begin)
+
+extern "C" int somhip_batchmap_accumulate(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, int want_qerror) try {
+  CHK(check_pair(cb, ds, "somhip_batchmap_accumulate"));
+  CHK(batchmap_check_codebook(cb, "somhip_batchmap_accumulate"));
+  CHK(batchmap_check_data(ds, first, n, "somhip_batchmap_accumulate"));
+  CHK(batchmap_check_open(cb, "somhip_batchmap_accumulate"));
+  if (cb->bm_moved) return fail("somhip_batchmap_accumulate: the codebook has moved (somhip_batchmap_finish has run; somhip_batchmap_begin opens the next epoch)");
+  somhip_engine *e = cb->e;
+  HIPCHK(hipSetDevice(e->device));
+  BatchmapTail tail;
+  CHK(batchmap_read_tail(cb, n, "somhip_batchmap_accumulate", &tail));  // (the last refusal: nothing is bound before it)
+  BatchmapBufs b;
+  CHK(batchmap_bind(cb, n, &b, cb->bm_state));
+  return batchmap_take_piece(cb, ds, first, n, b, want_qerror != 0, nullptr, tail);
+} ABI_CATCH(somhip_batchmap_accumulate)
+
+extern "C" int somhip_batchmap_finish(somhip_codebook *cb, float r, int64_t group_first, int64_t group_count, float *qerror_out) try {
+  CHK(check_codebook(cb, true, "somhip_batchmap_finish"));
+  CHK(batchmap_check_codebook(cb, "somhip_batchmap_finish"));
+  CHK(batchmap_check_open(cb, "somhip_batchmap_finish"));
+  if (!(r >= 0.0f)) return fail("somhip_batchmap_finish: radius %g < 0", (double)r);
+  if (group_first < 0 || group_count < 0 || group_first > cb->v.ngroups || group_count > cb->v.ngroups - group_first)
+    return fail("somhip_batchmap_finish: row groups [%lld, +%lld) outside [0, %lld]", (long long)group_first, (long long)group_count,
+                (long long)cb->v.ngroups);
+  somhip_engine *e = cb->e;
+  HIPCHK(hipSetDevice(e->device));
+  BatchmapBufs b;
+  CHK(batchmap_bind(cb, 0, &b, cb->bm_state));
+  if (group_count > 0) cb->bm_moved = true;                             // (an empty range writes no row)
+  CHK(batchmap_combine_stage(cb, r, b, group_first, group_count));
+  BatchmapTail tail{};
+  if (qerror_out) CHK(to_host(e, &tail, batchmap_tail(cb), 1));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  if (qerror_out) *qerror_out = tail.q;
+  return 0;
+} ABI_CATCH(somhip_batchmap_finish)
+
+extern "C" int somhip_batchmap_end(somhip_codebook *cb) try {
+  CHK(check_codebook(cb, true, "somhip_batchmap_end"));
+  somhip_engine *e = cb->e;
+  HIPCHK(hipSetDevice(e->device));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  if (cb->bm_state) HIPCHK(hipFree(cb->bm_state));
+  cb->bm_state = nullptr;
+  cb->bm_open = cb->bm_moved = false;
+  return 0;
+} ABI_CATCH(somhip_batchmap_end)
+
+extern "C" int somhip_batchmap_state(somhip_codebook *cb, void **dev_state, int64_t *bytes) try {
+  CHK(check_codebook(cb, dev_state && bytes, "somhip_batchmap_state"));
+  CHK(batchmap_check_open(cb, "somhip_batchmap_state"));
+  *dev_state = cb->bm_state;
+  *bytes = (int64_t)batchmap_state_bytes(cb);
+  return 0;
+} ABI_CATCH(somhip_batchmap_state)
+
+// The epochs of somhip_som_batchmap over the row blocks of the communicator's ranks, block by block in rank order.  Every
+// rank holds the whole map.  Per epoch: the group stage on every rank's own block at once (the search); then, rank after
+// rank, the continued sums and the q chain on the rank whose turn it is, and the state broadcast from it; the combine of
+// the rank's share of the row groups; an all-gather of the shares' tile ranges.
+extern "C" int somhip_som_batchmap_ranks(somhip_codebook *cb, somhip_dataset *block, const somhip_batchmap_params *p, somhip_comm *c,
+                                         float *qerror_out) try {
+  const char *who = "somhip_som_batchmap_ranks";
+  CHK(check_codebook(cb, p && c, who));
+  const bool empty = p->n == 0;                                          // a rank whose block holds no row: legal here and only here
+  if (!empty) CHK(check_pair(cb, block, who));
+  CHK(batchmap_check_codebook(cb, who));
+  if (!empty) CHK(batchmap_check_data(block, p->first, p->n, who));
+  if (c->e != cb->e) return fail("%s: codebook and communicator belong to different engines", who);
+  if (p->epochs < 1) return fail("%s: epochs %lld < 1", who, (long long)p->epochs);
+  if (!(p->radius >= 1.0f)) return fail("%s: radius %g < 1", who, (double)p->radius);
+  if (p->start_epoch < 0 || p->count < 0 || p->start_epoch + p->count > p->epochs)
+    return fail("%s: epochs [%lld, %lld) outside [0, %lld)", who, (long long)p->start_epoch, (long long)(p->start_epoch + p->count), (long long)p->epochs);
+  somhip_engine *e = cb->e;
+  HIPCHK(hipSetDevice(e->device));
+  const int64_t ngroups = cb->v.ngroups, share = (ngroups + c->world - 1) / c->world;
+  const int64_t g0 = std::min<int64_t>((int64_t)c->rank * share, ngroups), gn = std::min<int64_t>(share, ngroups - g0);
+  const size_t group_floats = (size_t)cb->v.d4 * WAVE * 4;              // a row group's tiles: one contiguous range of cb.tiles
+  struct Staging {
+    float *send = nullptr, *recv = nullptr;
+    uint32_t *words = nullptr;
+    ~Staging() { if (send) (void)hipFree(send); if (recv) (void)hipFree(recv); if (words) (void)hipFree(words); }
+  } st;
+  // The blocks' rows together must fit the 32-bit hit counts: every rank learns the total (summed as two 16-bit halves, so
+  // the words cannot overflow) and refuses alike, before any rank has launched anything.
+  HIPCHK(hipMalloc((void **)&st.words, 2 * sizeof(uint32_t)));
+  uint32_t halves[2] = {(uint32_t)(p->n >> 16), (uint32_t)(p->n & 0xffff)};
+  CHK(to_device(e, st.words, halves, 2));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  CHK(somhip_comm_allreduce_sum_u32(c, st.words, 2));
+  CHK(to_host_sync(e, halves, st.words, 2));
+  const uint64_t total = ((uint64_t)halves[0] << 16) + halves[1];
+  if (total >= (uint64_t)1 << 32) return fail("%s: the ranks' %llu samples do not fit the 32-bit hit counts", who, (unsigned long long)total);
+  HIPCHK(hipMalloc((void **)&st.send, sizeof(float) * group_floats * (size_t)share));
+  HIPCHK(hipMalloc((void **)&st.recv, sizeof(float) * group_floats * (size_t)share * (size_t)c->world));
+  HIPCHK(hipMemsetAsync(st.send, 0, sizeof(float) * group_floats * (size_t)share, e->stream));     // (the last share's padding)
+  auto epochs = [&]() -> int {
+    BatchmapBufs b;
+    std::vector<float> dist;
+    const float T = (float)p->epochs;
+    for (int64_t t = p->start_epoch; t < p->start_epoch + p->count; t++) {
+      const float r = 1.0f + (p->radius - 1.0f) * (float)(p->epochs - t) / T;
+      float *q = qerror_out ? qerror_out + (t - p->start_epoch) : nullptr;
+      CHK(batchmap_state_open(cb));
+      b = BatchmapBufs();
+      CHK(batchmap_bind(cb, p->n, &b, cb->bm_state));
+      float unused = 0.0f;
+      if (!empty) CHK(batchmap_group_stage(cb, block, p->first, p->n, b, q ? &unused : nullptr, &dist));
+      for (int root = 0; root < c->world; root++) {
+        if (root == c->rank && !empty) {
+          BatchmapTail tail;
+          CHK(batchmap_read_tail(cb, p->n, who, &tail));
+          CHK(batchmap_take_piece(cb, block, p->first, p->n, b, q != nullptr, &dist, tail));
+        }
+        CHK(somhip_comm_broadcast(c, cb->bm_state, (int64_t)batchmap_state_bytes(cb), root));
+      }
+      CHK(batchmap_combine_stage(cb, r, b, g0, gn));
+      if (gn > 0) CHK(on_device(e, st.send, cb->v.tiles + group_floats * (size_t)g0, group_floats * (size_t)gn));
+      CHK(somhip_comm_allgather(c, st.send, st.recv, (int64_t)(sizeof(float) * group_floats * (size_t)share)));
+      CHK(on_device(e, cb->v.tiles, st.recv, group_floats * (size_t)ngroups));   // (shares are consecutive: the gathered ranges are the tiles)
+      cb->prep_valid = false;
+      if (q) {
+        BatchmapTail tail;
+        CHK(to_host_sync(e, &tail, batchmap_tail(cb), 1));
+        *q = tail.q;
+      }
+    }
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return 0;
+  };
+  const int rc = epochs();
+  // The state was the epochs' own, on every way out: closed, so that no later _finish combines a state that was broadcast
+  // half way, and freed (units x (dim + 1) doubles are not kept for a codebook that may never accumulate again).
+  (void)hipStreamSynchronize(e->stream);
+  if (cb->bm_state) (void)hipFree(cb->bm_state);
+  cb->bm_state = nullptr;
+  cb->bm_open = cb->bm_moved = false;
+  return rc;
+} ABI_CATCH(somhip_som_batchmap_ranks)

@@ -23,6 +23,7 @@ struct RcclApi {
   ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
   ncclResult_t (*AllReduce)(const void *, void *, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
   ncclResult_t (*AllGather)(const void *, void *, size_t, ncclDataType_t, ncclComm_t, hipStream_t) = nullptr;
+  ncclResult_t (*Broadcast)(const void *, void *, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
   const char *(*GetErrorString)(ncclResult_t) = nullptr;
 };
 RcclApi g_rccl;
@@ -41,6 +42,7 @@ int rccl_load() {
   SYM(CommDestroy, "ncclCommDestroy");
   SYM(AllReduce, "ncclAllReduce");
   SYM(AllGather, "ncclAllGather");
+  SYM(Broadcast, "ncclBroadcast");
   SYM(GetErrorString, "ncclGetErrorString");
 #undef SYM
   g_rccl.so = so;
@@ -230,3 +232,31 @@ extern "C" int somhip_comm_allgather(somhip_comm *c, const void *dev_send, void 
   HIPCHK(hipStreamSynchronize(e->stream));
   return 0;
 } ABI_CATCH(somhip_comm_allgather)
+
+// dev_buf of rank `root` to every rank's dev_buf (the batch map's state going from rank to rank, host_batchmap.inc)
+extern "C" int somhip_comm_broadcast(somhip_comm *c, void *dev_buf, int64_t bytes, int root) try {
+  if (!c || !dev_buf) return fail("somhip_comm_broadcast: null argument");
+  if (root < 0 || root >= c->world) return fail("somhip_comm_broadcast: root %d of %d ranks", root, c->world);
+  if (bytes <= 0) return 0;
+  somhip_engine *e = c->e;
+  HIPCHK(hipSetDevice(e->device));
+  if (c->nccl) {
+    NCCLCHK(g_rccl.Broadcast(dev_buf, dev_buf, (size_t)bytes, ncclUint8, root, c->nccl, e->stream));
+    return 0;
+  }
+  if (c->world == 1) return 0;
+  // the star: the root's bytes reach rank 0, which passes them to every other rank
+  c->stage.resize((size_t)bytes);
+  if (c->rank == root) CHK(to_host_sync(e, c->stage.data(), static_cast<const uint8_t *>(dev_buf), c->stage.size()));
+  if (c->rank == 0) {
+    if (root != 0 && read_all(c->fds[(size_t)root - 1], c->stage.data(), c->stage.size())) return fail("somhip_comm: rank %d went away", root);
+    for (int r = 1; r < c->world; r++)
+      if (r != root && write_all(c->fds[(size_t)r - 1], c->stage.data(), c->stage.size())) return fail("somhip_comm: rank %d went away", r);
+  } else if (c->rank == root ? write_all(c->fds[0], c->stage.data(), c->stage.size()) : read_all(c->fds[0], c->stage.data(), c->stage.size()))
+    return fail("somhip_comm: rank 0 went away");
+  if (c->rank != root) {
+    CHK(to_device(e, static_cast<uint8_t *>(dev_buf), c->stage.data(), c->stage.size()));
+    HIPCHK(hipStreamSynchronize(e->stream));
+  }
+  return 0;
+} ABI_CATCH(somhip_comm_broadcast)

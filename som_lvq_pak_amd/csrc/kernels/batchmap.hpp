@@ -15,6 +15,7 @@ namespace somhip {
 //            (win, idx) by win (the host, rocPRIM) leaves list[]: the samples of unit u at list[starts[u] ..
 //            starts[u + 1]) in data order.
 //   sums     k_batchmap_sums: S[u][k] = one chain of fp64 additions from +0.0 over the unit's list, S[u][dim] = hits[u].
+//            k_batchmap_sums<true> continues the chains a piece of the data left in S (somhip_batchmap_accumulate).
 //   combine  k_batchmap_combine: [N | D] = H x [S | hits] on v_mfma_f64_16x16x4_f64, H generated per lane, then
 //            m_i[k] = (float)(N[i][k] / D[i]) into the codebook's tiles where D[i] > 0.
 //
@@ -75,6 +76,11 @@ __global__ __launch_bounds__(BM_SCAN_THREADS) void k_batchmap_starts(const uint3
 // of (double)x[k] over the unit's samples in data order (sample s is data row (first + s) % n_rows, first < n_rows);
 // S[u][d] = (double)hits[u].  S is [n_units][d + 1].  The list is known, so BM_SUM_AHEAD rows are loaded -- a wave reads
 // 256 contiguous bytes of each -- before their additions run in order.
+// CONT: the data come in pieces and S holds what the pieces before this one left (+0.0 and a count of 0.0 before the
+// first): the chain goes on from S[u][k] and the count grows by hits[u] (exact: an integer below 2^32 in fp64).  A chain
+// from a stored +0.0 is the chain from +0.0, so the pieces leave the bits of one call over their rows in order.  An
+// instantiation of its own: the one-call kernel keeps its code, with no load of S ahead of its chain.
+template <bool CONT>
 __global__ __launch_bounds__(BM_SUM_DIMS) void k_batchmap_sums(const float *__restrict__ rows, int64_t n_rows, int d,
                                                                int64_t first, const uint32_t *__restrict__ list,
                                                                const uint32_t *__restrict__ starts, double *__restrict__ S) {
@@ -83,13 +89,14 @@ __global__ __launch_bounds__(BM_SUM_DIMS) void k_batchmap_sums(const float *__re
   const uint32_t lo = starts[u], hi = starts[u + 1];
   if (k > d) return;
   double *out = S + static_cast<int64_t>(u) * (d + 1) + k;
-  if (k == d) { *out = static_cast<double>(hi - lo); return; }
+  if (k == d) { *out = CONT ? *out + static_cast<double>(hi - lo) : static_cast<double>(hi - lo); return; }
   auto row_of = [&](uint32_t i) {
     int64_t r = first + static_cast<int64_t>(list[i]);
     if (r >= n_rows) { r -= n_rows; if (r >= n_rows) r %= n_rows; }
     return r;
   };
-  double acc = 0.0;
+  if (CONT && lo == hi) return;                               // no sample of this piece: the chain stands
+  double acc = CONT ? *out : 0.0;
   uint32_t i = lo;
   for (; hi - i >= BM_SUM_AHEAD; i += BM_SUM_AHEAD) {
     float x[BM_SUM_AHEAD];
@@ -133,7 +140,7 @@ __device__ __forceinline__ void bm_group_box(const CbView &cb, int64_t g, int &x
   else { x0 = 0; x1 = cb.xdim - 1; }
 }
 
-// [N | D] = H x [S | hits] and the division, for the 64 rows of row group blockIdx.x and the columns
+// [N | D] = H x [S | hits] and the division, for the 64 rows of row group g0 + blockIdx.x and the columns
 // [blockIdx.y * BM_COLS, + BM_COLS) of a whole map: 4 waves, wave w the rows 16 w .. 16 w + 15, five 16 x 16 fp64
 // accumulator tiles each (four of numerators, one whose column 0 is D).  The source units come in storage order, a row
 // group (BM_TILE rows) per staged LDS tile, rows and columns past the end as zeros, the next tile's loads in flight in
@@ -145,12 +152,12 @@ __device__ __forceinline__ void bm_group_box(const CbView &cb, int64_t g, int &x
 // (float)(N / D) into the tiles where D > 0; it has read S only, so writing in place is safe.
 template <bool GAUSS>
 __global__ __launch_bounds__(256, 3) void k_batchmap_combine(CbView cb, int ydim, const double *__restrict__ S, float thresh,
-                                                          int small_map, const double *__restrict__ table) {
+                                                          int small_map, const double *__restrict__ table, int64_t g0) {
   __shared__ double s_b[BM_TILE * BM_LDS_COLS];
   __shared__ int2 s_xy[BM_TILE];
   const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid >> 6;
   const int kq = lane >> 4, cl = lane & 15;
-  const int64_t g = blockIdx.x;
+  const int64_t g = g0 + blockIdx.x;
   const int col0 = static_cast<int>(blockIdx.y) * BM_COLS;
   const int d = cb.d;
   const int64_t ld = d + 1;

@@ -510,6 +510,9 @@ struct somhip_codebook {
   float *d_rowmajor = nullptr;     // [ngroups*64][d] fp32 rows, row-major: what the exact re-rank of single rows gathers from (a row is
                                    // 4 d contiguous bytes here, 16 bytes per KiB in the tiles); written by the full k_prep_codes_bf16
   bool rowmajor_valid = false;     // ... and current only together with prep_valid and until a partial re-split (LVQ) clears it
+  double *bm_state = nullptr;      // the batch map's continued accumulation (host_batchmap.inc): [S | counts][the tail], the codebook's own
+  bool bm_open = false;            // ... opened by somhip_batchmap_begin; closed by _end and by every other writer of the rows
+  bool bm_moved = false;           // ... a _finish has written rows from it: no further piece until the next _begin
 };
 struct somhip_dataset {
   somhip_engine *e = nullptr;
@@ -546,6 +549,7 @@ static bool sample_is_empty(const somhip_dataset *ds, int64_t row) { return !ds-
 static int upload_rows(somhip_codebook *cb, const float *rows) {
   somhip_engine *e = cb->e;
   cb->prep_valid = false;
+  cb->bm_open = false;
   float *stage;
   const size_t count = (size_t)cb->v.n * cb->v.d;
   CHK(scratch(e, SLOT_STAGE, count, &stage));
@@ -670,6 +674,8 @@ static void codebook_release(somhip_codebook *cb) {
   cb->d_rowmajor = nullptr;
   if (cb->d_chi) (void)hipFree(cb->d_chi);
   if (cb->d_clo) (void)hipFree(cb->d_clo);
+  if (cb->bm_state) (void)hipFree(cb->bm_state);
+  cb->bm_state = nullptr; cb->bm_open = false;
   cb->v.tiles = nullptr;
   cb->d_labels = nullptr; cb->d_talpha = nullptr; cb->d_cn = nullptr; cb->d_cnmax = nullptr;
   cb->d_chi = cb->d_clo = nullptr;

@@ -154,6 +154,17 @@ class Engine:
     def device_free(self, p):
         check(self.lib.somhip_device_free(self.h, p))
 
+    def copy_to_host(self, addr, nbytes):
+        """uint8[nbytes] from device address addr (somhip_copy_to_host)"""
+        out = np.empty(nbytes, dtype=np.uint8)
+        check(self.lib.somhip_copy_to_host(self.h, out.ctypes.data_as(C.c_void_p), C.c_void_p(addr), nbytes))
+        return out
+
+    def copy_to_device(self, addr, data):
+        """the bytes of the array `data` to device address addr (somhip_copy_to_device)"""
+        data = np.ascontiguousarray(data)
+        check(self.lib.somhip_copy_to_device(self.h, C.c_void_p(addr), data.ctypes.data_as(C.c_void_p), data.nbytes))
+
     def __del__(self):
         try:
             self.close()
@@ -547,6 +558,41 @@ def batchmap_combine(cb, r, hits, sums):
     sums = np.ascontiguousarray(sums, dtype=np.float64)
     assert hits.shape == (cb.n,) and sums.shape == (cb.n, cb.dim)
     check(cb.e.lib.somhip_debug_batchmap_combine(cb.h, float(np.float32(r)), _p(hits, _lib.c_u32_p), _p(sums, _lib.c_double_p)))
+
+
+def batchmap_begin(cb):
+    """Opens, or re-zeroes, the codebook's continued accumulation of a batch-map epoch (somhip_batchmap_begin): the data
+    may then come in pieces, in order, and leave the bits of one som_batchmap epoch over the pieces' rows concatenated"""
+    check(cb.e.lib.somhip_batchmap_begin(cb.h))
+
+
+def batchmap_accumulate(cb, ds, first=0, n=None, qerror=True):
+    """One piece (somhip_batchmap_accumulate): rows (first + s) % ds.n, s < n, of ds continue the per-unit fp64 chains, the
+    counts and -- with qerror -- find_qerror's float chain"""
+    n = ds.n if n is None else n
+    check(cb.e.lib.somhip_batchmap_accumulate(cb.h, ds.h, first, n, 1 if qerror else 0))
+
+
+def batchmap_finish(cb, r, group_first=0, group_count=None, qerror=True):
+    """The combine at radius r from the accumulated state, for the destination row groups [group_first, + group_count) of
+    (cb.n + 63) // 64 (somhip_batchmap_finish; all of them by default).  Returns the q chain as a float, or None."""
+    group_count = (cb.n + 63) // 64 - group_first if group_count is None else group_count
+    q = np.zeros(1, dtype=np.float32) if qerror else None
+    check(cb.e.lib.somhip_batchmap_finish(cb.h, float(np.float32(r)), group_first, group_count, _p(q, _lib.c_float_p)))
+    return float(q[0]) if qerror else None
+
+
+def batchmap_end(cb):
+    """Frees the accumulation's state (somhip_batchmap_end)"""
+    check(cb.e.lib.somhip_batchmap_end(cb.h))
+
+
+def batchmap_state(cb):
+    """(device address, bytes) of the one blob that is the whole state (somhip_batchmap_state): [S | counts] as
+    float64[cb.n, dim + 1], then 16 bytes {float32 q, uint32 unused, uint64 samples}"""
+    addr, nbytes = C.c_void_p(), C.c_int64(0)
+    check(cb.e.lib.somhip_batchmap_state(cb.h, C.byref(addr), C.byref(nbytes)))
+    return int(addr.value), int(nbytes.value)
 
 
 def device_ptrs(cb, ds):

@@ -1,7 +1,9 @@
 /* bsom -- teach a self-organizing map with Kohonen's batch map on the MI355X engine (somhip_som_batchmap): every epoch
  * finds the winners of the whole data set against the frozen map and replaces every model vector by the
  * neighbourhood-weighted mean of the data, the radius going from -radius down to 1 over -epochs epochs.  No learning
- * rate; the result does not depend on the order of the data.  This project's own tool: SOM_PAK has none. */
+ * rate; the result does not depend on the order of the data.  This project's own tool: SOM_PAK has none.
+ * -buffer N takes the data through the engine N rows at a time and -gpus G divides its rows over G ranks; both leave the
+ * file and the -v lines of the plain run, byte for byte (the sums' chains are continued, include/somhip.h). */
 #include <stdlib.h>
 #include <string.h>
 #include "pak.h"
@@ -10,8 +12,25 @@ static const char *usage =
     "bsom - teach self-organizing map, batch map (MI355X engine)\n"
     "Required:  -cin file  -din file  -cout file  -epochs T  -radius R\n"
     "Optional:  -v (one line per epoch to stdout: epoch, radius, quantization error before it)\n"
+    "           -buffer N (the device holds N data rows at a time; same result)\n"
+    "           -gpus G (one process per GPU, the data's rows divided over them; same result; not with -buffer;\n"
+    "                    SOMHIP_COMM=rccl|sockets in the environment names the ranks' transport and, as with vsom,\n"
+    "                    sends even one rank through it)\n"
     "Topology and neighbourhood come from the codebook's header.\n"
     "Files:     text (.dat/.cod), raw fp32 (a name ending in .f32; see datconv), or -din gen:k=..,dim=..,n=..,seed=..\n";
+
+/* what the run ends with, on the one process or on rank 0: the -v lines, then the codebook */
+struct bsom_out { const char *cout; long epochs; float radius; float *qerror; };
+static int save_codes(struct teach_params *teach, void *arg)
+{
+  struct bsom_out *o = arg;
+  for (long t = 0; o->qerror && t < o->epochs; t++) {
+    const float r = 1.0f + (o->radius - 1.0f) * (float)(o->epochs - t) / (float)o->epochs;   /* the engine's r_t */
+    fprintf(stdout, "epoch %ld radius %.9g qerror %.9g\n", t, (double)r, (double)o->qerror[t]);
+  }
+  ifverbose(2) fprintf(stderr, "Codebook entries are saved to file %s\n", o->cout);
+  return save_entries(teach->codes, (char *)o->cout) ? 1 : 0;
+}
 
 int main(int argc, char **argv)
 {
@@ -31,6 +50,12 @@ int main(int argc, char **argv)
   float radius = (float)atof(extract_parameter(argc, argv, "-radius", ALWAYS));
   if (epochs < 1) { fprintf(stderr, "bsom: -epochs %ld < 1\n", epochs); exit(1); }
   if (!(radius >= 1.0f)) { fprintf(stderr, "bsom: -radius %g < 1\n", (double)radius); exit(1); }
+  char *buffer_s = extract_parameter(argc, argv, "-buffer", OPTION), *gpus_s = extract_parameter(argc, argv, "-gpus", OPTION);
+  long buffer = oatoi(buffer_s, 0);
+  int gpus = (int)oatoi(gpus_s, 1);
+  if (buffer < 0) { fprintf(stderr, "bsom: -buffer %ld < 0\n", buffer); exit(1); }
+  if (gpus < 1 || gpus > 64) { fprintf(stderr, "bsom: -gpus %d outside 1 .. 64\n", gpus); exit(1); }
+  if (gpus_s && buffer_s) { fprintf(stderr, "bsom: -gpus together with -buffer is not available (give one of the two)\n"); exit(1); }
 
   pak_gen_virtual_ok = 1;                                /* a gen: source is generated in HBM, never on the host */
   if (pak_open_inputs(din, 0, "cant open data file '%s'\n", cin, 0, "Can't open code file '%s'\n", 1, &io)) goto end;
@@ -39,14 +64,11 @@ int main(int argc, char **argv)
   set_teach_params(&params, io.codes, io.data, NULL);
   params.radius = radius;
   float *qerror = lines ? calloc((size_t)epochs, sizeof *qerror) : NULL;
-  if (!som_batchmap_training(&params, epochs, qerror)) {
-    for (long t = 0; qerror && t < epochs; t++) {
-      const float r = 1.0f + (radius - 1.0f) * (float)(epochs - t) / (float)epochs;   /* the engine's r_t */
-      fprintf(stdout, "epoch %ld radius %.9g qerror %.9g\n", t, (double)r, (double)qerror[t]);
-    }
-    ifverbose(2) fprintf(stderr, "Codebook entries are saved to file %s\n", cout);
-    error = save_entries(io.codes, cout) ? 1 : 0;
-  }
+  struct bsom_out out = {cout, epochs, radius, qerror};
+  if (!buffer_s && (gpus > 1 || getenv("SOMHIP_COMM")))  /* the ranks train, as in vsom; rank 0 prints and saves */
+    error = som_batchmap_training_multi(&params, epochs, qerror, gpus, save_codes, &out);
+  else if (!som_batchmap_training(&params, epochs, buffer, qerror))
+    error = save_codes(&params, &out);
   free(qerror);
 end:
   close_entries(io.data);

@@ -175,8 +175,15 @@ struct map_quality { float qerror; long searched, topo_defined, topo_errors; uin
 int find_map_quality(struct teach_params *teach, long buffer, struct map_quality *q);
 /* Kohonen's batch map (somhip_som_batchmap): `epochs` epochs over all of teach->data from teach->radius down to 1, the
  * lattice and neighbourhood of teach->codes, whose vectors it replaces.  qerror: NULL, or [epochs] for the quantization error
- * (find_qerror's sum) of the map every epoch started from.  0, or 1 after a message. */
-int som_batchmap_training(struct teach_params *teach, long epochs, float *qerror);
+ * (find_qerror's sum) of the map every epoch started from.  0, or 1 after a message.
+ * buffer > 0: per epoch the data goes through the engine `buffer` rows at a time (somhip_batchmap_begin / _accumulate /
+ * _finish), each piece a data set of its own -- uploaded, or generated in place for a gen: source -- that is destroyed
+ * once it is taken: the device never holds more than `buffer` rows, and the result is the same, bit for bit. */
+int som_batchmap_training(struct teach_params *teach, long epochs, long buffer, float *qerror);
+/* bsom -gpus G: the data's rows in G blocks, one per rank, every rank the whole map (somhip_som_batchmap_ranks); rank 0
+ * ends with the map in teach->codes and the epochs' qerror in qerror ([epochs]) and runs after(teach, arg) -- print, save */
+int som_batchmap_training_multi(struct teach_params *teach, long epochs, float *qerror, int gpus,
+                                int (*after)(struct teach_params *, void *), void *arg);
 /* winners of every data row (the scan behind compute_accuracy / find_labels) */
 int find_all_winners(struct teach_params *teach, int32_t *index, float *diff, int32_t *ret);
 /* the k nearest codes of every data row (knntest): k <= 8 */

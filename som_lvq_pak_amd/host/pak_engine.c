@@ -663,16 +663,50 @@ int find_map_quality(struct teach_params *teach, long buffer, struct map_quality
   return rc;
 }
 
-int som_batchmap_training(struct teach_params *teach, long epochs, float *qerror)
+/* the rows [first, first + count) of data as a device data set of their own: uploaded, or generated in place */
+somhip_dataset *pak_mirror_data_rows(struct entries *data, long first, long count)
+{
+  somhip_engine *en = pak_engine();
+  if (!en) return NULL;
+  somhip_dataset *ds = NULL;
+  const long dim = data->dimension;
+  int rc = data->is_virtual ? somhip_dataset_generate(en, data->gen_seed, data->gen_k, (int)dim, first, count, NULL, &ds)
+                            : somhip_dataset_create(en, data->points + first * dim, count, (int)dim,
+                                                    data->masks ? (const uint8_t *)data->masks + first * dim : NULL, NULL, NULL, NULL, &ds);
+  return said(rc) ? NULL : ds;
+}
+
+int som_batchmap_training(struct teach_params *teach, long epochs, long buffer, float *qerror)
 {
   if (set_som_params(teach)) { fprintf(stderr, "som_batchmap_training: can't set SOM parameters\n"); return 1; }
-  if (teach->data->num_entries <= 0) { fprintf(stderr, "som_batchmap_training: can't get data\n"); return 1; }
-  struct mirrors m;
-  int rc = mirrors_open(&m, teach->codes, 0, teach->data, 0);
-  if (!rc) {
-    somhip_batchmap_params p = {epochs, teach->radius, 0, epochs, 0, teach->data->num_entries};
-    rc = said(somhip_som_batchmap(m.cb, m.ds, &p, qerror)) || said(somhip_codebook_download(m.cb, teach->codes->points));
+  const long n = teach->data->num_entries;
+  if (n <= 0) { fprintf(stderr, "som_batchmap_training: can't get data\n"); return 1; }
+  struct mirrors m = {NULL, NULL};
+  int rc;
+  if (buffer <= 0) {
+    rc = mirrors_open(&m, teach->codes, 0, teach->data, 0);
+    if (!rc) {
+      somhip_batchmap_params p = {epochs, teach->radius, 0, epochs, 0, n};
+      rc = said(somhip_som_batchmap(m.cb, m.ds, &p, qerror)) || said(somhip_codebook_download(m.cb, teach->codes->points));
+    }
+    mirrors_close(&m);
+    return rc;
   }
+  /* the epoch over pieces: the sums' chains go on from piece to piece, so any cut gives the bits of one call */
+  const long ngroups = (teach->codes->num_entries + 63) / 64;
+  rc = !(m.cb = pak_mirror_codes(teach->codes, 0));
+  for (long t = 0; !rc && t < epochs; t++) {
+    const float r = 1.0f + (teach->radius - 1.0f) * (float)(epochs - t) / (float)epochs;   /* the engine's r_t */
+    rc = said(somhip_batchmap_begin(m.cb));
+    for (long first = 0; !rc && first < n; first += buffer) {
+      const long c = buffer < n - first ? buffer : n - first;
+      somhip_dataset *piece = pak_mirror_data_rows(teach->data, first, c);
+      rc = !piece || said(somhip_batchmap_accumulate(m.cb, piece, 0, c, qerror != NULL));
+      if (piece) somhip_dataset_destroy(piece);
+    }
+    if (!rc) rc = said(somhip_batchmap_finish(m.cb, r, 0, ngroups, qerror ? qerror + t : NULL));
+  }
+  if (!rc) rc = said(somhip_batchmap_end(m.cb)) || said(somhip_codebook_download(m.cb, teach->codes->points));
   mirrors_close(&m);
   return rc;
 }

@@ -1,5 +1,5 @@
 /* pak_ranks.c -- the multi-process side of the tools' host library: the fork/socketpair rank launcher with its kill
- * logic, and the drivers of `vsom -gpus G` and `lvqtrain -gpus G` that run in every rank. */
+ * logic, and the drivers of `vsom -gpus G`, `lvqtrain -gpus G` and `bsom -gpus G` that run in every rank. */
 #define _GNU_SOURCE
 #include "pak_int.h"
 
@@ -387,4 +387,58 @@ int lvq_training_multi(struct teach_params *teach, int kind, float winlen, float
   if (pak_check_inputs(teach, "lvq training", PAK_CHECK_RANKS)) return 1;
   struct lvq_multi m = { teach, kind, winlen, epsilon, clamp, talpha, after, arg };
   return pak_run_ranks(gpus, lvq_training_rank, &m);
+}
+
+/* ------------------------------------------------------------------ the batch map on G GPUs (bsom -gpus G)
+ * The DATA is cut into contiguous row blocks, one per rank; every rank holds the whole map.  somhip_som_batchmap_ranks
+ * runs the epochs: the winner search of every block at the same time, the ordered sums rank after rank with the state
+ * broadcast in between, the combine divided by row groups.  Every rank ends with the same map; rank 0 returns it. */
+struct bsom_multi { struct teach_params *teach; long epochs; float *qerror; int (*after)(struct teach_params *, void *); void *arg; };
+
+static int batchmap_training_rank(int rank, int world, int *fds, void *pp)
+{
+  struct bsom_multi *m = pp;
+  struct entries *codes = m->teach->codes, *data = m->teach->data;
+  long r0, r1;
+  rank_block(data->num_entries, world, rank, &r0, &r1);
+  int ndev = 0, rc = 1;
+  somhip_comm *comm = NULL;
+  somhip_codebook *cb = NULL;
+  somhip_dataset *ds = NULL;
+  float *q = calloc((size_t)m->epochs + 1, sizeof *q);      /* every rank asks for it: the chain goes through all of them */
+  if (pak_rank_device(rank) < 0 || somhip_device_count(&ndev)) { free(q); return 1; }
+  somhip_engine *en = pak_engine();
+  if (!en) { free(q); return 1; }
+  int use_rccl;
+  const int no_comm = rank_comm_open(en, rank, world, ndev, fds, &comm, &use_rccl);
+  if (no_comm > 0) goto hip_fail;
+  if (no_comm) goto done;
+  ifverbose(2) fprintf(stderr, "rank %d/%d on GPU %d, data rows [%ld, %ld), state by %s\n", rank, world, pak_device, r0, r1,
+                       use_rccl ? "RCCL" : "host sockets");
+  if (!(cb = pak_mirror_codes(codes, 0))) goto done;
+  if (r1 > r0 && !(ds = pak_mirror_data_rows(data, r0, r1 - r0))) goto done;
+  somhip_batchmap_params p = { m->epochs, m->teach->radius, 0, m->epochs, 0, r1 - r0 };
+  if (somhip_som_batchmap_ranks(cb, ds, &p, comm, q)) goto hip_fail;
+  if (rank == 0) {
+    if (somhip_codebook_download(cb, codes->points)) goto hip_fail;
+    if (m->qerror) memcpy(m->qerror, q, sizeof *q * (size_t)m->epochs);
+    rc = m->after ? m->after(m->teach, m->arg) : 0;
+  } else rc = 0;
+  goto done;
+hip_fail:
+  fprintf(stderr, "som_batchmap_training (rank %d): %s\n", rank, somhip_last_error());
+done:
+  if (ds) somhip_dataset_destroy(ds);
+  if (cb) somhip_codebook_destroy(cb);
+  if (comm) somhip_comm_destroy(comm);
+  free(q);
+  return rc;
+}
+
+int som_batchmap_training_multi(struct teach_params *teach, long epochs, float *qerror, int gpus,
+                                int (*after)(struct teach_params *, void *), void *arg)
+{
+  if (pak_check_inputs(teach, "som_batchmap_training", PAK_CHECK_SOM | PAK_CHECK_RANKS)) return 1;
+  struct bsom_multi m = { teach, epochs, qerror, after, arg };
+  return pak_run_ranks(gpus, batchmap_training_rank, &m);
 }

@@ -15,8 +15,21 @@ Derived figures, computed here from the shapes:
            is used (half the guide's 157.3 TFLOP/s fp32 matrix rate)
 
 --parent-lib PATH: also times somhip_som_train at batch auto over the same number of vectors with that library (the parent
-commit's, built from a clean checkout of it), in a child process that loads it through SOMHIP_LIB."""
+commit's, built from a clean checkout of it), in a child process that loads it through SOMHIP_LIB.
+
+--pieces: the report on the epoch over data in pieces (somhip_batchmap_begin / _accumulate / _finish).
+  one call   somhip_som_batchmap, one bubble epoch per shape at the first radius, in child processes that alternate between
+             the library under --parent-lib and this commit's, `--rounds` of each: per child a warm-up call, `--reps` calls
+             on the host clock with events off, `--reps` with the stage events on.  Reported: every child's medians, the
+             spread of the parent's children among themselves (largest less smallest median) and this commit's median
+             of medians less the parent's.
+  pieces     this commit, the same epoch through begin / accumulate x k / finish for k = 1, 4, 16 equal pieces, timed the
+             same way; the rows are compared with the one call's by bit pattern before any time is printed.
+  the tool   `bsom` end to end (process start to exit, the host clock of this script) on a gen: source, without -buffer and
+             with -buffer at a quarter and a sixteenth of the rows; with two or more devices also -gpus 2 and -gpus <all>.
+  ranks      the bytes one epoch broadcasts, computed from the shapes: G times the state."""
 import argparse
+import ctypes as C
 import json
 import os
 import statistics
@@ -148,6 +161,138 @@ def measure_online(E, eng, reps, shapes, out, who):
         cb.close(); ds.close()
 
 
+def onecall_child(E, eng, reps, shapes, who):
+    """one bubble epoch per shape at its first radius: a JSON line per shape"""
+    for xdim, ydim, dim, n, radii in shapes:
+        units = xdim * ydim
+        ds = E.Dataset(eng, generate=(9, 16, dim, 0, n))
+        codes = E.gen_rows(9, 16, dim, n, units)[0]
+        cb = E.Codebook(eng, codes, E.TOPOL_HEXA, E.NEIGH_BUBBLE, xdim, ydim)
+
+        def epoch(events):
+            cb.upload(codes)
+            eng.timing(events)
+            eng.timing_reset()
+            eng.sync()
+            t0 = time.perf_counter()
+            E.som_batchmap(cb, ds, 1, radii[0], qerror=False)
+            wall = (time.perf_counter() - t0) * 1e3
+            st = eng.batchmap_timing() if events else None
+            eng.timing(False)
+            return wall, st
+        epoch(False)
+        walls = [epoch(False)[0] for _ in range(reps)]
+        timed = [epoch(True)[1] for _ in range(reps)]
+        print("JSON " + json.dumps({"who": who, "shape": [xdim, ydim, dim, n], "walls": walls,
+                                    "group": [t["group"][1] for t in timed], "sums": [t["k_batchmap_sums"][1] for t in timed],
+                                    "combine": [t["k_batchmap_combine"][1] for t in timed]}), flush=True)
+        cb.close(); ds.close()
+
+
+def pieces_report(E, a, shapes, out):
+    me = os.path.abspath(__file__)
+    small = ["--small"] if a.small else []
+    runs = {}
+    order = (["parent", "this"] if a.parent_lib else ["this"]) * a.rounds
+    for who in order:
+        env = dict(os.environ)
+        if who == "parent":
+            env["SOMHIP_LIB"] = os.path.abspath(a.parent_lib)
+        p = subprocess.run([sys.executable, me, "--onecall-only", who, "--reps", str(a.reps)] + small, env=env, stdout=subprocess.PIPE,
+                           text=True, check=True, timeout=600)
+        for s in p.stdout.split("\n"):
+            if s.startswith("JSON "):
+                r = json.loads(s[5:])
+                runs.setdefault(tuple(r["shape"]), []).append(r)
+    out("== one call (somhip_som_batchmap, one bubble epoch, events off for the wall, on for the stages), children alternating")
+    for shape, rs in runs.items():
+        out("  %d x %d x %d over %d vectors" % shape)
+        meds = {"parent": [], "this": []}
+        for r in rs:
+            meds[r["who"]].append(med(r["walls"]))
+            out("    %-6s wall ms median %.3f of %s | group %.3f sums %.3f combine %.3f"
+                % (r["who"], med(r["walls"]), fmt(r["walls"]), med(r["group"]), med(r["sums"]), med(r["combine"])))
+        if meds["parent"]:
+            spread = max(meds["parent"]) - min(meds["parent"])
+            diff = med(meds["this"]) - med(meds["parent"])
+            out("    parent's children among themselves: spread %.3f ms; this commit less the parent: %+.3f ms (%+.2f %%)"
+                % (spread, diff, 100 * diff / med(meds["parent"])))
+    eng = E.Engine(0)
+    out("== this commit: the same epoch through begin / accumulate x k / finish")
+    for xdim, ydim, dim, n, radii in shapes:
+        units = xdim * ydim
+        ds = E.Dataset(eng, generate=(9, 16, dim, 0, n))
+        codes = E.gen_rows(9, 16, dim, n, units)[0]
+        cb = E.Codebook(eng, codes, E.TOPOL_HEXA, E.NEIGH_BUBBLE, xdim, ydim)
+        E.som_batchmap(cb, ds, 1, radii[0], qerror=False)
+        want = cb.download()
+        r0 = E.batchmap_radius(radii[0], 1, 0)
+        out("  %d x %d x %d over %d vectors, radius %g" % (xdim, ydim, dim, n, radii[0]))
+        for k in (1, 4, 16):
+            per = (n + k - 1) // k
+
+            def epoch(events):
+                cb.upload(codes)
+                eng.timing(events)
+                eng.timing_reset()
+                eng.sync()
+                t0 = time.perf_counter()
+                E.batchmap_begin(cb)
+                for first in range(0, n, per):
+                    E.batchmap_accumulate(cb, ds, first, min(per, n - first), qerror=False)
+                E.batchmap_finish(cb, r0, qerror=False)
+                wall = (time.perf_counter() - t0) * 1e3
+                st = eng.batchmap_timing() if events else None
+                eng.timing(False)
+                return wall, st
+            epoch(False)
+            assert np.array_equal(cb.download().view(np.uint32), want.view(np.uint32)), "pieces differ from the one call"
+            walls = [epoch(False)[0] for _ in range(a.reps)]
+            timed = [epoch(True)[1] for _ in range(a.reps)]
+            out("    %2d pieces: wall ms median %.3f of %s | group %.3f (%d launches) sums %.3f combine %.3f"
+                % (k, med(walls), fmt(walls), med([t["group"][1] for t in timed]), timed[0]["group"][0],
+                   med([t["k_batchmap_sums"][1] for t in timed]), med([t["k_batchmap_combine"][1] for t in timed])))
+        E.batchmap_end(cb)
+        cb.close(); ds.close()
+    eng.close()
+    # the tool, end to end
+    import tempfile
+    from som_lvq_pak_amd import _lib, textio
+    bsom = os.path.join(ROOT, "som_lvq_pak_amd", "host", "bin", "bsom")
+    xdim, ydim, dim, n, radii = shapes[-1]
+    ndev = C.c_int(0)
+    _lib.load().somhip_device_count(C.byref(ndev))
+    with tempfile.TemporaryDirectory() as tmp:
+        m = textio.Entries()
+        m.dim, m.topol, m.neigh, m.xdim, m.ydim = dim, E.TOPOL_HEXA, E.NEIGH_BUBBLE, xdim, ydim
+        m.points = E.gen_rows(9, 16, dim, n, xdim * ydim)[0]
+        cod = os.path.join(tmp, "m.cod")
+        textio.write_entries(cod, m)
+        src = "gen:k=16,dim=%d,n=%d,seed=9" % (dim, n)
+        out("== bsom end to end, %d x %d x %d, -din %s, 4 epochs from radius %g (process start to exit)" % (xdim, ydim, dim, src, radii[0]))
+        variants = [[], ["-buffer", str((n + 3) // 4)], ["-buffer", str((n + 15) // 16)]]
+        if ndev.value >= 2:
+            variants += [["-gpus", "2"]] + ([["-gpus", str(ndev.value)]] if ndev.value > 2 else [])
+        ref = None
+        for extra in variants:
+            walls = []
+            for rep in range(a.reps):
+                o = os.path.join(tmp, "o.cod")
+                t0 = time.perf_counter()
+                subprocess.run([bsom, "-cin", cod, "-din", src, "-cout", o, "-epochs", "4", "-radius", str(radii[0])] + extra, check=True,
+                               stdout=subprocess.DEVNULL, timeout=600)
+                walls.append((time.perf_counter() - t0) * 1e3)
+                data = open(o, "rb").read()
+                ref = ref or data
+                assert data == ref, "bsom %s writes another file" % " ".join(extra)
+            out("    %-16s wall ms median %.1f of %s (the plain run's file, byte for byte)" % (" ".join(extra) or "(plain)", med(walls), fmt(walls)))
+        if ndev.value < 2:
+            out("    one device visible: -gpus not timed (ranks that share a GPU say nothing about speed)")
+    out("== ranks: bytes broadcast per epoch = G x the state (units x (dim + 1) x 8 + 16)")
+    for units, dim in ((65536, 512), (1024, 128)):
+        out("    %d x %d: state %.1f MB per rank's turn" % (units, dim + 1, (units * (dim + 1) * 8 + 16) / 1e6))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
@@ -155,6 +300,9 @@ def main():
     ap.add_argument("--online-only", default=None, help="(the child process) label of the library under SOMHIP_LIB")
     ap.add_argument("--batchmap-only", action="store_true", help="leave the online runs out")
     ap.add_argument("--small", action="store_true", help="one small shape: a rehearsal of the script, not a measurement")
+    ap.add_argument("--pieces", action="store_true", help="the report on the epoch over data in pieces (see the top)")
+    ap.add_argument("--rounds", type=int, default=3, help="--pieces: child processes per library")
+    ap.add_argument("--onecall-only", default=None, help="(a --pieces child process) label of the library under SOMHIP_LIB")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     shapes = [(24, 16, 40, 5000, (6.0, 1.0))] if a.small else SHAPES
@@ -168,6 +316,22 @@ def main():
     if a.online_only:                                   # the parent's library has no batch map: bind what it has
         for name in [k for k in _lib.SIGNATURES if "batchmap" in k]:
             del _lib.SIGNATURES[name]
+    if a.onecall_only or a.pieces:
+        if a.onecall_only == "parent":                  # ... nor the pieces' entry points
+            for name in [k for k in _lib.SIGNATURES if k.startswith("somhip_batchmap_") and k != "somhip_batchmap_timing"] + \
+                    ["somhip_som_batchmap_ranks", "somhip_comm_broadcast"]:
+                del _lib.SIGNATURES[name]
+        if a.onecall_only:
+            eng = E.Engine(0)
+            onecall_child(E, eng, a.reps, shapes, a.onecall_only)
+            eng.close()
+        else:
+            pieces_report(E, a, shapes, out)
+            if a.out:
+                with open(a.out, "w") as f:
+                    f.write("\n".join(lines) + "\n")
+        print(json.dumps({"lines": len(lines)}))
+        return
     eng = E.Engine(0)
     if a.online_only:
         measure_online(E, eng, a.reps, shapes, out, a.online_only)
