@@ -273,6 +273,40 @@ int  somhip_map_quality(somhip_codebook *cb, somhip_dataset *ds, int64_t first, 
 /* HIP-event totals of its two kernels since somhip_timing_reset, while somhip_timing_enable is on (not in the table of
  * somhip_kernel_count): [0] the pair pass, [1] the unit pass; one launch of each per chunk */
 int  somhip_map_quality_timing(somhip_engine *e, int64_t launches[2], double total_ms[2]);
+/* Map connectivity (K1c; no reference function): CADJ(i, j), the number of samples whose best unit is i and second-best
+ * unit j -- the cumulative adjacency matrix of Tasdemir and Merenyi (CONN = CADJ + its transpose), and on a codebook
+ * without a lattice the edges competitive Hebbian learning draws (Martinetz and Schulten).  Searched, b1, b2 are K1q's
+ * above; a sample is defined when it is searched and has both.  Units are unit indices u = y * xdim + x.
+ * A somhip_conn is a pair table on the device, owned by the caller: the pairs with a non-zero count, ascending by (i, j),
+ * each with a 64-bit count.  It is a handle like a codebook: destroying the engine first releases its device memory, after
+ * which every call on it but somhip_conn_destroy fails with a message.
+ *   somhip_conn_clear   empties the table (it may then take the pairs of a codebook of another size)
+ *   somhip_conn_size    *pairs = entries, *samples = the sum of their counts (either may be NULL)
+ *   somhip_conn_read    entries [first, first + n) in table order into b1, b2, count (each may be NULL); refused outside
+ *                       [0, pairs]
+ * somhip_map_connectivity adds the pairs of data rows (first + s) % n_rows, s = 0 .. count-1, to the table.  Every result
+ * is an integer: a run cut into any number of calls, over one data set or several, leaves the same table.
+ *   out == NULL   that alone; any codebook that is not a shard, with a lattice or without; hits and qsum must be NULL
+ *   out != NULL   somhip_map_quality beside it, from the same search: the same refusals and the same bits in hits, qsum
+ *                 and out
+ * Refused before anything is launched, the table untouched: null handles, handles of different engines or of a destroyed
+ * one, different dimensions, a row shard, first < 0, count >= 2^32, a table that holds pairs of a codebook with another
+ * number of units.  count <= 0 does nothing.  The keys of SOMHIP_CONN_SLAB samples are sorted at a time: the device memory
+ * of a call is that slab's and the table's, whatever count is.
+ * somhip_conn_timing: HIP-event totals since somhip_timing_reset, while somhip_timing_enable is on (not in the table of
+ * somhip_kernel_count): [0] the key pass (one launch per chunk), [1] the sort, [2] the run pass, [3] the merge (per slab:
+ * one, three and three timed scopes). */
+typedef struct somhip_conn somhip_conn;
+#define SOMHIP_CONN_SLAB 1048576
+int  somhip_conn_create(somhip_engine *e, somhip_conn **out);
+void somhip_conn_destroy(somhip_conn *c);
+int  somhip_conn_clear(somhip_conn *c);
+int  somhip_conn_size(somhip_conn *c, int64_t *pairs, uint64_t *samples);
+int  somhip_conn_read(somhip_conn *c, int64_t first, int64_t n, uint32_t *b1, uint32_t *b2, uint64_t *count);
+int  somhip_map_connectivity(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count, somhip_conn *c,
+                             uint32_t *hits /*[n_rows] in/out or NULL*/, double *qsum /*[n_rows] in/out or NULL*/,
+                             float qerror_in, somhip_quality_totals *out /* or NULL */);
+int  somhip_conn_timing(somhip_engine *e, int64_t launches[4], double total_ms[4]);
 
 /* ---- som_training (som_rout.c:556-671) --------------------------------------
  * Runs iterations [start_iter, start_iter+count) of a schedule of `length`

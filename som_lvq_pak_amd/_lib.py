@@ -99,6 +99,14 @@ SIGNATURES = {
     "somhip_map_quality": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, c_u32_p, c_double_p, C.c_float,
                                      C.POINTER(QualityTotals)]),
     "somhip_map_quality_timing": (C.c_int, [C.c_void_p, c_i64_p, c_double_p]),
+    "somhip_conn_create": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "somhip_conn_destroy": (None, [C.c_void_p]),
+    "somhip_conn_clear": (C.c_int, [C.c_void_p]),
+    "somhip_conn_size": (C.c_int, [C.c_void_p, c_i64_p, c_u64_p]),
+    "somhip_conn_read": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, c_u32_p, c_u32_p, c_u64_p]),
+    "somhip_map_connectivity": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, c_u32_p, c_double_p,
+                                          C.c_float, C.POINTER(QualityTotals)]),
+    "somhip_conn_timing": (C.c_int, [C.c_void_p, c_i64_p, c_double_p]),
     "somhip_som_train": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(SomParams), c_i32_p, c_float_p]),
     "somhip_som_batchmap": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(BatchmapParams), c_float_p]),
     "somhip_debug_batchmap_sums": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, c_u32_p, c_double_p]),

@@ -28,6 +28,7 @@
 #include "kernels/knn_wide.hpp"
 #include "kernels/knn_vote.hpp"
 #include "kernels/map_quality.hpp"
+#include "kernels/map_conn.hpp"
 #include "kernels/batchmap.hpp"
 #include "kernels/som_update.hpp"
 #include "kernels/som_update_gemm.hpp"

@@ -88,9 +88,10 @@ static const char *kKernelNames[KID_COUNT] = {
 // The table above is what somhip_kernel_count / somhip_kernel_name publish, and it is closed: callers index it and select
 // from it by bit.  Kernels added since are timed by LaunchTimer all the same, under ids that follow the table; an entry
 // point of their own reports them (somhip_mapset_timing, somhip_knn_timing, somhip_knn_vote_timing, somhip_map_quality_timing,
-// somhip_batchmap_timing).
+// somhip_batchmap_timing, somhip_conn_timing).
 enum TimedOnlyId { KID_MAPSET_TRAIN = KID_COUNT, KID_MAPSET_WINNERS, KID_KNN_DIST, KID_KNN_SELECT, KID_KNN_VOTE, KID_QUALITY_PAIRS,
-                   KID_QUALITY_UNITS, KID_BATCHMAP_GROUP, KID_BATCHMAP_SUMS, KID_BATCHMAP_COMBINE, KID_TIMED };
+                   KID_QUALITY_UNITS, KID_BATCHMAP_GROUP, KID_BATCHMAP_SUMS, KID_BATCHMAP_COMBINE, KID_CONN_KEYS, KID_CONN_SORT,
+                   KID_CONN_RUNS, KID_CONN_MERGE, KID_TIMED };
 static_assert(KID_TIMED <= 64, "somhip_timing_select's mask has one bit per kernel id");
 extern "C" int somhip_kernel_count(void) { return KID_COUNT; }
 extern "C" const char *somhip_kernel_name(int i) { return (i >= 0 && i < KID_COUNT) ? kKernelNames[i] : ""; }
@@ -149,7 +150,7 @@ enum ScratchSlot {
   SLOT_L2_OUT,             // two-level pre-filter, nearest row: level 2's minimum and mask of every list entry at the entry's
                            // own slot, from level 2 to the re-rank's selection (k_rerank_select_lists)
   SLOT_KNN_DIST,           // wide k-NN: the distances of a chunk of samples to every row, from the distance stage to the select
-  SLOT_QUALITY,            // somhip_map_quality: the run's qsum, totals and hits, around the searches of its chunks (SLOT_CALL_A the
+  SLOT_QUALITY,            // somhip_map_quality, somhip_map_connectivity: the run's qsum, totals and hits, around the searches of its chunks (SLOT_CALL_A the
                            // chunk's keys, SLOT_CALL_B its per-sample terms, units and distances)
   SLOT_BATCHMAP,           // the batch map (host_batchmap.inc): per unit -- the sums and counts, the gaussian table, hits and starts
   SLOT_BATCHMAP_LIST,      // ... per sample -- winners, sample numbers, their sorted copies, the sort's room (SLOT_CALL_A the
@@ -202,6 +203,7 @@ struct somhip_engine {
   std::vector<somhip_codebook *> codebooks;
   std::vector<somhip_dataset *> datasets;
   std::vector<somhip_mapset *> mapsets;
+  std::vector<somhip_conn *> conns;
   unsigned lds_raised = 0;                     // bit LdsKernel: that kernel's dynamic LDS limit is raised on this device
   int n_cus = 0;                               // compute units of the device (grid of the persistent kernels)
   LvqCtl *lvq_hctl = nullptr;                  // pinned: read-backs of the LVQ batch loop's control block, one per batch in flight
@@ -344,6 +346,7 @@ static int launch_timed(somhip_engine *e, int kid, const char *name, void (*kern
 static void codebook_release(somhip_codebook *cb);   // device memory of a mirror (defined with the mirrors below)
 static void dataset_release(somhip_dataset *ds);
 static void mapset_release(somhip_mapset *ms);
+static void conn_release(somhip_conn *c);
 
 extern "C" int somhip_engine_create(int device, somhip_engine **out) try {
   if (!out) return fail("somhip_engine_create: null out");
@@ -376,6 +379,7 @@ extern "C" void somhip_engine_destroy(somhip_engine *e) try {
   for (auto *cb : e->codebooks) codebook_release(cb);     // (these also clear the mirror's engine pointer)
   for (auto *ds : e->datasets) dataset_release(ds);
   for (auto *ms : e->mapsets) mapset_release(ms);
+  for (auto *c : e->conns) conn_release(c);
   for (auto &p : e->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
   for (auto ev : e->pool) (void)hipEventDestroy(ev);
   for (int i = 0; i < SLOT_COUNT; i++) if (e->scratch[i]) (void)hipFree(e->scratch[i]);
@@ -821,5 +825,6 @@ extern "C" void somhip_dataset_destroy(somhip_dataset *ds) try {
 #include "host_class.inc"
 #include "host_umat.inc"
 #include "host_planes.inc"
+#include "host_conn.inc"
 #include "host_quality.inc"
 #include "host_batchmap.inc"

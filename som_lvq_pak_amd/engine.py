@@ -138,6 +138,15 @@ class Engine:
         check(self.lib.somhip_map_quality_timing(self.h, n, ms))
         return {"k_quality_pairs": (n[0], ms[0]), "k_quality_units": (n[1], ms[1])}
 
+    def conn_timing(self):
+        """(launches, ms) of map_connectivity's pair passes while timing is on (somhip_conn_timing; they are not in
+        timing_table): the key pass once per chunk of samples; per slab the sort once, the run pass and the merge three
+        timed scopes each (two kernels around a scan)"""
+        n = (C.c_int64 * 4)()
+        ms = (C.c_double * 4)()
+        check(self.lib.somhip_conn_timing(self.h, n, ms))
+        return {"k_conn_keys": (n[0], ms[0]), "sort": (n[1], ms[1]), "runs": (n[2], ms[2]), "merge": (n[3], ms[3])}
+
     def batchmap_timing(self):
         """(launches, ms) of the batch map's stages while timing is on (somhip_batchmap_timing; they are not in
         timing_table): group = the winners pass per chunk, the scan of the counts and the sort by winner"""
@@ -421,6 +430,68 @@ def map_quality(cb, ds, first=0, count=None, hits=None, qsum=None, qerror=0.0):
     tot = _lib.QualityTotals()
     check(cb.e.lib.somhip_map_quality(cb.h, ds.h, first, count, _p(hits, _lib.c_u32_p), _p(qsum, _lib.c_double_p),
                                       float(np.float32(qerror)), C.byref(tot)))
+    return ({"searched": tot.searched, "topo_defined": tot.topo_defined, "topo_errors": tot.topo_errors,
+             "qerror": np.float32(tot.qerror)}, hits, qsum)
+
+
+CONN_SLAB = 1 << 20      # somhip.h SOMHIP_CONN_SLAB: the samples whose pairs map_connectivity sorts at a time
+
+
+class Conn:
+    """A pair table on the device (somhip_conn): for every ordered pair (best unit, second-best unit) that some sample
+    has, the number of such samples, ascending by pair.  map_connectivity adds to it; it lives until closed."""
+
+    def __init__(self, engine):
+        self.e = engine
+        h = C.c_void_p()
+        check(engine.lib.somhip_conn_create(engine.h, C.byref(h)))
+        self.h = h
+        engine._adopt(self)
+
+    def clear(self):
+        check(self.e.lib.somhip_conn_clear(self.h))
+
+    def size(self):
+        """(pairs, samples): the entries and the sum of their counts"""
+        pairs, samples = C.c_int64(0), C.c_uint64(0)
+        check(self.e.lib.somhip_conn_size(self.h, C.byref(pairs), C.byref(samples)))
+        return pairs.value, samples.value
+
+    def read(self, first=0, n=None):
+        """(b1, b2, count) of entries [first, first + n) in table order: uint32, uint32, uint64 arrays"""
+        n = self.size()[0] - first if n is None else n
+        m = max(n, 0)
+        b1, b2, count = np.empty(m, dtype=np.uint32), np.empty(m, dtype=np.uint32), np.empty(m, dtype=np.uint64)
+        check(self.e.lib.somhip_conn_read(self.h, first, n, _p(b1, _lib.c_u32_p), _p(b2, _lib.c_u32_p), _p(count, _lib.c_u64_p)))
+        return b1, b2, count
+
+    def close(self):
+        if self.h and self.e.h:
+            self.e.lib.somhip_conn_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def map_connectivity(cb, ds, conn, first=0, count=None, quality=False, hits=None, qsum=None, qerror=0.0):
+    """Adds to `conn`, per ordered pair (best unit, second-best unit), the samples of data rows (first + s) % ds.n,
+    s < count, that have it (somhip_map_connectivity).  quality=False: returns None; any whole codebook, with a lattice or
+    without.  quality=True: map_quality's (totals, hits, qsum) from the same search, with the same bits."""
+    count = ds.n if count is None else count
+    if not quality:
+        assert hits is None and qsum is None
+        check(cb.e.lib.somhip_map_connectivity(cb.h, ds.h, first, count, conn.h, None, None, 0.0, None))
+        return None
+    hits = np.zeros(cb.n, dtype=np.uint32) if hits is None else np.array(hits, dtype=np.uint32)
+    qsum = np.zeros(cb.n, dtype=np.float64) if qsum is None else np.array(qsum, dtype=np.float64)
+    assert hits.shape == (cb.n,) and qsum.shape == (cb.n,)
+    tot = _lib.QualityTotals()
+    check(cb.e.lib.somhip_map_connectivity(cb.h, ds.h, first, count, conn.h, _p(hits, _lib.c_u32_p), _p(qsum, _lib.c_double_p),
+                                           float(np.float32(qerror)), C.byref(tot)))
     return ({"searched": tot.searched, "topo_defined": tot.topo_defined, "topo_errors": tot.topo_errors,
              "qerror": np.float32(tot.qerror)}, hits, qsum)
 

@@ -170,9 +170,15 @@ float find_qerror(struct teach_params *teach);
 float find_qerror2(struct teach_params *teach);   /* qerror -qetype 1 (som_rout.c:823) */
 /* find_qerror's sum together with the topographic error and the per-unit statistics of the map (somhip_map_quality), the
  * data taken `buffer` rows per engine call (<= 0: at once) with the same result.  hits / qsum: arrays of the codebook's
- * entries, the caller's to free.  0, or 1 after a message. */
-struct map_quality { float qerror; long searched, topo_defined, topo_errors; uint32_t *hits; double *qsum; };
-int find_map_quality(struct teach_params *teach, long buffer, struct map_quality *q);
+ * entries.  want_pairs: the same search also counts the samples per ordered pair (best unit, second-best unit)
+ * (somhip_map_connectivity, one pair table through all buffers): b1 / b2 / pair_count are the n_pairs pairs with a non-zero
+ * count, ascending by (b1, b2).  The arrays are the caller's to free (free_map_quality).  0, or 1 after a message. */
+struct map_quality {
+  float qerror; long searched, topo_defined, topo_errors; uint32_t *hits; double *qsum;
+  long n_pairs; uint32_t *b1, *b2; uint64_t *pair_count;
+};
+int find_map_quality(struct teach_params *teach, long buffer, int want_pairs, struct map_quality *q);
+void free_map_quality(struct map_quality *q);
 /* Kohonen's batch map (somhip_som_batchmap): `epochs` epochs over all of teach->data from teach->radius down to 1, the
  * lattice and neighbourhood of teach->codes, whose vectors it replaces.  qerror: NULL, or [epochs] for the quantization error
  * (find_qerror's sum) of the map every epoch started from.  0, or 1 after a message.

@@ -640,7 +640,7 @@ float find_qerror(struct teach_params *teach)                 /* som_rout.c:678-
   return qerror;
 }
 
-int find_map_quality(struct teach_params *teach, long buffer, struct map_quality *q)
+int find_map_quality(struct teach_params *teach, long buffer, int want_pairs, struct map_quality *q)
 {
   memset(q, 0, sizeof *q);
   if (set_som_params(teach)) { fprintf(stderr, "find_map_quality: can't set SOM parameters\n"); return 1; }
@@ -650,17 +650,38 @@ int find_map_quality(struct teach_params *teach, long buffer, struct map_quality
   q->hits = calloc(noc + 1, sizeof *q->hits);
   q->qsum = calloc(noc + 1, sizeof *q->qsum);
   struct mirrors m;
+  somhip_conn *conn = NULL;
   int rc = mirrors_open(&m, teach->codes, 0, teach->data, 0);
-  for (long first = 0; !rc && first < n; first += buffer) {      /* hits, qsum and the float chain go from buffer to buffer */
-    somhip_quality_totals t;
-    rc = said(somhip_map_quality(m.cb, m.ds, first, buffer < n - first ? buffer : n - first, q->hits, q->qsum, q->qerror, &t));
+  if (!rc && want_pairs) rc = said(somhip_conn_create(pak_engine(), &conn));
+  for (long first = 0; !rc && first < n; first += buffer) {      /* hits, qsum and the float chain go from buffer to buffer, */
+    somhip_quality_totals t;                                      /* and one pair table takes the pairs of them all */
+    const long count = buffer < n - first ? buffer : n - first;
+    rc = said(conn ? somhip_map_connectivity(m.cb, m.ds, first, count, conn, q->hits, q->qsum, q->qerror, &t)
+                   : somhip_map_quality(m.cb, m.ds, first, count, q->hits, q->qsum, q->qerror, &t));
     if (rc) break;
     q->qerror = t.qerror;
     q->searched += t.searched; q->topo_defined += t.topo_defined; q->topo_errors += t.topo_errors;
   }
+  if (!rc && conn) {
+    int64_t pairs = 0;
+    rc = said(somhip_conn_size(conn, &pairs, NULL));
+    if (!rc) {
+      q->n_pairs = (long)pairs;
+      q->b1 = calloc(pairs + 1, sizeof *q->b1);
+      q->b2 = calloc(pairs + 1, sizeof *q->b2);
+      q->pair_count = calloc(pairs + 1, sizeof *q->pair_count);
+      rc = said(somhip_conn_read(conn, 0, pairs, q->b1, q->b2, q->pair_count));
+    }
+  }
+  if (conn) somhip_conn_destroy(conn);
   mirrors_close(&m);
-  if (rc) { free(q->hits); free(q->qsum); q->hits = NULL; q->qsum = NULL; }
+  if (rc) free_map_quality(q);
   return rc;
+}
+void free_map_quality(struct map_quality *q)
+{
+  free(q->hits); free(q->qsum); free(q->b1); free(q->b2); free(q->pair_count);
+  q->hits = NULL; q->qsum = NULL; q->b1 = q->b2 = NULL; q->pair_count = NULL; q->n_pairs = 0;
 }
 
 /* the rows [first, first + count) of data as a device data set of their own: uploaded, or generated in place */
