@@ -430,6 +430,59 @@ int  somhip_batchmap_finish(somhip_codebook *cb, float r, int64_t group_first, i
 int  somhip_batchmap_end(somhip_codebook *cb);
 int  somhip_batchmap_state(somhip_codebook *cb, void **dev_state, int64_t *bytes);
 
+/* ---- map distortion (K1d; no reference function) ----------------------------------
+ * The distortion measure of a map (Lampinen and Oja; SOM Toolbox's som_distortion): its energy at a neighbourhood radius,
+ *   E(r) = sum over samples s, sum over units j, of  h_r(c(s), j) * || x_s - m_j ||^2 ,
+ * the function one epoch of the batch map minimises for fixed winners.  It is not swept over samples x units x dim: with
+ *   1. c(s), hits[c], S[c][k] exactly steps 2-3 of the batch map above (SOMHIP_TIE_FIRST winners, integer counts, one
+ *      fp64 chain from +0.0 per (unit, column) in data order)
+ *   2. q_s = |x_s|^2 in fp64: lane l of 64 adds (double)x[k] * (double)x[k] (exact) for k = l, l + 64, ... in order from
+ *      +0.0, the 64 partials are folded by the xor butterfly 32, 16, 8, 4, 2, 1 -- an order that depends on dim alone;
+ *      Q[c] = one chain of fp64 additions of q_s from +0.0 over the unit's samples in data order
+ *   3. h(j, c) step 4 of the batch map, at any r >= 0 (bubble at r = 0: E is the plain sum of the squared quantization
+ *      errors; gaussian at r = 0 is 0 / 0 on the diagonal by that definition: not a number)
+ *   4. [N | D | A] = H x [S | hits | Q] in fp64 (v_mfma_f64_16x16x4_f64; the order over c is the storage order of the rows),
+ *      e_j = A_j - 2 sum_k m_jk N_jk + D_j sum_k m_jk^2, formed as A_j + sum_k m_jk (D_j m_jk - 2 N_jk) with the additions
+ *      over k and over the blocks of 64 columns in an order fixed by the shape; e_j = 0 where D_j == 0; E = sum_j e_j by a
+ *      tree fixed by the number of units.  The same inputs give the same bits on every run; no floating-point atomics.
+ *   5. scale = sum_j 2 * (A_j + D_j |m_j|^2) bounds the sum of the absolute values of all terms of E (2 |m.x| <= |m|^2 +
+ *      |x|^2).  E resolves about 2^-52 * scale: for data far from the origin scale >> E, and scale / E says how many of E's
+ *      digits mean anything.  Centre such data first.
+ * A somhip_distortion is a state on the device, the caller's, made for the engine, the number of units and the dimension
+ * of the codebook given to _create: [S | hits] as n_rows x (dim + 1) doubles, Q[n_rows], the samples taken.  A handle like
+ * a codebook: destroying the engine first releases its device memory, after which every call on it but _destroy fails.
+ *   _clear       back to all +0.0 and no samples
+ *   _accumulate  steps 1-2 over rows (first + s) % n_rows, s < n, of ds against the codebook's rows as they are: the chains
+ *                and counts go on from what the calls before left, so any cut of the data into calls, buffers or data sets
+ *                leaves the bits of one call.  The caller keeps the codebook frozen between the pieces.
+ *   _evaluate    steps 3-5 at radius r against the codebook's CURRENT rows (the energy of other rows under the accumulated
+ *                winners may be asked for): unit_out[n_rows] (or NULL) = e_j by unit, totals.  It writes nothing but its
+ *                outputs: the codebook, its prepared copies and an open somhip_batchmap_* state stay as they are.
+ *   _read        the state to the host: hits[n_rows], sums[n_rows][dim], sq[n_rows] (each may be NULL)
+ * somhip_debug_distortion_evaluate: the evaluate stage on host-supplied hits, sums and sq.
+ * Refused by name before anything is launched, state and codebook untouched: null handles, handles of different engines
+ * or of a destroyed one, data with x components, sharded codebooks, codebooks without a lattice, a codebook or data set
+ * whose shape is not the state's, first < 0, n <= 0, a piece that takes the total to 2^32 samples, r < 0 or NaN.
+ * somhip_distortion_timing: HIP-event totals since somhip_timing_reset, while somhip_timing_enable is on (not in the table
+ * of somhip_kernel_count): [0] group (the winners pass per chunk, the scan, the sort), [1] the sums and the two Q passes,
+ * [2] evaluate (the gaussian table, the kernel, the two fold passes). */
+typedef struct somhip_distortion somhip_distortion;
+typedef struct somhip_distortion_totals {
+  double   energy;       /* E(r) */
+  double   scale;        /* E resolves about 2^-52 * scale */
+  uint64_t samples;      /* the samples accumulated */
+} somhip_distortion_totals;
+int  somhip_distortion_create(somhip_codebook *cb, somhip_distortion **out);
+void somhip_distortion_destroy(somhip_distortion *st);
+int  somhip_distortion_clear(somhip_distortion *st);
+int  somhip_distortion_accumulate(somhip_distortion *st, somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n);
+int  somhip_distortion_evaluate(somhip_distortion *st, somhip_codebook *cb, float r, double *unit_out /*[n_rows] or NULL*/,
+                                somhip_distortion_totals *totals);
+int  somhip_distortion_read(somhip_distortion *st, uint32_t *hits, double *sums, double *sq);
+int  somhip_debug_distortion_evaluate(somhip_codebook *cb, float r, const uint32_t *hits, const double *sums, const double *sq,
+                                      double *unit_out /*[n_rows] or NULL*/, somhip_distortion_totals *totals);
+int  somhip_distortion_timing(somhip_engine *e, int64_t launches[3], double total_ms[3]);
+
 /* ---- map sets: many maps of one shape, trained at once ---------------------------
  * What vfind does: N maps that share shape, data and schedule and differ only in their initial rows.  The online
  * algorithm on ONE small map is one launch per iteration and the launch is the cost (a 12x8x5 map is one workgroup of

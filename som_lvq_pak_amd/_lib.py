@@ -37,6 +37,10 @@ class QualityTotals(C.Structure):
     _fields_ = [("searched", C.c_int64), ("topo_defined", C.c_int64), ("topo_errors", C.c_int64), ("qerror", C.c_float)]
 
 
+class DistortionTotals(C.Structure):
+    _fields_ = [("energy", C.c_double), ("scale", C.c_double), ("samples", C.c_uint64)]
+
+
 class BatchmapParams(C.Structure):
     _fields_ = [("epochs", C.c_int64), ("radius", C.c_float), ("start_epoch", C.c_int64), ("count", C.c_int64),
                 ("first", C.c_int64), ("n", C.c_int64)]
@@ -117,6 +121,15 @@ SIGNATURES = {
     "somhip_batchmap_finish": (C.c_int, [C.c_void_p, C.c_float, C.c_int64, C.c_int64, c_float_p]),
     "somhip_batchmap_end": (C.c_int, [C.c_void_p]),
     "somhip_batchmap_state": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), c_i64_p]),
+    "somhip_distortion_create": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "somhip_distortion_destroy": (None, [C.c_void_p]),
+    "somhip_distortion_clear": (C.c_int, [C.c_void_p]),
+    "somhip_distortion_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]),
+    "somhip_distortion_evaluate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, c_double_p, C.POINTER(DistortionTotals)]),
+    "somhip_distortion_read": (C.c_int, [C.c_void_p, c_u32_p, c_double_p, c_double_p]),
+    "somhip_debug_distortion_evaluate": (C.c_int, [C.c_void_p, C.c_float, c_u32_p, c_double_p, c_double_p, c_double_p,
+                                                   C.POINTER(DistortionTotals)]),
+    "somhip_distortion_timing": (C.c_int, [C.c_void_p, c_i64_p, c_double_p]),
     "somhip_som_batchmap_ranks": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(BatchmapParams), C.c_void_p, c_float_p]),
     "somhip_mapset_create": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.POINTER(C.c_void_p)]),

@@ -52,9 +52,9 @@ static inline void batchmap_q_step(float &q, float d1) { q += sqrt((double)d1); 
 // sort by winner.  q (or null: no per-sample copy leaves the device): find_qerror's float chain over the winners' distances
 // in data order, as somhip_map_quality forms it, continued from *q.  keep (with q): the chain is not run; the distances
 // it would take are kept in data order instead (-1 for a sample it skips), for a caller that learns where the chain
-// starts only later.
+// starts only later.  kid: the timing id the stage's launches count under (map distortion runs it under its own).
 static int batchmap_group_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, const BatchmapBufs &b, float *q,
-                                std::vector<float> *keep = nullptr) {
+                                std::vector<float> *keep = nullptr, int kid = KID_BATCHMAP_GROUP) {
   somhip_engine *e = cb->e;
   const uint32_t units = (uint32_t)cb->v.n;
   HIPCHK(hipMemsetAsync(b.hits, 0, sizeof(uint32_t) * (size_t)units, e->stream));
@@ -64,7 +64,7 @@ static int batchmap_group_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t
   CHK(knn_chunk_keys(cb, ds, first, n, 1, 0, [&](int64_t off, int64_t f, int64_t c, const uint64_t *dk, int stride) {
     float *dd1 = nullptr;
     if (q) CHK(scratch(e, SLOT_CALL_B, (size_t)c, &dd1));
-    CHK(LAUNCH_TIMED(e, KID_BATCHMAP_GROUP, k_batchmap_winners, dim3((unsigned)((c + BM_THREADS - 1) / BM_THREADS)), dim3(BM_THREADS), 0, dk,
+    CHK(LAUNCH_TIMED(e, kid, k_batchmap_winners, dim3((unsigned)((c + BM_THREADS - 1) / BM_THREADS)), dim3(BM_THREADS), 0, dk,
         stride, off, c, units, b.win, b.idx, dd1, b.hits));
     if (!q) return 0;
     if (hd.empty()) hd.resize((size_t)c);                               // (the first chunk is the longest)
@@ -76,9 +76,9 @@ static int batchmap_group_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t
     }
     return 0;
   }));
-  CHK(LAUNCH_TIMED(e, KID_BATCHMAP_GROUP, k_batchmap_starts, dim3(1), dim3(BM_SCAN_THREADS), 0, b.hits, units, b.starts));
+  CHK(LAUNCH_TIMED(e, kid, k_batchmap_starts, dim3(1), dim3(BM_SCAN_THREADS), 0, b.hits, units, b.starts));
   {
-    LaunchTimer t(e, KID_BATCHMAP_GROUP);                               // (rocPRIM's own launches, on the engine's stream)
+    LaunchTimer t(e, kid);                                              // (rocPRIM's own launches, on the engine's stream)
     size_t bytes = b.sort_bytes;
     const hipError_t er = rocprim::radix_sort_pairs(b.sort_tmp, bytes, b.win, b.win_sorted, b.idx, b.list, (size_t)n, 0u, b.sort_bits, e->stream);
     if (er != hipSuccess) return fail("batch map: the sort by winner failed: %s", hipGetErrorString(er));
@@ -87,13 +87,14 @@ static int batchmap_group_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t
   return 0;
 }
 // ... and the sums half: b.S <- [S | hits] from the lists.  cont: the chains and counts go on from what b.S holds.
-static int batchmap_sums_launch(somhip_codebook *cb, somhip_dataset *ds, int64_t first, const BatchmapBufs &b, bool cont) {
+static int batchmap_sums_launch(somhip_codebook *cb, somhip_dataset *ds, int64_t first, const BatchmapBufs &b, bool cont,
+                                int kid = KID_BATCHMAP_SUMS) {
   somhip_engine *e = cb->e;
   const dim3 grid((unsigned)cb->v.n, (unsigned)((cb->v.d + 1 + BM_SUM_DIMS - 1) / BM_SUM_DIMS));
   if (cont)
-    return LAUNCH_TIMED(e, KID_BATCHMAP_SUMS, k_batchmap_sums<true>, grid, dim3(BM_SUM_DIMS), 0, ds->d_rows, ds->n, ds->d, first % ds->n, b.list,
+    return LAUNCH_TIMED(e, kid, k_batchmap_sums<true>, grid, dim3(BM_SUM_DIMS), 0, ds->d_rows, ds->n, ds->d, first % ds->n, b.list,
                         b.starts, b.S);
-  return LAUNCH_TIMED(e, KID_BATCHMAP_SUMS, k_batchmap_sums<false>, grid, dim3(BM_SUM_DIMS), 0, ds->d_rows, ds->n, ds->d, first % ds->n, b.list,
+  return LAUNCH_TIMED(e, kid, k_batchmap_sums<false>, grid, dim3(BM_SUM_DIMS), 0, ds->d_rows, ds->n, ds->d, first % ds->n, b.list,
                       b.starts, b.S);
 }
 static int batchmap_sums_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, const BatchmapBufs &b, float *qerror) {

@@ -30,6 +30,7 @@
 #include "kernels/map_quality.hpp"
 #include "kernels/map_conn.hpp"
 #include "kernels/batchmap.hpp"
+#include "kernels/map_distortion.hpp"
 #include "kernels/som_update.hpp"
 #include "kernels/som_update_gemm.hpp"
 #include "kernels/som_online.hpp"

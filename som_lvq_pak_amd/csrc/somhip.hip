@@ -88,10 +88,10 @@ static const char *kKernelNames[KID_COUNT] = {
 // The table above is what somhip_kernel_count / somhip_kernel_name publish, and it is closed: callers index it and select
 // from it by bit.  Kernels added since are timed by LaunchTimer all the same, under ids that follow the table; an entry
 // point of their own reports them (somhip_mapset_timing, somhip_knn_timing, somhip_knn_vote_timing, somhip_map_quality_timing,
-// somhip_batchmap_timing, somhip_conn_timing).
+// somhip_batchmap_timing, somhip_conn_timing, somhip_distortion_timing).
 enum TimedOnlyId { KID_MAPSET_TRAIN = KID_COUNT, KID_MAPSET_WINNERS, KID_KNN_DIST, KID_KNN_SELECT, KID_KNN_VOTE, KID_QUALITY_PAIRS,
                    KID_QUALITY_UNITS, KID_BATCHMAP_GROUP, KID_BATCHMAP_SUMS, KID_BATCHMAP_COMBINE, KID_CONN_KEYS, KID_CONN_SORT,
-                   KID_CONN_RUNS, KID_CONN_MERGE, KID_TIMED };
+                   KID_CONN_RUNS, KID_CONN_MERGE, KID_DISTORTION_GROUP, KID_DISTORTION_SUMS, KID_DISTORTION_EVALUATE, KID_TIMED };
 static_assert(KID_TIMED <= 64, "somhip_timing_select's mask has one bit per kernel id");
 extern "C" int somhip_kernel_count(void) { return KID_COUNT; }
 extern "C" const char *somhip_kernel_name(int i) { return (i >= 0 && i < KID_COUNT) ? kKernelNames[i] : ""; }
@@ -204,6 +204,7 @@ struct somhip_engine {
   std::vector<somhip_dataset *> datasets;
   std::vector<somhip_mapset *> mapsets;
   std::vector<somhip_conn *> conns;
+  std::vector<somhip_distortion *> distortions;
   unsigned lds_raised = 0;                     // bit LdsKernel: that kernel's dynamic LDS limit is raised on this device
   int n_cus = 0;                               // compute units of the device (grid of the persistent kernels)
   LvqCtl *lvq_hctl = nullptr;                  // pinned: read-backs of the LVQ batch loop's control block, one per batch in flight
@@ -347,6 +348,7 @@ static void codebook_release(somhip_codebook *cb);   // device memory of a mirro
 static void dataset_release(somhip_dataset *ds);
 static void mapset_release(somhip_mapset *ms);
 static void conn_release(somhip_conn *c);
+static void distortion_release(somhip_distortion *st);
 
 extern "C" int somhip_engine_create(int device, somhip_engine **out) try {
   if (!out) return fail("somhip_engine_create: null out");
@@ -380,6 +382,7 @@ extern "C" void somhip_engine_destroy(somhip_engine *e) try {
   for (auto *ds : e->datasets) dataset_release(ds);
   for (auto *ms : e->mapsets) mapset_release(ms);
   for (auto *c : e->conns) conn_release(c);
+  for (auto *st : e->distortions) distortion_release(st);
   for (auto &p : e->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
   for (auto ev : e->pool) (void)hipEventDestroy(ev);
   for (int i = 0; i < SLOT_COUNT; i++) if (e->scratch[i]) (void)hipFree(e->scratch[i]);
@@ -828,3 +831,4 @@ extern "C" void somhip_dataset_destroy(somhip_dataset *ds) try {
 #include "host_conn.inc"
 #include "host_quality.inc"
 #include "host_batchmap.inc"
+#include "host_distortion.inc"

@@ -155,6 +155,15 @@ class Engine:
         check(self.lib.somhip_batchmap_timing(self.h, n, ms))
         return {"group": (n[0], ms[0]), "k_batchmap_sums": (n[1], ms[1]), "k_batchmap_combine": (n[2], ms[2])}
 
+    def distortion_timing(self):
+        """(launches, ms) of map distortion's stages while timing is on (somhip_distortion_timing; they are not in
+        timing_table): group = the winners pass per chunk, the scan of the counts and the sort by winner; sums = the
+        continued sums and the two Q passes; evaluate = the gaussian table, the kernel and the two fold passes"""
+        n = (C.c_int64 * 3)()
+        ms = (C.c_double * 3)()
+        check(self.lib.somhip_distortion_timing(self.h, n, ms))
+        return {"group": (n[0], ms[0]), "sums": (n[1], ms[1]), "evaluate": (n[2], ms[2])}
+
     def device_alloc(self, nbytes):
         p = C.c_void_p()
         check(self.lib.somhip_device_alloc(self.h, nbytes, C.byref(p)))
@@ -664,6 +673,86 @@ def batchmap_state(cb):
     addr, nbytes = C.c_void_p(), C.c_int64(0)
     check(cb.e.lib.somhip_batchmap_state(cb.h, C.byref(addr), C.byref(nbytes)))
     return int(addr.value), int(nbytes.value)
+
+
+def _distortion_totals(tot):
+    return {"energy": tot.energy, "scale": tot.scale, "samples": tot.samples}
+
+
+class Distortion:
+    """The state of a map distortion on the device (somhip_distortion), made for the shape of `cb`: per unit the samples
+    it wins, the fp64 sums of their rows and of their squared norms.  accumulate adds data to it piece by piece -- any cut
+    leaves the bits of one call; evaluate gives the energy E(r) = sum_s sum_j h_r(c(s), j) |x_s - m_j|^2 of the
+    codebook's current rows under the accumulated winners.  It lives until closed."""
+
+    def __init__(self, cb):
+        self.e = cb.e
+        self.n, self.dim = cb.n, cb.dim
+        h = C.c_void_p()
+        check(cb.e.lib.somhip_distortion_create(cb.h, C.byref(h)))
+        self.h = h
+        cb.e._adopt(self)
+
+    def clear(self):
+        check(self.e.lib.somhip_distortion_clear(self.h))
+
+    def accumulate(self, cb, ds, first=0, n=None):
+        """data rows (first + s) % ds.n, s < n, against cb's rows as they are (somhip_distortion_accumulate)"""
+        n = ds.n if n is None else n
+        check(self.e.lib.somhip_distortion_accumulate(self.h, cb.h, ds.h, first, n))
+
+    def evaluate(self, cb, r, units=True):
+        """(totals, e): totals = {"energy", "scale", "samples"} at radius r against cb's current rows -- the energy resolves
+        about 2^-52 * scale -- and e = float64[cb.n], the energy per unit (None with units=False)
+        (somhip_distortion_evaluate)"""
+        e = np.zeros(self.n, dtype=np.float64) if units else None
+        tot = _lib.DistortionTotals()
+        check(self.e.lib.somhip_distortion_evaluate(self.h, cb.h, float(np.float32(r)), _p(e, _lib.c_double_p), C.byref(tot)))
+        return _distortion_totals(tot), e
+
+    def read(self):
+        """(hits uint32[n], sums float64[n, dim], sq float64[n]): the state as it stands (somhip_distortion_read)"""
+        hits = np.zeros(self.n, dtype=np.uint32)
+        sums = np.zeros((self.n, self.dim), dtype=np.float64)
+        sq = np.zeros(self.n, dtype=np.float64)
+        check(self.e.lib.somhip_distortion_read(self.h, _p(hits, _lib.c_u32_p), _p(sums, _lib.c_double_p), _p(sq, _lib.c_double_p)))
+        return hits, sums, sq
+
+    def close(self):
+        if self.h and self.e.h:
+            self.e.lib.somhip_distortion_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def map_distortion(cb, ds, r, first=0, n=None, units=True):
+    """The distortion of a map over data rows (first + s) % ds.n, s < n, at radius r in one call: a Distortion made,
+    accumulated, evaluated and closed.  Returns (totals, e) as Distortion.evaluate does."""
+    st = Distortion(cb)
+    try:
+        st.accumulate(cb, ds, first, n)
+        return st.evaluate(cb, r, units)
+    finally:
+        st.close()
+
+
+def distortion_evaluate(cb, r, hits, sums, sq, units=True):
+    """The evaluate stage alone on host-supplied per-unit hits, sums and squared-norm sums
+    (somhip_debug_distortion_evaluate): (totals, e) as Distortion.evaluate gives them"""
+    hits = np.ascontiguousarray(hits, dtype=np.uint32)
+    sums = np.ascontiguousarray(sums, dtype=np.float64)
+    sq = np.ascontiguousarray(sq, dtype=np.float64)
+    assert hits.shape == (cb.n,) and sums.shape == (cb.n, cb.dim) and sq.shape == (cb.n,)
+    e = np.zeros(cb.n, dtype=np.float64) if units else None
+    tot = _lib.DistortionTotals()
+    check(cb.e.lib.somhip_debug_distortion_evaluate(cb.h, float(np.float32(r)), _p(hits, _lib.c_u32_p), _p(sums, _lib.c_double_p),
+                                                    _p(sq, _lib.c_double_p), _p(e, _lib.c_double_p), C.byref(tot)))
+    return _distortion_totals(tot), e
 
 
 def device_ptrs(cb, ds):

@@ -172,12 +172,16 @@ float find_qerror2(struct teach_params *teach);   /* qerror -qetype 1 (som_rout.
  * data taken `buffer` rows per engine call (<= 0: at once) with the same result.  hits / qsum: arrays of the codebook's
  * entries.  want_pairs: the same search also counts the samples per ordered pair (best unit, second-best unit)
  * (somhip_map_connectivity, one pair table through all buffers): b1 / b2 / pair_count are the n_pairs pairs with a non-zero
- * count, ascending by (b1, b2).  The arrays are the caller's to free (free_map_quality).  0, or 1 after a message. */
+ * count, ascending by (b1, b2).  distortion_radius >= 0: the map's distortion at that radius too (somhip_distortion_*, one
+ * state through all buffers, a winner search of its own per buffer): energy, scale, distortion_samples and unit_energy, an
+ * array of the codebook's entries; < 0: none.  The arrays are the caller's to free (free_map_quality).  0, or 1 after a
+ * message. */
 struct map_quality {
   float qerror; long searched, topo_defined, topo_errors; uint32_t *hits; double *qsum;
   long n_pairs; uint32_t *b1, *b2; uint64_t *pair_count;
+  double energy, scale; unsigned long long distortion_samples; double *unit_energy;
 };
-int find_map_quality(struct teach_params *teach, long buffer, int want_pairs, struct map_quality *q);
+int find_map_quality(struct teach_params *teach, long buffer, int want_pairs, float distortion_radius, struct map_quality *q);
 void free_map_quality(struct map_quality *q);
 /* Kohonen's batch map (somhip_som_batchmap): `epochs` epochs over all of teach->data from teach->radius down to 1, the
  * lattice and neighbourhood of teach->codes, whose vectors it replaces.  qerror: NULL, or [epochs] for the quantization error

@@ -640,7 +640,7 @@ float find_qerror(struct teach_params *teach)                 /* som_rout.c:678-
   return qerror;
 }
 
-int find_map_quality(struct teach_params *teach, long buffer, int want_pairs, struct map_quality *q)
+int find_map_quality(struct teach_params *teach, long buffer, int want_pairs, float distortion_radius, struct map_quality *q)
 {
   memset(q, 0, sizeof *q);
   if (set_som_params(teach)) { fprintf(stderr, "find_map_quality: can't set SOM parameters\n"); return 1; }
@@ -651,8 +651,10 @@ int find_map_quality(struct teach_params *teach, long buffer, int want_pairs, st
   q->qsum = calloc(noc + 1, sizeof *q->qsum);
   struct mirrors m;
   somhip_conn *conn = NULL;
+  somhip_distortion *dist = NULL;
   int rc = mirrors_open(&m, teach->codes, 0, teach->data, 0);
   if (!rc && want_pairs) rc = said(somhip_conn_create(pak_engine(), &conn));
+  if (!rc && distortion_radius >= 0.0f) rc = said(somhip_distortion_create(m.cb, &dist));
   for (long first = 0; !rc && first < n; first += buffer) {      /* hits, qsum and the float chain go from buffer to buffer, */
     somhip_quality_totals t;                                      /* and one pair table takes the pairs of them all */
     const long count = buffer < n - first ? buffer : n - first;
@@ -661,6 +663,13 @@ int find_map_quality(struct teach_params *teach, long buffer, int want_pairs, st
     if (rc) break;
     q->qerror = t.qerror;
     q->searched += t.searched; q->topo_defined += t.topo_defined; q->topo_errors += t.topo_errors;
+    if (dist) rc = said(somhip_distortion_accumulate(dist, m.cb, m.ds, first, count));   /* the chains go from buffer to buffer too */
+  }
+  if (!rc && dist) {
+    somhip_distortion_totals dt;
+    q->unit_energy = calloc(noc + 1, sizeof *q->unit_energy);
+    rc = said(somhip_distortion_evaluate(dist, m.cb, distortion_radius, q->unit_energy, &dt));
+    if (!rc) { q->energy = dt.energy; q->scale = dt.scale; q->distortion_samples = dt.samples; }
   }
   if (!rc && conn) {
     int64_t pairs = 0;
@@ -674,14 +683,15 @@ int find_map_quality(struct teach_params *teach, long buffer, int want_pairs, st
     }
   }
   if (conn) somhip_conn_destroy(conn);
+  if (dist) somhip_distortion_destroy(dist);
   mirrors_close(&m);
   if (rc) free_map_quality(q);
   return rc;
 }
 void free_map_quality(struct map_quality *q)
 {
-  free(q->hits); free(q->qsum); free(q->b1); free(q->b2); free(q->pair_count);
-  q->hits = NULL; q->qsum = NULL; q->b1 = q->b2 = NULL; q->pair_count = NULL; q->n_pairs = 0;
+  free(q->hits); free(q->qsum); free(q->b1); free(q->b2); free(q->pair_count); free(q->unit_energy);
+  q->hits = NULL; q->qsum = NULL; q->b1 = q->b2 = NULL; q->pair_count = NULL; q->n_pairs = 0; q->unit_energy = NULL;
 }
 
 /* the rows [first, first + count) of data as a device data set of their own: uploaded, or generated in place */
