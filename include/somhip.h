@@ -609,7 +609,8 @@ int  somhip_qerror2(somhip_codebook *cb, somhip_dataset *ds, float radius, int64
  * order and an element-wise MIN across shards is exactly find_winner_euc over the
  * whole codebook, lowest index winning ties (lvq_pak.c:79).  "No winner in this shard"
  * is 0x7FFFFFFFFFFFFFFF, so every key is non-negative as int64 and a SIGNED 64-bit MIN
- * (all that torch.distributed / RCCL offer) orders them the same way. */
+ * (all that torch.distributed / RCCL offer) orders them the same way.  A row at FLT_MAX or
+ * beyond, or at NaN, beats nothing (lvq_pak.c:56): a sample with only such rows has that key too. */
 int  somhip_batch_winner_keys(somhip_codebook *cb, somhip_dataset *ds, int64_t first,
                               int64_t count, uint64_t *dev_keys);
 int  somhip_som_batch_update(somhip_codebook *cb, somhip_dataset *ds, const somhip_som_params *p,
@@ -631,7 +632,8 @@ int  somhip_som_batch_update(somhip_codebook *cb, somhip_dataset *ds, const somh
  * remove rows that provably cannot win).  The three calls of one search share the engine's scratch memory: nothing else
  * may run on the engine between them (a call that is not the continuation of the search begun -- out of order, another
  * codebook, data set or range, a whole search in between -- is refused with an error).  somhip_shard_exchange_available: 1 if this shape takes the path (bf16 pre-filter,
- * dim a multiple of 32, 225 <= count <= 65504, no masks), else 0 -- every rank must take the same path, so a host
+ * ceil(ceil(dim / 4) / 2) a multiple of 4 -- dim 25..32, 57..64, 89..96, ... --, at least 64 rows, 225 <= count <= 65504,
+ * no masks), else 0 -- every rank must take the same path, so a host
  * all-reduces the answer (MIN) once per run. */
 int  somhip_shard_exchange_available(somhip_codebook *cb, somhip_dataset *ds, int64_t count);
 int  somhip_shard_winner_begin(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count,

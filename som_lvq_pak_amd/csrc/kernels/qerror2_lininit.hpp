@@ -185,10 +185,11 @@ __global__ __launch_bounds__(256) void k_column_minmax(const float *__restrict__
 }
 
 // keys handed to a host-side collective: signed 64-bit MIN must order them like unsigned MIN, so
-// the all-ones "no winner" key becomes INT64_MAX (still >= FLT_MAX in its distance half)
+// the all-ones "no winner" key becomes INT64_MAX (still >= FLT_MAX in its distance half) -- and so does the key of a
+// row at FLT_MAX or beyond, or at NaN, which beats nothing (lvq_pak.c:56): one "no winner" key, as include/somhip.h states
 __global__ void k_clamp_keys(uint64_t *__restrict__ keys, int64_t n) {
   int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (i < n && (keys[i] >> 63)) keys[i] = 0x7FFFFFFFFFFFFFFFull;
+  if (i < n && static_cast<uint32_t>(keys[i] >> 32) >= FLT_MAX_BITS) keys[i] = 0x7FFFFFFFFFFFFFFFull;
 }
 
 __global__ void k_fill_u64(uint64_t *p, int64_t n, uint64_t v) {

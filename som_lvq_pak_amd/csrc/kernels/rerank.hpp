@@ -53,7 +53,8 @@ __global__ __launch_bounds__(256) void k_rerank(CbView cb, const float *__restri
       // same arithmetic and order as k_scan_exact / k_som_online_step, loads pipelined
       const float acc = vec ? online_stream<false, true, false, true, 8>(cb, g, lane, false, 0.f, x, x, nullptr, nullptr)
                             : online_stream<false, true, false, false, 8>(cb, g, lane, false, 0.f, x, x, nullptr, nullptr);
-      const bool ok = mine && row < cb.n;
+      // (a row at FLT_MAX or beyond, or at NaN, beats nothing, lvq_pak.c:56: the sample keeps the preset "no winner" key)
+      const bool ok = mine && row < cb.n && acc < __uint_as_float(FLT_MAX_BITS);
       const uint64_t k = ok ? make_key(acc, unit_of_row(cb, row)) : KEY_NONE;
       best = k < best ? k : best;
       ngroups_done++;
@@ -886,7 +887,7 @@ __global__ __launch_bounds__(256) void k_rerank_pairs(CbView cb, const float *__
 #undef QADD
 #undef QB
     }
-    if (j == 0) {
+    if (j == 0 && acc < __uint_as_float(FLT_MAX_BITS)) {   // (as K2r: FLT_MAX, +inf and NaN beat nothing)
       const uint64_t k = make_key(acc, unit_of_row(cb, row));
       atomicMin(reinterpret_cast<unsigned long long *>(keys + pr.x), static_cast<unsigned long long>(k));
     }
