@@ -430,6 +430,65 @@ int  somhip_batchmap_finish(somhip_codebook *cb, float r, int64_t group_first, i
 int  somhip_batchmap_end(somhip_codebook *cb);
 int  somhip_batchmap_state(somhip_codebook *cb, void **dev_state, int64_t *bytes);
 
+/* ---- batch GLVQ (K9; no reference function) ---------------------------------------
+ * Sato and Yamada's Generalized LVQ as full-batch gradient steps: E = mean_s f(mu_s), mu = (d+ - d-) / (d+ + d-), d+ the
+ * squared distance to the nearest row of the sample's class and d- to the nearest row of any other class.  No dependence
+ * on the order of the data beyond the order of its sums; the same bits on every run.
+ * One call runs epochs t = start_epoch .. start_epoch + count - 1 of a run of T = epochs epochs over data rows
+ * (first + s) % n_rows, s = 0 .. n-1.  Per epoch:
+ *   1. alpha_t = alpha * (float)(T - t) / (float)T, in float (LVQ_PAK's linear rate)
+ *   2. per sample, against the codebook as the epoch found it: (d+, i+) = the smallest find_winner_euc squared distance
+ *      (fp32: sub, mul, add in dimension order, three roundings) over the rows whose label equals the sample's, and that
+ *      row; (d-, i-) the same over the rows whose label differs; the lowest row index among equal distances
+ *   3. per sample in fp64, every operation one rounding in the order written: dp = (double)d+, dm = (double)d-,
+ *      D = dp + dm; identity (sigmoid_beta == 0): mu = (dp - dm) / D, f = mu, fp = 1; sigmoid: f = 1 / (1 + exp(-beta * mu)),
+ *      fp = beta * f * (1 - f); xi+ = ((4.0 * fp) * dm) / (D * D), xi- = ((4.0 * fp) * dp) / (D * D); D == 0: mu = 0,
+ *      xi+ = xi- = 0.  The sample counts as correct when the key (d+, i+) is smaller than the key (d-, i-)
+ *   4. per row j, each sum ONE chain of fp64 additions from +0.0 in data order, no floating-point atomics: over the samples
+ *      with i+ = j: Sp[j][k] = sum xi+ * (double)x[k] (multiply, then add), sp[j] = sum xi+, cost[j] = sum f, np[j] their
+ *      number (uint32); over the samples with i- = j: Sm[j][k] = sum xi- * (double)x[k], sm[j] = sum xi-, nm[j]
+ *   5. with W = (double)w_j[k] and a = (double)alpha_t / (double)n: g = (Sp[j][k] - sp[j] * W) - (Sm[j][k] - sm[j] * W),
+ *      w_j[k] = (float)(W + a * g); a row with np[j] == nm[j] == 0 keeps its bits
+ * cost_out (host, [count], or NULL): per epoch (the fp64 chain over cost[j] in row order, formed on the host) / n;
+ * correct_out (host, [count], or NULL): the number of correct samples.  Both describe the codebook the epoch started from.
+ * alpha has the unit of a squared distance (the step is alpha_t times a mean of xi (x - w), and xi is 1 / distance^2).
+ * Refused, with a message that names the entry point, before anything is launched and with the codebook untouched: a
+ * codebook or data set without labels, x components in the data, a sharded codebook, a dimension mismatch, a data label no
+ * codebook row carries, a codebook whose rows all carry one label, n <= 0, n >= 2^32, first < 0, epochs < 1, epochs
+ * outside [0, epochs), alpha negative or NaN, sigmoid_beta negative or NaN.  Fixed points and weights are not taken. */
+typedef struct somhip_glvq_params {
+  int64_t epochs;        /* T */
+  int64_t start_epoch, count;
+  int64_t first, n;      /* the data rows of every epoch */
+  float   alpha;         /* the rate the run starts from */
+  float   sigmoid_beta;  /* 0: f is the identity */
+} somhip_glvq_params;
+int  somhip_glvq_train(somhip_codebook *cb, somhip_dataset *ds, const somhip_glvq_params *p, double *cost_out /*[count] or NULL*/,
+                       int64_t *correct_out /*[count] or NULL*/);
+/* The stages somhip_glvq_train is made of, each on its own.
+ * _search: step 2 to the host, dplus / dminus [n] and iplus / iminus [n].  route: SOMHIP_GLVQ_DIRECT -- every sample
+ * against every row by the class-wise scan; SOMHIP_GLVQ_LIST -- the engine's exact top-8 lists, each role's first entry,
+ * and the class-wise scan over the samples whose list lacks a role; SOMHIP_GLVQ_PLAN -- what the training takes for this
+ * shape (somhip_debug_glvq_plan).  remainder (or NULL): the samples that went through the class-wise scan.
+ * _sums: steps 2-4 to the host: xi_plus, xi_minus, f [n]; sums_plus, sums_minus [n_rows of the codebook][dim + 1], the
+ * last column sp / sm; n_plus, n_minus, cost [n_rows]; *correct.
+ * _update: step 5 with a = (double)alpha_t / (double)n on host-supplied sums; it writes the codebook. */
+#define SOMHIP_GLVQ_PLAN   (-1)
+#define SOMHIP_GLVQ_DIRECT 0
+#define SOMHIP_GLVQ_LIST   1
+int  somhip_debug_glvq_plan(int64_t n_rows, int dim, int64_t n, int32_t *route);
+int  somhip_debug_glvq_search(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, int route, float *dplus,
+                              int32_t *iplus, float *dminus, int32_t *iminus, int64_t *remainder);
+int  somhip_debug_glvq_sums(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, float sigmoid_beta,
+                            double *xi_plus, double *xi_minus, double *f, double *sums_plus, uint32_t *n_plus,
+                            double *sums_minus, uint32_t *n_minus, double *cost, int64_t *correct);
+int  somhip_debug_glvq_update(somhip_codebook *cb, float alpha_t, int64_t n, const double *sums_plus, const uint32_t *n_plus,
+                              const double *sums_minus, const uint32_t *n_minus);
+/* HIP-event totals of its stages since somhip_timing_reset, while somhip_timing_enable is on (not in the table of
+ * somhip_kernel_count): [0] the search (the list route as one span around the top-8 search, the pick and the remainder's
+ * scan), [1] the terms and the grouping (scans of the counts, sorts by winner), [2] the sums, [3] the update */
+int  somhip_glvq_timing(somhip_engine *e, int64_t launches[4], double total_ms[4]);
+
 /* ---- map distortion (K1d; no reference function) ----------------------------------
  * The distortion measure of a map (Lampinen and Oja; SOM Toolbox's som_distortion): its energy at a neighbourhood radius,
  *   E(r) = sum over samples s, sum over units j, of  h_r(c(s), j) * || x_s - m_j ||^2 ,

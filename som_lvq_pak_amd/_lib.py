@@ -46,6 +46,11 @@ class BatchmapParams(C.Structure):
                 ("first", C.c_int64), ("n", C.c_int64)]
 
 
+class GlvqParams(C.Structure):
+    _fields_ = [("epochs", C.c_int64), ("start_epoch", C.c_int64), ("count", C.c_int64), ("first", C.c_int64), ("n", C.c_int64),
+                ("alpha", C.c_float), ("sigmoid_beta", C.c_float)]
+
+
 # name -> (restype, argtypes); exactly the symbols include/somhip.h declares
 SIGNATURES = {
     "somhip_last_error": (C.c_char_p, []),
@@ -121,6 +126,14 @@ SIGNATURES = {
     "somhip_batchmap_finish": (C.c_int, [C.c_void_p, C.c_float, C.c_int64, C.c_int64, c_float_p]),
     "somhip_batchmap_end": (C.c_int, [C.c_void_p]),
     "somhip_batchmap_state": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), c_i64_p]),
+    "somhip_glvq_train": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(GlvqParams), c_double_p, c_i64_p]),
+    "somhip_debug_glvq_plan": (C.c_int, [C.c_int64, C.c_int, C.c_int64, c_i32_p]),
+    "somhip_debug_glvq_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, c_float_p, c_i32_p, c_float_p,
+                                           c_i32_p, c_i64_p]),
+    "somhip_debug_glvq_sums": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_float, c_double_p, c_double_p,
+                                         c_double_p, c_double_p, c_u32_p, c_double_p, c_u32_p, c_double_p, c_i64_p]),
+    "somhip_debug_glvq_update": (C.c_int, [C.c_void_p, C.c_float, C.c_int64, c_double_p, c_u32_p, c_double_p, c_u32_p]),
+    "somhip_glvq_timing": (C.c_int, [C.c_void_p, c_i64_p, c_double_p]),
     "somhip_distortion_create": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "somhip_distortion_destroy": (None, [C.c_void_p]),
     "somhip_distortion_clear": (C.c_int, [C.c_void_p]),

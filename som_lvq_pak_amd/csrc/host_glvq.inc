@@ -1,0 +1,305 @@
+// host_glvq.inc -- K9, batch GLVQ: per epoch the class-wise winners of every sample against the frozen codebook (search),
+// the per-sample terms and the grouping by winner of both roles (terms), the per-prototype ordered fp64 sums (sums) and
+// the update; the four stages on their own for the tests
+// (included by somhip.hip behind host_batchmap.inc: one translation unit, shared static helpers, rocPRIM's sort)
+
+// The route of the search, for every caller: a function of the shape alone.  The list route costs one exact top-8 search
+// more than the class-wise scan of its remainder, and the remainder is every sample wherever the eight nearest rows of a
+// sample carry one label (measured: all of 100 000 samples at both bench shapes, whose classes are separate clusters with
+// 100 rows each).  The shape cannot say how the classes overlap, so the list route is taken where its worst case is cheap:
+// where the top-8 search has its two-level pre-filter (512 row groups) and rows are long, it costs 4 % of the class-wise
+// scan (100 000 x 1024: 58 of 1451 ms) and can save up to 96 % of it; at 10 000 x 256 it costs 45 % (14 of 31 ms) and the
+// class-wise scan runs alone.  Between those two shapes nothing is measured (DESIGN.md K9).
+constexpr int64_t GLVQ_LIST_MIN_ROWS = 32768;
+constexpr int GLVQ_LIST_MIN_DIM = 512;
+constexpr int GLVQ_LIST_WIDTH = 8;              // the entries of a sample's list: the widest exact top-K search
+constexpr int64_t GLVQ_CHUNK = 16384;           // samples of a class-wise scan launch: whole tiles (dim 1024: 64 MiB of sample tiles)
+static int glvq_plan(int64_t rows, int dim, int64_t n) {
+  return rows >= GLVQ_LIST_MIN_ROWS && dim >= GLVQ_LIST_MIN_DIM && n >= MFMA_MIN_SAMPLES ? SOMHIP_GLVQ_LIST : SOMHIP_GLVQ_DIRECT;
+}
+
+// The device arrays of a GLVQ call.  SLOT_GLVQ, per row: [S: 2 x rows x (dim + 1) doubles][cost][hits: 2 x rows]
+// [starts: 2 x (rows + 1)][correct, the remainder's length].  SLOT_GLVQ_LIST, per sample: [keys2][xi: 2 x n][f][win: 2 x n]
+// [idx][the sorted winners][list: 2 x n][the remainder][the sort's own room].  Role + comes first in every pair.
+struct GlvqBufs {
+  double *S = nullptr, *cost = nullptr, *xi = nullptr, *f = nullptr;
+  uint64_t *keys2 = nullptr;
+  uint32_t *hits = nullptr, *starts = nullptr, *correct = nullptr, *rem_count = nullptr;
+  uint32_t *win = nullptr, *idx = nullptr, *win_sorted = nullptr, *list = nullptr, *rem = nullptr;
+  void *sort_tmp = nullptr;
+  size_t sort_bytes = 0;
+  unsigned sort_bits = 0;
+};
+// n: the samples of the call, 0 where only the update runs
+static int glvq_bind(somhip_codebook *cb, int64_t n, GlvqBufs *b) {
+  somhip_engine *e = cb->e;
+  const size_t units = (size_t)cb->v.n, ns = (size_t)n, s_len = 2 * units * (size_t)(cb->v.d + 1);
+  void *p;
+  CHK(engine_scratch(e, SLOT_GLVQ, sizeof(double) * (s_len + units) + sizeof(uint32_t) * (4 * units + 4), &p));
+  b->S = (double *)p;
+  b->cost = b->S + s_len;
+  b->hits = reinterpret_cast<uint32_t *>(b->cost + units);
+  b->starts = b->hits + 2 * units;
+  b->correct = b->starts + 2 * (units + 1);
+  b->rem_count = b->correct + 1;
+  if (n <= 0) return 0;
+  for (size_t u = units; u; u >>= 1) b->sort_bits++;
+  const hipError_t er = rocprim::radix_sort_pairs(nullptr, b->sort_bytes, b->win, b->win_sorted, b->idx, b->list, ns, 0u, b->sort_bits, e->stream);
+  if (er != hipSuccess) return fail("glvq: the sort's size query failed: %s", hipGetErrorString(er));
+  const size_t arrays = (sizeof(uint64_t) * 2 * ns + sizeof(double) * 3 * ns + sizeof(uint32_t) * 7 * ns + 255) / 256 * 256;
+  CHK(engine_scratch(e, SLOT_GLVQ_LIST, arrays + b->sort_bytes, &p));
+  b->keys2 = (uint64_t *)p;
+  b->xi = reinterpret_cast<double *>(b->keys2 + 2 * ns);
+  b->f = b->xi + 2 * ns;
+  b->win = reinterpret_cast<uint32_t *>(b->f + ns);
+  b->idx = b->win + 2 * ns;
+  b->win_sorted = b->idx + ns;
+  b->list = b->win_sorted + ns;
+  b->rem = b->list + 2 * ns;
+  b->sort_tmp = (char *)p + arrays;
+  return 0;
+}
+
+// The class-wise scan over `count` samples of the run into b.keys2 (which holds KEY_NONE for them): the run's samples
+// base .. base + count - 1, or the listed ones sel[0 .. count).  Chunks of whole sample tiles; the sample labels are on the
+// device.  timed: its launches count under the search's id (the list route times one span around everything instead).
+static int glvq_scan_class(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t base, int64_t count, const uint32_t *sel,
+                           const GlvqBufs &b, bool timed) {
+  somhip_engine *e = cb->e;
+  const int64_t f0 = first % ds->n;
+  const bool wide = cb->v.ngroups >= 4 * GLVQ_R;
+  const dim3 block(256);
+  for (int64_t off = 0; off < count; off += GLVQ_CHUNK) {
+    const int64_t c = std::min(GLVQ_CHUNK, count - off), nsb = (c + GLVQ_S - 1) / GLVQ_S;
+    float4 *xt;
+    CHK(scratch(e, SLOT_SAMPLES, (size_t)nsb * cb->v.d4 * GLVQ_S, &xt));
+    if (sel)
+      CHK(LAUNCH(e, k_glvq_pack_listed<GLVQ_S>, dim3((unsigned)nsb), block, 0, ds->d_rows, ds->n, ds->d, cb->v.d4, f0, sel + off, c, xt));
+    else
+      CHK(LAUNCH_TIMED(e, KID_PACK_SAMPLES, k_pack_samples<GLVQ_S>, dim3((unsigned)nsb), block, 0, ds->d_rows, ds->n, ds->d, cb->v.d4,
+          (f0 + base + off) % ds->n, c, xt));
+    const dim3 grid((unsigned)nsb, (unsigned)((cb->v.ngroups + (wide ? 4 * GLVQ_R : 4) - 1) / (wide ? 4 * GLVQ_R : 4)));
+    const uint32_t *sl = sel ? sel + off : nullptr;
+    LaunchTimer t(e, timed ? KID_GLVQ_SEARCH : -1);
+    if (wide)
+      CHK(LAUNCH(e, (k_scan_class<GLVQ_S, GLVQ_R>), grid, block, 0, cb->v, xt, c, cb->d_labels, ds->d_labels, ds->n, f0, base + off, sl, b.keys2));
+    else
+      CHK(LAUNCH(e, (k_scan_class<GLVQ_S, 1>), grid, block, 0, cb->v, xt, c, cb->d_labels, ds->d_labels, ds->n, f0, base + off, sl, b.keys2));
+  }
+  e->samples_searched += (uint64_t)count;
+  return 0;
+}
+
+// Step 2: b.keys2 <- the two keys of every sample of the run, by the route given.  remainder (or null): the samples the
+// class-wise scan took.
+static int glvq_search_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, int route, const GlvqBufs &b,
+                             int64_t *remainder) {
+  somhip_engine *e = cb->e;
+  if (route == SOMHIP_GLVQ_DIRECT) {
+    HIPCHK(hipMemsetAsync(b.keys2, 0xFF, sizeof(uint64_t) * 2 * (size_t)n, e->stream));
+    if (remainder) *remainder = n;
+    return glvq_scan_class(cb, ds, first, 0, n, nullptr, b, true);
+  }
+  LaunchTimer span(e, KID_GLVQ_SEARCH);
+  HIPCHK(hipMemsetAsync(b.rem_count, 0, sizeof(uint32_t), e->stream));
+  const int64_t f0 = first % ds->n;
+  CHK(knn_chunk_keys(cb, ds, first, n, GLVQ_LIST_WIDTH, 0, [&](int64_t off, int64_t, int64_t c, const uint64_t *dk, int stride) {
+    return LAUNCH(e, k_glvq_pick, dim3((unsigned)((c + GLVQ_THREADS - 1) / GLVQ_THREADS)), dim3(GLVQ_THREADS), 0, dk, stride, GLVQ_LIST_WIDTH, off, c,
+                  (uint32_t)cb->v.n, cb->d_labels, ds->d_labels, ds->n, f0, b.keys2, b.rem, b.rem_count);
+  }));
+  uint32_t nrem = 0;
+  CHK(to_host_sync(e, &nrem, b.rem_count, 1));      // (the remainder's launches are sized by it)
+  if (remainder) *remainder = nrem;
+  if (nrem) CHK(glvq_scan_class(cb, ds, first, 0, nrem, b.rem, b, false));
+  return 0;
+}
+
+// Step 3 and the grouping: the terms, then per role K8's scan of the counts and the stable sort of (winner, sample) by
+// winner, which leaves the samples of row u in role r at list[r][starts[r][u] .. starts[r][u + 1]) in data order.
+static int glvq_terms_stage(somhip_codebook *cb, int64_t n, float beta, const GlvqBufs &b) {
+  somhip_engine *e = cb->e;
+  const uint32_t units = (uint32_t)cb->v.n;
+  HIPCHK(hipMemsetAsync(b.hits, 0, sizeof(uint32_t) * 2 * (size_t)units, e->stream));
+  HIPCHK(hipMemsetAsync(b.correct, 0, sizeof(uint32_t), e->stream));
+  CHK(LAUNCH_TIMED(e, KID_GLVQ_TERMS, k_glvq_terms, dim3((unsigned)((n + GLVQ_THREADS - 1) / GLVQ_THREADS)), dim3(GLVQ_THREADS), 0, b.keys2, n, units,
+      (double)beta, b.xi, b.f, b.win, b.idx, b.hits, b.correct));
+  for (int role = 0; role < 2; role++) {
+    CHK(LAUNCH_TIMED(e, KID_GLVQ_TERMS, k_batchmap_starts, dim3(1), dim3(BM_SCAN_THREADS), 0, b.hits + (size_t)role * units, units,
+        b.starts + (size_t)role * (units + 1)));
+    LaunchTimer t(e, KID_GLVQ_TERMS);                                    // (rocPRIM's own launches, on the engine's stream)
+    size_t bytes = b.sort_bytes;
+    const hipError_t er = rocprim::radix_sort_pairs(b.sort_tmp, bytes, b.win + (size_t)role * n, b.win_sorted, b.idx, b.list + (size_t)role * n,
+                                                    (size_t)n, 0u, b.sort_bits, e->stream);
+    if (er != hipSuccess) return fail("glvq: the sort by winner failed: %s", hipGetErrorString(er));
+  }
+  return 0;
+}
+// Step 4: b.S and b.cost from the lists
+static int glvq_sums_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, const GlvqBufs &b) {
+  const dim3 grid((unsigned)cb->v.n, (unsigned)((cb->v.d + 2 + BM_SUM_DIMS - 1) / BM_SUM_DIMS), 2);
+  return LAUNCH_TIMED(cb->e, KID_GLVQ_SUMS, k_glvq_sums, grid, dim3(BM_SUM_DIMS), 0, ds->d_rows, ds->n, ds->d, first % ds->n, n, (uint32_t)cb->v.n,
+                      b.list, b.starts, b.xi, b.f, b.S, b.cost);
+}
+// Step 5: the rows from b.S and b.hits
+static int glvq_update_stage(somhip_codebook *cb, float alpha_t, int64_t n, const GlvqBufs &b) {
+  const int64_t threads = cb->v.ngroups * cb->v.d4 * WAVE;
+  cb->prep_valid = false;
+  cb->bm_open = false;
+  return LAUNCH_TIMED(cb->e, KID_GLVQ_UPDATE, k_glvq_update, dim3((unsigned)((threads + GLVQ_THREADS - 1) / GLVQ_THREADS)), dim3(GLVQ_THREADS), 0, cb->v,
+                      b.S, b.hits, (double)alpha_t / (double)n);
+}
+
+// what every GLVQ entry point refuses before anything is launched
+static int glvq_check_codebook(const somhip_codebook *cb, const char *who) {
+  if (!cb->d_labels) return fail("%s: the codebook has no labels", who);
+  if (is_shard(cb)) return fail("%s: sharded codebook not supported (a shard does not hold the other shards' rows)", who);
+  return 0;
+}
+static int glvq_check(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, const char *who) {
+  CHK(check_pair(cb, ds, who));
+  CHK(glvq_check_codebook(cb, who));
+  if (ds->labels.empty()) return fail("%s: the data set has no labels", who);
+  if (ds->d_mask) return fail("%s: data with masked components (x) is not supported", who);
+  if (first < 0) return fail("%s: first row %lld < 0", who, (long long)first);
+  if (n <= 0) return fail("%s: n %lld <= 0", who, (long long)n);
+  if (n >= (int64_t)1 << 32) return fail("%s: n %lld does not fit the 32-bit counts", who, (long long)n);
+  somhip_engine *e = cb->e;
+  HIPCHK(hipSetDevice(e->device));
+  std::vector<int32_t> cl((size_t)cb->v.n);
+  CHK(to_host_sync(e, cl.data(), cb->d_labels, cl.size()));
+  std::sort(cl.begin(), cl.end());
+  if (cl.front() == cl.back()) return fail("%s: every row of the codebook carries label %d (no other class to be wrong with)", who, (int)cl.front());
+  for (int64_t s = 0; s < std::min(n, ds->n); s++) {
+    const int32_t l = ds->labels[(size_t)((first + s) % ds->n)];
+    if (!std::binary_search(cl.begin(), cl.end(), l))
+      return fail("%s: data row %lld carries label %d, which no row of the codebook carries", who, (long long)((first + s) % ds->n), (int)l);
+  }
+  return dataset_device_labels(ds);
+}
+static int glvq_check_beta(float beta, const char *who) {
+  return beta >= 0.0f ? 0 : fail("%s: sigmoid_beta %g is negative or not a number", who, (double)beta);
+}
+
+extern "C" int somhip_debug_glvq_plan(int64_t n_rows, int dim, int64_t n, int32_t *route) try {
+  if (!route) return fail("somhip_debug_glvq_plan: null output");
+  if (n_rows <= 0 || dim <= 0 || n <= 0) return fail("somhip_debug_glvq_plan: bad shape (%lld x %d, %lld samples)", (long long)n_rows, dim, (long long)n);
+  *route = glvq_plan(n_rows, dim, n);
+  return 0;
+} ABI_CATCH(somhip_debug_glvq_plan)
+
+extern "C" int somhip_glvq_train(somhip_codebook *cb, somhip_dataset *ds, const somhip_glvq_params *p, double *cost_out,
+                                 int64_t *correct_out) try {
+  const char *who = "somhip_glvq_train";
+  if (!p) return fail("%s: null parameters", who);
+  if (!cb || !ds) return fail("%s: null handle", who);
+  if (p->epochs < 1) return fail("%s: epochs %lld < 1", who, (long long)p->epochs);
+  if (p->start_epoch < 0 || p->count < 0 || p->start_epoch + p->count > p->epochs)
+    return fail("%s: epochs [%lld, %lld) outside [0, %lld)", who, (long long)p->start_epoch, (long long)(p->start_epoch + p->count), (long long)p->epochs);
+  if (!(p->alpha >= 0.0f)) return fail("%s: alpha %g is negative or not a number", who, (double)p->alpha);
+  CHK(glvq_check_beta(p->sigmoid_beta, who));
+  CHK(glvq_check(cb, ds, p->first, p->n, who));
+  somhip_engine *e = cb->e;
+  GlvqBufs b;
+  CHK(glvq_bind(cb, p->n, &b));
+  const int route = glvq_plan(cb->v.n, cb->v.d, p->n);
+  const float T = (float)p->epochs;
+  std::vector<double> hc((size_t)(cost_out ? cb->v.n : 0));
+  for (int64_t t = p->start_epoch; t < p->start_epoch + p->count; t++) {
+    const float alpha_t = p->alpha * (float)(p->epochs - t) / T;        // LVQ_PAK's linear rate over epochs
+    CHK(glvq_search_stage(cb, ds, p->first, p->n, route, b, nullptr));
+    CHK(glvq_terms_stage(cb, p->n, p->sigmoid_beta, b));
+    CHK(glvq_sums_stage(cb, ds, p->first, p->n, b));
+    if (cost_out || correct_out) {
+      uint32_t correct = 0;
+      if (cost_out) CHK(to_host(e, hc.data(), b.cost, hc.size()));
+      CHK(to_host_sync(e, &correct, b.correct, 1));
+      if (cost_out) {
+        double chain = 0.0;
+        for (double c : hc) chain += c;
+        cost_out[t - p->start_epoch] = chain / (double)p->n;
+      }
+      if (correct_out) correct_out[t - p->start_epoch] = (int64_t)correct;
+    }
+    CHK(glvq_update_stage(cb, alpha_t, p->n, b));
+  }
+  HIPCHK(hipStreamSynchronize(e->stream));
+  return 0;
+} ABI_CATCH(somhip_glvq_train)
+
+extern "C" int somhip_debug_glvq_search(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, int route, float *dplus,
+                                        int32_t *iplus, float *dminus, int32_t *iminus, int64_t *remainder) try {
+  const char *who = "somhip_debug_glvq_search";
+  if (!dplus || !iplus || !dminus || !iminus) return fail("%s: null output", who);
+  if (route != SOMHIP_GLVQ_PLAN && route != SOMHIP_GLVQ_DIRECT && route != SOMHIP_GLVQ_LIST) return fail("%s: unknown route %d", who, route);
+  CHK(glvq_check(cb, ds, first, n, who));
+  somhip_engine *e = cb->e;
+  GlvqBufs b;
+  CHK(glvq_bind(cb, n, &b));
+  CHK(glvq_search_stage(cb, ds, first, n, route == SOMHIP_GLVQ_PLAN ? glvq_plan(cb->v.n, cb->v.d, n) : route, b, remainder));
+  std::vector<uint64_t> hk(2 * (size_t)n);
+  CHK(to_host_sync(e, hk.data(), b.keys2, hk.size()));
+  for (int64_t s = 0; s < n; s++) {
+    decode_key(hk[2 * (size_t)s], false, iplus + s, dplus + s);
+    decode_key(hk[2 * (size_t)s + 1], false, iminus + s, dminus + s);
+  }
+  return 0;
+} ABI_CATCH(somhip_debug_glvq_search)
+
+extern "C" int somhip_debug_glvq_sums(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, float sigmoid_beta,
+                                      double *xi_plus, double *xi_minus, double *f, double *sums_plus, uint32_t *n_plus,
+                                      double *sums_minus, uint32_t *n_minus, double *cost, int64_t *correct) try {
+  const char *who = "somhip_debug_glvq_sums";
+  if (!xi_plus || !xi_minus || !f || !sums_plus || !n_plus || !sums_minus || !n_minus || !cost || !correct) return fail("%s: null output", who);
+  CHK(glvq_check_beta(sigmoid_beta, who));
+  CHK(glvq_check(cb, ds, first, n, who));
+  somhip_engine *e = cb->e;
+  GlvqBufs b;
+  CHK(glvq_bind(cb, n, &b));
+  CHK(glvq_search_stage(cb, ds, first, n, glvq_plan(cb->v.n, cb->v.d, n), b, nullptr));
+  CHK(glvq_terms_stage(cb, n, sigmoid_beta, b));
+  CHK(glvq_sums_stage(cb, ds, first, n, b));
+  const size_t units = (size_t)cb->v.n, ld = (size_t)cb->v.d + 1, ns = (size_t)n;
+  uint32_t hcorrect = 0;
+  CHK(to_host(e, xi_plus, b.xi, ns));
+  CHK(to_host(e, xi_minus, b.xi + ns, ns));
+  CHK(to_host(e, f, b.f, ns));
+  CHK(to_host(e, sums_plus, b.S, units * ld));
+  CHK(to_host(e, sums_minus, b.S + units * ld, units * ld));
+  CHK(to_host(e, n_plus, b.hits, units));
+  CHK(to_host(e, n_minus, b.hits + units, units));
+  CHK(to_host(e, cost, b.cost, units));
+  CHK(to_host_sync(e, &hcorrect, b.correct, 1));
+  *correct = (int64_t)hcorrect;
+  return 0;
+} ABI_CATCH(somhip_debug_glvq_sums)
+
+extern "C" int somhip_debug_glvq_update(somhip_codebook *cb, float alpha_t, int64_t n, const double *sums_plus, const uint32_t *n_plus,
+                                        const double *sums_minus, const uint32_t *n_minus) try {
+  const char *who = "somhip_debug_glvq_update";
+  CHK(check_codebook(cb, sums_plus && n_plus && sums_minus && n_minus, who));
+  CHK(glvq_check_codebook(cb, who));
+  if (n <= 0) return fail("%s: n %lld <= 0", who, (long long)n);
+  somhip_engine *e = cb->e;
+  HIPCHK(hipSetDevice(e->device));
+  GlvqBufs b;
+  CHK(glvq_bind(cb, 0, &b));
+  const size_t units = (size_t)cb->v.n, ld = (size_t)cb->v.d + 1;
+  CHK(to_device(e, b.S, sums_plus, units * ld));
+  CHK(to_device(e, b.S + units * ld, sums_minus, units * ld));
+  CHK(to_device(e, b.hits, n_plus, units));
+  CHK(to_device(e, b.hits + units, n_minus, units));
+  CHK(glvq_update_stage(cb, alpha_t, n, b));
+  HIPCHK(hipStreamSynchronize(e->stream));                              // (the host arrays are read until the copies have run)
+  return 0;
+} ABI_CATCH(somhip_debug_glvq_update)
+
+// HIP-event totals of the stages since somhip_timing_reset, while somhip_timing_enable is on (ids of their own behind the
+// published table): [0] search, [1] terms and grouping, [2] sums, [3] update
+extern "C" int somhip_glvq_timing(somhip_engine *e, int64_t launches[4], double total_ms[4]) try {
+  CHK(check_engine(e, "somhip_glvq_timing"));
+  if (!launches || !total_ms) return fail("somhip_glvq_timing: null output");
+  CHK(timing_flush(e));
+  const int kid[4] = {KID_GLVQ_SEARCH, KID_GLVQ_TERMS, KID_GLVQ_SUMS, KID_GLVQ_UPDATE};
+  for (int i = 0; i < 4; i++) { launches[i] = e->launches[kid[i]]; total_ms[i] = e->total_ms[kid[i]]; }
+  return 0;
+} ABI_CATCH(somhip_glvq_timing)

@@ -834,6 +834,14 @@ extern "C" int somhip_find_winners(somhip_codebook *cb, somhip_dataset *ds, int6
   });
 } ABI_CATCH(somhip_find_winners)
 
+// the device copy of a data set's row labels, made when first wanted (none for a data set without labels)
+static int dataset_device_labels(somhip_dataset *ds) {
+  if (ds->labels.empty() || ds->d_labels) return 0;
+  HIPCHK(hipMalloc((void **)&ds->d_labels, sizeof(int32_t) * (size_t)ds->n));
+  HIPCHK(hipMemcpy(ds->d_labels, ds->labels.data(), sizeof(int32_t) * (size_t)ds->n, hipMemcpyHostToDevice));
+  return 0;
+}
+
 // K1v: the class vote of find_winner_knn's neighbours over a run of samples (include/somhip.h).  Per chunk
 // (knn_chunk_keys, so the routes, the chunks, the wrap and masked data are somhip_find_winners'): the keys, k_knn_vote
 // behind them, one copy of 16 bytes per sample.  A sample with every component masked has no neighbours, whatever its keys say.
@@ -849,10 +857,7 @@ extern "C" int somhip_knn_vote(somhip_codebook *cb, somhip_dataset *ds, int64_t 
   if (count <= 0) return 0;
   somhip_engine *e = cb->e;
   HIPCHK(hipSetDevice(e->device));
-  if (!ds->labels.empty() && !ds->d_labels) {                           // the device copy of the rows' labels, when first wanted
-    HIPCHK(hipMalloc((void **)&ds->d_labels, sizeof(int32_t) * (size_t)ds->n));
-    HIPCHK(hipMemcpy(ds->d_labels, ds->labels.data(), sizeof(int32_t) * (size_t)ds->n, hipMemcpyHostToDevice));
-  }
+  CHK(dataset_device_labels(ds));
   std::vector<int32_t> hv;
   return knn_chunk_keys(cb, ds, first, count, knn, 1, [&](int64_t off, int64_t f, int64_t c, const uint64_t *dk, int stride) {
     int4 *dv;

@@ -31,6 +31,7 @@
 #include "kernels/map_conn.hpp"
 #include "kernels/batchmap.hpp"
 #include "kernels/map_distortion.hpp"
+#include "kernels/glvq.hpp"
 #include "kernels/som_update.hpp"
 #include "kernels/som_update_gemm.hpp"
 #include "kernels/som_online.hpp"

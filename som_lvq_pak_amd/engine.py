@@ -155,6 +155,15 @@ class Engine:
         check(self.lib.somhip_batchmap_timing(self.h, n, ms))
         return {"group": (n[0], ms[0]), "k_batchmap_sums": (n[1], ms[1]), "k_batchmap_combine": (n[2], ms[2])}
 
+    def glvq_timing(self):
+        """(launches, ms) of batch GLVQ's stages while timing is on (somhip_glvq_timing; they are not in timing_table):
+        search = the class-wise scan per chunk, or one span around the list route's top-8 search, pick and remainder;
+        terms = k_glvq_terms, the scans of the counts and the sorts by winner"""
+        n = (C.c_int64 * 4)()
+        ms = (C.c_double * 4)()
+        check(self.lib.somhip_glvq_timing(self.h, n, ms))
+        return {"search": (n[0], ms[0]), "terms": (n[1], ms[1]), "k_glvq_sums": (n[2], ms[2]), "k_glvq_update": (n[3], ms[3])}
+
     def distortion_timing(self):
         """(launches, ms) of map distortion's stages while timing is on (somhip_distortion_timing; they are not in
         timing_table): group = the winners pass per chunk, the scan of the counts and the sort by winner; sums = the
@@ -673,6 +682,78 @@ def batchmap_state(cb):
     addr, nbytes = C.c_void_p(), C.c_int64(0)
     check(cb.e.lib.somhip_batchmap_state(cb.h, C.byref(addr), C.byref(nbytes)))
     return int(addr.value), int(nbytes.value)
+
+
+GLVQ_PLAN, GLVQ_DIRECT, GLVQ_LIST = -1, 0, 1
+
+
+def glvq_alpha(alpha, epochs, t):
+    """alpha_t of epoch t of a GLVQ run of `epochs` epochs from `alpha`: the float the engine forms"""
+    f = np.float32
+    return f(f(f(alpha) * f(epochs - t)) / f(epochs))
+
+
+def glvq_plan(n_rows, dim, n, lib=None):
+    """The route glvq_train's search takes for this shape (somhip_debug_glvq_plan): GLVQ_DIRECT or GLVQ_LIST.  Host
+    arithmetic: no GPU needed."""
+    lib = lib or _lib.load()
+    route = C.c_int32(0)
+    check(lib.somhip_debug_glvq_plan(n_rows, dim, n, C.byref(route)))
+    return route.value
+
+
+def glvq_train(cb, ds, epochs, alpha, sigmoid_beta=0.0, start_epoch=0, count=None, first=0, n=None, stats=True):
+    """Epochs [start_epoch, start_epoch + count) of batch GLVQ over data rows (first + s) % ds.n, s < n (somhip_glvq_train):
+    every epoch is one full-batch gradient step of E = mean f(mu) at the rate glvq_alpha(alpha, epochs, t).  alpha has the
+    unit of a squared distance.  Returns (cost float64[count], correct int64[count]) of the codebook each epoch started
+    from, or None with stats=False."""
+    count = epochs - start_epoch if count is None else count
+    n = ds.n if n is None else n
+    p = _lib.GlvqParams(epochs, start_epoch, count, first, n, alpha, sigmoid_beta)
+    cost = np.zeros(max(count, 0), dtype=np.float64) if stats else None
+    correct = np.zeros(max(count, 0), dtype=np.int64) if stats else None
+    check(cb.e.lib.somhip_glvq_train(cb.h, ds.h, C.byref(p), _p(cost, _lib.c_double_p), _p(correct, _lib.c_i64_p)))
+    return (cost, correct) if stats else None
+
+
+def glvq_search(cb, ds, first=0, n=None, route=GLVQ_PLAN):
+    """The class-wise winner search alone (somhip_debug_glvq_search): (dplus float32[n], iplus int32[n], dminus, iminus,
+    remainder) -- per sample the nearest row of its own class and of any other, and how many samples went through the
+    class-wise scan (all of them on the direct route)"""
+    n = ds.n if n is None else n
+    dp, dm = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.float32)
+    ip, im = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    rem = C.c_int64(0)
+    check(cb.e.lib.somhip_debug_glvq_search(cb.h, ds.h, first, n, route, _p(dp, _lib.c_float_p), _p(ip, _lib.c_i32_p),
+                                            _p(dm, _lib.c_float_p), _p(im, _lib.c_i32_p), C.byref(rem)))
+    return dp, ip, dm, im, rem.value
+
+
+def glvq_sums(cb, ds, first=0, n=None, sigmoid_beta=0.0):
+    """Search, terms and sums of a GLVQ epoch (somhip_debug_glvq_sums), as a dict: xi_plus, xi_minus, f float64[n];
+    sums_plus, sums_minus float64[cb.n, dim + 1] (the last column is the sum of xi); n_plus, n_minus uint32[cb.n];
+    cost float64[cb.n]; correct"""
+    n = ds.n if n is None else n
+    d = lambda *shape: np.zeros(shape, dtype=np.float64)
+    out = {"xi_plus": d(n), "xi_minus": d(n), "f": d(n), "sums_plus": d(cb.n, cb.dim + 1), "sums_minus": d(cb.n, cb.dim + 1),
+           "n_plus": np.zeros(cb.n, dtype=np.uint32), "n_minus": np.zeros(cb.n, dtype=np.uint32), "cost": d(cb.n)}
+    correct = C.c_int64(0)
+    dp, up = _lib.c_double_p, _lib.c_u32_p
+    check(cb.e.lib.somhip_debug_glvq_sums(cb.h, ds.h, first, n, sigmoid_beta, _p(out["xi_plus"], dp), _p(out["xi_minus"], dp),
+                                          _p(out["f"], dp), _p(out["sums_plus"], dp), _p(out["n_plus"], up),
+                                          _p(out["sums_minus"], dp), _p(out["n_minus"], up), _p(out["cost"], dp), C.byref(correct)))
+    out["correct"] = correct.value
+    return out
+
+
+def glvq_update(cb, alpha_t, n, sums_plus, n_plus, sums_minus, n_minus):
+    """The update alone (somhip_debug_glvq_update) from host-supplied sums as glvq_sums returns them, with
+    a = float64(alpha_t) / n; a row with n_plus == n_minus == 0 keeps its bits"""
+    sp, sm = np.ascontiguousarray(sums_plus, dtype=np.float64), np.ascontiguousarray(sums_minus, dtype=np.float64)
+    cp, cm = np.ascontiguousarray(n_plus, dtype=np.uint32), np.ascontiguousarray(n_minus, dtype=np.uint32)
+    assert sp.shape == sm.shape == (cb.n, cb.dim + 1) and cp.shape == cm.shape == (cb.n,)
+    check(cb.e.lib.somhip_debug_glvq_update(cb.h, float(np.float32(alpha_t)), n, _p(sp, _lib.c_double_p), _p(cp, _lib.c_u32_p),
+                                            _p(sm, _lib.c_double_p), _p(cm, _lib.c_u32_p)))
 
 
 def _distortion_totals(tot):

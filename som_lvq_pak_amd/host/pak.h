@@ -194,6 +194,10 @@ int som_batchmap_training(struct teach_params *teach, long epochs, long buffer, 
  * ends with the map in teach->codes and the epochs' qerror in qerror ([epochs]) and runs after(teach, arg) -- print, save */
 int som_batchmap_training_multi(struct teach_params *teach, long epochs, float *qerror, int gpus,
                                 int (*after)(struct teach_params *, void *), void *arg);
+/* batch GLVQ (somhip_glvq_train): `epochs` epochs over all of teach->data at rates from teach->alpha down, sigmoid_beta 0
+ * for the identity, on the labelled rows of teach->codes, which it replaces.  cost, correct: NULL, or [epochs] for the cost
+ * and the number of correctly classified rows of the codebook every epoch started from.  0, or 1 after a message. */
+int glvq_training(struct teach_params *teach, long epochs, float sigmoid_beta, double *cost, int64_t *correct);
 /* winners of every data row (the scan behind compute_accuracy / find_labels) */
 int find_all_winners(struct teach_params *teach, int32_t *index, float *diff, int32_t *ret);
 /* the k nearest codes of every data row (knntest): k <= 8 */

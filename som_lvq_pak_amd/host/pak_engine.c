@@ -742,6 +742,20 @@ int som_batchmap_training(struct teach_params *teach, long epochs, long buffer, 
   return rc;
 }
 
+int glvq_training(struct teach_params *teach, long epochs, float sigmoid_beta, double *cost, int64_t *correct)
+{
+  const long n = teach->data->num_entries;
+  if (n <= 0) { fprintf(stderr, "glvq_training: can't get data\n"); return 1; }
+  struct mirrors m = {NULL, NULL};
+  int rc = mirrors_open(&m, teach->codes, 1, teach->data, 1);
+  if (!rc) {
+    somhip_glvq_params p = {epochs, 0, epochs, 0, n, teach->alpha, sigmoid_beta};
+    rc = said(somhip_glvq_train(m.cb, m.ds, &p, cost, correct)) || said(somhip_codebook_download(m.cb, teach->codes->points));
+  }
+  mirrors_close(&m);
+  return rc;
+}
+
 float find_qerror2(struct teach_params *teach)                /* som_rout.c:823-885 */
 {
   if (set_som_params(teach)) { fprintf(stderr, "find_qerror2: can't set SOM parameters\n"); return -1; }
