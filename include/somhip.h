@@ -489,6 +489,66 @@ int  somhip_debug_glvq_update(somhip_codebook *cb, float alpha_t, int64_t n, con
  * scan), [1] the terms and the grouping (scans of the counts, sorts by winner), [2] the sums, [3] the update */
 int  somhip_glvq_timing(somhip_engine *e, int64_t launches[4], double total_ms[4]);
 
+/* ---- batch neural gas (K10; no reference function) ---------------------------------
+ * Martinetz and Schulten's neural gas in its batch form (Cottrell, Hammer, Hasenfuss, Villmann 2006): the vector
+ * quantizer for a codebook with neither a lattice nor labels.  Every sample feeds its first K ranked units with the
+ * weight exp(-rank / lambda); every unit becomes the weighted mean of what it was fed.  No learning rate, no dependence on
+ * the order of the data beyond the order of its sums; the same bits on every run.
+ * One call runs epochs t = start_epoch .. start_epoch + count - 1 of a run of T = epochs epochs over data rows
+ * (first + s) % n_rows, s = 0 .. n-1, on a codebook of `units` rows.  Per epoch:
+ *   1. in double on the host: lambda_t = lambda0 * pow(lambda_end / lambda0, (double)t / (double)(T - 1)) (T == 1: lambda0);
+ *      K_t = ranks if ranks > 0, else min(units, SOMHIP_KNN_MAX, 1 + floor(17.0 * lambda_t)); w[r] = exp(-(double)r /
+ *      lambda_t), r < K_t.  17 is the smallest integer with exp(-17) < 2^-24: a rank the rule drops weighs less than half
+ *      an ulp of the float a row is stored in, relative to rank 0 -- a constant of the definition, not a knob
+ *   2. per sample, against the codebook as the epoch found it: its K_t nearest rows by find_winner_euc's squared distance
+ *      (fp32: sub, mul, add in dimension order, three roundings), equal distances in find_winner_knn's order (the later
+ *      row first) at every K_t -- K_t == 1 on two rows and more takes the first of the two nearest, so the order of ties
+ *      does not change along a run; a one-row codebook has one rank
+ *   3. per unit j, over the samples that rank j at some r < K_t, in data order, no floating-point atomics:
+ *      S[j][k] = ONE chain of fp64 additions from +0.0 of w[r] * (double)x_s[k] (a multiply, then an add, no FMA),
+ *      W[j] = the same chain over w[r] alone, hits[j] = the number of such samples (uint32)
+ *   4. m_j[k] = (float)(S[j][k] / W[j]) where W[j] > 0; a unit outside every sample's first K_t ranks, or whose weights all
+ *      underflowed to zero, keeps its bits
+ * On codebooks of at most SOMHIP_KNN_MAX (256) rows, while 17 lambda_t >= units - 1, this is neural gas without any
+ * truncation.  Beyond 256 rows it is neural gas TRUNCATED at the 256 nearest units of every sample: no rank past the
+ * 256th is ever fed, whatever lambda is.
+ * qerror_out (host, [count], or NULL): per epoch find_qerror's float sum over the rank-0 distances in data order -- the
+ * quantization error of the codebook the epoch started from; NULL: no per-sample copy leaves the device.
+ * Any whole codebook is taken, with or without a lattice, with or without labels; header and labels are not touched.  It
+ * closes an open batch-map state, like the other writers of the rows.
+ * Refused, with a message that names the entry point, before anything is launched and with the rows untouched: data with x
+ * components, sharded codebooks, a dimension mismatch, n <= 0, n >= 2^32, first < 0, epochs < 1, lambda0 not > 0,
+ * lambda_end not in (0, lambda0], ranks outside 0 .. 256, epochs outside [0, epochs). */
+typedef struct somhip_ng_params {
+  int64_t epochs;        /* T */
+  double  lambda0;       /* the neighbourhood range, in ranks, the run starts from */
+  double  lambda_end;    /* ... and ends at */
+  int64_t ranks;         /* 0: K_t by the rule above; 1 .. 256: K_t of every epoch */
+  int64_t start_epoch, count;
+  int64_t first, n;      /* the data rows of every epoch */
+} somhip_ng_params;
+int  somhip_ng_train(somhip_codebook *cb, somhip_dataset *ds, const somhip_ng_params *p, float *qerror_out /*[count] or NULL*/);
+/* The stages somhip_ng_train is made of, each on its own.
+ * _schedule: step 1 of epoch t for a codebook of `units` rows, on the host (no GPU): *lambda, *K and weights[256], zeros
+ * behind K.
+ * _ranks: step 2 to the host, units_out / dist_out [n][K] (K 1 .. 256): the r-th nearest unit and its squared distance,
+ * -1 / -1.0f where the codebook has no r-th row below FLT_MAX.
+ * _sums: steps 2-3 with K ranks and host-supplied weights[K]: hits [units], sums [units][dim], wsum [units] to the host.
+ * The data go through in segments of `segment` samples (<= 0: the engine's own rule, at most 2^24 (sample, rank) pairs a
+ * segment); the segments after the first continue the chains, so every segment length leaves the same bits.
+ * _update: step 4 on host-supplied sums and wsum (hits: as _sums returns them; W decides which rows move); it writes the
+ * codebook. */
+int  somhip_debug_ng_schedule(const somhip_ng_params *p, int64_t units, int64_t t, double *lambda, int32_t *K, double *weights /*[256]*/);
+int  somhip_debug_ng_ranks(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, int K, int32_t *units_out,
+                           float *dist_out);
+int  somhip_debug_ng_sums(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, int K, const double *weights,
+                          int64_t segment, uint32_t *hits, double *sums, double *wsum);
+int  somhip_debug_ng_update(somhip_codebook *cb, const uint32_t *hits, const double *sums, const double *wsum);
+/* HIP-event totals of its stages since somhip_timing_reset, while somhip_timing_enable is on (not in the table of
+ * somhip_kernel_count): [0] the entries pass per chunk and the grouping (scan of the counts, sort by unit), [1] the sums,
+ * [2] the update.  The search's launches count under their own ids (somhip_timing_get, somhip_knn_timing). */
+int  somhip_ng_timing(somhip_engine *e, int64_t launches[3], double total_ms[3]);
+
 /* ---- map distortion (K1d; no reference function) ----------------------------------
  * The distortion measure of a map (Lampinen and Oja; SOM Toolbox's som_distortion): its energy at a neighbourhood radius,
  *   E(r) = sum over samples s, sum over units j, of  h_r(c(s), j) * || x_s - m_j ||^2 ,

@@ -51,6 +51,11 @@ class GlvqParams(C.Structure):
                 ("alpha", C.c_float), ("sigmoid_beta", C.c_float)]
 
 
+class NgParams(C.Structure):
+    _fields_ = [("epochs", C.c_int64), ("lambda0", C.c_double), ("lambda_end", C.c_double), ("ranks", C.c_int64),
+                ("start_epoch", C.c_int64), ("count", C.c_int64), ("first", C.c_int64), ("n", C.c_int64)]
+
+
 # name -> (restype, argtypes); exactly the symbols include/somhip.h declares
 SIGNATURES = {
     "somhip_last_error": (C.c_char_p, []),
@@ -134,6 +139,13 @@ SIGNATURES = {
                                          c_double_p, c_double_p, c_u32_p, c_double_p, c_u32_p, c_double_p, c_i64_p]),
     "somhip_debug_glvq_update": (C.c_int, [C.c_void_p, C.c_float, C.c_int64, c_double_p, c_u32_p, c_double_p, c_u32_p]),
     "somhip_glvq_timing": (C.c_int, [C.c_void_p, c_i64_p, c_double_p]),
+    "somhip_ng_train": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(NgParams), c_float_p]),
+    "somhip_debug_ng_schedule": (C.c_int, [C.POINTER(NgParams), C.c_int64, C.c_int64, c_double_p, c_i32_p, c_double_p]),
+    "somhip_debug_ng_ranks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, c_i32_p, c_float_p]),
+    "somhip_debug_ng_sums": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, c_double_p, C.c_int64, c_u32_p,
+                                       c_double_p, c_double_p]),
+    "somhip_debug_ng_update": (C.c_int, [C.c_void_p, c_u32_p, c_double_p, c_double_p]),
+    "somhip_ng_timing": (C.c_int, [C.c_void_p, c_i64_p, c_double_p]),
     "somhip_distortion_create": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "somhip_distortion_destroy": (None, [C.c_void_p]),
     "somhip_distortion_clear": (C.c_int, [C.c_void_p]),

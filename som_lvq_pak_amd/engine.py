@@ -164,6 +164,15 @@ class Engine:
         check(self.lib.somhip_glvq_timing(self.h, n, ms))
         return {"search": (n[0], ms[0]), "terms": (n[1], ms[1]), "k_glvq_sums": (n[2], ms[2]), "k_glvq_update": (n[3], ms[3])}
 
+    def ng_timing(self):
+        """(launches, ms) of batch neural gas's stages while timing is on (somhip_ng_timing; they are not in timing_table):
+        group = k_ng_entries per chunk, the scan of the counts and the sort by unit, once per segment.  The search counts
+        under its own kernels (timing_table, knn_timing)."""
+        n = (C.c_int64 * 3)()
+        ms = (C.c_double * 3)()
+        check(self.lib.somhip_ng_timing(self.h, n, ms))
+        return {"group": (n[0], ms[0]), "k_ng_sums": (n[1], ms[1]), "k_ng_update": (n[2], ms[2])}
+
     def distortion_timing(self):
         """(launches, ms) of map distortion's stages while timing is on (somhip_distortion_timing; they are not in
         timing_table): group = the winners pass per chunk, the scan of the counts and the sort by winner; sums = the
@@ -754,6 +763,71 @@ def glvq_update(cb, alpha_t, n, sums_plus, n_plus, sums_minus, n_minus):
     assert sp.shape == sm.shape == (cb.n, cb.dim + 1) and cp.shape == cm.shape == (cb.n,)
     check(cb.e.lib.somhip_debug_glvq_update(cb.h, float(np.float32(alpha_t)), n, _p(sp, _lib.c_double_p), _p(cp, _lib.c_u32_p),
                                             _p(sm, _lib.c_double_p), _p(cm, _lib.c_u32_p)))
+
+
+def _ng_params(units, epochs, lambda0, lambda_end, ranks, start_epoch=0, count=0, first=0, n=0):
+    lambda0 = min(units, 256) / 2.0 if lambda0 is None else lambda0
+    return _lib.NgParams(epochs, lambda0, lambda_end, ranks, start_epoch, count, first, n)
+
+
+def ng_schedule(units, epochs, t, lambda0=None, lambda_end=0.01, ranks=0, lib=None):
+    """Epoch t of a neural-gas run of `epochs` epochs on `units` rows (somhip_debug_ng_schedule): (lambda_t float,
+    K_t int, w float64[K_t]) exactly as the engine forms them -- lambda0 None is min(units, 256) / 2.  Host arithmetic:
+    no GPU needed."""
+    lib = lib or _lib.load()
+    p = _ng_params(units, epochs, lambda0, lambda_end, ranks)
+    lam, k = C.c_double(0), C.c_int32(0)
+    w = np.zeros(256, dtype=np.float64)
+    check(lib.somhip_debug_ng_schedule(C.byref(p), units, t, C.byref(lam), C.byref(k), _p(w, _lib.c_double_p)))
+    return lam.value, k.value, w[:k.value].copy()
+
+
+def ng_train(cb, ds, epochs, lambda0=None, lambda_end=0.01, ranks=0, start_epoch=0, count=None, first=0, n=None, qerror=True):
+    """Epochs [start_epoch, start_epoch + count) of batch neural gas over data rows (first + s) % ds.n, s < n
+    (somhip_ng_train): every epoch replaces each row by the mean of the data weighted by exp(-rank / lambda_t), over the
+    first K_t ranks of every sample (ng_schedule).  Beyond 256 rows the ranks are truncated at the 256 nearest.  Returns
+    float32[count], per epoch the quantization error (find_qerror's float sum) of the codebook the epoch started from, or
+    None with qerror=False (no per-sample copy leaves the device)."""
+    count = epochs - start_epoch if count is None else count
+    n = ds.n if n is None else n
+    p = _ng_params(cb.n, epochs, lambda0, lambda_end, ranks, start_epoch, count, first, n)
+    q = np.zeros(max(count, 0), dtype=np.float32) if qerror else None
+    check(cb.e.lib.somhip_ng_train(cb.h, ds.h, C.byref(p), _p(q, _lib.c_float_p)))
+    return q
+
+
+def ng_ranks(cb, ds, K, first=0, n=None):
+    """The rank search alone (somhip_debug_ng_ranks): (units int32[n, K], dist float32[n, K]) -- per sample its K nearest
+    rows, nearest first, the later row first among equal distances; -1 / -1.0 where the codebook has no such row"""
+    n = ds.n if n is None else n
+    units = np.zeros((n, K), dtype=np.int32)
+    dist = np.zeros((n, K), dtype=np.float32)
+    check(cb.e.lib.somhip_debug_ng_ranks(cb.h, ds.h, first, n, K, _p(units, _lib.c_i32_p), _p(dist, _lib.c_float_p)))
+    return units, dist
+
+
+def ng_sums(cb, ds, weights, first=0, n=None, segment=0):
+    """Ranks, grouping and sums of a neural-gas epoch with K = len(weights) ranks (somhip_debug_ng_sums): (hits uint32[cb.n],
+    sums float64[cb.n, dim], wsum float64[cb.n]) -- per unit the samples that rank it, and one chain of fp64 additions in
+    data order of w[rank] * x and of w[rank].  segment: samples per segment (0: the engine's rule); same bits for all."""
+    n = ds.n if n is None else n
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    hits = np.zeros(cb.n, dtype=np.uint32)
+    sums = np.zeros((cb.n, cb.dim), dtype=np.float64)
+    wsum = np.zeros(cb.n, dtype=np.float64)
+    check(cb.e.lib.somhip_debug_ng_sums(cb.h, ds.h, first, n, len(w), _p(w, _lib.c_double_p), segment, _p(hits, _lib.c_u32_p),
+                                        _p(sums, _lib.c_double_p), _p(wsum, _lib.c_double_p)))
+    return hits, sums, wsum
+
+
+def ng_update(cb, hits, sums, wsum):
+    """The update alone (somhip_debug_ng_update) from host-supplied sums as ng_sums returns them: row j becomes
+    float32(sums[j] / wsum[j]) where wsum[j] > 0 and keeps its bits elsewhere"""
+    hits = np.ascontiguousarray(hits, dtype=np.uint32)
+    sums = np.ascontiguousarray(sums, dtype=np.float64)
+    wsum = np.ascontiguousarray(wsum, dtype=np.float64)
+    assert hits.shape == wsum.shape == (cb.n,) and sums.shape == (cb.n, cb.dim)
+    check(cb.e.lib.somhip_debug_ng_update(cb.h, _p(hits, _lib.c_u32_p), _p(sums, _lib.c_double_p), _p(wsum, _lib.c_double_p)))
 
 
 def _distortion_totals(tot):

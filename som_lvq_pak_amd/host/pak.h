@@ -198,6 +198,12 @@ int som_batchmap_training_multi(struct teach_params *teach, long epochs, float *
  * for the identity, on the labelled rows of teach->codes, which it replaces.  cost, correct: NULL, or [epochs] for the cost
  * and the number of correctly classified rows of the codebook every epoch started from.  0, or 1 after a message. */
 int glvq_training(struct teach_params *teach, long epochs, float sigmoid_beta, double *cost, int64_t *correct);
+/* batch neural gas (somhip_ng_train): `epochs` epochs over all of teach->data, lambda from lambda0 down to lambda_end,
+ * ranks 0 for the engine's rule, on the rows of teach->codes, which it replaces (lattice and labels play no part).  line:
+ * NULL, or [epochs] for each epoch's lambda and ranks as the engine forms them and the quantization error (find_qerror's sum)
+ * of the codebook the epoch started from.  0, or 1 after a message. */
+struct ng_line { double lambda; int ranks; float qerror; };
+int ng_training(struct teach_params *teach, long epochs, double lambda0, double lambda_end, long ranks, struct ng_line *line);
 /* winners of every data row (the scan behind compute_accuracy / find_labels) */
 int find_all_winners(struct teach_params *teach, int32_t *index, float *diff, int32_t *ret);
 /* the k nearest codes of every data row (knntest): k <= 8 */

@@ -756,6 +756,27 @@ int glvq_training(struct teach_params *teach, long epochs, float sigmoid_beta, d
   return rc;
 }
 
+int ng_training(struct teach_params *teach, long epochs, double lambda0, double lambda_end, long ranks, struct ng_line *line)
+{
+  const long n = teach->data->num_entries;
+  if (n <= 0) { fprintf(stderr, "ng_training: can't get data\n"); return 1; }
+  somhip_ng_params p = {epochs, lambda0, lambda_end, ranks, 0, epochs, 0, n};
+  float *qerror = line ? calloc((size_t)epochs, sizeof *qerror) : NULL;
+  struct mirrors m = {NULL, NULL};
+  int rc = mirrors_open(&m, teach->codes, 0, teach->data, 0);
+  if (!rc) rc = said(somhip_ng_train(m.cb, m.ds, &p, qerror)) || said(somhip_codebook_download(m.cb, teach->codes->points));
+  for (long t = 0; !rc && line && t < epochs; t++) {
+    double w[256];
+    int32_t k = 0;
+    rc = said(somhip_debug_ng_schedule(&p, teach->codes->num_entries, t, &line[t].lambda, &k, w));
+    line[t].ranks = (int)k;
+    line[t].qerror = qerror[t];
+  }
+  mirrors_close(&m);
+  free(qerror);
+  return rc;
+}
+
 float find_qerror2(struct teach_params *teach)                /* som_rout.c:823-885 */
 {
   if (set_som_params(teach)) { fprintf(stderr, "find_qerror2: can't set SOM parameters\n"); return -1; }
