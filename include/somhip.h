@@ -549,6 +549,69 @@ int  somhip_debug_ng_update(somhip_codebook *cb, const uint32_t *hits, const dou
  * [2] the update.  The search's launches count under their own ids (somhip_timing_get, somhip_knn_timing). */
 int  somhip_ng_timing(somhip_engine *e, int64_t launches[3], double total_ms[3]);
 
+/* ---- batch GRLVQ (K11; no reference function) --------------------------------------
+ * Hammer and Villmann's relevance GLVQ as full-batch gradient steps: batch GLVQ (above) under the weighted metric
+ *   d_lambda(x, w) = sum_k lambda[k] * (x[k] - w[k])^2 ,  lambda[k] >= 0,
+ * whose weights, the relevances, are learned by the gradient that moves the rows.  lambda is a host float[dim] the caller
+ * owns: read on entry, written on return, never normalised on entry.  So five calls of one epoch that hand lambda on equal
+ * one call of five, and lambda all 1.0f with eps = 0 gives somhip_glvq_train's codebook, cost and count bit for bit.
+ * One call runs epochs t = start_epoch .. start_epoch + count - 1 of a run of T = epochs epochs over data rows
+ * (first + s) % n_rows, s = 0 .. n-1.  Per epoch, everything against the codebook and the lambda the epoch started from:
+ *   1. alpha_t = alpha * (float)(T - t) / (float)T and eps_t = eps * (float)(T - t) / (float)T, in float
+ *   2. (d+, i+) and (d-, i-) as in somhip_glvq_train step 2, the distance being the weighted fp32 chain in dimension order
+ *      from +0.0f: t = c - x, u = lambda[k] * t, p = u * t, acc = acc + p -- four separately rounded operations, no FMA; the
+ *      lowest row index among equal distances.  With lambda[k] == 1.0f this is the unweighted chain bit for bit
+ *   3. somhip_glvq_train step 3, unchanged: xi+, xi-, f, correct
+ *   4. somhip_glvq_train step 4, unchanged: Sp, sp, cost, np; Sm, sm, nm.  Beside them, per row j and component k,
+ *      Rp[j][k] = ONE chain of fp64 additions from +0.0 over the samples with i+ = j in data order of
+ *      td = (double)x[k] - (double)w_j[k], tt = td * td, pr = xi+ * tt, acc += pr, every operation one rounding;
+ *      Rm[j][k] the same over the samples with i- = j, with xi-
+ *   5. G[k] = one chain from +0.0 over the rows j = 0 .. rows-1 in unit order of (Rp[j][k] - Rm[j][k]), a subtraction and
+ *      then an addition.  No floating-point atomics anywhere
+ *   6. with W = (double)w_j[k], a = (double)alpha_t / (double)n and g as in somhip_glvq_train step 5:
+ *      w_j[k] = (float)(W + (a * (double)lambda[k]) * g); a row with np[j] == nm[j] == 0 keeps its bits
+ *   7. only where eps_t > 0, in IEEE fp64 on the host: e = (double)eps_t / (2.0 * (double)n),
+ *      l[k] = (double)lambda[k] - e * G[k], negative values become 0.0, s = the chain of l[k] in order from +0.0; where
+ *      s > 0: lambda[k] = (float)(l[k] / s), otherwise lambda keeps its bits.  With eps_t == 0 lambda is neither stepped
+ *      nor normalised
+ * cost_out, correct_out: as somhip_glvq_train's, under d_lambda; they describe the state the epoch started from.
+ * Only the class-wise scan searches here: the pre-filters behind the top-8 lists are unweighted.
+ * Refused, with a message that names the entry point, before anything is launched and with the codebook and lambda
+ * untouched: everything somhip_glvq_train refuses; a NULL lambda; a lambda[k] that is negative, NaN or infinite; lambda
+ * summing to zero; eps negative or NaN. */
+typedef struct somhip_grlvq_params {
+  int64_t epochs;        /* T */
+  int64_t start_epoch, count;
+  int64_t first, n;      /* the data rows of every epoch */
+  float   alpha;         /* the rate of the rows the run starts from */
+  float   sigmoid_beta;  /* 0: f is the identity */
+  float   eps;           /* the rate of the relevances the run starts from; 0: lambda stays as given */
+} somhip_grlvq_params;
+int  somhip_grlvq_train(somhip_codebook *cb, somhip_dataset *ds, const somhip_grlvq_params *p, float *lambda /*[dim], in and out*/,
+                        double *cost_out /*[count] or NULL*/, int64_t *correct_out /*[count] or NULL*/);
+/* Step 2 to the host, with lambda given: dplus / dminus [n] and iplus / iminus [n].  What evaluating a trained model needs:
+ * a sample is classified correctly when the key (d+, i+) is smaller than the key (d-, i-).  A lambda of zeros is taken
+ * (every distance is 0 and the lowest row of either role wins); the other refusals are somhip_grlvq_train's. */
+int  somhip_grlvq_search(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, const float *lambda, float *dplus,
+                         int32_t *iplus, float *dminus, int32_t *iminus);
+/* The stages somhip_grlvq_train is made of, each on its own.
+ * _sums: steps 2-5 to the host: somhip_debug_glvq_sums' outputs under d_lambda, then rel_plus, rel_minus
+ * [n_rows of the codebook][dim] (Rp, Rm) and grad [dim] (G).
+ * _update: step 6 with a = (double)alpha_t / (double)n on host-supplied sums, with the lambda given, and then step 7
+ * with eps_t and grad: it writes the codebook and lambda. */
+int  somhip_debug_grlvq_sums(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, float sigmoid_beta,
+                             const float *lambda, double *xi_plus, double *xi_minus, double *f, double *sums_plus,
+                             uint32_t *n_plus, double *sums_minus, uint32_t *n_minus, double *cost, int64_t *correct,
+                             double *rel_plus, double *rel_minus, double *grad);
+int  somhip_debug_grlvq_update(somhip_codebook *cb, float alpha_t, float eps_t, int64_t n, float *lambda,
+                               const double *sums_plus, const uint32_t *n_plus, const double *sums_minus,
+                               const uint32_t *n_minus, const double *grad);
+/* HIP-event totals of its stages since somhip_timing_reset, while somhip_timing_enable is on (not in the table of
+ * somhip_kernel_count): [0] the weighted class-wise scan, [1] the terms and the grouping (batch GLVQ's stage, counted under
+ * its id: somhip_glvq_timing [1] reports the same figures), [2] the sums with the relevance chain, [3] the reduction of
+ * the relevance gradient over the rows, [4] the update */
+int  somhip_grlvq_timing(somhip_engine *e, int64_t launches[5], double total_ms[5]);
+
 /* ---- map distortion (K1d; no reference function) ----------------------------------
  * The distortion measure of a map (Lampinen and Oja; SOM Toolbox's som_distortion): its energy at a neighbourhood radius,
  *   E(r) = sum over samples s, sum over units j, of  h_r(c(s), j) * || x_s - m_j ||^2 ,

@@ -56,6 +56,11 @@ class NgParams(C.Structure):
                 ("start_epoch", C.c_int64), ("count", C.c_int64), ("first", C.c_int64), ("n", C.c_int64)]
 
 
+class GrlvqParams(C.Structure):
+    _fields_ = [("epochs", C.c_int64), ("start_epoch", C.c_int64), ("count", C.c_int64), ("first", C.c_int64), ("n", C.c_int64),
+                ("alpha", C.c_float), ("sigmoid_beta", C.c_float), ("eps", C.c_float)]
+
+
 # name -> (restype, argtypes); exactly the symbols include/somhip.h declares
 SIGNATURES = {
     "somhip_last_error": (C.c_char_p, []),
@@ -146,6 +151,15 @@ SIGNATURES = {
                                        c_double_p, c_double_p]),
     "somhip_debug_ng_update": (C.c_int, [C.c_void_p, c_u32_p, c_double_p, c_double_p]),
     "somhip_ng_timing": (C.c_int, [C.c_void_p, c_i64_p, c_double_p]),
+    "somhip_grlvq_train": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(GrlvqParams), c_float_p, c_double_p, c_i64_p]),
+    "somhip_grlvq_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, c_float_p, c_float_p, c_i32_p, c_float_p,
+                                      c_i32_p]),
+    "somhip_debug_grlvq_sums": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_float, c_float_p, c_double_p,
+                                          c_double_p, c_double_p, c_double_p, c_u32_p, c_double_p, c_u32_p, c_double_p, c_i64_p,
+                                          c_double_p, c_double_p, c_double_p]),
+    "somhip_debug_grlvq_update": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_int64, c_float_p, c_double_p, c_u32_p,
+                                            c_double_p, c_u32_p, c_double_p]),
+    "somhip_grlvq_timing": (C.c_int, [C.c_void_p, c_i64_p, c_double_p]),
     "somhip_distortion_create": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "somhip_distortion_destroy": (None, [C.c_void_p]),
     "somhip_distortion_clear": (C.c_int, [C.c_void_p]),

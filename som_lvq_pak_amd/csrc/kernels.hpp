@@ -32,6 +32,7 @@
 #include "kernels/batchmap.hpp"
 #include "kernels/map_distortion.hpp"
 #include "kernels/glvq.hpp"
+#include "kernels/grlvq.hpp"
 #include "kernels/ngas.hpp"
 #include "kernels/som_update.hpp"
 #include "kernels/som_update_gemm.hpp"

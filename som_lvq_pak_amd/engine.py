@@ -173,6 +173,16 @@ class Engine:
         check(self.lib.somhip_ng_timing(self.h, n, ms))
         return {"group": (n[0], ms[0]), "k_ng_sums": (n[1], ms[1]), "k_ng_update": (n[2], ms[2])}
 
+    def grlvq_timing(self):
+        """(launches, ms) of batch GRLVQ's stages while timing is on (somhip_grlvq_timing; they are not in timing_table):
+        search = the weighted class-wise scan per chunk; terms = batch GLVQ's stage, counted under its id (glvq_timing
+        reports the same figures)"""
+        n = (C.c_int64 * 5)()
+        ms = (C.c_double * 5)()
+        check(self.lib.somhip_grlvq_timing(self.h, n, ms))
+        return {"search": (n[0], ms[0]), "terms": (n[1], ms[1]), "k_grlvq_sums": (n[2], ms[2]), "k_grlvq_relevance": (n[3], ms[3]),
+                "k_grlvq_update": (n[4], ms[4])}
+
     def distortion_timing(self):
         """(launches, ms) of map distortion's stages while timing is on (somhip_distortion_timing; they are not in
         timing_table): group = the winners pass per chunk, the scan of the counts and the sort by winner; sums = the
@@ -828,6 +838,81 @@ def ng_update(cb, hits, sums, wsum):
     wsum = np.ascontiguousarray(wsum, dtype=np.float64)
     assert hits.shape == wsum.shape == (cb.n,) and sums.shape == (cb.n, cb.dim)
     check(cb.e.lib.somhip_debug_ng_update(cb.h, _p(hits, _lib.c_u32_p), _p(sums, _lib.c_double_p), _p(wsum, _lib.c_double_p)))
+
+
+def _grlvq_lambda(cb, lam):
+    """a float32[dim] copy of the relevance vector the call may write; None: 1 / dim each"""
+    if lam is None:
+        return np.full(cb.dim, np.float32(1.0) / np.float32(cb.dim), dtype=np.float32)
+    lam = np.array(lam, dtype=np.float32).reshape(-1)
+    if lam.shape != (cb.dim,):
+        raise ValueError("lambda has %d entries, the codebook %d components" % (lam.size, cb.dim))
+    return lam
+
+
+def grlvq_train(cb, ds, epochs, alpha, eps, lam=None, sigmoid_beta=0.0, start_epoch=0, count=None, first=0, n=None, stats=True):
+    """Epochs [start_epoch, start_epoch + count) of batch GRLVQ over data rows (first + s) % ds.n, s < n
+    (somhip_grlvq_train): batch GLVQ under d_lambda = sum_k lambda[k] (x[k] - w[k])^2, the relevances lambda learned at the
+    rate glvq_alpha(eps, epochs, t) by the gradient that moves the rows, clamped at 0 and normalised to sum 1 after every
+    step.  lam: the relevances the call starts from, taken as they are (None: 1 / dim each); eps = 0 leaves them alone.
+    Returns (lambda float32[dim], cost float64[count], correct int64[count]) -- cost and correct of the state each epoch
+    started from -- or lambda alone with stats=False.  Hand lambda on to continue a run."""
+    count = epochs - start_epoch if count is None else count
+    n = ds.n if n is None else n
+    lam = _grlvq_lambda(cb, lam)
+    p = _lib.GrlvqParams(epochs, start_epoch, count, first, n, alpha, sigmoid_beta, eps)
+    cost = np.zeros(max(count, 0), dtype=np.float64) if stats else None
+    correct = np.zeros(max(count, 0), dtype=np.int64) if stats else None
+    check(cb.e.lib.somhip_grlvq_train(cb.h, ds.h, C.byref(p), _p(lam, _lib.c_float_p), _p(cost, _lib.c_double_p),
+                                      _p(correct, _lib.c_i64_p)))
+    return (lam, cost, correct) if stats else lam
+
+
+def grlvq_search(cb, ds, lam=None, first=0, n=None):
+    """The class-wise winner search under d_lambda (somhip_grlvq_search): (dplus float32[n], iplus int32[n], dminus,
+    iminus) -- per sample the nearest row of its own class and of any other.  A sample is classified correctly where
+    (dplus, iplus) < (dminus, iminus)."""
+    n = ds.n if n is None else n
+    lam = _grlvq_lambda(cb, lam)
+    dp, dm = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.float32)
+    ip, im = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    check(cb.e.lib.somhip_grlvq_search(cb.h, ds.h, first, n, _p(lam, _lib.c_float_p), _p(dp, _lib.c_float_p), _p(ip, _lib.c_i32_p),
+                                       _p(dm, _lib.c_float_p), _p(im, _lib.c_i32_p)))
+    return dp, ip, dm, im
+
+
+def grlvq_sums(cb, ds, lam=None, first=0, n=None, sigmoid_beta=0.0):
+    """Search, terms, sums and relevance gradient of a GRLVQ epoch (somhip_debug_grlvq_sums), as a dict: glvq_sums' entries
+    under d_lambda, and rel_plus, rel_minus float64[cb.n, dim] (Rp, Rm), grad float64[dim] (G)"""
+    n = ds.n if n is None else n
+    lam = _grlvq_lambda(cb, lam)
+    d = lambda *shape: np.zeros(shape, dtype=np.float64)
+    out = {"xi_plus": d(n), "xi_minus": d(n), "f": d(n), "sums_plus": d(cb.n, cb.dim + 1), "sums_minus": d(cb.n, cb.dim + 1),
+           "n_plus": np.zeros(cb.n, dtype=np.uint32), "n_minus": np.zeros(cb.n, dtype=np.uint32), "cost": d(cb.n),
+           "rel_plus": d(cb.n, cb.dim), "rel_minus": d(cb.n, cb.dim), "grad": d(cb.dim)}
+    correct = C.c_int64(0)
+    dp, up = _lib.c_double_p, _lib.c_u32_p
+    check(cb.e.lib.somhip_debug_grlvq_sums(cb.h, ds.h, first, n, sigmoid_beta, _p(lam, _lib.c_float_p), _p(out["xi_plus"], dp),
+                                           _p(out["xi_minus"], dp), _p(out["f"], dp), _p(out["sums_plus"], dp), _p(out["n_plus"], up),
+                                           _p(out["sums_minus"], dp), _p(out["n_minus"], up), _p(out["cost"], dp), C.byref(correct),
+                                           _p(out["rel_plus"], dp), _p(out["rel_minus"], dp), _p(out["grad"], dp)))
+    out["correct"] = correct.value
+    return out
+
+
+def grlvq_update(cb, alpha_t, eps_t, n, lam, sums_plus, n_plus, sums_minus, n_minus, grad):
+    """The update and the relevance step alone (somhip_debug_grlvq_update) from host-supplied sums as grlvq_sums returns
+    them: the rows move with a = float64(alpha_t) / n and the lambda given; returns the lambda after the step with eps_t
+    (the bits of the one given where eps_t == 0 or every component is clamped)"""
+    sp, sm = np.ascontiguousarray(sums_plus, dtype=np.float64), np.ascontiguousarray(sums_minus, dtype=np.float64)
+    cp, cm = np.ascontiguousarray(n_plus, dtype=np.uint32), np.ascontiguousarray(n_minus, dtype=np.uint32)
+    g = np.ascontiguousarray(grad, dtype=np.float64)
+    assert sp.shape == sm.shape == (cb.n, cb.dim + 1) and cp.shape == cm.shape == (cb.n,) and g.shape == (cb.dim,)
+    lam = _grlvq_lambda(cb, lam)
+    check(cb.e.lib.somhip_debug_grlvq_update(cb.h, float(np.float32(alpha_t)), float(np.float32(eps_t)), n, _p(lam, _lib.c_float_p),
+                                             _p(sp, _lib.c_double_p), _p(cp, _lib.c_u32_p), _p(sm, _lib.c_double_p),
+                                             _p(cm, _lib.c_u32_p), _p(g, _lib.c_double_p)))
+    return lam
 
 
 def _distortion_totals(tot):

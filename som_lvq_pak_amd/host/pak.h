@@ -198,6 +198,11 @@ int som_batchmap_training_multi(struct teach_params *teach, long epochs, float *
  * for the identity, on the labelled rows of teach->codes, which it replaces.  cost, correct: NULL, or [epochs] for the cost
  * and the number of correctly classified rows of the codebook every epoch started from.  0, or 1 after a message. */
 int glvq_training(struct teach_params *teach, long epochs, float sigmoid_beta, double *cost, int64_t *correct);
+/* batch GRLVQ (somhip_grlvq_train): glvq_training under the relevance-weighted metric.  lambda ([dim], in and out): the
+ * relevances, taken as they are and left as the run ends; eps: their rate.  epochs 0: nothing is trained.  Then one more
+ * search (somhip_grlvq_search): *final_cost and *final_correct describe teach->codes under lambda as the call leaves them. */
+int grlvq_training(struct teach_params *teach, long epochs, float sigmoid_beta, float eps, float *lambda, double *cost, int64_t *correct,
+                   double *final_cost, int64_t *final_correct);
 /* batch neural gas (somhip_ng_train): `epochs` epochs over all of teach->data, lambda from lambda0 down to lambda_end,
  * ranks 0 for the engine's rule, on the rows of teach->codes, which it replaces (lattice and labels play no part).  line:
  * NULL, or [epochs] for each epoch's lambda and ranks as the engine forms them and the quantization error (find_qerror's sum)
