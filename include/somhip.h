@@ -612,6 +612,78 @@ int  somhip_debug_grlvq_update(somhip_codebook *cb, float alpha_t, float eps_t, 
  * the relevance gradient over the rows, [4] the update */
 int  somhip_grlvq_timing(somhip_engine *e, int64_t launches[5], double total_ms[5]);
 
+/* ---- batch GMLVQ (K12; no reference function) --------------------------------------
+ * Schneider, Biehl and Hammer's matrix relevance GLVQ as full-batch gradient steps: batch GLVQ (above) under the metric
+ *   d(x, w) = | Omega (x - w) |^2 ,  Omega of rank (= m) x dim, 1 <= m <= dim,
+ * whose matrix is learned by the gradient that moves the rows.  omega is a host float[m][dim], row-major, the caller owns:
+ * read on entry, written on return, never normalised on entry.  So five calls of one epoch that hand omega on equal one
+ * call of five, and omega the dim x dim identity with eps = 0 gives somhip_glvq_train's codebook, cost and count bit for bit.
+ * One call runs epochs t = start_epoch .. start_epoch + count - 1 of a run of T = epochs epochs over data rows
+ * (first + s) % n_rows, s = 0 .. n-1.  Per epoch, everything against the codebook and the omega the epoch started from:
+ *   1. alpha_t = alpha * (float)(T - t) / (float)T and eps_t = eps * (float)(T - t) / (float)T, in float
+ *   2. the projection of every data row and every codebook row z: y[r] = (float)acc_dim with acc_0 = +0.0 and
+ *      acc_{k+1} = fma((double)omega[r][k], (double)z[k], acc_k) in fp64, in dimension order (the product of two floats is
+ *      exact in fp64, so each step rounds once).  Y = Omega X is [n][m], V = Omega W is [rows][m]
+ *   3. (d+, i+) and (d-, i-) exactly as in somhip_glvq_train step 2, on V and Y: the fp32 chain of (c - x)^2 over the m
+ *      columns, three separately rounded operations per column, the lowest row index among equal distances
+ *   4. somhip_glvq_train step 3, unchanged: xi+, xi-, f, correct
+ *   5. somhip_glvq_train step 4, unchanged, on the original rows x: Sp, sp, cost, np; Sm, sm, nm
+ *   6. in fp64, with W = (double)w_j[k], a = (double)alpha_t / (double)n and g_j[k] as in somhip_glvq_train step 5:
+ *      P[j][r] = ONE chain over k in order from +0.0 of acc + (g_j[k] * (double)omega[r][k]), the product rounded, then
+ *      added; Dl[j][k] = one chain over r in order from +0.0 of acc + (P[j][r] * (double)omega[r][k]);
+ *      w_j[k] = (float)(W + a * Dl[j][k]); a row with np[j] == nm[j] == 0 keeps its bits
+ *   7. the gradient Gm[m][dim].  The run's samples are cut into blocks of 4096 consecutive samples.  Per block and (r, k)
+ *      one chain from +0.0 in data order, two steps per sample:  acc = acc + ((xi+ * u+[r]) * t+[k]), then
+ *      acc = acc - ((xi- * u-[r]) * t-[k]),  with u+- = (double)y_s[r] - (double)v_{i+-}[r] and
+ *      t+- = (double)x_s[k] - (double)w_{i+-}[k], every operation one rounding.  Gm[r][k] = one chain from +0.0 over the
+ *      blocks in order.  No floating-point atomics anywhere
+ *   8. only where eps_t > 0, in IEEE fp64 on the host: O = (double)omega - ((double)eps_t / (double)n) * Gm, s = the chain
+ *      from +0.0 over O * O in row-major order; where s > 0: omega = (float)(O / sqrt(s)), otherwise omega keeps its bits.
+ *      With eps_t == 0 omega is neither stepped nor normalised
+ * cost_out, correct_out: as somhip_glvq_train's, under the projected distance; they describe the state the epoch started
+ * from.  Only the class-wise scan searches here.
+ * Refused, with a message that names the entry point, before anything is launched and with the codebook and omega
+ * untouched: everything somhip_glvq_train refuses; rank < 1 or rank > dim; a NULL omega; an entry that is NaN or infinite;
+ * an omega of zeros; eps negative or NaN. */
+typedef struct somhip_gmlvq_params {
+  int64_t epochs;        /* T */
+  int64_t start_epoch, count;
+  int64_t first, n;      /* the data rows of every epoch */
+  float   alpha;         /* the rate of the rows the run starts from */
+  float   sigmoid_beta;  /* 0: f is the identity */
+  float   eps;           /* the rate of omega the run starts from; 0: omega stays as given */
+  int32_t rank;          /* m: the rows of omega */
+} somhip_gmlvq_params;
+int  somhip_gmlvq_train(somhip_codebook *cb, somhip_dataset *ds, const somhip_gmlvq_params *p, float *omega /*[rank][dim], in and out*/,
+                        double *cost_out /*[count] or NULL*/, int64_t *correct_out /*[count] or NULL*/);
+/* Steps 2 and 3 to the host, with omega given: dplus / dminus [n] and iplus / iminus [n].  What evaluating a trained model
+ * needs: a sample is classified correctly when the key (d+, i+) is smaller than the key (d-, i-).  An omega of zeros is
+ * taken (every distance is +0 and the lowest row of either role wins); the other refusals are somhip_gmlvq_train's. */
+int  somhip_gmlvq_search(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, const float *omega, int32_t rank,
+                         float *dplus, int32_t *iplus, float *dminus, int32_t *iminus);
+/* Step 2 alone, row-major: with ds, out[n][rank] = the projections of data rows (first + s) % n_rows; with ds NULL,
+ * out[rows][rank] = the projections of the codebook's rows in unit order (first and n play no part).  The discriminative
+ * picture at rank 2 or 3, and the values the search of step 3 reads. */
+int  somhip_gmlvq_project(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, const float *omega, int32_t rank,
+                          float *out);
+/* The stages somhip_gmlvq_train is made of, each on its own.
+ * _sums: steps 2-5 and 7 to the host: somhip_debug_glvq_sums' outputs under the projected distance, then grad [rank][dim] (Gm).
+ * _update: step 6 with a = (double)alpha_t / (double)n on host-supplied sums, with the omega given, and then step 8 with
+ * eps_t and grad: it writes the codebook and omega. */
+int  somhip_debug_gmlvq_sums(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, float sigmoid_beta,
+                             const float *omega, int32_t rank, double *xi_plus, double *xi_minus, double *f, double *sums_plus,
+                             uint32_t *n_plus, double *sums_minus, uint32_t *n_minus, double *cost, int64_t *correct,
+                             double *grad);
+int  somhip_debug_gmlvq_update(somhip_codebook *cb, float alpha_t, float eps_t, int64_t n, float *omega, int32_t rank,
+                               const double *sums_plus, const uint32_t *n_plus, const double *sums_minus,
+                               const uint32_t *n_minus, const double *grad);
+/* HIP-event totals of its stages since somhip_timing_reset, while somhip_timing_enable is on (not in the table of
+ * somhip_kernel_count): [0] the projections of the samples and of the rows, [1] the class-wise scan over the projected
+ * tiles, [2] the terms and the grouping, [3] the sums (these three are batch GLVQ's stages, counted under its ids:
+ * somhip_glvq_timing [0] to [2] report the same figures), [4] the gradient of omega with its reduction over the blocks,
+ * [5] the update */
+int  somhip_gmlvq_timing(somhip_engine *e, int64_t launches[6], double total_ms[6]);
+
 /* ---- map distortion (K1d; no reference function) ----------------------------------
  * The distortion measure of a map (Lampinen and Oja; SOM Toolbox's som_distortion): its energy at a neighbourhood radius,
  *   E(r) = sum over samples s, sum over units j, of  h_r(c(s), j) * || x_s - m_j ||^2 ,

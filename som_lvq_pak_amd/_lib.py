@@ -61,6 +61,11 @@ class GrlvqParams(C.Structure):
                 ("alpha", C.c_float), ("sigmoid_beta", C.c_float), ("eps", C.c_float)]
 
 
+class GmlvqParams(C.Structure):
+    _fields_ = [("epochs", C.c_int64), ("start_epoch", C.c_int64), ("count", C.c_int64), ("first", C.c_int64), ("n", C.c_int64),
+                ("alpha", C.c_float), ("sigmoid_beta", C.c_float), ("eps", C.c_float), ("rank", C.c_int32)]
+
+
 # name -> (restype, argtypes); exactly the symbols include/somhip.h declares
 SIGNATURES = {
     "somhip_last_error": (C.c_char_p, []),
@@ -160,6 +165,16 @@ SIGNATURES = {
     "somhip_debug_grlvq_update": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_int64, c_float_p, c_double_p, c_u32_p,
                                             c_double_p, c_u32_p, c_double_p]),
     "somhip_grlvq_timing": (C.c_int, [C.c_void_p, c_i64_p, c_double_p]),
+    "somhip_gmlvq_train": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(GmlvqParams), c_float_p, c_double_p, c_i64_p]),
+    "somhip_gmlvq_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, c_float_p, C.c_int32, c_float_p, c_i32_p,
+                                      c_float_p, c_i32_p]),
+    "somhip_gmlvq_project": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, c_float_p, C.c_int32, c_float_p]),
+    "somhip_debug_gmlvq_sums": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_float, c_float_p, C.c_int32, c_double_p,
+                                          c_double_p, c_double_p, c_double_p, c_u32_p, c_double_p, c_u32_p, c_double_p, c_i64_p,
+                                          c_double_p]),
+    "somhip_debug_gmlvq_update": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_int64, c_float_p, C.c_int32, c_double_p, c_u32_p,
+                                            c_double_p, c_u32_p, c_double_p]),
+    "somhip_gmlvq_timing": (C.c_int, [C.c_void_p, c_i64_p, c_double_p]),
     "somhip_distortion_create": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "somhip_distortion_destroy": (None, [C.c_void_p]),
     "somhip_distortion_clear": (C.c_int, [C.c_void_p]),

@@ -47,3 +47,4 @@
 #include "kernels/class_nearest.hpp"
 #include "kernels/umat.hpp"
 #include "kernels/planes.hpp"
+#include "kernels/gmlvq.hpp"

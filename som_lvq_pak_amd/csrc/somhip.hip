@@ -89,12 +89,13 @@ static const char *kKernelNames[KID_COUNT] = {
 // from it by bit.  Kernels added since are timed by LaunchTimer all the same, under ids that follow the table; an entry
 // point of their own reports them (somhip_mapset_timing, somhip_knn_timing, somhip_knn_vote_timing, somhip_map_quality_timing,
 // somhip_batchmap_timing, somhip_conn_timing, somhip_distortion_timing, somhip_glvq_timing, somhip_ng_timing,
-// somhip_grlvq_timing).
+// somhip_grlvq_timing, somhip_gmlvq_timing).
 enum TimedOnlyId { KID_MAPSET_TRAIN = KID_COUNT, KID_MAPSET_WINNERS, KID_KNN_DIST, KID_KNN_SELECT, KID_KNN_VOTE, KID_QUALITY_PAIRS,
                    KID_QUALITY_UNITS, KID_BATCHMAP_GROUP, KID_BATCHMAP_SUMS, KID_BATCHMAP_COMBINE, KID_CONN_KEYS, KID_CONN_SORT,
                    KID_CONN_RUNS, KID_CONN_MERGE, KID_DISTORTION_GROUP, KID_DISTORTION_SUMS, KID_DISTORTION_EVALUATE, KID_GLVQ_SEARCH,
                    KID_GLVQ_TERMS, KID_GLVQ_SUMS, KID_GLVQ_UPDATE, KID_NG_GROUP, KID_NG_SUMS, KID_NG_UPDATE,
-                   KID_GRLVQ_SEARCH, KID_GRLVQ_SUMS, KID_GRLVQ_RELEVANCE, KID_GRLVQ_UPDATE, KID_TIMED };
+                   KID_GRLVQ_SEARCH, KID_GRLVQ_SUMS, KID_GRLVQ_RELEVANCE, KID_GRLVQ_UPDATE,
+                   KID_GMLVQ_PROJECT, KID_GMLVQ_GRAD, KID_GMLVQ_UPDATE, KID_TIMED };
 static_assert(KID_TIMED <= 64, "somhip_timing_select's mask has one bit per kernel id");
 extern "C" int somhip_kernel_count(void) { return KID_COUNT; }
 extern "C" const char *somhip_kernel_name(int i) { return (i >= 0 && i < KID_COUNT) ? kKernelNames[i] : ""; }
@@ -166,6 +167,9 @@ enum ScratchSlot {
                            // (SLOT_CALL_A the chunk's keys, SLOT_CALL_B its rank-0 distances)
   SLOT_GRLVQ,              // batch GRLVQ (host_grlvq.inc) beside SLOT_GLVQ and SLOT_GLVQ_LIST: the relevance sums of both roles per
                            // row and component, the relevance gradient, the relevance vector as a padded float4 tile
+  SLOT_GMLVQ,              // batch GMLVQ (host_gmlvq.inc) beside SLOT_GLVQ and SLOT_GLVQ_LIST: the projected storage tiles and sample
+                           // tiles, K9's g and P per row, the gradient of Omega, Omega and its transpose
+  SLOT_GMLVQ_PART,         // ... the gradient's partial sums per block of samples; the public projection's row-major output
   SLOT_COUNT
 };
 
@@ -846,3 +850,4 @@ extern "C" void somhip_dataset_destroy(somhip_dataset *ds) try {
 #include "host_ngas.inc"
 #include "host_grlvq.inc"
 #include "host_distortion.inc"
+#include "host_gmlvq.inc"

@@ -183,6 +183,16 @@ class Engine:
         return {"search": (n[0], ms[0]), "terms": (n[1], ms[1]), "k_grlvq_sums": (n[2], ms[2]), "k_grlvq_relevance": (n[3], ms[3]),
                 "k_grlvq_update": (n[4], ms[4])}
 
+    def gmlvq_timing(self):
+        """(launches, ms) of batch GMLVQ's stages while timing is on (somhip_gmlvq_timing; they are not in timing_table):
+        project = the projections of the samples and of the rows; search, terms, sums = batch GLVQ's stages, counted under
+        its ids (glvq_timing reports the same figures); k_gmlvq_omega_grad = the gradient of omega with its reduction"""
+        n = (C.c_int64 * 6)()
+        ms = (C.c_double * 6)()
+        check(self.lib.somhip_gmlvq_timing(self.h, n, ms))
+        return {"k_gmlvq_project": (n[0], ms[0]), "search": (n[1], ms[1]), "terms": (n[2], ms[2]), "sums": (n[3], ms[3]),
+                "k_gmlvq_omega_grad": (n[4], ms[4]), "k_gmlvq_update": (n[5], ms[5])}
+
     def distortion_timing(self):
         """(launches, ms) of map distortion's stages while timing is on (somhip_distortion_timing; they are not in
         timing_table): group = the winners pass per chunk, the scan of the counts and the sort by winner; sums = the
@@ -913,6 +923,102 @@ def grlvq_update(cb, alpha_t, eps_t, n, lam, sums_plus, n_plus, sums_minus, n_mi
                                              _p(sp, _lib.c_double_p), _p(cp, _lib.c_u32_p), _p(sm, _lib.c_double_p),
                                              _p(cm, _lib.c_u32_p), _p(g, _lib.c_double_p)))
     return lam
+
+
+def gmlvq_omega(dim, rank=None):
+    """the matrix a GMLVQ run starts from where none is given: float32[rank, dim] with (float)(1 / sqrt(dim)) where
+    k % rank == r and 0 elsewhere -- every component takes part, trace(Omega^T Omega) is 1"""
+    rank = dim if rank is None else rank
+    om = np.zeros((rank, dim), dtype=np.float32)
+    k = np.arange(dim)
+    om[k % rank, k] = np.float32(1.0 / np.sqrt(np.float64(dim)))
+    return om
+
+
+def _gmlvq_omega(cb, omega):
+    """a float32[rank, dim] copy of the matrix the call may write; None: gmlvq_omega(dim)"""
+    if omega is None:
+        return gmlvq_omega(cb.dim)
+    omega = np.array(omega, dtype=np.float32, ndmin=2)
+    if omega.ndim != 2 or omega.shape[1] != cb.dim:
+        raise ValueError("omega has shape %s, the codebook %d components" % (omega.shape, cb.dim))
+    return np.ascontiguousarray(omega)
+
+
+def gmlvq_train(cb, ds, epochs, alpha, eps, omega=None, sigmoid_beta=0.0, start_epoch=0, count=None, first=0, n=None, stats=True):
+    """Epochs [start_epoch, start_epoch + count) of batch GMLVQ over data rows (first + s) % ds.n, s < n
+    (somhip_gmlvq_train): batch GLVQ under d(x, w) = |Omega (x - w)|^2, the matrix Omega [rank, dim] learned at the rate
+    glvq_alpha(eps, epochs, t) by the gradient that moves the rows and scaled to trace(Omega^T Omega) = 1 after every
+    step.  omega: the matrix the call starts from, taken as it is (None: gmlvq_omega(dim)); its rows are the rank; eps = 0
+    leaves it alone.  Returns (omega float32[rank, dim], cost float64[count], correct int64[count]) -- cost and correct of
+    the state each epoch started from -- or omega alone with stats=False.  Hand omega on to continue a run."""
+    count = epochs - start_epoch if count is None else count
+    n = ds.n if n is None else n
+    om = _gmlvq_omega(cb, omega)
+    p = _lib.GmlvqParams(epochs, start_epoch, count, first, n, alpha, sigmoid_beta, eps, om.shape[0])
+    cost = np.zeros(max(count, 0), dtype=np.float64) if stats else None
+    correct = np.zeros(max(count, 0), dtype=np.int64) if stats else None
+    check(cb.e.lib.somhip_gmlvq_train(cb.h, ds.h, C.byref(p), _p(om, _lib.c_float_p), _p(cost, _lib.c_double_p),
+                                      _p(correct, _lib.c_i64_p)))
+    return (om, cost, correct) if stats else om
+
+
+def gmlvq_search(cb, ds, omega=None, first=0, n=None):
+    """The class-wise winner search under |Omega (x - w)|^2 (somhip_gmlvq_search): (dplus float32[n], iplus int32[n],
+    dminus, iminus) -- per sample the nearest row of its own class and of any other.  A sample is classified correctly
+    where (dplus, iplus) < (dminus, iminus)."""
+    n = ds.n if n is None else n
+    om = _gmlvq_omega(cb, omega)
+    dp, dm = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.float32)
+    ip, im = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    check(cb.e.lib.somhip_gmlvq_search(cb.h, ds.h, first, n, _p(om, _lib.c_float_p), om.shape[0], _p(dp, _lib.c_float_p),
+                                       _p(ip, _lib.c_i32_p), _p(dm, _lib.c_float_p), _p(im, _lib.c_i32_p)))
+    return dp, ip, dm, im
+
+
+def gmlvq_project(cb, ds=None, omega=None, first=0, n=None):
+    """Omega applied to rows (somhip_gmlvq_project): float32[n, rank] for data rows (first + s) % ds.n, s < n, or, with ds
+    None, float32[cb.n, rank] for the codebook's rows -- the values the search reads, and the picture at rank 2"""
+    om = _gmlvq_omega(cb, omega)
+    n = (cb.n if ds is None else ds.n) if n is None else n
+    out = np.zeros((max(n, 0), om.shape[0]), dtype=np.float32)
+    check(cb.e.lib.somhip_gmlvq_project(cb.h, None if ds is None else ds.h, first, n, _p(om, _lib.c_float_p), om.shape[0],
+                                        _p(out, _lib.c_float_p)))
+    return out
+
+
+def gmlvq_sums(cb, ds, omega=None, first=0, n=None, sigmoid_beta=0.0):
+    """Projection, search, terms, sums and the gradient of omega of a GMLVQ epoch (somhip_debug_gmlvq_sums), as a dict:
+    glvq_sums' entries under the projected distance, and grad float64[rank, dim] (Gm)"""
+    n = ds.n if n is None else n
+    om = _gmlvq_omega(cb, omega)
+    d = lambda *shape: np.zeros(shape, dtype=np.float64)
+    out = {"xi_plus": d(n), "xi_minus": d(n), "f": d(n), "sums_plus": d(cb.n, cb.dim + 1), "sums_minus": d(cb.n, cb.dim + 1),
+           "n_plus": np.zeros(cb.n, dtype=np.uint32), "n_minus": np.zeros(cb.n, dtype=np.uint32), "cost": d(cb.n),
+           "grad": d(om.shape[0], cb.dim)}
+    correct = C.c_int64(0)
+    dp, up = _lib.c_double_p, _lib.c_u32_p
+    check(cb.e.lib.somhip_debug_gmlvq_sums(cb.h, ds.h, first, n, sigmoid_beta, _p(om, _lib.c_float_p), om.shape[0],
+                                           _p(out["xi_plus"], dp), _p(out["xi_minus"], dp), _p(out["f"], dp), _p(out["sums_plus"], dp),
+                                           _p(out["n_plus"], up), _p(out["sums_minus"], dp), _p(out["n_minus"], up), _p(out["cost"], dp),
+                                           C.byref(correct), _p(out["grad"], dp)))
+    out["correct"] = correct.value
+    return out
+
+
+def gmlvq_update(cb, alpha_t, eps_t, n, omega, sums_plus, n_plus, sums_minus, n_minus, grad):
+    """The update and omega's step alone (somhip_debug_gmlvq_update) from host-supplied sums as gmlvq_sums returns them:
+    the rows move with a = float64(alpha_t) / n through the omega given; returns the omega after the step with eps_t (the
+    bits of the one given where eps_t == 0 or the step lands on the zero matrix)"""
+    sp, sm = np.ascontiguousarray(sums_plus, dtype=np.float64), np.ascontiguousarray(sums_minus, dtype=np.float64)
+    cp, cm = np.ascontiguousarray(n_plus, dtype=np.uint32), np.ascontiguousarray(n_minus, dtype=np.uint32)
+    om = _gmlvq_omega(cb, omega)
+    g = np.ascontiguousarray(grad, dtype=np.float64)
+    assert sp.shape == sm.shape == (cb.n, cb.dim + 1) and cp.shape == cm.shape == (cb.n,) and g.shape == om.shape
+    check(cb.e.lib.somhip_debug_gmlvq_update(cb.h, float(np.float32(alpha_t)), float(np.float32(eps_t)), n, _p(om, _lib.c_float_p),
+                                             om.shape[0], _p(sp, _lib.c_double_p), _p(cp, _lib.c_u32_p), _p(sm, _lib.c_double_p),
+                                             _p(cm, _lib.c_u32_p), _p(g, _lib.c_double_p)))
+    return om
 
 
 def _distortion_totals(tot):

@@ -203,6 +203,12 @@ int glvq_training(struct teach_params *teach, long epochs, float sigmoid_beta, d
  * search (somhip_grlvq_search): *final_cost and *final_correct describe teach->codes under lambda as the call leaves them. */
 int grlvq_training(struct teach_params *teach, long epochs, float sigmoid_beta, float eps, float *lambda, double *cost, int64_t *correct,
                    double *final_cost, int64_t *final_correct);
+/* batch GMLVQ (somhip_gmlvq_train): glvq_training under d(x, w) = |Omega (x - w)|^2.  omega ([rank][dim], in and out): the
+ * matrix, taken as it is and left as the run ends; eps: its rate.  epochs 0: nothing is trained.  Then one more search
+ * (somhip_gmlvq_search): *final_cost and *final_correct describe teach->codes under omega as the call leaves them.
+ * projected: NULL, or [rows of the data][rank] for the data under that omega (somhip_gmlvq_project). */
+int gmlvq_training(struct teach_params *teach, long epochs, float sigmoid_beta, float eps, float *omega, int rank, double *cost,
+                   int64_t *correct, double *final_cost, int64_t *final_correct, float *projected);
 /* batch neural gas (somhip_ng_train): `epochs` epochs over all of teach->data, lambda from lambda0 down to lambda_end,
  * ranks 0 for the engine's rule, on the rows of teach->codes, which it replaces (lattice and labels play no part).  line:
  * NULL, or [epochs] for each epoch's lambda and ranks as the engine forms them and the quantization error (find_qerror's sum)

@@ -788,6 +788,39 @@ int grlvq_training(struct teach_params *teach, long epochs, float sigmoid_beta, 
   return rc;
 }
 
+int gmlvq_training(struct teach_params *teach, long epochs, float sigmoid_beta, float eps, float *omega, int rank, double *cost,
+                   int64_t *correct, double *final_cost, int64_t *final_correct, float *projected)
+{
+  const long n = teach->data->num_entries;
+  if (n <= 0) { fprintf(stderr, "gmlvq_training: can't get data\n"); return 1; }
+  struct mirrors m = {NULL, NULL};
+  int rc = mirrors_open(&m, teach->codes, 1, teach->data, 1);
+  if (!rc && epochs > 0) {
+    somhip_gmlvq_params p = {epochs, 0, epochs, 0, n, teach->alpha, sigmoid_beta, eps, rank};
+    rc = said(somhip_gmlvq_train(m.cb, m.ds, &p, omega, cost, correct)) || said(somhip_codebook_download(m.cb, teach->codes->points));
+  }
+  if (!rc) {                                               /* the state it ends with: one more search, the terms in double here */
+    float *d = malloc(sizeof(float) * 2 * (size_t)n);
+    int32_t *i = malloc(sizeof(int32_t) * 2 * (size_t)n);
+    rc = said(somhip_gmlvq_search(m.cb, m.ds, 0, n, omega, rank, d, i, d + n, i + n));
+    double chain = 0.0;
+    int64_t right = 0;
+    for (long s = 0; !rc && s < n; s++) {
+      const double dp = (double)d[s], dm = (double)d[n + s], D = dp + dm;
+      const double mu = D == 0.0 ? 0.0 : (dp - dm) / D;
+      chain += sigmoid_beta != 0.0f ? 1.0 / (1.0 + exp(-(double)sigmoid_beta * mu)) : mu;
+      right += d[s] < d[n + s] || (d[s] == d[n + s] && i[s] < i[n + s]);
+    }
+    *final_cost = chain / (double)n;
+    *final_correct = right;
+    free(d);
+    free(i);
+  }
+  if (!rc && projected) rc = said(somhip_gmlvq_project(m.cb, m.ds, 0, n, omega, rank, projected));
+  mirrors_close(&m);
+  return rc;
+}
+
 int ng_training(struct teach_params *teach, long epochs, double lambda0, double lambda_end, long ranks, struct ng_line *line)
 {
   const long n = teach->data->num_entries;
