@@ -117,6 +117,15 @@ int  somhip_debug_prepared(somhip_codebook *cb, somhip_dataset *ds, int64_t firs
                            uint16_t *chi, uint16_t *clo, float *cn, float *rowmajor, uint16_t *xhi, uint16_t *xlo,
                            uint16_t *xrow, float *tau, float *tau1, int32_t info[4]);
 
+/* diagnostics (tests): the codebook's cache of prepared copies as it lies on the device now, left by whatever search or
+ * writer ran last, and the flags that say whether a search may trust it.  Nothing is launched and no flag changes; the
+ * engine's stream is synchronised.  flags[0] = the tiles and norms describe the rows as they are (prep_valid), flags[1] =
+ * so does the row-major copy (rowmajor_valid), flags[2] = a batch-map accumulation is open (bm_open), flags[3] = a
+ * somhip_batchmap_finish has written rows from it (bm_moved).  chi, clo, cn, rowmajor: as somhip_debug_prepared sizes
+ * them; each may be null, and one the codebook never allocated is left unwritten -- whatever the flags say. */
+int  somhip_debug_prepared_state(somhip_codebook *cb, int32_t flags[4], uint16_t *chi, uint16_t *clo, float *cn,
+                                 float *rowmajor);
+
 /* diagnostics (tests): the nearest-row search of data rows [first, first+count) on a pre-filter route, with the pairs of
  * the exact re-rank selected from level 2's lists (from_lists = 1, two-level route only: what the search itself does
  * there) or from the whole matrix of group minima (from_lists = 0).  Returns, with *bpad = count rounded up to 32 and

@@ -87,6 +87,7 @@ SIGNATURES = {
     "somhip_debug_level1": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, c_float_p, c_u32_p, c_i64_p]),
     "somhip_debug_prepared": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, c_u16_p, c_u16_p, c_float_p, c_float_p,
                                         c_u16_p, c_u16_p, c_u16_p, c_float_p, c_float_p, c_i32_p]),
+    "somhip_debug_prepared_state": (C.c_int, [C.c_void_p, c_i32_p, c_u16_p, c_u16_p, c_float_p, c_float_p]),
     "somhip_debug_rerank_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, c_float_p, c_u64_p, c_u32_p,
                                             c_float_p, c_u32_p, c_u32_p, c_u32_p, C.c_int64, c_i64_p, c_u64_p, c_i64_p]),
     "somhip_debug_scan_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, c_i32_p]),

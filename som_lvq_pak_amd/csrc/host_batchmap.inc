@@ -112,7 +112,7 @@ static int batchmap_combine_stage(somhip_codebook *cb, float r, const BatchmapBu
   if (groups < 0) groups = cb->v.ngroups;
   if (groups == 0) return 0;
   const dim3 grid((unsigned)groups, (unsigned)((cb->v.d + BM_COLS - 1) / BM_COLS));
-  cb->prep_valid = false;
+  cb->prep_valid = cb->rowmajor_valid = false;
   if (gauss) {
     const size_t t_len = batchmap_table_len(cb);
     CHK(LAUNCH_TIMED(e, KID_BATCHMAP_COMBINE, k_batchmap_gauss_table, dim3((unsigned)((t_len + BM_THREADS - 1) / BM_THREADS)), dim3(BM_THREADS), 0,
@@ -391,7 +391,7 @@ extern "C" int somhip_som_batchmap_ranks(somhip_codebook *cb, somhip_dataset *bl
       if (gn > 0) CHK(on_device(e, st.send, cb->v.tiles + group_floats * (size_t)g0, group_floats * (size_t)gn));
       CHK(somhip_comm_allgather(c, st.send, st.recv, (int64_t)(sizeof(float) * group_floats * (size_t)share)));
       CHK(on_device(e, cb->v.tiles, st.recv, group_floats * (size_t)ngroups));   // (shares are consecutive: the gathered ranges are the tiles)
-      cb->prep_valid = false;
+      cb->prep_valid = cb->rowmajor_valid = false;
       if (q) {
         BatchmapTail tail;
         CHK(to_host_sync(e, &tail, batchmap_tail(cb), 1));

@@ -143,7 +143,7 @@ static int glvq_sums_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t firs
 // Step 5: the rows from b.S and b.hits
 static int glvq_update_stage(somhip_codebook *cb, float alpha_t, int64_t n, const GlvqBufs &b) {
   const int64_t threads = cb->v.ngroups * cb->v.d4 * WAVE;
-  cb->prep_valid = false;
+  cb->prep_valid = cb->rowmajor_valid = false;
   cb->bm_open = false;
   return LAUNCH_TIMED(cb->e, KID_GLVQ_UPDATE, k_glvq_update, dim3((unsigned)((threads + GLVQ_THREADS - 1) / GLVQ_THREADS)), dim3(GLVQ_THREADS), 0, cb->v,
                       b.S, b.hits, (double)alpha_t / (double)n);

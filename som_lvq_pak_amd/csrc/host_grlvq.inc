@@ -81,7 +81,7 @@ static int grlvq_sums_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t fir
 // Step 6: the rows from b.g.S, b.g.hits and b.lam
 static int grlvq_update_stage(somhip_codebook *cb, float alpha_t, int64_t n, const GrlvqBufs &b) {
   const int64_t threads = cb->v.ngroups * cb->v.d4 * WAVE;
-  cb->prep_valid = false;
+  cb->prep_valid = cb->rowmajor_valid = false;
   cb->bm_open = false;
   return LAUNCH_TIMED(cb->e, KID_GRLVQ_UPDATE, k_grlvq_update<GLVQ_THREADS>, dim3((unsigned)((threads + GLVQ_THREADS - 1) / GLVQ_THREADS)), dim3(GLVQ_THREADS), 0,
                       cb->v, b.g.S, b.g.hits, reinterpret_cast<const float *>(b.lam), (double)alpha_t / (double)n);

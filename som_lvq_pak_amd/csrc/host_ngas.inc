@@ -134,7 +134,7 @@ static int ng_sums_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t first,
 // Step 4: the rows from b.S
 static int ng_update_stage(somhip_codebook *cb, const NgBufs &b) {
   const int64_t threads = cb->v.ngroups * cb->v.d4 * WAVE;
-  cb->prep_valid = false;
+  cb->prep_valid = cb->rowmajor_valid = false;
   cb->bm_open = false;                                                  // (the rows move: an open batch-map accumulation is over)
   return LAUNCH_TIMED(cb->e, KID_NG_UPDATE, k_ng_update, dim3((unsigned)((threads + NG_THREADS - 1) / NG_THREADS)), dim3(NG_THREADS), 0, cb->v, b.S);
 }

@@ -572,7 +572,7 @@ extern "C" int somhip_debug_prepared(somhip_codebook *cb, somhip_dataset *ds, in
   const bool two = p.route == ROUTE_TWO_LEVEL;
   PrefilterBufs b;
   CHK(bind_prefilter(cb, p, false, &b));
-  cb->prep_valid = false;                                // the codebook pass itself is what the caller asks about
+  cb->prep_valid = cb->rowmajor_valid = false;           // the codebook pass itself is what the caller asks about
   CHK(pf_prepare(cb, ds, first, count, p, b, nullptr, false));
   const size_t ctile = sizeof(uint4) * (size_t)cb->v.ngroups * p.d8 * WAVE, xtile = sizeof(uint4) * (size_t)p.nsb * p.d8 * 32;
   const bool has_lo = !two || p.l2_global;
@@ -590,6 +590,22 @@ extern "C" int somhip_debug_prepared(somhip_codebook *cb, somhip_dataset *ds, in
   info[0] = cb->rowmajor_valid; info[1] = has_lo; info[2] = two; info[3] = p.d8;
   return 0;
 } ABI_CATCH(somhip_debug_prepared)
+// the cache of prepared copies as it lies on the device, and its flags: nothing is launched, no flag changes
+extern "C" int somhip_debug_prepared_state(somhip_codebook *cb, int32_t *flags, uint16_t *chi, uint16_t *clo, float *cn,
+                                           float *rowmajor) try {
+  CHK(check_codebook(cb, flags != nullptr, "somhip_debug_prepared_state"));
+  somhip_engine *e = cb->e;
+  HIPCHK(hipSetDevice(e->device));
+  const size_t slots = (size_t)cb->v.ngroups * WAVE, ctile = sizeof(uint4) * slots * (size_t)((cb->v.d4 + 1) / 2);
+  auto get = [&](void *dst, const void *src, size_t bytes) { return dst && src ? to_host(e, (uint8_t *)dst, (const uint8_t *)src, bytes) : 0; };
+  CHK(get(chi, cb->d_chi, ctile));
+  CHK(get(clo, cb->d_clo, ctile));
+  CHK(get(cn, cb->d_cn, sizeof(float) * slots));
+  CHK(get(rowmajor, cb->d_rowmajor, sizeof(float) * slots * cb->v.d));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  flags[0] = cb->prep_valid; flags[1] = cb->rowmajor_valid; flags[2] = cb->bm_open; flags[3] = cb->bm_moved;
+  return 0;
+} ABI_CATCH(somhip_debug_prepared_state)
 // the nearest-row search of these rows with the selection of the re-rank's pairs by the kernel the caller names
 extern "C" int somhip_debug_rerank_pairs(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t count, int from_lists,
                                          float *wmin, uint64_t *wmask, uint32_t *gmin, float *tau, uint32_t *colcount,

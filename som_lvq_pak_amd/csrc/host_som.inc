@@ -91,7 +91,7 @@ static void som_trace(const StepScalars *sc, const uint64_t *keys, int64_t c, in
 static int som_train_online(somhip_codebook *cb, somhip_dataset *ds, const somhip_som_params *p,
                             int32_t *trace_index, float *trace_diff) {
   somhip_engine *e = cb->e;
-  cb->prep_valid = false;
+  cb->prep_valid = cb->rowmajor_valid = false;
   cb->bm_open = false;
   const int64_t CH = ONLINE_CHUNK;
   const bool G = cb->v.neigh == SOMHIP_NEIGH_GAUSSIAN, M = ds->d_mask != nullptr;
@@ -372,7 +372,7 @@ static int update_order_apply(somhip_engine *e, const somhip_codebook *cb, const
 static int som_update_planned(somhip_codebook *cb, somhip_dataset *ds, const UpdatePlan &p, int64_t data_first, int64_t count,
                               const uint64_t *d_keys, const StepScalars *d_sc) {
   somhip_engine *e = cb->e;
-  cb->prep_valid = false;
+  cb->prep_valid = cb->rowmajor_valid = false;
   cb->bm_open = false;
   UpdateBufs b; CHK(bind_update(e, cb, count, &b));
   if (p.decode) CHK(update_decode(e, cb, 0, count, d_keys, d_sc, b));
@@ -450,7 +450,7 @@ static int som_lazy_run(somhip_codebook *cb, somhip_dataset *ds, const UpdatePla
     if (p.decode) CHK(update_decode(e, cb, 0, head, kv, d_sc, b));
     CHK(update_members(e, cb, ds, p, row0, count, kv, d_sc, b));
   }
-  cb->prep_valid = false;
+  cb->prep_valid = cb->rowmajor_valid = false;
   cb->bm_open = false;
   return update_order_apply(e, cb, ds, p, row0, count, d_sc, b, !redo);
 }

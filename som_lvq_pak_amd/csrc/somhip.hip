@@ -531,7 +531,7 @@ struct somhip_codebook {
                                    // kept by the LVQ engine when it re-splits exactly the rows it corrected, cleared by every other writer)
   float *d_rowmajor = nullptr;     // [ngroups*64][d] fp32 rows, row-major: what the exact re-rank of single rows gathers from (a row is
                                    // 4 d contiguous bytes here, 16 bytes per KiB in the tiles); written by the full k_prep_codes_bf16
-  bool rowmajor_valid = false;     // ... and current only together with prep_valid and until a partial re-split (LVQ) clears it
+  bool rowmajor_valid = false;     // ... set only together with prep_valid; cleared with it by every writer, and alone by a partial re-split (LVQ)
   double *bm_state = nullptr;      // the batch map's continued accumulation (host_batchmap.inc): [S | counts][the tail], the codebook's own
   bool bm_open = false;            // ... opened by somhip_batchmap_begin; closed by _end and by every other writer of the rows
   bool bm_moved = false;           // ... a _finish has written rows from it: no further piece until the next _begin
@@ -570,7 +570,7 @@ static bool sample_is_empty(const somhip_dataset *ds, int64_t row) { return !ds-
 
 static int upload_rows(somhip_codebook *cb, const float *rows) {
   somhip_engine *e = cb->e;
-  cb->prep_valid = false;
+  cb->prep_valid = cb->rowmajor_valid = false;
   cb->bm_open = false;
   float *stage;
   const size_t count = (size_t)cb->v.n * cb->v.d;

@@ -584,6 +584,25 @@ def debug_prepared(cb, ds, first, count):
     return out
 
 
+def debug_prepared_state(cb):
+    """The codebook's cache of prepared copies as it lies on the device now (somhip_debug_prepared_state; nothing is
+    launched, no flag changes): a dict of the flags prep_valid, rowmajor_valid, bm_open, bm_moved (ints) and of chi, clo,
+    cn, rowmajor shaped as debug_prepared gives them -- None for a buffer the codebook never allocated.  The call leaves
+    such a buffer unwritten: the arrays go in as 0xFF bytes, which no copy of finite rows comes back as."""
+    d8, ng = (cb.dim + 7) // 8, (cb.n + 63) // 64
+    raw = {"chi": np.full((ng, d8, 64, 8), 0xFFFF, np.uint16), "clo": np.full((ng, d8, 64, 8), 0xFFFF, np.uint16),
+           "cn": np.full(ng * 64, 0xFFFFFFFF, np.uint32), "rowmajor": np.full((ng * 64, cb.dim), 0xFFFFFFFF, np.uint32)}
+    flags = (C.c_int32 * 4)()
+    u16, f32 = _lib.c_u16_p, _lib.c_float_p
+    check(cb.e.lib.somhip_debug_prepared_state(cb.h, flags, _p(raw["chi"], u16), _p(raw["clo"], u16), _p(raw["cn"].view(np.float32), f32),
+                                               _p(raw["rowmajor"].view(np.float32), f32)))
+    out = {"prep_valid": flags[0], "rowmajor_valid": flags[1], "bm_open": flags[2], "bm_moved": flags[3]}
+    for name, a in raw.items():
+        untouched = (a.view(np.uint8) == 0xFF).all()
+        out[name] = None if untouched else (a if a.dtype == np.uint16 else a.view(np.float32))
+    return out
+
+
 def debug_rerank_pairs(cb, ds, first, count, from_lists, pairs_cap=None):
     """The nearest-row search of data rows [first, first + count) with the re-rank's pairs selected from level 2's lists
     (from_lists) or from the whole matrix of group minima (somhip_debug_rerank_pairs): a dict of what the selection read
