@@ -1065,4 +1065,7 @@ int  somhip_timing_get(somhip_engine *e, int kernel, int64_t *launches, double *
 #ifdef __cplusplus
 }
 #endif
+
+/* batch Robust Soft LVQ (K13): its entry points have a header of their own, which every user of this one gets */
+#include "somhip_rslvq.h"
 #endif /* SOMHIP_H */

@@ -66,6 +66,11 @@ class GmlvqParams(C.Structure):
                 ("alpha", C.c_float), ("sigmoid_beta", C.c_float), ("eps", C.c_float), ("rank", C.c_int32)]
 
 
+class RslvqParams(C.Structure):
+    _fields_ = [("epochs", C.c_int64), ("start_epoch", C.c_int64), ("count", C.c_int64), ("first", C.c_int64), ("n", C.c_int64),
+                ("alpha", C.c_float), ("sigma2", C.c_float)]
+
+
 # name -> (restype, argtypes); exactly the symbols include/somhip.h declares
 SIGNATURES = {
     "somhip_last_error": (C.c_char_p, []),
@@ -240,6 +245,19 @@ SIGNATURES = {
     "somhip_timing_get": (C.c_int, [C.c_void_p, C.c_int, c_i64_p, c_double_p]),
 }
 
+# ... and exactly the symbols include/somhip_rslvq.h declares (batch Robust Soft LVQ, K13: the header somhip.h includes)
+RSLVQ_SIGNATURES = {
+    "somhip_rslvq_train": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RslvqParams), c_double_p, c_i64_p]),
+    "somhip_rslvq_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_float, c_double_p, c_i64_p, c_double_p]),
+    "somhip_debug_rslvq_chunk": (C.c_int, [C.c_int64, c_i64_p, c_i64_p]),
+    "somhip_debug_rslvq_posterior": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_float, C.c_int64, c_double_p,
+                                               c_double_p, c_i32_p, c_double_p]),
+    "somhip_debug_rslvq_sums": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, c_double_p, c_double_p,
+                                          c_double_p]),
+    "somhip_debug_rslvq_update": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_int64, c_double_p, c_double_p]),
+    "somhip_rslvq_timing": (C.c_int, [C.c_void_p, c_i64_p, c_double_p]),
+}
+
 _lib = None
 
 
@@ -251,7 +269,7 @@ def load():
             raise RuntimeError("%s not built -- run `make lib` (python -c 'import __graft_entry__ as g; "
                                "g.build()'); there is no CPU fallback" % LIB_PATH)
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(RSLVQ_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

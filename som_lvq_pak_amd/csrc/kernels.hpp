@@ -48,3 +48,4 @@
 #include "kernels/umat.hpp"
 #include "kernels/planes.hpp"
 #include "kernels/gmlvq.hpp"
+#include "kernels/rslvq.hpp"

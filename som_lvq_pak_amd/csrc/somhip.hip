@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -89,14 +90,16 @@ static const char *kKernelNames[KID_COUNT] = {
 // from it by bit.  Kernels added since are timed by LaunchTimer all the same, under ids that follow the table; an entry
 // point of their own reports them (somhip_mapset_timing, somhip_knn_timing, somhip_knn_vote_timing, somhip_map_quality_timing,
 // somhip_batchmap_timing, somhip_conn_timing, somhip_distortion_timing, somhip_glvq_timing, somhip_ng_timing,
-// somhip_grlvq_timing, somhip_gmlvq_timing).
+// somhip_grlvq_timing, somhip_gmlvq_timing, somhip_rslvq_timing).  somhip_timing_select's mask has one bit per id up to
+// 63; the ids from 64 on are outside it and are timed whenever timing is on.
 enum TimedOnlyId { KID_MAPSET_TRAIN = KID_COUNT, KID_MAPSET_WINNERS, KID_KNN_DIST, KID_KNN_SELECT, KID_KNN_VOTE, KID_QUALITY_PAIRS,
                    KID_QUALITY_UNITS, KID_BATCHMAP_GROUP, KID_BATCHMAP_SUMS, KID_BATCHMAP_COMBINE, KID_CONN_KEYS, KID_CONN_SORT,
                    KID_CONN_RUNS, KID_CONN_MERGE, KID_DISTORTION_GROUP, KID_DISTORTION_SUMS, KID_DISTORTION_EVALUATE, KID_GLVQ_SEARCH,
                    KID_GLVQ_TERMS, KID_GLVQ_SUMS, KID_GLVQ_UPDATE, KID_NG_GROUP, KID_NG_SUMS, KID_NG_UPDATE,
                    KID_GRLVQ_SEARCH, KID_GRLVQ_SUMS, KID_GRLVQ_RELEVANCE, KID_GRLVQ_UPDATE,
-                   KID_GMLVQ_PROJECT, KID_GMLVQ_GRAD, KID_GMLVQ_UPDATE, KID_TIMED };
-static_assert(KID_TIMED <= 64, "somhip_timing_select's mask has one bit per kernel id");
+                   KID_GMLVQ_PROJECT, KID_GMLVQ_GRAD, KID_GMLVQ_UPDATE,
+                   KID_RSLVQ_DIST, KID_RSLVQ_POSTERIOR, KID_RSLVQ_SUMS, KID_RSLVQ_UPDATE, KID_TIMED };
+static_assert(KID_RSLVQ_DIST == 64, "the ids somhip_timing_select's mask can name end with K12's");
 extern "C" int somhip_kernel_count(void) { return KID_COUNT; }
 extern "C" const char *somhip_kernel_name(int i) { return (i >= 0 && i < KID_COUNT) ? kKernelNames[i] : ""; }
 
@@ -170,6 +173,9 @@ enum ScratchSlot {
   SLOT_GMLVQ,              // batch GMLVQ (host_gmlvq.inc) beside SLOT_GLVQ and SLOT_GLVQ_LIST: the projected storage tiles and sample
                            // tiles, K9's g and P per row, the gradient of Omega, Omega and its transpose
   SLOT_GMLVQ_PART,         // ... the gradient's partial sums per block of samples; the public projection's row-major output
+  SLOT_RSLVQ,              // batch RSLVQ (host_rslvq.inc): [G | c] per row, and per sample cost, P(y | x) and the correct flag
+  SLOT_RSLVQ_Q,            // ... the posterior coefficients of a chunk of samples (SLOT_KNN_DIST the chunk's distances, SLOT_SAMPLES
+                           // its sample tiles)
   SLOT_COUNT
 };
 
@@ -322,7 +328,7 @@ struct LaunchTimer {   // HIP events on the engine's own stream around one launc
   hipEvent_t a = nullptr, b = nullptr;
   bool on = false;
   LaunchTimer(somhip_engine *e_, int kid_) : e(e_), kid(kid_) {
-    if (kid_ < 0 || !e->timing || !((e->timing_mask >> kid_) & 1ull)) return;
+    if (kid_ < 0 || !e->timing || (kid_ < 64 && !((e->timing_mask >> kid_) & 1ull))) return;
     auto get = [&](hipEvent_t *ev) {
       if (!e->pool.empty()) { *ev = e->pool.back(); e->pool.pop_back(); return true; }
       return hipEventCreate(ev) == hipSuccess;
@@ -851,3 +857,4 @@ extern "C" void somhip_dataset_destroy(somhip_dataset *ds) try {
 #include "host_grlvq.inc"
 #include "host_distortion.inc"
 #include "host_gmlvq.inc"
+#include "host_rslvq.inc"

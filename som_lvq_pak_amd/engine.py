@@ -193,6 +193,15 @@ class Engine:
         return {"k_gmlvq_project": (n[0], ms[0]), "search": (n[1], ms[1]), "terms": (n[2], ms[2]), "sums": (n[3], ms[3]),
                 "k_gmlvq_omega_grad": (n[4], ms[4]), "k_gmlvq_update": (n[5], ms[5])}
 
+    def rslvq_timing(self):
+        """(launches, ms) of batch RSLVQ's stages while timing is on (somhip_rslvq_timing; they are not in timing_table
+        and not under timing_select): distances = the sample tiles and k_knn_dist, one span per chunk"""
+        n = (C.c_int64 * 4)()
+        ms = (C.c_double * 4)()
+        check(self.lib.somhip_rslvq_timing(self.h, n, ms))
+        return {"distances": (n[0], ms[0]), "k_rslvq_posterior": (n[1], ms[1]), "k_rslvq_sums": (n[2], ms[2]),
+                "k_rslvq_update": (n[3], ms[3])}
+
     def distortion_timing(self):
         """(launches, ms) of map distortion's stages while timing is on (somhip_distortion_timing; they are not in
         timing_table): group = the winners pass per chunk, the scan of the counts and the sort by winner; sums = the
@@ -1038,6 +1047,76 @@ def gmlvq_update(cb, alpha_t, eps_t, n, omega, sums_plus, n_plus, sums_minus, n_
                                              om.shape[0], _p(sp, _lib.c_double_p), _p(cp, _lib.c_u32_p), _p(sm, _lib.c_double_p),
                                              _p(cm, _lib.c_u32_p), _p(g, _lib.c_double_p)))
     return om
+
+
+def rslvq_chunk(n_rows, lib=None):
+    """(chunk, ld) of a codebook of n_rows rows (somhip_debug_rslvq_chunk): the samples per chunk that rslvq_train and
+    rslvq_search take, and the leading dimension 64 * ceil(n_rows / 64) of the coefficients.  Host arithmetic: no GPU needed."""
+    lib = lib or _lib.load()
+    chunk, ld = C.c_int64(0), C.c_int64(0)
+    check(lib.somhip_debug_rslvq_chunk(n_rows, C.byref(chunk), C.byref(ld)))
+    return chunk.value, ld.value
+
+
+def rslvq_train(cb, ds, epochs, alpha, sigma2, start_epoch=0, count=None, first=0, n=None, stats=True):
+    """Epochs [start_epoch, start_epoch + count) of batch Robust Soft LVQ over data rows (first + s) % ds.n, s < n
+    (somhip_rslvq_train): every epoch is one full-batch gradient step of E = mean -log P(y | x) under a Gaussian mixture
+    of squared width sigma2 at the rate glvq_alpha(alpha, epochs, t) / sigma2.  alpha has the unit of a squared distance.
+    Returns (cost float64[count], correct int64[count]) of the codebook each epoch started from, or None with stats=False."""
+    count = epochs - start_epoch if count is None else count
+    n = ds.n if n is None else n
+    p = _lib.RslvqParams(epochs, start_epoch, count, first, n, alpha, sigma2)
+    cost = np.zeros(max(count, 0), dtype=np.float64) if stats else None
+    correct = np.zeros(max(count, 0), dtype=np.int64) if stats else None
+    check(cb.e.lib.somhip_rslvq_train(cb.h, ds.h, C.byref(p), _p(cost, _lib.c_double_p), _p(correct, _lib.c_i64_p)))
+    return (cost, correct) if stats else None
+
+
+def rslvq_search(cb, ds, sigma2, first=0, n=None, pown=True):
+    """The evaluation of a model (somhip_rslvq_search): (cost, correct, pown float64[n] or None) -- the mean of
+    -log P(y | x), the samples whose nearest row carries their label, and P(y | x) per sample.  The rows are not touched."""
+    n = ds.n if n is None else n
+    cost, correct = C.c_double(0), C.c_int64(0)
+    po = np.zeros(n, dtype=np.float64) if pown else None
+    check(cb.e.lib.somhip_rslvq_search(cb.h, ds.h, first, n, sigma2, C.byref(cost), C.byref(correct), _p(po, _lib.c_double_p)))
+    return cost.value, correct.value, po
+
+
+def rslvq_posterior(cb, ds, sigma2, first=0, n=None, chunk=0):
+    """Distances and posteriors of an RSLVQ epoch (somhip_debug_rslvq_posterior), as a dict: q float64[n, ld] (the
+    coefficients, zeros behind column cb.n), cost float64[n], correct int32[n], pown float64[n].  chunk: the samples per
+    launch, a multiple of 64 (0: rslvq_chunk's)."""
+    n = ds.n if n is None else n
+    ld = rslvq_chunk(cb.n, cb.e.lib)[1]
+    out = {"q": np.full((n, ld), np.nan), "cost": np.zeros(n), "correct": np.zeros(n, dtype=np.int32), "pown": np.zeros(n)}
+    dp = _lib.c_double_p
+    check(cb.e.lib.somhip_debug_rslvq_posterior(cb.h, ds.h, first, n, sigma2, chunk, _p(out["q"], dp), _p(out["cost"], dp),
+                                                _p(out["correct"], _lib.c_i32_p), _p(out["pown"], dp)))
+    return out
+
+
+def rslvq_sums(cb, ds, q, first=0, n=None, chunk=0):
+    """[G | c] = Q^T [X | 1] alone (somhip_debug_rslvq_sums) on the caller's q float64[n, cb.n] or [n, ld]: (G float64[cb.n,
+    dim], c float64[cb.n])"""
+    n = ds.n if n is None else n
+    ld = rslvq_chunk(cb.n, cb.e.lib)[1]
+    q = np.asarray(q, dtype=np.float64)
+    assert q.shape in ((n, cb.n), (n, ld)), q.shape
+    qp = np.zeros((n, ld), dtype=np.float64)
+    qp[:, :q.shape[1]] = q
+    G, c = np.zeros((cb.n, cb.dim), dtype=np.float64), np.zeros(cb.n, dtype=np.float64)
+    dp = _lib.c_double_p
+    check(cb.e.lib.somhip_debug_rslvq_sums(cb.h, ds.h, first, n, chunk, _p(qp, dp), _p(G, dp), _p(c, dp)))
+    return G, c
+
+
+def rslvq_update(cb, alpha_t, sigma2, n, G, c):
+    """The update alone (somhip_debug_rslvq_update) from host-supplied sums as rslvq_sums returns them, with
+    a = float64(alpha_t) / (float64(sigma2) * n); every row is stepped"""
+    G, c = np.ascontiguousarray(G, dtype=np.float64), np.ascontiguousarray(c, dtype=np.float64)
+    assert G.shape == (cb.n, cb.dim) and c.shape == (cb.n,)
+    check(cb.e.lib.somhip_debug_rslvq_update(cb.h, float(np.float32(alpha_t)), float(np.float32(sigma2)), n, _p(G, _lib.c_double_p),
+                                             _p(c, _lib.c_double_p)))
 
 
 def _distortion_totals(tot):

@@ -209,6 +209,13 @@ int grlvq_training(struct teach_params *teach, long epochs, float sigmoid_beta, 
  * projected: NULL, or [rows of the data][rank] for the data under that omega (somhip_gmlvq_project). */
 int gmlvq_training(struct teach_params *teach, long epochs, float sigmoid_beta, float eps, float *omega, int rank, double *cost,
                    int64_t *correct, double *final_cost, int64_t *final_correct, float *projected);
+/* batch Robust Soft LVQ (somhip_rslvq_train): `epochs` epochs over all of teach->data at rates from teach->alpha down, under
+ * a mixture of squared width sigma2, on the labelled rows of teach->codes, which it replaces.  epochs 0: nothing is trained.
+ * cost, correct: NULL, or [epochs] for the figures of the codebook every epoch started from.  Then one evaluation
+ * (somhip_rslvq_search): *final_cost and *final_correct describe teach->codes as the call leaves them; pown: NULL, or
+ * [rows of the data] for P(label | x) under them.  0, or 1 after a message. */
+int rslvq_training(struct teach_params *teach, long epochs, float sigma2, double *cost, int64_t *correct, double *final_cost,
+                   int64_t *final_correct, double *pown);
 /* batch neural gas (somhip_ng_train): `epochs` epochs over all of teach->data, lambda from lambda0 down to lambda_end,
  * ranks 0 for the engine's rule, on the rows of teach->codes, which it replaces (lattice and labels play no part).  line:
  * NULL, or [epochs] for each epoch's lambda and ranks as the engine forms them and the quantization error (find_qerror's sum)

@@ -756,6 +756,22 @@ int glvq_training(struct teach_params *teach, long epochs, float sigmoid_beta, d
   return rc;
 }
 
+int rslvq_training(struct teach_params *teach, long epochs, float sigma2, double *cost, int64_t *correct, double *final_cost,
+                   int64_t *final_correct, double *pown)
+{
+  const long n = teach->data->num_entries;
+  if (n <= 0) { fprintf(stderr, "rslvq_training: can't get data\n"); return 1; }
+  struct mirrors m = {NULL, NULL};
+  int rc = mirrors_open(&m, teach->codes, 1, teach->data, 1);
+  if (!rc && epochs > 0) {
+    somhip_rslvq_params p = {epochs, 0, epochs, 0, n, teach->alpha, sigma2};
+    rc = said(somhip_rslvq_train(m.cb, m.ds, &p, cost, correct)) || said(somhip_codebook_download(m.cb, teach->codes->points));
+  }
+  if (!rc) rc = said(somhip_rslvq_search(m.cb, m.ds, 0, n, sigma2, final_cost, final_correct, pown));   /* the state it ends with */
+  mirrors_close(&m);
+  return rc;
+}
+
 int grlvq_training(struct teach_params *teach, long epochs, float sigmoid_beta, float eps, float *lambda, double *cost, int64_t *correct,
                    double *final_cost, int64_t *final_correct)
 {
