@@ -67,6 +67,21 @@ def posterior(codes, clab, data, dlab, sigma2, first=0, n=None, d=None):
             "z_all": z_all, "z_own": z_own, "la": la, "lo": lo, "d": d}
 
 
+PER_SAMPLE = ("q", "cost", "pown", "correct", "P", "t", "own", "z_all", "z_own", "la", "lo", "d")
+
+
+def posterior_by_row(codes, clab, data, dlab, sigma2):
+    """posterior() of every data row once: a sample's figures depend on its data row alone, so those of a run of any
+    length are posterior_of_run of this"""
+    return posterior(codes, clab, data, dlab, sigma2, 0, data.shape[0])
+
+
+def posterior_of_run(by_row, first, n):
+    """the dict posterior(..., first, n) returns, taken from posterior_by_row's: run sample s is data row (first + s) % rows"""
+    r = run_rows(by_row["cost"].shape[0], first, n)
+    return {key: by_row[key][r] for key in PER_SAMPLE}
+
+
 def posterior_bounds(p):
     """(bound of q [n][rows], of cost [n], of pown [n], of sum_j q [n]) between two evaluations of the definition whose exp
     and log are each within 1 ulp.  R = the rows.
@@ -103,6 +118,19 @@ def sums_longdouble(q, data, first=0):
     G, c = ql.T @ x, ql.sum(axis=0)
     k = (2.0 * n + 16.0) * ULP
     return G, c, k * (np.abs(ql).T @ np.abs(x)).astype(f64) + TINY, k * np.abs(ql).sum(axis=0).astype(f64) + TINY
+
+
+def sums_by_row_longdouble(q_rows, data, first, n):
+    """sums_longdouble of the run (first, n) from one q row per data row (posterior_by_row's): every distinct row enters
+    once, weighted by how often the run takes it -- the same sums and the same bound with the same n, without the
+    [n][rows] array of a long run over a large codebook"""
+    ld = np.longdouble
+    w = np.bincount(run_rows(data.shape[0], first, n), minlength=data.shape[0]).astype(ld)
+    x, ql = data.astype(ld), q_rows.astype(ld)
+    qw, aw = ql * w[:, None], np.abs(ql) * w[:, None]
+    G, c = qw.T @ x, qw.sum(axis=0)
+    k = (2.0 * n + 16.0) * ULP
+    return G, c, k * (aw.T @ np.abs(x)).astype(f64) + TINY, k * aw.sum(axis=0).astype(f64) + TINY
 
 
 def sums_mfma(q, data, first=0):

@@ -222,8 +222,11 @@ def edge_case(seed, rows, dim, n_data, classes):
 WORST = {}
 
 
-def check_posterior(E, eng, c, cl, x, dl, sigma2, first, n, tag):
-    cb, ds = E.Codebook(eng, c, labels=cl), E.Dataset(eng, x, labels=dl)
+def check_posterior(E, eng, c, cl, x, dl, sigma2, first, n, tag, cb=None):
+    """cb: the caller's codebook of the rows c and labels cl (a map stored in patches, say), left open; else one without a
+    lattice is made here"""
+    mine = cb is None
+    cb, ds = E.Codebook(eng, c, labels=cl) if mine else cb, E.Dataset(eng, x, labels=dl)
     rows = c.shape[0]
     got = E.rslvq_posterior(cb, ds, sigma2, first, n, chunk=64)
     again = E.rslvq_posterior(cb, ds, sigma2, first, n, chunk=64)
@@ -248,14 +251,17 @@ def check_posterior(E, eng, c, cl, x, dl, sigma2, first, n, tag):
     for k, v in worst.items():
         WORST[k] = max(WORST.get(k, 0.0), v)
     print("rslvq posterior", tag, "largest difference / bound:", worst, "so far:", WORST)
-    cb.close(); ds.close()
+    ds.close()
+    if mine:
+        cb.close()
     return got, p
 
 
 # rows x dim x samples x classes: every row count, dimension and run length the issue names, run lengths 65 / 130 / 200
-# crossing one, two and three edges of the 64-sample chunk
+# crossing one, two and three edges of the 64-sample chunk; 321 and 1030 rows are 6 and 17 row groups without a lattice,
+# the last of 1 and of 6 rows: k_knn_dist's last grid.y block (four groups a block) holds two live groups and one
 POSTERIOR_SHAPES = [(2, 1, 1, 2), (3, 3, 3, 3), (63, 63, 4, 3), (64, 64, 5, 4), (65, 65, 63, 5), (130, 129, 64, 7), (130, 3, 65, 2),
-                    (65, 64, 130, 6), (130, 16, 200, 7), (3, 129, 200, 2)]
+                    (65, 64, 130, 6), (130, 16, 200, 7), (3, 129, 200, 2), (321, 5, 70, 6), (1030, 3, 65, 4)]
 
 
 @pytest.mark.gpu
@@ -274,15 +280,22 @@ def test_posterior_within_the_derived_bounds(E, eng, rows, dim, n, classes):
 def test_posterior_at_the_ends_of_sigma2(E, eng, rows, dim, n, classes):
     """sigma2 so small that every posterior but the nearest rows' underflows to zero, and so large that they are uniform"""
     c, cl, x, dl = edge_case(2100 + rows, rows, dim, max(n, 5), classes)
-    got, p = check_posterior(E, eng, c, cl, x, dl, 1e-30, 0, n, (rows, dim, n, "tiny"))
+    check_the_ends_of_sigma2(E, eng, c, cl, x, dl, n, (rows, dim, n))
+
+
+def check_the_ends_of_sigma2(E, eng, c, cl, x, dl, n, tag, cb=None):
+    """(the posteriors at sigma2 = 1e-30, the replay's) after the assertions of both ends"""
+    rows = c.shape[0]
+    tiny = got, p = check_posterior(E, eng, c, cl, x, dl, 1e-30, 0, n, tag + ("tiny",), cb)
     d = p["d"]
     nearest = d == d.min(axis=1, keepdims=True)
     assert (got["q"][:, :rows][~nearest & ~p["own"]] == 0).all()                    # underflowed, not merely small
     lost = ~(nearest & p["own"]).any(axis=1)                                        # no own-label row among the nearest
     assert (got["pown"][lost] == 0).all() and (got["correct"][lost] == 0).all()
-    got, p = check_posterior(E, eng, c, cl, x, dl, 1e30, 0, n, (rows, dim, n, "huge"))
+    got, p = check_posterior(E, eng, c, cl, x, dl, 1e30, 0, n, tag + ("huge",), cb)
     n_own = p["own"].sum(axis=1)
     assert np.allclose(got["pown"], n_own / rows, rtol=1e-12) and np.allclose(got["q"][:, :rows][~p["own"]], -1.0 / rows, rtol=1e-12)
+    return tiny
 
 
 @pytest.mark.gpu
@@ -310,7 +323,8 @@ def random_q(seed, n, rows):
     return q
 
 
-SUMS_SHAPES = [(2, 1, 1), (3, 3, 5), (63, 63, 63), (64, 64, 64), (65, 65, 65), (130, 129, 200), (130, 64, 4), (65, 3, 3), (2, 130, 130)]
+SUMS_SHAPES = [(2, 1, 1), (3, 3, 5), (63, 63, 63), (64, 64, 64), (65, 65, 65), (130, 129, 200), (130, 64, 4), (65, 3, 3), (2, 130, 130),
+               (321, 5, 130)]                                                         # six workgroups along grid.x, the last of one row
 
 
 @pytest.mark.gpu
