@@ -1040,8 +1040,9 @@ int  somhip_umatrix(somhip_codebook *cb, int filters, float *u, double minmax[2]
  *           and 0.5 where the float difference maxval - minval is zero (planes.c:172-176).
  * Any topology is taken.  A caller bounds what both sides hold at once by asking for the planes in windows.
  * Refused before any launch: null arguments, a codebook whose engine was destroyed, a shard (contiguous or
- * interleaved), n_planes < 1, a window that is not inside [0, dim).  Non-finite components: a NaN takes no part in
- * minval and maxval, as in the reference; what follows from there is not specified. */
+ * interleaved), n_planes < 1, a window that is not inside [0, dim).  Non-finite components: as in the reference,
+ * minval starts at FLT_MAX and maxval at -FLT_MAX, so a NaN takes no part in either, +inf is never minval and -inf never
+ * maxval (a column of +inf alone has lo = FLT_MAX, hi = +inf); the grey levels follow from those by the formula above. */
 int  somhip_planes(somhip_codebook *cb, int first_plane, int n_planes, float *grey, float *lo, float *hi);
 
 /* device scratch helpers for hosts without their own allocator */

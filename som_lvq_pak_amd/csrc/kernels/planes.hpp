@@ -14,8 +14,10 @@
 //                      lo key = (order(p) << 32) | unit      hi key = (~order(p) << 32) | unit
 //                    order() maps float bits to unsigned integers of the same order (negative floats do not order as
 //                    their bit patterns) with both zeros at one value, so the smallest key is the extreme value at the
-//                    first unit that holds it -- the row whose bits the reference keeps.  NaN wins no comparison in the
-//                    reference and gets no key here.  Padding lanes of the last row group and padding dims of the last
+//                    first unit that holds it -- the row whose bits the reference keeps.  The reference starts from
+//                    minval = FLT_MAX and maxval = -FLT_MAX, so NaN wins no comparison and gets no key, a value
+//                    >= FLT_MAX (+inf) gets no lo key and a value <= -FLT_MAX (-inf) no hi key: a column of +inf alone
+//                    keeps minval = FLT_MAX.  Padding lanes of the last row group and padding dims of the last
 //                    chunk get no key either.  Every wave walks a slab of row groups and leaves its keys in a table
 //                    of partial results; no atomics (with one pair of words per plane, the 64 to 128 waves that meet
 //                    at each word took as long as the read of the rows: profiles/planes_vs_host.txt).
@@ -52,12 +54,13 @@ __device__ __forceinline__ uint32_t planes_order(float v) {
   return b ^ (static_cast<uint32_t>(static_cast<int32_t>(b) >> 31) | 0x80000000u);
 }
 
+// a lo key only for p < FLT_MAX and a hi key only for p > -FLT_MAX: the comparisons the reference's start values lose
 __device__ __forceinline__ void planes_keys(float p, uint32_t unit, bool take, uint64_t &klo, uint64_t &khi) {
-  if (!take || p != p) return;
+  if (!take) return;
   const uint32_t o = planes_order(p);
   const uint64_t a = (static_cast<uint64_t>(o) << 32) | unit, b = (static_cast<uint64_t>(~o) << 32) | unit;
-  klo = a < klo ? a : klo;
-  khi = b < khi ? b : khi;
+  klo = (p < __uint_as_float(FLT_MAX_BITS) && a < klo) ? a : klo;
+  khi = (p > -__uint_as_float(FLT_MAX_BITS) && b < khi) ? b : khi;
 }
 
 // =====================================================================================

@@ -35,6 +35,19 @@ def bounds(col):
     return col[np.argmin(col)], col[np.argmax(col)]
 
 
+def bounds_any(col):
+    """bounds() for columns that may hold NaN and infinities: planes.c:147-154 as it runs.  minval starts at FLT_MAX and
+    maxval at -FLT_MAX; `minval > p` / `maxval < p` replace them in row order.  So NaN never replaces either, a value
+    >= FLT_MAX never becomes minval, a value <= -FLT_MAX never becomes maxval, and a column without a candidate keeps the
+    start value.  Equal to bounds() on finite columns whose values lie strictly between the two start values."""
+    col = np.ascontiguousarray(col, dtype=F32)
+    with np.errstate(invalid="ignore"):
+        below, above = np.nonzero(col < FLT_MAX)[0], np.nonzero(col > -FLT_MAX)[0]
+    lo = col[below[np.argmin(col[below])]] if len(below) else F32(FLT_MAX)
+    hi = col[above[np.argmax(col[above])]] if len(above) else F32(-FLT_MAX)
+    return lo, hi
+
+
 def grey_of(col, lo, hi, mode="reference"):
     """cv of every row.  mode: "reference"; "all_float" (every operation in float32) and "double_difference" (p - minval
     and maxval - minval taken in float64) are the two near misses the rounding map tells apart"""
@@ -55,14 +68,15 @@ def grey_of(col, lo, hi, mode="reference"):
         return (F64(0.05) + quot).astype(F32)
 
 
-def planes(rows, first=0, count=None, mode="reference"):
-    """(grey [count, n], lo [count], hi [count]) float32: what somhip_planes returns"""
+def planes(rows, first=0, count=None, mode="reference", bounds_of=bounds):
+    """(grey [count, n], lo [count], hi [count]) float32: what somhip_planes returns (bounds_of=bounds_any for rows with
+    NaN or infinities)"""
     rows = np.ascontiguousarray(rows, dtype=F32)
     count = rows.shape[1] - first if count is None else count
     grey = np.empty((count, rows.shape[0]), dtype=F32)
     lo, hi = np.empty(count, dtype=F32), np.empty(count, dtype=F32)
     for j in range(count):
-        lo[j], hi[j] = bounds(rows[:, first + j])
+        lo[j], hi[j] = bounds_of(rows[:, first + j])
         grey[j] = grey_of(rows[:, first + j], lo[j], hi[j], mode)
     return grey, lo, hi
 
