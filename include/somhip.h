@@ -1069,4 +1069,7 @@ int  somhip_timing_get(somhip_engine *e, int kernel, int64_t *launches, double *
 
 /* batch Robust Soft LVQ (K13): its entry points have a header of their own, which every user of this one gets */
 #include "somhip_rslvq.h"
+/* batch GLVQ (K9) over data in pieces and over the row blocks of ranks: somhip_glvq_begin / _accumulate / _finish / _end /
+ * _state and somhip_glvq_train_ranks, likewise */
+#include "somhip_glvq_pieces.h"
 #endif /* SOMHIP_H */

@@ -258,6 +258,16 @@ RSLVQ_SIGNATURES = {
     "somhip_rslvq_timing": (C.c_int, [C.c_void_p, c_i64_p, c_double_p]),
 }
 
+# ... and exactly the symbols include/somhip_glvq_pieces.h declares (batch GLVQ, K9, over data in pieces and over ranks)
+GLVQ_PIECES_SIGNATURES = {
+    "somhip_glvq_begin": (C.c_int, [C.c_void_p]),
+    "somhip_glvq_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_float]),
+    "somhip_glvq_finish": (C.c_int, [C.c_void_p, C.c_float, c_double_p, c_i64_p, c_i64_p]),
+    "somhip_glvq_end": (C.c_int, [C.c_void_p]),
+    "somhip_glvq_state": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), c_i64_p]),
+    "somhip_glvq_train_ranks": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(GlvqParams), C.c_void_p, c_double_p, c_i64_p]),
+}
+
 _lib = None
 
 
@@ -269,7 +279,7 @@ def load():
             raise RuntimeError("%s not built -- run `make lib` (python -c 'import __graft_entry__ as g; "
                                "g.build()'); there is no CPU fallback" % LIB_PATH)
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(RSLVQ_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(RSLVQ_SIGNATURES.items()) + list(GLVQ_PIECES_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

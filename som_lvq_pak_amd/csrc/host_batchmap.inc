@@ -113,6 +113,7 @@ static int batchmap_combine_stage(somhip_codebook *cb, float r, const BatchmapBu
   if (groups == 0) return 0;
   const dim3 grid((unsigned)groups, (unsigned)((cb->v.d + BM_COLS - 1) / BM_COLS));
   cb->prep_valid = cb->rowmajor_valid = false;
+  cb->gl_open = false;                                                  // (the rows move: an open GLVQ accumulation is over)
   if (gauss) {
     const size_t t_len = batchmap_table_len(cb);
     CHK(LAUNCH_TIMED(e, KID_BATCHMAP_COMBINE, k_batchmap_gauss_table, dim3((unsigned)((t_len + BM_THREADS - 1) / BM_THREADS)), dim3(BM_THREADS), 0,
@@ -151,7 +152,7 @@ extern "C" int somhip_som_batchmap(somhip_codebook *cb, somhip_dataset *ds, cons
                 (long long)p->epochs);
   somhip_engine *e = cb->e;
   HIPCHK(hipSetDevice(e->device));
-  cb->bm_open = false;                                                  // (the rows move: an open accumulation is over)
+  cb->bm_open = cb->gl_open = false;                                                  // (the rows move: an open accumulation is over)
   BatchmapBufs b;
   CHK(batchmap_bind(cb, p->n, &b));
   const float T = (float)p->epochs;
@@ -188,7 +189,7 @@ extern "C" int somhip_debug_batchmap_combine(somhip_codebook *cb, float r, const
   if (!(r >= 0.0f)) return fail("somhip_debug_batchmap_combine: radius %g < 0", (double)r);
   somhip_engine *e = cb->e;
   HIPCHK(hipSetDevice(e->device));
-  cb->bm_open = false;
+  cb->bm_open = cb->gl_open = false;
   BatchmapBufs b;
   CHK(batchmap_bind(cb, 0, &b));
   const size_t units = (size_t)cb->v.n, d = (size_t)cb->v.d;

@@ -1,6 +1,8 @@
 // host_glvq.inc -- K9, batch GLVQ: per epoch the class-wise winners of every sample against the frozen codebook (search),
 // the per-sample terms and the grouping by winner of both roles (terms), the per-prototype ordered fp64 sums (sums) and
-// the update; the four stages on their own for the tests
+// the update; the four stages on their own for the tests; the same epoch over data in pieces (somhip_glvq_begin /
+// _accumulate / _finish: the sums' chains continued from piece to piece) and over the row blocks of G ranks
+// (somhip_glvq_train_ranks)
 // (included by somhip.hip behind host_batchmap.inc: one translation unit, shared static helpers, rocPRIM's sort)
 
 // The route of the search, for every caller: a function of the shape alone.  The list route costs one exact top-8 search
@@ -30,15 +32,16 @@ struct GlvqBufs {
   size_t sort_bytes = 0;
   unsigned sort_bits = 0;
 };
-// n: the samples of the call, 0 where only the update runs
-static int glvq_bind(somhip_codebook *cb, int64_t n, GlvqBufs *b) {
+// n: the samples of the call, 0 where only the update runs.  state (or null): S and cost are the codebook's own continued
+// accumulation, not engine scratch, and the slot holds the rest only (hits is then the piece's own counts).
+static int glvq_bind(somhip_codebook *cb, int64_t n, GlvqBufs *b, double *state = nullptr) {
   somhip_engine *e = cb->e;
   const size_t units = (size_t)cb->v.n, ns = (size_t)n, s_len = 2 * units * (size_t)(cb->v.d + 1);
   void *p;
-  CHK(engine_scratch(e, SLOT_GLVQ, sizeof(double) * (s_len + units) + sizeof(uint32_t) * (4 * units + 4), &p));
-  b->S = (double *)p;
+  CHK(engine_scratch(e, SLOT_GLVQ, sizeof(double) * (state ? 0 : s_len + units) + sizeof(uint32_t) * (4 * units + 4), &p));
+  b->S = state ? state : (double *)p;
   b->cost = b->S + s_len;
-  b->hits = reinterpret_cast<uint32_t *>(b->cost + units);
+  b->hits = state ? (uint32_t *)p : reinterpret_cast<uint32_t *>(b->cost + units);
   b->starts = b->hits + 2 * units;
   b->correct = b->starts + 2 * (units + 1);
   b->rem_count = b->correct + 1;
@@ -134,17 +137,20 @@ static int glvq_terms_stage(somhip_codebook *cb, int64_t n, float beta, const Gl
   }
   return 0;
 }
-// Step 4: b.S and b.cost from the lists
-static int glvq_sums_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, const GlvqBufs &b) {
+// Step 4: b.S and b.cost from the lists.  cont: the chains go on from what b.S and b.cost hold.
+static int glvq_sums_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, const GlvqBufs &b, bool cont = false) {
   const dim3 grid((unsigned)cb->v.n, (unsigned)((cb->v.d + 2 + BM_SUM_DIMS - 1) / BM_SUM_DIMS), 2);
-  return LAUNCH_TIMED(cb->e, KID_GLVQ_SUMS, k_glvq_sums, grid, dim3(BM_SUM_DIMS), 0, ds->d_rows, ds->n, ds->d, first % ds->n, n, (uint32_t)cb->v.n,
+  if (cont)
+    return LAUNCH_TIMED(cb->e, KID_GLVQ_SUMS, k_glvq_sums<true>, grid, dim3(BM_SUM_DIMS), 0, ds->d_rows, ds->n, ds->d, first % ds->n, n, (uint32_t)cb->v.n,
+                        b.list, b.starts, b.xi, b.f, b.S, b.cost);
+  return LAUNCH_TIMED(cb->e, KID_GLVQ_SUMS, k_glvq_sums<false>, grid, dim3(BM_SUM_DIMS), 0, ds->d_rows, ds->n, ds->d, first % ds->n, n, (uint32_t)cb->v.n,
                       b.list, b.starts, b.xi, b.f, b.S, b.cost);
 }
 // Step 5: the rows from b.S and b.hits
 static int glvq_update_stage(somhip_codebook *cb, float alpha_t, int64_t n, const GlvqBufs &b) {
   const int64_t threads = cb->v.ngroups * cb->v.d4 * WAVE;
   cb->prep_valid = cb->rowmajor_valid = false;
-  cb->bm_open = false;
+  cb->bm_open = cb->gl_open = false;
   return LAUNCH_TIMED(cb->e, KID_GLVQ_UPDATE, k_glvq_update, dim3((unsigned)((threads + GLVQ_THREADS - 1) / GLVQ_THREADS)), dim3(GLVQ_THREADS), 0, cb->v,
                       b.S, b.hits, (double)alpha_t / (double)n);
 }
@@ -303,3 +309,206 @@ extern "C" int somhip_glvq_timing(somhip_engine *e, int64_t launches[4], double 
   for (int i = 0; i < 4; i++) { launches[i] = e->launches[kid[i]]; total_ms[i] = e->total_ms[kid[i]]; }
   return 0;
 } ABI_CATCH(somhip_glvq_timing)
+
+// ---------------------------------------------------------------------------------
+// The epoch over data in pieces (include/somhip_glvq_pieces.h).  The state is one device blob the codebook owns:
+// [Sp | sp][Sm | sm] as 2 x rows x (dim + 1) doubles, cost[rows] doubles, np[rows] and nm[rows] as uint32, then the tail --
+// the samples taken and the correct ones among them.  Nothing of an accumulation lives on the host between calls, so the
+// blob copied into another codebook of the same shape (its own state opened by _begin) continues there: that is what hands
+// the chains from rank to rank.
+// ---------------------------------------------------------------------------------
+struct GlvqTail { uint64_t samples, correct; };
+static_assert(sizeof(GlvqTail) == 16, "the tail of the GLVQ state is two words of 8 bytes");
+static size_t glvq_state_doubles(const somhip_codebook *cb) { return (size_t)cb->v.n * (2 * (size_t)(cb->v.d + 1) + 1); }
+static size_t glvq_state_bytes(const somhip_codebook *cb) {
+  return sizeof(double) * glvq_state_doubles(cb) + sizeof(uint32_t) * 2 * (size_t)cb->v.n + sizeof(GlvqTail);
+}
+static uint32_t *glvq_state_counts(const somhip_codebook *cb) { return reinterpret_cast<uint32_t *>(cb->gl_state + glvq_state_doubles(cb)); }
+static GlvqTail *glvq_state_tail(const somhip_codebook *cb) { return reinterpret_cast<GlvqTail *>(glvq_state_counts(cb) + 2 * (size_t)cb->v.n); }
+
+// opens the state as all-zero bits (+0.0 throughout, counts and tail 0)
+static int glvq_state_open(somhip_codebook *cb) {
+  if (!cb->gl_state) HIPCHK(hipMalloc((void **)&cb->gl_state, glvq_state_bytes(cb)));
+  HIPCHK(hipMemsetAsync(cb->gl_state, 0, glvq_state_bytes(cb), cb->e->stream));
+  cb->gl_open = true;
+  cb->gl_moved = false;
+  return 0;
+}
+static void glvq_state_free(somhip_codebook *cb) {
+  if (cb->gl_state) (void)hipFree(cb->gl_state);
+  cb->gl_state = nullptr;
+  cb->gl_open = cb->gl_moved = false;
+}
+static int glvq_check_open(const somhip_codebook *cb, const char *who) {
+  return cb->gl_open && cb->gl_state ? 0 : fail("%s: no accumulation is open on this codebook (somhip_glvq_begin first; a call that writes "
+                                                 "the rows closes it)", who);
+}
+// The tail as the pieces so far left it, and the refusal of a piece of n samples that would take the total to 2^32: a copy
+// and a comparison, before anything is bound or launched.
+static int glvq_read_tail(somhip_codebook *cb, int64_t n, const char *who, GlvqTail *tail) {
+  CHK(to_host_sync(cb->e, tail, glvq_state_tail(cb), 1));
+  if (tail->samples + (uint64_t)n >= (uint64_t)1 << 32)
+    return fail("%s: %llu + %lld samples do not fit the 32-bit counts", who, (unsigned long long)tail->samples, (long long)n);
+  return 0;
+}
+// The sums half of a piece whose search, terms and grouping have run into b (bound with the state): the chains go on, the
+// counts and the tail grow -- on the device, by one writer per word.
+static int glvq_take_piece(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, const GlvqBufs &b) {
+  const uint32_t words = 2 * (uint32_t)cb->v.n;
+  CHK(glvq_sums_stage(cb, ds, first, n, b, true));
+  return LAUNCH_TIMED(cb->e, KID_GLVQ_SUMS, k_glvq_counts, dim3((words + GLVQ_THREADS - 1) / GLVQ_THREADS), dim3(GLVQ_THREADS), 0, b.hits, b.correct,
+                      (uint64_t)n, words, glvq_state_counts(cb), reinterpret_cast<uint64_t *>(glvq_state_tail(cb)));
+}
+// Step 5 from the state, whose tail the caller has read (samples > 0), with the epoch's two figures: the host's chain over
+// cost[] in row order / samples, and the tail's count.  The state stays open, moved.
+static int glvq_finish_state(somhip_codebook *cb, float alpha_t, const GlvqTail &tail, double *cost_out, int64_t *correct_out) {
+  somhip_engine *e = cb->e;
+  GlvqBufs b;
+  b.S = cb->gl_state;
+  b.cost = b.S + 2 * (size_t)cb->v.n * (size_t)(cb->v.d + 1);
+  b.hits = glvq_state_counts(cb);
+  if (cost_out) {
+    std::vector<double> hc((size_t)cb->v.n);
+    CHK(to_host_sync(e, hc.data(), b.cost, hc.size()));
+    double chain = 0.0;
+    for (double c : hc) chain += c;
+    *cost_out = chain / (double)tail.samples;
+  }
+  if (correct_out) *correct_out = (int64_t)tail.correct;
+  CHK(glvq_update_stage(cb, alpha_t, (int64_t)tail.samples, b));
+  cb->gl_open = cb->gl_moved = true;                                    // (the update closes every accumulation; this one stays, moved)
+  return 0;
+}
+
+extern "C" int somhip_glvq_begin(somhip_codebook *cb) try {
+  const char *who = "somhip_glvq_begin";
+  CHK(check_codebook(cb, true, who));
+  CHK(glvq_check_codebook(cb, who));
+  HIPCHK(hipSetDevice(cb->e->device));
+  CHK(glvq_state_open(cb));
+  HIPCHK(hipStreamSynchronize(cb->e->stream));
+  return 0;
+} ABI_CATCH(somhip_glvq_begin)
+
+extern "C" int somhip_glvq_accumulate(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, float sigmoid_beta) try {
+  const char *who = "somhip_glvq_accumulate";
+  CHK(check_pair(cb, ds, who));
+  CHK(glvq_check_beta(sigmoid_beta, who));
+  CHK(glvq_check(cb, ds, first, n, who));
+  CHK(glvq_check_open(cb, who));
+  if (cb->gl_moved) return fail("%s: the codebook has moved (somhip_glvq_finish has run; somhip_glvq_begin opens the next epoch)", who);
+  somhip_engine *e = cb->e;
+  GlvqTail tail;
+  CHK(glvq_read_tail(cb, n, who, &tail));                               // (the last refusal: nothing is bound before it)
+  GlvqBufs b;
+  CHK(glvq_bind(cb, n, &b, cb->gl_state));
+  CHK(glvq_search_stage(cb, ds, first, n, glvq_plan(cb->v.n, cb->v.d, n), b, nullptr));
+  CHK(glvq_terms_stage(cb, n, sigmoid_beta, b));
+  CHK(glvq_take_piece(cb, ds, first, n, b));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  return 0;
+} ABI_CATCH(somhip_glvq_accumulate)
+
+extern "C" int somhip_glvq_finish(somhip_codebook *cb, float alpha_t, double *cost_out, int64_t *correct_out, int64_t *samples_out) try {
+  const char *who = "somhip_glvq_finish";
+  CHK(check_codebook(cb, true, who));
+  CHK(glvq_check_codebook(cb, who));
+  CHK(glvq_check_open(cb, who));
+  if (!(alpha_t >= 0.0f)) return fail("%s: alpha_t %g is negative or not a number", who, (double)alpha_t);
+  if (cb->gl_moved) return fail("%s: the codebook has moved (somhip_glvq_finish has run; somhip_glvq_begin opens the next epoch)", who);
+  somhip_engine *e = cb->e;
+  HIPCHK(hipSetDevice(e->device));
+  GlvqTail tail;
+  CHK(glvq_read_tail(cb, 0, who, &tail));
+  if (tail.samples == 0) return fail("%s: the state holds no sample", who);
+  CHK(glvq_finish_state(cb, alpha_t, tail, cost_out, correct_out));
+  if (samples_out) *samples_out = (int64_t)tail.samples;
+  HIPCHK(hipStreamSynchronize(e->stream));
+  return 0;
+} ABI_CATCH(somhip_glvq_finish)
+
+extern "C" int somhip_glvq_end(somhip_codebook *cb) try {
+  CHK(check_codebook(cb, true, "somhip_glvq_end"));
+  somhip_engine *e = cb->e;
+  HIPCHK(hipSetDevice(e->device));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  glvq_state_free(cb);
+  return 0;
+} ABI_CATCH(somhip_glvq_end)
+
+extern "C" int somhip_glvq_state(somhip_codebook *cb, void **dev_state, int64_t *bytes) try {
+  CHK(check_codebook(cb, dev_state && bytes, "somhip_glvq_state"));
+  CHK(glvq_check_open(cb, "somhip_glvq_state"));
+  *dev_state = cb->gl_state;
+  *bytes = (int64_t)glvq_state_bytes(cb);
+  return 0;
+} ABI_CATCH(somhip_glvq_state)
+
+// The epochs of somhip_glvq_train over the row blocks of the communicator's ranks, block by block in rank order.  Every
+// rank holds the whole codebook.  Per epoch: search, terms and grouping on every rank's own block at once; then, rank after
+// rank, the continued sums on the rank whose turn it is and the state broadcast from it; then the same update from the
+// same state on every rank.
+extern "C" int somhip_glvq_train_ranks(somhip_codebook *cb, somhip_dataset *block, const somhip_glvq_params *p, somhip_comm *c,
+                                       double *cost_out, int64_t *correct_out) try {
+  const char *who = "somhip_glvq_train_ranks";
+  CHK(check_codebook(cb, p && c, who));
+  const bool empty = p->n == 0;                                          // a rank whose block holds no row: legal here and only here
+  if (p->epochs < 1) return fail("%s: epochs %lld < 1", who, (long long)p->epochs);
+  if (p->start_epoch < 0 || p->count < 0 || p->start_epoch + p->count > p->epochs)
+    return fail("%s: epochs [%lld, %lld) outside [0, %lld)", who, (long long)p->start_epoch, (long long)(p->start_epoch + p->count), (long long)p->epochs);
+  if (!(p->alpha >= 0.0f)) return fail("%s: alpha %g is negative or not a number", who, (double)p->alpha);
+  CHK(glvq_check_beta(p->sigmoid_beta, who));
+  if (c->e != cb->e) return fail("%s: codebook and communicator belong to different engines", who);
+  if (empty) CHK(glvq_check_codebook(cb, who));
+  else CHK(glvq_check(cb, block, p->first, p->n, who));
+  somhip_engine *e = cb->e;
+  HIPCHK(hipSetDevice(e->device));
+  // The blocks' rows together must fit the 32-bit counts: every rank learns the total (summed as two 16-bit halves, so the
+  // words cannot overflow) and refuses alike, before any rank has launched anything.
+  struct Words {
+    uint32_t *d = nullptr;
+    ~Words() { if (d) (void)hipFree(d); }
+  } w;
+  HIPCHK(hipMalloc((void **)&w.d, 2 * sizeof(uint32_t)));
+  uint32_t halves[2] = {(uint32_t)(p->n >> 16), (uint32_t)(p->n & 0xffff)};
+  CHK(to_device(e, w.d, halves, 2));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  CHK(somhip_comm_allreduce_sum_u32(c, w.d, 2));
+  CHK(to_host_sync(e, halves, w.d, 2));
+  const uint64_t total = ((uint64_t)halves[0] << 16) + halves[1];
+  if (total >= (uint64_t)1 << 32) return fail("%s: the ranks' %llu samples do not fit the 32-bit counts", who, (unsigned long long)total);
+  if (total == 0) return fail("%s: no rank holds a row", who);
+  auto epochs = [&]() -> int {
+    const int route = empty ? SOMHIP_GLVQ_DIRECT : glvq_plan(cb->v.n, cb->v.d, p->n);
+    const float T = (float)p->epochs;
+    CHK(glvq_state_open(cb));                                           // (the blob exists from here on: its address is bound once;
+    GlvqBufs b;                                                         //  every epoch opens it again, which re-zeroes it)
+    CHK(glvq_bind(cb, p->n, &b, cb->gl_state));
+    for (int64_t t = p->start_epoch; t < p->start_epoch + p->count; t++) {
+      const float alpha_t = p->alpha * (float)(p->epochs - t) / T;
+      CHK(glvq_state_open(cb));
+      if (!empty) {
+        CHK(glvq_search_stage(cb, block, p->first, p->n, route, b, nullptr));
+        CHK(glvq_terms_stage(cb, p->n, p->sigmoid_beta, b));
+      }
+      for (int root = 0; root < c->world; root++) {
+        if (root == c->rank && !empty) CHK(glvq_take_piece(cb, block, p->first, p->n, b));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        CHK(somhip_comm_broadcast(c, cb->gl_state, (int64_t)glvq_state_bytes(cb), root));
+      }
+      GlvqTail tail;
+      CHK(to_host_sync(e, &tail, glvq_state_tail(cb), 1));
+      if (tail.samples != total) return fail("%s: the state holds %llu of %llu samples", who, (unsigned long long)tail.samples, (unsigned long long)total);
+      CHK(glvq_finish_state(cb, alpha_t, tail, cost_out ? cost_out + (t - p->start_epoch) : nullptr,
+                            correct_out ? correct_out + (t - p->start_epoch) : nullptr));
+    }
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return 0;
+  };
+  const int rc = epochs();
+  // The state was the epochs' own, on every way out: closed, so that no later _finish updates from a state that was
+  // broadcast half way, and freed.
+  (void)hipStreamSynchronize(e->stream);
+  glvq_state_free(cb);
+  return rc;
+} ABI_CATCH(somhip_glvq_train_ranks)

@@ -109,7 +109,7 @@ static int gmlvq_grad_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t fir
 // Step 6: the rows from b.g.S, b.g.hits and b.om
 static int gmlvq_update_stage(somhip_codebook *cb, float alpha_t, int64_t n, const GmlvqBufs &b) {
   cb->prep_valid = cb->rowmajor_valid = false;
-  cb->bm_open = false;
+  cb->bm_open = cb->gl_open = false;
   return LAUNCH_TIMED(cb->e, KID_GMLVQ_UPDATE, k_gmlvq_update<GMLVQ_THREADS>, dim3((unsigned)cb->v.n), dim3(GMLVQ_THREADS), 0, cb->v, b.g.S, b.g.hits, b.om,
                       b.omT, b.m, b.gbuf, b.P, (double)alpha_t / (double)n);
 }

@@ -82,7 +82,7 @@ static int grlvq_sums_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t fir
 static int grlvq_update_stage(somhip_codebook *cb, float alpha_t, int64_t n, const GrlvqBufs &b) {
   const int64_t threads = cb->v.ngroups * cb->v.d4 * WAVE;
   cb->prep_valid = cb->rowmajor_valid = false;
-  cb->bm_open = false;
+  cb->bm_open = cb->gl_open = false;
   return LAUNCH_TIMED(cb->e, KID_GRLVQ_UPDATE, k_grlvq_update<GLVQ_THREADS>, dim3((unsigned)((threads + GLVQ_THREADS - 1) / GLVQ_THREADS)), dim3(GLVQ_THREADS), 0,
                       cb->v, b.g.S, b.g.hits, reinterpret_cast<const float *>(b.lam), (double)alpha_t / (double)n);
 }

@@ -135,7 +135,7 @@ static int ng_sums_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t first,
 static int ng_update_stage(somhip_codebook *cb, const NgBufs &b) {
   const int64_t threads = cb->v.ngroups * cb->v.d4 * WAVE;
   cb->prep_valid = cb->rowmajor_valid = false;
-  cb->bm_open = false;                                                  // (the rows move: an open batch-map accumulation is over)
+  cb->bm_open = cb->gl_open = false;                                                  // (the rows move: an open batch-map accumulation is over)
   return LAUNCH_TIMED(cb->e, KID_NG_UPDATE, k_ng_update, dim3((unsigned)((threads + NG_THREADS - 1) / NG_THREADS)), dim3(NG_THREADS), 0, cb->v, b.S);
 }
 
@@ -186,7 +186,7 @@ extern "C" int somhip_ng_train(somhip_codebook *cb, somhip_dataset *ds, const so
   CHK(ng_check(cb, ds, p->first, p->n, who));
   somhip_engine *e = cb->e;
   HIPCHK(hipSetDevice(e->device));
-  cb->bm_open = false;
+  cb->bm_open = cb->gl_open = false;
   const int64_t units = cb->v.n;
   // the schedule of every epoch of the call, before the first launch: the tables are read until their copies have run
   std::vector<double> w((size_t)p->count * SOMHIP_KNN_MAX);

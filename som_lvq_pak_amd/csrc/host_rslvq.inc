@@ -70,7 +70,7 @@ static int rslvq_sums_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t fir
 static int rslvq_update_stage(somhip_codebook *cb, float alpha_t, float sigma2, int64_t n, const RslvqBufs &b) {
   const int64_t threads = cb->v.ngroups * cb->v.d4 * WAVE;
   cb->prep_valid = cb->rowmajor_valid = false;
-  cb->bm_open = false;
+  cb->bm_open = cb->gl_open = false;
   const double den = (double)sigma2 * (double)n;
   return LAUNCH_TIMED(cb->e, KID_RSLVQ_UPDATE, k_rslvq_update, dim3((unsigned)((threads + RS_THREADS - 1) / RS_THREADS)), dim3(RS_THREADS), 0, cb->v,
                       b.G, (double)alpha_t / den);

@@ -92,7 +92,7 @@ static int som_train_online(somhip_codebook *cb, somhip_dataset *ds, const somhi
                             int32_t *trace_index, float *trace_diff) {
   somhip_engine *e = cb->e;
   cb->prep_valid = cb->rowmajor_valid = false;
-  cb->bm_open = false;
+  cb->bm_open = cb->gl_open = false;
   const int64_t CH = ONLINE_CHUNK;
   const bool G = cb->v.neigh == SOMHIP_NEIGH_GAUSSIAN, M = ds->d_mask != nullptr;
   uint64_t *slot; StepScalars *sc; int64_t *rowidx;
@@ -373,7 +373,7 @@ static int som_update_planned(somhip_codebook *cb, somhip_dataset *ds, const Upd
                               const uint64_t *d_keys, const StepScalars *d_sc) {
   somhip_engine *e = cb->e;
   cb->prep_valid = cb->rowmajor_valid = false;
-  cb->bm_open = false;
+  cb->bm_open = cb->gl_open = false;
   UpdateBufs b; CHK(bind_update(e, cb, count, &b));
   if (p.decode) CHK(update_decode(e, cb, 0, count, d_keys, d_sc, b));
   CHK(update_members(e, cb, ds, p, data_first, count, d_keys, d_sc, b));
@@ -451,7 +451,7 @@ static int som_lazy_run(somhip_codebook *cb, somhip_dataset *ds, const UpdatePla
     CHK(update_members(e, cb, ds, p, row0, count, kv, d_sc, b));
   }
   cb->prep_valid = cb->rowmajor_valid = false;
-  cb->bm_open = false;
+  cb->bm_open = cb->gl_open = false;
   return update_order_apply(e, cb, ds, p, row0, count, d_sc, b, !redo);
 }
 // the plan som_update_run makes for a run (somhip.h): the same checks as somhip_som_batch_update, host arithmetic only

@@ -17,6 +17,8 @@ namespace somhip {
 //            integer atomics; then K8's k_batchmap_starts and the stable sort by winner, once per role.
 //   sums     k_glvq_sums: per (prototype, role) one chain of fp64 additions from +0.0 over the role's list in data order
 //            of xi * (double)x[k]; the trailing column carries the sum of xi, and for role + the sum of f goes to cost[].
+//            k_glvq_sums<true> continues the chains a piece of the data left in S and cost (somhip_glvq_accumulate), and
+//            k_glvq_counts behind it adds the piece's counts to the state's integers.
 //   update   k_glvq_update: w <- (float)(W + a * ((Sp - sp W) - (Sm - sm W))) over the storage tiles, in place.
 //
 // No floating-point atomics anywhere: every sum is a function of the data, the codebook and the shape alone.
@@ -237,6 +239,11 @@ __global__ __launch_bounds__(GLVQ_THREADS) void k_glvq_terms(const uint64_t *__r
 // of u in data order (sample s is data row (first + s) % n_rows, first < n_rows); column k = d: the same chain over xi
 // alone (xi * 1.0 is xi); column k = d + 1 of role +: the chain over f[s], written to cost[u].  S is [2][n_units][d + 1].
 // The list is known, so GLVQ_SUM_AHEAD entries -- sample, weight, row element -- are requested before their additions run.
+// CONT: the data come in pieces and S, cost hold what the pieces before this one left (all +0.0 before the first): every
+// chain goes on from its stored value, and a (u, role) without a sample in this piece is left as it stands.  A chain from a
+// stored +0.0 is the chain from +0.0, so the pieces leave the bits of one call over their rows in order.  An instantiation
+// of its own (k_batchmap_sums<true>'s way): the one-call kernel keeps its code, with no load of S ahead of its chain.
+template <bool CONT>
 __global__ __launch_bounds__(BM_SUM_DIMS) void k_glvq_sums(const float *__restrict__ rows, int64_t n_rows, int d, int64_t first,
                                                            int64_t n, uint32_t n_units, const uint32_t *__restrict__ list,
                                                            const uint32_t *__restrict__ starts, const double *__restrict__ xi,
@@ -256,6 +263,10 @@ __global__ __launch_bounds__(BM_SUM_DIMS) void k_glvq_sums(const float *__restri
     return rows[r * d + k];
   };
   double acc = 0.0;
+  if (CONT) {
+    if (lo == hi) return;                                     // no sample of this piece for (u, role): the chains stand
+    acc = k == d + 1 ? cost[u] : S[(static_cast<int64_t>(role) * n_units + u) * (d + 1) + k];
+  }
   uint32_t i = lo;
   for (; hi - i >= GLVQ_SUM_AHEAD; i += GLVQ_SUM_AHEAD) {
     float x[GLVQ_SUM_AHEAD];
@@ -279,6 +290,17 @@ __global__ __launch_bounds__(BM_SUM_DIMS) void k_glvq_sums(const float *__restri
   }
   if (k == d + 1) cost[u] = acc;
   else S[(static_cast<int64_t>(role) * n_units + u) * (d + 1) + k] = acc;
+}
+
+// The integers of the state of an epoch over data in pieces (somhip_glvq_accumulate), behind a piece's k_glvq_sums<true>:
+// counts[role][u] (np, nm) grow by the piece's hits[role][u], one thread per element; thread 0 also takes the piece into
+// the tail: tail[0] (samples) grows by n, tail[1] (correct) by the piece's *correct.  One writer per word, no atomics.
+__global__ __launch_bounds__(GLVQ_THREADS) void k_glvq_counts(const uint32_t *__restrict__ hits, const uint32_t *__restrict__ correct,
+                                                              uint64_t n, uint32_t n_words, uint32_t *__restrict__ counts,
+                                                              uint64_t *__restrict__ tail) {
+  const uint32_t i = blockIdx.x * GLVQ_THREADS + threadIdx.x;
+  if (i < n_words) counts[i] += hits[i];
+  if (i == 0) { tail[0] += n; tail[1] += *correct; }
 }
 
 // Step 5, in place over the storage tiles: thread = (row group, chunk of 4 dims, lane).  With W = (double)w_j[k]:

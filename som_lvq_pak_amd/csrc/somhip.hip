@@ -541,6 +541,9 @@ struct somhip_codebook {
   double *bm_state = nullptr;      // the batch map's continued accumulation (host_batchmap.inc): [S | counts][the tail], the codebook's own
   bool bm_open = false;            // ... opened by somhip_batchmap_begin; closed by _end and by every other writer of the rows
   bool bm_moved = false;           // ... a _finish has written rows from it: no further piece until the next _begin
+  double *gl_state = nullptr;      // batch GLVQ's continued accumulation (host_glvq.inc): [Sp | sp][Sm | sm][cost][np][nm][the tail], the codebook's own
+  bool gl_open = false;            // ... opened by somhip_glvq_begin; closed by _end and by every other writer of the rows
+  bool gl_moved = false;           // ... somhip_glvq_finish has written rows from it: no further piece until the next _begin
 };
 struct somhip_dataset {
   somhip_engine *e = nullptr;
@@ -577,7 +580,7 @@ static bool sample_is_empty(const somhip_dataset *ds, int64_t row) { return !ds-
 static int upload_rows(somhip_codebook *cb, const float *rows) {
   somhip_engine *e = cb->e;
   cb->prep_valid = cb->rowmajor_valid = false;
-  cb->bm_open = false;
+  cb->bm_open = cb->gl_open = false;
   float *stage;
   const size_t count = (size_t)cb->v.n * cb->v.d;
   CHK(scratch(e, SLOT_STAGE, count, &stage));
@@ -704,6 +707,8 @@ static void codebook_release(somhip_codebook *cb) {
   if (cb->d_clo) (void)hipFree(cb->d_clo);
   if (cb->bm_state) (void)hipFree(cb->bm_state);
   cb->bm_state = nullptr; cb->bm_open = false;
+  if (cb->gl_state) (void)hipFree(cb->gl_state);
+  cb->gl_state = nullptr; cb->gl_open = false;
   cb->v.tiles = nullptr;
   cb->d_labels = nullptr; cb->d_talpha = nullptr; cb->d_cn = nullptr; cb->d_cnmax = nullptr;
   cb->d_chi = cb->d_clo = nullptr;

@@ -813,6 +813,70 @@ def glvq_update(cb, alpha_t, n, sums_plus, n_plus, sums_minus, n_minus):
                                             _p(sm, _lib.c_double_p), _p(cm, _lib.c_u32_p)))
 
 
+def glvq_begin(cb):
+    """Opens, or re-zeroes, the codebook's continued accumulation of a GLVQ epoch (somhip_glvq_begin): the data may then
+    come in pieces, in order, and leave the bits of one glvq_train epoch over the pieces' rows concatenated"""
+    check(cb.e.lib.somhip_glvq_begin(cb.h))
+
+
+def glvq_accumulate(cb, ds, first=0, n=None, sigmoid_beta=0.0):
+    """One piece (somhip_glvq_accumulate): search, terms and grouping of rows (first + s) % ds.n, s < n, of ds against the
+    codebook as it stands; the per-row fp64 chains, the counts and the tail go on from the state"""
+    n = ds.n if n is None else n
+    check(cb.e.lib.somhip_glvq_accumulate(cb.h, ds.h, first, n, sigmoid_beta))
+
+
+def glvq_finish(cb, alpha_t):
+    """The update from the state with a = float64(alpha_t) / samples (somhip_glvq_finish).  Returns (cost, correct,
+    samples): what one glvq_train epoch reports, and the samples the pieces held."""
+    cost, correct, samples = C.c_double(0.0), C.c_int64(0), C.c_int64(0)
+    check(cb.e.lib.somhip_glvq_finish(cb.h, float(np.float32(alpha_t)), C.byref(cost), C.byref(correct), C.byref(samples)))
+    return cost.value, correct.value, samples.value
+
+
+def glvq_end(cb):
+    """Frees the accumulation's state (somhip_glvq_end)"""
+    check(cb.e.lib.somhip_glvq_end(cb.h))
+
+
+def glvq_state(cb):
+    """(device address, bytes) of the one blob that is the whole state (somhip_glvq_state): [Sp | sp] and [Sm | sm] as
+    float64[2, cb.n, dim + 1], cost float64[cb.n], np and nm uint32[cb.n] each, then 16 bytes {uint64 samples, uint64
+    correct}"""
+    addr, nbytes = C.c_void_p(), C.c_int64(0)
+    check(cb.e.lib.somhip_glvq_state(cb.h, C.byref(addr), C.byref(nbytes)))
+    return int(addr.value), int(nbytes.value)
+
+
+def glvq_state_arrays(cb):
+    """The state blob on the host, taken apart as glvq_sums names its parts: a dict of sums_plus, sums_minus
+    float64[cb.n, dim + 1], cost float64[cb.n], n_plus, n_minus uint32[cb.n], samples, correct"""
+    addr, nbytes = glvq_state(cb)
+    blob = cb.e.copy_to_host(addr, nbytes)
+    ld, r = cb.dim + 1, cb.n
+    s_bytes, c_bytes = 8 * 2 * r * ld, 8 * r
+    assert nbytes == s_bytes + c_bytes + 8 * r + 16
+    S = blob[:s_bytes].view(np.float64).reshape(2, r, ld)
+    counts = blob[s_bytes + c_bytes:s_bytes + c_bytes + 8 * r].view(np.uint32).reshape(2, r)
+    tail = blob[s_bytes + c_bytes + 8 * r:].view(np.uint64)
+    return {"sums_plus": S[0].copy(), "sums_minus": S[1].copy(), "cost": blob[s_bytes:s_bytes + c_bytes].view(np.float64).copy(),
+            "n_plus": counts[0].copy(), "n_minus": counts[1].copy(), "samples": int(tail[0]), "correct": int(tail[1])}
+
+
+def glvq_train_ranks(cb, block, comm, epochs, alpha, sigmoid_beta=0.0, start_epoch=0, count=None, first=0, n=None, stats=True):
+    """glvq_train over the row blocks of the ranks of `comm` (a somhip_comm handle), this rank's block being rows
+    (first + s) % block.n, s < n, of `block` (somhip_glvq_train_ranks; block None with n 0: a rank without rows).  Every
+    rank ends with the rows of glvq_train over the blocks in rank order.  Returns (cost, correct) or None."""
+    count = epochs - start_epoch if count is None else count
+    n = (block.n if block is not None else 0) if n is None else n
+    p = _lib.GlvqParams(epochs, start_epoch, count, first, n, alpha, sigmoid_beta)
+    cost = np.zeros(max(count, 0), dtype=np.float64) if stats else None
+    correct = np.zeros(max(count, 0), dtype=np.int64) if stats else None
+    check(cb.e.lib.somhip_glvq_train_ranks(cb.h, block.h if block is not None else None, C.byref(p), comm,
+                                           _p(cost, _lib.c_double_p), _p(correct, _lib.c_i64_p)))
+    return (cost, correct) if stats else None
+
+
 def _ng_params(units, epochs, lambda0, lambda_end, ranks, start_epoch=0, count=0, first=0, n=0):
     lambda0 = min(units, 256) / 2.0 if lambda0 is None else lambda0
     return _lib.NgParams(epochs, lambda0, lambda_end, ranks, start_epoch, count, first, n)

@@ -1,7 +1,9 @@
 /* glvq -- train a labelled codebook with batch GLVQ on the MI355X engine (somhip_glvq_train): Sato and Yamada's
  * Generalized LVQ as full-batch gradient steps of E = mean f(mu), mu = (d+ - d-) / (d+ + d-), the rate going linearly
  * from -alpha to 0 over -epochs epochs.  The result does not depend on the order of the data beyond the order of its
- * sums, and is the same on every run.  This project's own tool: LVQ_PAK has none. */
+ * sums, and is the same on every run.  This project's own tool: LVQ_PAK has none.
+ * -buffer N takes the data through the engine N rows at a time and -gpus G divides its rows over G ranks; both leave the
+ * file and the -v lines of the plain run, byte for byte (the sums' chains are continued, include/somhip_glvq_pieces.h). */
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -12,6 +14,10 @@ static const char *usage =
     "Required:  -cin file  -din file  -cout file  -epochs T  -alpha A\n"
     "Optional:  -sigmoid B (the cost is 1 / (1 + exp(-B mu)); without it, mu itself)\n"
     "           -v (one line per epoch to stdout: epoch, alpha, cost and accuracy before it)\n"
+    "           -buffer N (the device holds N data rows at a time; same result)\n"
+    "           -gpus G (one process per GPU, the data's rows divided over them; same result; not with -buffer;\n"
+    "                    SOMHIP_COMM=rccl|sockets in the environment names the ranks' transport and, as with bsom,\n"
+    "                    sends even one rank through it)\n"
     "-alpha has the unit of a squared distance: about the squared distance between neighbouring classes.\n"
     "Files:     text (.dat/.cod) or raw fp32 (a name ending in .f32; see datconv); every row carries a label\n";
 
@@ -24,6 +30,20 @@ static int unlabelled(struct entries *e, const char *what, const char *name)
       return 1;
     }
   return 0;
+}
+
+/* what the run ends with, on the one process or on rank 0: the -v lines, then the codebook */
+struct glvq_out { const char *cout; long epochs; float alpha; double *cost; int64_t *correct; };
+static int save_codes(struct teach_params *teach, void *arg)
+{
+  struct glvq_out *o = arg;
+  for (long t = 0; o->cost && t < o->epochs; t++) {
+    const float a = o->alpha * (float)(o->epochs - t) / (float)o->epochs;   /* the engine's alpha_t */
+    fprintf(stdout, "epoch %ld alpha %.9g cost %.17g accuracy %.2f %%\n", t, (double)a, o->cost[t],
+            100.0 * (double)o->correct[t] / (double)teach->data->num_entries);
+  }
+  ifverbose(2) fprintf(stderr, "Codebook entries are saved to file %s\n", o->cout);
+  return save_entries(teach->codes, (char *)o->cout) ? 1 : 0;
 }
 
 int main(int argc, char **argv)
@@ -46,6 +66,12 @@ int main(int argc, char **argv)
   if (epochs < 1) { fprintf(stderr, "glvq: -epochs %ld < 1\n", epochs); exit(1); }
   if (!(alpha >= 0.0f)) { fprintf(stderr, "glvq: -alpha %g is negative or not a number\n", (double)alpha); exit(1); }
   if (!(beta >= 0.0f)) { fprintf(stderr, "glvq: -sigmoid %g is negative or not a number\n", (double)beta); exit(1); }
+  char *buffer_s = extract_parameter(argc, argv, "-buffer", OPTION), *gpus_s = extract_parameter(argc, argv, "-gpus", OPTION);
+  long buffer = oatoi(buffer_s, 0);
+  int gpus = (int)oatoi(gpus_s, 1);
+  if (buffer_s && buffer < 1) { fprintf(stderr, "glvq: -buffer %ld < 1\n", buffer); exit(1); }
+  if (gpus < 1 || gpus > 64) { fprintf(stderr, "glvq: -gpus %d outside 1 .. 64\n", gpus); exit(1); }
+  if (gpus_s && buffer_s) { fprintf(stderr, "glvq: -gpus together with -buffer is not available (give one of the two)\n"); exit(1); }
 
   if (pak_open_inputs(din, 0, "cant open data file '%s'\n", cin, 0, "Can't open code file '%s'\n", 0, &io)) goto end;
   if (io.codes->masks) { fprintf(stderr, "glvq: codebook %s has masked components (x): not supported\n", cin); goto end; }
@@ -68,15 +94,12 @@ int main(int argc, char **argv)
   {
     double *cost = lines ? calloc((size_t)epochs, sizeof *cost) : NULL;
     int64_t *correct = lines ? calloc((size_t)epochs, sizeof *correct) : NULL;
-    if (!glvq_training(&params, epochs, beta, cost, correct)) {
-      for (long t = 0; lines && t < epochs; t++) {
-        const float a = alpha * (float)(epochs - t) / (float)epochs;   /* the engine's alpha_t */
-        fprintf(stdout, "epoch %ld alpha %.9g cost %.17g accuracy %.2f %%\n", t, (double)a, cost[t],
-                100.0 * (double)correct[t] / (double)io.data->num_entries);
-      }
-      ifverbose(2) fprintf(stderr, "Codebook entries are saved to file %s\n", cout);
-      error = save_entries(io.codes, cout) ? 1 : 0;
-    }
+    struct glvq_out out = {cout, epochs, alpha, cost, correct};
+    if (!buffer_s && (gpus > 1 || getenv("SOMHIP_COMM")))  /* the ranks train, as in bsom; rank 0 prints and saves */
+      error = glvq_training_multi(&params, epochs, beta, cost, correct, gpus, save_codes, &out);
+    else if (!(buffer_s ? glvq_training_buffered(&params, epochs, buffer, beta, cost, correct)
+                        : glvq_training(&params, epochs, beta, cost, correct)))
+      error = save_codes(&params, &out);
     free(cost);
     free(correct);
   }

@@ -198,6 +198,15 @@ int som_batchmap_training_multi(struct teach_params *teach, long epochs, float *
  * for the identity, on the labelled rows of teach->codes, which it replaces.  cost, correct: NULL, or [epochs] for the cost
  * and the number of correctly classified rows of the codebook every epoch started from.  0, or 1 after a message. */
 int glvq_training(struct teach_params *teach, long epochs, float sigmoid_beta, double *cost, int64_t *correct);
+/* the same run with the data going through the engine `buffer` rows at a time, every epoch (somhip_glvq_begin / _accumulate
+ * / _finish): each piece a data set of its own with its labels, uploaded and destroyed once it is taken, so the device
+ * never holds more than `buffer` data rows; the codebook, cost and correct are the plain run's, bit for bit */
+int glvq_training_buffered(struct teach_params *teach, long epochs, long buffer, float sigmoid_beta, double *cost, int64_t *correct);
+/* glvq -gpus G: the data's rows in G contiguous blocks, one per rank, every rank the whole codebook
+ * (somhip_glvq_train_ranks); rank 0 ends with the codebook in teach->codes and the epochs' cost and correct ([epochs] or
+ * NULL) and runs after(teach, arg) -- print, save */
+int glvq_training_multi(struct teach_params *teach, long epochs, float sigmoid_beta, double *cost, int64_t *correct, int gpus,
+                        int (*after)(struct teach_params *, void *), void *arg);
 /* batch GRLVQ (somhip_grlvq_train): glvq_training under the relevance-weighted metric.  lambda ([dim], in and out): the
  * relevances, taken as they are and left as the run ends; eps: their rate.  epochs 0: nothing is trained.  Then one more
  * search (somhip_grlvq_search): *final_cost and *final_correct describe teach->codes under lambda as the call leaves them. */

@@ -756,6 +756,45 @@ int glvq_training(struct teach_params *teach, long epochs, float sigmoid_beta, d
   return rc;
 }
 
+somhip_dataset *pak_mirror_labelled_rows(struct entries *data, long first, long count)
+{
+  somhip_engine *en = pak_engine();
+  if (!en) return NULL;
+  if (data->is_virtual && pak_materialize(data)) return NULL;
+  somhip_dataset *ds = NULL;
+  const long dim = data->dimension;
+  int32_t *lab = malloc(sizeof(int32_t) * (count + 1));
+  for (long r = 0; r < count; r++) lab[r] = get_entry_label(&data->rows[first + r]);
+  int rc = somhip_dataset_create(en, data->points + first * dim, count, (int)dim,
+                                 data->masks ? (const uint8_t *)data->masks + first * dim : NULL, lab, NULL, NULL, &ds);
+  free(lab);
+  return said(rc) ? NULL : ds;
+}
+
+int glvq_training_buffered(struct teach_params *teach, long epochs, long buffer, float sigmoid_beta, double *cost, int64_t *correct)
+{
+  const long n = teach->data->num_entries;
+  if (n <= 0) { fprintf(stderr, "glvq_training: can't get data\n"); return 1; }
+  if (buffer < 1) { fprintf(stderr, "glvq_training: buffer %ld < 1\n", buffer); return 1; }
+  /* the epoch over pieces: the sums' chains go on from piece to piece, so any cut gives the bits of one call */
+  somhip_codebook *cb = pak_mirror_codes(teach->codes, 1);
+  int rc = !cb;
+  for (long t = 0; !rc && t < epochs; t++) {
+    const float alpha_t = teach->alpha * (float)(epochs - t) / (float)epochs;   /* the engine's alpha_t */
+    rc = said(somhip_glvq_begin(cb));
+    for (long first = 0; !rc && first < n; first += buffer) {
+      const long c = buffer < n - first ? buffer : n - first;
+      somhip_dataset *piece = pak_mirror_labelled_rows(teach->data, first, c);
+      rc = !piece || said(somhip_glvq_accumulate(cb, piece, 0, c, sigmoid_beta));
+      if (piece) somhip_dataset_destroy(piece);
+    }
+    if (!rc) rc = said(somhip_glvq_finish(cb, alpha_t, cost ? cost + t : NULL, correct ? correct + t : NULL, NULL));
+  }
+  if (!rc) rc = said(somhip_glvq_end(cb)) || said(somhip_codebook_download(cb, teach->codes->points));
+  if (cb) somhip_codebook_destroy(cb);
+  return rc;
+}
+
 int rslvq_training(struct teach_params *teach, long epochs, float sigma2, double *cost, int64_t *correct, double *final_cost,
                    int64_t *final_correct, double *pown)
 {

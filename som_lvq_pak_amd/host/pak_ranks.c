@@ -1,5 +1,5 @@
 /* pak_ranks.c -- the multi-process side of the tools' host library: the fork/socketpair rank launcher with its kill
- * logic, and the drivers of `vsom -gpus G`, `lvqtrain -gpus G` and `bsom -gpus G` that run in every rank. */
+ * logic, and the drivers of `vsom -gpus G`, `lvqtrain -gpus G`, `bsom -gpus G` and `glvq -gpus G` that run in every rank. */
 #define _GNU_SOURCE
 #include "pak_int.h"
 
@@ -441,4 +441,64 @@ int som_batchmap_training_multi(struct teach_params *teach, long epochs, float *
   if (pak_check_inputs(teach, "som_batchmap_training", PAK_CHECK_SOM | PAK_CHECK_RANKS)) return 1;
   struct bsom_multi m = { teach, epochs, qerror, after, arg };
   return pak_run_ranks(gpus, batchmap_training_rank, &m);
+}
+
+/* ------------------------------------------------------------------ batch GLVQ on G GPUs (glvq -gpus G)
+ * The DATA is cut into contiguous row blocks, one per rank, each with its labels; every rank holds the whole labelled
+ * codebook.  somhip_glvq_train_ranks runs the epochs: the class-wise search of every block at the same time, the ordered
+ * sums rank after rank with the state broadcast in between, the same update on every rank.  Every rank ends with the
+ * same codebook, cost and count; rank 0 returns them. */
+struct glvq_multi {
+  struct teach_params *teach; long epochs; float beta; double *cost; int64_t *correct;
+  int (*after)(struct teach_params *, void *); void *arg;
+};
+
+static int glvq_training_rank(int rank, int world, int *fds, void *pp)
+{
+  struct glvq_multi *m = pp;
+  struct entries *codes = m->teach->codes, *data = m->teach->data;
+  long r0, r1;
+  rank_block(data->num_entries, world, rank, &r0, &r1);
+  int ndev = 0, rc = 1;
+  somhip_comm *comm = NULL;
+  somhip_codebook *cb = NULL;
+  somhip_dataset *ds = NULL;
+  double *cost = calloc((size_t)m->epochs + 1, sizeof *cost);
+  int64_t *correct = calloc((size_t)m->epochs + 1, sizeof *correct);
+  if (pak_rank_device(rank) < 0 || somhip_device_count(&ndev)) { free(cost); free(correct); return 1; }
+  somhip_engine *en = pak_engine();
+  if (!en) { free(cost); free(correct); return 1; }
+  int use_rccl;
+  const int no_comm = rank_comm_open(en, rank, world, ndev, fds, &comm, &use_rccl);
+  if (no_comm > 0) goto hip_fail;
+  if (no_comm) goto done;
+  ifverbose(2) fprintf(stderr, "rank %d/%d on GPU %d, data rows [%ld, %ld), state by %s\n", rank, world, pak_device, r0, r1,
+                       use_rccl ? "RCCL" : "host sockets");
+  if (!(cb = pak_mirror_codes(codes, 1))) goto done;
+  if (r1 > r0 && !(ds = pak_mirror_labelled_rows(data, r0, r1 - r0))) goto done;
+  somhip_glvq_params p = { m->epochs, 0, m->epochs, 0, r1 - r0, m->teach->alpha, m->beta };
+  if (somhip_glvq_train_ranks(cb, ds, &p, comm, cost, correct)) goto hip_fail;
+  if (rank == 0) {
+    if (somhip_codebook_download(cb, codes->points)) goto hip_fail;
+    if (m->cost) memcpy(m->cost, cost, sizeof *cost * (size_t)m->epochs);
+    if (m->correct) memcpy(m->correct, correct, sizeof *correct * (size_t)m->epochs);
+    rc = m->after ? m->after(m->teach, m->arg) : 0;
+  } else rc = 0;
+  goto done;
+hip_fail:
+  fprintf(stderr, "glvq_training (rank %d): %s\n", rank, somhip_last_error());
+done:
+  if (ds) somhip_dataset_destroy(ds);
+  if (cb) somhip_codebook_destroy(cb);
+  if (comm) somhip_comm_destroy(comm);
+  free(cost); free(correct);
+  return rc;
+}
+
+int glvq_training_multi(struct teach_params *teach, long epochs, float sigmoid_beta, double *cost, int64_t *correct, int gpus,
+                        int (*after)(struct teach_params *, void *), void *arg)
+{
+  if (pak_check_inputs(teach, "glvq_training", PAK_CHECK_RANKS)) return 1;
+  struct glvq_multi m = { teach, epochs, sigmoid_beta, cost, correct, after, arg };
+  return pak_run_ranks(gpus, glvq_training_rank, &m);
 }
