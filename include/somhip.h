@@ -1072,4 +1072,6 @@ int  somhip_timing_get(somhip_engine *e, int kernel, int64_t *launches, double *
 /* batch GLVQ (K9) over data in pieces and over the row blocks of ranks: somhip_glvq_begin / _accumulate / _finish / _end /
  * _state and somhip_glvq_train_ranks, likewise */
 #include "somhip_glvq_pieces.h"
+/* dense batch neural gas (K10d): somhip_ng_train_dense, neural gas over every rank of up to SOMHIP_NG_DENSE_MAX rows, likewise */
+#include "somhip_ng_dense.h"
 #endif /* SOMHIP_H */

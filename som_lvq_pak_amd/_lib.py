@@ -268,6 +268,16 @@ GLVQ_PIECES_SIGNATURES = {
     "somhip_glvq_train_ranks": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(GlvqParams), C.c_void_p, c_double_p, c_i64_p]),
 }
 
+# ... and exactly the symbols include/somhip_ng_dense.h declares (dense batch neural gas, K10d)
+NG_DENSE_SIGNATURES = {
+    "somhip_ng_train_dense": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(NgParams), c_float_p]),
+    "somhip_debug_ng_dense_schedule": (C.c_int, [C.POINTER(NgParams), C.c_int64, C.c_int64, c_double_p, c_double_p]),
+    "somhip_debug_ng_dense_ranks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, c_i32_p, c_float_p]),
+    "somhip_debug_ng_dense_sums": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_int64, c_double_p,
+                                             c_double_p]),
+    "somhip_ng_dense_timing": (C.c_int, [C.c_void_p, c_i64_p, c_double_p]),
+}
+
 _lib = None
 
 
@@ -279,7 +289,8 @@ def load():
             raise RuntimeError("%s not built -- run `make lib` (python -c 'import __graft_entry__ as g; "
                                "g.build()'); there is no CPU fallback" % LIB_PATH)
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(RSLVQ_SIGNATURES.items()) + list(GLVQ_PIECES_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(RSLVQ_SIGNATURES.items()) + list(GLVQ_PIECES_SIGNATURES.items()) + \
+                list(NG_DENSE_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

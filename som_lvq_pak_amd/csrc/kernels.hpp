@@ -49,3 +49,4 @@
 #include "kernels/planes.hpp"
 #include "kernels/gmlvq.hpp"
 #include "kernels/rslvq.hpp"
+#include "kernels/ngas_dense.hpp"

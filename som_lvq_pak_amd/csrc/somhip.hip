@@ -90,7 +90,7 @@ static const char *kKernelNames[KID_COUNT] = {
 // from it by bit.  Kernels added since are timed by LaunchTimer all the same, under ids that follow the table; an entry
 // point of their own reports them (somhip_mapset_timing, somhip_knn_timing, somhip_knn_vote_timing, somhip_map_quality_timing,
 // somhip_batchmap_timing, somhip_conn_timing, somhip_distortion_timing, somhip_glvq_timing, somhip_ng_timing,
-// somhip_grlvq_timing, somhip_gmlvq_timing, somhip_rslvq_timing).  somhip_timing_select's mask has one bit per id up to
+// somhip_grlvq_timing, somhip_gmlvq_timing, somhip_rslvq_timing, somhip_ng_dense_timing).  somhip_timing_select's mask has one bit per id up to
 // 63; the ids from 64 on are outside it and are timed whenever timing is on.
 enum TimedOnlyId { KID_MAPSET_TRAIN = KID_COUNT, KID_MAPSET_WINNERS, KID_KNN_DIST, KID_KNN_SELECT, KID_KNN_VOTE, KID_QUALITY_PAIRS,
                    KID_QUALITY_UNITS, KID_BATCHMAP_GROUP, KID_BATCHMAP_SUMS, KID_BATCHMAP_COMBINE, KID_CONN_KEYS, KID_CONN_SORT,
@@ -98,7 +98,8 @@ enum TimedOnlyId { KID_MAPSET_TRAIN = KID_COUNT, KID_MAPSET_WINNERS, KID_KNN_DIS
                    KID_GLVQ_TERMS, KID_GLVQ_SUMS, KID_GLVQ_UPDATE, KID_NG_GROUP, KID_NG_SUMS, KID_NG_UPDATE,
                    KID_GRLVQ_SEARCH, KID_GRLVQ_SUMS, KID_GRLVQ_RELEVANCE, KID_GRLVQ_UPDATE,
                    KID_GMLVQ_PROJECT, KID_GMLVQ_GRAD, KID_GMLVQ_UPDATE,
-                   KID_RSLVQ_DIST, KID_RSLVQ_POSTERIOR, KID_RSLVQ_SUMS, KID_RSLVQ_UPDATE, KID_TIMED };
+                   KID_RSLVQ_DIST, KID_RSLVQ_POSTERIOR, KID_RSLVQ_SUMS, KID_RSLVQ_UPDATE,
+                   KID_NG_DENSE_DIST, KID_NG_DENSE_WEIGHTS, KID_NG_DENSE_SUMS, KID_TIMED };
 static_assert(KID_RSLVQ_DIST == 64, "the ids somhip_timing_select's mask can name end with K12's");
 extern "C" int somhip_kernel_count(void) { return KID_COUNT; }
 extern "C" const char *somhip_kernel_name(int i) { return (i >= 0 && i < KID_COUNT) ? kKernelNames[i] : ""; }
@@ -176,6 +177,9 @@ enum ScratchSlot {
   SLOT_RSLVQ,              // batch RSLVQ (host_rslvq.inc): [G | c] per row, and per sample cost, P(y | x) and the correct flag
   SLOT_RSLVQ_Q,            // ... the posterior coefficients of a chunk of samples (SLOT_KNN_DIST the chunk's distances, SLOT_SAMPLES
                            // its sample tiles)
+  SLOT_NGAS_DENSE,         // dense batch neural gas (host_ngas_dense.inc) beside SLOT_NGAS's [S | W]: the epoch's weight table, one
+                           // double per row, and the run's rank-0 distances (SLOT_RSLVQ_Q the chunk's weights Q, SLOT_KNN_DIST its
+                           // distances, SLOT_SAMPLES its sample tiles; the ranks stage: SLOT_CALL_A ranks, SLOT_CALL_B distances by unit)
   SLOT_COUNT
 };
 
@@ -863,3 +867,4 @@ extern "C" void somhip_dataset_destroy(somhip_dataset *ds) try {
 #include "host_distortion.inc"
 #include "host_gmlvq.inc"
 #include "host_rslvq.inc"
+#include "host_ngas_dense.inc"

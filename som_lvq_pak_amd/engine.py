@@ -173,6 +173,15 @@ class Engine:
         check(self.lib.somhip_ng_timing(self.h, n, ms))
         return {"group": (n[0], ms[0]), "k_ng_sums": (n[1], ms[1]), "k_ng_update": (n[2], ms[2])}
 
+    def ng_dense_timing(self):
+        """(launches, ms) of dense batch neural gas's stages while timing is on (somhip_ng_dense_timing; they are not in
+        timing_table and not under timing_select): distances = the sample tiles and k_knn_dist, one span per chunk; sums =
+        k_rslvq_sums.  The update counts under ng_timing's k_ng_update."""
+        n = (C.c_int64 * 3)()
+        ms = (C.c_double * 3)()
+        check(self.lib.somhip_ng_dense_timing(self.h, n, ms))
+        return {"distances": (n[0], ms[0]), "k_ng_dense_weights": (n[1], ms[1]), "sums": (n[2], ms[2])}
+
     def grlvq_timing(self):
         """(launches, ms) of batch GRLVQ's stages while timing is on (somhip_grlvq_timing; they are not in timing_table):
         search = the weighted class-wise scan per chunk; terms = batch GLVQ's stage, counted under its id (glvq_timing
@@ -940,6 +949,57 @@ def ng_update(cb, hits, sums, wsum):
     wsum = np.ascontiguousarray(wsum, dtype=np.float64)
     assert hits.shape == wsum.shape == (cb.n,) and sums.shape == (cb.n, cb.dim)
     check(cb.e.lib.somhip_debug_ng_update(cb.h, _p(hits, _lib.c_u32_p), _p(sums, _lib.c_double_p), _p(wsum, _lib.c_double_p)))
+
+
+NG_DENSE_MAX = 4096      # SOMHIP_NG_DENSE_MAX: the most rows of a codebook the dense form takes
+
+
+def ng_dense_schedule(units, epochs, t, lambda0=None, lambda_end=0.01, lib=None):
+    """Epoch t of a dense neural-gas run of `epochs` epochs on `units` rows (somhip_debug_ng_dense_schedule): (lambda_t
+    float, w float64[units]) exactly as the engine forms them: ng_schedule's lambda_t and exp(-r / lambda_t) for every
+    rank, +0.0 where it underflows.  Host arithmetic: no GPU needed."""
+    lib = lib or _lib.load()
+    p = _ng_params(units, epochs, lambda0, lambda_end, 0)
+    lam = C.c_double(0)
+    w = np.zeros(units, dtype=np.float64)
+    check(lib.somhip_debug_ng_dense_schedule(C.byref(p), units, t, C.byref(lam), _p(w, _lib.c_double_p)))
+    return lam.value, w
+
+
+def ng_train_dense(cb, ds, epochs, lambda0=None, lambda_end=0.01, ranks=0, start_epoch=0, count=None, first=0, n=None, qerror=True):
+    """Epochs [start_epoch, start_epoch + count) of dense batch neural gas over data rows (first + s) % ds.n, s < n
+    (somhip_ng_train_dense): every epoch replaces each row by the mean of the data weighted by exp(-rank / lambda_t), the
+    rank taken among ALL rows (at most NG_DENSE_MAX of them) -- ng_train without its truncation at 256 ranks, the sums
+    formed on the fp64 MFMA.  ranks must be 0.  Returns float32[count], per epoch the quantization error (find_qerror's
+    float sum) of the codebook the epoch started from, or None with qerror=False."""
+    count = epochs - start_epoch if count is None else count
+    n = ds.n if n is None else n
+    p = _ng_params(cb.n, epochs, lambda0, lambda_end, ranks, start_epoch, count, first, n)
+    q = np.zeros(max(count, 0), dtype=np.float32) if qerror else None
+    check(cb.e.lib.somhip_ng_train_dense(cb.h, ds.h, C.byref(p), _p(q, _lib.c_float_p)))
+    return q
+
+
+def ng_dense_ranks(cb, ds, first=0, n=None):
+    """The full ranking alone (somhip_debug_ng_dense_ranks): (rank int32[n, cb.n], dist float32[n, cb.n]) -- per sample
+    and unit the number of units before it in the order (distance ascending, the later row first among equal distances),
+    and its squared distance"""
+    n = ds.n if n is None else n
+    rank = np.zeros((max(n, 0), cb.n), dtype=np.int32)
+    dist = np.zeros((max(n, 0), cb.n), dtype=np.float32)
+    check(cb.e.lib.somhip_debug_ng_dense_ranks(cb.h, ds.h, first, n, _p(rank, _lib.c_i32_p), _p(dist, _lib.c_float_p)))
+    return rank, dist
+
+
+def ng_dense_sums(cb, ds, lam, first=0, n=None, chunk=0):
+    """Distances, ranking and sums of a dense neural-gas epoch at lambda = lam (somhip_debug_ng_dense_sums): (sums
+    float64[cb.n, dim], wsum float64[cb.n]) = Q^T [X | 1] with Q[s][j] = exp(-rank[s][j] / lam).  chunk: samples per cut, a
+    multiple of 64 (0: the engine's own); same bits for all.  ng_update takes the pair (its hits are not read)."""
+    n = ds.n if n is None else n
+    sums = np.zeros((cb.n, cb.dim), dtype=np.float64)
+    wsum = np.zeros(cb.n, dtype=np.float64)
+    check(cb.e.lib.somhip_debug_ng_dense_sums(cb.h, ds.h, first, n, lam, chunk, _p(sums, _lib.c_double_p), _p(wsum, _lib.c_double_p)))
+    return sums, wsum
 
 
 def _grlvq_lambda(cb, lam):

@@ -231,6 +231,9 @@ int rslvq_training(struct teach_params *teach, long epochs, float sigma2, double
  * of the codebook the epoch started from.  0, or 1 after a message. */
 struct ng_line { double lambda; int ranks; float qerror; };
 int ng_training(struct teach_params *teach, long epochs, double lambda0, double lambda_end, long ranks, struct ng_line *line);
+/* ... over every rank (somhip_ng_train_dense): the same run with no truncation, on a codebook of at most SOMHIP_NG_DENSE_MAX
+ * rows; a line's ranks is the number of rows */
+int ng_training_dense(struct teach_params *teach, long epochs, double lambda0, double lambda_end, struct ng_line *line);
 /* winners of every data row (the scan behind compute_accuracy / find_labels) */
 int find_all_winners(struct teach_params *teach, int32_t *index, float *diff, int32_t *ret);
 /* the k nearest codes of every data row (knntest): k <= 8 */

@@ -897,6 +897,27 @@ int ng_training(struct teach_params *teach, long epochs, double lambda0, double 
   return rc;
 }
 
+int ng_training_dense(struct teach_params *teach, long epochs, double lambda0, double lambda_end, struct ng_line *line)
+{
+  const long n = teach->data->num_entries, units = teach->codes->num_entries;
+  if (n <= 0) { fprintf(stderr, "ng_training_dense: can't get data\n"); return 1; }
+  somhip_ng_params p = {epochs, lambda0, lambda_end, 0, 0, epochs, 0, n};
+  float *qerror = line ? calloc((size_t)epochs, sizeof *qerror) : NULL;
+  double *w = line ? malloc(sizeof *w * (size_t)(units > 0 ? units : 1)) : NULL;
+  struct mirrors m = {NULL, NULL};
+  int rc = mirrors_open(&m, teach->codes, 0, teach->data, 0);
+  if (!rc) rc = said(somhip_ng_train_dense(m.cb, m.ds, &p, qerror)) || said(somhip_codebook_download(m.cb, teach->codes->points));
+  for (long t = 0; !rc && line && t < epochs; t++) {
+    rc = said(somhip_debug_ng_dense_schedule(&p, units, t, &line[t].lambda, w));
+    line[t].ranks = (int)units;
+    line[t].qerror = qerror[t];
+  }
+  mirrors_close(&m);
+  free(w);
+  free(qerror);
+  return rc;
+}
+
 float find_qerror2(struct teach_params *teach)                /* som_rout.c:823-885 */
 {
   if (set_som_params(teach)) { fprintf(stderr, "find_qerror2: can't set SOM parameters\n"); return -1; }
