@@ -2,7 +2,7 @@
 // ordered fp64 sums (stage 1) and the neighbourhood combine on the fp64 MFMA (stage 2); the same epoch over data in pieces
 // (somhip_batchmap_begin / _accumulate / _finish: the sums' chains continued from piece to piece) and over the row blocks
 // of G ranks (somhip_som_batchmap_ranks)
-// (included by somhip.hip: one translation unit, shared static helpers)
+// (included by somhip.hip behind host_proto.inc: one translation unit, the trainers' shared checks)
 #include <rocprim/device/device_radix_sort.hpp>
 
 // The device arrays of a batch-map call.  SLOT_BATCHMAP, per unit: [S: units x (dim + 1) doubles][the gaussian table]
@@ -112,8 +112,7 @@ static int batchmap_combine_stage(somhip_codebook *cb, float r, const BatchmapBu
   if (groups < 0) groups = cb->v.ngroups;
   if (groups == 0) return 0;
   const dim3 grid((unsigned)groups, (unsigned)((cb->v.d + BM_COLS - 1) / BM_COLS));
-  cb->prep_valid = cb->rowmajor_valid = false;
-  cb->gl_open = false;                                                  // (the rows move: an open GLVQ accumulation is over)
+  rows_written(cb);                                                     // (the caller whose own state this is re-opens it)
   if (gauss) {
     const size_t t_len = batchmap_table_len(cb);
     CHK(LAUNCH_TIMED(e, KID_BATCHMAP_COMBINE, k_batchmap_gauss_table, dim3((unsigned)((t_len + BM_THREADS - 1) / BM_THREADS)), dim3(BM_THREADS), 0,
@@ -145,19 +144,16 @@ extern "C" int somhip_som_batchmap(somhip_codebook *cb, somhip_dataset *ds, cons
   if (!p) return fail("somhip_som_batchmap: null parameters");
   CHK(batchmap_check_codebook(cb, "somhip_som_batchmap"));
   CHK(batchmap_check_data(ds, p->first, p->n, "somhip_som_batchmap"));
-  if (p->epochs < 1) return fail("somhip_som_batchmap: epochs %lld < 1", (long long)p->epochs);
+  CHK(check_epochs(p->epochs, "somhip_som_batchmap"));
   if (!(p->radius >= 1.0f)) return fail("somhip_som_batchmap: radius %g < 1", (double)p->radius);
-  if (p->start_epoch < 0 || p->count < 0 || p->start_epoch + p->count > p->epochs)
-    return fail("somhip_som_batchmap: epochs [%lld, %lld) outside [0, %lld)", (long long)p->start_epoch, (long long)(p->start_epoch + p->count),
-                (long long)p->epochs);
+  CHK(check_epoch_window(p->start_epoch, p->count, p->epochs, "somhip_som_batchmap"));
   somhip_engine *e = cb->e;
   HIPCHK(hipSetDevice(e->device));
-  cb->bm_open = cb->gl_open = false;                                                  // (the rows move: an open accumulation is over)
+  close_accumulations(cb);                                              // (the rows move: an open accumulation is over)
   BatchmapBufs b;
   CHK(batchmap_bind(cb, p->n, &b));
-  const float T = (float)p->epochs;
   for (int64_t t = p->start_epoch; t < p->start_epoch + p->count; t++) {
-    const float r = 1.0f + (p->radius - 1.0f) * (float)(p->epochs - t) / T;   // som_rout.c:615 over epochs
+    const float r = 1.0f + linear_rate(p->radius - 1.0f, p->epochs, t);       // som_rout.c:615 over epochs
     CHK(batchmap_sums_stage(cb, ds, p->first, p->n, b, qerror_out ? qerror_out + (t - p->start_epoch) : nullptr));
     CHK(batchmap_combine_stage(cb, r, b));
   }
@@ -179,7 +175,7 @@ extern "C" int somhip_debug_batchmap_sums(somhip_codebook *cb, somhip_dataset *d
   std::vector<double> hs(units * (d + 1));
   CHK(to_host(e, hits, b.hits, units));
   CHK(to_host_sync(e, hs.data(), b.S, hs.size()));
-  for (size_t u = 0; u < units; u++) memcpy(sums + u * d, hs.data() + u * (d + 1), sizeof(double) * d);
+  split_trailing(hs.data(), units, d, sums, nullptr);
   return 0;
 } ABI_CATCH(somhip_debug_batchmap_sums)
 
@@ -189,7 +185,7 @@ extern "C" int somhip_debug_batchmap_combine(somhip_codebook *cb, float r, const
   if (!(r >= 0.0f)) return fail("somhip_debug_batchmap_combine: radius %g < 0", (double)r);
   somhip_engine *e = cb->e;
   HIPCHK(hipSetDevice(e->device));
-  cb->bm_open = cb->gl_open = false;
+  close_accumulations(cb);
   BatchmapBufs b;
   CHK(batchmap_bind(cb, 0, &b));
   const size_t units = (size_t)cb->v.n, d = (size_t)cb->v.d;
@@ -208,12 +204,8 @@ extern "C" int somhip_debug_batchmap_combine(somhip_codebook *cb, float r, const
 // behind the published table): [0] group (winners pass, scan, sort), [1] k_batchmap_sums, [2] the combine (with the
 // gaussian table)
 extern "C" int somhip_batchmap_timing(somhip_engine *e, int64_t launches[3], double total_ms[3]) try {
-  CHK(check_engine(e, "somhip_batchmap_timing"));
-  if (!launches || !total_ms) return fail("somhip_batchmap_timing: null output");
-  CHK(timing_flush(e));
   const int kid[3] = {KID_BATCHMAP_GROUP, KID_BATCHMAP_SUMS, KID_BATCHMAP_COMBINE};
-  for (int i = 0; i < 3; i++) { launches[i] = e->launches[kid[i]]; total_ms[i] = e->total_ms[kid[i]]; }
-  return 0;
+  return stage_timing(e, "somhip_batchmap_timing", kid, 3, launches, total_ms);
 } ABI_CATCH(somhip_batchmap_timing)
 
 // ---------------------------------------------------------------------------------
@@ -301,7 +293,9 @@ extern "C" int somhip_batchmap_finish(somhip_codebook *cb, float r, int64_t grou
   BatchmapBufs b;
   CHK(batchmap_bind(cb, 0, &b, cb->bm_state));
   if (group_count > 0) cb->bm_moved = true;                             // (an empty range writes no row)
-  CHK(batchmap_combine_stage(cb, r, b, group_first, group_count));
+  const int rc = batchmap_combine_stage(cb, r, b, group_first, group_count);
+  cb->bm_open = true;                                                   // (the combine closes every accumulation; this one stays,
+  CHK(rc);                                                              //  also where a launch of the combine failed)
   BatchmapTail tail{};
   if (qerror_out) CHK(to_host(e, &tail, batchmap_tail(cb), 1));
   HIPCHK(hipStreamSynchronize(e->stream));
@@ -341,10 +335,9 @@ extern "C" int somhip_som_batchmap_ranks(somhip_codebook *cb, somhip_dataset *bl
   CHK(batchmap_check_codebook(cb, who));
   if (!empty) CHK(batchmap_check_data(block, p->first, p->n, who));
   if (c->e != cb->e) return fail("%s: codebook and communicator belong to different engines", who);
-  if (p->epochs < 1) return fail("%s: epochs %lld < 1", who, (long long)p->epochs);
+  CHK(check_epochs(p->epochs, who));
   if (!(p->radius >= 1.0f)) return fail("%s: radius %g < 1", who, (double)p->radius);
-  if (p->start_epoch < 0 || p->count < 0 || p->start_epoch + p->count > p->epochs)
-    return fail("%s: epochs [%lld, %lld) outside [0, %lld)", who, (long long)p->start_epoch, (long long)(p->start_epoch + p->count), (long long)p->epochs);
+  CHK(check_epoch_window(p->start_epoch, p->count, p->epochs, who));
   somhip_engine *e = cb->e;
   HIPCHK(hipSetDevice(e->device));
   const int64_t ngroups = cb->v.ngroups, share = (ngroups + c->world - 1) / c->world;
@@ -371,9 +364,8 @@ extern "C" int somhip_som_batchmap_ranks(somhip_codebook *cb, somhip_dataset *bl
   auto epochs = [&]() -> int {
     BatchmapBufs b;
     std::vector<float> dist;
-    const float T = (float)p->epochs;
     for (int64_t t = p->start_epoch; t < p->start_epoch + p->count; t++) {
-      const float r = 1.0f + (p->radius - 1.0f) * (float)(p->epochs - t) / T;
+      const float r = 1.0f + linear_rate(p->radius - 1.0f, p->epochs, t);
       float *q = qerror_out ? qerror_out + (t - p->start_epoch) : nullptr;
       CHK(batchmap_state_open(cb));
       b = BatchmapBufs();
@@ -392,7 +384,7 @@ extern "C" int somhip_som_batchmap_ranks(somhip_codebook *cb, somhip_dataset *bl
       if (gn > 0) CHK(on_device(e, st.send, cb->v.tiles + group_floats * (size_t)g0, group_floats * (size_t)gn));
       CHK(somhip_comm_allgather(c, st.send, st.recv, (int64_t)(sizeof(float) * group_floats * (size_t)share)));
       CHK(on_device(e, cb->v.tiles, st.recv, group_floats * (size_t)ngroups));   // (shares are consecutive: the gathered ranges are the tiles)
-      cb->prep_valid = cb->rowmajor_valid = false;
+      rows_written(cb);
       if (q) {
         BatchmapTail tail;
         CHK(to_host_sync(e, &tail, batchmap_tail(cb), 1));

@@ -222,10 +222,6 @@ static int conn_take_chunk(somhip_conn *c, const somhip_codebook *cb, const somh
 // the published table): [0] k_conn_keys, [1] the sort, [2] the runs (heads, scan, k_conn_runs), [3] the merge (rank, scan,
 // k_conn_merge)
 extern "C" int somhip_conn_timing(somhip_engine *e, int64_t launches[4], double total_ms[4]) try {
-  CHK(check_engine(e, "somhip_conn_timing"));
-  if (!launches || !total_ms) return fail("somhip_conn_timing: null output");
-  CHK(timing_flush(e));
   const int kid[4] = {KID_CONN_KEYS, KID_CONN_SORT, KID_CONN_RUNS, KID_CONN_MERGE};
-  for (int i = 0; i < 4; i++) { launches[i] = e->launches[kid[i]]; total_ms[i] = e->total_ms[kid[i]]; }
-  return 0;
+  return stage_timing(e, "somhip_conn_timing", kid, 4, launches, total_ms);
 } ABI_CATCH(somhip_conn_timing)

@@ -217,10 +217,6 @@ extern "C" int somhip_debug_distortion_evaluate(somhip_codebook *cb, float r, co
 // behind the published table): [0] group (winners pass, scan, sort), [1] the sums and the two Q passes, [2] evaluate (the
 // gaussian table, the kernel, the two fold passes)
 extern "C" int somhip_distortion_timing(somhip_engine *e, int64_t launches[3], double total_ms[3]) try {
-  CHK(check_engine(e, "somhip_distortion_timing"));
-  if (!launches || !total_ms) return fail("somhip_distortion_timing: null output");
-  CHK(timing_flush(e));
   const int kid[3] = {KID_DISTORTION_GROUP, KID_DISTORTION_SUMS, KID_DISTORTION_EVALUATE};
-  for (int i = 0; i < 3; i++) { launches[i] = e->launches[kid[i]]; total_ms[i] = e->total_ms[kid[i]]; }
-  return 0;
+  return stage_timing(e, "somhip_distortion_timing", kid, 3, launches, total_ms);
 } ABI_CATCH(somhip_distortion_timing)

@@ -3,7 +3,8 @@
 // the update; the four stages on their own for the tests; the same epoch over data in pieces (somhip_glvq_begin /
 // _accumulate / _finish: the sums' chains continued from piece to piece) and over the row blocks of G ranks
 // (somhip_glvq_train_ranks)
-// (included by somhip.hip behind host_batchmap.inc: one translation unit, shared static helpers, rocPRIM's sort)
+// (included by somhip.hip behind host_proto.inc and host_batchmap.inc: one translation unit, the trainers' shared checks,
+// GlvqBufs, class_scan_walk and copies from host_proto.inc, rocPRIM's sort)
 
 // The route of the search, for every caller: a function of the shape alone.  The list route costs one exact top-8 search
 // more than the class-wise scan of its remainder, and the remainder is every sample wherever the eight nearest rows of a
@@ -15,23 +16,11 @@
 constexpr int64_t GLVQ_LIST_MIN_ROWS = 32768;
 constexpr int GLVQ_LIST_MIN_DIM = 512;
 constexpr int GLVQ_LIST_WIDTH = 8;              // the entries of a sample's list: the widest exact top-K search
-constexpr int64_t GLVQ_CHUNK = 16384;           // samples of a class-wise scan launch: whole tiles (dim 1024: 64 MiB of sample tiles)
 static int glvq_plan(int64_t rows, int dim, int64_t n) {
   return rows >= GLVQ_LIST_MIN_ROWS && dim >= GLVQ_LIST_MIN_DIM && n >= MFMA_MIN_SAMPLES ? SOMHIP_GLVQ_LIST : SOMHIP_GLVQ_DIRECT;
 }
 
-// The device arrays of a GLVQ call.  SLOT_GLVQ, per row: [S: 2 x rows x (dim + 1) doubles][cost][hits: 2 x rows]
-// [starts: 2 x (rows + 1)][correct, the remainder's length].  SLOT_GLVQ_LIST, per sample: [keys2][xi: 2 x n][f][win: 2 x n]
-// [idx][the sorted winners][list: 2 x n][the remainder][the sort's own room].  Role + comes first in every pair.
-struct GlvqBufs {
-  double *S = nullptr, *cost = nullptr, *xi = nullptr, *f = nullptr;
-  uint64_t *keys2 = nullptr;
-  uint32_t *hits = nullptr, *starts = nullptr, *correct = nullptr, *rem_count = nullptr;
-  uint32_t *win = nullptr, *idx = nullptr, *win_sorted = nullptr, *list = nullptr, *rem = nullptr;
-  void *sort_tmp = nullptr;
-  size_t sort_bytes = 0;
-  unsigned sort_bits = 0;
-};
+// The device arrays of a GLVQ call: GlvqBufs (host_proto.inc), bound here.
 // n: the samples of the call, 0 where only the update runs.  state (or null): S and cost are the codebook's own continued
 // accumulation, not engine scratch, and the slot holds the rest only (hits is then the piece's own counts).
 static int glvq_bind(somhip_codebook *cb, int64_t n, GlvqBufs *b, double *state = nullptr) {
@@ -63,36 +52,6 @@ static int glvq_bind(somhip_codebook *cb, int64_t n, GlvqBufs *b, double *state 
   return 0;
 }
 
-// The class-wise scan over `count` samples of the run into b.keys2 (which holds KEY_NONE for them): the run's samples
-// base .. base + count - 1, or the listed ones sel[0 .. count).  Chunks of whole sample tiles; the sample labels are on the
-// device.  timed: its launches count under the search's id (the list route times one span around everything instead).
-static int glvq_scan_class(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t base, int64_t count, const uint32_t *sel,
-                           const GlvqBufs &b, bool timed) {
-  somhip_engine *e = cb->e;
-  const int64_t f0 = first % ds->n;
-  const bool wide = cb->v.ngroups >= 4 * GLVQ_R;
-  const dim3 block(256);
-  for (int64_t off = 0; off < count; off += GLVQ_CHUNK) {
-    const int64_t c = std::min(GLVQ_CHUNK, count - off), nsb = (c + GLVQ_S - 1) / GLVQ_S;
-    float4 *xt;
-    CHK(scratch(e, SLOT_SAMPLES, (size_t)nsb * cb->v.d4 * GLVQ_S, &xt));
-    if (sel)
-      CHK(LAUNCH(e, k_glvq_pack_listed<GLVQ_S>, dim3((unsigned)nsb), block, 0, ds->d_rows, ds->n, ds->d, cb->v.d4, f0, sel + off, c, xt));
-    else
-      CHK(LAUNCH_TIMED(e, KID_PACK_SAMPLES, k_pack_samples<GLVQ_S>, dim3((unsigned)nsb), block, 0, ds->d_rows, ds->n, ds->d, cb->v.d4,
-          (f0 + base + off) % ds->n, c, xt));
-    const dim3 grid((unsigned)nsb, (unsigned)((cb->v.ngroups + (wide ? 4 * GLVQ_R : 4) - 1) / (wide ? 4 * GLVQ_R : 4)));
-    const uint32_t *sl = sel ? sel + off : nullptr;
-    LaunchTimer t(e, timed ? KID_GLVQ_SEARCH : -1);
-    if (wide)
-      CHK(LAUNCH(e, (k_scan_class<GLVQ_S, GLVQ_R>), grid, block, 0, cb->v, xt, c, cb->d_labels, ds->d_labels, ds->n, f0, base + off, sl, b.keys2));
-    else
-      CHK(LAUNCH(e, (k_scan_class<GLVQ_S, 1>), grid, block, 0, cb->v, xt, c, cb->d_labels, ds->d_labels, ds->n, f0, base + off, sl, b.keys2));
-  }
-  e->samples_searched += (uint64_t)count;
-  return 0;
-}
-
 // Step 2: b.keys2 <- the two keys of every sample of the run, by the route given.  remainder (or null): the samples the
 // class-wise scan took.
 static int glvq_search_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, int route, const GlvqBufs &b,
@@ -101,7 +60,7 @@ static int glvq_search_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t fi
   if (route == SOMHIP_GLVQ_DIRECT) {
     HIPCHK(hipMemsetAsync(b.keys2, 0xFF, sizeof(uint64_t) * 2 * (size_t)n, e->stream));
     if (remainder) *remainder = n;
-    return glvq_scan_class(cb, ds, first, 0, n, nullptr, b, true);
+    return class_scan_walk(e, cb->v, cb->d_labels, ds, first, n, /*projected*/ nullptr, /*sel*/ nullptr, /*lam*/ nullptr, KID_GLVQ_SEARCH, b.keys2);
   }
   LaunchTimer span(e, KID_GLVQ_SEARCH);
   HIPCHK(hipMemsetAsync(b.rem_count, 0, sizeof(uint32_t), e->stream));
@@ -113,7 +72,7 @@ static int glvq_search_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t fi
   uint32_t nrem = 0;
   CHK(to_host_sync(e, &nrem, b.rem_count, 1));      // (the remainder's launches are sized by it)
   if (remainder) *remainder = nrem;
-  if (nrem) CHK(glvq_scan_class(cb, ds, first, 0, nrem, b.rem, b, false));
+  if (nrem) CHK(class_scan_walk(e, cb->v, cb->d_labels, ds, first, nrem, /*projected*/ nullptr, /*sel*/ b.rem, /*lam*/ nullptr, /*kid*/ -1, b.keys2));
   return 0;
 }
 
@@ -149,8 +108,7 @@ static int glvq_sums_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t firs
 // Step 5: the rows from b.S and b.hits
 static int glvq_update_stage(somhip_codebook *cb, float alpha_t, int64_t n, const GlvqBufs &b) {
   const int64_t threads = cb->v.ngroups * cb->v.d4 * WAVE;
-  cb->prep_valid = cb->rowmajor_valid = false;
-  cb->bm_open = cb->gl_open = false;
+  rows_written(cb);
   return LAUNCH_TIMED(cb->e, KID_GLVQ_UPDATE, k_glvq_update, dim3((unsigned)((threads + GLVQ_THREADS - 1) / GLVQ_THREADS)), dim3(GLVQ_THREADS), 0, cb->v,
                       b.S, b.hits, (double)alpha_t / (double)n);
 }
@@ -198,20 +156,18 @@ extern "C" int somhip_glvq_train(somhip_codebook *cb, somhip_dataset *ds, const 
   const char *who = "somhip_glvq_train";
   if (!p) return fail("%s: null parameters", who);
   if (!cb || !ds) return fail("%s: null handle", who);
-  if (p->epochs < 1) return fail("%s: epochs %lld < 1", who, (long long)p->epochs);
-  if (p->start_epoch < 0 || p->count < 0 || p->start_epoch + p->count > p->epochs)
-    return fail("%s: epochs [%lld, %lld) outside [0, %lld)", who, (long long)p->start_epoch, (long long)(p->start_epoch + p->count), (long long)p->epochs);
-  if (!(p->alpha >= 0.0f)) return fail("%s: alpha %g is negative or not a number", who, (double)p->alpha);
+  CHK(check_epochs(p->epochs, who));
+  CHK(check_epoch_window(p->start_epoch, p->count, p->epochs, who));
+  CHK(check_alpha(p->alpha, who));
   CHK(glvq_check_beta(p->sigmoid_beta, who));
   CHK(glvq_check(cb, ds, p->first, p->n, who));
   somhip_engine *e = cb->e;
   GlvqBufs b;
   CHK(glvq_bind(cb, p->n, &b));
   const int route = glvq_plan(cb->v.n, cb->v.d, p->n);
-  const float T = (float)p->epochs;
   std::vector<double> hc((size_t)(cost_out ? cb->v.n : 0));
   for (int64_t t = p->start_epoch; t < p->start_epoch + p->count; t++) {
-    const float alpha_t = p->alpha * (float)(p->epochs - t) / T;        // LVQ_PAK's linear rate over epochs
+    const float alpha_t = linear_rate(p->alpha, p->epochs, t);
     CHK(glvq_search_stage(cb, ds, p->first, p->n, route, b, nullptr));
     CHK(glvq_terms_stage(cb, p->n, p->sigmoid_beta, b));
     CHK(glvq_sums_stage(cb, ds, p->first, p->n, b));
@@ -219,11 +175,7 @@ extern "C" int somhip_glvq_train(somhip_codebook *cb, somhip_dataset *ds, const 
       uint32_t correct = 0;
       if (cost_out) CHK(to_host(e, hc.data(), b.cost, hc.size()));
       CHK(to_host_sync(e, &correct, b.correct, 1));
-      if (cost_out) {
-        double chain = 0.0;
-        for (double c : hc) chain += c;
-        cost_out[t - p->start_epoch] = chain / (double)p->n;
-      }
+      if (cost_out) cost_out[t - p->start_epoch] = cost_figure(hc, (double)p->n);
       if (correct_out) correct_out[t - p->start_epoch] = (int64_t)correct;
     }
     CHK(glvq_update_stage(cb, alpha_t, p->n, b));
@@ -242,13 +194,7 @@ extern "C" int somhip_debug_glvq_search(somhip_codebook *cb, somhip_dataset *ds,
   GlvqBufs b;
   CHK(glvq_bind(cb, n, &b));
   CHK(glvq_search_stage(cb, ds, first, n, route == SOMHIP_GLVQ_PLAN ? glvq_plan(cb->v.n, cb->v.d, n) : route, b, remainder));
-  std::vector<uint64_t> hk(2 * (size_t)n);
-  CHK(to_host_sync(e, hk.data(), b.keys2, hk.size()));
-  for (int64_t s = 0; s < n; s++) {
-    decode_key(hk[2 * (size_t)s], false, iplus + s, dplus + s);
-    decode_key(hk[2 * (size_t)s + 1], false, iminus + s, dminus + s);
-  }
-  return 0;
+  return glvq_keys_to_host(e, b, n, dplus, iplus, dminus, iminus);
 } ABI_CATCH(somhip_debug_glvq_search)
 
 extern "C" int somhip_debug_glvq_sums(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, float sigmoid_beta,
@@ -264,16 +210,8 @@ extern "C" int somhip_debug_glvq_sums(somhip_codebook *cb, somhip_dataset *ds, i
   CHK(glvq_search_stage(cb, ds, first, n, glvq_plan(cb->v.n, cb->v.d, n), b, nullptr));
   CHK(glvq_terms_stage(cb, n, sigmoid_beta, b));
   CHK(glvq_sums_stage(cb, ds, first, n, b));
-  const size_t units = (size_t)cb->v.n, ld = (size_t)cb->v.d + 1, ns = (size_t)n;
   uint32_t hcorrect = 0;
-  CHK(to_host(e, xi_plus, b.xi, ns));
-  CHK(to_host(e, xi_minus, b.xi + ns, ns));
-  CHK(to_host(e, f, b.f, ns));
-  CHK(to_host(e, sums_plus, b.S, units * ld));
-  CHK(to_host(e, sums_minus, b.S + units * ld, units * ld));
-  CHK(to_host(e, n_plus, b.hits, units));
-  CHK(to_host(e, n_minus, b.hits + units, units));
-  CHK(to_host(e, cost, b.cost, units));
+  CHK(glvq_sums_to_host(cb, b, n, xi_plus, xi_minus, f, sums_plus, n_plus, sums_minus, n_minus, cost));
   CHK(to_host_sync(e, &hcorrect, b.correct, 1));
   *correct = (int64_t)hcorrect;
   return 0;
@@ -289,11 +227,7 @@ extern "C" int somhip_debug_glvq_update(somhip_codebook *cb, float alpha_t, int6
   HIPCHK(hipSetDevice(e->device));
   GlvqBufs b;
   CHK(glvq_bind(cb, 0, &b));
-  const size_t units = (size_t)cb->v.n, ld = (size_t)cb->v.d + 1;
-  CHK(to_device(e, b.S, sums_plus, units * ld));
-  CHK(to_device(e, b.S + units * ld, sums_minus, units * ld));
-  CHK(to_device(e, b.hits, n_plus, units));
-  CHK(to_device(e, b.hits + units, n_minus, units));
+  CHK(glvq_sums_to_device(cb, b, sums_plus, n_plus, sums_minus, n_minus));
   CHK(glvq_update_stage(cb, alpha_t, n, b));
   HIPCHK(hipStreamSynchronize(e->stream));                              // (the host arrays are read until the copies have run)
   return 0;
@@ -302,12 +236,8 @@ extern "C" int somhip_debug_glvq_update(somhip_codebook *cb, float alpha_t, int6
 // HIP-event totals of the stages since somhip_timing_reset, while somhip_timing_enable is on (ids of their own behind the
 // published table): [0] search, [1] terms and grouping, [2] sums, [3] update
 extern "C" int somhip_glvq_timing(somhip_engine *e, int64_t launches[4], double total_ms[4]) try {
-  CHK(check_engine(e, "somhip_glvq_timing"));
-  if (!launches || !total_ms) return fail("somhip_glvq_timing: null output");
-  CHK(timing_flush(e));
   const int kid[4] = {KID_GLVQ_SEARCH, KID_GLVQ_TERMS, KID_GLVQ_SUMS, KID_GLVQ_UPDATE};
-  for (int i = 0; i < 4; i++) { launches[i] = e->launches[kid[i]]; total_ms[i] = e->total_ms[kid[i]]; }
-  return 0;
+  return stage_timing(e, "somhip_glvq_timing", kid, 4, launches, total_ms);
 } ABI_CATCH(somhip_glvq_timing)
 
 // ---------------------------------------------------------------------------------
@@ -370,9 +300,7 @@ static int glvq_finish_state(somhip_codebook *cb, float alpha_t, const GlvqTail 
   if (cost_out) {
     std::vector<double> hc((size_t)cb->v.n);
     CHK(to_host_sync(e, hc.data(), b.cost, hc.size()));
-    double chain = 0.0;
-    for (double c : hc) chain += c;
-    *cost_out = chain / (double)tail.samples;
+    *cost_out = cost_figure(hc, (double)tail.samples);
   }
   if (correct_out) *correct_out = (int64_t)tail.correct;
   CHK(glvq_update_stage(cb, alpha_t, (int64_t)tail.samples, b));
@@ -453,10 +381,9 @@ extern "C" int somhip_glvq_train_ranks(somhip_codebook *cb, somhip_dataset *bloc
   const char *who = "somhip_glvq_train_ranks";
   CHK(check_codebook(cb, p && c, who));
   const bool empty = p->n == 0;                                          // a rank whose block holds no row: legal here and only here
-  if (p->epochs < 1) return fail("%s: epochs %lld < 1", who, (long long)p->epochs);
-  if (p->start_epoch < 0 || p->count < 0 || p->start_epoch + p->count > p->epochs)
-    return fail("%s: epochs [%lld, %lld) outside [0, %lld)", who, (long long)p->start_epoch, (long long)(p->start_epoch + p->count), (long long)p->epochs);
-  if (!(p->alpha >= 0.0f)) return fail("%s: alpha %g is negative or not a number", who, (double)p->alpha);
+  CHK(check_epochs(p->epochs, who));
+  CHK(check_epoch_window(p->start_epoch, p->count, p->epochs, who));
+  CHK(check_alpha(p->alpha, who));
   CHK(glvq_check_beta(p->sigmoid_beta, who));
   if (c->e != cb->e) return fail("%s: codebook and communicator belong to different engines", who);
   if (empty) CHK(glvq_check_codebook(cb, who));
@@ -480,12 +407,11 @@ extern "C" int somhip_glvq_train_ranks(somhip_codebook *cb, somhip_dataset *bloc
   if (total == 0) return fail("%s: no rank holds a row", who);
   auto epochs = [&]() -> int {
     const int route = empty ? SOMHIP_GLVQ_DIRECT : glvq_plan(cb->v.n, cb->v.d, p->n);
-    const float T = (float)p->epochs;
     CHK(glvq_state_open(cb));                                           // (the blob exists from here on: its address is bound once;
     GlvqBufs b;                                                         //  every epoch opens it again, which re-zeroes it)
     CHK(glvq_bind(cb, p->n, &b, cb->gl_state));
     for (int64_t t = p->start_epoch; t < p->start_epoch + p->count; t++) {
-      const float alpha_t = p->alpha * (float)(p->epochs - t) / T;
+      const float alpha_t = linear_rate(p->alpha, p->epochs, t);
       CHK(glvq_state_open(cb));
       if (!empty) {
         CHK(glvq_search_stage(cb, block, p->first, p->n, route, b, nullptr));

@@ -2,7 +2,9 @@
 // the rows, K9's class-wise scan on the projected tiles, K9's terms, grouping and sums (unchanged), the block-wise ordered
 // gradient of Omega with its reduction, the update through Omega^T Omega, and Omega's step on the host; the stages on their
 // own for the tests
-// (included by somhip.hip last: one translation unit, K9's buffers, checks and stages by name)
+// (included by somhip.hip behind host_grlvq.inc: one translation unit; K9's checks, binding, terms and sums stages by name,
+// K11's check of eps, and the trainers' shared pieces of host_proto.inc: the class-wise scan's walk over tiles that are
+// there already, the family's copies)
 
 // The device arrays of a GMLVQ call beside K9's (GlvqBufs: SLOT_GLVQ, SLOT_GLVQ_LIST).  SLOT_GMLVQ: [vt: the projected storage
 // tiles, groups x d4m x 64 float4][xt: the projected sample tiles of the whole run, ceil(n / 32) x d4m x 32 float4]
@@ -74,26 +76,12 @@ static int gmlvq_project_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t 
   return LAUNCH_TIMED(e, KID_GMLVQ_PROJECT, (k_gmlvq_project<GLVQ_S, GMLVQ_RT>), dim3((unsigned)cb->v.ngroups, ry), dim3(256), 0, b.om, cb->v.d, b.m, b.d4m,
                       nullptr, 0, 0, cb->v, cb->v.n, nullptr, b.vt, nullptr);
 }
-// Step 3: b.g.keys2 <- the two keys of every sample of the run: K9's class-wise scan over the projected tiles, in its chunks
+// Step 3: b.g.keys2 <- the two keys of every sample of the run: the class-wise scan's walk over the projected tiles, which
+// packs nothing, under K9's id
 static int gmlvq_search_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, const GmlvqBufs &b) {
-  somhip_engine *e = cb->e;
-  HIPCHK(hipMemsetAsync(b.g.keys2, 0xFF, sizeof(uint64_t) * 2 * (size_t)n, e->stream));
-  const int64_t f0 = first % ds->n;
-  const bool wide = b.pv.ngroups >= 4 * GLVQ_R;
-  const dim3 block(256);
-  for (int64_t off = 0; off < n; off += GLVQ_CHUNK) {
-    const int64_t c = std::min(GLVQ_CHUNK, n - off), nsb = (c + GLVQ_S - 1) / GLVQ_S;
-    const float4 *xt = reinterpret_cast<const float4 *>(b.xt) + (off / GLVQ_S) * b.d4m * GLVQ_S;
-    const dim3 grid((unsigned)nsb, (unsigned)((b.pv.ngroups + (wide ? 4 * GLVQ_R : 4) - 1) / (wide ? 4 * GLVQ_R : 4)));
-    if (wide)
-      CHK(LAUNCH_TIMED(e, KID_GLVQ_SEARCH, (k_scan_class<GLVQ_S, GLVQ_R>), grid, block, 0, b.pv, xt, c, cb->d_labels, ds->d_labels, ds->n, f0, off, nullptr,
-          b.g.keys2));
-    else
-      CHK(LAUNCH_TIMED(e, KID_GLVQ_SEARCH, (k_scan_class<GLVQ_S, 1>), grid, block, 0, b.pv, xt, c, cb->d_labels, ds->d_labels, ds->n, f0, off, nullptr,
-          b.g.keys2));
-  }
-  e->samples_searched += (uint64_t)n;
-  return 0;
+  HIPCHK(hipMemsetAsync(b.g.keys2, 0xFF, sizeof(uint64_t) * 2 * (size_t)n, cb->e->stream));
+  return class_scan_walk(cb->e, b.pv, cb->d_labels, ds, first, n, /*projected*/ reinterpret_cast<const float4 *>(b.xt), /*sel*/ nullptr,
+                         /*lam*/ nullptr, KID_GLVQ_SEARCH, b.g.keys2);
 }
 // Step 7: b.Gm from the terms, the winners and both projections
 static int gmlvq_grad_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, const GmlvqBufs &b) {
@@ -108,8 +96,7 @@ static int gmlvq_grad_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t fir
 }
 // Step 6: the rows from b.g.S, b.g.hits and b.om
 static int gmlvq_update_stage(somhip_codebook *cb, float alpha_t, int64_t n, const GmlvqBufs &b) {
-  cb->prep_valid = cb->rowmajor_valid = false;
-  cb->bm_open = cb->gl_open = false;
+  rows_written(cb);
   return LAUNCH_TIMED(cb->e, KID_GMLVQ_UPDATE, k_gmlvq_update<GMLVQ_THREADS>, dim3((unsigned)cb->v.n), dim3(GMLVQ_THREADS), 0, cb->v, b.g.S, b.g.hits, b.om,
                       b.omT, b.m, b.gbuf, b.P, (double)alpha_t / (double)n);
 }
@@ -137,10 +124,9 @@ extern "C" int somhip_gmlvq_train(somhip_codebook *cb, somhip_dataset *ds, const
   const char *who = "somhip_gmlvq_train";
   if (!p) return fail("%s: null parameters", who);
   if (!cb || !ds) return fail("%s: null handle", who);
-  if (p->epochs < 1) return fail("%s: epochs %lld < 1", who, (long long)p->epochs);
-  if (p->start_epoch < 0 || p->count < 0 || p->start_epoch + p->count > p->epochs)
-    return fail("%s: epochs [%lld, %lld) outside [0, %lld)", who, (long long)p->start_epoch, (long long)(p->start_epoch + p->count), (long long)p->epochs);
-  if (!(p->alpha >= 0.0f)) return fail("%s: alpha %g is negative or not a number", who, (double)p->alpha);
+  CHK(check_epochs(p->epochs, who));
+  CHK(check_epoch_window(p->start_epoch, p->count, p->epochs, who));
+  CHK(check_alpha(p->alpha, who));
   CHK(glvq_check_beta(p->sigmoid_beta, who));
   CHK(grlvq_check_eps(p->eps, who));
   CHK(glvq_check(cb, ds, p->first, p->n, who));
@@ -148,13 +134,11 @@ extern "C" int somhip_gmlvq_train(somhip_codebook *cb, somhip_dataset *ds, const
   somhip_engine *e = cb->e;
   GmlvqBufs b;
   CHK(gmlvq_bind(cb, p->n, p->rank, &b));
-  const float T = (float)p->epochs;
   const size_t len = (size_t)p->rank * cb->v.d;
   std::vector<double> hc((size_t)(cost_out ? cb->v.n : 0)), Gm(len);
   std::vector<float> stage, om(omega, omega + len);
   for (int64_t t = p->start_epoch; t < p->start_epoch + p->count; t++) {
-    const float alpha_t = p->alpha * (float)(p->epochs - t) / T;        // LVQ_PAK's linear rate over epochs
-    const float eps_t = p->eps * (float)(p->epochs - t) / T;
+    const float alpha_t = linear_rate(p->alpha, p->epochs, t), eps_t = linear_rate(p->eps, p->epochs, t);
     CHK(gmlvq_put_omega(cb, om.data(), stage, b));
     CHK(gmlvq_project_stage(cb, ds, p->first, p->n, b));
     CHK(gmlvq_search_stage(cb, ds, p->first, p->n, b));
@@ -167,11 +151,7 @@ extern "C" int somhip_gmlvq_train(somhip_codebook *cb, somhip_dataset *ds, const
     if (eps_t > 0.0f) CHK(to_host(e, Gm.data(), b.Gm, len));
     CHK(gmlvq_update_stage(cb, alpha_t, p->n, b));                      // (with the omega the epoch started from, on the device)
     HIPCHK(hipStreamSynchronize(e->stream));                            // (the copies have landed; `stage` may be rewritten)
-    if (cost_out) {
-      double chain = 0.0;
-      for (double c : hc) chain += c;
-      cost_out[t - p->start_epoch] = chain / (double)p->n;
-    }
+    if (cost_out) cost_out[t - p->start_epoch] = cost_figure(hc, (double)p->n);
     if (correct_out) correct_out[t - p->start_epoch] = (int64_t)correct;
     gmlvq_omega_step(om.data(), len, Gm.data(), eps_t, p->n);
   }
@@ -193,13 +173,7 @@ extern "C" int somhip_gmlvq_search(somhip_codebook *cb, somhip_dataset *ds, int6
   CHK(gmlvq_put_omega(cb, omega, stage, b));
   CHK(gmlvq_project_stage(cb, ds, first, n, b));
   CHK(gmlvq_search_stage(cb, ds, first, n, b));
-  std::vector<uint64_t> hk(2 * (size_t)n);
-  CHK(to_host_sync(e, hk.data(), b.g.keys2, hk.size()));
-  for (int64_t s = 0; s < n; s++) {
-    decode_key(hk[2 * (size_t)s], false, iplus + s, dplus + s);
-    decode_key(hk[2 * (size_t)s + 1], false, iminus + s, dminus + s);
-  }
-  return 0;
+  return glvq_keys_to_host(e, b.g, n, dplus, iplus, dminus, iminus);
 } ABI_CATCH(somhip_gmlvq_search)
 
 extern "C" int somhip_gmlvq_project(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, const float *omega, int32_t rank,
@@ -254,16 +228,8 @@ extern "C" int somhip_debug_gmlvq_sums(somhip_codebook *cb, somhip_dataset *ds, 
   CHK(glvq_terms_stage(cb, n, sigmoid_beta, b.g));
   CHK(glvq_sums_stage(cb, ds, first, n, b.g));
   CHK(gmlvq_grad_stage(cb, ds, first, n, b));
-  const size_t units = (size_t)cb->v.n, ld = (size_t)cb->v.d + 1, ns = (size_t)n;
   uint32_t hcorrect = 0;
-  CHK(to_host(e, xi_plus, b.g.xi, ns));
-  CHK(to_host(e, xi_minus, b.g.xi + ns, ns));
-  CHK(to_host(e, f, b.g.f, ns));
-  CHK(to_host(e, sums_plus, b.g.S, units * ld));
-  CHK(to_host(e, sums_minus, b.g.S + units * ld, units * ld));
-  CHK(to_host(e, n_plus, b.g.hits, units));
-  CHK(to_host(e, n_minus, b.g.hits + units, units));
-  CHK(to_host(e, cost, b.g.cost, units));
+  CHK(glvq_sums_to_host(cb, b.g, n, xi_plus, xi_minus, f, sums_plus, n_plus, sums_minus, n_minus, cost));
   CHK(to_host(e, grad, b.Gm, (size_t)rank * cb->v.d));
   CHK(to_host_sync(e, &hcorrect, b.g.correct, 1));
   *correct = (int64_t)hcorrect;
@@ -283,13 +249,9 @@ extern "C" int somhip_debug_gmlvq_update(somhip_codebook *cb, float alpha_t, flo
   HIPCHK(hipSetDevice(e->device));
   GmlvqBufs b;
   CHK(gmlvq_bind(cb, 0, rank, &b));
-  const size_t units = (size_t)cb->v.n, ld = (size_t)cb->v.d + 1;
   std::vector<float> stage;
   CHK(gmlvq_put_omega(cb, omega, stage, b));
-  CHK(to_device(e, b.g.S, sums_plus, units * ld));
-  CHK(to_device(e, b.g.S + units * ld, sums_minus, units * ld));
-  CHK(to_device(e, b.g.hits, n_plus, units));
-  CHK(to_device(e, b.g.hits + units, n_minus, units));
+  CHK(glvq_sums_to_device(cb, b.g, sums_plus, n_plus, sums_minus, n_minus));
   CHK(gmlvq_update_stage(cb, alpha_t, n, b));
   HIPCHK(hipStreamSynchronize(e->stream));                              // (the host arrays are read until the copies have run)
   gmlvq_omega_step(omega, (size_t)rank * cb->v.d, grad, eps_t, n);
@@ -300,10 +262,6 @@ extern "C" int somhip_debug_gmlvq_update(somhip_codebook *cb, float alpha_t, flo
 // class-wise scan, [2] terms and grouping, [3] sums (these three K9's stages under K9's ids), [4] the gradient of Omega with
 // its reduction, [5] update
 extern "C" int somhip_gmlvq_timing(somhip_engine *e, int64_t launches[6], double total_ms[6]) try {
-  CHK(check_engine(e, "somhip_gmlvq_timing"));
-  if (!launches || !total_ms) return fail("somhip_gmlvq_timing: null output");
-  CHK(timing_flush(e));
   const int kid[6] = {KID_GMLVQ_PROJECT, KID_GLVQ_SEARCH, KID_GLVQ_TERMS, KID_GLVQ_SUMS, KID_GMLVQ_GRAD, KID_GMLVQ_UPDATE};
-  for (int i = 0; i < 6; i++) { launches[i] = e->launches[kid[i]]; total_ms[i] = e->total_ms[kid[i]]; }
-  return 0;
+  return stage_timing(e, "somhip_gmlvq_timing", kid, 6, launches, total_ms);
 } ABI_CATCH(somhip_gmlvq_timing)

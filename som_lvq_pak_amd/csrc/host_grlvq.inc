@@ -1,7 +1,8 @@
 // host_grlvq.inc -- K11, batch GRLVQ: K9's epoch under the relevance-weighted metric -- the weighted class-wise search, K9's
 // terms and grouping (unchanged), the sums with the relevance chain, the ordered reduction of the relevance gradient over
 // the rows, the weighted update, and the relevance step on the host; the stages on their own for the tests
-// (included by somhip.hip behind host_glvq.inc: one translation unit, K9's buffers, checks and stages by name)
+// (included by somhip.hip behind host_glvq.inc: one translation unit; K9's checks, binding, terms stage by name, and the
+// trainers' shared pieces of host_proto.inc: the class-wise scan's walk with the relevance tile, the family's copies)
 
 // The device arrays of a GRLVQ call beside K9's (GlvqBufs: SLOT_GLVQ, SLOT_GLVQ_LIST).  SLOT_GRLVQ: [lam: d4 float4, the
 // padding zero][R: 2 x rows x dim doubles][G: dim doubles].  R is what makes the feature large: 16 bytes per row and
@@ -45,30 +46,10 @@ static int grlvq_put_lambda(somhip_codebook *cb, const float *lambda, std::vecto
   return to_device(cb->e, reinterpret_cast<float *>(b.lam), tile.data(), tile.size());
 }
 
-// Step 2: b.g.keys2 <- the two keys of every sample of the run under d_lambda.  Chunks of whole sample tiles, as K9's
-// class-wise scan takes them.
+// Step 2: b.g.keys2 <- the two keys of every sample of the run under b.lam: the class-wise scan's walk, weighted
 static int grlvq_search_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, const GrlvqBufs &b) {
-  somhip_engine *e = cb->e;
-  HIPCHK(hipMemsetAsync(b.g.keys2, 0xFF, sizeof(uint64_t) * 2 * (size_t)n, e->stream));
-  const int64_t f0 = first % ds->n;
-  const bool wide = cb->v.ngroups >= 4 * GLVQ_R;
-  const dim3 block(256);
-  for (int64_t off = 0; off < n; off += GLVQ_CHUNK) {
-    const int64_t c = std::min(GLVQ_CHUNK, n - off), nsb = (c + GLVQ_S - 1) / GLVQ_S;
-    float4 *xt;
-    CHK(scratch(e, SLOT_SAMPLES, (size_t)nsb * cb->v.d4 * GLVQ_S, &xt));
-    CHK(LAUNCH_TIMED(e, KID_PACK_SAMPLES, k_pack_samples<GLVQ_S>, dim3((unsigned)nsb), block, 0, ds->d_rows, ds->n, ds->d, cb->v.d4,
-        (f0 + off) % ds->n, c, xt));
-    const dim3 grid((unsigned)nsb, (unsigned)((cb->v.ngroups + (wide ? 4 * GLVQ_R : 4) - 1) / (wide ? 4 * GLVQ_R : 4)));
-    if (wide)
-      CHK(LAUNCH_TIMED(e, KID_GRLVQ_SEARCH, (k_scan_class_weighted<GLVQ_S, GLVQ_R>), grid, block, 0, cb->v, xt, b.lam, c, cb->d_labels,
-          ds->d_labels, ds->n, f0, off, b.g.keys2));
-    else
-      CHK(LAUNCH_TIMED(e, KID_GRLVQ_SEARCH, (k_scan_class_weighted<GLVQ_S, 1>), grid, block, 0, cb->v, xt, b.lam, c, cb->d_labels,
-          ds->d_labels, ds->n, f0, off, b.g.keys2));
-  }
-  e->samples_searched += (uint64_t)n;
-  return 0;
+  HIPCHK(hipMemsetAsync(b.g.keys2, 0xFF, sizeof(uint64_t) * 2 * (size_t)n, cb->e->stream));
+  return class_scan_walk(cb->e, cb->v, cb->d_labels, ds, first, n, /*projected*/ nullptr, /*sel*/ nullptr, /*lam*/ b.lam, KID_GRLVQ_SEARCH, b.g.keys2);
 }
 // Step 4: b.g.S, b.g.cost and b.R from the lists; step 5: b.G from b.R
 static int grlvq_sums_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, const GrlvqBufs &b) {
@@ -81,8 +62,7 @@ static int grlvq_sums_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t fir
 // Step 6: the rows from b.g.S, b.g.hits and b.lam
 static int grlvq_update_stage(somhip_codebook *cb, float alpha_t, int64_t n, const GrlvqBufs &b) {
   const int64_t threads = cb->v.ngroups * cb->v.d4 * WAVE;
-  cb->prep_valid = cb->rowmajor_valid = false;
-  cb->bm_open = cb->gl_open = false;
+  rows_written(cb);
   return LAUNCH_TIMED(cb->e, KID_GRLVQ_UPDATE, k_grlvq_update<GLVQ_THREADS>, dim3((unsigned)((threads + GLVQ_THREADS - 1) / GLVQ_THREADS)), dim3(GLVQ_THREADS), 0,
                       cb->v, b.g.S, b.g.hits, reinterpret_cast<const float *>(b.lam), (double)alpha_t / (double)n);
 }
@@ -109,10 +89,9 @@ extern "C" int somhip_grlvq_train(somhip_codebook *cb, somhip_dataset *ds, const
   const char *who = "somhip_grlvq_train";
   if (!p) return fail("%s: null parameters", who);
   if (!cb || !ds) return fail("%s: null handle", who);
-  if (p->epochs < 1) return fail("%s: epochs %lld < 1", who, (long long)p->epochs);
-  if (p->start_epoch < 0 || p->count < 0 || p->start_epoch + p->count > p->epochs)
-    return fail("%s: epochs [%lld, %lld) outside [0, %lld)", who, (long long)p->start_epoch, (long long)(p->start_epoch + p->count), (long long)p->epochs);
-  if (!(p->alpha >= 0.0f)) return fail("%s: alpha %g is negative or not a number", who, (double)p->alpha);
+  CHK(check_epochs(p->epochs, who));
+  CHK(check_epoch_window(p->start_epoch, p->count, p->epochs, who));
+  CHK(check_alpha(p->alpha, who));
   CHK(glvq_check_beta(p->sigmoid_beta, who));
   CHK(grlvq_check_eps(p->eps, who));
   CHK(glvq_check(cb, ds, p->first, p->n, who));
@@ -120,13 +99,11 @@ extern "C" int somhip_grlvq_train(somhip_codebook *cb, somhip_dataset *ds, const
   somhip_engine *e = cb->e;
   GrlvqBufs b;
   CHK(grlvq_bind(cb, p->n, &b));
-  const float T = (float)p->epochs;
   const int d = cb->v.d;
   std::vector<double> hc((size_t)(cost_out ? cb->v.n : 0)), G((size_t)d);
   std::vector<float> tile, lam(lambda, lambda + d);
   for (int64_t t = p->start_epoch; t < p->start_epoch + p->count; t++) {
-    const float alpha_t = p->alpha * (float)(p->epochs - t) / T;        // LVQ_PAK's linear rate over epochs
-    const float eps_t = p->eps * (float)(p->epochs - t) / T;
+    const float alpha_t = linear_rate(p->alpha, p->epochs, t), eps_t = linear_rate(p->eps, p->epochs, t);
     CHK(grlvq_put_lambda(cb, lam.data(), tile, b));
     CHK(grlvq_search_stage(cb, ds, p->first, p->n, b));
     CHK(glvq_terms_stage(cb, p->n, p->sigmoid_beta, b.g));
@@ -135,11 +112,7 @@ extern "C" int somhip_grlvq_train(somhip_codebook *cb, somhip_dataset *ds, const
     if (cost_out) CHK(to_host(e, hc.data(), b.g.cost, hc.size()));
     if (correct_out) CHK(to_host(e, &correct, b.g.correct, 1));
     CHK(to_host_sync(e, G.data(), b.G, G.size()));
-    if (cost_out) {
-      double chain = 0.0;
-      for (double c : hc) chain += c;
-      cost_out[t - p->start_epoch] = chain / (double)p->n;
-    }
+    if (cost_out) cost_out[t - p->start_epoch] = cost_figure(hc, (double)p->n);
     if (correct_out) correct_out[t - p->start_epoch] = (int64_t)correct;
     CHK(grlvq_update_stage(cb, alpha_t, p->n, b));                      // (with the lambda the epoch started from, on the device)
     grlvq_relevance_step(lam.data(), d, G.data(), eps_t, p->n);
@@ -161,13 +134,7 @@ extern "C" int somhip_grlvq_search(somhip_codebook *cb, somhip_dataset *ds, int6
   std::vector<float> tile;
   CHK(grlvq_put_lambda(cb, lambda, tile, b));
   CHK(grlvq_search_stage(cb, ds, first, n, b));
-  std::vector<uint64_t> hk(2 * (size_t)n);
-  CHK(to_host_sync(e, hk.data(), b.g.keys2, hk.size()));
-  for (int64_t s = 0; s < n; s++) {
-    decode_key(hk[2 * (size_t)s], false, iplus + s, dplus + s);
-    decode_key(hk[2 * (size_t)s + 1], false, iminus + s, dminus + s);
-  }
-  return 0;
+  return glvq_keys_to_host(e, b.g, n, dplus, iplus, dminus, iminus);
 } ABI_CATCH(somhip_grlvq_search)
 
 extern "C" int somhip_debug_grlvq_sums(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, float sigmoid_beta,
@@ -188,16 +155,9 @@ extern "C" int somhip_debug_grlvq_sums(somhip_codebook *cb, somhip_dataset *ds, 
   CHK(grlvq_search_stage(cb, ds, first, n, b));
   CHK(glvq_terms_stage(cb, n, sigmoid_beta, b.g));
   CHK(grlvq_sums_stage(cb, ds, first, n, b));
-  const size_t units = (size_t)cb->v.n, d = (size_t)cb->v.d, ld = d + 1, ns = (size_t)n;
+  const size_t units = (size_t)cb->v.n, d = (size_t)cb->v.d;
   uint32_t hcorrect = 0;
-  CHK(to_host(e, xi_plus, b.g.xi, ns));
-  CHK(to_host(e, xi_minus, b.g.xi + ns, ns));
-  CHK(to_host(e, f, b.g.f, ns));
-  CHK(to_host(e, sums_plus, b.g.S, units * ld));
-  CHK(to_host(e, sums_minus, b.g.S + units * ld, units * ld));
-  CHK(to_host(e, n_plus, b.g.hits, units));
-  CHK(to_host(e, n_minus, b.g.hits + units, units));
-  CHK(to_host(e, cost, b.g.cost, units));
+  CHK(glvq_sums_to_host(cb, b.g, n, xi_plus, xi_minus, f, sums_plus, n_plus, sums_minus, n_minus, cost));
   CHK(to_host(e, rel_plus, b.R, units * d));
   CHK(to_host(e, rel_minus, b.R + units * d, units * d));
   CHK(to_host(e, grad, b.G, d));
@@ -219,13 +179,9 @@ extern "C" int somhip_debug_grlvq_update(somhip_codebook *cb, float alpha_t, flo
   HIPCHK(hipSetDevice(e->device));
   GrlvqBufs b;
   CHK(grlvq_bind(cb, 0, &b));
-  const size_t units = (size_t)cb->v.n, ld = (size_t)cb->v.d + 1;
   std::vector<float> tile;
   CHK(grlvq_put_lambda(cb, lambda, tile, b));
-  CHK(to_device(e, b.g.S, sums_plus, units * ld));
-  CHK(to_device(e, b.g.S + units * ld, sums_minus, units * ld));
-  CHK(to_device(e, b.g.hits, n_plus, units));
-  CHK(to_device(e, b.g.hits + units, n_minus, units));
+  CHK(glvq_sums_to_device(cb, b.g, sums_plus, n_plus, sums_minus, n_minus));
   CHK(grlvq_update_stage(cb, alpha_t, n, b));
   HIPCHK(hipStreamSynchronize(e->stream));                              // (the host arrays are read until the copies have run)
   grlvq_relevance_step(lambda, cb->v.d, grad, eps_t, n);
@@ -236,10 +192,6 @@ extern "C" int somhip_debug_grlvq_update(somhip_codebook *cb, float alpha_t, flo
 // published table, but for the terms, which are K9's stage under K9's id): [0] search, [1] terms and grouping, [2] sums,
 // [3] the relevance reduction, [4] update
 extern "C" int somhip_grlvq_timing(somhip_engine *e, int64_t launches[5], double total_ms[5]) try {
-  CHK(check_engine(e, "somhip_grlvq_timing"));
-  if (!launches || !total_ms) return fail("somhip_grlvq_timing: null output");
-  CHK(timing_flush(e));
   const int kid[5] = {KID_GRLVQ_SEARCH, KID_GLVQ_TERMS, KID_GRLVQ_SUMS, KID_GRLVQ_RELEVANCE, KID_GRLVQ_UPDATE};
-  for (int i = 0; i < 5; i++) { launches[i] = e->launches[kid[i]]; total_ms[i] = e->total_ms[kid[i]]; }
-  return 0;
+  return stage_timing(e, "somhip_grlvq_timing", kid, 5, launches, total_ms);
 } ABI_CATCH(somhip_grlvq_timing)

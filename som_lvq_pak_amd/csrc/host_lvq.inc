@@ -227,8 +227,8 @@ static int lvq_commit(somhip_codebook *cb, const LvqPlan &pl, const LvqBatchBufs
 // never made them so: re-splitting a few rows of stale tiles must not validate them)
 static int lvq_refresh_prepared(somhip_codebook *cb, const LvqBatchBufs &b, int bound, const int32_t *skip) {
   somhip_engine *e = cb->e;
-  cb->bm_open = cb->gl_open = false;                                    // (rows were rewritten: a batch-map accumulation no longer describes them)
-  if (!cb->prep_valid || !cb->d_chi || !cb->d_cn || e->scan_mode != SOMHIP_SCAN_MFMA_BF16) { cb->prep_valid = cb->rowmajor_valid = false; return 0; }
+  if (!cb->prep_valid || !cb->d_chi || !cb->d_cn || e->scan_mode != SOMHIP_SCAN_MFMA_BF16) { rows_written(cb); return 0; }
+  close_accumulations(cb);                                              // (rows were rewritten: an accumulation no longer describes them)
   CHK(LAUNCH(e, k_prep_rows_bf16, dim3((unsigned)((bound + 3) / 4)), dim3(256), 0, cb->v, (cb->v.d4 + 1) / 2, b.mod_rows, bound, b.mod_count,
       cb->d_cn, cb->d_chi, cb->d_clo, skip));
   cb->rowmajor_valid = false;                             // (the row-major copy is not re-split row by row)
@@ -403,8 +403,7 @@ static int lvq_train_batched(somhip_codebook *cb, somhip_dataset *ds, const somh
 static int lvq_train_online(somhip_codebook *cb, somhip_dataset *ds, const somhip_lvq_params *p, const LvqPlan &pl,
                             int32_t *trace_index, float *trace_diff) {
   somhip_engine *e = cb->e;
-  cb->prep_valid = cb->rowmajor_valid = false;            // the per-iteration kernel rewrites rows in place
-  cb->bm_open = cb->gl_open = false;
+  rows_written(cb);            // the per-iteration kernel rewrites rows in place
   const int64_t CH = 4096;
   const int nblk = (int)((cb->v.ngroups + 3) / 4);
   const bool want_trace = trace_index || trace_diff;

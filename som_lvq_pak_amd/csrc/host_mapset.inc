@@ -237,10 +237,6 @@ extern "C" int somhip_mapset_winners(somhip_mapset *ms, somhip_dataset *ds, int6
 // HIP-event totals of the two set kernels since somhip_timing_reset, while somhip_timing_enable is on (the kernel table
 // of somhip_kernel_count is closed; these two are timed under ids of their own): [0] k_mapset_train, [1] k_mapset_winners
 extern "C" int somhip_mapset_timing(somhip_engine *e, int64_t launches[2], double total_ms[2]) try {
-  CHK(check_engine(e, "somhip_mapset_timing"));
-  if (!launches || !total_ms) return fail("somhip_mapset_timing: null output");
-  CHK(timing_flush(e));
-  launches[0] = e->launches[KID_MAPSET_TRAIN]; launches[1] = e->launches[KID_MAPSET_WINNERS];
-  total_ms[0] = e->total_ms[KID_MAPSET_TRAIN]; total_ms[1] = e->total_ms[KID_MAPSET_WINNERS];
-  return 0;
+  const int kid[2] = {KID_MAPSET_TRAIN, KID_MAPSET_WINNERS};
+  return stage_timing(e, "somhip_mapset_timing", kid, 2, launches, total_ms);
 } ABI_CATCH(somhip_mapset_timing)

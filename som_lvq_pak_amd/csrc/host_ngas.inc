@@ -1,7 +1,8 @@
 // host_ngas.inc -- K10, batch neural gas: per epoch the schedule (host, double), the K nearest units of every sample against
 // the frozen codebook (the engine's k-NN search), the (unit, sample, rank) entries grouped by unit, the per-unit ordered
 // fp64 sums of rank-weighted rows and the update; the stages on their own for the tests
-// (included by somhip.hip behind host_glvq.inc: one translation unit, shared static helpers, rocPRIM's sort)
+// (included by somhip.hip behind host_glvq.inc: one translation unit, the trainers' shared checks and the trailing column
+// of host_proto.inc, K8's scan of the counts, rocPRIM's sort)
 
 // The segment rule, stated once.  The data go through the entries, the sort and the sums in segments of consecutive
 // samples; a segment holds at most NG_SEGMENT_PAIRS (sample, rank) pairs, so the sort's buffers stay bounded (16 bytes a
@@ -134,8 +135,7 @@ static int ng_sums_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t first,
 // Step 4: the rows from b.S
 static int ng_update_stage(somhip_codebook *cb, const NgBufs &b) {
   const int64_t threads = cb->v.ngroups * cb->v.d4 * WAVE;
-  cb->prep_valid = cb->rowmajor_valid = false;
-  cb->bm_open = cb->gl_open = false;                                                  // (the rows move: an open batch-map accumulation is over)
+  rows_written(cb);
   return LAUNCH_TIMED(cb->e, KID_NG_UPDATE, k_ng_update, dim3((unsigned)((threads + NG_THREADS - 1) / NG_THREADS)), dim3(NG_THREADS), 0, cb->v, b.S);
 }
 
@@ -158,7 +158,7 @@ static int ng_check_ranks(int64_t K, int least, const char *who) {
 }
 static int ng_check_params(const somhip_ng_params *p, const char *who) {
   if (!p) return fail("%s: null parameters", who);
-  if (p->epochs < 1) return fail("%s: epochs %lld < 1", who, (long long)p->epochs);
+  CHK(check_epochs(p->epochs, who));
   if (!(p->lambda0 > 0.0) || std::isinf(p->lambda0)) return fail("%s: lambda0 %g is not a positive number", who, p->lambda0);
   if (!(p->lambda_end > 0.0) || !(p->lambda_end <= p->lambda0))
     return fail("%s: lambda_end %g outside (0, lambda0 = %g]", who, p->lambda_end, p->lambda0);
@@ -181,12 +181,11 @@ extern "C" int somhip_ng_train(somhip_codebook *cb, somhip_dataset *ds, const so
   const char *who = "somhip_ng_train";
   if (!cb || !ds) return fail("%s: null handle", who);
   CHK(ng_check_params(p, who));
-  if (p->start_epoch < 0 || p->count < 0 || p->start_epoch + p->count > p->epochs)
-    return fail("%s: epochs [%lld, %lld) outside [0, %lld)", who, (long long)p->start_epoch, (long long)(p->start_epoch + p->count), (long long)p->epochs);
+  CHK(check_epoch_window(p->start_epoch, p->count, p->epochs, who));
   CHK(ng_check(cb, ds, p->first, p->n, who));
   somhip_engine *e = cb->e;
   HIPCHK(hipSetDevice(e->device));
-  cb->bm_open = cb->gl_open = false;
+  close_accumulations(cb);
   const int64_t units = cb->v.n;
   // the schedule of every epoch of the call, before the first launch: the tables are read until their copies have run
   std::vector<double> w((size_t)p->count * SOMHIP_KNN_MAX);
@@ -257,10 +256,7 @@ extern "C" int somhip_debug_ng_sums(somhip_codebook *cb, somhip_dataset *ds, int
   std::vector<double> hs(units * (d + 1));
   CHK(to_host(e, hits, b.hits, units));
   CHK(to_host_sync(e, hs.data(), b.S, hs.size()));
-  for (size_t u = 0; u < units; u++) {
-    memcpy(sums + u * d, hs.data() + u * (d + 1), sizeof(double) * d);
-    wsum[u] = hs[u * (d + 1) + d];
-  }
+  split_trailing(hs.data(), units, d, sums, wsum);
   return 0;
 } ABI_CATCH(somhip_debug_ng_sums)
 
@@ -274,10 +270,7 @@ extern "C" int somhip_debug_ng_update(somhip_codebook *cb, const uint32_t *hits,
   CHK(ng_bind(cb, 0, &b));
   const size_t units = (size_t)cb->v.n, d = (size_t)cb->v.d;
   std::vector<double> hs(units * (d + 1));
-  for (size_t u = 0; u < units; u++) {
-    memcpy(hs.data() + u * (d + 1), sums + u * d, sizeof(double) * d);
-    hs[u * (d + 1) + d] = wsum[u];
-  }
+  join_trailing(hs.data(), units, d, sums, wsum);
   CHK(to_device(e, b.S, hs.data(), hs.size()));                        // (hits: what the sums stage returns beside them; W decides, not hits)
   CHK(ng_update_stage(cb, b));
   HIPCHK(hipStreamSynchronize(e->stream));                              // (the host arrays are read until the copies have run)
@@ -288,10 +281,6 @@ extern "C" int somhip_debug_ng_update(somhip_codebook *cb, const uint32_t *hits,
 // published table): [0] the entries pass per chunk and the grouping, [1] the sums, [2] the update.  The search's launches
 // count under their own ids (the published table, somhip_knn_timing).
 extern "C" int somhip_ng_timing(somhip_engine *e, int64_t launches[3], double total_ms[3]) try {
-  CHK(check_engine(e, "somhip_ng_timing"));
-  if (!launches || !total_ms) return fail("somhip_ng_timing: null output");
-  CHK(timing_flush(e));
   const int kid[3] = {KID_NG_GROUP, KID_NG_SUMS, KID_NG_UPDATE};
-  for (int i = 0; i < 3; i++) { launches[i] = e->launches[kid[i]]; total_ms[i] = e->total_ms[kid[i]]; }
-  return 0;
+  return stage_timing(e, "somhip_ng_timing", kid, 3, launches, total_ms);
 } ABI_CATCH(somhip_ng_timing)

@@ -2,7 +2,8 @@
 // chunk of samples the exact distances to every row (K1w's distance stage), the full ranking turned into the chunk's
 // weights Q (k_ng_dense_weights), [S | W] = Q^T x [X | 1] on the fp64 MFMA, continued from chunk to chunk (K13's
 // k_rslvq_sums); then K10's update; the stages on their own for the tests
-// (included by somhip.hip behind host_rslvq.inc: one translation unit, K10's refusals and update, K13's chunk rule)
+// (included by somhip.hip behind host_rslvq.inc: one translation unit, K10's refusals and update, K13's chunk rule, and
+// from host_proto.inc the distance and sums stages of a chunk, which K13 runs as well)
 
 static_assert(NGD_MAX == SOMHIP_NG_DENSE_MAX, "the kernel's cap is the header's");
 
@@ -43,31 +44,14 @@ static int ngd_bind(somhip_codebook *cb, int64_t n, int64_t chunk, NgDenseBufs *
   return 0;
 }
 
-// Step 2 for the c samples of the run from `off` on: b.dist <- every distance (k_pack_samples, k_knn_dist, unchanged)
-static int ngd_dist_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t off, int64_t c, const NgDenseBufs &b) {
-  somhip_engine *e = cb->e;
-  const int64_t nsb = (c + SCAN_S - 1) / SCAN_S;
-  float4 *xt;
-  CHK(scratch(e, SLOT_SAMPLES, (size_t)nsb * cb->v.d4 * SCAN_S, &xt));
-  LaunchTimer t(e, KID_NG_DENSE_DIST);
-  CHK(LAUNCH(e, k_pack_samples<SCAN_S>, dim3((unsigned)nsb), dim3(256), 0, ds->d_rows, ds->n, ds->d, cb->v.d4, (first % ds->n + off) % ds->n, c, xt));
-  CHK(LAUNCH(e, k_knn_dist<SCAN_S>, dim3((unsigned)nsb, (unsigned)((cb->v.ngroups + 3) / 4)), dim3(256), 0, cb->v, xt, c, b.ld, b.dist));
-  e->samples_searched += (uint64_t)c;
-  return 0;
-}
+// Step 2, b.dist <- every distance of c samples of the run from `off` on, is dist_chunk_stage (host_proto.inc) under
+// KID_NG_DENSE_DIST; step 4, [S | W] <- the accumulators continued behind the run's first chunk, is sums_chunk_stage under
+// KID_NG_DENSE_SUMS.
 // Step 3 for those samples: b.Q <- the chunk's weights, b.d0 at the run's sample numbers (Q null: the ranks stage's outputs
 // alone)
 static int ngd_weights_stage(somhip_codebook *cb, int64_t off, int64_t c, const NgDenseBufs &b, double *Q, int32_t *rank, float *dunit) {
   return LAUNCH_TIMED(cb->e, KID_NG_DENSE_WEIGHTS, k_ng_dense_weights, dim3((unsigned)c), dim3(NGD_THREADS), sizeof(uint64_t) * (size_t)b.P, cb->v,
                       b.dist, b.ld, off, b.P, b.w, Q, b.d0, rank, dunit);
-}
-// Step 4 for those samples: [S | W] <- the accumulators, from +0.0 for the run's first chunk and from [S | W] behind it
-static int ngd_sums_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t off, int64_t c, const NgDenseBufs &b) {
-  const dim3 grid((unsigned)cb->v.ngroups, (unsigned)((cb->v.d + RS_COLS - 1) / RS_COLS));
-  const int64_t f = (first % ds->n + off) % ds->n;
-  if (off > 0)
-    return LAUNCH_TIMED(cb->e, KID_NG_DENSE_SUMS, k_rslvq_sums<true>, grid, dim3(256), 0, b.Q, b.ld, c, ds->d_rows, ds->n, ds->d, f, cb->v.n, b.ng.S);
-  return LAUNCH_TIMED(cb->e, KID_NG_DENSE_SUMS, k_rslvq_sums<false>, grid, dim3(256), 0, b.Q, b.ld, c, ds->d_rows, ds->n, ds->d, f, cb->v.n, b.ng.S);
 }
 // Steps 2-4 of an epoch with the weights `w` (host, units doubles; read until the copy has run): chunk after chunk.
 // q (or null): find_qerror's float chain over the rank-0 distances in data order.
@@ -76,9 +60,9 @@ static int ngd_walk(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int6
   CHK(to_device(e, b.w, w, (size_t)cb->v.n));
   for (int64_t off = 0; off < n; off += b.chunk) {
     const int64_t c = std::min(b.chunk, n - off);
-    CHK(ngd_dist_stage(cb, ds, first, off, c, b));
+    CHK(dist_chunk_stage(cb, ds, first, off, c, KID_NG_DENSE_DIST, b.ld, b.dist));
     CHK(ngd_weights_stage(cb, off, c, b, b.Q, nullptr, nullptr));
-    CHK(ngd_sums_stage(cb, ds, first, off, c, b));
+    CHK(sums_chunk_stage(cb, ds, first, off, c, KID_NG_DENSE_SUMS, b.Q, b.ld, b.ng.S));
   }
   if (!q) return 0;
   std::vector<float> hd((size_t)n);
@@ -118,12 +102,11 @@ extern "C" int somhip_ng_train_dense(somhip_codebook *cb, somhip_dataset *ds, co
   const char *who = "somhip_ng_train_dense";
   if (!cb || !ds) return fail("%s: null handle", who);
   CHK(ngd_check_params(p, who));
-  if (p->start_epoch < 0 || p->count < 0 || p->start_epoch + p->count > p->epochs)
-    return fail("%s: epochs [%lld, %lld) outside [0, %lld)", who, (long long)p->start_epoch, (long long)(p->start_epoch + p->count), (long long)p->epochs);
+  CHK(check_epoch_window(p->start_epoch, p->count, p->epochs, who));
   CHK(ngd_check(cb, ds, p->first, p->n, who));
   somhip_engine *e = cb->e;
   HIPCHK(hipSetDevice(e->device));
-  cb->bm_open = cb->gl_open = false;
+  close_accumulations(cb);
   const int64_t units = cb->v.n;
   NgDenseBufs b;
   CHK(ngd_bind(cb, p->n, rslvq_chunk(cb->v.ngroups), &b));
@@ -157,7 +140,7 @@ extern "C" int somhip_debug_ng_dense_ranks(somhip_codebook *cb, somhip_dataset *
   std::vector<float> hd(hr.size());
   for (int64_t off = 0; off < n; off += b.chunk) {
     const int64_t c = std::min(b.chunk, n - off);
-    CHK(ngd_dist_stage(cb, ds, first, off, c, b));
+    CHK(dist_chunk_stage(cb, ds, first, off, c, KID_NG_DENSE_DIST, b.ld, b.dist));
     CHK(ngd_weights_stage(cb, off, c, b, nullptr, rank, dunit));
     CHK(to_host(e, hr.data(), rank, (size_t)c * ld));
     CHK(to_host_sync(e, hd.data(), dunit, (size_t)c * ld));
@@ -186,20 +169,13 @@ extern "C" int somhip_debug_ng_dense_sums(somhip_codebook *cb, somhip_dataset *d
   CHK(ngd_walk(cb, ds, first, n, w.data(), b, nullptr));
   std::vector<double> hs(units * (d + 1));
   CHK(to_host_sync(e, hs.data(), b.ng.S, hs.size()));
-  for (size_t u = 0; u < units; u++) {
-    memcpy(sums + u * d, hs.data() + u * (d + 1), sizeof(double) * d);
-    wsum[u] = hs[u * (d + 1) + d];
-  }
+  split_trailing(hs.data(), units, d, sums, wsum);
   return 0;
 } ABI_CATCH(somhip_debug_ng_dense_sums)
 
 // HIP-event totals of the stages since somhip_timing_reset, while somhip_timing_enable is on (ids of their own behind the
 // published table): [0] distances (the sample tiles and k_knn_dist), [1] k_ng_dense_weights, [2] sums
 extern "C" int somhip_ng_dense_timing(somhip_engine *e, int64_t launches[3], double total_ms[3]) try {
-  CHK(check_engine(e, "somhip_ng_dense_timing"));
-  if (!launches || !total_ms) return fail("somhip_ng_dense_timing: null output");
-  CHK(timing_flush(e));
   const int kid[3] = {KID_NG_DENSE_DIST, KID_NG_DENSE_WEIGHTS, KID_NG_DENSE_SUMS};
-  for (int i = 0; i < 3; i++) { launches[i] = e->launches[kid[i]]; total_ms[i] = e->total_ms[kid[i]]; }
-  return 0;
+  return stage_timing(e, "somhip_ng_dense_timing", kid, 3, launches, total_ms);
 } ABI_CATCH(somhip_ng_dense_timing)

@@ -103,10 +103,6 @@ extern "C" int somhip_map_connectivity(somhip_codebook *cb, somhip_dataset *ds, 
 // HIP-event totals of the two kernels since somhip_timing_reset, while somhip_timing_enable is on (ids of their own behind
 // the published table, like the vote's): [0] k_quality_pairs, [1] k_quality_units
 extern "C" int somhip_map_quality_timing(somhip_engine *e, int64_t launches[2], double total_ms[2]) try {
-  CHK(check_engine(e, "somhip_map_quality_timing"));
-  if (!launches || !total_ms) return fail("somhip_map_quality_timing: null output");
-  CHK(timing_flush(e));
-  launches[0] = e->launches[KID_QUALITY_PAIRS]; launches[1] = e->launches[KID_QUALITY_UNITS];
-  total_ms[0] = e->total_ms[KID_QUALITY_PAIRS]; total_ms[1] = e->total_ms[KID_QUALITY_UNITS];
-  return 0;
+  const int kid[2] = {KID_QUALITY_PAIRS, KID_QUALITY_UNITS};
+  return stage_timing(e, "somhip_map_quality_timing", kid, 2, launches, total_ms);
 } ABI_CATCH(somhip_map_quality_timing)

@@ -1,7 +1,8 @@
 // host_rslvq.inc -- K13, batch Robust Soft LVQ: per epoch and chunk of samples the exact distances to every row (K1w's
 // distance stage), the posteriors and their coefficients Q (posterior), [G | c] = Q^T x [X | 1] on the fp64 MFMA, continued
 // from chunk to chunk (sums); then the update; the stages on their own for the tests
-// (included by somhip.hip behind host_gmlvq.inc: one translation unit, shared static helpers, K9's refusals)
+// (included by somhip.hip behind host_gmlvq.inc: one translation unit, K9's refusals, and from host_proto.inc the distance
+// and sums stages of a chunk, which the dense neural gas runs as well)
 
 constexpr int64_t RSLVQ_CHUNK_MAX = 4096;                       // samples of a chunk at most
 constexpr size_t RSLVQ_Q_BYTES = (size_t)256 << 20;             // ... and the room its Q may take
@@ -39,18 +40,8 @@ static int rslvq_bind(somhip_codebook *cb, int64_t n, int64_t chunk, RslvqBufs *
   return 0;
 }
 
-// Step 2 for the c samples of the run from `off` on: b.dist <- every distance (k_pack_samples, k_knn_dist, unchanged)
-static int rslvq_dist_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t off, int64_t c, const RslvqBufs &b) {
-  somhip_engine *e = cb->e;
-  const int64_t nsb = (c + SCAN_S - 1) / SCAN_S;
-  float4 *xt;
-  CHK(scratch(e, SLOT_SAMPLES, (size_t)nsb * cb->v.d4 * SCAN_S, &xt));
-  LaunchTimer t(e, KID_RSLVQ_DIST);
-  CHK(LAUNCH(e, k_pack_samples<SCAN_S>, dim3((unsigned)nsb), dim3(256), 0, ds->d_rows, ds->n, ds->d, cb->v.d4, (first % ds->n + off) % ds->n, c, xt));
-  CHK(LAUNCH(e, k_knn_dist<SCAN_S>, dim3((unsigned)nsb, (unsigned)((cb->v.ngroups + 3) / 4)), dim3(256), 0, cb->v, xt, c, b.ld, b.dist));
-  e->samples_searched += (uint64_t)c;
-  return 0;
-}
+// Step 2, b.dist <- every distance of c samples of the run from `off` on, is dist_chunk_stage (host_proto.inc) under
+// KID_RSLVQ_DIST; step 4, b.G <- the chains continued behind the run's first chunk, is sums_chunk_stage under KID_RSLVQ_SUMS.
 // Step 3 for those samples: b.Q <- the chunk's coefficients; cost_s, pown, correct_s at the run's sample numbers
 static int rslvq_posterior_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t off, int64_t c, float sigma2,
                                  const RslvqBufs &b) {
@@ -58,19 +49,10 @@ static int rslvq_posterior_stage(somhip_codebook *cb, somhip_dataset *ds, int64_
                       cb->v, b.dist, b.ld, c, off, cb->d_labels, ds->d_labels, ds->n, first % ds->n, 2.0 * (double)sigma2, b.Q, b.cost_s,
                       b.correct_s, b.pown);
 }
-// Step 4 for those samples: b.G <- the chains, from +0.0 for the run's first chunk and from b.G behind it
-static int rslvq_sums_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t off, int64_t c, const RslvqBufs &b) {
-  const dim3 grid((unsigned)cb->v.ngroups, (unsigned)((cb->v.d + RS_COLS - 1) / RS_COLS));
-  const int64_t f = (first % ds->n + off) % ds->n;
-  if (off > 0)
-    return LAUNCH_TIMED(cb->e, KID_RSLVQ_SUMS, k_rslvq_sums<true>, grid, dim3(256), 0, b.Q, b.ld, c, ds->d_rows, ds->n, ds->d, f, cb->v.n, b.G);
-  return LAUNCH_TIMED(cb->e, KID_RSLVQ_SUMS, k_rslvq_sums<false>, grid, dim3(256), 0, b.Q, b.ld, c, ds->d_rows, ds->n, ds->d, f, cb->v.n, b.G);
-}
 // Step 5: the rows from b.G
 static int rslvq_update_stage(somhip_codebook *cb, float alpha_t, float sigma2, int64_t n, const RslvqBufs &b) {
   const int64_t threads = cb->v.ngroups * cb->v.d4 * WAVE;
-  cb->prep_valid = cb->rowmajor_valid = false;
-  cb->bm_open = cb->gl_open = false;
+  rows_written(cb);
   const double den = (double)sigma2 * (double)n;
   return LAUNCH_TIMED(cb->e, KID_RSLVQ_UPDATE, k_rslvq_update, dim3((unsigned)((threads + RS_THREADS - 1) / RS_THREADS)), dim3(RS_THREADS), 0, cb->v,
                       b.G, (double)alpha_t / den);
@@ -79,9 +61,9 @@ static int rslvq_update_stage(somhip_codebook *cb, float alpha_t, float sigma2, 
 static int rslvq_walk(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, float sigma2, bool sums, const RslvqBufs &b) {
   for (int64_t off = 0; off < n; off += b.chunk) {
     const int64_t c = std::min(b.chunk, n - off);
-    CHK(rslvq_dist_stage(cb, ds, first, off, c, b));
+    CHK(dist_chunk_stage(cb, ds, first, off, c, KID_RSLVQ_DIST, b.ld, b.dist));
     CHK(rslvq_posterior_stage(cb, ds, first, off, c, sigma2, b));
-    if (sums) CHK(rslvq_sums_stage(cb, ds, first, off, c, b));
+    if (sums) CHK(sums_chunk_stage(cb, ds, first, off, c, KID_RSLVQ_SUMS, b.Q, b.ld, b.G));
   }
   return 0;
 }
@@ -93,11 +75,7 @@ static int rslvq_figures(somhip_codebook *cb, int64_t n, const RslvqBufs &b, dou
   if (cost) CHK(to_host(e, hc.data(), b.cost_s, hc.size()));
   if (correct) CHK(to_host(e, hr.data(), b.correct_s, hr.size()));
   HIPCHK(hipStreamSynchronize(e->stream));
-  if (cost) {
-    double chain = 0.0;
-    for (double c : hc) chain += c;
-    *cost = chain / (double)n;
-  }
+  if (cost) *cost = cost_figure(hc, (double)n);
   if (correct) {
     int64_t right = 0;
     for (int32_t r : hr) right += r;
@@ -124,18 +102,16 @@ extern "C" int somhip_rslvq_train(somhip_codebook *cb, somhip_dataset *ds, const
   const char *who = "somhip_rslvq_train";
   if (!p) return fail("%s: null parameters", who);
   if (!cb || !ds) return fail("%s: null handle", who);
-  if (p->epochs < 1) return fail("%s: epochs %lld < 1", who, (long long)p->epochs);
-  if (p->start_epoch < 0 || p->count < 0 || p->start_epoch + p->count > p->epochs)
-    return fail("%s: epochs [%lld, %lld) outside [0, %lld)", who, (long long)p->start_epoch, (long long)(p->start_epoch + p->count), (long long)p->epochs);
-  if (!(p->alpha >= 0.0f)) return fail("%s: alpha %g is negative or not a number", who, (double)p->alpha);
+  CHK(check_epochs(p->epochs, who));
+  CHK(check_epoch_window(p->start_epoch, p->count, p->epochs, who));
+  CHK(check_alpha(p->alpha, who));
   CHK(rslvq_check_sigma2(p->sigma2, who));
   CHK(glvq_check(cb, ds, p->first, p->n, who));
   somhip_engine *e = cb->e;
   RslvqBufs b;
   CHK(rslvq_bind(cb, p->n, rslvq_chunk(cb->v.ngroups), &b));
-  const float T = (float)p->epochs;
   for (int64_t t = p->start_epoch; t < p->start_epoch + p->count; t++) {
-    const float alpha_t = p->alpha * (float)(p->epochs - t) / T;        // LVQ_PAK's linear rate over epochs
+    const float alpha_t = linear_rate(p->alpha, p->epochs, t);
     CHK(rslvq_walk(cb, ds, p->first, p->n, p->sigma2, true, b));
     if (cost_out || correct_out)
       CHK(rslvq_figures(cb, p->n, b, cost_out ? cost_out + (t - p->start_epoch) : nullptr, correct_out ? correct_out + (t - p->start_epoch) : nullptr));
@@ -179,7 +155,7 @@ extern "C" int somhip_debug_rslvq_posterior(somhip_codebook *cb, somhip_dataset 
   CHK(rslvq_bind(cb, n, chunk, &b));
   for (int64_t off = 0; off < n; off += b.chunk) {
     const int64_t c = std::min(b.chunk, n - off);
-    CHK(rslvq_dist_stage(cb, ds, first, off, c, b));
+    CHK(dist_chunk_stage(cb, ds, first, off, c, KID_RSLVQ_DIST, b.ld, b.dist));
     CHK(rslvq_posterior_stage(cb, ds, first, off, c, sigma2, b));
     CHK(to_host_sync(e, q_out + (size_t)off * (size_t)b.ld, b.Q, (size_t)c * (size_t)b.ld));
   }
@@ -201,16 +177,13 @@ extern "C" int somhip_debug_rslvq_sums(somhip_codebook *cb, somhip_dataset *ds, 
   for (int64_t off = 0; off < n; off += b.chunk) {
     const int64_t c = std::min(b.chunk, n - off);
     CHK(to_device(e, b.Q, q_in + (size_t)off * (size_t)b.ld, (size_t)c * (size_t)b.ld));
-    CHK(rslvq_sums_stage(cb, ds, first, off, c, b));
+    CHK(sums_chunk_stage(cb, ds, first, off, c, KID_RSLVQ_SUMS, b.Q, b.ld, b.G));
     HIPCHK(hipStreamSynchronize(e->stream));                            // (the host array is read until the copy has run)
   }
   const size_t units = (size_t)cb->v.n, ldg = (size_t)cb->v.d + 1;
   std::vector<double> hg(units * ldg);
   CHK(to_host_sync(e, hg.data(), b.G, hg.size()));
-  for (size_t j = 0; j < units; j++) {
-    memcpy(G + j * (ldg - 1), hg.data() + j * ldg, sizeof(double) * (ldg - 1));
-    c_out[j] = hg[j * ldg + ldg - 1];
-  }
+  split_trailing(hg.data(), units, ldg - 1, G, c_out);
   return 0;
 } ABI_CATCH(somhip_debug_rslvq_sums)
 
@@ -226,10 +199,7 @@ extern "C" int somhip_debug_rslvq_update(somhip_codebook *cb, float alpha_t, flo
   CHK(rslvq_bind(cb, 0, 0, &b));
   const size_t units = (size_t)cb->v.n, ldg = (size_t)cb->v.d + 1;
   std::vector<double> hg(units * ldg);
-  for (size_t j = 0; j < units; j++) {
-    memcpy(hg.data() + j * ldg, G + j * (ldg - 1), sizeof(double) * (ldg - 1));
-    hg[j * ldg + ldg - 1] = c_in[j];
-  }
+  join_trailing(hg.data(), units, ldg - 1, G, c_in);
   CHK(to_device(e, b.G, hg.data(), hg.size()));
   CHK(rslvq_update_stage(cb, alpha_t, sigma2, n, b));
   HIPCHK(hipStreamSynchronize(e->stream));                              // (the host array is read until the copy has run)
@@ -239,10 +209,6 @@ extern "C" int somhip_debug_rslvq_update(somhip_codebook *cb, float alpha_t, flo
 // HIP-event totals of the stages since somhip_timing_reset, while somhip_timing_enable is on (ids of their own behind the
 // published table): [0] distances (the sample tiles and k_knn_dist), [1] posteriors, [2] sums, [3] update
 extern "C" int somhip_rslvq_timing(somhip_engine *e, int64_t launches[4], double total_ms[4]) try {
-  CHK(check_engine(e, "somhip_rslvq_timing"));
-  if (!launches || !total_ms) return fail("somhip_rslvq_timing: null output");
-  CHK(timing_flush(e));
   const int kid[4] = {KID_RSLVQ_DIST, KID_RSLVQ_POSTERIOR, KID_RSLVQ_SUMS, KID_RSLVQ_UPDATE};
-  for (int i = 0; i < 4; i++) { launches[i] = e->launches[kid[i]]; total_ms[i] = e->total_ms[kid[i]]; }
-  return 0;
+  return stage_timing(e, "somhip_rslvq_timing", kid, 4, launches, total_ms);
 } ABI_CATCH(somhip_rslvq_timing)

@@ -814,12 +814,8 @@ static int knn_chunk_keys(somhip_codebook *cb, somhip_dataset *ds, int64_t first
 // HIP-event totals of the wide route's two stages since somhip_timing_reset, while somhip_timing_enable is on (timed under
 // ids of their own, like the map-set kernels): [0] the distance stage (k_knn_dist / k_knn_dist_masked), [1] k_knn_select
 extern "C" int somhip_knn_timing(somhip_engine *e, int64_t launches[2], double total_ms[2]) try {
-  CHK(check_engine(e, "somhip_knn_timing"));
-  if (!launches || !total_ms) return fail("somhip_knn_timing: null output");
-  CHK(timing_flush(e));
-  launches[0] = e->launches[KID_KNN_DIST]; launches[1] = e->launches[KID_KNN_SELECT];
-  total_ms[0] = e->total_ms[KID_KNN_DIST]; total_ms[1] = e->total_ms[KID_KNN_SELECT];
-  return 0;
+  const int kid[2] = {KID_KNN_DIST, KID_KNN_SELECT};
+  return stage_timing(e, "somhip_knn_timing", kid, 2, launches, total_ms);
 } ABI_CATCH(somhip_knn_timing)
 
 // find_winner_euc / find_winner_knn over a run of samples (include/somhip.h); masked data sets take K1m / K1mk for
@@ -896,12 +892,8 @@ extern "C" int somhip_knn_vote(somhip_codebook *cb, somhip_dataset *ds, int64_t 
 // HIP-event total of k_knn_vote since somhip_timing_reset, while somhip_timing_enable is on (an id of its own behind the
 // published table, like the wide route's stages)
 extern "C" int somhip_knn_vote_timing(somhip_engine *e, int64_t *launches, double *total_ms) try {
-  CHK(check_engine(e, "somhip_knn_vote_timing"));
-  if (!launches || !total_ms) return fail("somhip_knn_vote_timing: null output");
-  CHK(timing_flush(e));
-  *launches = e->launches[KID_KNN_VOTE];
-  *total_ms = e->total_ms[KID_KNN_VOTE];
-  return 0;
+  const int kid[1] = {KID_KNN_VOTE};
+  return stage_timing(e, "somhip_knn_vote_timing", kid, 1, launches, total_ms);
 } ABI_CATCH(somhip_knn_vote_timing)
 
 // lininit's data passes (find_eigenvectors, som_rout.c:211-289): per-component sums / counts over the

@@ -91,8 +91,7 @@ static void som_trace(const StepScalars *sc, const uint64_t *keys, int64_t c, in
 static int som_train_online(somhip_codebook *cb, somhip_dataset *ds, const somhip_som_params *p,
                             int32_t *trace_index, float *trace_diff) {
   somhip_engine *e = cb->e;
-  cb->prep_valid = cb->rowmajor_valid = false;
-  cb->bm_open = cb->gl_open = false;
+  rows_written(cb);
   const int64_t CH = ONLINE_CHUNK;
   const bool G = cb->v.neigh == SOMHIP_NEIGH_GAUSSIAN, M = ds->d_mask != nullptr;
   uint64_t *slot; StepScalars *sc; int64_t *rowidx;
@@ -372,8 +371,7 @@ static int update_order_apply(somhip_engine *e, const somhip_codebook *cb, const
 static int som_update_planned(somhip_codebook *cb, somhip_dataset *ds, const UpdatePlan &p, int64_t data_first, int64_t count,
                               const uint64_t *d_keys, const StepScalars *d_sc) {
   somhip_engine *e = cb->e;
-  cb->prep_valid = cb->rowmajor_valid = false;
-  cb->bm_open = cb->gl_open = false;
+  rows_written(cb);
   UpdateBufs b; CHK(bind_update(e, cb, count, &b));
   if (p.decode) CHK(update_decode(e, cb, 0, count, d_keys, d_sc, b));
   CHK(update_members(e, cb, ds, p, data_first, count, d_keys, d_sc, b));
@@ -450,8 +448,7 @@ static int som_lazy_run(somhip_codebook *cb, somhip_dataset *ds, const UpdatePla
     if (p.decode) CHK(update_decode(e, cb, 0, head, kv, d_sc, b));
     CHK(update_members(e, cb, ds, p, row0, count, kv, d_sc, b));
   }
-  cb->prep_valid = cb->rowmajor_valid = false;
-  cb->bm_open = cb->gl_open = false;
+  rows_written(cb);
   return update_order_apply(e, cb, ds, p, row0, count, d_sc, b, !redo);
 }
 // the plan som_update_run makes for a run (somhip.h): the same checks as somhip_som_batch_update, host arithmetic only

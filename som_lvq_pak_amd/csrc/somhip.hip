@@ -325,6 +325,15 @@ static int timing_flush(somhip_engine *e) {
   e->pending.clear();
   return 0;
 }
+// What every somhip_*_timing entry point answers with: the launches and the HIP-event milliseconds of `count` kernel ids
+// since somhip_timing_reset, in the order the entry point's header gives
+static int stage_timing(somhip_engine *e, const char *who, const int *kid, int count, int64_t *launches, double *total_ms) {
+  CHK(check_engine(e, who));
+  if (!launches || !total_ms) return fail("%s: null output", who);
+  CHK(timing_flush(e));
+  for (int i = 0; i < count; i++) { launches[i] = e->launches[kid[i]]; total_ms[i] = e->total_ms[kid[i]]; }
+  return 0;
+}
 
 struct LaunchTimer {   // HIP events on the engine's own stream around one launch (kid < 0: not timed)
   somhip_engine *e;
@@ -538,7 +547,7 @@ struct somhip_codebook {
   bool cnmax_clean = false;        // ... which is known to be zero
   uint4 *d_chi = nullptr, *d_clo = nullptr;   // bf16 hi/lo tiles [ngroups][d8][64] (bf16 pre-filter)
   bool prep_valid = false;         // d_cn / d_chi / d_clo describe the rows as they are now (set by a full k_prep_codes_bf16,
-                                   // kept by the LVQ engine when it re-splits exactly the rows it corrected, cleared by every other writer)
+                                   // kept by the LVQ engine when it re-splits exactly the rows it corrected, cleared by every other writer: rows_written)
   float *d_rowmajor = nullptr;     // [ngroups*64][d] fp32 rows, row-major: what the exact re-rank of single rows gathers from (a row is
                                    // 4 d contiguous bytes here, 16 bytes per KiB in the tiles); written by the full k_prep_codes_bf16
   bool rowmajor_valid = false;     // ... set only together with prep_valid; cleared with it by every writer, and alone by a partial re-split (LVQ)
@@ -581,10 +590,18 @@ static bool is_shard(const somhip_codebook *cb) { return cb->v.row_offset != 0 |
 // every component of this row is masked: it has no distance to anything, so no winner
 static bool sample_is_empty(const somhip_dataset *ds, int64_t row) { return !ds->all_masked.empty() && ds->all_masked[(size_t)row]; }
 
+// The rows of this codebook move, or the caller is about to move them: every open accumulation over them is over (the
+// state stays allocated; _begin opens it again).  An owner that updates from its own state re-opens it behind the call.
+static void close_accumulations(somhip_codebook *cb) { cb->bm_open = false; cb->gl_open = false; }
+// What every writer of the rows says, in one place: the prepared copies no longer describe them, and see above
+static void rows_written(somhip_codebook *cb) {
+  cb->prep_valid = cb->rowmajor_valid = false;
+  close_accumulations(cb);
+}
+
 static int upload_rows(somhip_codebook *cb, const float *rows) {
   somhip_engine *e = cb->e;
-  cb->prep_valid = cb->rowmajor_valid = false;
-  cb->bm_open = cb->gl_open = false;
+  rows_written(cb);
   float *stage;
   const size_t count = (size_t)cb->v.n * cb->v.d;
   CHK(scratch(e, SLOT_STAGE, count, &stage));
@@ -860,6 +877,7 @@ extern "C" void somhip_dataset_destroy(somhip_dataset *ds) try {
 #include "host_planes.inc"
 #include "host_conn.inc"
 #include "host_quality.inc"
+#include "host_proto.inc"
 #include "host_batchmap.inc"
 #include "host_glvq.inc"
 #include "host_ngas.inc"

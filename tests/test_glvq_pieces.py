@@ -29,7 +29,7 @@ HEXA, BUBBLE = 3, 1                                                      # inclu
 NEW = ("somhip_glvq_begin", "somhip_glvq_accumulate", "somhip_glvq_finish", "somhip_glvq_end", "somhip_glvq_state",
        "somhip_glvq_train_ranks")
 TOOL_TIMEOUT = 120
-CHUNK = 16384                                                            # GLVQ_CHUNK of host_glvq.inc: samples of a class-wise scan launch
+CHUNK = 16384                                                            # GLVQ_CHUNK of host_proto.inc: samples of a class-wise scan launch
 N = 16500
 ALPHA = 30.0
 

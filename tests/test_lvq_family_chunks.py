@@ -1,9 +1,9 @@
 """The GLVQ family (K9 glvq, K11 grlvq, K12 gmlvq) on runs longer than one launch of the class-wise scan.
 
-GLVQ_CHUNK = 16384 (csrc/host_glvq.inc:16) cuts the scan in three loops written out by hand -- glvq_scan_class,
-grlvq_search_stage (host_grlvq.inc) and gmlvq_search_stage (host_gmlvq.inc) -- and the list route is cut again, at 4096
-samples, by knn_chunk_keys (csrc/host_scan.inc:762), after which k_glvq_pick adds the chunk's offset and the remainder goes
-through glvq_scan_class with its own list.  A wrong offset in any of them reads in bounds and returns plausible winners, so
+GLVQ_CHUNK = 16384 (csrc/host_proto.inc) cuts the scan in one loop, class_scan_walk, which glvq_search_stage,
+grlvq_search_stage (host_grlvq.inc) and gmlvq_search_stage (host_gmlvq.inc) walk with their own tiles -- and the list route
+is cut again, at 4096 samples, by knn_chunk_keys (csrc/host_scan.inc), after which k_glvq_pick adds the chunk's offset and the
+remainder goes through class_scan_walk with its own list.  A wrong offset in any of them reads in bounds and returns plausible winners, so
 the runs here cross every one of those edges over a data set of 5000 rows whose labels and values differ between run
 sample s and run sample s - 16384 for every s (test_samples_a_chunk_apart_differ), and the winners and distance bits are
 compared with the replays.  Neither constant is exposed by the library: test_the_chunk_sizes_are_the_sources checks them
@@ -24,7 +24,7 @@ from test_glvq import built                                            # noqa: F
 f32, f64 = np.float32, np.float64
 bits32, bits64 = TG.bits32, TG.bits64
 
-GLVQ_CHUNK = 16384                                                     # csrc/host_glvq.inc:16
+GLVQ_CHUNK = 16384                                                     # csrc/host_proto.inc
 KNN_CHUNK = 4096                                                       # csrc/host_scan.inc:762, knn_chunk_keys at knn <= 8
 N_ROWS = 5000                                                          # data rows: every long run wraps several times
 CLASSES = 4
@@ -97,12 +97,15 @@ def same_search(got, want, what):
 # ------------------------------------------------------------------------------------------------ without a GPU
 def test_the_chunk_sizes_are_the_sources():
     src = os.path.join(ROOT, "som_lvq_pak_amd", "csrc")
-    assert int(re.search(r"constexpr int64_t GLVQ_CHUNK = (\d+);", open(os.path.join(src, "host_glvq.inc")).read()).group(1)) == GLVQ_CHUNK
+    proto = open(os.path.join(src, "host_proto.inc")).read()
+    assert int(re.search(r"constexpr int64_t GLVQ_CHUNK = (\d+);", proto).group(1)) == GLVQ_CHUNK
     scan = open(os.path.join(src, "host_scan.inc")).read()
     body = scan[scan.index("static int knn_chunk_keys("):]
     assert int(re.search(r"const int64_t CH = std::min<int64_t>\((\d+), count\);", body).group(1)) == KNN_CHUNK
-    for name in ("host_grlvq.inc", "host_gmlvq.inc"):                   # the two other loops take the same constant
-        assert "off += GLVQ_CHUNK" in open(os.path.join(src, name)).read(), name
+    assert proto.count("off += GLVQ_CHUNK") == 1                        # one loop, class_scan_walk, and all three searches walk it
+    for name in ("host_glvq.inc", "host_grlvq.inc", "host_gmlvq.inc"):
+        text = open(os.path.join(src, name)).read()
+        assert "class_scan_walk(" in text and "GLVQ_CHUNK" not in text, name
     assert GLVQ_CHUNK % N_ROWS != 0 and GLVQ_CHUNK % 32 == 0
 
 

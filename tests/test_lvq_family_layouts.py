@@ -9,7 +9,7 @@ test_ngas do on codebooks without a lattice, and whole runs also with the same r
 
 The shapes are the smallest at which a code path differs: 16x8 (two row groups, k_scan_class<32, 1>; the smallest map that
 permutes), 24x16 (three patches per row of patches: the patch row matters), 32x32 (16 row groups: the first shape on
-k_scan_class<32, 4>, GLVQ_R = 4 in kernels/glvq.hpp and `wide` in host_glvq.inc's glvq_scan_class) and 40x40 (25 groups:
+k_scan_class<32, 4>, GLVQ_R = 4 in kernels/glvq.hpp and `wide` in host_proto.inc's class_scan_walk) and 40x40 (25 groups:
 the last wave of the wide kernel holds one live group of four).  No new tolerance: the sigmoid case uses the bounds of
 DESIGN.md K9 and K12 as test_glvq and test_gmlvq do.  The runs across the scan chunks are in test_lvq_family_chunks.py."""
 import copy
@@ -117,12 +117,15 @@ def metrics(k):
 
 # ------------------------------------------------------------------------------------------------ without a GPU
 def test_the_wide_search_starts_where_the_shapes_say():
-    """GLVQ_R and the three `wide` switches are not exposed: read from the source, so the shapes have to follow a change"""
+    """GLVQ_R and the `wide` switch of the three searches are not exposed: read from the source, so the shapes have to follow a change"""
     src = os.path.join(TG.ROOT, "som_lvq_pak_amd", "csrc")
     m = re.search(r"constexpr int GLVQ_R = (\d+);", open(os.path.join(src, "kernels", "glvq.hpp")).read())
     assert m and 4 * int(m.group(1)) == WIDE_GROUPS
+    assert open(os.path.join(src, "host_proto.inc")).read().count("const bool wide = v.ngroups >= 4 * GLVQ_R;") == 1
     for name, view in (("host_glvq.inc", "cb->v"), ("host_grlvq.inc", "cb->v"), ("host_gmlvq.inc", "b.pv")):
-        assert "const bool wide = %s.ngroups >= 4 * GLVQ_R;" % view in open(os.path.join(src, name)).read(), name
+        text = open(os.path.join(src, name)).read()                        # v: the view each search hands to the one walk
+        assert "class_scan_walk(cb->e, %s, " % view in text or "class_scan_walk(e, %s, " % view in text, name
+        assert not re.search(r"\bwide\b", text), name
 
 
 @pytest.mark.parametrize("xdim,ydim,dim", MAPS)
