@@ -17,7 +17,7 @@ all: lib oracle tools
 lib: $(LIB)
 KHDR      = $(CSRC)/kernels.hpp $(wildcard $(CSRC)/kernels/*.hpp) $(wildcard $(CSRC)/host_*.inc)
 # librccl.so is opened at run time by the first somhip_comm_create (host_comm.inc), never linked: -ldl only
-$(LIB): $(CSRC)/somhip.hip $(CSRC)/umat.hip $(CSRC)/planes.hip $(KHDR) $(CSRC)/schedule.hpp include/somhip.h include/somhip_rslvq.h include/somhip_glvq_pieces.h include/somhip_ng_dense.h Makefile
+$(LIB): $(CSRC)/somhip.hip $(CSRC)/umat.hip $(CSRC)/planes.hip $(KHDR) $(CSRC)/schedule.hpp include/somhip.h include/somhip_rslvq.h include/somhip_glvq_pieces.h include/somhip_ng_dense.h include/somhip_batchmap_missing.h Makefile
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(CSRC)/somhip.hip $(CSRC)/umat.hip $(CSRC)/planes.hip -ldl
 
 # device ISA of the kernels, for the no-FMA check (tests/test_build.py) and for reading

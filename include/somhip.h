@@ -1074,4 +1074,7 @@ int  somhip_timing_get(somhip_engine *e, int kernel, int64_t *launches, double *
 #include "somhip_glvq_pieces.h"
 /* dense batch neural gas (K10d): somhip_ng_train_dense, neural gas over every rank of up to SOMHIP_NG_DENSE_MAX rows, likewise */
 #include "somhip_ng_dense.h"
+/* the batch map over data with missing values (K8m): somhip_som_batchmap_missing, its two stages and its five calls over
+ * data in pieces, likewise */
+#include "somhip_batchmap_missing.h"
 #endif /* SOMHIP_H */

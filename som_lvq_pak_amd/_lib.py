@@ -278,6 +278,18 @@ NG_DENSE_SIGNATURES = {
     "somhip_ng_dense_timing": (C.c_int, [C.c_void_p, c_i64_p, c_double_p]),
 }
 
+# ... and exactly the symbols include/somhip_batchmap_missing.h declares (the batch map over data with missing values, K8m)
+BATCHMAP_MISSING_SIGNATURES = {
+    "somhip_som_batchmap_missing": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(BatchmapParams), c_float_p]),
+    "somhip_debug_batchmap_missing_sums": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, c_double_p, c_double_p]),
+    "somhip_debug_batchmap_missing_combine": (C.c_int, [C.c_void_p, C.c_float, c_double_p, c_double_p]),
+    "somhip_batchmap_missing_begin": (C.c_int, [C.c_void_p]),
+    "somhip_batchmap_missing_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int]),
+    "somhip_batchmap_missing_finish": (C.c_int, [C.c_void_p, C.c_float, C.c_int64, C.c_int64, c_float_p]),
+    "somhip_batchmap_missing_end": (C.c_int, [C.c_void_p]),
+    "somhip_batchmap_missing_state": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), c_i64_p]),
+}
+
 _lib = None
 
 
@@ -290,7 +302,7 @@ def load():
                                "g.build()'); there is no CPU fallback" % LIB_PATH)
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(RSLVQ_SIGNATURES.items()) + list(GLVQ_PIECES_SIGNATURES.items()) + \
-                list(NG_DENSE_SIGNATURES.items()):
+                list(NG_DENSE_SIGNATURES.items()) + list(BATCHMAP_MISSING_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

@@ -2,12 +2,19 @@
 // ordered fp64 sums (stage 1) and the neighbourhood combine on the fp64 MFMA (stage 2); the same epoch over data in pieces
 // (somhip_batchmap_begin / _accumulate / _finish: the sums' chains continued from piece to piece) and over the row blocks
 // of G ranks (somhip_som_batchmap_ranks)
+// K8m, the same over data with missing values (somhip_som_batchmap_missing, somhip_batchmap_missing_*): the state holds a
+// count per component, [S | C], the sums skip masked components and the combine divides per component.  Every entry
+// point of either form is one body here, told which form it serves.
 // (included by somhip.hip behind host_proto.inc: one translation unit, the trainers' shared checks)
 #include <rocprim/device/device_radix_sort.hpp>
 
 // The device arrays of a batch-map call.  SLOT_BATCHMAP, per unit: [S: units x (dim + 1) doubles][the gaussian table]
 // [hits][starts: units + 1].  SLOT_BATCHMAP_LIST, per sample: [win][idx][the sorted winners][list][the sort's own room].
+// The two forms of S, stated here once.  Plain: [S | hits], a unit's dim sums and behind them its one count.  Missing:
+// [S | C] as units x 2 dim doubles, C following S per unit -- unit u's sums at [u * 2 dim, + dim), the counts of the same
+// components at [u * 2 dim + dim, + dim).  A continued state is S in the same form, then the 16-byte tail.
 struct BatchmapBufs {
+  bool missing = false;               // the form of S
   double *S = nullptr, *table = nullptr;
   uint32_t *hits = nullptr, *starts = nullptr, *win = nullptr, *idx = nullptr, *win_sorted = nullptr, *list = nullptr;
   void *sort_tmp = nullptr;
@@ -19,10 +26,12 @@ static size_t batchmap_table_len(const somhip_codebook *cb) {
 }
 // n: the samples of a sums stage, 0 where only the combine runs.  state (or null): S is the codebook's own continued
 // accumulation, not engine scratch, and the slot holds the rest only.
-static int batchmap_bind(somhip_codebook *cb, int64_t n, BatchmapBufs *b, double *state = nullptr) {
+static size_t batchmap_unit_doubles(const somhip_codebook *cb, bool missing) { return missing ? 2 * (size_t)cb->v.d : (size_t)cb->v.d + 1; }
+static int batchmap_bind(somhip_codebook *cb, int64_t n, BatchmapBufs *b, double *state = nullptr, bool missing = false) {
   somhip_engine *e = cb->e;
-  const size_t units = (size_t)cb->v.n, ns = (size_t)n, s_len = state ? 0 : units * (size_t)(cb->v.d + 1), t_len = batchmap_table_len(cb);
+  const size_t units = (size_t)cb->v.n, ns = (size_t)n, s_len = state ? 0 : units * batchmap_unit_doubles(cb, missing), t_len = batchmap_table_len(cb);
   void *p;
+  b->missing = missing;
   CHK(engine_scratch(e, SLOT_BATCHMAP, sizeof(double) * (s_len + t_len) + sizeof(uint32_t) * (2 * units + 1), &p));
   b->S = state ? state : (double *)p;
   b->table = (double *)p + s_len;
@@ -86,10 +95,19 @@ static int batchmap_group_stage(somhip_codebook *cb, somhip_dataset *ds, int64_t
   if (q) *q = chain;
   return 0;
 }
-// ... and the sums half: b.S <- [S | hits] from the lists.  cont: the chains and counts go on from what b.S holds.
+// ... and the sums half: b.S <- [S | hits], or [S | C] under the data's mask, from the lists.  cont: the chains and counts
+// go on from what b.S holds.
 static int batchmap_sums_launch(somhip_codebook *cb, somhip_dataset *ds, int64_t first, const BatchmapBufs &b, bool cont,
                                 int kid = KID_BATCHMAP_SUMS) {
   somhip_engine *e = cb->e;
+  if (b.missing) {
+    const dim3 mgrid((unsigned)cb->v.n, (unsigned)((cb->v.d + BM_SUM_DIMS - 1) / BM_SUM_DIMS));
+    if (cont)
+      return LAUNCH_TIMED(e, kid, k_batchmap_sums_missing<true>, mgrid, dim3(BM_SUM_DIMS), 0, ds->d_rows, ds->d_mask, ds->n, ds->d, first % ds->n,
+                          b.list, b.starts, b.S);
+    return LAUNCH_TIMED(e, kid, k_batchmap_sums_missing<false>, mgrid, dim3(BM_SUM_DIMS), 0, ds->d_rows, ds->d_mask, ds->n, ds->d, first % ds->n,
+                        b.list, b.starts, b.S);
+  }
   const dim3 grid((unsigned)cb->v.n, (unsigned)((cb->v.d + 1 + BM_SUM_DIMS - 1) / BM_SUM_DIMS));
   if (cont)
     return LAUNCH_TIMED(e, kid, k_batchmap_sums<true>, grid, dim3(BM_SUM_DIMS), 0, ds->d_rows, ds->n, ds->d, first % ds->n, b.list,
@@ -112,13 +130,19 @@ static int batchmap_combine_stage(somhip_codebook *cb, float r, const BatchmapBu
   if (groups < 0) groups = cb->v.ngroups;
   if (groups == 0) return 0;
   const dim3 grid((unsigned)groups, (unsigned)((cb->v.d + BM_COLS - 1) / BM_COLS));
+  const dim3 mgrid((unsigned)groups, (unsigned)((cb->v.d + BMM_COLS - 1) / BMM_COLS));
   rows_written(cb);                                                     // (the caller whose own state this is re-opens it)
   if (gauss) {
     const size_t t_len = batchmap_table_len(cb);
     CHK(LAUNCH_TIMED(e, KID_BATCHMAP_COMBINE, k_batchmap_gauss_table, dim3((unsigned)((t_len + BM_THREADS - 1) / BM_THREADS)), dim3(BM_THREADS), 0,
         cb->v.topol, cb->v.xdim, cb->ydim, r, b.table));
+    if (b.missing)
+      return LAUNCH_TIMED(e, KID_BATCHMAP_COMBINE, k_batchmap_combine_missing<true>, mgrid, dim3(256), 0, cb->v, cb->ydim, b.S, r, small_map, b.table, g0);
     return LAUNCH_TIMED(e, KID_BATCHMAP_COMBINE, k_batchmap_combine<true>, grid, dim3(256), 0, cb->v, cb->ydim, b.S, r, small_map, b.table, g0);
   }
+  if (b.missing)
+    return LAUNCH_TIMED(e, KID_BATCHMAP_COMBINE, k_batchmap_combine_missing<false>, mgrid, dim3(256), 0, cb->v, cb->ydim, b.S, bubble_threshold(r),
+                        small_map, nullptr, g0);
   return LAUNCH_TIMED(e, KID_BATCHMAP_COMBINE, k_batchmap_combine<false>, grid, dim3(256), 0, cb->v, cb->ydim, b.S, bubble_threshold(r), small_map,
                       nullptr, g0);
 }
@@ -131,27 +155,29 @@ static int batchmap_check_codebook(const somhip_codebook *cb, const char *who) {
   if (cb->v.neigh != SOMHIP_NEIGH_BUBBLE && cb->v.neigh != SOMHIP_NEIGH_GAUSSIAN) return fail("%s: unknown neighbourhood %d", who, cb->v.neigh);
   return 0;
 }
-static int batchmap_check_data(const somhip_dataset *ds, int64_t first, int64_t n, const char *who) {
-  if (ds->d_mask) return fail("%s: data with masked components (x) is not supported", who);
+static int batchmap_check_data(const somhip_dataset *ds, int64_t first, int64_t n, const char *who, bool masks_ok = false) {
+  if (ds->d_mask && !masks_ok) return fail("%s: data with masked components (x) is not supported", who);
   if (first < 0) return fail("%s: first row %lld < 0", who, (long long)first);
   if (n <= 0) return fail("%s: n %lld <= 0", who, (long long)n);
   if (n >= (int64_t)1 << 32) return fail("%s: n %lld does not fit the 32-bit hit counts", who, (long long)n);
   return 0;
 }
 
-extern "C" int somhip_som_batchmap(somhip_codebook *cb, somhip_dataset *ds, const somhip_batchmap_params *p, float *qerror_out) try {
-  CHK(check_pair(cb, ds, "somhip_som_batchmap"));
-  if (!p) return fail("somhip_som_batchmap: null parameters");
-  CHK(batchmap_check_codebook(cb, "somhip_som_batchmap"));
-  CHK(batchmap_check_data(ds, p->first, p->n, "somhip_som_batchmap"));
-  CHK(check_epochs(p->epochs, "somhip_som_batchmap"));
-  if (!(p->radius >= 1.0f)) return fail("somhip_som_batchmap: radius %g < 1", (double)p->radius);
-  CHK(check_epoch_window(p->start_epoch, p->count, p->epochs, "somhip_som_batchmap"));
+// The epochs of either form (missing: K8m, masks taken)
+static int batchmap_train(somhip_codebook *cb, somhip_dataset *ds, const somhip_batchmap_params *p, float *qerror_out, bool missing,
+                          const char *who) {
+  CHK(check_pair(cb, ds, who));
+  if (!p) return fail("%s: null parameters", who);
+  CHK(batchmap_check_codebook(cb, who));
+  CHK(batchmap_check_data(ds, p->first, p->n, who, missing));
+  CHK(check_epochs(p->epochs, who));
+  if (!(p->radius >= 1.0f)) return fail("%s: radius %g < 1", who, (double)p->radius);
+  CHK(check_epoch_window(p->start_epoch, p->count, p->epochs, who));
   somhip_engine *e = cb->e;
   HIPCHK(hipSetDevice(e->device));
   close_accumulations(cb);                                              // (the rows move: an open accumulation is over)
   BatchmapBufs b;
-  CHK(batchmap_bind(cb, p->n, &b));
+  CHK(batchmap_bind(cb, p->n, &b, nullptr, missing));
   for (int64_t t = p->start_epoch; t < p->start_epoch + p->count; t++) {
     const float r = 1.0f + linear_rate(p->radius - 1.0f, p->epochs, t);       // som_rout.c:615 over epochs
     CHK(batchmap_sums_stage(cb, ds, p->first, p->n, b, qerror_out ? qerror_out + (t - p->start_epoch) : nullptr));
@@ -159,7 +185,13 @@ extern "C" int somhip_som_batchmap(somhip_codebook *cb, somhip_dataset *ds, cons
   }
   HIPCHK(hipStreamSynchronize(e->stream));
   return 0;
+}
+extern "C" int somhip_som_batchmap(somhip_codebook *cb, somhip_dataset *ds, const somhip_batchmap_params *p, float *qerror_out) try {
+  return batchmap_train(cb, ds, p, qerror_out, false, "somhip_som_batchmap");
 } ABI_CATCH(somhip_som_batchmap)
+extern "C" int somhip_som_batchmap_missing(somhip_codebook *cb, somhip_dataset *ds, const somhip_batchmap_params *p, float *qerror_out) try {
+  return batchmap_train(cb, ds, p, qerror_out, true, "somhip_som_batchmap_missing");
+} ABI_CATCH(somhip_som_batchmap_missing)
 
 extern "C" int somhip_debug_batchmap_sums(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, uint32_t *hits, double *sums) try {
   CHK(check_pair(cb, ds, "somhip_debug_batchmap_sums"));
@@ -200,6 +232,49 @@ extern "C" int somhip_debug_batchmap_combine(somhip_codebook *cb, float r, const
   return 0;
 } ABI_CATCH(somhip_debug_batchmap_combine)
 
+// ... and the two stages of the missing form: sums and counts are [units][dim] each on the host, interleaved per unit in S
+extern "C" int somhip_debug_batchmap_missing_sums(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, double *sums,
+                                                  double *counts) try {
+  CHK(check_pair(cb, ds, "somhip_debug_batchmap_missing_sums"));
+  if (!sums || !counts) return fail("somhip_debug_batchmap_missing_sums: null output");
+  CHK(batchmap_check_codebook(cb, "somhip_debug_batchmap_missing_sums"));
+  CHK(batchmap_check_data(ds, first, n, "somhip_debug_batchmap_missing_sums", true));
+  somhip_engine *e = cb->e;
+  HIPCHK(hipSetDevice(e->device));
+  BatchmapBufs b;
+  CHK(batchmap_bind(cb, n, &b, nullptr, true));
+  CHK(batchmap_sums_stage(cb, ds, first, n, b, nullptr));
+  const size_t units = (size_t)cb->v.n, d = (size_t)cb->v.d;
+  std::vector<double> hs(units * 2 * d);
+  CHK(to_host_sync(e, hs.data(), b.S, hs.size()));
+  for (size_t u = 0; u < units; u++) {
+    memcpy(sums + u * d, hs.data() + u * 2 * d, sizeof(double) * d);
+    memcpy(counts + u * d, hs.data() + u * 2 * d + d, sizeof(double) * d);
+  }
+  return 0;
+} ABI_CATCH(somhip_debug_batchmap_missing_sums)
+
+extern "C" int somhip_debug_batchmap_missing_combine(somhip_codebook *cb, float r, const double *sums, const double *counts) try {
+  CHK(check_codebook(cb, sums && counts, "somhip_debug_batchmap_missing_combine"));
+  CHK(batchmap_check_codebook(cb, "somhip_debug_batchmap_missing_combine"));
+  if (!(r >= 0.0f)) return fail("somhip_debug_batchmap_missing_combine: radius %g < 0", (double)r);
+  somhip_engine *e = cb->e;
+  HIPCHK(hipSetDevice(e->device));
+  close_accumulations(cb);
+  BatchmapBufs b;
+  CHK(batchmap_bind(cb, 0, &b, nullptr, true));
+  const size_t units = (size_t)cb->v.n, d = (size_t)cb->v.d;
+  std::vector<double> hs(units * 2 * d);
+  for (size_t u = 0; u < units; u++) {
+    memcpy(hs.data() + u * 2 * d, sums + u * d, sizeof(double) * d);
+    memcpy(hs.data() + u * 2 * d + d, counts + u * d, sizeof(double) * d);
+  }
+  CHK(to_device(e, b.S, hs.data(), hs.size()));
+  CHK(batchmap_combine_stage(cb, r, b));
+  HIPCHK(hipStreamSynchronize(e->stream));                              // (hs is read until the copy has run)
+  return 0;
+} ABI_CATCH(somhip_debug_batchmap_missing_combine)
+
 // HIP-event totals of the batch map's stages since somhip_timing_reset, while somhip_timing_enable is on (ids of their own
 // behind the published table): [0] group (winners pass, scan, sort), [1] k_batchmap_sums, [2] the combine (with the
 // gaussian table)
@@ -216,22 +291,35 @@ extern "C" int somhip_batchmap_timing(somhip_engine *e, int64_t launches[3], dou
 // ---------------------------------------------------------------------------------
 struct BatchmapTail { float q; uint32_t unused; uint64_t samples; };
 static_assert(sizeof(BatchmapTail) == 16, "the tail of the batch map's state is two words of 8 bytes");
-static size_t batchmap_state_doubles(const somhip_codebook *cb) { return (size_t)cb->v.n * (size_t)(cb->v.d + 1); }
+// (the form is that of the state the codebook holds: cb->bm_missing)
+static size_t batchmap_state_doubles(const somhip_codebook *cb) { return (size_t)cb->v.n * batchmap_unit_doubles(cb, cb->bm_missing); }
 static size_t batchmap_state_bytes(const somhip_codebook *cb) { return sizeof(double) * batchmap_state_doubles(cb) + sizeof(BatchmapTail); }
 static BatchmapTail *batchmap_tail(const somhip_codebook *cb) { return reinterpret_cast<BatchmapTail *>(cb->bm_state + batchmap_state_doubles(cb)); }
 
-// opens the state as all +0.0 (bits of zero throughout, the tail included)
-static int batchmap_state_open(somhip_codebook *cb) {
+// opens the state as all +0.0 (bits of zero throughout, the tail included).  A codebook holds one state, of one form: a
+// state of the other form is given up here, so opening one form closes the other.
+static int batchmap_state_open(somhip_codebook *cb, bool missing = false) {
   somhip_engine *e = cb->e;
+  if (cb->bm_state && cb->bm_missing != missing) {
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipFree(cb->bm_state));
+    cb->bm_state = nullptr;                                             // (open and moved are set below)
+  }
+  cb->bm_missing = missing;
   if (!cb->bm_state) HIPCHK(hipMalloc((void **)&cb->bm_state, batchmap_state_bytes(cb)));
   HIPCHK(hipMemsetAsync(cb->bm_state, 0, batchmap_state_bytes(cb), e->stream));
   cb->bm_open = true;
   cb->bm_moved = false;
   return 0;
 }
-static int batchmap_check_open(const somhip_codebook *cb, const char *who) {
-  return cb->bm_open && cb->bm_state ? 0 : fail("%s: no accumulation is open on this codebook (somhip_batchmap_begin first; a call that writes "
-                                                 "the rows closes it)", who);
+static int batchmap_check_open(const somhip_codebook *cb, const char *who, bool missing = false) {
+  if (!(cb->bm_open && cb->bm_state))
+    return fail("%s: no accumulation is open on this codebook (%s first; a call that writes the rows closes it)", who,
+                missing ? "somhip_batchmap_missing_begin" : "somhip_batchmap_begin");
+  if (cb->bm_missing != missing)
+    return fail("%s: the open accumulation has the other form, %s (it is continued by the somhip_batchmap_%s* calls)", who,
+                cb->bm_missing ? "[S | C] of somhip_batchmap_missing_begin" : "[S | hits] of somhip_batchmap_begin", cb->bm_missing ? "missing_" : "");
+  return 0;
 }
 // The tail as the pieces so far left it, and the refusal of a piece of n samples that would take the total to 2^32: a copy
 // and a comparison, before anything is bound or launched.
@@ -256,42 +344,50 @@ static int batchmap_take_piece(somhip_codebook *cb, somhip_dataset *ds, int64_t 
   return 0;
 }
 
-extern "C" int somhip_batchmap_begin(somhip_codebook *cb) try {
-  CHK(check_codebook(cb, true, "somhip_batchmap_begin"));
-  CHK(batchmap_check_codebook(cb, "somhip_batchmap_begin"));
+// The five calls of either form (missing: the state is [S | C] and the pieces may carry masks), each one body
+static int batchmap_begin(somhip_codebook *cb, bool missing, const char *who) {
+  CHK(check_codebook(cb, true, who));
+  CHK(batchmap_check_codebook(cb, who));
   HIPCHK(hipSetDevice(cb->e->device));
-  CHK(batchmap_state_open(cb));
+  CHK(batchmap_state_open(cb, missing));
   HIPCHK(hipStreamSynchronize(cb->e->stream));
   return 0;
-} ABI_CATCH(somhip_batchmap_begin)
-
-extern "C" int somhip_batchmap_accumulate(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, int want_qerror) try {
-  CHK(check_pair(cb, ds, "somhip_batchmap_accumulate"));
-  CHK(batchmap_check_codebook(cb, "somhip_batchmap_accumulate"));
-  CHK(batchmap_check_data(ds, first, n, "somhip_batchmap_accumulate"));
-  CHK(batchmap_check_open(cb, "somhip_batchmap_accumulate"));
-  if (cb->bm_moved) return fail("somhip_batchmap_accumulate: the codebook has moved (somhip_batchmap_finish has run; somhip_batchmap_begin opens the next epoch)");
+}
+static int batchmap_accumulate(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, int want_qerror, bool missing,
+                               const char *who) {
+  CHK(check_pair(cb, ds, who));
+  CHK(batchmap_check_codebook(cb, who));
+  CHK(batchmap_check_data(ds, first, n, who, missing));
+  CHK(batchmap_check_open(cb, who, missing));
+  if (cb->bm_moved)
+    return fail("%s: the codebook has moved (somhip_batchmap_%sfinish has run; somhip_batchmap_%sbegin opens the next epoch)", who,
+                missing ? "missing_" : "", missing ? "missing_" : "");
   somhip_engine *e = cb->e;
   HIPCHK(hipSetDevice(e->device));
   BatchmapTail tail;
-  CHK(batchmap_read_tail(cb, n, "somhip_batchmap_accumulate", &tail));  // (the last refusal: nothing is bound before it)
+  CHK(batchmap_read_tail(cb, n, who, &tail));                           // (the last refusal: nothing is bound before it)
   BatchmapBufs b;
-  CHK(batchmap_bind(cb, n, &b, cb->bm_state));
+  CHK(batchmap_bind(cb, n, &b, cb->bm_state, missing));
   return batchmap_take_piece(cb, ds, first, n, b, want_qerror != 0, nullptr, tail);
-} ABI_CATCH(somhip_batchmap_accumulate)
-
+}
+// _finish is one body too, and it is somhip_batchmap_finish's own: the one owner of a batch-map state that updates the rows
+// from it and re-opens it behind the combine.  somhip_batchmap_missing_finish runs that body and says so here, for the
+// calling thread: the name the refusals go by, null for the plain call.
+static thread_local const char *bm_finish_as = nullptr;
 extern "C" int somhip_batchmap_finish(somhip_codebook *cb, float r, int64_t group_first, int64_t group_count, float *qerror_out) try {
-  CHK(check_codebook(cb, true, "somhip_batchmap_finish"));
-  CHK(batchmap_check_codebook(cb, "somhip_batchmap_finish"));
-  CHK(batchmap_check_open(cb, "somhip_batchmap_finish"));
-  if (!(r >= 0.0f)) return fail("somhip_batchmap_finish: radius %g < 0", (double)r);
+  const bool missing = bm_finish_as != nullptr;
+  const char *who = missing ? bm_finish_as : "somhip_batchmap_finish";
+  CHK(check_codebook(cb, true, who));
+  CHK(batchmap_check_codebook(cb, who));
+  CHK(batchmap_check_open(cb, who, missing));
+  if (!(r >= 0.0f)) return fail("%s: radius %g < 0", who, (double)r);
   if (group_first < 0 || group_count < 0 || group_first > cb->v.ngroups || group_count > cb->v.ngroups - group_first)
-    return fail("somhip_batchmap_finish: row groups [%lld, +%lld) outside [0, %lld]", (long long)group_first, (long long)group_count,
+    return fail("%s: row groups [%lld, +%lld) outside [0, %lld]", who, (long long)group_first, (long long)group_count,
                 (long long)cb->v.ngroups);
   somhip_engine *e = cb->e;
   HIPCHK(hipSetDevice(e->device));
   BatchmapBufs b;
-  CHK(batchmap_bind(cb, 0, &b, cb->bm_state));
+  CHK(batchmap_bind(cb, 0, &b, cb->bm_state, missing));
   if (group_count > 0) cb->bm_moved = true;                             // (an empty range writes no row)
   const int rc = batchmap_combine_stage(cb, r, b, group_first, group_count);
   cb->bm_open = true;                                                   // (the combine closes every accumulation; this one stays,
@@ -302,9 +398,9 @@ extern "C" int somhip_batchmap_finish(somhip_codebook *cb, float r, int64_t grou
   if (qerror_out) *qerror_out = tail.q;
   return 0;
 } ABI_CATCH(somhip_batchmap_finish)
-
-extern "C" int somhip_batchmap_end(somhip_codebook *cb) try {
-  CHK(check_codebook(cb, true, "somhip_batchmap_end"));
+// (_end frees the state whichever form it has: there is one)
+static int batchmap_end(somhip_codebook *cb, const char *who) {
+  CHK(check_codebook(cb, true, who));
   somhip_engine *e = cb->e;
   HIPCHK(hipSetDevice(e->device));
   HIPCHK(hipStreamSynchronize(e->stream));
@@ -312,15 +408,47 @@ extern "C" int somhip_batchmap_end(somhip_codebook *cb) try {
   cb->bm_state = nullptr;
   cb->bm_open = cb->bm_moved = false;
   return 0;
-} ABI_CATCH(somhip_batchmap_end)
-
-extern "C" int somhip_batchmap_state(somhip_codebook *cb, void **dev_state, int64_t *bytes) try {
-  CHK(check_codebook(cb, dev_state && bytes, "somhip_batchmap_state"));
-  CHK(batchmap_check_open(cb, "somhip_batchmap_state"));
+}
+static int batchmap_state(somhip_codebook *cb, void **dev_state, int64_t *bytes, bool missing, const char *who) {
+  CHK(check_codebook(cb, dev_state && bytes, who));
+  CHK(batchmap_check_open(cb, who, missing));
   *dev_state = cb->bm_state;
   *bytes = (int64_t)batchmap_state_bytes(cb);
   return 0;
+}
+
+extern "C" int somhip_batchmap_begin(somhip_codebook *cb) try {
+  return batchmap_begin(cb, false, "somhip_batchmap_begin");
+} ABI_CATCH(somhip_batchmap_begin)
+extern "C" int somhip_batchmap_accumulate(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, int want_qerror) try {
+  return batchmap_accumulate(cb, ds, first, n, want_qerror, false, "somhip_batchmap_accumulate");
+} ABI_CATCH(somhip_batchmap_accumulate)
+extern "C" int somhip_batchmap_end(somhip_codebook *cb) try {
+  return batchmap_end(cb, "somhip_batchmap_end");
+} ABI_CATCH(somhip_batchmap_end)
+extern "C" int somhip_batchmap_state(somhip_codebook *cb, void **dev_state, int64_t *bytes) try {
+  return batchmap_state(cb, dev_state, bytes, false, "somhip_batchmap_state");
 } ABI_CATCH(somhip_batchmap_state)
+
+extern "C" int somhip_batchmap_missing_begin(somhip_codebook *cb) try {
+  return batchmap_begin(cb, true, "somhip_batchmap_missing_begin");
+} ABI_CATCH(somhip_batchmap_missing_begin)
+extern "C" int somhip_batchmap_missing_accumulate(somhip_codebook *cb, somhip_dataset *ds, int64_t first, int64_t n, int want_qerror) try {
+  return batchmap_accumulate(cb, ds, first, n, want_qerror, true, "somhip_batchmap_missing_accumulate");
+} ABI_CATCH(somhip_batchmap_missing_accumulate)
+extern "C" int somhip_batchmap_missing_finish(somhip_codebook *cb, float r, int64_t group_first, int64_t group_count, float *qerror_out) try {
+  struct As {
+    As() { bm_finish_as = "somhip_batchmap_missing_finish"; }
+    ~As() { bm_finish_as = nullptr; }
+  } as;
+  return somhip_batchmap_finish(cb, r, group_first, group_count, qerror_out);
+} ABI_CATCH(somhip_batchmap_missing_finish)
+extern "C" int somhip_batchmap_missing_end(somhip_codebook *cb) try {
+  return batchmap_end(cb, "somhip_batchmap_missing_end");
+} ABI_CATCH(somhip_batchmap_missing_end)
+extern "C" int somhip_batchmap_missing_state(somhip_codebook *cb, void **dev_state, int64_t *bytes) try {
+  return batchmap_state(cb, dev_state, bytes, true, "somhip_batchmap_missing_state");
+} ABI_CATCH(somhip_batchmap_missing_state)
 
 // The epochs of somhip_som_batchmap over the row blocks of the communicator's ranks, block by block in rank order.  Every
 // rank holds the whole map.  Per epoch: the group stage on every rank's own block at once (the search); then, rank after

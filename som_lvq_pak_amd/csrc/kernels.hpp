@@ -30,6 +30,7 @@
 #include "kernels/map_quality.hpp"
 #include "kernels/map_conn.hpp"
 #include "kernels/batchmap.hpp"
+#include "kernels/batchmap_missing.hpp"
 #include "kernels/map_distortion.hpp"
 #include "kernels/glvq.hpp"
 #include "kernels/grlvq.hpp"

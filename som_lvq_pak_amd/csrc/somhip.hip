@@ -554,6 +554,7 @@ struct somhip_codebook {
   double *bm_state = nullptr;      // the batch map's continued accumulation (host_batchmap.inc): [S | counts][the tail], the codebook's own
   bool bm_open = false;            // ... opened by somhip_batchmap_begin; closed by _end and by every other writer of the rows
   bool bm_moved = false;           // ... a _finish has written rows from it: no further piece until the next _begin
+  bool bm_missing = false;         // ... the form of bm_state: [S | C] of somhip_batchmap_missing_begin, a count per component (one state, one form)
   double *gl_state = nullptr;      // batch GLVQ's continued accumulation (host_glvq.inc): [Sp | sp][Sm | sm][cost][np][nm][the tail], the codebook's own
   bool gl_open = false;            // ... opened by somhip_glvq_begin; closed by _end and by every other writer of the rows
   bool gl_moved = false;           // ... somhip_glvq_finish has written rows from it: no further piece until the next _begin

@@ -750,6 +750,73 @@ def batchmap_state(cb):
     return int(addr.value), int(nbytes.value)
 
 
+def som_batchmap_missing(cb, ds, epochs, radius, start_epoch=0, count=None, first=0, n=None, qerror=True):
+    """som_batchmap over data with missing values (somhip_som_batchmap_missing): a sample is matched over the components
+    it has, and a component of a model vector becomes the weighted mean of the samples that know it; a component no sample
+    of the neighbourhood knows keeps its bits.  Arguments and return value are som_batchmap's; on data without masks the
+    bits are som_batchmap's too."""
+    count = epochs - start_epoch if count is None else count
+    n = ds.n if n is None else n
+    p = _lib.BatchmapParams(epochs, radius, start_epoch, count, first, n)
+    q = np.zeros(max(count, 0), dtype=np.float32) if qerror else None
+    check(cb.e.lib.somhip_som_batchmap_missing(cb.h, ds.h, C.byref(p), _p(q, _lib.c_float_p)))
+    return q
+
+
+def batchmap_missing_sums(cb, ds, first=0, n=None):
+    """The first stage of such an epoch alone (somhip_debug_batchmap_missing_sums): (sums float64[cb.n, dim], counts
+    float64[cb.n, dim]) -- per unit and component the fp64 chain over the samples the unit wins that know the component, in
+    data order, and their number"""
+    n = ds.n if n is None else n
+    sums = np.zeros((cb.n, cb.dim), dtype=np.float64)
+    counts = np.zeros((cb.n, cb.dim), dtype=np.float64)
+    check(cb.e.lib.somhip_debug_batchmap_missing_sums(cb.h, ds.h, first, n, _p(sums, _lib.c_double_p), _p(counts, _lib.c_double_p)))
+    return sums, counts
+
+
+def batchmap_missing_combine(cb, r, sums, counts):
+    """The second stage alone (somhip_debug_batchmap_missing_combine): every component of the codebook's rows becomes the
+    neighbourhood-weighted mean of `sums` over `counts` at radius r; a component whose weighted count is 0 keeps its bits"""
+    sums = np.ascontiguousarray(sums, dtype=np.float64)
+    counts = np.ascontiguousarray(counts, dtype=np.float64)
+    assert sums.shape == (cb.n, cb.dim) and counts.shape == (cb.n, cb.dim)
+    check(cb.e.lib.somhip_debug_batchmap_missing_combine(cb.h, float(np.float32(r)), _p(sums, _lib.c_double_p), _p(counts, _lib.c_double_p)))
+
+
+def batchmap_missing_begin(cb):
+    """batchmap_begin for data with missing values (somhip_batchmap_missing_begin): opens, or re-zeroes, a state of the form
+    [S | C]; a codebook holds one batch-map accumulation, so an open one of the plain form is given up"""
+    check(cb.e.lib.somhip_batchmap_missing_begin(cb.h))
+
+
+def batchmap_missing_accumulate(cb, ds, first=0, n=None, qerror=True):
+    """One piece (somhip_batchmap_missing_accumulate): as batchmap_accumulate, the piece may carry masks"""
+    n = ds.n if n is None else n
+    check(cb.e.lib.somhip_batchmap_missing_accumulate(cb.h, ds.h, first, n, 1 if qerror else 0))
+
+
+def batchmap_missing_finish(cb, r, group_first=0, group_count=None, qerror=True):
+    """The per-component combine at radius r from the accumulated state (somhip_batchmap_missing_finish); arguments and
+    return value are batchmap_finish's"""
+    group_count = (cb.n + 63) // 64 - group_first if group_count is None else group_count
+    q = np.zeros(1, dtype=np.float32) if qerror else None
+    check(cb.e.lib.somhip_batchmap_missing_finish(cb.h, float(np.float32(r)), group_first, group_count, _p(q, _lib.c_float_p)))
+    return float(q[0]) if qerror else None
+
+
+def batchmap_missing_end(cb):
+    """Frees the accumulation's state (somhip_batchmap_missing_end)"""
+    check(cb.e.lib.somhip_batchmap_missing_end(cb.h))
+
+
+def batchmap_missing_state(cb):
+    """(device address, bytes) of the state (somhip_batchmap_missing_state): [S | C] as float64[cb.n, 2 * dim], a row
+    holding a unit's dim sums and behind them its dim counts, then 16 bytes {float32 q, uint32 unused, uint64 samples}"""
+    addr, nbytes = C.c_void_p(), C.c_int64(0)
+    check(cb.e.lib.somhip_batchmap_missing_state(cb.h, C.byref(addr), C.byref(nbytes)))
+    return int(addr.value), int(nbytes.value)
+
+
 GLVQ_PLAN, GLVQ_DIRECT, GLVQ_LIST = -1, 0, 1
 
 

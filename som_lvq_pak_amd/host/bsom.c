@@ -3,7 +3,10 @@
  * neighbourhood-weighted mean of the data, the radius going from -radius down to 1 over -epochs epochs.  No learning
  * rate; the result does not depend on the order of the data.  This project's own tool: SOM_PAK has none.
  * -buffer N takes the data through the engine N rows at a time and -gpus G divides its rows over G ranks; both leave the
- * file and the -v lines of the plain run, byte for byte (the sums' chains are continued, include/somhip.h). */
+ * file and the -v lines of the plain run, byte for byte (the sums' chains are continued, include/somhip.h).
+ * -missing takes data whose samples leave components out (x): a sample is matched over the components it has and a
+ * component of a model vector becomes the weighted mean of the samples that know it
+ * (include/somhip_batchmap_missing.h); on data without x it writes the plain run's bytes. */
 #include <stdlib.h>
 #include <string.h>
 #include "pak.h"
@@ -16,6 +19,9 @@ static const char *usage =
     "           -gpus G (one process per GPU, the data's rows divided over them; same result; not with -buffer;\n"
     "                    SOMHIP_COMM=rccl|sockets in the environment names the ranks' transport and, as with vsom,\n"
     "                    sends even one rank through it)\n"
+    "           -missing (take data with missing components, x: a sample is matched over the components it has, a\n"
+    "                     component of a model vector becomes the mean of the samples that know it; data without x\n"
+    "                     give the same map as without the option; works with -buffer, not with -gpus)\n"
     "Topology and neighbourhood come from the codebook's header.\n"
     "Files:     text (.dat/.cod), raw fp32 (a name ending in .f32; see datconv), or -din gen:k=..,dim=..,n=..,seed=..\n";
 
@@ -55,17 +61,24 @@ int main(int argc, char **argv)
   int gpus = (int)oatoi(gpus_s, 1);
   if (buffer < 0) { fprintf(stderr, "bsom: -buffer %ld < 0\n", buffer); exit(1); }
   if (gpus < 1 || gpus > 64) { fprintf(stderr, "bsom: -gpus %d outside 1 .. 64\n", gpus); exit(1); }
+  int missing = extract_parameter(argc, argv, "-missing", OPTION2) != NULL;
+  if (missing && gpus_s) { fprintf(stderr, "bsom: -missing together with -gpus is not available (the ranks train without masks)\n"); exit(1); }
   if (gpus_s && buffer_s) { fprintf(stderr, "bsom: -gpus together with -buffer is not available (give one of the two)\n"); exit(1); }
 
   pak_gen_virtual_ok = 1;                                /* a gen: source is generated in HBM, never on the host */
   if (pak_open_inputs(din, 0, "cant open data file '%s'\n", cin, 0, "Can't open code file '%s'\n", 1, &io)) goto end;
   if (io.codes->masks) { fprintf(stderr, "bsom: codebook %s has masked components (x): not supported\n", cin); goto end; }
-  if (io.data->masks) { fprintf(stderr, "bsom: data %s has masked components (x): not supported\n", din); goto end; }
+  if (io.data->masks && !missing) {
+    fprintf(stderr, "bsom: data %s has masked components (x): not supported without -missing\n", din);
+    goto end;
+  }
   set_teach_params(&params, io.codes, io.data, NULL);
   params.radius = radius;
   float *qerror = lines ? calloc((size_t)epochs, sizeof *qerror) : NULL;
   struct bsom_out out = {cout, epochs, radius, qerror};
-  if (!buffer_s && (gpus > 1 || getenv("SOMHIP_COMM")))  /* the ranks train, as in vsom; rank 0 prints and saves */
+  if (missing) {
+    if (!som_batchmap_missing_training(&params, epochs, buffer, qerror)) error = save_codes(&params, &out);
+  } else if (!buffer_s && (gpus > 1 || getenv("SOMHIP_COMM")))  /* the ranks train, as in vsom; rank 0 prints and saves */
     error = som_batchmap_training_multi(&params, epochs, qerror, gpus, save_codes, &out);
   else if (!som_batchmap_training(&params, epochs, buffer, qerror))
     error = save_codes(&params, &out);

@@ -190,6 +190,10 @@ void free_map_quality(struct map_quality *q);
  * _finish), each piece a data set of its own -- uploaded, or generated in place for a gen: source -- that is destroyed
  * once it is taken: the device never holds more than `buffer` rows, and the result is the same, bit for bit. */
 int som_batchmap_training(struct teach_params *teach, long epochs, long buffer, float *qerror);
+/* bsom -missing: the same over data whose samples may leave components out (somhip_som_batchmap_missing; with buffer > 0
+ * somhip_batchmap_missing_begin / _accumulate / _finish): a component of a model vector becomes the weighted mean of the
+ * samples that know it.  On data without masks the result is som_batchmap_training's, bit for bit. */
+int som_batchmap_missing_training(struct teach_params *teach, long epochs, long buffer, float *qerror);
 /* bsom -gpus G: the data's rows in G blocks, one per rank, every rank the whole map (somhip_som_batchmap_ranks); rank 0
  * ends with the map in teach->codes and the epochs' qerror in qerror ([epochs]) and runs after(teach, arg) -- print, save */
 int som_batchmap_training_multi(struct teach_params *teach, long epochs, float *qerror, int gpus,

@@ -707,7 +707,7 @@ somhip_dataset *pak_mirror_data_rows(struct entries *data, long first, long coun
   return said(rc) ? NULL : ds;
 }
 
-int som_batchmap_training(struct teach_params *teach, long epochs, long buffer, float *qerror)
+static int batchmap_training(struct teach_params *teach, long epochs, long buffer, float *qerror, int missing)
 {
   if (set_som_params(teach)) { fprintf(stderr, "som_batchmap_training: can't set SOM parameters\n"); return 1; }
   const long n = teach->data->num_entries;
@@ -718,7 +718,8 @@ int som_batchmap_training(struct teach_params *teach, long epochs, long buffer, 
     rc = mirrors_open(&m, teach->codes, 0, teach->data, 0);
     if (!rc) {
       somhip_batchmap_params p = {epochs, teach->radius, 0, epochs, 0, n};
-      rc = said(somhip_som_batchmap(m.cb, m.ds, &p, qerror)) || said(somhip_codebook_download(m.cb, teach->codes->points));
+      rc = said(missing ? somhip_som_batchmap_missing(m.cb, m.ds, &p, qerror) : somhip_som_batchmap(m.cb, m.ds, &p, qerror)) ||
+           said(somhip_codebook_download(m.cb, teach->codes->points));
     }
     mirrors_close(&m);
     return rc;
@@ -728,18 +729,28 @@ int som_batchmap_training(struct teach_params *teach, long epochs, long buffer, 
   rc = !(m.cb = pak_mirror_codes(teach->codes, 0));
   for (long t = 0; !rc && t < epochs; t++) {
     const float r = 1.0f + (teach->radius - 1.0f) * (float)(epochs - t) / (float)epochs;   /* the engine's r_t */
-    rc = said(somhip_batchmap_begin(m.cb));
+    rc = said(missing ? somhip_batchmap_missing_begin(m.cb) : somhip_batchmap_begin(m.cb));
     for (long first = 0; !rc && first < n; first += buffer) {
       const long c = buffer < n - first ? buffer : n - first;
       somhip_dataset *piece = pak_mirror_data_rows(teach->data, first, c);
-      rc = !piece || said(somhip_batchmap_accumulate(m.cb, piece, 0, c, qerror != NULL));
+      rc = !piece || said(missing ? somhip_batchmap_missing_accumulate(m.cb, piece, 0, c, qerror != NULL)
+                                  : somhip_batchmap_accumulate(m.cb, piece, 0, c, qerror != NULL));
       if (piece) somhip_dataset_destroy(piece);
     }
-    if (!rc) rc = said(somhip_batchmap_finish(m.cb, r, 0, ngroups, qerror ? qerror + t : NULL));
+    if (!rc) rc = said(missing ? somhip_batchmap_missing_finish(m.cb, r, 0, ngroups, qerror ? qerror + t : NULL)
+                               : somhip_batchmap_finish(m.cb, r, 0, ngroups, qerror ? qerror + t : NULL));
   }
-  if (!rc) rc = said(somhip_batchmap_end(m.cb)) || said(somhip_codebook_download(m.cb, teach->codes->points));
+  if (!rc) rc = said(somhip_batchmap_end(m.cb)) || said(somhip_codebook_download(m.cb, teach->codes->points));   /* (either form's state) */
   mirrors_close(&m);
   return rc;
+}
+int som_batchmap_training(struct teach_params *teach, long epochs, long buffer, float *qerror)
+{
+  return batchmap_training(teach, epochs, buffer, qerror, 0);
+}
+int som_batchmap_missing_training(struct teach_params *teach, long epochs, long buffer, float *qerror)
+{
+  return batchmap_training(teach, epochs, buffer, qerror, 1);
 }
 
 int glvq_training(struct teach_params *teach, long epochs, float sigmoid_beta, double *cost, int64_t *correct)

@@ -27,7 +27,18 @@ commit's, built from a clean checkout of it), in a child process that loads it t
              same way; the rows are compared with the one call's by bit pattern before any time is printed.
   the tool   `bsom` end to end (process start to exit, the host clock of this script) on a gen: source, without -buffer and
              with -buffer at a quarter and a sixteenth of the rows; with two or more devices also -gpus 2 and -gpus <all>.
-  ranks      the bytes one epoch broadcasts, computed from the shapes: G times the state."""
+  ranks      the bytes one epoch broadcasts, computed from the shapes: G times the state.
+
+--missing: the report on the batch map over data with missing values (somhip_som_batchmap_missing, K8m).
+  plain paths   somhip_som_batchmap per shape at bubble radius 1, bubble and gaussian at the first radius, in child processes
+                that alternate between the library under --parent-lib and this commit's, `--rounds` of each, timed as under
+                --pieces; and `bsom` end to end with the tool under --parent-bsom and this commit's, alternating.  Reported:
+                every child's medians, the parent's spread among its own children, this commit less the parent.
+  new stages    this commit's children also run somhip_som_batchmap_missing on the same unmasked data: the sums and the
+                combine of the missing form beside the parent's plain stages, as ratios of the medians of medians.
+  masked epoch  this commit, 30 % of the components masked at random (host data, uploaded), one epoch per stage; the
+                winner search is the masked direct scan, one sample per launch column, so the large shape runs over
+                --masked-large vectors only and its search time per vector is what carries to a larger run."""
 import argparse
 import ctypes as C
 import json
@@ -293,6 +304,135 @@ def pieces_report(E, a, shapes, out):
         out("    %d x %d: state %.1f MB per rank's turn" % (units, dim + 1, (units * (dim + 1) * 8 + 16) / 1e6))
 
 
+MISSING_CASES = lambda E, radii: (("bubble", E.NEIGH_BUBBLE, 1.0), ("bubble", E.NEIGH_BUBBLE, radii[0]), ("gaussian", E.NEIGH_GAUSSIAN, radii[0]))  # noqa: E731
+
+
+def timed_epochs(E, eng, cb, ds, codes, radius, reps, train):
+    """one warm-up epoch, `reps` on the host clock with events off, `reps` with the stage events on: (walls, group, sums, combine)"""
+    def epoch(events):
+        cb.upload(codes)
+        eng.timing(events)
+        eng.timing_reset()
+        eng.sync()
+        t0 = time.perf_counter()
+        train(cb, ds, 1, radius, qerror=False)
+        wall = (time.perf_counter() - t0) * 1e3
+        st = eng.batchmap_timing() if events else None
+        eng.timing(False)
+        return wall, st
+    epoch(False)
+    walls = [epoch(False)[0] for _ in range(reps)]
+    timed = [epoch(True)[1] for _ in range(reps)]
+    return (walls, [t["group"][1] for t in timed], [t["k_batchmap_sums"][1] for t in timed], [t["k_batchmap_combine"][1] for t in timed])
+
+
+def missing_child(E, eng, reps, shapes, who):
+    """per shape and case the plain epoch, and with this commit's library the missing form on the same unmasked data: a JSON
+    line each"""
+    for xdim, ydim, dim, n, radii in shapes:
+        ds = E.Dataset(eng, generate=(9, 16, dim, 0, n))
+        codes = E.gen_rows(9, 16, dim, n, xdim * ydim)[0]
+        for nname, neigh, radius in MISSING_CASES(E, radii):
+            cb = E.Codebook(eng, codes, E.TOPOL_HEXA, neigh, xdim, ydim)
+            forms = [("plain", E.som_batchmap)] + ([("missing", E.som_batchmap_missing)] if who == "this" else [])
+            rows = {}
+            for form, train in forms:
+                walls, grp, sums, comb = timed_epochs(E, eng, cb, ds, codes, radius, reps, train)
+                rows[form] = cb.download()
+                print("JSON " + json.dumps({"who": who, "form": form, "shape": [xdim, ydim, dim, n], "case": "%s radius %g" % (nname, radius),
+                                            "walls": walls, "group": grp, "sums": sums, "combine": comb}), flush=True)
+            if "missing" in rows:
+                assert np.array_equal(rows["plain"].view(np.uint32), rows["missing"].view(np.uint32)), "the missing form differs on unmasked data"
+            cb.close()
+        ds.close()
+
+
+def missing_report(E, a, shapes, out):
+    me = os.path.abspath(__file__)
+    small = ["--small"] if a.small else []
+    runs = {}
+    order = (["parent", "this"] if a.parent_lib else ["this"]) * a.rounds
+    for who in order:
+        env = dict(os.environ)
+        if who == "parent":
+            env["SOMHIP_LIB"] = os.path.abspath(a.parent_lib)
+        p = subprocess.run([sys.executable, me, "--missing-child", who, "--reps", str(a.reps)] + small, env=env, stdout=subprocess.PIPE,
+                           text=True, check=True, timeout=900)
+        for s in p.stdout.split("\n"):
+            if s.startswith("JSON "):
+                r = json.loads(s[5:])
+                runs.setdefault((tuple(r["shape"]), r["case"]), []).append(r)
+    out("== one epoch on unmasked generated vectors, hexa; children alternating between the parent's library and this commit's;")
+    out("   per child: medians of %d calls (wall: events off; stages: events on)" % a.reps)
+    for (shape, case), rs in runs.items():
+        out("  %d x %d x %d over %d vectors, %s" % (shape + (case,)))
+        m = {}
+        for r in rs:
+            key = (r["who"], r["form"])
+            m.setdefault(key, {"wall": [], "sums": [], "combine": []})
+            m[key]["wall"].append(med(r["walls"])); m[key]["sums"].append(med(r["sums"])); m[key]["combine"].append(med(r["combine"]))
+            out("    %-6s %-7s wall ms median %.3f of %s | group %.3f sums %.3f combine %.3f"
+                % (r["who"], r["form"], med(r["walls"]), fmt(r["walls"]), med(r["group"]), med(r["sums"]), med(r["combine"])))
+        base = m.get(("parent", "plain")) or m[("this", "plain")]
+        if ("parent", "plain") in m:
+            for what in ("wall", "sums", "combine"):
+                pv, tv = m[("parent", "plain")][what], m[("this", "plain")][what]
+                out("    plain %-7s parent's children among themselves: spread %.3f ms (%.2f %%); this commit less the parent: %+.3f ms (%+.2f %%)"
+                    % (what, max(pv) - min(pv), 100 * (max(pv) - min(pv)) / med(pv), med(tv) - med(pv), 100 * (med(tv) - med(pv)) / med(pv)))
+        if ("this", "missing") in m:
+            for what in ("sums", "combine"):
+                bv, mv = base[what], m[("this", "missing")][what]
+                out("    missing %-7s %.3f ms against the %s plain %.3f ms: ratio %.3f (plain spread %.2f %%, missing spread %.2f %%)"
+                    % (what, med(mv), "parent's" if ("parent", "plain") in m else "this commit's", med(bv), med(mv) / med(bv),
+                       100 * (max(bv) - min(bv)) / med(bv), 100 * (max(mv) - min(mv)) / med(mv)))
+    # the tool, end to end, the parent's beside this commit's
+    import tempfile
+    from som_lvq_pak_amd import textio
+    bsom = os.path.join(ROOT, "som_lvq_pak_amd", "host", "bin", "bsom")
+    xdim, ydim, dim, n, radii = shapes[-1]
+    with tempfile.TemporaryDirectory() as tmp:
+        m = textio.Entries()
+        m.dim, m.topol, m.neigh, m.xdim, m.ydim = dim, E.TOPOL_HEXA, E.NEIGH_BUBBLE, xdim, ydim
+        m.points = E.gen_rows(9, 16, dim, n, xdim * ydim)[0]
+        cod = os.path.join(tmp, "m.cod")
+        textio.write_entries(cod, m)
+        src = "gen:k=16,dim=%d,n=%d,seed=9" % (dim, n)
+        out("== bsom end to end, %d x %d x %d, -din %s, 4 epochs from radius %g (process start to exit), runs alternating" % (xdim, ydim, dim, src, radii[0]))
+        variants = ([("parent", a.parent_bsom, [])] if a.parent_bsom else []) + [("this", bsom, []), ("this", bsom, ["-missing"])]
+        walls, ref = {}, None
+        for rnd in range(a.rounds):
+            for who, exe, extra in variants:
+                o = os.path.join(tmp, "o.cod")
+                t0 = time.perf_counter()
+                subprocess.run([exe, "-cin", cod, "-din", src, "-cout", o, "-epochs", "4", "-radius", str(radii[0])] + extra, check=True,
+                               stdout=subprocess.DEVNULL, timeout=600)
+                walls.setdefault((who, " ".join(extra)), []).append((time.perf_counter() - t0) * 1e3)
+                data = open(o, "rb").read()
+                ref = ref or data
+                assert data == ref, "bsom %s %s writes another file" % (who, " ".join(extra))
+        for (who, extra), w in walls.items():
+            out("    %-6s bsom %-9s wall ms median %.1f of %s, spread %.1f (one file, byte for byte)" % (who, extra, med(w), fmt(w), max(w) - min(w)))
+    # a masked epoch, per stage
+    eng = E.Engine(0)
+    out("== this commit: one epoch of somhip_som_batchmap_missing, 30 % of the components masked at random, hexa bubble (events on)")
+    for i, (xdim, ydim, dim, n, radii) in enumerate(shapes):
+        if i == 0 and not a.small:
+            n = a.masked_large
+        rs = np.random.RandomState(5)
+        x = rs.standard_normal((n, dim)).astype(np.float32)
+        mask = (rs.uniform(size=(n, dim)) < 0.3).astype(np.uint8)
+        ds = E.Dataset(eng, x, mask=mask)
+        codes = rs.standard_normal((xdim * ydim, dim)).astype(np.float32)
+        cb = E.Codebook(eng, codes, E.TOPOL_HEXA, E.NEIGH_BUBBLE, xdim, ydim)
+        walls, grp, sums, comb = timed_epochs(E, eng, cb, ds, codes, radii[0], a.reps, E.som_batchmap_missing)
+        rest = med(walls) - med(grp) - med(sums) - med(comb)
+        out("  %d x %d x %d over %d vectors, radius %g: wall ms (events off) median %.3f of %s | group %.3f sums %.3f combine %.3f | the rest, "
+            "the masked search with the copies: %.3f ms = %.3f us a vector"
+            % (xdim, ydim, dim, n, radii[0], med(walls), fmt(walls), med(grp), med(sums), med(comb), rest, 1e3 * rest / n))
+        cb.close(); ds.close()
+    eng.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
@@ -303,6 +443,10 @@ def main():
     ap.add_argument("--pieces", action="store_true", help="the report on the epoch over data in pieces (see the top)")
     ap.add_argument("--rounds", type=int, default=3, help="--pieces: child processes per library")
     ap.add_argument("--onecall-only", default=None, help="(a --pieces child process) label of the library under SOMHIP_LIB")
+    ap.add_argument("--missing", action="store_true", help="the report on the batch map over data with missing values (see the top)")
+    ap.add_argument("--missing-child", default=None, help="(a --missing child process) label of the library under SOMHIP_LIB")
+    ap.add_argument("--parent-bsom", default=None, help="--missing: the parent commit's bsom, beside its own library")
+    ap.add_argument("--masked-large", type=int, default=16384, help="--missing: vectors of the masked epoch at the first shape")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     shapes = [(24, 16, 40, 5000, (6.0, 1.0))] if a.small else SHAPES
@@ -316,6 +460,20 @@ def main():
     if a.online_only:                                   # the parent's library has no batch map: bind what it has
         for name in [k for k in _lib.SIGNATURES if "batchmap" in k]:
             del _lib.SIGNATURES[name]
+    if a.missing_child or a.missing:
+        if a.missing_child == "parent":                 # the parent's library has no missing form
+            _lib.BATCHMAP_MISSING_SIGNATURES.clear()
+        if a.missing_child:
+            eng = E.Engine(0)
+            missing_child(E, eng, a.reps, shapes, a.missing_child)
+            eng.close()
+        else:
+            missing_report(E, a, shapes, out)
+            if a.out:
+                with open(a.out, "w") as f:
+                    f.write("\n".join(lines) + "\n")
+        print(json.dumps({"lines": len(lines)}))
+        return
     if a.onecall_only or a.pieces:
         if a.onecall_only == "parent":                  # ... nor the pieces' entry points
             for name in [k for k in _lib.SIGNATURES if k.startswith("somhip_batchmap_") and k != "somhip_batchmap_timing"] + \
