@@ -17,7 +17,9 @@ namespace somhip {
 //   sums     k_batchmap_sums: S[u][k] = one chain of fp64 additions from +0.0 over the unit's list, S[u][dim] = hits[u].
 //            k_batchmap_sums<true> continues the chains a piece of the data left in S (somhip_batchmap_accumulate).
 //   combine  k_batchmap_combine: [N | D] = H x [S | hits] on v_mfma_f64_16x16x4_f64, H generated per lane, then
-//            m_i[k] = (float)(N[i][k] / D[i]) into the codebook's tiles where D[i] > 0.
+//            m_i[k] = (float)(N[i][k] / D[i]) into the codebook's tiles where D[i] > 0.  Its bubble group-skip rule,
+//            bm_group_skipped, is stated here once for K8m's and K1d's lattice GEMMs too; the rest of the walk (fetch,
+//            staging, weights, MFMA loop) is written out in each of the three kernels.
 //
 // No floating-point atomics: S has the same bits on every run, and the combine's order of additions over the source
 // units is the storage order of the rows, four at a time inside the MFMA -- a function of the shape alone.
@@ -90,22 +92,17 @@ __global__ __launch_bounds__(BM_SUM_DIMS) void k_batchmap_sums(const float *__re
   if (k > d) return;
   double *out = S + static_cast<int64_t>(u) * (d + 1) + k;
   if (k == d) { *out = CONT ? *out + static_cast<double>(hi - lo) : static_cast<double>(hi - lo); return; }
-  auto row_of = [&](uint32_t i) {
-    int64_t r = first + static_cast<int64_t>(list[i]);
-    if (r >= n_rows) { r -= n_rows; if (r >= n_rows) r %= n_rows; }
-    return r;
-  };
   if (CONT && lo == hi) return;                               // no sample of this piece: the chain stands
   double acc = CONT ? *out : 0.0;
   uint32_t i = lo;
   for (; hi - i >= BM_SUM_AHEAD; i += BM_SUM_AHEAD) {
     float x[BM_SUM_AHEAD];
 #pragma unroll
-    for (int a = 0; a < BM_SUM_AHEAD; a++) x[a] = rows[row_of(i + a) * d + k];
+    for (int a = 0; a < BM_SUM_AHEAD; a++) x[a] = rows[run_row(first, list[i + a], n_rows) * d + k];
 #pragma unroll
     for (int a = 0; a < BM_SUM_AHEAD; a++) acc += static_cast<double>(x[a]);
   }
-  for (; i < hi; i++) acc += static_cast<double>(rows[row_of(i) * d + k]);
+  for (; i < hi; i++) acc += static_cast<double>(rows[run_row(first, list[i], n_rows) * d + k]);
   *out = acc;
 }
 
@@ -138,6 +135,25 @@ __device__ __forceinline__ void bm_group_box(const CbView &cb, int64_t g, int &x
   y0 = static_cast<int>(u0 / cb.xdim); y1 = static_cast<int>(u1 / cb.xdim);
   if (y0 == y1) { x0 = static_cast<int>(u0 % cb.xdim); x1 = static_cast<int>(u1 % cb.xdim); }
   else { x0 = 0; x1 = cb.xdim - 1; }
+}
+
+// The group-skip rule of the lattice GEMMs (k_batchmap_combine below, k_batchmap_combine_missing in
+// kernels/batchmap_missing.hpp, k_distortion_evaluate in kernels/map_distortion.hpp), stated here alone: under bubble, source
+// row group s -- in patch order the patch (spx, spy) -- is skipped where its lattice box lies wholly outside the radius of the
+// destination group's box [dx0, dx1] x [dy0, dy1]; gaussian skips none.  A group skipped wrongly drops samples from a
+// neighbourhood without a sound.  Uniform over the workgroup: the groups and the shape only.
+template <bool GAUSS>
+__device__ __forceinline__ bool bm_group_skipped(const CbView &cb, int64_t s, int spx, int spy, int dx0, int dx1, int dy0, int dy1,
+                                                 float thresh) {
+  if (GAUSS) return false;
+  int sx0, sx1, sy0, sy1;
+  if (cb.patch_w) { sx0 = spx * 8; sx1 = sx0 + 7; sy0 = spy * 8; sy1 = sy0 + 7; }
+  else bm_group_box(cb, s, sx0, sx1, sy0, sy1);
+  const double gx = static_cast<double>(max(0, max(sx0 - dx1, dx0 - sx1)));
+  const double gy = static_cast<double>(max(0, max(sy0 - dy1, dy0 - sy1)));
+  const double hx = cb.topol == 4 ? gx : fmax(0.0, gx - 0.5);     // a hexagonal row is shifted by half a unit at most
+  const double least = hx * hx + (cb.topol == 4 ? 1.0 : 0.75) * gy * gy;
+  return least > static_cast<double>(thresh) * 1.000001;
 }
 
 // [N | D] = H x [S | hits] and the division, for the 64 rows of row group g0 + blockIdx.x and the columns
@@ -176,17 +192,7 @@ __global__ __launch_bounds__(256, 3) void k_batchmap_combine(CbView cb, int ydim
   // The walk over the source groups that are not skipped (uniform over the workgroup: g, the group and the shape only).
   // In patch order the group's patch coordinates are counted along, not divided out.
   int spx = 0, spy = 0;
-  auto skipped = [&](int64_t s) -> bool {
-    if (GAUSS) return false;
-    int sx0, sx1, sy0, sy1;
-    if (cb.patch_w) { sx0 = spx * 8; sx1 = sx0 + 7; sy0 = spy * 8; sy1 = sy0 + 7; }
-    else bm_group_box(cb, s, sx0, sx1, sy0, sy1);
-    const double gx = static_cast<double>(max(0, max(sx0 - dx1, dx0 - sx1)));
-    const double gy = static_cast<double>(max(0, max(sy0 - dy1, dy0 - sy1)));
-    const double hx = cb.topol == 4 ? gx : fmax(0.0, gx - 0.5);     // a hexagonal row is shifted by half a unit at most
-    const double least = hx * hx + (cb.topol == 4 ? 1.0 : 0.75) * gy * gy;
-    return least > static_cast<double>(thresh) * 1.000001;
-  };
+  auto skipped = [&](int64_t s) -> bool { return bm_group_skipped<GAUSS>(cb, s, spx, spy, dx0, dx1, dy0, dy1, thresh); };
   auto after = [&](int64_t s) -> int64_t {                            // the first group behind s that is not skipped
     do {
       s++;

@@ -37,11 +37,6 @@ __global__ __launch_bounds__(BM_SUM_DIMS) void k_batchmap_sums_missing(const flo
   const uint32_t lo = starts[u], hi = starts[u + 1];
   if (k >= d) return;
   double *out = S + static_cast<int64_t>(u) * (2 * d) + k;
-  auto row_of = [&](uint32_t i) {
-    int64_t r = first + static_cast<int64_t>(list[i]);
-    if (r >= n_rows) { r -= n_rows; if (r >= n_rows) r %= n_rows; }
-    return r;
-  };
   if (CONT && lo == hi) return;                               // no sample of this piece: the chain and the count stand
   double acc = CONT ? out[0] : 0.0;
   uint32_t cnt = 0;
@@ -51,7 +46,7 @@ __global__ __launch_bounds__(BM_SUM_DIMS) void k_batchmap_sums_missing(const flo
     uint8_t m[BM_SUM_AHEAD];
 #pragma unroll
     for (int a = 0; a < BM_SUM_AHEAD; a++) {
-      const int64_t at = row_of(i + a) * d + k;
+      const int64_t at = run_row(first, list[i + a], n_rows) * d + k;
       x[a] = rows[at];
       m[a] = mask ? mask[at] : static_cast<uint8_t>(0);
     }
@@ -63,7 +58,7 @@ __global__ __launch_bounds__(BM_SUM_DIMS) void k_batchmap_sums_missing(const flo
     }
   }
   for (; i < hi; i++) {
-    const int64_t at = row_of(i) * d + k;
+    const int64_t at = run_row(first, list[i], n_rows) * d + k;
     const bool known = !(mask && mask[at]);
     const double next = acc + static_cast<double>(rows[at]);
     acc = known ? next : acc;
@@ -74,8 +69,8 @@ __global__ __launch_bounds__(BM_SUM_DIMS) void k_batchmap_sums_missing(const flo
 }
 
 // [N | D] = H x [S | C] and the division per component, for the 64 rows of row group g0 + blockIdx.x and the columns
-// [blockIdx.y * BMM_COLS, + BMM_COLS) of a whole map.  k_batchmap_combine's walk, staging, weights and group skip (see
-// there), with four accumulator tiles a wave: tiles 0, 1 the numerators of 32 columns, tiles 2, 3 the denominators of the
+// [blockIdx.y * BMM_COLS, + BMM_COLS) of a whole map.  k_batchmap_combine's walk, staging and weights written out again (see
+// there), its group-skip rule called (bm_group_skipped, kernels/batchmap.hpp), with four accumulator tiles a wave: tiles 0, 1 the numerators of 32 columns, tiles 2, 3 the denominators of the
 // same columns.  A staged row is [32 S | 32 C]: lanes 0 .. 31 fetch the sums, lanes 32 .. 63 the counts.  N and D of an
 // element lie in the same lane and register of their tiles (the C / D layout of the f64 MFMA), so the division needs no
 // exchange between lanes.  D[i][k] is accumulated by the very sequence of MFMAs that K8 accumulates D[i] by: where
@@ -102,17 +97,7 @@ __global__ __launch_bounds__(256, 3) void k_batchmap_combine_missing(CbView cb, 
   for (int t = 0; t < 4; t++) acc[t] = f64x4{0.0, 0.0, 0.0, 0.0};
 
   int spx = 0, spy = 0;
-  auto skipped = [&](int64_t s) -> bool {                             // (k_batchmap_combine's rule, word for word)
-    if (GAUSS) return false;
-    int sx0, sx1, sy0, sy1;
-    if (cb.patch_w) { sx0 = spx * 8; sx1 = sx0 + 7; sy0 = spy * 8; sy1 = sy0 + 7; }
-    else bm_group_box(cb, s, sx0, sx1, sy0, sy1);
-    const double gx = static_cast<double>(max(0, max(sx0 - dx1, dx0 - sx1)));
-    const double gy = static_cast<double>(max(0, max(sy0 - dy1, dy0 - sy1)));
-    const double hx = cb.topol == 4 ? gx : fmax(0.0, gx - 0.5);
-    const double least = hx * hx + (cb.topol == 4 ? 1.0 : 0.75) * gy * gy;
-    return least > static_cast<double>(thresh) * 1.000001;
-  };
+  auto skipped = [&](int64_t s) -> bool { return bm_group_skipped<GAUSS>(cb, s, spx, spy, dx0, dx1, dy0, dy1, thresh); };
   auto after = [&](int64_t s) -> int64_t {
     do {
       s++;

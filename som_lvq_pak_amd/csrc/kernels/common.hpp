@@ -1,4 +1,4 @@
-// kernels/common.hpp -- shared types and exact-arithmetic helpers (CbView, keys, lattice distances, step scalars)
+// kernels/common.hpp -- shared types and exact-arithmetic helpers (CbView, keys, lattice distances, step scalars, the row of a run sample)
 // (part of kernels.hpp; see the notes at the top of that file)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -213,5 +213,13 @@ struct StepScalars {
 __host__ __device__ __forceinline__ int32_t fixed_pack(int fx, int fy) { return (fy << 15) | fx; }   // 0 <= fx, fy < 32768
 __host__ __device__ __forceinline__ int fixed_x(int32_t f) { return f & 32767; }
 __host__ __device__ __forceinline__ int fixed_y(int32_t f) { return f >> 15; }
+
+// The data row of sample s of a run that starts at data row first < n_rows and wraps: (first + s) % n_rows, the division
+// taken only by a run that wraps more than once.  The ordered sums of K8, K8m, K9 and K11 find their rows through this.
+__device__ __forceinline__ int64_t run_row(int64_t first, uint32_t s, int64_t n_rows) {
+  int64_t r = first + static_cast<int64_t>(s);
+  if (r >= n_rows) { r -= n_rows; if (r >= n_rows) r %= n_rows; }
+  return r;
+}
 
 }  // namespace somhip

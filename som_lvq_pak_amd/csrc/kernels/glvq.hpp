@@ -21,6 +21,11 @@ namespace somhip {
 //            k_glvq_counts behind it adds the piece's counts to the state's integers.
 //   update   k_glvq_update: w <- (float)(W + a * ((Sp - sp W) - (Sm - sm W))) over the storage tiles, in place.
 //
+// Bodies stated here once and used by K11 and K12 too: glvq_sums_chain (k_glvq_sums, k_grlvq_sums), glvq_step_g (the g of
+// a chosen row: k_glvq_update, k_grlvq_update, k_gmlvq_update) and glvq_update_tiles (k_glvq_update, k_grlvq_update).  The
+// search is not among them: k_scan_class and K11's k_scan_class_weighted are written out each, since one body behind a
+// function boundary changed their register allotment (profiles/kernel_bodies_vs_parent.txt).
+//
 // No floating-point atomics anywhere: every sum is a function of the data, the codebook and the shape alone.
 // =====================================================================================
 constexpr int GLVQ_S = 32;                    // samples of a search tile (K1's SCAN_S)
@@ -238,17 +243,22 @@ __global__ __launch_bounds__(GLVQ_THREADS) void k_glvq_terms(const uint64_t *__r
 // the chain of fp64 additions from +0.0 of xi[role][s] * (double)x_s[k] -- a multiply, then an add -- over the role's list
 // of u in data order (sample s is data row (first + s) % n_rows, first < n_rows); column k = d: the same chain over xi
 // alone (xi * 1.0 is xi); column k = d + 1 of role +: the chain over f[s], written to cost[u].  S is [2][n_units][d + 1].
-// The list is known, so GLVQ_SUM_AHEAD entries -- sample, weight, row element -- are requested before their additions run.
+// The list is known, so AHEAD (GLVQ_SUM_AHEAD) entries -- sample, weight, row element -- are requested before their additions
+// run.  One body, glvq_sums_chain, gives k_glvq_sums<CONT> below and k_grlvq_sums<AHEAD> (kernels/grlvq.hpp).
 // CONT: the data come in pieces and S, cost hold what the pieces before this one left (all +0.0 before the first): every
 // chain goes on from its stored value, and a (u, role) without a sample in this piece is left as it stands.  A chain from a
-// stored +0.0 is the chain from +0.0, so the pieces leave the bits of one call over their rows in order.  An instantiation
-// of its own (k_batchmap_sums<true>'s way): the one-call kernel keeps its code, with no load of S ahead of its chain.
-template <bool CONT>
-__global__ __launch_bounds__(BM_SUM_DIMS) void k_glvq_sums(const float *__restrict__ rows, int64_t n_rows, int d, int64_t first,
-                                                           int64_t n, uint32_t n_units, const uint32_t *__restrict__ list,
-                                                           const uint32_t *__restrict__ starts, const double *__restrict__ xi,
-                                                           const double *__restrict__ f, double *__restrict__ S,
-                                                           double *__restrict__ cost) {
+// stored +0.0 is the chain from +0.0, so the pieces leave the bits of one call over their rows in order.  A compile-time
+// flag (k_batchmap_sums<true>'s way): the one-call kernels have no load of S ahead of their chains.
+// RELEVANCE (K11's step 4, k_grlvq_sums in kernels/grlvq.hpp): a second accumulator in the same lane, for k < d
+// R[role][u][k] = the chain of fp64 additions from +0.0 over the same list of  xi * (td * td),  td = (double)x_s[k] -
+// (double)w_u[k]: a subtraction, two multiplications and an addition, each rounded.  w_u[k] is read once from the storage
+// tiles of cb (null without RELEVANCE).  R is [2][n_units][d].
+template <bool CONT, bool RELEVANCE, int AHEAD>
+__device__ __forceinline__ void glvq_sums_chain(const CbView *cb, const float *__restrict__ rows, int64_t n_rows, int d, int64_t first,
+                                                int64_t n, uint32_t n_units, const uint32_t *__restrict__ list,
+                                                const uint32_t *__restrict__ starts, const double *__restrict__ xi,
+                                                const double *__restrict__ f, double *__restrict__ S, double *__restrict__ R,
+                                                double *__restrict__ cost) {
   const uint32_t u = blockIdx.x, role = blockIdx.z;
   const int k = static_cast<int>(blockIdx.y) * BM_SUM_DIMS + static_cast<int>(threadIdx.x);
   if (k > d + 1 || (k == d + 1 && role != 0)) return;
@@ -256,40 +266,62 @@ __global__ __launch_bounds__(BM_SUM_DIMS) void k_glvq_sums(const float *__restri
   const uint32_t *st = starts + static_cast<int64_t>(role) * (n_units + 1);
   const double *wt = k == d + 1 ? f : xi + static_cast<int64_t>(role) * n;
   const uint32_t lo = st[u], hi = st[u + 1];
+  double W = 0.0;
+  if constexpr (RELEVANCE) {
+    if (k < d) {
+      const int64_t row = row_of_unit(*cb, u);
+      const float *tile = reinterpret_cast<const float *>(tile_ptr(*cb, row >> 6, k >> 2, static_cast<int>(row & 63)));
+      W = static_cast<double>(tile[k & 3]);
+    }
+  }
   auto elem = [&](uint32_t s) -> float {
-    if (k >= d) return 1.0f;
-    int64_t r = first + static_cast<int64_t>(s);
-    if (r >= n_rows) { r -= n_rows; if (r >= n_rows) r %= n_rows; }
-    return rows[r * d + k];
+    return k >= d ? 1.0f : rows[run_row(first, s, n_rows) * d + k];
   };
-  double acc = 0.0;
+  double acc = 0.0, rel = 0.0;
+  auto add = [&](double ws, double xd) {
+    const double p = ws * xd;
+    acc += p;
+    if constexpr (RELEVANCE) {
+      const double td = xd - W;
+      const double tt = td * td;
+      const double pr = ws * tt;
+      rel += pr;
+    }
+  };
   if (CONT) {
     if (lo == hi) return;                                     // no sample of this piece for (u, role): the chains stand
     acc = k == d + 1 ? cost[u] : S[(static_cast<int64_t>(role) * n_units + u) * (d + 1) + k];
   }
   uint32_t i = lo;
-  for (; hi - i >= GLVQ_SUM_AHEAD; i += GLVQ_SUM_AHEAD) {
-    float x[GLVQ_SUM_AHEAD];
-    double w[GLVQ_SUM_AHEAD];
+  for (; hi - i >= AHEAD; i += AHEAD) {
+    float x[AHEAD];
+    double w[AHEAD];
 #pragma unroll
-    for (int a = 0; a < GLVQ_SUM_AHEAD; a++) {
+    for (int a = 0; a < AHEAD; a++) {
       const uint32_t s = lst[i + a];
       w[a] = wt[s];
       x[a] = elem(s);
     }
 #pragma unroll
-    for (int a = 0; a < GLVQ_SUM_AHEAD; a++) {
-      const double p = w[a] * static_cast<double>(x[a]);
-      acc += p;
-    }
+    for (int a = 0; a < AHEAD; a++) add(w[a], static_cast<double>(x[a]));
   }
-  for (; i < hi; i++) {
-    const uint32_t s = lst[i];
-    const double p = wt[s] * static_cast<double>(elem(s));
-    acc += p;
+  for (; i < hi; i++) {                                         // (the tail asks for its two loads in the order each kernel
+    const uint32_t s = lst[i];                                  // had them, so both keep their instructions)
+    if constexpr (RELEVANCE) { const double xd = static_cast<double>(elem(s)); add(wt[s], xd); }
+    else add(wt[s], static_cast<double>(elem(s)));
   }
-  if (k == d + 1) cost[u] = acc;
-  else S[(static_cast<int64_t>(role) * n_units + u) * (d + 1) + k] = acc;
+  if (k == d + 1) { cost[u] = acc; return; }
+  S[(static_cast<int64_t>(role) * n_units + u) * (d + 1) + k] = acc;
+  if constexpr (RELEVANCE)
+    if (k < d) R[(static_cast<int64_t>(role) * n_units + u) * d + k] = rel;
+}
+template <bool CONT>
+__global__ __launch_bounds__(BM_SUM_DIMS) void k_glvq_sums(const float *__restrict__ rows, int64_t n_rows, int d, int64_t first,
+                                                           int64_t n, uint32_t n_units, const uint32_t *__restrict__ list,
+                                                           const uint32_t *__restrict__ starts, const double *__restrict__ xi,
+                                                           const double *__restrict__ f, double *__restrict__ S,
+                                                           double *__restrict__ cost) {
+  glvq_sums_chain<CONT, false, GLVQ_SUM_AHEAD>(nullptr, rows, n_rows, d, first, n, n_units, list, starts, xi, f, S, nullptr, cost);
 }
 
 // The integers of the state of an epoch over data in pieces (somhip_glvq_accumulate), behind a piece's k_glvq_sums<true>:
@@ -303,12 +335,22 @@ __global__ __launch_bounds__(GLVQ_THREADS) void k_glvq_counts(const uint32_t *__
   if (i == 0) { tail[0] += n; tail[1] += *correct; }
 }
 
-// Step 5, in place over the storage tiles: thread = (row group, chunk of 4 dims, lane).  With W = (double)w_j[k]:
-// g = (Sp[j][k] - sp[j] * W) - (Sm[j][k] - sm[j] * W), w_j[k] = (float)(W + a * g).  A row no sample chose in either role
-// (hits of both 0) keeps its bits; so does the padding.
-__global__ __launch_bounds__(GLVQ_THREADS) void k_glvq_update(CbView cb, const double *__restrict__ S, const uint32_t *__restrict__ hits,
-                                                              double a) {
-  const int64_t t = static_cast<int64_t>(blockIdx.x) * GLVQ_THREADS + threadIdx.x;
+// The step of a chosen row j at component k, with W = (double)w_j[k]: g = (Sp[j][k] - sp[j] * W) - (Sm[j][k] - sm[j] * W),
+// five roundings in the order written.  K9's, K11's and K12's updates all start from it.
+__device__ __forceinline__ double glvq_step_g(double Spk, double Smk, double sp, double sm, double W) {
+  const double pw = sp * W, mw = sm * W;
+  const double gp = Spk - pw, gm = Smk - mw;
+  return gp - gm;
+}
+
+// Step 5, in place over the storage tiles: thread = (row group, chunk of 4 dims, lane).  With W = (double)w_j[k] and g of
+// glvq_step_g: w_j[k] = (float)(W + a * g), or with RELEVANCE (K11's step 6) (float)(W + (a * (double)lam[k]) * g), lam the
+// float4[d4] tile of the weighted search read as floats.  A row no sample chose in either role (hits of both 0) keeps its
+// bits; so does the padding.  The body of k_glvq_update and of k_grlvq_update (kernels/grlvq.hpp).
+template <int THREADS, bool RELEVANCE>
+__device__ __forceinline__ void glvq_update_tiles(const CbView &cb, const double *__restrict__ S, const uint32_t *__restrict__ hits,
+                                                  const float *__restrict__ lam, double a) {
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * THREADS + threadIdx.x;
   const int lane = static_cast<int>(t & (WAVE - 1));
   const int64_t gq = t >> 6;
   if (gq >= cb.ngroups * cb.d4) return;
@@ -330,13 +372,17 @@ __global__ __launch_bounds__(GLVQ_THREADS) void k_glvq_update(CbView cb, const d
     const int k = q * 4 + j;
     if (k >= cb.d) continue;
     const double W = static_cast<double>(v[j]);
-    const double pw = sp * W, mw = sm * W;
-    const double gp = Sp[k] - pw, gm = Sm[k] - mw;
-    const double gg = gp - gm;
-    const double step = a * gg;
+    const double gg = glvq_step_g(Sp[k], Sm[k], sp, sm, W);
+    double al = a;
+    if constexpr (RELEVANCE) al = a * static_cast<double>(lam[k]);
+    const double step = al * gg;
     v[j] = static_cast<float>(W + step);
   }
   *cp = make_float4(v[0], v[1], v[2], v[3]);
+}
+__global__ __launch_bounds__(GLVQ_THREADS) void k_glvq_update(CbView cb, const double *__restrict__ S, const uint32_t *__restrict__ hits,
+                                                              double a) {
+  glvq_update_tiles<GLVQ_THREADS, false>(cb, S, hits, nullptr, a);
 }
 
 }  // namespace somhip

@@ -16,7 +16,8 @@ namespace somhip {
 //   sums      K9's k_glvq_sums, unchanged, on the original rows.
 //   gradient  k_gmlvq_omega_grad: per block of GMLVQ_BLOCK samples and element (r, k) one chain in data order;
 //             k_gmlvq_omega_reduce: one chain over the blocks per element.
-//   update    k_gmlvq_update: w <- (float)(W + a * (Omega^T (Omega g))[k]), both products ordered chains, in place.
+//   update    k_gmlvq_update: w <- (float)(W + a * (Omega^T (Omega g))[k]), both products ordered chains, in place; g is
+//             K9's glvq_step_g (kernels/glvq.hpp).
 //
 // No floating-point atomics anywhere.
 // =====================================================================================
@@ -234,9 +235,7 @@ __global__ __launch_bounds__(THREADS) void k_gmlvq_update(CbView cb, const doubl
   const int tid = threadIdx.x;
   for (int k = tid; k < dim; k += THREADS) {
     const double W = static_cast<double>(tile[static_cast<int64_t>(k >> 2) * (WAVE * 4) + (k & 3)]);
-    const double pw = sp * W, mw = sm * W;
-    const double gp = Sp[k] - pw, gm = Sm[k] - mw;
-    g[k] = gp - gm;
+    g[k] = glvq_step_g(Sp[k], Sm[k], sp, sm, W);
   }
   __syncthreads();
   for (int r = tid; r < m; r += THREADS) {

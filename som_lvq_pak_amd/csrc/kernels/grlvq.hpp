@@ -14,9 +14,11 @@ namespace somhip {
 //              a chain of four separately rounded fp32 operations per component.  Only this direct route exists: the
 //              pre-filters behind the top-8 lists are unweighted.
 //   terms      K9's k_glvq_terms, K8's k_batchmap_starts and the stable sort, unchanged.
-//   sums       k_grlvq_sums: K9's chain of xi * (double)x[k] and, in the same lane, the chain of xi * ((double)x[k] - (double)w[k])^2.
+//   sums       k_grlvq_sums: K9's chain of xi * (double)x[k] and, in the same lane, the chain of xi * ((double)x[k] - (double)w[k])^2:
+//              K9's body glvq_sums_chain (kernels/glvq.hpp) with its relevance flag.
 //   relevance  k_grlvq_relevance: G[k] = one chain over the rows in unit order of (Rp[j][k] - Rm[j][k]).
-//   update     k_grlvq_update: w <- (float)(W + (a * (double)lambda[k]) * ((Sp - sp W) - (Sm - sm W))), in place.
+//   update     k_grlvq_update: w <- (float)(W + (a * (double)lambda[k]) * ((Sp - sp W) - (Sm - sm W))), in place: K9's body
+//              glvq_update_tiles (kernels/glvq.hpp) with the relevance in the step factor.
 //
 // No floating-point atomics anywhere.
 // =====================================================================================
@@ -131,77 +133,16 @@ __global__ __launch_bounds__(256) void k_scan_class_weighted(CbView cb, const fl
   }
 }
 
-// Step 4 with the relevance chain.  K9's k_glvq_sums -- one wave per (prototype u = blockIdx.x, 64 columns, role =
-// blockIdx.z), lane = column k, AHEAD (GLVQ_SUM_AHEAD) entries requested ahead -- with two accumulators per lane: S[role][u][k] as
-// there (column d the chain over xi, column d + 1 of role + the chain over f into cost[u]), and for k < d
-// R[role][u][k] = the chain of fp64 additions from +0.0 over the same list of  xi * (td * td),  td = (double)x_s[k] -
-// (double)w_u[k]: a subtraction, two multiplications and an addition, each rounded.  w_u[k] is read once from the storage
-// tiles.  S is [2][n_units][d + 1], R is [2][n_units][d].
-// (A template, as the two kernels below: the compiler emits a template where it is first used, behind every kernel the
-// library had, so those keep their places in the code object as well as their code.)
+// Step 4 with the relevance chain: K9's sums body (glvq_sums_chain, kernels/glvq.hpp) with RELEVANCE -- the second
+// accumulator per lane, w_u[k] from the storage tiles, R beside S -- in one call over the data, AHEAD (GLVQ_SUM_AHEAD) entries
+// requested ahead.  S is [2][n_units][d + 1], R is [2][n_units][d].
 template <int AHEAD>
 __global__ __launch_bounds__(BM_SUM_DIMS) void k_grlvq_sums(CbView cb, const float *__restrict__ rows, int64_t n_rows, int64_t first,
                                                             int64_t n, const uint32_t *__restrict__ list,
                                                             const uint32_t *__restrict__ starts, const double *__restrict__ xi,
                                                             const double *__restrict__ f, double *__restrict__ S,
                                                             double *__restrict__ R, double *__restrict__ cost) {
-  const uint32_t u = blockIdx.x, role = blockIdx.z;
-  const uint32_t n_units = static_cast<uint32_t>(cb.n);
-  const int d = cb.d;
-  const int k = static_cast<int>(blockIdx.y) * BM_SUM_DIMS + static_cast<int>(threadIdx.x);
-  if (k > d + 1 || (k == d + 1 && role != 0)) return;
-  const uint32_t *lst = list + static_cast<int64_t>(role) * n;
-  const uint32_t *st = starts + static_cast<int64_t>(role) * (n_units + 1);
-  const double *wt = k == d + 1 ? f : xi + static_cast<int64_t>(role) * n;
-  const uint32_t lo = st[u], hi = st[u + 1];
-  double W = 0.0;
-  if (k < d) {
-    const int64_t row = row_of_unit(cb, u);
-    const float *tile = reinterpret_cast<const float *>(tile_ptr(cb, row >> 6, k >> 2, static_cast<int>(row & 63)));
-    W = static_cast<double>(tile[k & 3]);
-  }
-  auto elem = [&](uint32_t s) -> float {
-    if (k >= d) return 1.0f;
-    int64_t r = first + static_cast<int64_t>(s);
-    if (r >= n_rows) { r -= n_rows; if (r >= n_rows) r %= n_rows; }
-    return rows[r * d + k];
-  };
-  double acc = 0.0, rel = 0.0;
-  uint32_t i = lo;
-  for (; hi - i >= AHEAD; i += AHEAD) {
-    float x[AHEAD];
-    double w[AHEAD];
-#pragma unroll
-    for (int a = 0; a < AHEAD; a++) {
-      const uint32_t s = lst[i + a];
-      w[a] = wt[s];
-      x[a] = elem(s);
-    }
-#pragma unroll
-    for (int a = 0; a < AHEAD; a++) {
-      const double xd = static_cast<double>(x[a]);
-      const double p = w[a] * xd;
-      acc += p;
-      const double td = xd - W;
-      const double tt = td * td;
-      const double pr = w[a] * tt;
-      rel += pr;
-    }
-  }
-  for (; i < hi; i++) {
-    const uint32_t s = lst[i];
-    const double xd = static_cast<double>(elem(s));
-    const double ws = wt[s];
-    const double p = ws * xd;
-    acc += p;
-    const double td = xd - W;
-    const double tt = td * td;
-    const double pr = ws * tt;
-    rel += pr;
-  }
-  if (k == d + 1) { cost[u] = acc; return; }
-  S[(static_cast<int64_t>(role) * n_units + u) * (d + 1) + k] = acc;
-  if (k < d) R[(static_cast<int64_t>(role) * n_units + u) * d + k] = rel;
+  glvq_sums_chain<false, true, AHEAD>(&cb, rows, n_rows, cb.d, first, n, static_cast<uint32_t>(cb.n), list, starts, xi, f, S, R, cost);
 }
 
 // Step 5: lane = component k, G[k] = one chain of fp64 additions from +0.0 over the rows j = 0 .. n_units - 1 in unit order
@@ -234,43 +175,13 @@ __global__ __launch_bounds__(WAVE) void k_grlvq_relevance(const double *__restri
   G[k] = acc;
 }
 
-// Step 6, in place over the storage tiles: K9's k_glvq_update with the component's relevance in the step.  With
-// W = (double)w_j[k]: g = (Sp[j][k] - sp[j] * W) - (Sm[j][k] - sm[j] * W), w_j[k] = (float)(W + (a * (double)lambda[k]) * g).
-// lam is the float4[d4] tile of the search, read as floats.  A row no sample chose in either role keeps its bits; so does
-// the padding.
+// Step 6, in place over the storage tiles: K9's update body (glvq_update_tiles, kernels/glvq.hpp) with the component's
+// relevance in the step: w_j[k] = (float)(W + (a * (double)lambda[k]) * g).  lam is the float4[d4] tile of the search, read as
+// floats.
 template <int THREADS>
 __global__ __launch_bounds__(THREADS) void k_grlvq_update(CbView cb, const double *__restrict__ S, const uint32_t *__restrict__ hits,
                                                                const float *__restrict__ lam, double a) {
-  const int64_t t = static_cast<int64_t>(blockIdx.x) * THREADS + threadIdx.x;
-  const int lane = static_cast<int>(t & (WAVE - 1));
-  const int64_t gq = t >> 6;
-  if (gq >= cb.ngroups * cb.d4) return;
-  const int64_t g = gq / cb.d4;
-  const int q = static_cast<int>(gq % cb.d4);
-  const int64_t row = g * WAVE + lane;
-  if (row >= cb.n) return;
-  const uint32_t u = unit_of_row(cb, row);
-  const uint32_t n_units = static_cast<uint32_t>(cb.n);
-  if (hits[u] == 0 && hits[n_units + u] == 0) return;
-  const int64_t ld = cb.d + 1;
-  const double *Sp = S + static_cast<int64_t>(u) * ld, *Sm = S + (static_cast<int64_t>(n_units) + u) * ld;
-  const double sp = Sp[cb.d], sm = Sm[cb.d];
-  float4 *cp = tile_ptr_w(cb, g, q, lane);
-  const float4 c = *cp;
-  float v[4] = {c.x, c.y, c.z, c.w};
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    const int k = q * 4 + j;
-    if (k >= cb.d) continue;
-    const double W = static_cast<double>(v[j]);
-    const double pw = sp * W, mw = sm * W;
-    const double gp = Sp[k] - pw, gm = Sm[k] - mw;
-    const double gg = gp - gm;
-    const double al = a * static_cast<double>(lam[k]);
-    const double step = al * gg;
-    v[j] = static_cast<float>(W + step);
-  }
-  *cp = make_float4(v[0], v[1], v[2], v[3]);
+  glvq_update_tiles<THREADS, true>(cb, S, hits, lam, a);
 }
 
 }  // namespace somhip

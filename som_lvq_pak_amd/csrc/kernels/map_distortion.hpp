@@ -85,8 +85,8 @@ __global__ __launch_bounds__(DS_THREADS) void k_distortion_qsums(const uint32_t 
 
 // [N | D | A] = H x [S | hits | Q] for the 64 rows of row group blockIdx.x and the columns [blockIdx.y * BM_COLS, + BM_COLS)
 // of a whole map, reduced against the rows' own m_jk.  The tiling, the operand layouts, the staged tile with the next
-// tile's loads in flight, the weights and the bubble group skip are k_batchmap_combine's (batchmap.hpp), which stays as
-// it is; here the fifth tile carries hits in its column 0 and Q in its column 1.  Epilogue, per destination row j (lane:
+// tile's loads in flight and the weights are k_batchmap_combine's (batchmap.hpp) written out again, and the bubble group
+// skip is its rule called (bm_group_skipped); here the fifth tile carries hits in its column 0 and Q in its column 1.  Epilogue, per destination row j (lane:
 // rows (lane >> 4) + 4 reg of the wave's 16, column lane & 15 of each tile): with m = m_jk read from the codebook's tiles
 // (0 past the end), t_k = m * (D_j * m - 2 N_jk) and m * m (exact) are added over the lane's four tiles in order from +0.0,
 // the 16 lanes of a row are folded by the xor butterfly 8, 4, 2, 1, and lane 0 of the row writes
@@ -120,17 +120,7 @@ __global__ __launch_bounds__(256, 3) void k_distortion_evaluate(CbView cb, int y
                                                                                                       // columns 0 and 1 are ever written again
 
   int spx = 0, spy = 0;
-  auto skipped = [&](int64_t s) -> bool {
-    if (GAUSS) return false;
-    int sx0, sx1, sy0, sy1;
-    if (cb.patch_w) { sx0 = spx * 8; sx1 = sx0 + 7; sy0 = spy * 8; sy1 = sy0 + 7; }
-    else bm_group_box(cb, s, sx0, sx1, sy0, sy1);
-    const double gx = static_cast<double>(max(0, max(sx0 - dx1, dx0 - sx1)));
-    const double gy = static_cast<double>(max(0, max(sy0 - dy1, dy0 - sy1)));
-    const double hx = cb.topol == 4 ? gx : fmax(0.0, gx - 0.5);     // a hexagonal row is shifted by half a unit at most
-    const double least = hx * hx + (cb.topol == 4 ? 1.0 : 0.75) * gy * gy;
-    return least > static_cast<double>(thresh) * 1.000001;
-  };
+  auto skipped = [&](int64_t s) -> bool { return bm_group_skipped<GAUSS>(cb, s, spx, spy, dx0, dx1, dy0, dy1, thresh); };
   auto after = [&](int64_t s) -> int64_t {                            // the first group behind s that is not skipped
     do {
       s++;
