@@ -27,10 +27,7 @@ int main(int argc, char **argv)
   int error = 1;
 
   memset(&params, 0, sizeof params);
-  int lines = extract_parameter(argc, argv, "-v", OPTION2) != NULL;
-  global_options(argc, argv);
-  char *level = extract_parameter(argc, argv, "-v", OPTION);
-  if (lines && (!level || level[0] == '-')) verbose_level = 1;   /* a bare -v: the next argument is no level */
+  int lines = pak_batch_verbose(argc, argv);
   if (extract_parameter(argc, argv, "-help", OPTION2)) { fputs(usage, stdout); exit(0); }
   char *din = extract_parameter(argc, argv, "-din", ALWAYS), *cin = extract_parameter(argc, argv, "-cin", ALWAYS);
   char *cout = extract_parameter(argc, argv, "-cout", ALWAYS);
@@ -50,8 +47,7 @@ int main(int argc, char **argv)
 
   pak_gen_virtual_ok = 1;                                /* a gen: source is generated in HBM, never on the host */
   if (pak_open_inputs(din, 0, "cant open data file '%s'\n", cin, 0, "Can't open code file '%s'\n", 0, &io)) goto end;
-  if (io.codes->masks) { fprintf(stderr, "bng: codebook %s has masked components (x): not supported\n", cin); goto end; }
-  if (io.data->masks) { fprintf(stderr, "bng: data %s has masked components (x): not supported\n", din); goto end; }
+  if (pak_masked_inputs("bng", &io, cin, din, "")) goto end;
   if (dense && io.codes->num_entries > SOMHIP_NG_DENSE_MAX) {
     fprintf(stderr, "bng: codebook %s has %ld rows, -dense takes at most %d\n", cin, (long)io.codes->num_entries, SOMHIP_NG_DENSE_MAX);
     goto end;
@@ -65,8 +61,7 @@ int main(int argc, char **argv)
       for (long t = 0; lines && t < epochs; t++)         /* the figure as the qerror tool prints it */
         fprintf(stdout, "epoch %ld lambda %.17g ranks %d qerror %f\n", t, line[t].lambda, line[t].ranks,
                 line[t].qerror / (float)io.data->num_entries);
-      ifverbose(2) fprintf(stderr, "Codebook entries are saved to file %s\n", cout);
-      error = save_entries(io.codes, cout) ? 1 : 0;
+      error = pak_save_codes(io.codes, cout);
     }
     free(line);
   }

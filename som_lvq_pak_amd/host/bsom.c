@@ -30,12 +30,9 @@ struct bsom_out { const char *cout; long epochs; float radius; float *qerror; };
 static int save_codes(struct teach_params *teach, void *arg)
 {
   struct bsom_out *o = arg;
-  for (long t = 0; o->qerror && t < o->epochs; t++) {
-    const float r = 1.0f + (o->radius - 1.0f) * (float)(o->epochs - t) / (float)o->epochs;   /* the engine's r_t */
-    fprintf(stdout, "epoch %ld radius %.9g qerror %.9g\n", t, (double)r, (double)o->qerror[t]);
-  }
-  ifverbose(2) fprintf(stderr, "Codebook entries are saved to file %s\n", o->cout);
-  return save_entries(teach->codes, (char *)o->cout) ? 1 : 0;
+  for (long t = 0; o->qerror && t < o->epochs; t++)
+    fprintf(stdout, "epoch %ld radius %.9g qerror %.9g\n", t, (double)pak_linear_radius(o->radius, o->epochs, t), (double)o->qerror[t]);
+  return pak_save_codes(teach->codes, o->cout);
 }
 
 int main(int argc, char **argv)
@@ -45,10 +42,7 @@ int main(int argc, char **argv)
   int error = 1;
 
   memset(&params, 0, sizeof params);
-  int lines = extract_parameter(argc, argv, "-v", OPTION2) != NULL;
-  global_options(argc, argv);
-  char *level = extract_parameter(argc, argv, "-v", OPTION);
-  if (lines && (!level || level[0] == '-')) verbose_level = 1;   /* a bare -v: the next argument is no level */
+  int lines = pak_batch_verbose(argc, argv);
   if (extract_parameter(argc, argv, "-help", OPTION2)) { fputs(usage, stdout); exit(0); }
   char *din = extract_parameter(argc, argv, "-din", ALWAYS), *cin = extract_parameter(argc, argv, "-cin", ALWAYS);
   char *cout = extract_parameter(argc, argv, "-cout", ALWAYS);
@@ -56,31 +50,24 @@ int main(int argc, char **argv)
   float radius = (float)atof(extract_parameter(argc, argv, "-radius", ALWAYS));
   if (epochs < 1) { fprintf(stderr, "bsom: -epochs %ld < 1\n", epochs); exit(1); }
   if (!(radius >= 1.0f)) { fprintf(stderr, "bsom: -radius %g < 1\n", (double)radius); exit(1); }
-  char *buffer_s = extract_parameter(argc, argv, "-buffer", OPTION), *gpus_s = extract_parameter(argc, argv, "-gpus", OPTION);
-  long buffer = oatoi(buffer_s, 0);
-  int gpus = (int)oatoi(gpus_s, 1);
-  if (buffer < 0) { fprintf(stderr, "bsom: -buffer %ld < 0\n", buffer); exit(1); }
-  if (gpus < 1 || gpus > 64) { fprintf(stderr, "bsom: -gpus %d outside 1 .. 64\n", gpus); exit(1); }
+  struct pak_pieces_cli pc;
+  pak_pieces_cli(argc, argv, "bsom", 0, &pc);
   int missing = extract_parameter(argc, argv, "-missing", OPTION2) != NULL;
-  if (missing && gpus_s) { fprintf(stderr, "bsom: -missing together with -gpus is not available (the ranks train without masks)\n"); exit(1); }
-  if (gpus_s && buffer_s) { fprintf(stderr, "bsom: -gpus together with -buffer is not available (give one of the two)\n"); exit(1); }
+  if (missing && pc.gpus_s) { fprintf(stderr, "bsom: -missing together with -gpus is not available (the ranks train without masks)\n"); exit(1); }
+  if (pc.gpus_s && pc.buffer_s) { fprintf(stderr, "bsom: -gpus together with -buffer is not available (give one of the two)\n"); exit(1); }
 
   pak_gen_virtual_ok = 1;                                /* a gen: source is generated in HBM, never on the host */
   if (pak_open_inputs(din, 0, "cant open data file '%s'\n", cin, 0, "Can't open code file '%s'\n", 1, &io)) goto end;
-  if (io.codes->masks) { fprintf(stderr, "bsom: codebook %s has masked components (x): not supported\n", cin); goto end; }
-  if (io.data->masks && !missing) {
-    fprintf(stderr, "bsom: data %s has masked components (x): not supported without -missing\n", din);
-    goto end;
-  }
+  if (pak_masked_inputs("bsom", &io, cin, din, missing ? NULL : " without -missing")) goto end;
   set_teach_params(&params, io.codes, io.data, NULL);
   params.radius = radius;
   float *qerror = lines ? calloc((size_t)epochs, sizeof *qerror) : NULL;
   struct bsom_out out = {cout, epochs, radius, qerror};
   if (missing) {
-    if (!som_batchmap_missing_training(&params, epochs, buffer, qerror)) error = save_codes(&params, &out);
-  } else if (!buffer_s && (gpus > 1 || getenv("SOMHIP_COMM")))  /* the ranks train, as in vsom; rank 0 prints and saves */
-    error = som_batchmap_training_multi(&params, epochs, qerror, gpus, save_codes, &out);
-  else if (!som_batchmap_training(&params, epochs, buffer, qerror))
+    if (!som_batchmap_missing_training(&params, epochs, pc.buffer, qerror)) error = save_codes(&params, &out);
+  } else if (!pc.buffer_s && (pc.gpus > 1 || getenv("SOMHIP_COMM")))  /* the ranks train, as in vsom; rank 0 prints and saves */
+    error = som_batchmap_training_multi(&params, epochs, qerror, pc.gpus, save_codes, &out);
+  else if (!som_batchmap_training(&params, epochs, pc.buffer, qerror))
     error = save_codes(&params, &out);
   free(qerror);
 end:

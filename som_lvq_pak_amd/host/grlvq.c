@@ -20,17 +20,6 @@ static const char *usage =
     "-alpha has the unit of a squared distance: about the squared distance between neighbouring classes.\n"
     "Files:     text (.dat/.cod) or raw fp32 (a name ending in .f32; see datconv); every row carries a label\n";
 
-/* 1 after a message when a row of e has no label */
-static int unlabelled(struct entries *e, const char *what, const char *name)
-{
-  for (long r = 0; r < e->num_entries; r++)
-    if (get_entry_label(&e->rows[r]) == LABEL_EMPTY) {
-      fprintf(stderr, "grlvq: %s %s has no labels on row %ld\n", what, name, r);
-      return 1;
-    }
-  return 0;
-}
-
 /* the relevances of file `name` into lambda[dim]; 1 after a message */
 static int read_relevances(const char *name, int dim, float *lambda)
 {
@@ -77,10 +66,7 @@ int main(int argc, char **argv)
   int error = 1;
 
   memset(&params, 0, sizeof params);
-  int lines = extract_parameter(argc, argv, "-v", OPTION2) != NULL;
-  global_options(argc, argv);
-  char *level = extract_parameter(argc, argv, "-v", OPTION);
-  if (lines && (!level || level[0] == '-')) verbose_level = 1;   /* a bare -v: the next argument is no level */
+  int lines = pak_batch_verbose(argc, argv);
   if (extract_parameter(argc, argv, "-help", OPTION2)) { fputs(usage, stdout); exit(0); }
   char *din = extract_parameter(argc, argv, "-din", ALWAYS), *cin = extract_parameter(argc, argv, "-cin", ALWAYS);
   char *rin = extract_parameter(argc, argv, "-rin", OPTION), *rout = extract_parameter(argc, argv, "-rout", OPTION);
@@ -91,26 +77,13 @@ int main(int argc, char **argv)
   float beta = oatof(extract_parameter(argc, argv, "-sigmoid", OPTION), 0.0f);
   if (epochs < 0) { fprintf(stderr, "grlvq: -epochs %ld < 0\n", epochs); exit(1); }
   if (epochs == 0 && !rin) { fprintf(stderr, "grlvq: -epochs 0 evaluates a trained model and needs its relevances (-rin)\n"); exit(1); }
-  if (!(alpha >= 0.0f)) { fprintf(stderr, "grlvq: -alpha %g is negative or not a number\n", (double)alpha); exit(1); }
-  if (!(eps >= 0.0f)) { fprintf(stderr, "grlvq: -eps %g is negative or not a number\n", (double)eps); exit(1); }
-  if (!(beta >= 0.0f)) { fprintf(stderr, "grlvq: -sigmoid %g is negative or not a number\n", (double)beta); exit(1); }
+  pak_rate_check("grlvq", "-alpha", alpha);
+  pak_rate_check("grlvq", "-eps", eps);
+  pak_rate_check("grlvq", "-sigmoid", beta);
 
   if (pak_open_inputs(din, 0, "cant open data file '%s'\n", cin, 0, "Can't open code file '%s'\n", 0, &io)) goto end;
-  if (io.codes->masks) { fprintf(stderr, "grlvq: codebook %s has masked components (x): not supported\n", cin); goto end; }
-  if (io.data->masks) { fprintf(stderr, "grlvq: data %s has masked components (x): not supported\n", din); goto end; }
-  if (unlabelled(io.codes, "codebook", cin) || unlabelled(io.data, "data", din)) goto end;
-  {                                                      /* the labels of the two files, before an engine is asked for */
-    const long noc = io.codes->num_entries;
-    int one = 1;
-    for (long r = 1; r < noc; r++) one &= get_entry_label(&io.codes->rows[r]) == get_entry_label(&io.codes->rows[0]);
-    if (one) { fprintf(stderr, "grlvq: every row of codebook %s carries one label (no other class to be wrong with)\n", cin); goto end; }
-    for (long s = 0; s < io.data->num_entries; s++) {
-      const int l = get_entry_label(&io.data->rows[s]);
-      long r = 0;
-      while (r < noc && get_entry_label(&io.codes->rows[r]) != l) r++;
-      if (r == noc) { fprintf(stderr, "grlvq: data row %ld carries label %s, which no codebook row carries\n", s, find_conv_to_lab(l)); goto end; }
-    }
-  }
+  if (pak_masked_inputs("grlvq", &io, cin, din, "")) goto end;
+  if (pak_labelled_inputs("grlvq", &io, cin, din)) goto end;
   const int dim = io.codes->dimension;
   lambda = malloc(sizeof *lambda * (size_t)dim);
   if (rin) { if (read_relevances(rin, dim, lambda)) goto end; }
@@ -126,18 +99,9 @@ int main(int argc, char **argv)
     double *cost = lines && epochs ? calloc((size_t)epochs, sizeof *cost) : NULL, final_cost = 0.0;
     int64_t *correct = lines && epochs ? calloc((size_t)epochs, sizeof *correct) : NULL, final_correct = 0;
     if (!grlvq_training(&params, epochs, beta, eps, lambda, cost, correct, &final_cost, &final_correct)) {
-      for (long t = 0; lines && t < epochs; t++) {
-        const float a = alpha * (float)(epochs - t) / (float)epochs;   /* the engine's alpha_t and eps_t */
-        const float e = eps * (float)(epochs - t) / (float)epochs;
-        fprintf(stdout, "epoch %ld alpha %.9g eps %.9g cost %.17g accuracy %.2f %%\n", t, (double)a, (double)e, cost[t],
-                100.0 * (double)correct[t] / (double)io.data->num_entries);
-      }
-      fprintf(stdout, "final cost %.17g accuracy %.2f %%\n", final_cost, 100.0 * (double)final_correct / (double)io.data->num_entries);
-      error = 0;
-      if (epochs > 0) {
-        ifverbose(2) fprintf(stderr, "Codebook entries are saved to file %s\n", cout);
-        error = save_entries(io.codes, cout) ? 1 : 0;
-      }
+      pak_print_epoch_costs(stdout, epochs, alpha, &eps, cost, correct, io.data->num_entries);   /* the engine's alpha_t and eps_t */
+      pak_print_final_cost(stdout, final_cost, final_correct, io.data->num_entries);
+      error = epochs > 0 ? pak_save_codes(io.codes, cout) : 0;
       if (!error && rout) error = write_relevances(rout, dim, lambda);
     }
     free(cost);

@@ -273,6 +273,33 @@ void pak_train_cli(int argc, char **argv, struct pak_train_cli *o);
 /* init_random(-rand) and the data order it asks for: one shuffle of the whole file, or per-buffer
  * reshuffling when -buffer is smaller than the file (datafile.c:237-344) */
 void pak_apply_rand(struct entries *data, const char *rand_s, long buffer);
+/* ---- the batch tools' shared front end (bsom, bng, glvq, grlvq, gmlvq, rslvq; pak_io.c): the options, refusals and
+ * report lines they have in common, each stated once under the tool's name `tool` ---- */
+/* -v as the batch tools read it: 1 when -v is given (per-epoch lines are wanted); global_options sets the level, and a
+ * bare -v, whose next argument is no level, leaves it at 1 */
+int pak_batch_verbose(int argc, char **argv);
+/* exits with "tool: option value is negative or not a number" unless value >= 0 */
+void pak_rate_check(const char *tool, const char *option, float value);
+/* 1 after a message when the codebook, then the data, has masked components; data_tail: what the data's message ends
+ * in after "not supported", or NULL where masked data are taken (bsom -missing) */
+int pak_masked_inputs(const char *tool, const struct pak_inputs *io, const char *cin, const char *din, const char *data_tail);
+/* 1 after a message, in this order, for: a codebook row without a label, a data row without one, a codebook whose rows
+ * carry one label, a data row whose label no codebook row carries */
+int pak_labelled_inputs(const char *tool, const struct pak_inputs *io, const char *cin, const char *din);
+/* -buffer N and -gpus G of bsom and glvq: extracted, then refused with an exit when -buffer is given below
+ * least_buffer or -gpus lies outside 1 .. 64 (what the pair means together is the tool's to say) */
+struct pak_pieces_cli { char *buffer_s, *gpus_s; long buffer; int gpus; };
+void pak_pieces_cli(int argc, char **argv, const char *tool, long least_buffer, struct pak_pieces_cli *o);
+/* the engines' rate of epoch t of `epochs`, from a down to 0, and their radius, from r down to 1: these expressions, in
+ * this association, are what the engines compute */
+float pak_linear_rate(float a, long epochs, long t);
+float pak_linear_radius(float r, long epochs, long t);
+/* the per-epoch lines of the GLVQ family (eps: NULL, or the second rate for its column; nothing where cost is NULL) and
+ * the line of the final figures, over `rows` data rows */
+void pak_print_epoch_costs(FILE *fp, long epochs, float alpha, const float *eps, const double *cost, const int64_t *correct, long rows);
+void pak_print_final_cost(FILE *fp, double cost, int64_t correct, long rows);
+/* says at -v 2 where the codebook goes, and saves it: 0, or 1 */
+int pak_save_codes(struct entries *codes, const char *cout);
 void pak_shutdown(void);
 /* vsom -gpus G: one process per GPU, codebook sharded, RCCL all-reduce of the winner keys (pak_ranks.c).  Must be called
  * before this process has used a GPU; rank 0 runs after(teach, arg) (save the codebook) when training succeeded. */

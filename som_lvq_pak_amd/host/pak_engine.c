@@ -694,45 +694,56 @@ void free_map_quality(struct map_quality *q)
   q->hits = NULL; q->qsum = NULL; q->b1 = q->b2 = NULL; q->pair_count = NULL; q->n_pairs = 0; q->unit_energy = NULL;
 }
 
-/* the rows [first, first + count) of data as a device data set of their own: uploaded, or generated in place */
-somhip_dataset *pak_mirror_data_rows(struct entries *data, long first, long count)
+/* the rows [first, first + count) of data as a device data set of their own, with the rows' first labels or without:
+ * uploaded, or -- a gen: source without labels -- generated in place (labels are host rows', so they materialise it) */
+somhip_dataset *pak_mirror_rows(struct entries *data, long first, long count, int with_labels)
 {
   somhip_engine *en = pak_engine();
   if (!en) return NULL;
+  if (with_labels && pak_materialize(data)) return NULL;
   somhip_dataset *ds = NULL;
   const long dim = data->dimension;
-  int rc = data->is_virtual ? somhip_dataset_generate(en, data->gen_seed, data->gen_k, (int)dim, first, count, NULL, &ds)
-                            : somhip_dataset_create(en, data->points + first * dim, count, (int)dim,
-                                                    data->masks ? (const uint8_t *)data->masks + first * dim : NULL, NULL, NULL, NULL, &ds);
+  if (data->is_virtual) return said(somhip_dataset_generate(en, data->gen_seed, data->gen_k, (int)dim, first, count, NULL, &ds)) ? NULL : ds;
+  int32_t *lab = with_labels ? malloc(sizeof(int32_t) * (count + 1)) : NULL;
+  for (long r = 0; lab && r < count; r++) lab[r] = get_entry_label(&data->rows[first + r]);
+  int rc = somhip_dataset_create(en, data->points + first * dim, count, (int)dim,
+                                 data->masks ? (const uint8_t *)data->masks + first * dim : NULL, lab, NULL, NULL, &ds);
+  free(lab);
   return said(rc) ? NULL : ds;
+}
+
+/* how a batch training over the whole data opens: who's "can't get data", then both mirrors, with labels or without */
+static int batch_open(struct teach_params *teach, const char *who, int with_labels, struct mirrors *m)
+{
+  m->cb = NULL; m->ds = NULL;
+  return pak_check_inputs(teach, who, 0) || mirrors_open(m, teach->codes, with_labels, teach->data, with_labels);
 }
 
 static int batchmap_training(struct teach_params *teach, long epochs, long buffer, float *qerror, int missing)
 {
   if (set_som_params(teach)) { fprintf(stderr, "som_batchmap_training: can't set SOM parameters\n"); return 1; }
-  const long n = teach->data->num_entries;
-  if (n <= 0) { fprintf(stderr, "som_batchmap_training: can't get data\n"); return 1; }
   struct mirrors m = {NULL, NULL};
   int rc;
   if (buffer <= 0) {
-    rc = mirrors_open(&m, teach->codes, 0, teach->data, 0);
+    rc = batch_open(teach, "som_batchmap_training", 0, &m);
     if (!rc) {
-      somhip_batchmap_params p = {epochs, teach->radius, 0, epochs, 0, n};
+      somhip_batchmap_params p = {epochs, teach->radius, 0, epochs, 0, teach->data->num_entries};
       rc = said(missing ? somhip_som_batchmap_missing(m.cb, m.ds, &p, qerror) : somhip_som_batchmap(m.cb, m.ds, &p, qerror)) ||
            said(somhip_codebook_download(m.cb, teach->codes->points));
     }
     mirrors_close(&m);
     return rc;
   }
+  if (pak_check_inputs(teach, "som_batchmap_training", 0)) return 1;
   /* the epoch over pieces: the sums' chains go on from piece to piece, so any cut gives the bits of one call */
-  const long ngroups = (teach->codes->num_entries + 63) / 64;
+  const long n = teach->data->num_entries, ngroups = (teach->codes->num_entries + 63) / 64;
   rc = !(m.cb = pak_mirror_codes(teach->codes, 0));
   for (long t = 0; !rc && t < epochs; t++) {
-    const float r = 1.0f + (teach->radius - 1.0f) * (float)(epochs - t) / (float)epochs;   /* the engine's r_t */
+    const float r = pak_linear_radius(teach->radius, epochs, t);   /* the engine's r_t */
     rc = said(missing ? somhip_batchmap_missing_begin(m.cb) : somhip_batchmap_begin(m.cb));
     for (long first = 0; !rc && first < n; first += buffer) {
       const long c = buffer < n - first ? buffer : n - first;
-      somhip_dataset *piece = pak_mirror_data_rows(teach->data, first, c);
+      somhip_dataset *piece = pak_mirror_rows(teach->data, first, c, 0);
       rc = !piece || said(missing ? somhip_batchmap_missing_accumulate(m.cb, piece, 0, c, qerror != NULL)
                                   : somhip_batchmap_accumulate(m.cb, piece, 0, c, qerror != NULL));
       if (piece) somhip_dataset_destroy(piece);
@@ -755,47 +766,30 @@ int som_batchmap_missing_training(struct teach_params *teach, long epochs, long 
 
 int glvq_training(struct teach_params *teach, long epochs, float sigmoid_beta, double *cost, int64_t *correct)
 {
-  const long n = teach->data->num_entries;
-  if (n <= 0) { fprintf(stderr, "glvq_training: can't get data\n"); return 1; }
-  struct mirrors m = {NULL, NULL};
-  int rc = mirrors_open(&m, teach->codes, 1, teach->data, 1);
+  struct mirrors m;
+  int rc = batch_open(teach, "glvq_training", 1, &m);
   if (!rc) {
-    somhip_glvq_params p = {epochs, 0, epochs, 0, n, teach->alpha, sigmoid_beta};
+    somhip_glvq_params p = {epochs, 0, epochs, 0, teach->data->num_entries, teach->alpha, sigmoid_beta};
     rc = said(somhip_glvq_train(m.cb, m.ds, &p, cost, correct)) || said(somhip_codebook_download(m.cb, teach->codes->points));
   }
   mirrors_close(&m);
   return rc;
 }
 
-somhip_dataset *pak_mirror_labelled_rows(struct entries *data, long first, long count)
-{
-  somhip_engine *en = pak_engine();
-  if (!en) return NULL;
-  if (data->is_virtual && pak_materialize(data)) return NULL;
-  somhip_dataset *ds = NULL;
-  const long dim = data->dimension;
-  int32_t *lab = malloc(sizeof(int32_t) * (count + 1));
-  for (long r = 0; r < count; r++) lab[r] = get_entry_label(&data->rows[first + r]);
-  int rc = somhip_dataset_create(en, data->points + first * dim, count, (int)dim,
-                                 data->masks ? (const uint8_t *)data->masks + first * dim : NULL, lab, NULL, NULL, &ds);
-  free(lab);
-  return said(rc) ? NULL : ds;
-}
-
 int glvq_training_buffered(struct teach_params *teach, long epochs, long buffer, float sigmoid_beta, double *cost, int64_t *correct)
 {
-  const long n = teach->data->num_entries;
-  if (n <= 0) { fprintf(stderr, "glvq_training: can't get data\n"); return 1; }
+  if (pak_check_inputs(teach, "glvq_training", 0)) return 1;
   if (buffer < 1) { fprintf(stderr, "glvq_training: buffer %ld < 1\n", buffer); return 1; }
-  /* the epoch over pieces: the sums' chains go on from piece to piece, so any cut gives the bits of one call */
+  /* the epoch over pieces, as in batchmap_training */
+  const long n = teach->data->num_entries;
   somhip_codebook *cb = pak_mirror_codes(teach->codes, 1);
   int rc = !cb;
   for (long t = 0; !rc && t < epochs; t++) {
-    const float alpha_t = teach->alpha * (float)(epochs - t) / (float)epochs;   /* the engine's alpha_t */
+    const float alpha_t = pak_linear_rate(teach->alpha, epochs, t);   /* the engine's alpha_t */
     rc = said(somhip_glvq_begin(cb));
     for (long first = 0; !rc && first < n; first += buffer) {
       const long c = buffer < n - first ? buffer : n - first;
-      somhip_dataset *piece = pak_mirror_labelled_rows(teach->data, first, c);
+      somhip_dataset *piece = pak_mirror_rows(teach->data, first, c, 1);
       rc = !piece || said(somhip_glvq_accumulate(cb, piece, 0, c, sigmoid_beta));
       if (piece) somhip_dataset_destroy(piece);
     }
@@ -810,9 +804,8 @@ int rslvq_training(struct teach_params *teach, long epochs, float sigma2, double
                    int64_t *final_correct, double *pown)
 {
   const long n = teach->data->num_entries;
-  if (n <= 0) { fprintf(stderr, "rslvq_training: can't get data\n"); return 1; }
-  struct mirrors m = {NULL, NULL};
-  int rc = mirrors_open(&m, teach->codes, 1, teach->data, 1);
+  struct mirrors m;
+  int rc = batch_open(teach, "rslvq_training", 1, &m);
   if (!rc && epochs > 0) {
     somhip_rslvq_params p = {epochs, 0, epochs, 0, n, teach->alpha, sigma2};
     rc = said(somhip_rslvq_train(m.cb, m.ds, &p, cost, correct)) || said(somhip_codebook_download(m.cb, teach->codes->points));
@@ -822,31 +815,37 @@ int rslvq_training(struct teach_params *teach, long epochs, float sigma2, double
   return rc;
 }
 
+/* The state a GRLVQ or GMLVQ run ends with, from one more search's d+ / i+ (d, i) and d- / i- (d + n, i + n) over the n
+ * rows, the terms in double here: the cost and the count of correctly classified rows */
+static void final_figures(const float *d, const int32_t *i, long n, float sigmoid_beta, double *final_cost, int64_t *final_correct)
+{
+  double chain = 0.0;
+  int64_t right = 0;
+  for (long s = 0; s < n; s++) {
+    const double dp = (double)d[s], dm = (double)d[n + s], D = dp + dm;
+    const double mu = D == 0.0 ? 0.0 : (dp - dm) / D;
+    chain += sigmoid_beta != 0.0f ? 1.0 / (1.0 + exp(-(double)sigmoid_beta * mu)) : mu;
+    right += d[s] < d[n + s] || (d[s] == d[n + s] && i[s] < i[n + s]);
+  }
+  *final_cost = chain / (double)n;
+  *final_correct = right;
+}
+
 int grlvq_training(struct teach_params *teach, long epochs, float sigmoid_beta, float eps, float *lambda, double *cost, int64_t *correct,
                    double *final_cost, int64_t *final_correct)
 {
   const long n = teach->data->num_entries;
-  if (n <= 0) { fprintf(stderr, "grlvq_training: can't get data\n"); return 1; }
-  struct mirrors m = {NULL, NULL};
-  int rc = mirrors_open(&m, teach->codes, 1, teach->data, 1);
+  struct mirrors m;
+  int rc = batch_open(teach, "grlvq_training", 1, &m);
   if (!rc && epochs > 0) {
     somhip_grlvq_params p = {epochs, 0, epochs, 0, n, teach->alpha, sigmoid_beta, eps};
     rc = said(somhip_grlvq_train(m.cb, m.ds, &p, lambda, cost, correct)) || said(somhip_codebook_download(m.cb, teach->codes->points));
   }
-  if (!rc) {                                               /* the state it ends with: one more search, the terms in double here */
+  if (!rc) {
     float *d = malloc(sizeof(float) * 2 * (size_t)n);
     int32_t *i = malloc(sizeof(int32_t) * 2 * (size_t)n);
     rc = said(somhip_grlvq_search(m.cb, m.ds, 0, n, lambda, d, i, d + n, i + n));
-    double chain = 0.0;
-    int64_t right = 0;
-    for (long s = 0; !rc && s < n; s++) {
-      const double dp = (double)d[s], dm = (double)d[n + s], D = dp + dm;
-      const double mu = D == 0.0 ? 0.0 : (dp - dm) / D;
-      chain += sigmoid_beta != 0.0f ? 1.0 / (1.0 + exp(-(double)sigmoid_beta * mu)) : mu;
-      right += d[s] < d[n + s] || (d[s] == d[n + s] && i[s] < i[n + s]);
-    }
-    *final_cost = chain / (double)n;
-    *final_correct = right;
+    if (!rc) final_figures(d, i, n, sigmoid_beta, final_cost, final_correct);
     free(d);
     free(i);
   }
@@ -858,27 +857,17 @@ int gmlvq_training(struct teach_params *teach, long epochs, float sigmoid_beta, 
                    int64_t *correct, double *final_cost, int64_t *final_correct, float *projected)
 {
   const long n = teach->data->num_entries;
-  if (n <= 0) { fprintf(stderr, "gmlvq_training: can't get data\n"); return 1; }
-  struct mirrors m = {NULL, NULL};
-  int rc = mirrors_open(&m, teach->codes, 1, teach->data, 1);
+  struct mirrors m;
+  int rc = batch_open(teach, "gmlvq_training", 1, &m);
   if (!rc && epochs > 0) {
     somhip_gmlvq_params p = {epochs, 0, epochs, 0, n, teach->alpha, sigmoid_beta, eps, rank};
     rc = said(somhip_gmlvq_train(m.cb, m.ds, &p, omega, cost, correct)) || said(somhip_codebook_download(m.cb, teach->codes->points));
   }
-  if (!rc) {                                               /* the state it ends with: one more search, the terms in double here */
+  if (!rc) {
     float *d = malloc(sizeof(float) * 2 * (size_t)n);
     int32_t *i = malloc(sizeof(int32_t) * 2 * (size_t)n);
     rc = said(somhip_gmlvq_search(m.cb, m.ds, 0, n, omega, rank, d, i, d + n, i + n));
-    double chain = 0.0;
-    int64_t right = 0;
-    for (long s = 0; !rc && s < n; s++) {
-      const double dp = (double)d[s], dm = (double)d[n + s], D = dp + dm;
-      const double mu = D == 0.0 ? 0.0 : (dp - dm) / D;
-      chain += sigmoid_beta != 0.0f ? 1.0 / (1.0 + exp(-(double)sigmoid_beta * mu)) : mu;
-      right += d[s] < d[n + s] || (d[s] == d[n + s] && i[s] < i[n + s]);
-    }
-    *final_cost = chain / (double)n;
-    *final_correct = right;
+    if (!rc) final_figures(d, i, n, sigmoid_beta, final_cost, final_correct);
     free(d);
     free(i);
   }
@@ -889,12 +878,10 @@ int gmlvq_training(struct teach_params *teach, long epochs, float sigmoid_beta, 
 
 int ng_training(struct teach_params *teach, long epochs, double lambda0, double lambda_end, long ranks, struct ng_line *line)
 {
-  const long n = teach->data->num_entries;
-  if (n <= 0) { fprintf(stderr, "ng_training: can't get data\n"); return 1; }
-  somhip_ng_params p = {epochs, lambda0, lambda_end, ranks, 0, epochs, 0, n};
+  somhip_ng_params p = {epochs, lambda0, lambda_end, ranks, 0, epochs, 0, teach->data->num_entries};
+  struct mirrors m;
+  int rc = batch_open(teach, "ng_training", 0, &m);
   float *qerror = line ? calloc((size_t)epochs, sizeof *qerror) : NULL;
-  struct mirrors m = {NULL, NULL};
-  int rc = mirrors_open(&m, teach->codes, 0, teach->data, 0);
   if (!rc) rc = said(somhip_ng_train(m.cb, m.ds, &p, qerror)) || said(somhip_codebook_download(m.cb, teach->codes->points));
   for (long t = 0; !rc && line && t < epochs; t++) {
     double w[256];
@@ -910,13 +897,12 @@ int ng_training(struct teach_params *teach, long epochs, double lambda0, double 
 
 int ng_training_dense(struct teach_params *teach, long epochs, double lambda0, double lambda_end, struct ng_line *line)
 {
-  const long n = teach->data->num_entries, units = teach->codes->num_entries;
-  if (n <= 0) { fprintf(stderr, "ng_training_dense: can't get data\n"); return 1; }
-  somhip_ng_params p = {epochs, lambda0, lambda_end, 0, 0, epochs, 0, n};
+  const long units = teach->codes->num_entries;
+  somhip_ng_params p = {epochs, lambda0, lambda_end, 0, 0, epochs, 0, teach->data->num_entries};
+  struct mirrors m;
+  int rc = batch_open(teach, "ng_training_dense", 0, &m);
   float *qerror = line ? calloc((size_t)epochs, sizeof *qerror) : NULL;
   double *w = line ? malloc(sizeof *w * (size_t)(units > 0 ? units : 1)) : NULL;
-  struct mirrors m = {NULL, NULL};
-  int rc = mirrors_open(&m, teach->codes, 0, teach->data, 0);
   if (!rc) rc = said(somhip_ng_train_dense(m.cb, m.ds, &p, qerror)) || said(somhip_codebook_download(m.cb, teach->codes->points));
   for (long t = 0; !rc && line && t < epochs; t++) {
     rc = said(somhip_debug_ng_dense_schedule(&p, units, t, &line[t].lambda, w));

@@ -15,11 +15,10 @@ extern int pak_device;                  /* a rank of a multi-GPU run sets this b
 int32_t *pak_first_labels(struct entries *e);      /* [num_entries], malloc'd */
 somhip_codebook *pak_mirror_codes(struct entries *codes, int with_labels);
 somhip_dataset *pak_mirror_data(struct entries *data, int with_labels);
-/* rows [first, first + count) alone, without labels: uploaded, or -- a gen: source -- generated in place from `first` */
-somhip_dataset *pak_mirror_data_rows(struct entries *data, long first, long count);
-/* ... and with the rows' first labels, of host rows (a labelled gen: source has them: pak_io.c makes its rows and labels
- * on the host when it is opened) */
-somhip_dataset *pak_mirror_labelled_rows(struct entries *data, long first, long count);
+/* rows [first, first + count) alone: uploaded, or -- a gen: source -- generated in place from `first`; with_labels: with
+ * the first labels of the host rows (a labelled gen: source has them: pak_io.c makes its rows and labels on the host
+ * when it is opened) */
+somhip_dataset *pak_mirror_rows(struct entries *data, long first, long count, int with_labels);
 
 /* What every training entry point refuses before it touches a GPU, with the messages under the caller's prefix
  * `who`: no data, always; PAK_CHECK_SOM: a lattice set_som_params refuses, code dimension != data dimension;

@@ -1,8 +1,8 @@
 /* pak_io.c -- the part of the tools' host library that needs no GPU: arguments, labels, hit lists, the .dat/.cod
  * text files with the "#!somf32" side format and the gen: generator, the .lra rate files, the reference's LCG and
- * -rand shuffle, the alpha schedules and the tools' shared front end.  Links with -lm alone (pak_engine.c and
- * pak_ranks.c hand the hot path to libsomhip.so).  Written from scratch over dense storage; file formats, flag
- * names, messages and numerics follow SOM_PAK/LVQ_PAK 3.2 (citations: file:line in hynde/som_lvq_pak). */
+ * -rand shuffle, the alpha schedules, the tools' shared front end and the batch tools' own.  Links with -lm alone
+ * (pak_engine.c and pak_ranks.c hand the hot path to libsomhip.so).  Written from scratch over dense storage; file
+ * formats, flag names, messages and numerics follow SOM_PAK/LVQ_PAK 3.2 (citations: file:line in hynde/som_lvq_pak). */
 #define _GNU_SOURCE
 #include "pak_int.h"
 
@@ -768,4 +768,85 @@ void pak_apply_rand(struct entries *data, const char *rand_s, long buffer)
   if (pak_materialize(data)) exit(1);                  /* a shuffle needs the rows on the host */
   if (buffer > 0 && buffer < data->num_entries) { data->buffer = buffer; data->random_order = 1; }   /* reshuffled per buffer */
   else randomize_entry_order(data);                                                               /* once, at load */
+}
+
+/* ------------------------------------------------------------------ the batch tools' shared front end */
+int pak_batch_verbose(int argc, char **argv)
+{
+  int lines = extract_parameter(argc, argv, "-v", OPTION2) != NULL;
+  global_options(argc, argv);
+  char *level = extract_parameter(argc, argv, "-v", OPTION);
+  if (lines && (!level || level[0] == '-')) verbose_level = 1;   /* a bare -v: the next argument is no level */
+  return lines;
+}
+
+void pak_rate_check(const char *tool, const char *option, float value)
+{
+  if (!(value >= 0.0f)) { fprintf(stderr, "%s: %s %g is negative or not a number\n", tool, option, (double)value); exit(1); }
+}
+
+int pak_masked_inputs(const char *tool, const struct pak_inputs *io, const char *cin, const char *din, const char *data_tail)
+{
+  if (io->codes->masks) { fprintf(stderr, "%s: codebook %s has masked components (x): not supported\n", tool, cin); return 1; }
+  if (io->data->masks && data_tail) { fprintf(stderr, "%s: data %s has masked components (x): not supported%s\n", tool, din, data_tail); return 1; }
+  return 0;
+}
+
+/* 1 after a message when a row of e has no label */
+static int unlabelled(const char *tool, const struct entries *e, const char *what, const char *name)
+{
+  for (long r = 0; r < e->num_entries; r++)
+    if (get_entry_label(&e->rows[r]) == LABEL_EMPTY) {
+      fprintf(stderr, "%s: %s %s has no labels on row %ld\n", tool, what, name, r);
+      return 1;
+    }
+  return 0;
+}
+
+int pak_labelled_inputs(const char *tool, const struct pak_inputs *io, const char *cin, const char *din)
+{
+  if (unlabelled(tool, io->codes, "codebook", cin) || unlabelled(tool, io->data, "data", din)) return 1;
+  const long noc = io->codes->num_entries;                 /* the labels of the two files, before an engine is asked for */
+  int one = 1;
+  for (long r = 1; r < noc; r++) one &= get_entry_label(&io->codes->rows[r]) == get_entry_label(&io->codes->rows[0]);
+  if (one) { fprintf(stderr, "%s: every row of codebook %s carries one label (no other class to be wrong with)\n", tool, cin); return 1; }
+  for (long s = 0; s < io->data->num_entries; s++) {
+    const int l = get_entry_label(&io->data->rows[s]);
+    long r = 0;
+    while (r < noc && get_entry_label(&io->codes->rows[r]) != l) r++;
+    if (r == noc) { fprintf(stderr, "%s: data row %ld carries label %s, which no codebook row carries\n", tool, s, find_conv_to_lab(l)); return 1; }
+  }
+  return 0;
+}
+
+void pak_pieces_cli(int argc, char **argv, const char *tool, long least_buffer, struct pak_pieces_cli *o)
+{
+  o->buffer_s = extract_parameter(argc, argv, "-buffer", OPTION);
+  o->gpus_s = extract_parameter(argc, argv, "-gpus", OPTION);
+  o->buffer = oatoi(o->buffer_s, 0);
+  o->gpus = (int)oatoi(o->gpus_s, 1);
+  if (o->buffer_s && o->buffer < least_buffer) { fprintf(stderr, "%s: -buffer %ld < %ld\n", tool, o->buffer, least_buffer); exit(1); }
+  if (o->gpus < 1 || o->gpus > 64) { fprintf(stderr, "%s: -gpus %d outside 1 .. 64\n", tool, o->gpus); exit(1); }
+}
+
+float pak_linear_rate(float a, long epochs, long t) { return a * (float)(epochs - t) / (float)epochs; }
+float pak_linear_radius(float r, long epochs, long t) { return 1.0f + pak_linear_rate(r - 1.0f, epochs, t); }   /* the same tree */
+
+void pak_print_epoch_costs(FILE *fp, long epochs, float alpha, const float *eps, const double *cost, const int64_t *correct, long rows)
+{
+  for (long t = 0; cost && t < epochs; t++) {
+    fprintf(fp, "epoch %ld alpha %.9g ", t, (double)pak_linear_rate(alpha, epochs, t));
+    if (eps) fprintf(fp, "eps %.9g ", (double)pak_linear_rate(*eps, epochs, t));
+    fprintf(fp, "cost %.17g accuracy %.2f %%\n", cost[t], 100.0 * (double)correct[t] / (double)rows);
+  }
+}
+void pak_print_final_cost(FILE *fp, double cost, int64_t correct, long rows)
+{
+  fprintf(fp, "final cost %.17g accuracy %.2f %%\n", cost, 100.0 * (double)correct / (double)rows);
+}
+
+int pak_save_codes(struct entries *codes, const char *cout)
+{
+  ifverbose(2) fprintf(stderr, "Codebook entries are saved to file %s\n", cout);
+  return save_entries(codes, cout) ? 1 : 0;
 }

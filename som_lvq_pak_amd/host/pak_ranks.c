@@ -389,116 +389,84 @@ int lvq_training_multi(struct teach_params *teach, int kind, float winlen, float
   return pak_run_ranks(gpus, lvq_training_rank, &m);
 }
 
-/* ------------------------------------------------------------------ the batch map on G GPUs (bsom -gpus G)
- * The DATA is cut into contiguous row blocks, one per rank; every rank holds the whole map.  somhip_som_batchmap_ranks
- * runs the epochs: the winner search of every block at the same time, the ordered sums rank after rank with the state
- * broadcast in between, the combine divided by row groups.  Every rank ends with the same map; rank 0 returns it. */
-struct bsom_multi { struct teach_params *teach; long epochs; float *qerror; int (*after)(struct teach_params *, void *); void *arg; };
+/* ------------------------------------------------------------------ the data in row blocks on G GPUs (bsom -gpus G, glvq -gpus G)
+ * The DATA is cut into contiguous row blocks, one per rank, with its labels where the trainer reads them; every rank
+ * holds the whole codebook.  The trainer's *_ranks call runs the epochs: the winner search of every block at the same
+ * time, the ordered sums rank after rank with the state broadcast in between, the same update (the batch map: the combine
+ * divided by row groups) on every rank.  Every rank ends with the same codebook and per-epoch figures; rank 0 returns them. */
+struct epoch_figures { float *qerror; double *cost; int64_t *correct; };   /* [epochs] each, or NULL */
+struct block_multi {
+  struct teach_params *teach; long epochs; float beta; const char *who; int with_labels;
+  /* the one call that trains over the ranks, on this rank's block of `rows` rows; f: this rank's own arrays */
+  int (*train)(const struct block_multi *m, somhip_codebook *cb, somhip_dataset *ds, long rows, somhip_comm *comm, struct epoch_figures *f);
+  struct epoch_figures out;              /* the caller's: rank 0 copies into those that are not NULL before after(teach, arg) */
+  int (*after)(struct teach_params *, void *); void *arg;
+};
 
-static int batchmap_training_rank(int rank, int world, int *fds, void *pp)
+static int block_training_rank(int rank, int world, int *fds, void *pp)
 {
-  struct bsom_multi *m = pp;
+  struct block_multi *m = pp;
   struct entries *codes = m->teach->codes, *data = m->teach->data;
+  const size_t epochs = (size_t)m->epochs;
   long r0, r1;
   rank_block(data->num_entries, world, rank, &r0, &r1);
   int ndev = 0, rc = 1;
   somhip_comm *comm = NULL;
   somhip_codebook *cb = NULL;
   somhip_dataset *ds = NULL;
-  float *q = calloc((size_t)m->epochs + 1, sizeof *q);      /* every rank asks for it: the chain goes through all of them */
-  if (pak_rank_device(rank) < 0 || somhip_device_count(&ndev)) { free(q); return 1; }
-  somhip_engine *en = pak_engine();
-  if (!en) { free(q); return 1; }
+  /* every rank asks for its figures: the chain goes through all of them */
+  struct epoch_figures f = { calloc(epochs + 1, sizeof *f.qerror), calloc(epochs + 1, sizeof *f.cost), calloc(epochs + 1, sizeof *f.correct) };
+  somhip_engine *en = pak_rank_device(rank) < 0 || somhip_device_count(&ndev) ? NULL : pak_engine();
+  if (!en) goto done;
   int use_rccl;
   const int no_comm = rank_comm_open(en, rank, world, ndev, fds, &comm, &use_rccl);
   if (no_comm > 0) goto hip_fail;
   if (no_comm) goto done;
   ifverbose(2) fprintf(stderr, "rank %d/%d on GPU %d, data rows [%ld, %ld), state by %s\n", rank, world, pak_device, r0, r1,
                        use_rccl ? "RCCL" : "host sockets");
-  if (!(cb = pak_mirror_codes(codes, 0))) goto done;
-  if (r1 > r0 && !(ds = pak_mirror_data_rows(data, r0, r1 - r0))) goto done;
-  somhip_batchmap_params p = { m->epochs, m->teach->radius, 0, m->epochs, 0, r1 - r0 };
-  if (somhip_som_batchmap_ranks(cb, ds, &p, comm, q)) goto hip_fail;
+  if (!(cb = pak_mirror_codes(codes, m->with_labels))) goto done;
+  if (r1 > r0 && !(ds = pak_mirror_rows(data, r0, r1 - r0, m->with_labels))) goto done;
+  if (m->train(m, cb, ds, r1 - r0, comm, &f)) goto hip_fail;
   if (rank == 0) {
     if (somhip_codebook_download(cb, codes->points)) goto hip_fail;
-    if (m->qerror) memcpy(m->qerror, q, sizeof *q * (size_t)m->epochs);
+    if (m->out.qerror) memcpy(m->out.qerror, f.qerror, sizeof *f.qerror * epochs);
+    if (m->out.cost) memcpy(m->out.cost, f.cost, sizeof *f.cost * epochs);
+    if (m->out.correct) memcpy(m->out.correct, f.correct, sizeof *f.correct * epochs);
     rc = m->after ? m->after(m->teach, m->arg) : 0;
   } else rc = 0;
   goto done;
 hip_fail:
-  fprintf(stderr, "som_batchmap_training (rank %d): %s\n", rank, somhip_last_error());
+  fprintf(stderr, "%s (rank %d): %s\n", m->who, rank, somhip_last_error());
 done:
   if (ds) somhip_dataset_destroy(ds);
   if (cb) somhip_codebook_destroy(cb);
   if (comm) somhip_comm_destroy(comm);
-  free(q);
+  free(f.qerror); free(f.cost); free(f.correct);
   return rc;
 }
 
+static int batchmap_over_ranks(const struct block_multi *m, somhip_codebook *cb, somhip_dataset *ds, long rows, somhip_comm *comm, struct epoch_figures *f)
+{
+  somhip_batchmap_params p = { m->epochs, m->teach->radius, 0, m->epochs, 0, rows };
+  return somhip_som_batchmap_ranks(cb, ds, &p, comm, f->qerror);
+}
 int som_batchmap_training_multi(struct teach_params *teach, long epochs, float *qerror, int gpus,
                                 int (*after)(struct teach_params *, void *), void *arg)
 {
   if (pak_check_inputs(teach, "som_batchmap_training", PAK_CHECK_SOM | PAK_CHECK_RANKS)) return 1;
-  struct bsom_multi m = { teach, epochs, qerror, after, arg };
-  return pak_run_ranks(gpus, batchmap_training_rank, &m);
+  struct block_multi m = { teach, epochs, 0.0f, "som_batchmap_training", 0, batchmap_over_ranks, { qerror, NULL, NULL }, after, arg };
+  return pak_run_ranks(gpus, block_training_rank, &m);
 }
 
-/* ------------------------------------------------------------------ batch GLVQ on G GPUs (glvq -gpus G)
- * The DATA is cut into contiguous row blocks, one per rank, each with its labels; every rank holds the whole labelled
- * codebook.  somhip_glvq_train_ranks runs the epochs: the class-wise search of every block at the same time, the ordered
- * sums rank after rank with the state broadcast in between, the same update on every rank.  Every rank ends with the
- * same codebook, cost and count; rank 0 returns them. */
-struct glvq_multi {
-  struct teach_params *teach; long epochs; float beta; double *cost; int64_t *correct;
-  int (*after)(struct teach_params *, void *); void *arg;
-};
-
-static int glvq_training_rank(int rank, int world, int *fds, void *pp)
+static int glvq_over_ranks(const struct block_multi *m, somhip_codebook *cb, somhip_dataset *ds, long rows, somhip_comm *comm, struct epoch_figures *f)
 {
-  struct glvq_multi *m = pp;
-  struct entries *codes = m->teach->codes, *data = m->teach->data;
-  long r0, r1;
-  rank_block(data->num_entries, world, rank, &r0, &r1);
-  int ndev = 0, rc = 1;
-  somhip_comm *comm = NULL;
-  somhip_codebook *cb = NULL;
-  somhip_dataset *ds = NULL;
-  double *cost = calloc((size_t)m->epochs + 1, sizeof *cost);
-  int64_t *correct = calloc((size_t)m->epochs + 1, sizeof *correct);
-  if (pak_rank_device(rank) < 0 || somhip_device_count(&ndev)) { free(cost); free(correct); return 1; }
-  somhip_engine *en = pak_engine();
-  if (!en) { free(cost); free(correct); return 1; }
-  int use_rccl;
-  const int no_comm = rank_comm_open(en, rank, world, ndev, fds, &comm, &use_rccl);
-  if (no_comm > 0) goto hip_fail;
-  if (no_comm) goto done;
-  ifverbose(2) fprintf(stderr, "rank %d/%d on GPU %d, data rows [%ld, %ld), state by %s\n", rank, world, pak_device, r0, r1,
-                       use_rccl ? "RCCL" : "host sockets");
-  if (!(cb = pak_mirror_codes(codes, 1))) goto done;
-  if (r1 > r0 && !(ds = pak_mirror_labelled_rows(data, r0, r1 - r0))) goto done;
-  somhip_glvq_params p = { m->epochs, 0, m->epochs, 0, r1 - r0, m->teach->alpha, m->beta };
-  if (somhip_glvq_train_ranks(cb, ds, &p, comm, cost, correct)) goto hip_fail;
-  if (rank == 0) {
-    if (somhip_codebook_download(cb, codes->points)) goto hip_fail;
-    if (m->cost) memcpy(m->cost, cost, sizeof *cost * (size_t)m->epochs);
-    if (m->correct) memcpy(m->correct, correct, sizeof *correct * (size_t)m->epochs);
-    rc = m->after ? m->after(m->teach, m->arg) : 0;
-  } else rc = 0;
-  goto done;
-hip_fail:
-  fprintf(stderr, "glvq_training (rank %d): %s\n", rank, somhip_last_error());
-done:
-  if (ds) somhip_dataset_destroy(ds);
-  if (cb) somhip_codebook_destroy(cb);
-  if (comm) somhip_comm_destroy(comm);
-  free(cost); free(correct);
-  return rc;
+  somhip_glvq_params p = { m->epochs, 0, m->epochs, 0, rows, m->teach->alpha, m->beta };
+  return somhip_glvq_train_ranks(cb, ds, &p, comm, f->cost, f->correct);
 }
-
 int glvq_training_multi(struct teach_params *teach, long epochs, float sigmoid_beta, double *cost, int64_t *correct, int gpus,
                         int (*after)(struct teach_params *, void *), void *arg)
 {
   if (pak_check_inputs(teach, "glvq_training", PAK_CHECK_RANKS)) return 1;
-  struct glvq_multi m = { teach, epochs, sigmoid_beta, cost, correct, after, arg };
-  return pak_run_ranks(gpus, glvq_training_rank, &m);
+  struct block_multi m = { teach, epochs, sigmoid_beta, "glvq_training", 1, glvq_over_ranks, { NULL, cost, correct }, after, arg };
+  return pak_run_ranks(gpus, block_training_rank, &m);
 }

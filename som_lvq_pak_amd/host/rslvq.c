@@ -17,17 +17,6 @@ static const char *usage =
     "-sigma2 is the squared width of the mixture's components; -alpha has the unit of a squared distance.\n"
     "Files:     text (.dat/.cod) or raw fp32 (a name ending in .f32; see datconv); every row carries a label\n";
 
-/* 1 after a message when a row of e has no label */
-static int unlabelled(struct entries *e, const char *what, const char *name)
-{
-  for (long r = 0; r < e->num_entries; r++)
-    if (get_entry_label(&e->rows[r]) == LABEL_EMPTY) {
-      fprintf(stderr, "rslvq: %s %s has no labels on row %ld\n", what, name, r);
-      return 1;
-    }
-  return 0;
-}
-
 /* "%.9g" is glvq's format of a rate; a probability gets the same digits */
 static int write_pown(const char *name, struct entries *data, const double *pown)
 {
@@ -46,10 +35,7 @@ int main(int argc, char **argv)
   int error = 1;
 
   memset(&params, 0, sizeof params);
-  int lines = extract_parameter(argc, argv, "-v", OPTION2) != NULL;
-  global_options(argc, argv);
-  char *level = extract_parameter(argc, argv, "-v", OPTION);
-  if (lines && (!level || level[0] == '-')) verbose_level = 1;   /* a bare -v: the next argument is no level */
+  int lines = pak_batch_verbose(argc, argv);
   if (extract_parameter(argc, argv, "-help", OPTION2)) { fputs(usage, stdout); exit(0); }
   char *din = extract_parameter(argc, argv, "-din", ALWAYS), *cin = extract_parameter(argc, argv, "-cin", ALWAYS);
   char *pout = extract_parameter(argc, argv, "-pout", OPTION);
@@ -58,25 +44,12 @@ int main(int argc, char **argv)
   float alpha = oatof(extract_parameter(argc, argv, "-alpha", epochs > 0 ? ALWAYS : OPTION), 0.0f);
   float sigma2 = (float)atof(extract_parameter(argc, argv, "-sigma2", ALWAYS));
   if (epochs < 0) { fprintf(stderr, "rslvq: -epochs %ld < 0\n", epochs); exit(1); }
-  if (!(alpha >= 0.0f)) { fprintf(stderr, "rslvq: -alpha %g is negative or not a number\n", (double)alpha); exit(1); }
+  pak_rate_check("rslvq", "-alpha", alpha);
   if (!(sigma2 > 0.0f) || isinf(sigma2)) { fprintf(stderr, "rslvq: -sigma2 %g is not a finite number above 0\n", (double)sigma2); exit(1); }
 
   if (pak_open_inputs(din, 0, "cant open data file '%s'\n", cin, 0, "Can't open code file '%s'\n", 0, &io)) goto end;
-  if (io.codes->masks) { fprintf(stderr, "rslvq: codebook %s has masked components (x): not supported\n", cin); goto end; }
-  if (io.data->masks) { fprintf(stderr, "rslvq: data %s has masked components (x): not supported\n", din); goto end; }
-  if (unlabelled(io.codes, "codebook", cin) || unlabelled(io.data, "data", din)) goto end;
-  {                                                      /* the labels of the two files, before an engine is asked for */
-    const long noc = io.codes->num_entries;
-    int one = 1;
-    for (long r = 1; r < noc; r++) one &= get_entry_label(&io.codes->rows[r]) == get_entry_label(&io.codes->rows[0]);
-    if (one) { fprintf(stderr, "rslvq: every row of codebook %s carries one label (no other class to be wrong with)\n", cin); goto end; }
-    for (long s = 0; s < io.data->num_entries; s++) {
-      const int l = get_entry_label(&io.data->rows[s]);
-      long r = 0;
-      while (r < noc && get_entry_label(&io.codes->rows[r]) != l) r++;
-      if (r == noc) { fprintf(stderr, "rslvq: data row %ld carries label %s, which no codebook row carries\n", s, find_conv_to_lab(l)); goto end; }
-    }
-  }
+  if (pak_masked_inputs("rslvq", &io, cin, din, "")) goto end;
+  if (pak_labelled_inputs("rslvq", &io, cin, din)) goto end;
   if (pout) pown = malloc(sizeof *pown * (size_t)io.data->num_entries);
   set_teach_params(&params, io.codes, io.data, NULL);
   params.alpha = alpha;
@@ -84,17 +57,9 @@ int main(int argc, char **argv)
     double *cost = lines && epochs ? calloc((size_t)epochs, sizeof *cost) : NULL, final_cost = 0.0;
     int64_t *correct = lines && epochs ? calloc((size_t)epochs, sizeof *correct) : NULL, final_correct = 0;
     if (!rslvq_training(&params, epochs, sigma2, cost, correct, &final_cost, &final_correct, pown)) {
-      for (long t = 0; lines && t < epochs; t++) {
-        const float a = alpha * (float)(epochs - t) / (float)epochs;   /* the engine's alpha_t */
-        fprintf(stdout, "epoch %ld alpha %.9g cost %.17g accuracy %.2f %%\n", t, (double)a, cost[t],
-                100.0 * (double)correct[t] / (double)io.data->num_entries);
-      }
-      fprintf(stdout, "final cost %.17g accuracy %.2f %%\n", final_cost, 100.0 * (double)final_correct / (double)io.data->num_entries);
-      error = 0;
-      if (epochs > 0) {
-        ifverbose(2) fprintf(stderr, "Codebook entries are saved to file %s\n", cout);
-        error = save_entries(io.codes, cout) ? 1 : 0;
-      }
+      pak_print_epoch_costs(stdout, epochs, alpha, NULL, cost, correct, io.data->num_entries);   /* the engine's alpha_t */
+      pak_print_final_cost(stdout, final_cost, final_correct, io.data->num_entries);
+      error = epochs > 0 ? pak_save_codes(io.codes, cout) : 0;
       if (!error && pout) error = write_pown(pout, io.data, pown);
     }
     free(cost);
